@@ -10,6 +10,11 @@ batch already resident in HBM.  Workload = BASELINE.json configs[2]/[3]:
 GMVAE, D=784, K=10, latent 64, batch 1024 PER GPU (weak scaling: 8 GPUs = the
 B=8192 config), hidden = the reference default 64 (scripts/run_gmvae.py:19).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds everything else: parity against the fp64 oracle, the CPU baseline,
+repeated regions, HIP-event and roofline figures, the data-parallel timeline.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -113,10 +118,17 @@ def parse():
     ap.add_argument("--safe-schedule", action="store_true",
                     help="start on the schedule without waits between the workgroups of a launch (GMVAE_SCHED_SAFE): what a run "
                          "that shares its GPU needs (tests: two ranks on one device)")
-    ap.add_argument("--no-iwae-bound", action="store_true", help="skip the -log p(x) IWAE bound (S = 50) of the parity block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline figure: parity against the fp64 oracle, the CPU baseline, "
+                         "repeated short regions, per-launch HIP events and roofline, the data-parallel timeline, the exact-"
+                         "triples step time and the replicas' checksum")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, <= 64 MB in "
+                         "all); on one GPU the same arguments give the same inputs in every run")
+    ap.add_argument("--no-iwae-bound", action="store_true", help="--full: skip the -log p(x) IWAE bound (S = 50) of the parity block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--levels", action="store_true", help="also print the per-launch table to stderr")
+    ap.add_argument("--levels", action="store_true", help="--full: also print the per-launch table to stderr")
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="a named workload (BASELINE.json configs / SURVEY.md 8(d)); the default line is configs2")
     ap.add_argument("--dp-world1", action="store_true",
@@ -126,6 +138,24 @@ def parse():
         for k, v in CONFIGS[a.config].items():
             setattr(a, k, v)
     return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array, flattened, as out_dir/<name>.npy in float32, DUMP_BYTES in all at most.  The budget is split
+    evenly; an array larger than its share keeps a fixed sample of its elements (np.random.default_rng(0), sorted flat
+    indices): the same from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for k, v in arrays.items()}
+    left = (DUMP_BYTES - 4096) // 4                        # elements (room for the .npy headers)
+    for i, (name, v) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        n = min(v.size, left // (len(arrays) - i))
+        if n < v.size:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, n, replace=False))]
+        left -= n
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
 
 
 def cpu_thread_counts():
@@ -227,21 +257,23 @@ def main_eval(a):
     x_np = (np.random.default_rng(1234).random((B, D)) < 0.87).astype(np.uint8)
     x = torch.from_numpy(x_np).cuda()
     flat0 = eng.params.detach().cpu().numpy()
-    # ---- parity: the bound on a seeded batch of <= 256 rows, HIP forward vs the fp64 oracle on identical (x, eps, u)
-    tiny = float(np.finfo(np.float32).tiny)
-    B_iw = max(8, min(256, B, int(2e7 // (D * S))))
-    rn = np.random.default_rng(4242)
-    eps_iw = rn.standard_normal((B_iw * S, Lz)).astype(np.float32)
-    u_iw = None
-    if a.model == "gmvae":
-        u_iw = np.clip(rn.uniform(tiny, 1.0, (B_iw * S, K)).astype(np.float32), tiny, np.nextafter(np.float32(1), np.float32(0)))
-    fw = eng.forward(x[:B_iw], torch.from_numpy(eps_iw), None if u_iw is None else torch.from_numpy(u_iw), n_samples=S)
-    torch.cuda.synchronize()
-    t_iw = fw["tail"].cpu().numpy().astype(np.float64)
-    iw_hip = float(t_iw[0] / t_iw[4])
-    iw_cpu = -cpu_parity(a.model, dims, flat0, x_np[:B_iw], eps_iw, u_iw)
-    parity = {"neg_log_px_bound_hip": iw_hip, "neg_log_px_bound_cpu_fp64": iw_cpu, "n_samples": S, "rows": B_iw,
-              "rel_err": float(abs(iw_hip - iw_cpu) / abs(iw_cpu))}
+    parity = None
+    if a.full:
+        # ---- parity: the bound on a seeded batch of <= 256 rows, HIP forward vs the fp64 oracle on identical (x, eps, u)
+        tiny = float(np.finfo(np.float32).tiny)
+        B_iw = max(8, min(256, B, int(2e7 // (D * S))))
+        rn = np.random.default_rng(4242)
+        eps_iw = rn.standard_normal((B_iw * S, Lz)).astype(np.float32)
+        u_iw = None
+        if a.model == "gmvae":
+            u_iw = np.clip(rn.uniform(tiny, 1.0, (B_iw * S, K)).astype(np.float32), tiny, np.nextafter(np.float32(1), np.float32(0)))
+        fw = eng.forward(x[:B_iw], torch.from_numpy(eps_iw), None if u_iw is None else torch.from_numpy(u_iw), n_samples=S)
+        torch.cuda.synchronize()
+        t_iw = fw["tail"].cpu().numpy().astype(np.float64)
+        iw_hip = float(t_iw[0] / t_iw[4])
+        iw_cpu = -cpu_parity(a.model, dims, flat0, x_np[:B_iw], eps_iw, u_iw)
+        parity = {"neg_log_px_bound_hip": iw_hip, "neg_log_px_bound_cpu_fp64": iw_cpu, "n_samples": S, "rows": B_iw,
+                  "rel_err": float(abs(iw_hip - iw_cpu) / abs(iw_cpu))}
     # ---- timing: W + K passes of ONE captured forward replayed back to back (HIP events on the launch stream)
     t_pre = time.perf_counter()
     while time.perf_counter() - t_pre < 0.75:                 # (DVFS: the host-side oracle above let the clocks drop)
@@ -252,6 +284,8 @@ def main_eval(a):
     levels, us_total, tail = eng.profile_forward(x, n_samples=S, iters=a.steps)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0                           # (includes the per-launch pass: not the figure of merit)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"loss_terms": tail.cpu().numpy()})     # the last pass's [TAIL] loss sums
     dt_ms = us_total * 1e-3
     value = B * S / (us_total * 1e-6)
     fl_alg = flops_forward(a.model, D, Lz, K, hidden, S, B)
@@ -312,7 +346,7 @@ def main_eval(a):
     except Exception:
         pass
     cpu = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         import oracle as O
         d_o = O.Dims(**dims)
         mid = O.MODEL_NAMES[a.model]
@@ -333,7 +367,7 @@ def main_eval(a):
                       "global_batch": B, "parallelism": "dp1", "hipgraph": True},
            "host_wall_seconds_of_the_profile_call": wall,
            "neg_log_px_bound_of_the_timed_batch": float(tail[0].item() / max(tail[4].item(), 1.0)),
-           "roofline": roof, "cpu_baseline": cpu, "parity": {"iwae_bound": parity}}
+           "roofline": roof, "cpu_baseline": cpu, "parity": {"iwae_bound": parity} if parity else None}
     print(json.dumps(out), flush=True)
 
 
@@ -393,20 +427,21 @@ def main():
     x_np = (np.random.default_rng(1234 + rank).random((B, d.D)) < 0.87).astype(np.uint8)
     x = torch.from_numpy(x_np).cuda()
 
-    # ---- parity in the same run: HIP vs the fp64 CPU restatement on identical (x, eps, u, parameters)
-    rn = np.random.default_rng(42)
-    tiny = float(np.finfo(np.float32).tiny)
-    eps_np = rn.standard_normal((B * d.S, d.L)).astype(np.float32)
-    u_np = np.clip(rn.uniform(tiny, 1.0, (B * d.S, d.K)).astype(np.float32), tiny, np.nextafter(np.float32(1), np.float32(0)))
-    if a.model != "gmvae":
-        u_np = None
-    flat0 = eng.params.detach().cpu().numpy()
-    buf = eng.step(x, torch.from_numpy(eps_np), None if u_np is None else torch.from_numpy(u_np))
-    torch.cuda.synchronize()
-    tail = buf[eng.P:].cpu().numpy().astype(np.float64)
-    elbo_hip = -tail[0] / tail[4]
     parity = {}
-    if rank == 0:
+    if a.full:
+        # ---- parity in the same run: HIP vs the fp64 CPU restatement on identical (x, eps, u, parameters)
+        rn = np.random.default_rng(42)
+        tiny = float(np.finfo(np.float32).tiny)
+        eps_np = rn.standard_normal((B * d.S, d.L)).astype(np.float32)
+        u_np = np.clip(rn.uniform(tiny, 1.0, (B * d.S, d.K)).astype(np.float32), tiny, np.nextafter(np.float32(1), np.float32(0)))
+        if a.model != "gmvae":
+            u_np = None
+        flat0 = eng.params.detach().cpu().numpy()
+        buf = eng.step(x, torch.from_numpy(eps_np), None if u_np is None else torch.from_numpy(u_np))
+        torch.cuda.synchronize()
+        tail = buf[eng.P:].cpu().numpy().astype(np.float64)
+        elbo_hip = -tail[0] / tail[4]
+    if a.full and rank == 0:
         elbo_cpu = cpu_parity(a.model, dims, flat0, x_np, eps_np, u_np)
         parity = {"elbo_hip": elbo_hip, "elbo_cpu_fp64": elbo_cpu, "rel_err": float(abs(elbo_hip - elbo_cpu) / abs(elbo_cpu))}
         if not a.no_iwae_bound:
@@ -533,6 +568,11 @@ def main():
         run_steps(2 * G)
         torch.cuda.synchronize()
     safe_schedule = bool(eng.safe_schedule)
+    if world == 1:
+        # the pre-warm runs for a wall time, not a step count: the W + K steps start again from the state the Engine was
+        # created in (random_seed 0), so that the last step sees the same inputs in every run (--dump-outputs).  (A train graph
+        # builds its weight images from the parameters at the first step of every launch: nothing stale survives this.)
+        eng.init_parameters(0)
     run_steps(a.warmup)
     torch.cuda.synchronize()
     if world > 1:
@@ -549,6 +589,40 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dt = dev_all_reduce(t, dist.ReduceOp.MAX).item()
     final_tail = eng.grads[eng.P:].cpu().numpy().astype(np.float64)
+    if a.dump_outputs and rank == 0:
+        # what a caller of the step receives: the updated parameters and Adam moments, and the last step's [TAIL] loss sums
+        dump_outputs(a.dump_outputs, {"params": eng.params.detach().cpu().numpy(), "adam_m": eng.m.cpu().numpy(),
+                                      "adam_v": eng.v.cpu().numpy(), "loss_terms": final_tail})
+    unit = G if multi_fn is not None else 1
+    value = n_gpus * B * d.S * a.steps / dt
+    from gmvae_amd import _lib as LIB
+    schedule = LIB.step_schedule(eng.dims(B), eng.model)
+    line = {
+        "metric": "ELBO-samples/sec", "value": value, "unit": "samples/sec", "n_gpus": n_gpus, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+        "steps_per_graph_launch": unit, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": PLANES_DTYPE if schedule.endswith("+planes") else "f32", "data": "synthetic",
+        "config": {"workload": f"{a.model} train step (noise+fwd+bwd+allreduce+TF-Adam), D={d.D} K={d.K} "
+                               f"L={d.L} hidden={hidden} S={d.S}, batch {B}/GPU x {n_gpus} GPU "
+                               f"({workload_name(a, n_gpus)})",
+                   "global_batch": B * n_gpus, "parallelism": f"dp{n_gpus}", "hipgraph": use_graph, "input_pipeline_on_device": bool(a.pipeline and world == 1), "safe_schedule": safe_schedule,
+                   "all_reduce": getattr(eng, "dp_mode", None) if use_graph or world == 1 else "torch.distributed (eager)",
+                   "dist_backend": backend if world > 1 else None, "replicas_identical": None},
+        "fallback": bool(fallbacks), "fallback_reasons": fallbacks or None,
+        "final_loss": final_tail[0] / max(final_tail[4], 1.0),
+    }
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        if fallbacks and not a.allow_fallback:
+            # the line above carries the slower path's number, marked; the exit code says it is not the path asked for
+            raise SystemExit(3)
+
+    if not a.full:
+        return finish(line)
     # ---- a short timed region (the driver runs --steps 20: ONE graph launch, 0.8 ms, a single host-clock sample) is
     # repeated: >= 10 more regions of the same K steps, each bracketed like the contract's; median alongside `value`
     region_ms = []
@@ -564,7 +638,6 @@ def main():
         region_ms.sort()
     # ---- the same loop once more with HIP events around every graph launch (median, events on the compute
     # stream).  `value` above stays the whole-region host clock the contract prescribes; this is the per-launch view.
-    unit = G if multi_fn is not None else 1
     launch_fn = multi_fn if multi_fn is not None else step_fn
     n_ev = int(max(8, min(200, a.steps // unit)))
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
@@ -582,7 +655,6 @@ def main():
         cs = eng.params.detach().double().sum().reshape(1)
         lo, hi = dev_all_reduce(cs.clone(), dist.ReduceOp.MIN), dev_all_reduce(cs.clone(), dist.ReduceOp.MAX)
         replicas_identical = bool((lo == hi).item())
-    value = n_gpus * B * d.S * a.steps / dt
     # the data-parallel step's timeline (device wall clock inside the launches on both sides of the RCCL node; COLLECTIVE:
     # every rank replays the same three-step graph 10 times)
     dp_tl = None
@@ -670,8 +742,6 @@ def main():
                 "launches_per_step": len(levels), "sum_launch_usec": sum(dur(l) for l in levels),
                 "levels": [[nm, round(us, 2), round(tl, 2)] for nm, us, _, tl in levels],
                 "levels_columns": ["launch", "usec_in_kernel_span", "usec_timeline_share"]}
-        from gmvae_amd import _lib as LIB
-        schedule = LIB.step_schedule(eng.dims(B), eng.model)
         roof["schedule"] = schedule
         if schedule.endswith("+planes") and dom[0] in ("fwd_dec_bernoulli", "bwd_dec_top"):
             # the launch multiplies fp32 values as piece products on pre-split operands (gemm.hpp plane_rounds2 / plane_rounds3):
@@ -826,31 +896,16 @@ def main():
             finally:
                 del os.environ["GMVAE_PLANES_EXACT"]
                 eng.drop_graphs()
-        out = {
-            "metric": "ELBO-samples/sec", "value": value, "unit": "samples/sec", "n_gpus": n_gpus, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "ms_per_step_median_hip_events": ms_median_events,
+        line["config"]["replicas_identical"] = replicas_identical
+        line.update({
+            "ms_per_step_median_hip_events": ms_median_events,
             "ms_per_step_median_of_repeats": region_ms[len(region_ms) // 2] if region_ms else None,
             "ms_per_step_repeats": [round(v, 5) for v in region_ms] if region_ms else None,
             "ms_per_step_exact_triples": exact_ms,
-            "steps_per_graph_launch": unit, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32" if not (roof or {}).get("schedule", "").endswith("+planes") else PLANES_DTYPE, "data": "synthetic",
-            "config": {"workload": f"{a.model} train step (noise+fwd+bwd+allreduce+TF-Adam), D={d.D} K={d.K} "
-                                   f"L={d.L} hidden={hidden} S={d.S}, batch {B}/GPU x {n_gpus} GPU "
-                                   f"({workload_name(a, n_gpus)})",
-                       "global_batch": B * n_gpus, "parallelism": f"dp{n_gpus}", "hipgraph": use_graph, "input_pipeline_on_device": bool(a.pipeline and world == 1), "safe_schedule": safe_schedule,
-                       "all_reduce": getattr(eng, "dp_mode", None) if use_graph or world == 1 else "torch.distributed (eager)",
-                       "dist_backend": backend if world > 1 else None, "replicas_identical": replicas_identical},
-            "fallback": bool(fallbacks), "fallback_reasons": fallbacks or None,
             "dp_timeline_usec": dp_tl, "allreduce_usec": (dp_tl or {}).get("allreduce_window"), "rccl_nranks": getattr(eng, "rccl_nranks", None) if dp else None,
             "roofline": roof, "cpu_baseline": cpu, "parity": parity,
-            "final_loss": final_tail[0] / max(final_tail[4], 1.0),
-        }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    if fallbacks and not a.allow_fallback:
-        # the line above carries the slower path's number, marked; the exit code says it is not the path asked for
-        raise SystemExit(3)
+        })
+    finish(line)
 
 
 if __name__ == "__main__":

@@ -439,7 +439,7 @@ def test_bench_world2_branch_on_one_gpu_prints_a_marked_line(tmp_path):
             env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
                        GMVAE_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
             procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                                           "--batch", "512", "--safe-schedule", "--no-cpu-baseline", "--no-iwae-bound"] + extra,
+                                           "--batch", "512", "--safe-schedule", "--full", "--no-cpu-baseline", "--no-iwae-bound"] + extra,
                                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
         outs = []
         try:

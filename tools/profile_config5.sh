@@ -7,7 +7,7 @@ O=$R/gpurun_out/prof_r$RN
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 n=config5_shard
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/$n -o $n -- python3 $R/bench.py --config configs4_shard --steps 100 --warmup 10 --no-cpu-baseline > $O/$n.json 2> $O/$n.err || { echo FAILED $n; tail -5 $O/$n.err; exit 1; }
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/$n -o $n -- python3 $R/bench.py --config configs4_shard --steps 100 --warmup 10 --full --no-cpu-baseline > $O/$n.json 2> $O/$n.err || { echo FAILED $n; tail -5 $O/$n.err; exit 1; }
 head -8 $O/$n/${n}_kernel_stats.csv | cut -c1-150
 find $O -name "*kernel_trace.csv" -size +3M -delete; find $O -name "*.db" -delete; find $O -name "*agent_info*" -delete
 cd $R && bash tools/pmc_config5_mfma.sh > /dev/null && bash tools/pmc_config5_traffic.sh > /dev/null
