@@ -86,7 +86,39 @@ struct EvalArgs {
   // the VAE family (evalf_rows_v): the encoder's output layer [64][2 L], [2 L] (applied once per batch row); VAE_GMP: the mixture
   // prior's variables loc [K][L], raw_scale_diag [K][L], mixture_logits [K] (scripts/vae.py:233-244)
   const float *We1, *be1, *loc, *raw_scale, *mixlog;
+  // gmvae_iw_bound (evalf_rows<3>, evalf_rows_v<2 | 3, L>): sample s of this launch is sample iw_s0 + s of iw_n; its noise is Philox row
+  // (row_base + b) * iw_n + iw_s0 + s (row_base = GmvaeDims::row0 here); samples iw_s0 + s >= iw_n are computed, never summed.
+  // iw_state [B][6] fp64 per batch row (max, sum exp(log w - max), sum log w, sum nll, sum kl), written by the first chunk;
+  // iw_final: the last chunk, which finishes the bound into iw_bound / iw_mlw [B] (either may be null) and the tail.
+  double* iw_state;
+  float *iw_bound, *iw_mlw;
+  unsigned long long iw_n, iw_s0;
+  int iw_final;
 };
+
+// Folds one chunk of batch row b (its max, and its sums of exp(log w - max), log w, nll, kl) into the row's fp64 state in a fixed
+// order: the first chunk writes the state, later ones read and rewrite it (plain stores from lane 0: a batch row has ONE owner).
+// On the last chunk the state is not written back: the row's -bound, mean nll and mean kl come back (zeros before it).
+__device__ __forceinline__ void iw_fold(const EvalArgs& a, const long long b, const int lane, double mx, double se, double slw,
+                                        double nl, double kl, float& o_loss, float& o_nl, float& o_kl) {
+  double* const st = a.iw_state + 6 * b;
+  if (a.iw_s0 != 0) {
+    const double m0 = st[0], m = fmax(m0, mx);
+    se = st[1] * exp(m0 - m) + se * exp(mx - m);
+    mx = m; slw = st[2] + slw; nl = st[3] + nl; kl = st[4] + kl;
+  }
+  o_loss = 0.f; o_nl = 0.f; o_kl = 0.f;
+  if (a.iw_final) {
+    const double n = (double)a.iw_n, bound = mx + log(se) - log(n);
+    if (lane == 0) {
+      if (a.iw_bound) a.iw_bound[b] = (float)bound;
+      if (a.iw_mlw) a.iw_mlw[b] = (float)(slw / n);
+    }
+    o_loss = (float)-bound; o_nl = (float)(nl / n); o_kl = (float)(kl / n);
+  } else if (lane == 0) {
+    st[0] = mx; st[1] = se; st[2] = slw; st[3] = nl; st[4] = kl;
+  }
+}
 
 // evalf_prep: the operand images from the parameters (one thread per image element) and the arrival counter.
 struct EvalPrepArgs {
@@ -296,9 +328,12 @@ __device__ __forceinline__ void ev_output_layer(const float* const gd1, float* c
   }
 }
 
-template <int MODE>      // 0: the kernel; 1 / 2: timing experiments (tools/evstamps.py): the output layer without its epilogue / without its matrix instructions
+// MODE 0: the kernel; 1 / 2: timing experiments (tools/evstamps.py): the output layer without its epilogue / without its matrix
+// instructions; 3 (ACC): one chunk of gmvae_iw_bound (EvalArgs::iw_*): strided noise, the bound folded into the fp64 row state.
+template <int MODE>
 __global__ __launch_bounds__(kMT) void evalf_rows(const EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr bool ACC = MODE == 3;
   constexpr int H = EV::H, L = EV::L, K = EV::K, D = EV::D;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ln = lane & 15, lk = lane >> 4;
@@ -387,7 +422,8 @@ __global__ __launch_bounds__(kMT) void evalf_rows(const EvalArgs a) {
         const bool rv = active && row < r_end;
         const long long rowc = rv ? row : r_end - 1;              // (clamped: lanes of absent rows compute on the last row, store nothing)
         const int bj = (int)(rowc / S) - bb;
-        const unsigned long long grow = a.row_base + (unsigned long long)rowc;
+        const unsigned long long grow = ACC ? (a.row_base + (unsigned long long)(bb + bj)) * a.iw_n + a.iw_s0 + (unsigned long long)(rowc - (long long)(bb + bj) * S)
+                                            : a.row_base + (unsigned long long)rowc;
         actv[pi] = active; rvA[pi] = rv; rowA[pi] = row; bjA[pi] = bj;
         xrA[pi] = reinterpret_cast<const unsigned char*>(T_x) + bj * D + 4 * lk;       // this row's x bytes (LDS)
         float lq = 0.f, lp_ = 0.f;
@@ -480,7 +516,7 @@ __global__ __launch_bounds__(kMT) void evalf_rows(const EvalArgs a) {
       }
       EV_ST(3 + 4 * min(p0 / (2 * kMW), 2));
       float lpxl[2];
-      ev_output_layer<MODE>(gd1, ring, B1, cc, p0 + 2 * kMW < panels || bb + EV::NB < b_end, Bp, actv, xrA, wave, lane, lpxl);
+      ev_output_layer<ACC ? 0 : MODE>(gd1, ring, B1, cc, p0 + 2 * kMW < panels || bb + EV::NB < b_end, Bp, actv, xrA, wave, lane, lpxl);
       EV_ST(4 + 4 * min(p0 / (2 * kMW), 2));
 #pragma unroll
       for (int pi = 0; pi < 2; ++pi) {
@@ -499,31 +535,42 @@ __global__ __launch_bounds__(kMT) void evalf_rows(const EvalArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const float logS = flog((float)S);
+    const int cnt = ACC ? (int)min((unsigned long long)S, a.iw_n - a.iw_s0) : S;      // (gmvae_iw_bound: the samples < n)
     for (int b = wave; b < nb; b += kMW) {
       const float* const rw = a.rows_ws + ((long long)(bb + b) * S) * 4;
-      float mx = -INFINITY, se = 0.f, nl = 0.f, kl = 0.f;
+      float mx = -INFINITY, se = 0.f, nl = 0.f, kl = 0.f, slw = 0.f;
       if (S <= 64) {                               // one sample row per lane: ONE 16-byte agent-scope load each
         u32x4_t v = {0u, 0u, 0u, 0u};
-        if (lane < S) { v = granule2_load(reinterpret_cast<const unsigned long long*>(rw + 4 * lane)); asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)::"memory"); }
-        const float lw = lane < S ? __uint_as_float(v[3]) : -INFINITY;
+        if (lane < cnt) { v = granule2_load(reinterpret_cast<const unsigned long long*>(rw + 4 * lane)); asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)::"memory"); }
+        const float lw = lane < cnt ? __uint_as_float(v[3]) : -INFINITY;
         mx = Wave64::max(lw);
-        se = lane < S ? fexp(lw - mx) : 0.f;
-        nl = lane < S ? -__uint_as_float(v[0]) : 0.f;
-        kl = lane < S ? __uint_as_float(v[1]) - __uint_as_float(v[2]) : 0.f;
+        se = lane < cnt ? fexp(lw - mx) : 0.f;
+        nl = lane < cnt ? -__uint_as_float(v[0]) : 0.f;
+        kl = lane < cnt ? __uint_as_float(v[1]) - __uint_as_float(v[2]) : 0.f;
+        if (ACC) slw = lane < cnt ? lw : 0.f;
       } else {
-        for (int s = lane; s < S; s += 64) mx = fmaxf(mx, ld_sc(rw + 4 * s + 3));
+        for (int s = lane; s < cnt; s += 64) mx = fmaxf(mx, ld_sc(rw + 4 * s + 3));
         mx = Wave64::max(mx);
-        for (int s = lane; s < S; s += 64) {
+        for (int s = lane; s < cnt; s += 64) {
           se += fexp(ld_sc(rw + 4 * s + 3) - mx);
           nl -= ld_sc(rw + 4 * s);
           kl += ld_sc(rw + 4 * s + 1) - ld_sc(rw + 4 * s + 2);
+          if (ACC) slw += ld_sc(rw + 4 * s + 3);
         }
       }
       se = Wave64::sum(se); nl = Wave64::sum(nl); kl = Wave64::sum(kl);
-      const float bound = mx + flog(se) - logS;
-      w_loss -= bound; w_nl += nl / (float)S; w_kl += kl / (float)S; w_ne += T_ne[b];
+      if (ACC) {
+        float o_loss, o_nl, o_kl;
+        iw_fold(a, bb + b, lane, mx, se, Wave64::sum(slw), nl, kl, o_loss, o_nl, o_kl);
+        w_loss += o_loss; w_nl += o_nl; w_kl += o_kl;
+        if (a.iw_final) w_ne += T_ne[b];
+      } else {
+        const float bound = mx + flog(se) - logS;
+        w_loss -= bound; w_nl += nl / (float)S; w_kl += kl / (float)S; w_ne += T_ne[b];
+      }
     }
   }
+  if (ACC && !a.iw_final) return;                  // (every workgroup: the batch sums wait for the last chunk)
   // ---- batch sums: waves -> workgroup slot -> the last workgroup to arrive adds the slots in order
   __syncthreads();
   if (lane == 0) { red[wave * 4] = w_loss; red[wave * 4 + 1] = w_nl; red[wave * 4 + 2] = w_kl; red[wave * 4 + 3] = w_ne; }
@@ -571,9 +618,11 @@ struct EVV {
   static constexpr int M_c = M_inv + 640;          // [16]
   static constexpr int lds = M_c + 16;
 };
-template <int MODEL, int L>      // MODEL 0: VAE (N(0, I) prior), 1: VAE_GMP (K = 10 mixture prior); L = 2 or 64
+template <int MV, int L>      // MV & 1 = MODEL: 0 VAE (N(0, I) prior), 1 VAE_GMP (K = 10 mixture prior); MV & 2: ACC (as evalf_rows<3>); L = 2 or 64
 __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int MODEL = MV & 1;
+  constexpr bool ACC = (MV & 2) != 0;
   constexpr int H = EV::H, D = EV::D, K = 10, L2 = 2 * L, LT = (L + 15) / 16;
   static_assert(L == 2 || L == 64, "latent sizes of the reference's configurations");
   static_assert(MODEL == 0 || L == 64, "VAE_GMP: latent 64");
@@ -649,7 +698,8 @@ __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
         const bool rv = active && row < r_end;
         const long long rowc = rv ? row : r_end - 1;
         const int bj = (int)(rowc / S) - bb;
-        const unsigned long long grow = a.row_base + (unsigned long long)rowc;
+        const unsigned long long grow = ACC ? (a.row_base + (unsigned long long)(bb + bj)) * a.iw_n + a.iw_s0 + (unsigned long long)(rowc - (long long)(bb + bj) * S)
+                                            : a.row_base + (unsigned long long)rowc;
         actv[pi] = active; rvA[pi] = rv; rowA[pi] = row;
         xrA[pi] = reinterpret_cast<const unsigned char*>(T_x) + bj * D + 4 * lk;
         if (active) {
@@ -741,20 +791,29 @@ __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const float logS = flog((float)S);
+    const int cnt = ACC ? (int)min((unsigned long long)S, a.iw_n - a.iw_s0) : S;
     for (int b = wave; b < nb; b += kMW) {
       const float* const rw = a.rows_ws + ((long long)(bb + b) * S) * 4;
-      float mx = -INFINITY, se = 0.f, nl = 0.f, kl = 0.f;
-      for (int s = lane; s < S; s += 64) mx = fmaxf(mx, ld_sc(rw + 4 * s + 3));
+      float mx = -INFINITY, se = 0.f, nl = 0.f, kl = 0.f, slw = 0.f;
+      for (int s = lane; s < cnt; s += 64) mx = fmaxf(mx, ld_sc(rw + 4 * s + 3));
       mx = Wave64::max(mx);
-      for (int s = lane; s < S; s += 64) {
+      for (int s = lane; s < cnt; s += 64) {
         se += fexp(ld_sc(rw + 4 * s + 3) - mx);
         nl -= ld_sc(rw + 4 * s);
         kl += ld_sc(rw + 4 * s + 1) - ld_sc(rw + 4 * s + 2);
+        if (ACC) slw += ld_sc(rw + 4 * s + 3);
       }
       se = Wave64::sum(se); nl = Wave64::sum(nl); kl = Wave64::sum(kl);
-      w_loss -= mx + flog(se) - logS; w_nl += nl / (float)S; w_kl += kl / (float)S;
+      if (ACC) {
+        float o_loss, o_nl, o_kl;
+        iw_fold(a, bb + b, lane, mx, se, Wave64::sum(slw), nl, kl, o_loss, o_nl, o_kl);
+        w_loss += o_loss; w_nl += o_nl; w_kl += o_kl;
+      } else {
+        w_loss -= mx + flog(se) - logS; w_nl += nl / (float)S; w_kl += kl / (float)S;
+      }
     }
   }
+  if (ACC && !a.iw_final) return;
   __syncthreads();
   if (lane == 0) { red[wave * 4] = w_loss; red[wave * 4 + 1] = w_nl; red[wave * 4 + 2] = w_kl; red[wave * 4 + 3] = 0.f; }
   __syncthreads();

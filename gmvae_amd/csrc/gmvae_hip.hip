@@ -33,6 +33,7 @@
 #include "skinny.hpp"
 #include "rowsws.hpp"
 #include "evalf.hpp"
+#include "iwbound.hpp"
 
 using namespace gmvae;
 
@@ -1826,9 +1827,10 @@ static int run_step_skinny(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, c
 
 // Forward-only evaluation at the reference's default sizes (evalf.hpp): first layers -> operand images -> ONE launch for the whole
 // per-row chain, the Bernoulli term, the IWAE bound and the batch sums.  scripts/runners.py:324-333.
-static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
+// eval_fused_front: the first layers over x and (prep) the operand images; eval_fused_args: the launch's arguments.
+static void eval_fused_front(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, const bool prep) {
   const GmvaeDims& d = *a.d;
-  const int B = d.B, S = d.S, D = d.D;
+  const int B = d.B, D = d.D;
   const float* P = a.params;
   hipStream_t st = cx.st;
   const bool gm = a.model == GMVAE_MODEL_GMVAE;
@@ -1849,7 +1851,7 @@ static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
     cx.mark("fwd_x_first_layers", 2.0 * B * D * nct * EV::H);
   }
   unsigned* const counter = reinterpret_cast<unsigned*>(w.ev_slots + 4 * 1024);
-  if (!(d.sched_flags & GMVAE_SCHED_EVAL_IMAGES_VALID)) {      // (else: a previous pass on fixed parameters left the images; its last workgroup reset the counter)
+  if (prep) {
     EvalPrepArgs pa;
     memset(&pa, 0, sizeof(pa));
     if (gm) { pa.Wp = P + L.prior.w[0]; pa.bp = P + L.prior.b[0]; pa.Wg0 = P + G.w[0]; pa.bg0 = P + G.b[0]; pa.Wg1 = P + G.w[1]; pa.bg1 = P + G.b[1]; }
@@ -1860,32 +1862,55 @@ static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
     cx.check();
     cx.mark("evalf_prep", 0);
   }
-  EvalArgs ea;
+}
+static void eval_fused_args(const StepArgs& a, const Layout& L, WS& w, EvalArgs& ea) {
+  const GmvaeDims& d = *a.d;
+  const float* P = a.params;
+  const bool gm = a.model == GMVAE_MODEL_GMVAE;
+  const NetL& E = gm ? L.ency : L.enc;
   memset(&ea, 0, sizeof(ea));
-  ea.B = B; ea.S = S; ea.x = a.x; ea.he1 = w.he[1]; ea.gx = w.gx; ea.img = w.ev_img;
+  ea.B = d.B; ea.S = d.S; ea.x = a.x; ea.he1 = w.he[1]; ea.gx = w.gx; ea.img = w.ev_img;
   if (gm) { ea.Wy1 = P + E.w[1]; ea.by1 = P + E.b[1]; }
   else {
     ea.We1 = P + E.w[1]; ea.be1 = P + E.b[1];
     if (a.model == GMVAE_MODEL_VAE_GMP) { ea.loc = P + L.loc; ea.raw_scale = P + L.rawscale; ea.mixlog = P + L.mixlog; }
   }
-  ea.eps = a.eps; ea.u = a.u; ea.seed = a.seed; ea.step = a.step; ea.row_base = (unsigned long long)d.row0 * S;
+  ea.eps = a.eps; ea.u = a.u; ea.seed = a.seed; ea.step = a.step; ea.row_base = (unsigned long long)d.row0 * d.S;
   ea.c = d.raw_sigma_bias; ea.smin = d.sigma_min; ea.invT = 1.f / d.temperature;
   ea.rows4 = a.row_terms; ea.z_out = a.z_out; ea.y_out = a.y_out; ea.logits_out = a.logits_out;
   ea.rows_ws = a.row_terms ? a.row_terms : w.ev_rows;
-  ea.slots = w.ev_slots; ea.counter = counter; ea.tail = a.tail;
+  ea.slots = w.ev_slots; ea.counter = reinterpret_cast<unsigned*>(w.ev_slots + 4 * 1024); ea.tail = a.tail;
   ea.dbg = getenv("GMVAE_EV_STAMPS") ? w.ev_dbg : nullptr;
   static bool eattr[64];
   if (first_on_device(eattr)) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows<0>), hipFuncAttributeMaxDynamicSharedMemorySize, EV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows<1>), hipFuncAttributeMaxDynamicSharedMemorySize, EV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows<2>), hipFuncAttributeMaxDynamicSharedMemorySize, EV::lds * (int)sizeof(float));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows<3>), hipFuncAttributeMaxDynamicSharedMemorySize, EV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<0, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<1, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<3, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
   }
+}
+static int eval_fused_grid(const GmvaeDims& d) {
   int grid = device_cus();
-  if (grid > B) grid = B;
+  if (grid > d.B) grid = d.B;
   if (grid > 1024) grid = 1024;
+  return grid;
+}
+static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
+  const GmvaeDims& d = *a.d;
+  const int B = d.B, S = d.S, D = d.D;
+  hipStream_t st = cx.st;
+  const bool gm = a.model == GMVAE_MODEL_GMVAE;
+  // (GMVAE_SCHED_EVAL_IMAGES_VALID: a previous pass on fixed parameters left the images; its last workgroup reset the counter)
+  eval_fused_front(cx, a, L, w, !(d.sched_flags & GMVAE_SCHED_EVAL_IMAGES_VALID));
+  EvalArgs ea;
+  eval_fused_args(a, L, w, ea);
+  const int grid = eval_fused_grid(d);
   const int ev_mode = getenv("GMVAE_EV_MODE") ? atoi(getenv("GMVAE_EV_MODE")) : 0;      // (timing experiments: wrong results)
   const size_t shv = (size_t)EVV::lds * sizeof(float);
   if (!gm) {
@@ -2462,6 +2487,90 @@ static int run_step(Ctx& cx, const StepArgs& a) {
 
 static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- gmvae_iw_bound: the workspace is the forward's at these dims (S = the chunk), then the call's own region (byte offsets)
+struct IwLay { uint64_t eps, u, rows, ftail, state, rsum, bytes; };
+static void iw_lay(const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
+  WS w;
+  carve(d, model, L, nullptr, w);
+  uint64_t off = (w.bytes + 255) / 256 * 256;
+  auto take = [&](uint64_t bytes) { const uint64_t r = off; off += (bytes + 255) / 256 * 256; return r; };
+  const uint64_t B = d.B, R = (uint64_t)d.B * d.S;
+  o.eps = take(pad4(R * d.L) * 4);               // general schedule: the chunk's explicit noise
+  o.u = take(model == GMVAE_MODEL_GMVAE ? pad4(R * d.K) * 4 : 0);
+  o.rows = take(R * 16);                         // ... its rows (log p(x|z), log q, log p, log w)
+  o.ftail = take(GMVAE_TAIL * 4);                // ... the forward's own tail (tail[3]: the batch's nent sum)
+  o.state = take(B * 6 * 8);                     // every schedule: the fp64 row state (evalf.hpp iw_fold)
+  o.rsum = take(B * 16);                         // general schedule: the rows' (-bound, nll, kl) for iw_tail
+  o.bytes = off;
+}
+
+// ceil(n / S) chunk passes.  evalf sizes: first layers + operand images once, then ONE evalf_rows<3> / evalf_rows_v<2|3, L> launch per
+// chunk (noise drawn in the kernel); every other shape: iw_noise_fill -> the forward with that noise -> iw_merge per chunk, iw_tail.
+static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* x, const float* params, uint64_t n,
+                        float* bound_out, float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
+  GmvaeDims d = d0;
+  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;      // (the operand images are prepared here, once per call)
+  Layout L;
+  build_layout(d, model, L);
+  WS w;
+  carve(d, model, L, workspace, w);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  char* const base = static_cast<char*>(workspace);
+  double* const state = reinterpret_cast<double*>(base + il.state);
+  const int B = d.B, S = d.S;
+  const uint64_t nch = (n + S - 1) / S;
+  hipStream_t st = cx.st;
+  const bool gm = model == GMVAE_MODEL_GMVAE;
+  if (evalf_ok(d, model) && w.ev_img) {
+    const StepArgs a = {&d, model, x, nullptr, nullptr, params, nullptr, tail, nullptr, nullptr, nullptr, nullptr, workspace,
+                        seed, step, nullptr, false};
+    eval_fused_front(cx, a, L, w, true);
+    EvalArgs ea;
+    eval_fused_args(a, L, w, ea);
+    ea.row_base = d.row0;                          // (the kernels stride it: Philox row (row0 + b) n + s)
+    ea.dbg = nullptr;
+    ea.iw_state = state; ea.iw_bound = bound_out; ea.iw_mlw = mlw_out; ea.iw_n = n;
+    const int grid = eval_fused_grid(d);
+    const size_t sh = (size_t)(gm ? EV::lds : EVV::lds) * sizeof(float);
+    for (uint64_t c = 0; c < nch; ++c) {
+      ea.iw_s0 = c * (uint64_t)S; ea.iw_final = c + 1 == nch;
+      if (gm) hipLaunchKernelGGL(evalf_rows<3>, dim3(grid), dim3(kMT), sh, st, ea);
+      else if (model == GMVAE_MODEL_VAE_GMP) hipLaunchKernelGGL((evalf_rows_v<3, 64>), dim3(grid), dim3(kMT), sh, st, ea);
+      else if (d.L == 2) hipLaunchKernelGGL((evalf_rows_v<2, 2>), dim3(grid), dim3(kMT), sh, st, ea);
+      else hipLaunchKernelGGL((evalf_rows_v<2, 64>), dim3(grid), dim3(kMT), sh, st, ea);
+      rowk(cx, gm ? "evalf_rows<3>" : "evalf_rows_v");
+    }
+    return cx.err;
+  }
+  float* const eps = reinterpret_cast<float*>(base + il.eps);
+  float* const u = gm ? reinterpret_cast<float*>(base + il.u) : nullptr;
+  float* const rows = reinterpret_cast<float*>(base + il.rows);
+  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
+  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
+  EvalArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.B = B; ma.S = S; ma.rows_ws = rows; ma.slots = rsum;
+  ma.iw_state = state; ma.iw_bound = bound_out; ma.iw_mlw = mlw_out; ma.iw_n = n;
+  const uint64_t q = noise_items(true, u != nullptr, (uint64_t)B * S, d.L, d.K);
+  for (uint64_t c = 0; c < nch; ++c) {
+    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, u, B, S, d.L, d.K,
+                       (unsigned long long)d.row0, (unsigned long long)n, (unsigned long long)(c * S), (unsigned long long)seed,
+                       (unsigned long long)step);
+    rowk(cx, "iw_noise_fill");
+    const StepArgs a = {&d, model, x, eps, u, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed, step,
+                        nullptr, false};
+    if (int e = run_step(cx, a)) return e;
+    ma.iw_s0 = c * (uint64_t)S; ma.iw_final = c + 1 == nch;
+    hipLaunchKernelGGL(iw_merge, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, ma);
+    rowk(cx, "iw_merge");
+  }
+  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, ftail, tail);
+  rowk(cx, "iw_tail");
+  return cx.err;
+}
+
+
 }  // namespace
 
 // ================================ C ABI ====================================
@@ -2545,6 +2654,32 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   StepArgs a = {dims, model, x, eps, u, params, nullptr, tail, row_terms, z_out, y_out, logits_out, workspace, seed,
                 step, nullptr, false};
   return run_step(cx, a);
+}
+
+int gmvae_iw_bound_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
+  if (int e = check_dims(dims, model)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  Layout L;
+  build_layout(*dims, model, L);
+  IwLay il;
+  iw_lay(*dims, model, L, il);
+  *bytes = il.bytes;
+  return 0;
+}
+
+int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                   float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
+                   void* stream) {
+  if (int e = check_dims(dims, model)) return e;
+  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
+  const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
+  if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
+  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) || (bound_out && !aligned16(bound_out)) ||
+      (mean_logw_out && !aligned16(mean_logw_out)))
+    return GMVAE_E_ALIGN;
+  Ctx cx;
+  cx.st = static_cast<hipStream_t>(stream);
+  return run_iw_bound(cx, *dims, model, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

@@ -1,0 +1,88 @@
+// gmvae_iw_bound on every shape and schedule the one-launch evaluation (evalf.hpp) does not take: per chunk of S samples a strided
+// Philox fill of eps / u, the forward with that explicit noise (its per-sample rows [B S][4] in the workspace), and iw_merge, which
+// folds the chunk into the fp64 row state (evalf.hpp iw_fold).  The last chunk adds iw_tail: the batch sums in a fixed order.
+#pragma once
+#include "evalf.hpp"
+
+namespace gmvae {
+
+// eps [B S][L], u [B S][K] (either may be null) of one chunk: row b S + s draws Philox row (row0 + b) n + s0 + s
+__global__ __launch_bounds__(256) void iw_noise_fill(float* eps, float* u, const int B, const int S, const int L, const int K,
+                                                     const unsigned long long row0, const unsigned long long n,
+                                                     const unsigned long long s0, const unsigned long long seed,
+                                                     const unsigned long long step) {
+  const unsigned long long rows = (unsigned long long)B * S;
+  const unsigned qe = eps ? (unsigned)(L + 3) / 4 : 0u, qu = u ? (unsigned)(K + 3) / 4 : 0u;
+  const unsigned long long n_e = rows * qe;
+  unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_e + rows * qu) return;
+  const bool is_u = i >= n_e;
+  if (is_u) i -= n_e;
+  const unsigned qpr = is_u ? qu : qe;
+  const unsigned long long row = i / qpr;
+  const unsigned quad = (unsigned)(i - row * qpr);
+  const unsigned long long b = row / (unsigned)S;
+  float o[4];
+  noise_vals((row0 + b) * n + s0 + (row - b * (unsigned)S), quad, is_u, seed, step, o);
+  const int w = is_u ? K : L;
+  float* const dst = (is_u ? u : eps) + row * (unsigned long long)w + quad * 4;
+  if ((w & 3) == 0) {
+    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if ((int)quad * 4 + j < w) dst[j] = o[j];
+  }
+}
+
+__device__ __forceinline__ double iw_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// a wave per batch row: the chunk's samples s < n - s0 of rows_ws [B S][4] (log p(x|z), log q, log p, log w) in fp64, folded into
+// iw_state; on the last chunk the row's (-bound, mean nll, mean kl) go to slots [B][4] for iw_tail
+__global__ __launch_bounds__(256) void iw_merge(const EvalArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const int S = a.S, cnt = (int)min((unsigned long long)S, a.iw_n - a.iw_s0);
+  const float* const rw = a.rows_ws + b * S * 4;
+  float mx = -INFINITY;
+  for (int s = lane; s < cnt; s += 64) mx = fmaxf(mx, rw[4 * s + 3]);
+  mx = Wave64::max(mx);
+  double se = 0., slw = 0., nl = 0., kl = 0.;
+  for (int s = lane; s < cnt; s += 64) {
+    const float4 v = *reinterpret_cast<const float4*>(rw + 4 * s);
+    se += exp((double)v.w - (double)mx);
+    slw += v.w;
+    nl -= v.x;
+    kl += (double)v.y - (double)v.z;
+  }
+  se = iw_wave_sum(se); slw = iw_wave_sum(slw); nl = iw_wave_sum(nl); kl = iw_wave_sum(kl);
+  float o_loss, o_nl, o_kl;
+  iw_fold(a, b, lane, mx, se, slw, nl, kl, o_loss, o_nl, o_kl);
+  if (a.iw_final && lane == 0) *reinterpret_cast<float4*>(a.slots + 4 * b) = make_float4(o_loss, o_nl, o_kl, 0.f);
+}
+
+// one workgroup: tail[0..2] = the sums of slots [B][4] over b (fixed order: strided fp64 partials, then a fixed tree), tail[3] =
+// nent_tail[3] (the sum of -H(q(y|x)) over the batch from the last chunk's forward: it does not depend on the noise), tail[4] = B
+__global__ __launch_bounds__(256) void iw_tail(const float* slots, const int B, const float* nent_tail, float* tail) {
+  __shared__ double red[3][256];
+  const int t = threadIdx.x;
+  double s0 = 0., s1 = 0., s2 = 0.;
+  for (int b = t; b < B; b += 256) { s0 += slots[4 * b]; s1 += slots[4 * b + 1]; s2 += slots[4 * b + 2]; }
+  red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) { red[0][t] += red[0][t + h]; red[1][t] += red[1][t + h]; red[2][t] += red[2][t + h]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    tail[0] = (float)red[0][0]; tail[1] = (float)red[1][0]; tail[2] = (float)red[2][0];
+    tail[3] = nent_tail ? nent_tail[3] : 0.f; tail[4] = (float)B; tail[5] = 0.f; tail[6] = 0.f; tail[7] = 0.f;
+  }
+}
+
+}  // namespace gmvae

@@ -85,6 +85,7 @@ class Engine:
         self._graph_gen = 0                     # bumped by drop_graphs: replay closures of dropped graphs raise
         self._param_epoch = 0                   # bumped by every Engine call that enqueues a writer of the parameter buffer
         self._eval_imgs: Dict[tuple, tuple] = {}   # (B, S) -> the state of the parameters a forward-only pass left images for
+        self._iw_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound's workspace
         self.init_parameters(random_seed)
 
     # ------------------------------------------------------------ parameters
@@ -272,6 +273,37 @@ class Engine:
                                  L.ptr(ws), self.noise_seed, self.global_step, L.current_stream())
         L.check(rc, "gmvae_forward")
         self._eval_imgs[(B, S)] = state
+        return o
+
+    IW_CHUNK_ROWS = 51200          # default B * chunk of iw_bound: the rows of bench.py's eval_iwae pass (B = 1024, S = 50)
+
+    def iw_bound(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
+        """The importance-weighted bound at any number of samples, streamed in chunks (include/gmvae_hip.h gmvae_iw_bound):
+        dict(bound [B] = logsumexp_s log w - log n, mean_logw [B], tail [8] as forward's at S = n).  chunk: samples per pass
+        (default: B * chunk near IW_CHUNK_ROWS, at most n_samples); the memory depends on B * chunk, not on n_samples.
+        Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step), row0 defaulting to
+        rank * B: the result does not depend on the chunk, the batch size or the sharding."""
+        x = self._prep_x(x)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        B, n = x.shape[0], int(n_samples)
+        if n < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n}")
+        chunk = max(1, min(n, self.IW_CHUNK_ROWS // B)) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        d = self.dims(B, chunk, row0)
+        nw = L.iw_bound_workspace_bytes(d, self.model) // 4 + 64
+        ws = self._iw_ws.get((B, chunk))
+        if ws is None or ws.numel() < nw:
+            ws = self._iw_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        o = dict(bound=torch.empty(B, **f32), mean_logw=torch.empty(B, **f32), tail=torch.empty(L.TAIL, **f32))
+        rc = L.lib.gmvae_iw_bound(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(o["bound"]),
+                                  L.ptr(o["mean_logw"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
+                                  L.current_stream())
+        L.check(rc, "gmvae_iw_bound")
+        self._keep_iw = x
         return o
 
     def mlp(self, net: int, inp: torch.Tensor, in2: Optional[torch.Tensor] = None) -> torch.Tensor:

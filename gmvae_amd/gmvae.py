@@ -93,6 +93,11 @@ class TrainableGMVAE(GMVAE):
         self._last_labels = labels
         return e.loss(images, eps, u)
 
+    def iw_bound(self, images, n_samples, chunk=None):
+        """Per-example importance-weighted bound at n_samples samples (the A15 bound compute_loss(n_samples=S) reports),
+        streamed in chunks of `chunk` samples: a [B] device tensor (Engine.iw_bound)."""
+        return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
+
     @property
     def summaries(self):
         """nll_scalar, kl_div_z, nent, elbo, cluster_acc of the last run_model

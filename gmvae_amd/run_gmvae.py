@@ -34,6 +34,9 @@ def build_parser():
     a("--eager", action="store_true", help="eager launches instead of summarise_every-aligned train graphs")
     a("--checkpoint_poll_seconds", type=float, default=60.0)     # eval: scripts/utils.py:100-111 sleeps 60 s
     a("--checkpoint_max_wait", type=float, default=None, help="eval: give up waiting after this many seconds")
+    a("--iw_samples", type=int, default=0, help="eval: also report the importance-weighted bound at this many samples per "
+      "example, streamed in chunks (Engine.iw_bound); 0 = off")
+    a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples (default: ~51,200 rows per pass)")
     return p
 
 

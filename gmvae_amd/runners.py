@@ -38,13 +38,14 @@ def _load_mnist(root: str, split: str):
     return None
 
 
-def create_dataset(config, split="train", shuffle=True, repeat=True, device="cuda"):
+def create_dataset(config, split="train", shuffle=True, repeat=True, device="cuda", with_index=False):
     """Yields (images bool/uint8 [B,784] on device, labels int64 [B]) -- the output contract of
     scripts/runners.py:21-62.  Dynamic binarisation keeps the reference's INVERTED rule
     `image < U(0,1)` (runners.py:44-47: P(pixel=1) = 1 - intensity) and is redrawn every epoch;
     examples are shuffled per epoch (the reference's batch-level shuffle order is not copied).
     The last partial batch is kept (no drop_remainder, runners.py:51).  Without local MNIST files
-    (--data_dir) a synthetic Bernoulli(0.87) set with random labels stands in."""
+    (--data_dir) a synthetic Bernoulli(0.87) set with random labels stands in.  with_index: yields a third item, the index in
+    the split of the batch's first example (its rows follow in order when shuffle=False)."""
     data = _load_mnist(getattr(config, "data_dir", "") or "", split) if getattr(config, "data_dir", None) else None
     rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
     gen = torch.Generator(device=device)
@@ -68,7 +69,7 @@ def create_dataset(config, split="train", shuffle=True, repeat=True, device="cud
             binar = (inten < torch.rand(inten.shape, device=device, generator=gen)).to(torch.uint8)
             for s in range(0, n, B):
                 idx = order[s:s + B]
-                yield binar[idx], labels[idx]
+                yield (binar[idx], labels[idx], a + s) if with_index else (binar[idx], labels[idx])
             if not repeat:
                 return
     return it()
@@ -365,7 +366,12 @@ def run_eval(config):
     eng = model._engine
     tot = torch.zeros(5, device=eng.device)
     ref_sum, n_batches, codes, labs = 0.0, 0, [], []
-    for images, labels in create_dataset(config, config.split, shuffle=False, repeat=False):
+    # --iw_samples N: the importance-weighted bound at N samples per example, streamed in chunks; row0 = the example's index in
+    # the split, so every example draws its own noise whatever --batch_size or the number of ranks
+    iw_n, iw_chunk, iw_rows = int(getattr(config, "iw_samples", 0) or 0), getattr(config, "iw_chunk", None), []
+    for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True):
+        if iw_n > 0:
+            iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first)["bound"])
         o = eng.forward(images)
         tot += o["tail"][:5]
         ref_sum += (o["tail"][0] / o["tail"][4]).item()
@@ -374,12 +380,16 @@ def run_eval(config):
         # code (gmvae.py:140-149) -- the forward pass's z is exactly that sample
         codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)
+    iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     if world > 1:
         parallel.all_reduce_flat(tot)
+        parallel.all_reduce_flat(iw_sum)
     n = tot[4].item()
     res = {f"{config.split}/loss_per_example": tot[0].item() / n, f"{config.split}/nll": tot[1].item() / n,
            f"{config.split}/kl_div_z": tot[2].item() / n, f"{config.split}/nent": tot[3].item() / n,
            f"{config.split}/reference_misnormalised_loss_per_example": ref_sum / n, "examples": int(n)}
+    if iw_n > 0:
+        res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if rank == 0:
         for k, v in res.items():
             print(f"{k}: {v}")
@@ -390,6 +400,7 @@ def run_eval(config):
     img_shape = (28, 28, 1) if data_dim == 784 else (data_dim, 1, 1)
     res["latent_state"] = torch.cat(codes) if codes else None
     res["labels"] = torch.cat(labs) if labs else None
+    res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
     res["samples"] = model.generate_samples(num_samples=int(config.num_samples))
     sample_images = utils.unflatten_tensor(model.generate_sample_images(num_samples=int(config.num_generations)), img_shape)
     if config.model == "gmvae":

@@ -76,6 +76,11 @@ class TrainableVAE(VAE):
             raise ValueError(f"model was created with n_samples={e.S}")
         return e.loss(images, eps, None)
 
+    def iw_bound(self, images, n_samples, chunk=None):
+        """Per-example IWAE estimate of log p(x) at n_samples samples (Burda et al.), streamed in chunks of `chunk` samples:
+        a [B] device tensor (Engine.iw_bound)."""
+        return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
+
     @property
     def summaries(self):
         """nll_scalar / kl_div_z / elbo of the last run_model (scripts/vae.py:178,182,186)."""

@@ -162,6 +162,25 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
                   const float* params, float* tail, float* row_terms, float* z_out, float* y_out,
                   float* logits_out, void* workspace, uint64_t seed, uint64_t step, void* stream);
 
+/* The importance-weighted bound at n_samples importance samples per row (the IWAE estimate of log p(x) for VAE / VAE_GMP; for
+ * the GMVAE the project's A15 bound -- relaxed y, the analytic -sum pi ln pi term -- that gmvae_forward reports at S = n),
+ * streamed in chunks of dims->S samples (the last chunk may be partial): memory does not grow with n_samples.
+ * Noise of sample s (0 <= s < n_samples) of batch row b: Philox row (dims->row0 + b) * n_samples + s, so the result does not
+ * depend on the chunk size, the batch size or the sharding.  With n_samples == dims->S this is exactly gmvae_forward's keying
+ * (row0*S + b*S + s).
+ *   bound_out [B] (may be NULL): logsumexp_s(log w_bs) - log n;  mean_logw_out [B] (may be NULL): mean_s log w_bs;
+ *   tail [GMVAE_TAIL]: as gmvae_forward's at S = n (sum of -bound, the per-row means of nll / kl, nent, count B).
+ * The workspace (its size from gmvae_iw_bound_workspace_bytes at the same dims; zeroed once, one set of dims) holds the forward's
+ * workspace at S = the chunk and the per-row running state (max and sum of exp, sums of log w, nll and kl, in fp64), which the
+ * first chunk initialises.  One call enqueues ceil(n_samples / S) chunk passes on `stream`; at the reference's default sizes
+ * (the ones evalf.hpp takes) ONE launch per chunk after the first layers.  It prepares its operand images itself, once per
+ * call (dims->sched_flags' GMVAE_SCHED_EVAL_IMAGES_VALID is ignored).  GMVAE_E_DIMS if n_samples == 0 or
+ * (row0 + B) * n_samples >= 2^38; GMVAE_E_ALIGN for unaligned x, params, outputs or workspace. */
+int gmvae_iw_bound_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes);
+int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                   float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
+                   void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
