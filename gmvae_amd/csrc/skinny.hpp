@@ -1397,7 +1397,6 @@ __device__ __forceinline__ void sk_gmp_update(const SkArgs& a, const int idx, co
 // the loss tail of a W launch (one workgroup): per-row terms from the partials, batch sums, counters
 __device__ __forceinline__ void sk_loss_tail(const SkArgs& a, float (&red)[4][256], const int tid) {
   const int B = a.B;
-  const unsigned long long dbg_c0 = __builtin_amdgcn_s_memtime(), dbg_r0 = __builtin_amdgcn_s_memrealtime();
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   const int nlt = (a.L + 15) / 16;
   if (tid < 256) {
@@ -1420,8 +1419,8 @@ __device__ __forceinline__ void sk_loss_tail(const SkArgs& a, float (&red)[4][25
     __syncthreads();
   }
   if (tid == 0) {
-    const unsigned long long dbg_c1 = __builtin_amdgcn_s_memtime(), dbg_r1 = __builtin_amdgcn_s_memrealtime();
-    const float tl[8] = {red[0][0], red[1][0], red[2][0], red[3][0], (float)B, 0.f, (float)(dbg_c1 - dbg_c0), (float)(dbg_r1 - dbg_r0)};
+    // (slots 5..7 are zero, as every other schedule leaves them: the tail is all-reduced and logged, so it must be reproducible)
+    const float tl[8] = {red[0][0], red[1][0], red[2][0], red[3][0], (float)B, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 8; ++j) { a.tail[j] = tl[j]; if (a.tail_log) a.tail_log[j] = tl[j]; }
     if (a.step_dev) a.step_dev[0] = a.step_dev[1] + 1ull;

@@ -58,8 +58,10 @@ def _device_masks(e, model, d, B):
     return out
 
 
-def _oracle_trajectory(L, model, d, flat0, xs, seed, step0=0, row_base=0, masks_of_step=None, params_of_step=None, tag=""):
+def _oracle_trajectory(L, model, d, flat0, xs, seed, step0=0, row_base=0, masks_of_step=None, params_of_step=None, tag="",
+                       terms=None):
     """n oracle steps (fp64) on the noise of device steps step0 .. step0+n-1; returns (flat, C_last, g_last, [g_t]).
+    terms: a list that receives every step's loss terms (the C of step t), for the per-step tails of a graph (tail_log).
 
     masks_of_step(t) -> the device's ReLU masks of step t (see _device_masks); params_of_step(t) -> the device's parameters
     BEFORE step t (None: the oracle's own).  ReLU has no derivative at 0 and an fp32 pre-activation that is zero to within rounding can land on the
@@ -110,7 +112,21 @@ def _oracle_trajectory(L, model, d, flat0, xs, seed, step0=0, row_base=0, masks_
         flat, m, v, Cc, g = O.train_step(model, d, flat, m, v, step0 + t + 1, xs[t], eps, u, lr=LR, dtype=np.float64,
                                          relu_masks=masks)
         gs.append(g)
+        if terms is not None:
+            terms.append(Cc)
     return flat, Cc, g, gs
+
+
+def _compare_tail(tail, B, Cc, tag=""):
+    """A step's loss sums and count (the [TAIL] slot of the gradient buffer, or a row of a graph's tail_log) against the
+    oracle's loss terms of that step."""
+    tail = np.asarray(tail, np.float64)
+    assert tail[4] == B, (tag, tail[4])
+    assert (tail[5:8] == 0).all(), (tag, tail[5:8])       # (unused slots: zero, or the all-reduced tail is not reproducible)
+    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (tag, tail[0] / B, Cc["loss"])
+    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), tag
+    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (tag, tail[2] / B, Cc["kl"])       # each term relative to
+    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (tag, tail[3] / B, Cc["nent"])  # itself (SURVEY A.2)
 
 
 def _compare_last_step(model, d, eng, B, Cc, g, at_device=None, tag=""):
@@ -124,12 +140,7 @@ def _compare_last_step(model, d, eng, B, Cc, g, at_device=None, tag=""):
     tolerance; no fp32 implementation, the reference's included, is pinned tighter than that by an fp64 trajectory."""
     P = eng.P
     buf = eng.grads.cpu().numpy().astype(np.float64)
-    tail = buf[P:]
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (tag, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), tag
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (tag, tail[2] / B, Cc["kl"])       # each term relative to
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (tag, tail[3] / B, Cc["nent"])  # itself (SURVEY A.2)
+    _compare_tail(buf[P:], B, Cc, tag)
     lay, _, _ = O.param_layout(model, d)
     for name, shape, off in lay:
         n = int(np.prod(shape))
@@ -320,28 +331,270 @@ def test_second_graph_launch_continues_the_trajectory():
     _compare_params(O.MODEL_GMVAE, d, e, flat_ref, gs, 2 * n, "two-launches")
 
 
-def test_dp_graph_world1_matches_oracle_trajectory():
-    """The data-parallel train graph (RCCL all-reduce captured inside, adam_tf_img after it) with a one-rank
-    communicator and a NON-ZERO global row offset: the trajectory of a rank that owns rows [3072, 4096) of a global
-    batch, checked against the oracle on the noise rows of exactly those global indices."""
-    from gmvae_amd import _lib as L
+# ------------------------------------------------------------------------- the data-parallel step on every schedule
+# dp_step_impl (csrc/gmvae_hip.hip) composes run_step with one of three optimizer tails behind the RCCL all-reduce: adam_tiles
+# (mega2's sizes), adam_tf_img (the other mega shapes: the Adam launch scatters the next step's weight images, and steps
+# 2..n of a graph run the first layer inside mega_fwd_bwd from them) or, without the scatter, adam_tf_step.  With a one-rank
+# communicator the all-reduce is the identity, so every DP trajectory has an exact fp64 reference.
+#   trace:  what GMVAE_TRACE=1 prints for EVERY mega_fwd_bwd call of the captured DP graph, (first_layer_inside,
+#           workgroups_per_panel, specialised); None where the step does not take the mega schedule at all (no line), and
+#           `sched` (gmvae_step_schedule) names the schedule it takes instead.
+#   single: the DP graph runs the same arithmetic in the same order as the single-device train graph of the same sizes
+#           (capture_train_step without all_reduce), so the two must agree bit for bit; False: the reason is in the comment.
+DP_CASES = [
+    # branch, model, D, L, K, hidden, S, B, n, seed, rank, env, safe, trace, sched, single
+    # BASELINE configs[2]: mega3_step in DP form (fuse_pending through a.dp_images at B = 1024: gradients only), the all-reduce,
+    # adam_tiles (mega2_ok).  The rank of 8 that owns rows [3072, 4096) of the global batch.  single: adam_tiles is the
+    # single-device mega3_step's optimizer epilogue moved behind the all-reduce (same tiles, adam_update, alpha_t and scale)
+    ("mega3+adam_tiles", "gmvae", 784, 64, 10, (64,), 1, 1024, 3, 8, 3, {}, False, (1, 4, 1), None, True),
+    # mega2_fwd_bwd + the weight-gradient tiles (B != 1024: no fuse_pending; a ragged last panel, an uneven shard), adam_tiles.
+    # single: the single device's dw_adam runs the same tiles with alpha_t from mega2_fwd_bwd (the same fp64 form)
+    ("mega2+adam_tiles-ragged", "gmvae", 784, 64, 10, (64,), 1, 1000, 3, 11, 5, {}, False, (1, 4, 1), None, True),
+    # GMVAE_NO_FL=1 (what the two-rank gloo children run): no scatter -> split-K first layer + aux, mega_fwd_bwd<FLT = 0>,
+    # finalize_grads, all-reduce, adam_tf_step.  single (here and under the safe schedule): the single device runs the same
+    # launches and applies the same adam_update to the same slab sums inside finalize_adam
+    ("noscatter-nofl", "gmvae", 784, 64, 10, (64,), 1, 1024, 3, 11, 1, {"GMVAE_NO_FL": "1"}, False, (0, 4, 1), None, True),
+    # use_safe_schedule(): sched_safe -> no scatter, one workgroup per panel
+    ("noscatter-safe", "gmvae", 784, 64, 10, (64,), 1, 1024, 3, 12, 6, {}, True, (0, 1, 1), None, True),
+    # the generic mega instance (L = 16): adam_tf_img scatters img_m / dimg, steps 2..n run the first layer from them (imgs_ready).
+    # Not single: without mega2 the single device's dw_adam computes alpha_t in fp32 (-expm1f form), adam_tf_img in fp64
+    ("mega-generic+adam_tf_img", "gmvae", 784, 16, 10, (64,), 1, 96, 3, 11, 2, {}, False, (1, 4, 0), None, False),
+    # BASELINE configs[0]: mega2v_fwd_bwd<0, 2, 1> (mega2v_ok: seven workgroups per panel), adam_tf_img into the MV0 images.
+    # single: the single device's mega3v_step runs the same per-row part and tiles, and the same update with the fp64 alpha_t
+    ("mega2v+adam_tf_img", "vae", 784, 2, 1, (64,), 1, 100, 4, 13, 7, {}, False, (1, 7, 1), None, True),
+    # the generic VAE mega instance (not single: alpha_t as for the generic GMVAE instance)
+    ("mega-vae-generic+adam_tf_img", "vae", 784, 8, 1, (64,), 1, 64, 3, 11, 4, {}, False, (1, 4, 0), None, False),
+    # BASELINE configs[1]: dp_step_impl never scatters for VAE_GMP (its prior's gradients are per-panel partials) -> split-K
+    # first layer, mega_fwd_bwd with seven workgroups per panel (mega2v_kind 2), finalize_grads, adam_tf_step.  Not single: the
+    # single device runs the first layer inside mega3v_step
+    ("noscatter-vae_gmp", "vae_gmp", 784, 64, 10, (64,), 1, 256, 3, 11, 0, {}, False, (0, 7, 1), None, False),
+    # skinny_ok (one hidden layer, a multiple of 64 wide, S = 1, B <= 4096): bin/run_train.sh's sizes, and VAE_GMP at H = 512.
+    # Not single: the single device's W launch applies Adam on its accumulators with alpha_t in fp32 (-expm1f form)
+    ("skinny", "gmvae", 784, 128, 10, (512,), 1, 64, 3, 11, 7, {}, False, None, "skinny", False),
+    ("skinny-vae_gmp", "vae_gmp", 784, 64, 10, (512,), 1, 256, 3, 11, 1, {}, False, None, "skinny", False),
+    # the general schedule: two hidden layers (neither mega_shape nor skinny_shape).  single (the three general cases): the single
+    # device's finalize_grads applies the same adam_update (fp64 alpha_t, 1 / count) to the same slab sums as adam_tf_step
+    ("general", "vae", 784, 8, 1, (96, 96), 1, 48, 3, 11, 2, {}, False, None, "general", True),
+    # planes_ok: IWAE rows R = B*S = 256 (a multiple of 128), D % 128 = 0, a 128-wide top decoder layer, forced from 128 rows as
+    # test_plane_gemms_inside_the_step does (the shape of BASELINE configs[4]'s path)
+    ("general+planes-S4", "gmvae", 256, 64, 10, (128,), 4, 64, 3, 11, 3, {"GMVAE_PLANES_MINROWS": "128"}, False, None,
+     "general+planes", True),
+    # S > 1 without the planes (D = 300: no plane tiles), L and K not multiples of 4
+    ("general-S3", "gmvae", 300, 6, 7, (40,), 3, 24, 3, 11, 5, {}, False, None, "general", True),
+]
+
+
+def _trace_lines(capfd):
+    """The mega_fwd_bwd lines GMVAE_TRACE=1 printed to stderr since the last call: [(first_layer_inside, workgroups_per_panel,
+    specialised)]."""
+    import re
+    err = capfd.readouterr().err
+    pat = r"mega_fwd_bwd: model \d+ B \d+ first_layer_inside (\d+) workgroups_per_panel (\d+) specialised (\d+)"
+    return [tuple(int(v) for v in m.groups()) for m in re.finditer(pat, err)]
+
+
+def _dp_engine(model, D, Lz, K, hidden, S, seed, rank, safe, rccl=True):
     from gmvae_amd.engine import Engine
-    B, n = 1024, 3
-    d = O.Dims(D=784, L=64, K=10, hidden=(64,))
-    e = Engine("gmvae", 784, 64, 10, [64], random_seed=8)
-    e.rank = 3                                    # as on rank 3 of 8: row0 = 3 * B enters the Philox counters only
-    flat0 = e.params.detach().cpu().numpy()
-    xs = (np.random.default_rng(6).random((n, B, 784)) < 0.87).astype(np.uint8)
-    e.enable_rccl()
-    sx, replay = e.capture_train_step(B, lr=LR, all_reduce=True, n_steps=n)
-    assert e.dp_mode == "rccl-in-hipgraph"
-    sx.copy_(torch.from_numpy(xs).cuda())
-    replay()
+    e = Engine(model, D, Lz, K, list(hidden), n_samples=S, random_seed=seed)
+    e.rank = rank                       # as on rank `rank` of a larger world: row0 = rank * B enters the Philox counters only
+    if safe:
+        e.use_safe_schedule()
+    if rccl:
+        e.enable_rccl()
+    return e
+
+
+def _release(engines):
+    """Destroy the engines' graphs, then their one-rank communicators."""
+    from gmvae_amd import _lib as L
     torch.cuda.synchronize()
-    assert e.handoff_timeouts() == 0
-    flat_ref, Cc, g, gs = _oracle_trajectory(L, O.MODEL_GMVAE, d, flat0, xs, e.noise_seed, row_base=3 * B)
-    _compare_last_step(O.MODEL_GMVAE, d, e, B, Cc, g)
-    _compare_params(O.MODEL_GMVAE, d, e, flat_ref, gs, n, "dp-world1")
+    for e in engines:
+        e.drop_graphs()
+        if getattr(e, "_comm", None):
+            L.check(L.lib.gmvae_comm_destroy(e._comm), "gmvae_comm_destroy")
+            e._comm = None
+
+
+def _at_device(L, mid, d, x, seed, step, row_base, pre, masks):
+    """(C, g) of the fp64 oracle at the device's own parameters `pre` before step `step`, with the device's ReLU masks."""
+    eps, u = _noise(L, x.shape[0] * d.S, d.L, d.K, row_base * d.S, seed, step, mid == O.MODEL_GMVAE)
+    C2, g2 = O.loss_and_grads(mid, d, O.unpack(mid, d, pre), x, eps, u, np.float64, relu_masks=masks)
+    return C2, O.pack(mid, d, g2, np.float64)
+
+
+def _state(e):
+    return (e.params.detach().clone(), e.m.clone(), e.v.clone(), e.grads.clone())
+
+
+def _bit_equal(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def _step_one_at_a_time(e, step, xd, B, mid, d):
+    """Runs step(xd[t]) for every t; returns the device's parameters before each step and the ReLU masks of each step."""
+    pre, masks = [], []
+    for t in range(xd.shape[0]):
+        pre.append(e.params.detach().cpu().numpy().astype(np.float64))
+        step(xd[t])
+        torch.cuda.synchronize()
+        masks.append(_device_masks(e, mid, d, B))
+    return pre, masks
+
+
+def dp_trajectory_case(capfd, monkeypatch, branch, model, D, Lz, K, hidden, S, B, n, seed, rank, env, safe, trace, sched, single):
+    """The DP twin of trajectory_case: one launch of an n-step DP graph (RCCL all-reduce captured inside) against n oracle
+    steps on the noise of global rows rank*B .., with the ReLU masks and parameters of a second engine that steps the same
+    batches through n launches of a ONE-step DP graph (bit for bit the same), the per-step tails of the graph against the
+    oracle's per-step loss terms, and a third engine that takes the same steps through eager dp_step."""
+    from gmvae_amd import _lib as L
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("GMVAE_TRACE", "1")
+    mid = O.MODEL_NAMES[model]
+    d = O.Dims(D=D, L=Lz, K=K, hidden=hidden, S=S)
+    tag = f"dp-{branch}-{model}-L{Lz}-H{'x'.join(map(str, hidden))}-S{S}-B{B}-r{rank}-seed{seed}"
+    xs = (np.random.default_rng(B + rank).random((n, B, D)) < 0.87).astype(np.uint8)
+    xd = torch.from_numpy(xs).cuda()
+    scatter = trace is not None and trace[0] == 1
+    engines = []
+    try:
+        e = _dp_engine(model, D, Lz, K, hidden, S, seed, rank, safe)
+        engines.append(e)
+        flat0 = e.params.detach().cpu().numpy()
+        if sched is not None:
+            assert L.step_schedule(e.dims(B), e.model) == sched, tag
+        capfd.readouterr()
+        sx, replay = e.capture_train_step(B, lr=LR, all_reduce=True, n_steps=n)
+        assert e.dp_mode == "rccl-in-hipgraph", f"{tag}: the DP graph's capture was refused ({e.dp_mode})"
+        got = _trace_lines(capfd)
+        # the scatter branches: step 1 builds the images (img_build), steps 2..n take what the previous adam_tf_img / adam_tiles left
+        assert got == ([trace] * n if trace else []), (tag, got)
+        sx.copy_(xd)
+        replay()
+        torch.cuda.synchronize()
+        assert e.handoff_timeouts() == 0 and e.global_step == n and int(e.step_dev[0].item()) == n, tag
+        tail_log = replay.tail_log.cpu().numpy().astype(np.float64)
+        graph = _state(e)
+
+        e1 = _dp_engine(model, D, Lz, K, hidden, S, seed, rank, safe)
+        engines.append(e1)
+        sx1, replay1 = e1.capture_train_step(B, lr=LR, all_reduce=True, n_steps=1)
+        assert e1.dp_mode == "rccl-in-hipgraph" and _trace_lines(capfd) == ([trace] if trace else []), tag
+
+        def one(xb):
+            sx1.copy_(xb)
+            replay1()
+        pre, masks = _step_one_at_a_time(e1, one, xd, B, mid, d)
+        assert e1.handoff_timeouts() == 0 and int(e1.step_dev[0].item()) == n
+        assert _bit_equal(graph[:3], _state(e1)[:3]), f"{tag}: n launches of a 1-step DP graph and one launch of an n-step DP graph differ"
+
+        terms = []
+        row_base = rank * B
+        flat_ref, Cc, g, gs = _oracle_trajectory(L, mid, d, flat0, xs, e.noise_seed, row_base=row_base,
+                                                 masks_of_step=lambda t: masks[t], params_of_step=lambda t: pre[t], tag=tag,
+                                                 terms=terms)
+        at = _at_device(L, mid, d, xs[n - 1], e.noise_seed, n - 1, row_base, pre[n - 1], masks[n - 1])
+        _compare_last_step(mid, d, e, B, Cc, g, at_device=at, tag=tag)
+        _compare_params(mid, d, e, flat_ref, gs, n, tag)
+        for t in range(n):
+            _compare_tail(tail_log[t], B, terms[t], f"{tag} tail_log[{t}]")
+
+        # eager dp_step (the rccl-eager-c fallback of capture_train_step): never scatters -- split-K first layer, adam_tf_step
+        e2 = _dp_engine(model, D, Lz, K, hidden, S, seed, rank, safe)
+        engines.append(e2)
+        pre2, masks2 = _step_one_at_a_time(e2, lambda xb: e2.dp_step(xb, LR), xd, B, mid, d)
+        assert e2.handoff_timeouts() == 0 and e2.global_step == n and int(e2.step_dev[0].item()) == n
+        assert _trace_lines(capfd) == ([(0,) + tuple(trace[1:])] * n if trace else []), tag
+        if not scatter:
+            # the no-scatter branch: the graph captured exactly the launches dp_step enqueues
+            assert _bit_equal(graph, _state(e2)), f"{tag}: eager dp_step and the DP graph differ"
+        else:
+            # the scatter branches: the graph's first layer runs inside the launch and its optimizer tail is adam_tiles /
+            # adam_tf_img, eager's is the split-K first layer and adam_tf_step (other summation orders): its own trajectory
+            flat2, Cc2, g2, gs2 = _oracle_trajectory(L, mid, d, flat0, xs, e.noise_seed, row_base=row_base,
+                                                     masks_of_step=lambda t: masks2[t], params_of_step=lambda t: pre2[t],
+                                                     tag=tag + "-eager")
+            at2 = _at_device(L, mid, d, xs[n - 1], e.noise_seed, n - 1, row_base, pre2[n - 1], masks2[n - 1])
+            _compare_last_step(mid, d, e2, B, Cc2, g2, at_device=at2, tag=tag + "-eager")
+            _compare_params(mid, d, e2, flat2, gs2, n, tag + "-eager")
+
+        e3 = _dp_engine(model, D, Lz, K, hidden, S, seed, rank, safe, rccl=False)
+        engines.append(e3)
+        sx3, replay3 = e3.capture_train_step(B, lr=LR, n_steps=n)
+        sx3.copy_(xd)
+        replay3()
+        torch.cuda.synchronize()
+        _trace_lines(capfd)
+        same = _bit_equal(graph, _state(e3))
+        print(f"\n[dp] {tag}: single-device graph bit-equal {same}")
+        if single:
+            assert same, f"{tag}: the DP graph and the single-device graph run the same arithmetic but differ"
+    finally:
+        _release(engines)
+
+
+@pytest.mark.parametrize("case", DP_CASES, ids=[c[0] + f"-{c[1]}-L{c[3]}-H{'x'.join(map(str, c[5]))}-S{c[6]}-B{c[7]}" for c in DP_CASES])
+def test_dp_graph_world1_matches_oracle_trajectory(case, capfd, monkeypatch):
+    """The data-parallel train graph (RCCL all-reduce captured inside) with a one-rank communicator and a non-zero global row
+    offset on every branch of dp_step_impl, checked against the oracle on the noise rows of exactly those global indices."""
+    dp_trajectory_case(capfd, monkeypatch, *case)
+
+
+@pytest.mark.parametrize("model,Lz,K,B,seed,rank", [("vae", 2, 1, 100, 12, 5), ("gmvae", 64, 10, 1024, 9, 2)],
+                         ids=["configs0-mega2v+adam_tf_img", "configs2-mega3+adam_tiles"])
+def test_dp_graph_eager_step_graph_continues_the_trajectory(model, Lz, K, B, seed, rank):
+    """An n-step DP graph, one eager dp_step, the graph again = 2n + 1 oracle steps: the device step counter (Philox step,
+    Adam's t) and the weight images carry over both launch boundaries.  A twin engine takes the same steps one launch at a
+    time (one-step DP graph, the same eager step) for the masks and parameters of every step, bit for bit the same."""
+    from gmvae_amd import _lib as L
+    n, D = 3, 784
+    mid = O.MODEL_NAMES[model]
+    d = O.Dims(D=D, L=Lz, K=K, hidden=(64,))
+    tag = f"dp-boundary-{model}-L{Lz}-B{B}"
+    xs = (np.random.default_rng(B + 1).random((2 * n + 1, B, D)) < 0.87).astype(np.uint8)
+    xd = torch.from_numpy(xs).cuda()
+    engines = []
+    try:
+        e = _dp_engine(model, D, Lz, K, (64,), 1, seed, rank, False)
+        engines.append(e)
+        flat0 = e.params.detach().cpu().numpy()
+        sx, replay = e.capture_train_step(B, lr=LR, all_reduce=True, n_steps=n)
+        assert e.dp_mode == "rccl-in-hipgraph"
+        sx.copy_(xd[:n])
+        replay()
+        e.dp_step(xd[n], LR)
+        sx.copy_(xd[n + 1:])
+        replay()
+        torch.cuda.synchronize()
+        assert e.handoff_timeouts() == 0 and e.global_step == 2 * n + 1 and int(e.step_dev[0].item()) == 2 * n + 1
+        tail_log = replay.tail_log.cpu().numpy().astype(np.float64)
+
+        e1 = _dp_engine(model, D, Lz, K, (64,), 1, seed, rank, False)
+        engines.append(e1)
+        sx1, replay1 = e1.capture_train_step(B, lr=LR, all_reduce=True, n_steps=1)
+
+        def one(t, xb):
+            if t == n:
+                e1.dp_step(xb, LR)
+            else:
+                sx1.copy_(xb)
+                replay1()
+        steps = iter(range(2 * n + 1))
+        pre, masks = _step_one_at_a_time(e1, lambda xb: one(next(steps), xb), xd, B, mid, d)
+        assert e1.handoff_timeouts() == 0 and int(e1.step_dev[0].item()) == 2 * n + 1
+        assert _bit_equal(_state(e)[:3], _state(e1)[:3]), f"{tag}: the twin that steps one launch at a time differs"
+
+        terms = []
+        flat_ref, Cc, g, gs = _oracle_trajectory(L, mid, d, flat0, xs, e.noise_seed, row_base=rank * B,
+                                                 masks_of_step=lambda t: masks[t], params_of_step=lambda t: pre[t], tag=tag,
+                                                 terms=terms)
+        at = _at_device(L, mid, d, xs[2 * n], e.noise_seed, 2 * n, rank * B, pre[2 * n], masks[2 * n])
+        _compare_last_step(mid, d, e, B, Cc, g, at_device=at, tag=tag)
+        _compare_params(mid, d, e, flat_ref, gs, 2 * n + 1, tag)
+        for t in range(n):                                   # the second launch's tails: steps n + 1 .. 2n
+            _compare_tail(tail_log[t], B, terms[n + 1 + t], f"{tag} tail_log[{t}]")
+    finally:
+        _release(engines)
 
 
 EAGER = [
