@@ -34,6 +34,7 @@
 #include "rowsws.hpp"
 #include "evalf.hpp"
 #include "iwbound.hpp"
+#include "ymarg.hpp"
 
 using namespace gmvae;
 
@@ -51,6 +52,9 @@ constexpr int kSkNs1 = 4;        // slabs of the skinny schedule's first layer (
 // GmvaeDims::sched_flags & GMVAE_SCHED_SAFE: the schedules in which no workgroup waits for another of its own launch
 // (one workgroup per panel, the first layer as a launch of its own) -- what a caller degrades to after a hand-off timeout
 static bool sched_safe(const GmvaeDims& d) { return (d.sched_flags & GMVAE_SCHED_SAFE) != 0; }
+// GMVAE_OBJ_MARGINAL_Y (ymarg.hpp): y summed out over its K values -- K rows per batch row where the Gumbel objective has S
+static bool marginal_y(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y) != 0; }
+static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K : d.S; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -142,6 +146,10 @@ static int check_dims(const GmvaeDims* d, int model) {
   if (d->gen_bias_vec && (reinterpret_cast<uintptr_t>(d->gen_bias_vec) & 3)) return GMVAE_E_ALIGN;
   if ((long long)d->B * d->S > (1LL << 30)) return GMVAE_E_DIMS;
   if (d->hidden_act < GMVAE_ACT_RELU || d->hidden_act > GMVAE_ACT_ELU) return GMVAE_E_DIMS;
+  if (d->sched_flags & GMVAE_OBJ_MARGINAL_Y) {
+    if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
+    if (d->S != 1 || (long long)d->B * d->K > (1LL << 30)) return GMVAE_E_DIMS;
+  }
   return 0;
 }
 
@@ -220,6 +228,7 @@ static int fwd_splits(int D) {
 // (the *_shape predicates read the dims only: carve() sizes the workspace with them, so that its layout never depends on an
 //  environment switch; the *_ok forms add the switches and choose the schedule)
 static bool mega_shape(const GmvaeDims& d, int model) {
+  if (marginal_y(d)) return false;             // (the enumerated objective runs the general schedule only)
   if (d.n_hidden != 1 || d.S != 1 || d.D % 16 || d.hidden_act != GMVAE_ACT_RELU) return false;
   if (d.gen_bias_vec) return false;            // the vector bias_init is applied by the grouped GEMM's epilogue (Problem::bias2)
   const int H = d.hidden[0];
@@ -244,6 +253,7 @@ static bool mega2_ok(const GmvaeDims& d, int model) {
 // mega2v_fwd_bwd (mega2v.hpp): the same design for the VAE family at small batches, SEVEN workgroups per panel -- the plain
 // VAE at latent 2 (BASELINE configs[0]) and VAE_GMP at latent 64, K = 10 (configs[1]), hidden 64, D = 784
 static int mega2v_kind(const GmvaeDims& d, int model) {       // 0: not these sizes; 1: VAE L = 2; 2: VAE_GMP L = 64 K = 10
+  if (marginal_y(d)) return 0;
   if (d.n_hidden != 1 || d.hidden[0] != 64 || d.D != 784 || d.S != 1 || d.gen_bias_vec) return 0;
   if ((d.B + kPanel - 1) / kPanel * 7 > 256) return 0;
   if (model == GMVAE_MODEL_VAE && d.L == 2) return 1;
@@ -263,7 +273,7 @@ constexpr int kSkMaxB = 4096;       // hard bound of the skinny schedule's batch
 static bool skinny_shape(const GmvaeDims& d, int model) {
   // GMVAE; the VAE with the standard-normal prior (no y path: eight launches); VAE_GMP (the learned mixture prior is not
   // column-local: its log-density, its share of dz and its variables' gradients stay three row kernels: eleven launches)
-  if (d.n_hidden != 1 || d.S != 1 || d.hidden_act != GMVAE_ACT_RELU) return false;
+  if (marginal_y(d) || d.n_hidden != 1 || d.S != 1 || d.hidden_act != GMVAE_ACT_RELU) return false;
   const int H = d.hidden[0];
   // measured against the general schedule at H = 128 / 256 / 512, L = 128 (tools/sk_sweep.py, one box): 2.9x faster at B = 32..64,
   // 2.4 - 2.6x at 256, 1.9 - 2.1x at 512, 1.8 - 1.9x at 1024, 1.5 - 1.6x at 2048, 1.2 - 1.4x at 4096 (round 4: the forms for
@@ -281,7 +291,7 @@ static bool skinny_ok(const GmvaeDims& d, int model) {
   return skinny_shape(d, model) && d.B <= maxb;
 }
 static bool fused_shape(const GmvaeDims& d, int model) {
-  if (model != GMVAE_MODEL_GMVAE || d.n_hidden != 1 || d.S != 1 || d.hidden_act != GMVAE_ACT_RELU) return false;
+  if (model != GMVAE_MODEL_GMVAE || marginal_y(d) || d.n_hidden != 1 || d.S != 1 || d.hidden_act != GMVAE_ACT_RELU) return false;
   const int H = d.hidden[0];
   if (H % 16 || H > 64 || d.L % 8 || d.L > 128 || d.K > 64) return false;
   const int f = fwd_lay(H, d.L, d.K).total, b = bwd_lay(H, d.L, d.K).total;
@@ -295,6 +305,7 @@ static bool fused_ok(const GmvaeDims& d, int model) {
 
 // evalf_rows (evalf.hpp): the forward-only pass of the GMVAE at the reference's default sizes, any batch, any number of samples
 static bool evalf_shape(const GmvaeDims& d, int model) {
+  if (marginal_y(d)) return false;
   if (d.n_hidden != 1 || d.hidden[0] != EV::H || d.D != EV::D || d.hidden_act != GMVAE_ACT_RELU || d.gen_bias_vec) return false;
   if (model == GMVAE_MODEL_GMVAE) return d.L == EV::L && d.K == EV::K;
   if (model == GMVAE_MODEL_VAE) return d.L == 2 || d.L == 64;          // (evalf_rows_v: BASELINE configs[0]'s latent size, and 64)
@@ -338,7 +349,7 @@ static bool planes_ok(const GmvaeDims& d, const Layout& L) {
   const char* e = getenv("GMVAE_NO_PLANES");
   if (e && atoi(e)) return false;
   if (d.hidden_act != GMVAE_ACT_RELU) return false;     // (the plane producers' epilogues are the ReLU ones)
-  const long long R = (long long)d.B * d.S;
+  const long long R = (long long)d.B * rows_per_x(d);
   const int Ht = L.dec.dim[L.dec.nl - 1];
   long long minr = 4096;
   if (const char* m = getenv("GMVAE_PLANES_MINROWS")) minr = atoll(m);     // (tests: the plane path at sizes the oracle covers)
@@ -355,7 +366,7 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     off += (nfloats * 4 + 255) / 256 * 256;
     return p;
   };
-  const uint64_t B = d.B, R = (uint64_t)d.B * d.S, K = d.K, Lz = d.L, D = d.D;
+  const uint64_t B = d.B, R = (uint64_t)d.B * rows_per_x(d), K = d.K, Lz = d.L, D = d.D;
   int maxh = 1;
   for (int i = 0; i < d.n_hidden; ++i) maxh = d.hidden[i] > maxh ? d.hidden[i] : maxh;
   memset(&w, 0, sizeof(w));
@@ -434,7 +445,7 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
   }
   w.dz = take(R * Lz);
   w.dqp = take(R * 2 * Lz);
-  if (d.S > 1) {
+  if (rows_per_x(d) > 1 || marginal_y(d)) {
     w.pb = take(B * 4);
     w.lw64 = reinterpret_cast<double*>(take(2 * R));
     if (model == GMVAE_MODEL_GMVAE) w.dsum = take(B * maxh);
@@ -495,7 +506,7 @@ static bool fwd_pairs_ok(const GmvaeDims& d, const Layout& L) {
   const char* x = getenv("GMVAE_PLANES_EXACT");
   if (x && atoi(x)) return false;
   if (d.hidden_act != GMVAE_ACT_RELU || L.dec.nl < 2) return false;
-  const long long R = (long long)d.B * d.S;
+  const long long R = (long long)d.B * rows_per_x(d);
   const int Ht = L.dec.dim[L.dec.nl - 1];
   long long minr = 8192;
   if (const char* m = getenv("GMVAE_PLANES_MINROWS")) minr = atoll(m);
@@ -1938,7 +1949,9 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   build_layout(d, model, L);
   WS w;
   carve(d, model, L, a.workspace, w);
-  const int B = d.B, S = d.S, R = B * S, K = d.K, Lz = d.L, D = d.D;
+  // marginal: the general schedule's S = K path with y = e_k on row b K + k (ymarg.hpp)
+  const bool marg = marginal_y(d);
+  const int B = d.B, S = rows_per_x(d), R = B * S, K = d.K, Lz = d.L, D = d.D;
   const float* P = a.params;
   const bool gm = model == GMVAE_MODEL_GMVAE;
   const float c = d.raw_sigma_bias, smin = d.sigma_min;
@@ -1956,7 +1969,7 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   const float* eps = a.eps;
   const float* u = a.u;
   float* ge = eps ? nullptr : w.eps;
-  float* gu = (gm && !u) ? w.u : nullptr;
+  float* gu = (gm && !u && !marg) ? w.u : nullptr;
   if (ge) eps = ge;
   if (gu) u = gu;
   tl_hact = 1 + d.hidden_act;                  // (every Problem built below for this step: its epilogue's activation kind)
@@ -2080,10 +2093,18 @@ static int run_step(Ctx& cx, const StepArgs& a) {
     launch_group(cx, g, gm ? "fwd_enc_y" : "fwd_enc");
   }
   if (gm) {
+    const NetL& G = L.encg;
+    if (marg) {
+      // y = e_k: encoder_gmm's first layer is a gather-add of one weight row, the prior head one of K rows (no GEMM)
+      const long long n = (long long)R * (G.dim[1] + 2 * Lz + K);
+      hipLaunchKernelGGL(ymarg_y_fwd, dim3(grid_for(n, 256, 4 * device_cus())), dim3(256), 0, st, w.gx,
+                         P + G.w[0] + (uint64_t)D * G.dim[1], P + G.b[0], (G.nl == 1) ? w.qp : w.hg[1], G.dim[1],
+                         G.nl > 1 ? tl_hact : 0, P + L.prior.w[0], P + L.prior.b[0], w.pp, 2 * Lz, w.y, B, K);
+      rowk(cx, "ymarg_y_layers");
+    } else {
     hipLaunchKernelGGL(y_head_fwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.logits, u, w.y, w.nent, R, S, K,
                        1.f / d.temperature);
     rowk(cx, "y_head_fwd");
-    const NetL& G = L.encg;
     if (rws_on && K == 64 && G.dim[1] % 64 == 0 && (2 * Lz) % 64 == 0 && rws_fits((G.dim[1] + 2 * Lz) / 64)) {
       RwsArgs ra;
       memset(&ra, 0, sizeof(ra));
@@ -2126,6 +2147,7 @@ static int run_step(Ctx& cx, const StepArgs& a) {
       g.add(p);
       g.add(p_nn(w.y, false, K, P + L.prior.w[0], 2 * Lz, R, 2 * Lz, K, w.pp, 2 * Lz, P + L.prior.b[0], false));
       launch_group(cx, g, "fwd_y_layers");
+    }
     }
     for (int i = 1; i < G.nl; ++i) {
       float* const out = (i == G.nl - 1) ? w.qp : w.hg[i + 1];
@@ -2246,8 +2268,12 @@ static int run_step(Ctx& cx, const StepArgs& a) {
     }
   }
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
-  const float* rwS = (S > 1 && a.backward) ? w.rw : nullptr;
-  if (S > 1 && S <= 64) {       // the row terms and the IWAE groups in one launch (a wave per batch row)
+  const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
+  if (marg) {                   // per-example terms over the K rows of each batch row: q(k|x), rw = q, the closed-form dlogits
+    hipLaunchKernelGGL(ymarg_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
+                       w.logw, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.dlogits, w.nent, w.pb, B, K);
+    rowk(cx, "ymarg_rows");
+  } else if (S > 1 && S <= 64) {       // the row terms and the IWAE groups in one launch (a wave per batch row)
     hipLaunchKernelGGL(iwae_rows_terms, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp,
                        gm ? w.nent : (const float*)nullptr, w.logpx, w.logw, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.pb, B, S);
     rowk(cx, "iwae_rows_terms");
@@ -2256,14 +2282,14 @@ static int run_step(Ctx& cx, const StepArgs& a) {
                        gm ? w.nent : (const float*)nullptr, S, w.logpx, w.logw, a.row_terms, R, S > 1 ? w.lw64 : (double*)nullptr);
     rowk(cx, "row_terms");
   }
-  if (S > 64) {
+  if (S > 64 && !marg) {
     hipLaunchKernelGGL(iwae_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.lw64, w.logpx, w.logq, w.logp,
                        a.backward ? w.rw : (float*)nullptr, w.pb, B, S);
     rowk(cx, "iwae_rows");
   }
   hipLaunchKernelGGL(loss_tail, dim3(1), dim3(1024), 0, st, w.logw, w.logpx, w.logq, w.logp,
-                     gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, S, a.step_dev,
-                     S > 1 ? w.pb : (const float*)nullptr);
+                     gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
+                     (S > 1 || marg) ? w.pb : (const float*)nullptr);
   rowk(cx, "loss_tail");
   if (a.z_out) hipMemcpyAsync(a.z_out, w.z, (size_t)R * Lz * 4, hipMemcpyDeviceToDevice, st);
   if (a.y_out && gm) hipMemcpyAsync(a.y_out, w.y, (size_t)R * K * 4, hipMemcpyDeviceToDevice, st);
@@ -2406,6 +2432,25 @@ static int run_step(Ctx& cx, const StepArgs& a) {
       const int nsx = (S > 1 && sxb.n + 2 <= kSlabRanges) ? NSB : NS;
       if (nsx != NS) { brange(G.w[0], (uint64_t)D * G.dim[1], nsx); brange(G.b[0], G.dim[1], nsx); }
       g.add(p_tn(a.x, true, D, 1, dg, G.dim[1], D, G.dim[1], B, sl + G.w[0], sl + G.b[0], nsx, PP, nullptr));
+      if (marg) {
+        // y = e_k: the y rows of the first layer's weight and the prior's weight take segmented column sums over the batch
+        // (ymarg_dw, slabs as the split-K GEMMs write them); no data gradient of y
+        launch_group(cx, g, "bwd_enc_gmm_l0");
+        int nsy = small_ns((long long)K * G.dim[1]);
+        if (((uint64_t)D * G.dim[1]) % 4) nsy = nsx;      // (the float4 the x and y rows share is summed over the x rows' slabs)
+        if (nsy != NS) brange(G.w[0] + (uint64_t)D * G.dim[1], (uint64_t)K * G.dim[1], nsy);
+        const int nsp = small_ns((long long)K * 2 * Lz);
+        if (nsp != NS) { brange(L.prior.w[0], (uint64_t)K * 2 * Lz, nsp); brange(L.prior.b[0], 2 * Lz, nsp); }
+        YmDwArgs ya;
+        memset(&ya, 0, sizeof(ya));
+        ya.np = 2; ya.B = B; ya.K = K; ya.slab_stride = PP;
+        ya.p[0].d = dcur; ya.p[0].dw = sl + G.w[0] + (uint64_t)D * G.dim[1]; ya.p[0].db = nullptr; ya.p[0].N = G.dim[1];
+        ya.p[0].ns = nsy; ya.p[0].blocks = nsy * ((G.dim[1] + 63) / 64);
+        ya.p[1].d = w.dpp; ya.p[1].dw = sl + L.prior.w[0]; ya.p[1].db = sl + L.prior.b[0]; ya.p[1].N = 2 * Lz;
+        ya.p[1].ns = nsp; ya.p[1].blocks = nsp * ((2 * Lz + 63) / 64);
+        hipLaunchKernelGGL(ymarg_dw, dim3((unsigned)(ya.p[0].blocks + ya.p[1].blocks)), dim3(256), 0, st, ya);
+        rowk(cx, "ymarg_dw");
+      } else {
       const int nsy = small_ns((long long)K * G.dim[1]);
       if (nsy != NS) brange(G.w[0] + (uint64_t)D * G.dim[1], (uint64_t)K * G.dim[1], nsy);
       g.add(p_tn(w.y, false, K, 1, dcur, G.dim[1], K, G.dim[1], R, sl + G.w[0] + (uint64_t)D * G.dim[1], nullptr, nsy,
@@ -2431,10 +2476,13 @@ static int run_step(Ctx& cx, const StepArgs& a) {
         ra.p[0].W2 = P + L.prior.w[0]; ra.p[0].ldw2 = 2 * Lz;
         launch_rws(ra, 2, "bwd_dy", G.dim[1] + 2 * Lz);
       }
+      }
     }
-    hipLaunchKernelGGL(y_head_bwd, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, w.y, w.dy, w.nent, w.dlogits, B,
-                       S, K, 1.f / d.temperature);
-    rowk(cx, "y_head_bwd");
+    if (!marg) {                  // (marginal: ymarg_rows left dlogits in closed form)
+      hipLaunchKernelGGL(y_head_bwd, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, w.y, w.dy, w.nent, w.dlogits, B,
+                         S, K, 1.f / d.temperature);
+      rowk(cx, "y_head_bwd");
+    }
     dcur = w.dlogits;
   } else {
     if (model == GMVAE_MODEL_VAE_GMP) {
@@ -2658,6 +2706,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
 
 int gmvae_iw_bound_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
   if (int e = check_dims(dims, model)) return e;
+  if (marginal_y(*dims)) return GMVAE_E_DIMS;
   if (!bytes) return GMVAE_E_NULL;
   Layout L;
   build_layout(*dims, model, L);
@@ -2671,6 +2720,7 @@ int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const flo
                    float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                    void* stream) {
   if (int e = check_dims(dims, model)) return e;
+  if (marginal_y(*dims)) return GMVAE_E_DIMS;                       // (the enumerated-y bound is not implemented)
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
   if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
@@ -3326,7 +3376,7 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s", nm, (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s", nm, marginal_y(d) ? "+marginal" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 

@@ -40,9 +40,18 @@ class _ElboFn(torch.autograd.Function):
 class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
-                 temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu"):
+                 temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
+                 y_inference: str = "gumbel"):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
-        that is added to the output of the fully connected network", e.g. the logit of the training-set mean)."""
+        that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
+        y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
+        "marginal": y summed out exactly over its K values (include/gmvae_hip.h GMVAE_OBJ_MARGINAL_Y).  Marginal steps have
+        B*K rows: eps is [B*K, L], u is not used, forward() returns rows / z / y of B*K rows; n_samples must be 1."""
+        if y_inference not in L.Y_INFERENCE:
+            raise ValueError(f"y_inference must be one of {L.Y_INFERENCE}, got {y_inference!r}")
+        if y_inference == "marginal" and (L.MODEL_IDS.get(model) != L.MODEL_GMVAE or int(n_samples) != 1):
+            raise ValueError("y_inference='marginal' needs the GMVAE model and n_samples=1 (y is enumerated over the K "
+                             "components instead of sampled)")
         self.device = L.require_gpu()
         # data parallel: this process's shard index.  Row b of a local batch of B rows is global row rank*B + b for the
         # Philox counters (GmvaeDims.row0), so G ranks draw the noise of ONE step on the global batch of G*B rows.
@@ -66,6 +75,9 @@ class Engine:
         if hidden_act not in L.ACTS:
             raise ValueError(f"hidden_act must be one of {sorted(L.ACTS)} (hidden_activation_fn, scripts/base.py:19), got {hidden_act!r}")
         self.hidden_act = hidden_act
+        self.y_inference = y_inference
+        self.marginal = y_inference == "marginal"
+        self.rows_per_x = self.K if self.marginal else self.S      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
         self.safe_schedule = False              # use_safe_schedule(): the schedules without mutual waits (per engine)
@@ -93,7 +105,8 @@ class Engine:
         """GmvaeDims for a local batch of B rows; row0 = global index of its first row (default rank * B)."""
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=self.S if S is None else S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
-                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | extra_flags, **self.hp)
+                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | (L.OBJ_MARGINAL_Y if self.marginal else 0)
+                           | extra_flags, **self.hp)
 
     def _params_state(self):
         """What identifies the parameter VALUES: torch's version counter of the buffer (in-place writes through torch) and the
@@ -220,6 +233,13 @@ class Engine:
             raise ValueError(f"expected [B,{self.D}] inputs, got {tuple(x.shape)}")
         return x
 
+    def _prep_u(self, u, rows):
+        if self.marginal:
+            if u is not None:
+                raise ValueError("y_inference='marginal' enumerates y: it takes no Gumbel noise u")
+            return None
+        return self._prep_noise(u, rows, self.K) if self.model == L.MODEL_GMVAE else None
+
     def _prep_noise(self, t, rows, cols):
         if t is None:
             return None
@@ -236,8 +256,8 @@ class Engine:
         x = self._prep_x(x)
         B = x.shape[0]
         d, ws = self._workspace(B, row0=row0)
-        eps = self._prep_noise(eps, B * self.S, self.Lz)
-        u = self._prep_noise(u, B * self.S, self.K) if self.model == L.MODEL_GMVAE else None
+        eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
+        u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
                               L.ptr(self.grads), L.ptr(ws), self.noise_seed, self.global_step,
                               L.ptr(self.step_dev) if use_step_dev else None, L.current_stream())
@@ -254,16 +274,18 @@ class Engine:
         x = self._prep_x(x)
         B = x.shape[0]
         S = self.S if n_samples is None else int(n_samples)
+        if self.marginal and S != 1:
+            raise ValueError("y_inference='marginal' enumerates y over the K components: n_samples must be 1")
         d, ws = self._workspace(B, S)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
         if self._eval_imgs.get((B, S)) == state:
             d = self.dims(B, S, extra_flags=L.SCHED_EVAL_IMAGES_VALID)
-        R = B * S
+        R = B * (self.K if self.marginal else S)
         eps = self._prep_noise(eps, R, self.Lz)
         gm = self.model == L.MODEL_GMVAE
-        u = self._prep_noise(u, R, self.K) if gm else None
+        u = self._prep_u(u, R)
         f32 = dict(dtype=torch.float32, device=self.device)
         o = dict(tail=torch.empty(L.TAIL, **f32), rows=torch.empty(R, 4, **f32), z=torch.empty(R, self.Lz, **f32),
                  y=torch.empty(R, self.K, **f32) if gm else None,
@@ -283,6 +305,9 @@ class Engine:
         (default: B * chunk near IW_CHUNK_ROWS, at most n_samples); the memory depends on B * chunk, not on n_samples.
         Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step), row0 defaulting to
         rank * B: the result does not depend on the chunk, the batch size or the sharding."""
+        if self.marginal:
+            raise ValueError("iw_bound: the importance-weighted bound is not available with y_inference='marginal' "
+                             "(it is the Gumbel objective's bound)")
         x = self._prep_x(x)
         if x.data_ptr() % 16:
             x = x.clone()

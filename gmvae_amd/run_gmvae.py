@@ -37,11 +37,26 @@ def build_parser():
     a("--iw_samples", type=int, default=0, help="eval: also report the importance-weighted bound at this many samples per "
       "example, streamed in chunks (Engine.iw_bound); 0 = off")
     a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples (default: ~51,200 rows per pass)")
+    a("--y_inference", default="gumbel", choices=["gumbel", "marginal"], help="gmvae: one Gumbel-softmax draw of y (the "
+      "reference) or y summed out exactly over the mixture components")
     return p
 
 
+def check_args(p, cfg):
+    """Flag combinations the marginal objective does not take (argument errors, before any device work)."""
+    if cfg.y_inference == "marginal":
+        if cfg.model != "gmvae":
+            p.error("--y_inference=marginal needs --model=gmvae")
+        if cfg.n_samples != 1:
+            p.error("--y_inference=marginal enumerates y: --n_samples must be 1")
+        if cfg.iw_samples:
+            p.error("--iw_samples is not available with --y_inference=marginal")
+    return cfg
+
+
 def main(argv=None):
-    cfg = build_parser().parse_args(argv)
+    p = build_parser()
+    cfg = check_args(p, p.parse_args(argv))
     return runners.run_train(cfg) if cfg.mode == "train" else runners.run_eval(cfg)
 
 

@@ -83,7 +83,8 @@ def create_model(config, data_dim):
     if config.model == "gmvae":
         return gmvae.create_gmvae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0,
-                                  random_seed=config.random_seed, n_samples=ns)
+                                  random_seed=config.random_seed, n_samples=ns,
+                                  y_inference=getattr(config, "y_inference", "gumbel"))
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
@@ -176,7 +177,8 @@ def _verify_launch(eng, snap, batches, g, lr):
     hp = dict(eng.hp)
     gb = eng.gen_bias_vec if eng.gen_bias_vec is not None else hp.pop("gen_bias_init")
     hp.pop("gen_bias_init", None)
-    sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0, **hp)
+    sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0,
+                y_inference=eng.y_inference, **hp)
     sh.rank, sh.noise_seed = eng.rank, eng.noise_seed
     with torch.no_grad():
         sh.params.copy_(p0); sh.m.copy_(m0); sh.v.copy_(v0)
@@ -378,7 +380,12 @@ def run_eval(config):
         n_batches += 1
         # z = model.transform(flat_inputs) (runners.py:274): the VAE's MEAN code (vae.py:108-114), the GMVAE's SAMPLED
         # code (gmvae.py:140-149) -- the forward pass's z is exactly that sample
-        codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
+        # (y enumerated: the code of the example's most probable component)
+        if config.model == "gmvae" and eng.marginal:
+            B = o["logits"].shape[0]
+            codes.append(o["z"].view(B, eng.K, eng.Lz)[torch.arange(B, device=eng.device), o["logits"].argmax(dim=1)])
+        else:
+            codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     if world > 1:

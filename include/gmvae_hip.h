@@ -81,7 +81,7 @@ typedef struct GmvaeDims {
    * output layer's epilogue; steps with a vector run the schedules whose decoder layer is a grouped-GEMM launch. */
   const float* gen_bias_vec;
   int32_t gen_bias_len;
-  /* ABI v4 -- schedule flags (the v3 `reserved_` word; 0 = the default schedules).  GMVAE_SCHED_SAFE: only schedules in which
+  /* ABI v4 -- schedule and objective flags (the v3 `reserved_` word; 0 = the default schedules).  GMVAE_SCHED_SAFE: only schedules in which
    * no workgroup waits for another workgroup of its own launch (one workgroup per 16-row panel, the first layer as a launch
    * of its own): slower (4 launches per step instead of 2), never stalling when something else holds part of the device.  A
    * caller sets it after a hand-off timeout (the workspace's error word) -- per call, not per process.  It changes neither
@@ -97,7 +97,18 @@ enum { GMVAE_SCHED_SAFE = 1,
        /* forward-only calls (gmvae_forward): the operand images a previous gmvae_forward left in THIS workspace were built from
         * the parameters as they still are (an evaluation walks a split batch by batch on fixed parameters): evalf_prep is skipped.
         * The caller vouches for it; gmvae_amd.Engine tracks every writer of its parameter buffer. */
-       GMVAE_SCHED_EVAL_IMAGES_VALID = 2 };
+       GMVAE_SCHED_EVAL_IMAGES_VALID = 2,
+       /* objective (GMVAE only, S == 1): y summed out exactly over its K values instead of one Gumbel-softmax draw --
+        *   L_b = sum_k q(k|x_b) [ -log p(x_b|z_bk) + log q(z_bk|x_b,k) - log p(z_bk|k) ] + sum_k q_bk ln q_bk,
+        *   z_bk = mu_q(x_b, e_k) + sigma_q(x_b, e_k) eps_bk.
+        * UNLIKE the schedule bits it changes sizes and the workspace: the sample-dependent tensors have R = B*K rows, row
+        * r = b*K + k with y_r = e_k; eps is [B*K, L] (NULL: Philox row (row0 + b)*K + k, gmvae_noise_fill's keying at
+        * row_base = row0*K), u is not used.  Tail: [0] sum_b L_b, [1] sum_b sum_k q_bk nll_bk, [2] the same of kl_bk, [3] sum_b
+        * nent_b, [4] B.  gmvae_forward: row_terms [B*K,4] = logpx, logq, logp, log w' = logpx + logp - logq (no nent term);
+        * z_out [B*K,L]; y_out [B*K,K] the one-hot rows; logits_out [B,K].  Takes the general schedule (gmvae_step_schedule:
+        * "general+marginal"); every entry point that runs a step honours it; gmvae_iw_bound refuses it (GMVAE_E_DIMS).
+        * GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS if S != 1 or B*K > 2^30. */
+       GMVAE_OBJ_MARGINAL_Y = 4 };
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -345,7 +356,7 @@ int gmvae_debug_sk_stamps(unsigned long long* host_out);
 int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
- * "fused" or "general", with "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
