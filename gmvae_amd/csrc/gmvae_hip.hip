@@ -54,7 +54,9 @@ constexpr int kSkNs1 = 4;        // slabs of the skinny schedule's first layer (
 static bool sched_safe(const GmvaeDims& d) { return (d.sched_flags & GMVAE_SCHED_SAFE) != 0; }
 // GMVAE_OBJ_MARGINAL_Y (ymarg.hpp): y summed out over its K values -- K rows per batch row where the Gumbel objective has S
 static bool marginal_y(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y) != 0; }
-static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K : d.S; }
+// (the public entry points take the bit at S == 1 only (check_dims); gmvae_iw_bound_enum_y runs its chunk of S samples as S K rows
+//  per batch row, row (b S + s) K + k)
+static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K * d.S : d.S; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -1949,8 +1951,9 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   build_layout(d, model, L);
   WS w;
   carve(d, model, L, a.workspace, w);
-  // marginal: the general schedule's S = K path with y = e_k on row b K + k (ymarg.hpp)
-  const bool marg = marginal_y(d);
+  // marginal: the general schedule's S = K path with y = e_k on row b K + k (ymarg.hpp); at d.S > 1 (only gmvae_iw_bound_enum_y's
+  // forward: S K rows per batch row, row (b d.S + s) K + k) the per-row terms alone, for iw_merge_enum
+  const bool marg = marginal_y(d), marg_iw = marg && d.S > 1;
   const int B = d.B, S = rows_per_x(d), R = B * S, K = d.K, Lz = d.L, D = d.D;
   const float* P = a.params;
   const bool gm = model == GMVAE_MODEL_GMVAE;
@@ -2099,7 +2102,8 @@ static int run_step(Ctx& cx, const StepArgs& a) {
       const long long n = (long long)R * (G.dim[1] + 2 * Lz + K);
       hipLaunchKernelGGL(ymarg_y_fwd, dim3(grid_for(n, 256, 4 * device_cus())), dim3(256), 0, st, w.gx,
                          P + G.w[0] + (uint64_t)D * G.dim[1], P + G.b[0], (G.nl == 1) ? w.qp : w.hg[1], G.dim[1],
-                         G.nl > 1 ? tl_hact : 0, P + L.prior.w[0], P + L.prior.b[0], w.pp, 2 * Lz, w.y, B, K);
+                         G.nl > 1 ? tl_hact : 0, P + L.prior.w[0], P + L.prior.b[0], w.pp, 2 * Lz,
+                         (marg_iw && !a.y_out) ? (float*)nullptr : w.y, B, K, S);
       rowk(cx, "ymarg_y_layers");
     } else {
     hipLaunchKernelGGL(y_head_fwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.logits, u, w.y, w.nent, R, S, K,
@@ -2269,7 +2273,11 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   }
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
   const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
-  if (marg) {                   // per-example terms over the K rows of each batch row: q(k|x), rw = q, the closed-form dlogits
+  if (marg_iw) {                // log w' = log p(x|z) + log p - log q per row (no nent term: iw_merge_enum weighs the rows by q)
+    hipLaunchKernelGGL(row_terms, dim3(grid_for(R, 256, 1 << 22)), dim3(256), 0, st, w.part, nparts, w.logq, w.logp,
+                       (const float*)nullptr, S, w.logpx, w.logw, a.row_terms, R, (double*)nullptr);
+    rowk(cx, "row_terms");
+  } else if (marg) {            // per-example terms over the K rows of each batch row: q(k|x), rw = q, the closed-form dlogits
     hipLaunchKernelGGL(ymarg_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
                        w.logw, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.dlogits, w.nent, w.pb, B, K);
     rowk(cx, "ymarg_rows");
@@ -2287,10 +2295,12 @@ static int run_step(Ctx& cx, const StepArgs& a) {
                        a.backward ? w.rw : (float*)nullptr, w.pb, B, S);
     rowk(cx, "iwae_rows");
   }
-  hipLaunchKernelGGL(loss_tail, dim3(1), dim3(1024), 0, st, w.logw, w.logpx, w.logq, w.logp,
-                     gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
-                     (S > 1 || marg) ? w.pb : (const float*)nullptr);
-  rowk(cx, "loss_tail");
+  if (!marg_iw) {                // (gmvae_iw_bound_enum_y: iw_tail writes the tail)
+    hipLaunchKernelGGL(loss_tail, dim3(1), dim3(1024), 0, st, w.logw, w.logpx, w.logq, w.logp,
+                       gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
+                       (S > 1 || marg) ? w.pb : (const float*)nullptr);
+    rowk(cx, "loss_tail");
+  }
   if (a.z_out) hipMemcpyAsync(a.z_out, w.z, (size_t)R * Lz * 4, hipMemcpyDeviceToDevice, st);
   if (a.y_out && gm) hipMemcpyAsync(a.y_out, w.y, (size_t)R * K * 4, hipMemcpyDeviceToDevice, st);
   if (a.logits_out && gm) hipMemcpyAsync(a.logits_out, w.logits, (size_t)B * K * 4, hipMemcpyDeviceToDevice, st);
@@ -2535,16 +2545,17 @@ static int run_step(Ctx& cx, const StepArgs& a) {
 
 static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// ---- gmvae_iw_bound: the workspace is the forward's at these dims (S = the chunk), then the call's own region (byte offsets)
+// ---- gmvae_iw_bound: the workspace is the forward's at these dims (S = the chunk), then the call's own region (byte offsets);
+// gmvae_iw_bound_enum_y: the same at its marginal dims (S K rows per batch row; no u)
 struct IwLay { uint64_t eps, u, rows, ftail, state, rsum, bytes; };
 static void iw_lay(const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
   WS w;
   carve(d, model, L, nullptr, w);
   uint64_t off = (w.bytes + 255) / 256 * 256;
   auto take = [&](uint64_t bytes) { const uint64_t r = off; off += (bytes + 255) / 256 * 256; return r; };
-  const uint64_t B = d.B, R = (uint64_t)d.B * d.S;
+  const uint64_t B = d.B, R = (uint64_t)d.B * rows_per_x(d);
   o.eps = take(pad4(R * d.L) * 4);               // general schedule: the chunk's explicit noise
-  o.u = take(model == GMVAE_MODEL_GMVAE ? pad4(R * d.K) * 4 : 0);
+  o.u = take(model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? pad4(R * d.K) * 4 : 0);
   o.rows = take(R * 16);                         // ... its rows (log p(x|z), log q, log p, log w)
   o.ftail = take(GMVAE_TAIL * 4);                // ... the forward's own tail (tail[3]: the batch's nent sum)
   o.state = take(B * 6 * 8);                     // every schedule: the fp64 row state (evalf.hpp iw_fold)
@@ -2616,6 +2627,63 @@ static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* 
   hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, ftail, tail);
   rowk(cx, "iw_tail");
   return cx.err;
+}
+
+// gmvae_iw_bound_enum_y, d = the caller's dims with GMVAE_OBJ_MARGINAL_Y set (S = the chunk): per chunk iw_noise_fill at S K rows
+// per batch row (Philox row ((row0 + b) n + s0 + s) K + k) -> the marginal forward at R = B S K rows (y = e_k on row
+// (b S + s) K + k; row_terms without the nent term) -> iw_merge_enum; iw_tail once (nent from iw_merge_enum's slots).
+static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* bound_out,
+                             float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
+  GmvaeDims d = d0;
+  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
+  const int model = GMVAE_MODEL_GMVAE;
+  Layout L;
+  build_layout(d, model, L);
+  WS w;
+  carve(d, model, L, workspace, w);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  char* const base = static_cast<char*>(workspace);
+  const int B = d.B, S = d.S, K = d.K;
+  const uint64_t nch = (n + S - 1) / S;
+  hipStream_t st = cx.st;
+  float* const eps = reinterpret_cast<float*>(base + il.eps);
+  float* const rows = reinterpret_cast<float*>(base + il.rows);
+  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
+  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
+  EvalArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  ma.B = B; ma.S = S; ma.rows_ws = rows; ma.slots = rsum;
+  ma.iw_state = reinterpret_cast<double*>(base + il.state); ma.iw_bound = bound_out; ma.iw_mlw = mlw_out; ma.iw_n = n;
+  const uint64_t q = noise_items(true, false, (uint64_t)B * S * K, d.L, K);
+  for (uint64_t c = 0; c < nch; ++c) {
+    // (iw_noise_fill at S K samples of n K per batch row from s0 K: sample s of component k is Philox row ((row0 + b) n + s0 + s) K + k)
+    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S * K, d.L, K,
+                       (unsigned long long)d.row0, (unsigned long long)(n * K), (unsigned long long)(c * S * K),
+                       (unsigned long long)seed, (unsigned long long)step);
+    rowk(cx, "iw_noise_fill");
+    const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed,
+                        step, nullptr, false};
+    if (int e = run_step(cx, a)) return e;
+    ma.iw_s0 = c * (uint64_t)S; ma.iw_final = c + 1 == nch;
+    hipLaunchKernelGGL(iw_merge_enum, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, ma, (const float*)w.logits, K);
+    rowk(cx, "iw_merge_enum");
+  }
+  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
+  rowk(cx, "iw_tail");
+  return cx.err;
+}
+
+// gmvae_iw_bound_enum_y's dims: the caller's with GMVAE_OBJ_MARGINAL_Y ignored on entry and set on return (S K rows per batch row)
+static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
+  if (!dims) return GMVAE_E_NULL;
+  d = *dims;
+  d.sched_flags &= ~GMVAE_OBJ_MARGINAL_Y;
+  if (int e = check_dims(&d, model)) return e;
+  if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
+  if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
+  d.sched_flags |= GMVAE_OBJ_MARGINAL_Y;
+  return 0;
 }
 
 
@@ -2720,7 +2788,7 @@ int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const flo
                    float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                    void* stream) {
   if (int e = check_dims(dims, model)) return e;
-  if (marginal_y(*dims)) return GMVAE_E_DIMS;                       // (the enumerated-y bound is not implemented)
+  if (marginal_y(*dims)) return GMVAE_E_DIMS;                       // (y summed out: gmvae_iw_bound_enum_y)
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
   if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
@@ -2730,6 +2798,34 @@ int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const flo
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   return run_iw_bound(cx, *dims, model, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
+}
+
+int gmvae_iw_bound_enum_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
+  GmvaeDims d;
+  if (int e = iw_enum_dims(dims, model, d)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  Layout L;
+  build_layout(d, model, L);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  *bytes = il.bytes;
+  return 0;
+}
+
+int gmvae_iw_bound_enum_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                          float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
+                          void* stream) {
+  GmvaeDims d;
+  if (int e = iw_enum_dims(dims, model, d)) return e;
+  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
+  const uint64_t end = d.row0 + (uint64_t)d.B;             // (row0 + B) n K < 2^38: the row field of noise_vals
+  if (n_samples == 0 || end < d.row0 || end > ((1ull << 38) - 1) / n_samples / (uint64_t)d.K) return GMVAE_E_DIMS;
+  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) || (bound_out && !aligned16(bound_out)) ||
+      (mean_logw_out && !aligned16(mean_logw_out)))
+    return GMVAE_E_ALIGN;
+  Ctx cx;
+  cx.st = static_cast<hipStream_t>(stream);
+  return run_iw_bound_enum(cx, d, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

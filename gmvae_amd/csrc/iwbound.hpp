@@ -1,6 +1,7 @@
 // gmvae_iw_bound on every shape and schedule the one-launch evaluation (evalf.hpp) does not take: per chunk of S samples a strided
 // Philox fill of eps / u, the forward with that explicit noise (its per-sample rows [B S][4] in the workspace), and iw_merge, which
 // folds the chunk into the fp64 row state (evalf.hpp iw_fold).  The last chunk adds iw_tail: the batch sums in a fixed order.
+// gmvae_iw_bound_enum_y (y summed out over K) is the same loop at S K rows per batch row with iw_merge_enum in iw_merge's place.
 #pragma once
 #include "evalf.hpp"
 
@@ -66,22 +67,62 @@ __global__ __launch_bounds__(256) void iw_merge(const EvalArgs a) {
   if (a.iw_final && lane == 0) *reinterpret_cast<float4*>(a.slots + 4 * b) = make_float4(o_loss, o_nl, o_kl, 0.f);
 }
 
+// gmvae_iw_bound_enum_y: a wave per batch row b, y summed out.  The chunk's rows_ws [B S K][4] (row (b S + s) K + k: log p(x|z),
+// log q, log p, log w' = log p(x|z) + log p(z|e_k) - log q(z|x,e_k)) of its samples s < n - s0, with q = softmax(logits_b) and
+// nent_b = sum_k q_k ln q_k (row_lse_parts and the arithmetic of ymarg_rows), fold into iw_state as
+//   max and sum of exp over (s, k) of log w';  sum log w += sum_s (sum_k q_k log w'_sk - nent_b);  nll, kl: q-weighted sums.
+// On the last chunk the row's (-bound, mean nll, mean kl, nent_b) go to slots [B][4] for iw_tail.
+__global__ __launch_bounds__(256) void iw_merge_enum(const EvalArgs a, const float* __restrict__ logits, const int K) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const float* const lg = logits + b * K;
+  float m, l;
+  row_lse_parts(lg, K, lane, m, l);
+  float ne = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float lpi = (lg[k] - m) - l, q = expf(lpi);
+    ne += q * lpi;
+  }
+  ne = wave_sum(ne);
+  const int cnt = (int)min((unsigned long long)a.S, a.iw_n - a.iw_s0), nr = cnt * K;
+  const float* const rw = a.rows_ws + b * a.S * K * 4;
+  float mx = -INFINITY;
+  for (int j = lane; j < nr; j += 64) mx = fmaxf(mx, rw[4 * j + 3]);
+  mx = Wave64::max(mx);
+  double se = 0., slw = 0., nl = 0., kl = 0.;
+  for (int j = lane; j < nr; j += 64) {
+    const float4 v = *reinterpret_cast<const float4*>(rw + 4 * j);
+    const int k = j % K;
+    const double q = expf((lg[k] - m) - l);
+    se += exp((double)v.w - (double)mx);
+    slw += q * v.w;
+    nl -= q * v.x;
+    kl += q * ((double)v.y - (double)v.z);
+  }
+  se = iw_wave_sum(se); slw = iw_wave_sum(slw) - (double)cnt * ne; nl = iw_wave_sum(nl); kl = iw_wave_sum(kl);
+  float o_loss, o_nl, o_kl;
+  iw_fold(a, b, lane, mx, se, slw, nl, kl, o_loss, o_nl, o_kl);
+  if (a.iw_final && lane == 0) *reinterpret_cast<float4*>(a.slots + 4 * b) = make_float4(o_loss, o_nl, o_kl, ne);
+}
+
 // one workgroup: tail[0..2] = the sums of slots [B][4] over b (fixed order: strided fp64 partials, then a fixed tree), tail[3] =
-// nent_tail[3] (the sum of -H(q(y|x)) over the batch from the last chunk's forward: it does not depend on the noise), tail[4] = B
+// nent_tail[3] (the sum of -H(q(y|x)) over the batch from the last chunk's forward: it does not depend on the noise) or, with
+// nent_tail null, the same sum of slots[b][3] (iw_merge_enum's nent_b), tail[4] = B
 __global__ __launch_bounds__(256) void iw_tail(const float* slots, const int B, const float* nent_tail, float* tail) {
-  __shared__ double red[3][256];
+  __shared__ double red[4][256];
   const int t = threadIdx.x;
-  double s0 = 0., s1 = 0., s2 = 0.;
-  for (int b = t; b < B; b += 256) { s0 += slots[4 * b]; s1 += slots[4 * b + 1]; s2 += slots[4 * b + 2]; }
-  red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
+  double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+  for (int b = t; b < B; b += 256) { s0 += slots[4 * b]; s1 += slots[4 * b + 1]; s2 += slots[4 * b + 2]; s3 += slots[4 * b + 3]; }
+  red[0][t] = s0; red[1][t] = s1; red[2][t] = s2; red[3][t] = s3;
   __syncthreads();
   for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) { red[0][t] += red[0][t + h]; red[1][t] += red[1][t + h]; red[2][t] += red[2][t + h]; }
+    if (t < h) { red[0][t] += red[0][t + h]; red[1][t] += red[1][t + h]; red[2][t] += red[2][t + h]; red[3][t] += red[3][t + h]; }
     __syncthreads();
   }
   if (t == 0) {
     tail[0] = (float)red[0][0]; tail[1] = (float)red[1][0]; tail[2] = (float)red[2][0];
-    tail[3] = nent_tail ? nent_tail[3] : 0.f; tail[4] = (float)B; tail[5] = 0.f; tail[6] = 0.f; tail[7] = 0.f;
+    tail[3] = nent_tail ? nent_tail[3] : (float)red[3][0]; tail[4] = (float)B; tail[5] = 0.f; tail[6] = 0.f; tail[7] = 0.f;
   }
 }
 

@@ -16,7 +16,8 @@
 
 namespace gmvae {
 
-// Forward of the layers that read y = e_k:
+// Forward of the layers that read y = e_k, rpx rows per batch row (K for the step; S K for gmvae_iw_bound_enum_y's chunk of S
+// samples, row (b S + s) K + k), b = r / rpx, k = r mod K:
 //   encoder_gmm layer 0:  hg[r][j] = act(gx[b][j] + Wy[k][j] + b0[j])   (act = 0: the layer is the network's output, no activation)
 //   prior_gmm:            pp[r][c] = Wp[k][c] + bp[c]                    (K distinct rows, gmvae.py:243 at y = e_k)
 //   y (may be null):      y[r][c] = [c == k]
@@ -24,16 +25,17 @@ namespace gmvae {
 __global__ __launch_bounds__(256) void ymarg_y_fwd(const float* __restrict__ gx, const float* __restrict__ Wy,
                                                    const float* __restrict__ b0, float* __restrict__ hg, int H, int act,
                                                    const float* __restrict__ Wp, const float* __restrict__ bp,
-                                                   float* __restrict__ pp, int N2, float* __restrict__ y, int B, int K) {
-  const long long R = (long long)B * K;
+                                                   float* __restrict__ pp, int N2, float* __restrict__ y, int B, int K,
+                                                   int rpx) {
+  const long long R = (long long)B * rpx;
   const long long nh = R * H, np = R * N2, ny = y ? R * K : 0;
   const long long n = nh + np + ny;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     if (i < nh) {
       const long long r = i / H;
       const int j = (int)(i - r * H);
-      const long long b = r / K;
-      const int k = (int)(r - b * K);
+      const long long b = r / rpx;
+      const int k = (int)(r % K);
       const float v = gx[b * H + j] + Wy[(long long)k * H + j] + b0[j];
       hg[i] = act ? act_apply(v, act) : v;
     } else if (i < nh + np) {

@@ -98,6 +98,7 @@ class Engine:
         self._param_epoch = 0                   # bumped by every Engine call that enqueues a writer of the parameter buffer
         self._eval_imgs: Dict[tuple, tuple] = {}   # (B, S) -> the state of the parameters a forward-only pass left images for
         self._iw_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound's workspace
+        self._iw_enum_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound_enum_y's workspace
         self.init_parameters(random_seed)
 
     # ------------------------------------------------------------ parameters
@@ -328,6 +329,39 @@ class Engine:
                                   L.ptr(o["mean_logw"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
                                   L.current_stream())
         L.check(rc, "gmvae_iw_bound")
+        self._keep_iw = x
+        return o
+
+    def iw_bound_enum_y(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
+        """The GMVAE's importance-weighted bound with y summed out exactly over its K components, streamed in chunks
+        (include/gmvae_hip.h gmvae_iw_bound_enum_y): dict(bound [B] = logsumexp_{s,k} log w'_sk - log n -- log p(x) + ln K for
+        a uniform p(y) --, mean_logw [B] = sum_k q_k mean_s log w'_sk - sum_k q_k ln q_k, tail [8]).  Any GMVAE engine,
+        y_inference 'gumbel' or 'marginal': the bound depends only on the generative model and q(z|x,y).  chunk: samples per
+        component per pass (default: B * K * chunk near IW_CHUNK_ROWS, at most n_samples).  Sample s of component k of row b
+        draws Philox row ((row0 + b) * n_samples + s) * K + k keyed by (noise_seed, global_step), row0 defaulting to rank * B:
+        the result does not depend on the chunk, the batch size or the sharding."""
+        if self.model != L.MODEL_GMVAE:
+            raise ValueError("iw_bound_enum_y sums y out over the GMVAE's mixture components: not available for the VAE family")
+        x = self._prep_x(x)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        B, n = x.shape[0], int(n_samples)
+        if n < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n}")
+        chunk = max(1, min(n, self.IW_CHUNK_ROWS // (B * self.K))) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        d = self.dims(B, chunk, row0)
+        nw = L.iw_bound_enum_y_workspace_bytes(d, self.model) // 4 + 64
+        ws = self._iw_enum_ws.get((B, chunk))
+        if ws is None or ws.numel() < nw:
+            ws = self._iw_enum_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        o = dict(bound=torch.empty(B, **f32), mean_logw=torch.empty(B, **f32), tail=torch.empty(L.TAIL, **f32))
+        rc = L.lib.gmvae_iw_bound_enum_y(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(o["bound"]),
+                                         L.ptr(o["mean_logw"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
+                                         L.current_stream())
+        L.check(rc, "gmvae_iw_bound_enum_y")
         self._keep_iw = x
         return o
 

@@ -98,6 +98,12 @@ class TrainableGMVAE(GMVAE):
         streamed in chunks of `chunk` samples: a [B] device tensor (Engine.iw_bound)."""
         return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
 
+    def iw_bound_enum_y(self, images, n_samples, chunk=None):
+        """Per-example importance-weighted bound with y summed out exactly over the K components (log p(x) + ln K for a
+        uniform p(y); the same for either y_inference), n_samples samples of z per component, streamed in chunks of `chunk`:
+        a [B] device tensor (Engine.iw_bound_enum_y)."""
+        return self._need_engine().iw_bound_enum_y(images, n_samples, chunk)["bound"]
+
     @property
     def summaries(self):
         """nll_scalar, kl_div_z, nent, elbo, cluster_acc of the last run_model

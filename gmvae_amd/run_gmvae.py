@@ -36,7 +36,11 @@ def build_parser():
     a("--checkpoint_max_wait", type=float, default=None, help="eval: give up waiting after this many seconds")
     a("--iw_samples", type=int, default=0, help="eval: also report the importance-weighted bound at this many samples per "
       "example, streamed in chunks (Engine.iw_bound); 0 = off")
-    a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples (default: ~51,200 rows per pass)")
+    a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples and --iw_enum_samples (default: "
+      "~51,200 rows per pass)")
+    a("--iw_enum_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the importance-weighted "
+      "bound with y summed out over the mixture components at this many samples per example and component "
+      "(Engine.iw_bound_enum_y); 0 = off")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal"], help="gmvae: one Gumbel-softmax draw of y (the "
       "reference) or y summed out exactly over the mixture components")
     return p
@@ -44,6 +48,8 @@ def build_parser():
 
 def check_args(p, cfg):
     """Flag combinations the marginal objective does not take (argument errors, before any device work)."""
+    if cfg.iw_enum_samples and cfg.model != "gmvae":
+        p.error("--iw_enum_samples sums y out over the mixture components: it needs --model=gmvae")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

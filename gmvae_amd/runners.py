@@ -371,9 +371,13 @@ def run_eval(config):
     # --iw_samples N: the importance-weighted bound at N samples per example, streamed in chunks; row0 = the example's index in
     # the split, so every example draws its own noise whatever --batch_size or the number of ranks
     iw_n, iw_chunk, iw_rows = int(getattr(config, "iw_samples", 0) or 0), getattr(config, "iw_chunk", None), []
+    # --iw_enum_samples N: the same with y summed out over the mixture components (GMVAE, either --y_inference), keyed alike
+    ie_n, ie_rows = int(getattr(config, "iw_enum_samples", 0) or 0), []
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True):
         if iw_n > 0:
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first)["bound"])
+        if ie_n > 0:
+            ie_rows.append(eng.iw_bound_enum_y(images, ie_n, chunk=iw_chunk, row0=first)["bound"])
         o = eng.forward(images)
         tot += o["tail"][:5]
         ref_sum += (o["tail"][0] / o["tail"][4]).item()
@@ -388,15 +392,20 @@ def run_eval(config):
             codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
+    ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     if world > 1:
         parallel.all_reduce_flat(tot)
         parallel.all_reduce_flat(iw_sum)
+        if ie_n > 0:
+            parallel.all_reduce_flat(ie_sum)
     n = tot[4].item()
     res = {f"{config.split}/loss_per_example": tot[0].item() / n, f"{config.split}/nll": tot[1].item() / n,
            f"{config.split}/kl_div_z": tot[2].item() / n, f"{config.split}/nent": tot[3].item() / n,
            f"{config.split}/reference_misnormalised_loss_per_example": ref_sum / n, "examples": int(n)}
     if iw_n > 0:
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
+    if ie_n > 0:
+        res[f"{config.split}/iw_bound_enum_y_{ie_n}_per_example"] = ie_sum.item() / n
     if rank == 0:
         for k, v in res.items():
             print(f"{k}: {v}")
@@ -408,6 +417,7 @@ def run_eval(config):
     res["latent_state"] = torch.cat(codes) if codes else None
     res["labels"] = torch.cat(labs) if labs else None
     res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
+    res["iw_bounds_enum_y"] = torch.cat(ie_rows) if ie_rows else None
     res["samples"] = model.generate_samples(num_samples=int(config.num_samples))
     sample_images = utils.unflatten_tensor(model.generate_sample_images(num_samples=int(config.num_generations)), img_shape)
     if config.model == "gmvae":

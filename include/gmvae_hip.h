@@ -106,7 +106,8 @@ enum { GMVAE_SCHED_SAFE = 1,
         * row_base = row0*K), u is not used.  Tail: [0] sum_b L_b, [1] sum_b sum_k q_bk nll_bk, [2] the same of kl_bk, [3] sum_b
         * nent_b, [4] B.  gmvae_forward: row_terms [B*K,4] = logpx, logq, logp, log w' = logpx + logp - logq (no nent term);
         * z_out [B*K,L]; y_out [B*K,K] the one-hot rows; logits_out [B,K].  Takes the general schedule (gmvae_step_schedule:
-        * "general+marginal"); every entry point that runs a step honours it; gmvae_iw_bound refuses it (GMVAE_E_DIMS).
+        * "general+marginal"); every entry point that runs a step honours it; gmvae_iw_bound refuses it (GMVAE_E_DIMS; the
+        * bound with y summed out is gmvae_iw_bound_enum_y, which ignores the bit).
         * GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS if S != 1 or B*K > 2^30. */
        GMVAE_OBJ_MARGINAL_Y = 4 };
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
@@ -191,6 +192,30 @@ int gmvae_iw_bound_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* b
 int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
                    float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                    void* stream);
+
+/* The GMVAE's importance-weighted bound with y summed out exactly over its K components (an importance-sampling estimate of
+ * log p(x) for the model's discrete y; q(y|x) cancels out of it), n_samples samples of z per component, streamed in chunks of
+ * dims->S samples per component:
+ *   bound_b = logsumexp_{s < n, k < K} log w'_bsk - log n,
+ *   log w'_bsk = log p(x_b|z_bsk) + log p(z_bsk|e_k) - log q(z_bsk|x_b,e_k),  z_bsk = mu_q(x_b,e_k) + sigma_q(x_b,e_k) eps_bsk,
+ * which is log p(x_b) + ln K for a uniform p(y) (the + ln K is left out, as in GMVAE_OBJ_MARGINAL_Y's objective).  It depends on
+ * the generative model and q(z|x,y) only: the same for a GMVAE trained with either objective.  GMVAE only (GMVAE_E_MODEL for
+ * the VAE family); the GMVAE_OBJ_MARGINAL_Y bit of dims->sched_flags is ignored (the result is the same with or without it).
+ * Noise of sample s of component k of batch row b: Philox row ((dims->row0 + b) * n_samples + s) * K + k -- independent of the
+ * chunk, the batch and the sharding; at n_samples == 1 the marginal gmvae_forward's keying ((row0 + b) * K + k).
+ *   bound_out [B] (may be NULL): bound_b;  mean_logw_out [B] (may be NULL): sum_k q_bk mean_s log w'_bsk - sum_k q_bk ln q_bk
+ *   (<= bound_b for every draw; at n_samples == 1 it is -L_b of the marginal objective);
+ *   tail [GMVAE_TAIL]: [0] sum_b -bound_b, [1] sum_b sum_k q_bk mean_s nll_bsk, [2] the same of kl, [3] sum_b nent_b, [4] B,
+ *   [5..7] 0 (at n_samples == 1, [1..4] are the marginal gmvae_forward's).
+ * The workspace (its size from gmvae_iw_bound_enum_y_workspace_bytes at the same dims; zeroed once) holds the marginal forward's
+ * at B * S * K rows and the per-row fp64 running state.  Per chunk: a strided noise fill, the forward (general schedule, y = e_k
+ * as gather-adds), one merge launch; the tail once.  Fixed-order reductions: two calls give the same bits.  GMVAE_E_DIMS if
+ * n_samples == 0, (row0 + B) * n_samples * K >= 2^38 or B * S * K > 2^30; GMVAE_E_ALIGN for unaligned x, params, outputs or
+ * workspace. */
+int gmvae_iw_bound_enum_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes);
+int gmvae_iw_bound_enum_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                          float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
+                          void* stream);
 
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
