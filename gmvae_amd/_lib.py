@@ -112,7 +112,9 @@ def check(rc: int, what: str):
 SCHED_SAFE = 1        # GmvaeDims.sched_flags: only schedules without waits between the workgroups of a launch
 SCHED_EVAL_IMAGES_VALID = 2      # ... forward-only: the images a previous gmvae_forward left in this workspace are current
 OBJ_MARGINAL_Y = 4    # ... objective: the GMVAE's y summed out exactly over its K values (R = B*K rows; GMVAE, S = 1 only)
-Y_INFERENCE = ("gumbel", "marginal")      # Engine(y_inference=...): one Gumbel-softmax draw of y (the reference), or y enumerated
+OBJ_MARGINAL_Y_IW = 8  # ... objective: the same, z importance-weighted over S samples per component (R = B*S*K rows; GMVAE)
+# Engine(y_inference=...): one Gumbel-softmax draw of y (the reference), y enumerated, or y enumerated with S importance samples of z
+Y_INFERENCE = ("gumbel", "marginal", "marginal_iw")
 
 
 ACTS = {"relu": 0, "tanh": 1, "sigmoid": 2, "elu": 3}       # GMVAE_ACT_*: GmvaeDims.hidden_act

@@ -52,10 +52,14 @@ constexpr int kSkNs1 = 4;        // slabs of the skinny schedule's first layer (
 // GmvaeDims::sched_flags & GMVAE_SCHED_SAFE: the schedules in which no workgroup waits for another of its own launch
 // (one workgroup per panel, the first layer as a launch of its own) -- what a caller degrades to after a hand-off timeout
 static bool sched_safe(const GmvaeDims& d) { return (d.sched_flags & GMVAE_SCHED_SAFE) != 0; }
-// GMVAE_OBJ_MARGINAL_Y (ymarg.hpp): y summed out over its K values -- K rows per batch row where the Gumbel objective has S
-static bool marginal_y(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y) != 0; }
-// (the public entry points take the bit at S == 1 only (check_dims); gmvae_iw_bound_enum_y runs its chunk of S samples as S K rows
-//  per batch row, row (b S + s) K + k)
+// GMVAE_OBJ_MARGINAL_Y / GMVAE_OBJ_MARGINAL_Y_IW (ymarg.hpp): y summed out over its K values -- S K rows per batch row, row
+// (b S + s) K + k, where the Gumbel objective has S
+static bool marginal_y(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW)) != 0; }
+// the importance-weighted objective over the S samples of each component (ymarg_iw_rows)
+static bool marginal_iw_obj(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y_IW) != 0; }
+// a chunk of gmvae_iw_bound_enum_y's forward: the public entry points take GMVAE_OBJ_MARGINAL_Y at S == 1 only (check_dims);
+// gmvae_iw_bound_enum_y sets it on its chunk of S samples (per-row log w' for iw_merge_enum, no per-example terms, no tail)
+static bool enum_y_chunk(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y) != 0 && d.S > 1; }
 static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K * d.S : d.S; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
@@ -151,6 +155,13 @@ static int check_dims(const GmvaeDims* d, int model) {
   if (d->sched_flags & GMVAE_OBJ_MARGINAL_Y) {
     if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
     if (d->S != 1 || (long long)d->B * d->K > (1LL << 30)) return GMVAE_E_DIMS;
+  }
+  if (d->sched_flags & GMVAE_OBJ_MARGINAL_Y_IW) {
+    if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
+    if (d->sched_flags & GMVAE_OBJ_MARGINAL_Y) return GMVAE_E_DIMS;
+    const uint64_t spx = (uint64_t)d->S * (uint64_t)d->K, end = d->row0 + (uint64_t)d->B;
+    if (spx > (1ull << 30) || (uint64_t)d->B * spx > (1ull << 30)) return GMVAE_E_DIMS;
+    if (end < d->row0 || end > ((1ull << 38) - 1) / spx) return GMVAE_E_DIMS;      // ((row0 + B) S K < 2^38: Philox's row field)
   }
   return 0;
 }
@@ -1951,9 +1962,10 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   build_layout(d, model, L);
   WS w;
   carve(d, model, L, a.workspace, w);
-  // marginal: the general schedule's S = K path with y = e_k on row b K + k (ymarg.hpp); at d.S > 1 (only gmvae_iw_bound_enum_y's
-  // forward: S K rows per batch row, row (b d.S + s) K + k) the per-row terms alone, for iw_merge_enum
-  const bool marg = marginal_y(d), marg_iw = marg && d.S > 1;
+  // marginal: the general schedule's S = K path with y = e_k on row b K + k (ymarg.hpp).  S K rows per batch row, row
+  // (b d.S + s) K + k: enum_chunk = gmvae_iw_bound_enum_y's forward (the per-row terms alone, for iw_merge_enum); marg_iwo =
+  // the importance-weighted objective GMVAE_OBJ_MARGINAL_Y_IW (ymarg_iw_rows; at d.S == 1 it is the marginal step: ymarg_rows)
+  const bool marg = marginal_y(d), enum_chunk = enum_y_chunk(d), marg_iwo = marginal_iw_obj(d);
   const int B = d.B, S = rows_per_x(d), R = B * S, K = d.K, Lz = d.L, D = d.D;
   const float* P = a.params;
   const bool gm = model == GMVAE_MODEL_GMVAE;
@@ -2103,7 +2115,7 @@ static int run_step(Ctx& cx, const StepArgs& a) {
       hipLaunchKernelGGL(ymarg_y_fwd, dim3(grid_for(n, 256, 4 * device_cus())), dim3(256), 0, st, w.gx,
                          P + G.w[0] + (uint64_t)D * G.dim[1], P + G.b[0], (G.nl == 1) ? w.qp : w.hg[1], G.dim[1],
                          G.nl > 1 ? tl_hact : 0, P + L.prior.w[0], P + L.prior.b[0], w.pp, 2 * Lz,
-                         (marg_iw && !a.y_out) ? (float*)nullptr : w.y, B, K, S);
+                         ((enum_chunk || marg_iwo) && !a.y_out) ? (float*)nullptr : w.y, B, K, S);
       rowk(cx, "ymarg_y_layers");
     } else {
     hipLaunchKernelGGL(y_head_fwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.logits, u, w.y, w.nent, R, S, K,
@@ -2273,10 +2285,14 @@ static int run_step(Ctx& cx, const StepArgs& a) {
   }
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
   const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
-  if (marg_iw) {                // log w' = log p(x|z) + log p - log q per row (no nent term: iw_merge_enum weighs the rows by q)
+  if (enum_chunk) {             // log w' = log p(x|z) + log p - log q per row (no nent term: iw_merge_enum weighs the rows by q)
     hipLaunchKernelGGL(row_terms, dim3(grid_for(R, 256, 1 << 22)), dim3(256), 0, st, w.part, nparts, w.logq, w.logp,
                        (const float*)nullptr, S, w.logpx, w.logw, a.row_terms, R, (double*)nullptr);
     rowk(cx, "row_terms");
+  } else if (marg_iwo && d.S > 1) {      // per example over its S K rows: q(k|x), rw = q softmax_s(log w'), the closed-form dlogits
+    hipLaunchKernelGGL(ymarg_iw_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
+                       w.logw, w.lw64, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.dlogits, w.nent, w.pb, B, d.S, K);
+    rowk(cx, "ymarg_iw_rows");
   } else if (marg) {            // per-example terms over the K rows of each batch row: q(k|x), rw = q, the closed-form dlogits
     hipLaunchKernelGGL(ymarg_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
                        w.logw, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.dlogits, w.nent, w.pb, B, K);
@@ -2295,7 +2311,7 @@ static int run_step(Ctx& cx, const StepArgs& a) {
                        a.backward ? w.rw : (float*)nullptr, w.pb, B, S);
     rowk(cx, "iwae_rows");
   }
-  if (!marg_iw) {                // (gmvae_iw_bound_enum_y: iw_tail writes the tail)
+  if (!enum_chunk) {             // (gmvae_iw_bound_enum_y: iw_tail writes the tail)
     hipLaunchKernelGGL(loss_tail, dim3(1), dim3(1024), 0, st, w.logw, w.logpx, w.logq, w.logp,
                        gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
                        (S > 1 || marg) ? w.pb : (const float*)nullptr);
@@ -2453,7 +2469,7 @@ static int run_step(Ctx& cx, const StepArgs& a) {
         if (nsp != NS) { brange(L.prior.w[0], (uint64_t)K * 2 * Lz, nsp); brange(L.prior.b[0], 2 * Lz, nsp); }
         YmDwArgs ya;
         memset(&ya, 0, sizeof(ya));
-        ya.np = 2; ya.B = B; ya.K = K; ya.slab_stride = PP;
+        ya.np = 2; ya.B = R / K; ya.K = K; ya.slab_stride = PP;     // (S K rows per batch row: B d.S "batch rows" of K rows each)
         ya.p[0].d = dcur; ya.p[0].dw = sl + G.w[0] + (uint64_t)D * G.dim[1]; ya.p[0].db = nullptr; ya.p[0].N = G.dim[1];
         ya.p[0].ns = nsy; ya.p[0].blocks = nsy * ((G.dim[1] + 63) / 64);
         ya.p[1].d = w.dpp; ya.p[1].dw = sl + L.prior.w[0]; ya.p[1].db = sl + L.prior.b[0]; ya.p[1].N = 2 * Lz;
@@ -2674,11 +2690,12 @@ static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, con
   return cx.err;
 }
 
-// gmvae_iw_bound_enum_y's dims: the caller's with GMVAE_OBJ_MARGINAL_Y ignored on entry and set on return (S K rows per batch row)
+// gmvae_iw_bound_enum_y's dims: the caller's with GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW ignored on entry and
+// GMVAE_OBJ_MARGINAL_Y set on return (S K rows per batch row)
 static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
   if (!dims) return GMVAE_E_NULL;
   d = *dims;
-  d.sched_flags &= ~GMVAE_OBJ_MARGINAL_Y;
+  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW);
   if (int e = check_dims(&d, model)) return e;
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
@@ -3472,7 +3489,8 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s", nm, marginal_y(d) ? "+marginal" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+           (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 

@@ -7,6 +7,8 @@
 // one-hot operand), the per-example terms (softmax of the logits, the row weights q_bk, the closed-form logits gradient) and
 // the one-hot weight gradients (segmented column sums over the batch into the split-K slabs).  Fixed summation orders
 // throughout: eager and graph steps give the same bits.
+// GMVAE_OBJ_MARGINAL_Y_IW adds S importance samples of z per component (R = B*S*K rows, row (b S + s) K + k): the same launches
+// at S K rows per batch row, with ymarg_iw_rows in ymarg_rows' place.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,7 +110,87 @@ __global__ __launch_bounds__(256) void ymarg_rows(const float* __restrict__ part
   }
 }
 
-// Weight gradients of the one-hot layers: dW[k][c] = sum_b d[b K + k][c] (and, with db, db[c] = sum_k dW[k][c]) for up to two
+// Per-example terms of GMVAE_OBJ_MARGINAL_Y_IW (y summed out, z importance-weighted over S samples per component), one wave per
+// batch row b, lanes over k (any K), a loop over s; row r = (b S + s) K + k, so neighbouring lanes read neighbouring rows:
+//   log w'_r = logpx_r + logp_r - logq_r (the Bernoulli partials summed in fp64 as ymarg_rows; lw64 keeps it in fp64)
+//   l_bk = -(logsumexp_s log w'_bsk - ln S)   (the differences to the maximum over s formed in fp64, as iwae_rows)
+//   q = softmax(logits_b) (row_lse_parts), nent_b = sum_k q ln q,  L_b = sum_k q_bk l_bk + nent_b
+//   rw_r = q_bk softmax_s(log w'_bsk)_s (may be null: forward only) -- the weight every per-row backward epilogue takes
+//   dlogits_bj = q_bj (l_bj - sum_k q_bk l_bk) + q_bj (ln q_bj - nent_b)
+//   pb[b] = (-L_b, sum_k q mean_s nll, sum_k q mean_s kl, 0) for loss_tail (S = 1 form), nent[b]
+// terms4 (may be null): [R][4] = logpx, logq, logp, log w'.  dlogits holds l_bk between the two passes over k (the lane that
+// writes it reads it back).  Fixed-order lane reductions, no atomics: deterministic.  (S == 1 is ymarg_rows: the host routes it.)
+__global__ __launch_bounds__(256) void ymarg_iw_rows(const float* __restrict__ part, int nparts, const float* __restrict__ logq,
+                                                     const float* __restrict__ logp, const float* __restrict__ logits,
+                                                     float* __restrict__ logpx, float* __restrict__ logw, double* __restrict__ lw64,
+                                                     float* __restrict__ terms4, float* __restrict__ rw, float* __restrict__ dlogits,
+                                                     float* __restrict__ nent, float* __restrict__ pb, int B, int S, int K) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* lg = logits + (long long)b * K;
+  float m, l;
+  row_lse_parts(lg, K, lane, m, l);
+  const float invS = 1.f / (float)S, lnS = logf((float)S);
+  const long long SK = (long long)S * K;
+  float ne = 0.f, sql = 0.f, nl = 0.f, kl = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const long long r0 = (long long)b * SK + k;
+    double mx = -INFINITY;
+    float na = 0.f, nk = 0.f;
+    for (int s = 0; s < S; ++s) {
+      const long long r = r0 + (long long)s * K;
+      double a64 = 0.0;
+      for (int i = 0; i < nparts; ++i) a64 += (double)part[r * nparts + i];
+      const float a = (float)a64, lq = logq[r], lp = logp[r];
+      const double w64 = a64 + (double)lp - (double)lq;
+      const float lw = (float)w64;
+      logpx[r] = a;
+      logw[r] = lw;
+      lw64[r] = w64;
+      if (terms4) {
+        terms4[4 * r + 0] = a;
+        terms4[4 * r + 1] = lq;
+        terms4[4 * r + 2] = lp;
+        terms4[4 * r + 3] = lw;
+      }
+      mx = fmax(mx, w64);
+      na -= a;
+      nk += lq - lp;
+    }
+    float se = 0.f;
+    for (int s = 0; s < S; ++s) se += expf((float)(lw64[r0 + (long long)s * K] - mx));
+    const float lrel = logf(se);
+    const float lk = -(float)(mx + (double)lrel - (double)lnS);
+    const float lpi = (lg[k] - m) - l, q = expf(lpi);
+    if (rw)
+      for (int s = 0; s < S; ++s) {
+        const long long r = r0 + (long long)s * K;
+        rw[r] = q * expf((float)(lw64[r] - mx) - lrel);
+      }
+    dlogits[(long long)b * K + k] = lk;
+    ne += q * lpi;
+    sql += q * lk;
+    nl += q * (na * invS);
+    kl += q * (nk * invS);
+  }
+  ne = wave_sum(ne); sql = wave_sum(sql); nl = wave_sum(nl); kl = wave_sum(kl);
+  for (int k = lane; k < K; k += 64) {
+    float* const dl = dlogits + (long long)b * K + k;
+    const float lpi = (lg[k] - m) - l, q = expf(lpi);
+    *dl = q * ((*dl - sql) + (lpi - ne));
+  }
+  if (lane == 0) {
+    nent[b] = ne;
+    pb[4 * b] = -(ne + sql);
+    pb[4 * b + 1] = nl;
+    pb[4 * b + 2] = kl;
+    pb[4 * b + 3] = 0.f;
+  }
+}
+
+// Weight gradients of the one-hot layers: dW[k][c] = sum_b d[b K + k][c] (B = the batch rows times S under GMVAE_OBJ_MARGINAL_Y_IW:
+// row (b S + s) K + k is "batch row" b S + s) (and, with db, db[c] = sum_k dW[k][c]) for up to two
 // row-gradient tensors d [R][N] -- the y rows of encoder_gmm's first layer (d = its pre-activation gradient) and prior_gmm
 // (d = dpp).  The batch is split into ns contiguous chunks; chunk s writes slab s of the split-K slab buffer (finalize_grads
 // sums the slabs in a fixed order).  A workgroup owns (problem, chunk, 64 columns); its four waves take every fourth k.

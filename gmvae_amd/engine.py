@@ -46,12 +46,17 @@ class Engine:
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
         "marginal": y summed out exactly over its K values (include/gmvae_hip.h GMVAE_OBJ_MARGINAL_Y).  Marginal steps have
-        B*K rows: eps is [B*K, L], u is not used, forward() returns rows / z / y of B*K rows; n_samples must be 1."""
+        B*K rows: eps is [B*K, L], u is not used, forward() returns rows / z / y of B*K rows; n_samples must be 1.
+        "marginal_iw": y summed out and z importance-weighted over n_samples = S samples per component (GMVAE_OBJ_MARGINAL_Y_IW;
+        at S = 1 the "marginal" objective).  Its steps have B*S*K rows, row (b*S + s)*K + k: eps is [B*S*K, L], u is not used,
+        forward(n_samples=S') returns rows / z / y of B*S'*K rows."""
         if y_inference not in L.Y_INFERENCE:
             raise ValueError(f"y_inference must be one of {L.Y_INFERENCE}, got {y_inference!r}")
         if y_inference == "marginal" and (L.MODEL_IDS.get(model) != L.MODEL_GMVAE or int(n_samples) != 1):
             raise ValueError("y_inference='marginal' needs the GMVAE model and n_samples=1 (y is enumerated over the K "
                              "components instead of sampled)")
+        if y_inference == "marginal_iw" and L.MODEL_IDS.get(model) != L.MODEL_GMVAE:
+            raise ValueError("y_inference='marginal_iw' sums y out over the GMVAE's mixture components: it needs the GMVAE model")
         self.device = L.require_gpu()
         # data parallel: this process's shard index.  Row b of a local batch of B rows is global row rank*B + b for the
         # Philox counters (GmvaeDims.row0), so G ranks draw the noise of ONE step on the global batch of G*B rows.
@@ -76,8 +81,9 @@ class Engine:
             raise ValueError(f"hidden_act must be one of {sorted(L.ACTS)} (hidden_activation_fn, scripts/base.py:19), got {hidden_act!r}")
         self.hidden_act = hidden_act
         self.y_inference = y_inference
-        self.marginal = y_inference == "marginal"
-        self.rows_per_x = self.K if self.marginal else self.S      # sample-dependent rows per batch row
+        self.marginal = y_inference in ("marginal", "marginal_iw")      # y enumerated over the K components
+        self.marginal_iw = y_inference == "marginal_iw"
+        self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
         self.safe_schedule = False              # use_safe_schedule(): the schedules without mutual waits (per engine)
@@ -106,8 +112,14 @@ class Engine:
         """GmvaeDims for a local batch of B rows; row0 = global index of its first row (default rank * B)."""
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=self.S if S is None else S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
-                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | (L.OBJ_MARGINAL_Y if self.marginal else 0)
-                           | extra_flags, **self.hp)
+                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | extra_flags, **self.hp)
+
+    def _obj_flags(self):
+        return L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
+
+    def _rows_per_x(self, S):
+        """Sample-dependent rows per batch row at S samples: S K with y summed out over the K components, else S."""
+        return S * self.K if self.marginal_iw else self.K if self.marginal else S
 
     def _params_state(self):
         """What identifies the parameter VALUES: torch's version counter of the buffer (in-place writes through torch) and the
@@ -237,7 +249,7 @@ class Engine:
     def _prep_u(self, u, rows):
         if self.marginal:
             if u is not None:
-                raise ValueError("y_inference='marginal' enumerates y: it takes no Gumbel noise u")
+                raise ValueError(f"y_inference={self.y_inference!r} enumerates y: it takes no Gumbel noise u")
             return None
         return self._prep_noise(u, rows, self.K) if self.model == L.MODEL_GMVAE else None
 
@@ -275,7 +287,7 @@ class Engine:
         x = self._prep_x(x)
         B = x.shape[0]
         S = self.S if n_samples is None else int(n_samples)
-        if self.marginal and S != 1:
+        if self.marginal and not self.marginal_iw and S != 1:
             raise ValueError("y_inference='marginal' enumerates y over the K components: n_samples must be 1")
         d, ws = self._workspace(B, S)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
@@ -283,7 +295,7 @@ class Engine:
         state = self._params_state() + (ws.data_ptr(),)
         if self._eval_imgs.get((B, S)) == state:
             d = self.dims(B, S, extra_flags=L.SCHED_EVAL_IMAGES_VALID)
-        R = B * (self.K if self.marginal else S)
+        R = B * self._rows_per_x(S)
         eps = self._prep_noise(eps, R, self.Lz)
         gm = self.model == L.MODEL_GMVAE
         u = self._prep_u(u, R)
@@ -307,7 +319,7 @@ class Engine:
         Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step), row0 defaulting to
         rank * B: the result does not depend on the chunk, the batch size or the sharding."""
         if self.marginal:
-            raise ValueError("iw_bound: the importance-weighted bound is not available with y_inference='marginal' "
+            raise ValueError(f"iw_bound: the importance-weighted bound is not available with y_inference={self.y_inference!r} "
                              "(it is the Gumbel objective's bound)")
         x = self._prep_x(x)
         if x.data_ptr() % 16:

@@ -138,8 +138,9 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                  hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel"):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference).  y_inference="marginal" trains and
-    evaluates the objective with y summed out exactly over the K components (Engine); the parameters and their names are
-    the same in both modes, so a checkpoint of either loads in the other."""
+    evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
+    importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
+    a checkpoint of any loads in the others."""
     if fcnet_hidden_sizes is None:
         fcnet_hidden_sizes = [latent_size]                     # scripts/gmvae.py:316-317
     engine = Engine("gmvae", data_size, latent_size, mixture_components, fcnet_hidden_sizes, n_samples=n_samples,

@@ -41,8 +41,9 @@ def build_parser():
     a("--iw_enum_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the importance-weighted "
       "bound with y summed out over the mixture components at this many samples per example and component "
       "(Engine.iw_bound_enum_y); 0 = off")
-    a("--y_inference", default="gumbel", choices=["gumbel", "marginal"], help="gmvae: one Gumbel-softmax draw of y (the "
-      "reference) or y summed out exactly over the mixture components")
+    a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
+      "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
+      "samples of z per component (marginal_iw)")
     return p
 
 
@@ -57,6 +58,13 @@ def check_args(p, cfg):
             p.error("--y_inference=marginal enumerates y: --n_samples must be 1")
         if cfg.iw_samples:
             p.error("--iw_samples is not available with --y_inference=marginal")
+    if cfg.y_inference == "marginal_iw":
+        if cfg.model != "gmvae":
+            p.error("--y_inference=marginal_iw needs --model=gmvae")
+        if cfg.n_samples < 1:
+            p.error("--y_inference=marginal_iw: --n_samples must be >= 1")
+        if cfg.iw_samples:
+            p.error("--iw_samples is not available with --y_inference=marginal_iw (use --iw_enum_samples)")
     return cfg
 
 

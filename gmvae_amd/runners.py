@@ -384,10 +384,11 @@ def run_eval(config):
         n_batches += 1
         # z = model.transform(flat_inputs) (runners.py:274): the VAE's MEAN code (vae.py:108-114), the GMVAE's SAMPLED
         # code (gmvae.py:140-149) -- the forward pass's z is exactly that sample
-        # (y enumerated: the code of the example's most probable component)
+        # (y enumerated: the code of the example's most probable component, at its sample 0 with --y_inference=marginal_iw)
         if config.model == "gmvae" and eng.marginal:
             B = o["logits"].shape[0]
-            codes.append(o["z"].view(B, eng.K, eng.Lz)[torch.arange(B, device=eng.device), o["logits"].argmax(dim=1)])
+            z = o["z"].view(B, eng.rows_per_x // eng.K, eng.K, eng.Lz)[:, 0]
+            codes.append(z[torch.arange(B, device=eng.device), o["logits"].argmax(dim=1)])
         else:
             codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)

@@ -109,7 +109,24 @@ enum { GMVAE_SCHED_SAFE = 1,
         * "general+marginal"); every entry point that runs a step honours it; gmvae_iw_bound refuses it (GMVAE_E_DIMS; the
         * bound with y summed out is gmvae_iw_bound_enum_y, which ignores the bit).
         * GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS if S != 1 or B*K > 2^30. */
-       GMVAE_OBJ_MARGINAL_Y = 4 };
+       GMVAE_OBJ_MARGINAL_Y = 4,
+       /* objective (GMVAE only, any S >= 1): y summed out exactly over its K values as under GMVAE_OBJ_MARGINAL_Y, z
+        * importance-weighted over S samples per component --
+        *   log w'_bsk = log p(x_b|z_bsk) + log p(z_bsk|e_k) - log q(z_bsk|x_b,e_k),
+        *   l_bk = -( logsumexp_s log w'_bsk - ln S ),   L_b = sum_k q_bk l_bk + sum_k q_bk ln q_bk,
+        *   z_bsk = mu_q(x_b, e_k) + sigma_q(x_b, e_k) eps_bsk.
+        * -L_b is a lower bound on log p(x_b) + ln K (for each k the IWAE bound in z; the q-weighted sum over k adds a Gibbs step);
+        * mean_logw_b <= -L_b <= bound_b of gmvae_iw_bound_enum_y at n_samples = S on the same noise.  At S == 1 it is
+        * GMVAE_OBJ_MARGINAL_Y's objective, step for step the same bits.  The sample-dependent tensors have R = B*S*K rows, row
+        * r = (b*S + s)*K + k with y_r = e_k; eps is [B*S*K, L] (NULL: Philox row ((row0 + b)*S + s)*K + k, gmvae_noise_fill's
+        * keying at row_base = row0*S*K and gmvae_iw_bound_enum_y's at n_samples = S), u is not used.  The workspace's per-row
+        * buffers lie where the Gumbel objective's lie at S*K samples.  Tail: [0] sum_b L_b, [1] sum_b sum_k q_bk mean_s nll_bsk,
+        * [2] the same of kl_bsk, [3] sum_b nent_b, [4] B.  gmvae_forward: row_terms [B*S*K,4] = logpx, logq, logp, log w';
+        * z_out [B*S*K,L]; y_out [B*S*K,K] the one-hot rows; logits_out [B,K].  Takes the general schedule
+        * (gmvae_step_schedule: "general+marginal_iw"); every entry point that runs a step honours it; gmvae_iw_bound refuses it
+        * (GMVAE_E_DIMS); gmvae_iw_bound_enum_y ignores it.  GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS if it is set
+        * together with GMVAE_OBJ_MARGINAL_Y, B*S*K > 2^30 or (row0 + B)*S*K >= 2^38. */
+       GMVAE_OBJ_MARGINAL_Y_IW = 8 };
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -200,7 +217,8 @@ int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const flo
  *   log w'_bsk = log p(x_b|z_bsk) + log p(z_bsk|e_k) - log q(z_bsk|x_b,e_k),  z_bsk = mu_q(x_b,e_k) + sigma_q(x_b,e_k) eps_bsk,
  * which is log p(x_b) + ln K for a uniform p(y) (the + ln K is left out, as in GMVAE_OBJ_MARGINAL_Y's objective).  It depends on
  * the generative model and q(z|x,y) only: the same for a GMVAE trained with either objective.  GMVAE only (GMVAE_E_MODEL for
- * the VAE family); the GMVAE_OBJ_MARGINAL_Y bit of dims->sched_flags is ignored (the result is the same with or without it).
+ * the VAE family); the GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW bits of dims->sched_flags are ignored (the result is
+ * the same with or without them).
  * Noise of sample s of component k of batch row b: Philox row ((dims->row0 + b) * n_samples + s) * K + k -- independent of the
  * chunk, the batch and the sharding; at n_samples == 1 the marginal gmvae_forward's keying ((row0 + b) * K + k).
  *   bound_out [B] (may be NULL): bound_b;  mean_logw_out [B] (may be NULL): sum_k q_bk mean_s log w'_bsk - sum_k q_bk ln q_bk
@@ -381,7 +399,8 @@ int gmvae_debug_sk_stamps(unsigned long long* host_out);
 int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
- * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
+ * GMVAE_OBJ_MARGINAL_Y_IW) and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
