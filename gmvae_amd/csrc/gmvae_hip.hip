@@ -2704,6 +2704,52 @@ static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
 }
 
 
+// gmvae_posterior_y: run_iw_bound_enum's loop with iw_merge_post in iw_merge_enum's place -- the fold kept per component in
+// post [B][K][3] fp64, the call's own region behind the IwLay ones (post_y_bytes) --, then iw_post_finish (ln r, the row's
+// stats, slots [B][4]) and iw_tail on those slots.
+static uint64_t post_y_bytes(const GmvaeDims& d) { return ((uint64_t)d.B * d.K * 3 * 8 + 255) / 256 * 256; }
+static int run_posterior_y(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
+                           float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
+  GmvaeDims d = d0;
+  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
+  const int model = GMVAE_MODEL_GMVAE;
+  Layout L;
+  build_layout(d, model, L);
+  WS w;
+  carve(d, model, L, workspace, w);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  char* const base = static_cast<char*>(workspace);
+  const int B = d.B, S = d.S, K = d.K;
+  const uint64_t nch = (n + S - 1) / S;
+  hipStream_t st = cx.st;
+  float* const eps = reinterpret_cast<float*>(base + il.eps);
+  float* const rows = reinterpret_cast<float*>(base + il.rows);
+  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
+  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
+  double* const post = reinterpret_cast<double*>(base + il.bytes);
+  const uint64_t q = noise_items(true, false, (uint64_t)B * S * K, d.L, K);
+  const dim3 grid((unsigned)((B + 3) / 4));
+  for (uint64_t c = 0; c < nch; ++c) {
+    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S * K, d.L, K,
+                       (unsigned long long)d.row0, (unsigned long long)(n * K), (unsigned long long)(c * S * K),
+                       (unsigned long long)seed, (unsigned long long)step);
+    rowk(cx, "iw_noise_fill");
+    const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed,
+                        step, nullptr, false};
+    if (int e = run_step(cx, a)) return e;
+    hipLaunchKernelGGL(iw_merge_post, grid, dim3(256), 0, st, (const float*)rows, post, B, S, K, (unsigned long long)n,
+                       (unsigned long long)(c * S));
+    rowk(cx, "iw_merge_post");
+  }
+  hipLaunchKernelGGL(iw_post_finish, grid, dim3(256), 0, st, (const double*)post, (const float*)w.logits, B, K,
+                     (unsigned long long)n, lj_out, lp_out, stats_out, rsum);
+  rowk(cx, "iw_post_finish");
+  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
+  rowk(cx, "iw_tail");
+  return cx.err;
+}
+
 }  // namespace
 
 // ================================ C ABI ====================================
@@ -2843,6 +2889,35 @@ int gmvae_iw_bound_enum_y(const GmvaeDims* dims, int model, const uint8_t* x, co
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   return run_iw_bound_enum(cx, d, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
+}
+
+int gmvae_posterior_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
+  GmvaeDims d;
+  if (int e = iw_enum_dims(dims, model, d)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  Layout L;
+  build_layout(d, model, L);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  *bytes = il.bytes + post_y_bytes(d);
+  return 0;
+}
+
+int gmvae_posterior_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                      float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace, uint64_t seed,
+                      uint64_t step, void* stream) {
+  GmvaeDims d;
+  if (int e = iw_enum_dims(dims, model, d)) return e;
+  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
+  const uint64_t end = d.row0 + (uint64_t)d.B;             // (row0 + B) n K < 2^38: the row field of noise_vals
+  if (n_samples == 0 || end < d.row0 || end > ((1ull << 38) - 1) / n_samples / (uint64_t)d.K) return GMVAE_E_DIMS;
+  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) ||
+      (log_joint_out && !aligned16(log_joint_out)) || (log_post_out && !aligned16(log_post_out)) ||
+      (stats_out && !aligned16(stats_out)))
+    return GMVAE_E_ALIGN;
+  Ctx cx;
+  cx.st = static_cast<hipStream_t>(stream);
+  return run_posterior_y(cx, d, x, params, n_samples, log_joint_out, log_post_out, stats_out, tail, workspace, seed, step);
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

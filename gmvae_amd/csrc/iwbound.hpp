@@ -2,6 +2,7 @@
 // Philox fill of eps / u, the forward with that explicit noise (its per-sample rows [B S][4] in the workspace), and iw_merge, which
 // folds the chunk into the fp64 row state (evalf.hpp iw_fold).  The last chunk adds iw_tail: the batch sums in a fixed order.
 // gmvae_iw_bound_enum_y (y summed out over K) is the same loop at S K rows per batch row with iw_merge_enum in iw_merge's place.
+// gmvae_posterior_y is that loop with iw_merge_post in the merge's place (the fold kept per component), then iw_post_finish.
 #pragma once
 #include "evalf.hpp"
 
@@ -123,6 +124,98 @@ __global__ __launch_bounds__(256) void iw_tail(const float* slots, const int B, 
   if (t == 0) {
     tail[0] = (float)red[0][0]; tail[1] = (float)red[1][0]; tail[2] = (float)red[2][0];
     tail[3] = nent_tail ? nent_tail[3] : (float)red[3][0]; tail[4] = (float)B; tail[5] = 0.f; tail[6] = 0.f; tail[7] = 0.f;
+  }
+}
+
+// gmvae_posterior_y: the chunk's rows_ws [B S K][4] (as iw_merge_enum reads them; only .w = log w'_bsk is used) folded PER COMPONENT
+// into post [B][K][3] fp64: (max_s log w', sum_s exp(log w' - max), sum_s exp(2 (log w' - max))) over the samples s < n - s0.
+// A wave per batch row.  The components go in tiles of Kt = min(64, K - k0); inside a tile lane g Kt + k (g < G = 64 / Kt) walks
+// the samples g, g + G, ... of component k0 + k, so at K = 10 sixty of the 64 lanes work (K = 80: a 64-wide tile, then a 16-wide
+// one at G = 4).  The G partial sums of a component meet in lane k by lane shuffles in the order g = 0 .. G - 1, and that lane --
+// the only owner of (b, k) -- writes the state on the first chunk and rescales and rewrites it on later ones (plain stores).
+__global__ __launch_bounds__(256) void iw_merge_post(const float* __restrict__ rows_ws, double* __restrict__ post, const int B,
+                                                     const int S, const int K, const unsigned long long n,
+                                                     const unsigned long long s0) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int cnt = (int)min((unsigned long long)S, n - s0);
+  const float* const rw = rows_ws + b * S * K * 4;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int Kt = min(64, K - k0), G = 64 / Kt;
+    const int g = lane / Kt, kl = lane - g * Kt;
+    const bool on = g < G;
+    const float* const col = rw + 4 * (k0 + kl) + 3;
+    float mx = -INFINITY;
+    if (on)
+      for (int s = g; s < cnt; s += G) mx = fmaxf(mx, col[4 * (long long)s * K]);
+    for (int j = 1; j < G; ++j) mx = fmaxf(mx, __shfl(mx, ((g + j) % G) * Kt + kl, 64));   // (max: the same in any order)
+    double p1 = 0., p2 = 0.;
+    if (on)
+      for (int s = g; s < cnt; s += G) {
+        const double e = exp((double)col[4 * (long long)s * K] - (double)mx);
+        p1 += e;
+        p2 += e * e;
+      }
+    double s1 = 0., s2 = 0.;
+    for (int j = 0; j < G; ++j) { s1 += __shfl(p1, j * Kt + kl, 64); s2 += __shfl(p2, j * Kt + kl, 64); }
+    if (lane < Kt) {
+      double* const st = post + (b * K + k0 + lane) * 3;
+      double m = mx;
+      if (s0 != 0) {
+        const double m0 = st[0];
+        m = fmax(m0, (double)mx);
+        const double r0 = exp(m0 - m), r1 = exp((double)mx - m);
+        s1 = st[1] * r0 + s1 * r1;
+        s2 = st[2] * r0 * r0 + s2 * r1 * r1;
+      }
+      st[0] = m; st[1] = s1; st[2] = s2;
+    }
+  }
+}
+
+// gmvae_posterior_y after the last chunk: a wave per batch row b, lanes over k.  From post [B][K][3] and q = softmax(logits_b)
+// (row_lse_parts, as iw_merge_enum):  l_k = max_k + ln(sum_k) - ln n -> log_joint;  bound = logsumexp_k l_k;  ln r_k = l_k - bound
+// -> log_post;  H(r) = -sum r ln r;  KL(q || r) = sum_k q_k (ln q_k - ln r_k);  ESS = (sum_k e^{M_k - M} sum_k)^2 /
+// sum_k e^{2 (M_k - M)} sumsq_k.  (bound, H, KL, ESS) -> stats [B][4]; (-bound, H, KL, ESS) -> slots [B][4] for iw_tail.
+__global__ __launch_bounds__(256) void iw_post_finish(const double* __restrict__ post, const float* __restrict__ logits,
+                                                      const int B, const int K, const unsigned long long n,
+                                                      float* __restrict__ log_joint, float* __restrict__ log_post,
+                                                      float* __restrict__ stats, float* __restrict__ slots) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const double* const st = post + b * K * 3;
+  const float* const lg = logits + b * K;
+  float m, l;
+  row_lse_parts(lg, K, lane, m, l);
+  const double ln_n = log((double)n);
+  double M = -INFINITY;
+  for (int k = lane; k < K; k += 64) M = fmax(M, st[3 * k]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o, 64));
+  double a1 = 0., a2 = 0.;                            // sums of w and w^2 over (s, k), in units of e^M and e^{2M}
+  for (int k = lane; k < K; k += 64) {
+    const double r = exp(st[3 * k] - M);
+    a1 += r * st[3 * k + 1];
+    a2 += r * r * st[3 * k + 2];
+  }
+  a1 = iw_wave_sum(a1); a2 = iw_wave_sum(a2);
+  const double bound = M + log(a1) - ln_n;
+  double h = 0., kl = 0.;
+  for (int k = lane; k < K; k += 64) {
+    const double lj = st[3 * k] + log(st[3 * k + 1]) - ln_n, lr = lj - bound;
+    const float lq = (lg[k] - m) - l;
+    h -= exp(lr) * lr;
+    kl += (double)expf(lq) * ((double)lq - lr);
+    if (log_joint) log_joint[b * K + k] = (float)lj;
+    if (log_post) log_post[b * K + k] = (float)lr;
+  }
+  h = iw_wave_sum(h); kl = iw_wave_sum(kl);
+  if (lane == 0) {
+    const float ess = (float)(a1 * a1 / a2);
+    if (stats) *reinterpret_cast<float4*>(stats + 4 * b) = make_float4((float)bound, (float)h, (float)kl, ess);
+    *reinterpret_cast<float4*>(slots + 4 * b) = make_float4((float)-bound, (float)h, (float)kl, ess);
   }
 }
 

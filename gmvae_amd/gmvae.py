@@ -104,6 +104,15 @@ class TrainableGMVAE(GMVAE):
         a [B] device tensor (Engine.iw_bound_enum_y)."""
         return self._need_engine().iw_bound_enum_y(images, n_samples, chunk)["bound"]
 
+    def posterior_y(self, images, n_samples, chunk=None):
+        """ln p(y = k | x) of the model itself (not the inference network's q(y|x)), by importance sampling with n_samples
+        samples of z per component, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_y)."""
+        return self._need_engine().posterior_y(images, n_samples, chunk)["log_post"]
+
+    def predict_clusters(self, images, n_samples):
+        """The component the model's posterior p(y | x) assigns each example to: an int64 [B] device tensor."""
+        return self.posterior_y(images, n_samples).argmax(dim=1)
+
     @property
     def summaries(self):
         """nll_scalar, kl_div_z, nent, elbo, cluster_acc of the last run_model

@@ -373,7 +373,13 @@ def run_eval(config):
     iw_n, iw_chunk, iw_rows = int(getattr(config, "iw_samples", 0) or 0), getattr(config, "iw_chunk", None), []
     # --iw_enum_samples N: the same with y summed out over the mixture components (GMVAE, either --y_inference), keyed alike
     ie_n, ie_rows = int(getattr(config, "iw_enum_samples", 0) or 0), []
+    # --posterior_samples N: the model's own posterior p(y|x) by importance sampling per component (GMVAE), keyed alike
+    py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True):
+        if py_n > 0:
+            po = eng.posterior_y(images, py_n, chunk=iw_chunk, row0=first)
+            py_rows.append(po["log_post"])
+            py_stats.append(torch.stack([po["bound"], po["entropy"], po["kl_q_post"], po["ess"]], dim=1))
         if iw_n > 0:
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first)["bound"])
         if ie_n > 0:
@@ -392,13 +398,18 @@ def run_eval(config):
         else:
             codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)
+        if py_n > 0:
+            py_logits.append(o["logits"])
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
+    py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
     if world > 1:
         parallel.all_reduce_flat(tot)
         parallel.all_reduce_flat(iw_sum)
         if ie_n > 0:
             parallel.all_reduce_flat(ie_sum)
+        if py_n > 0:
+            parallel.all_reduce_flat(py_tot)
     n = tot[4].item()
     res = {f"{config.split}/loss_per_example": tot[0].item() / n, f"{config.split}/nll": tot[1].item() / n,
            f"{config.split}/kl_div_z": tot[2].item() / n, f"{config.split}/nent": tot[3].item() / n,
@@ -407,6 +418,15 @@ def run_eval(config):
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:
         res[f"{config.split}/iw_bound_enum_y_{ie_n}_per_example"] = ie_sum.item() / n
+    if py_n > 0:
+        # clustering accuracy over the WHOLE split (the ranks' histograms add), by the model's posterior and by q(y|x)
+        K, all_labs = int(config.mixture_components), torch.cat(labs)
+        res[f"{config.split}/cluster_acc_posterior_{py_n}"] = utils.cluster_acc(torch.cat(py_rows), all_labs, K,
+                                                                                 all_reduce=True).item()
+        res[f"{config.split}/cluster_acc_q"] = utils.cluster_acc(torch.cat(py_logits), all_labs, K, all_reduce=True).item()
+        res[f"{config.split}/posterior_entropy_{py_n}_per_example"] = py_tot[1].item() / n
+        res[f"{config.split}/kl_q_posterior_{py_n}_per_example"] = py_tot[2].item() / n
+        res[f"{config.split}/ess_{py_n}_per_example"] = py_tot[3].item() / n
     if rank == 0:
         for k, v in res.items():
             print(f"{k}: {v}")
@@ -419,6 +439,9 @@ def run_eval(config):
     res["labels"] = torch.cat(labs) if labs else None
     res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
     res["iw_bounds_enum_y"] = torch.cat(ie_rows) if ie_rows else None
+    if py_n > 0:
+        res["log_posterior_y"] = torch.cat(py_rows)                  # [this rank's examples, K], in split order
+        res["posterior_y_stats"] = torch.cat(py_stats)               # [..., 4]: bound, entropy, KL(q || p(y|x)), ESS
     res["samples"] = model.generate_samples(num_samples=int(config.num_samples))
     sample_images = utils.unflatten_tensor(model.generate_sample_images(num_samples=int(config.num_generations)), img_shape)
     if config.model == "gmvae":

@@ -235,6 +235,32 @@ int gmvae_iw_bound_enum_y(const GmvaeDims* dims, int model, const uint8_t* x, co
                           float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                           void* stream);
 
+/* The GMVAE's own posterior over its component y, p(y = k | x_b) ~ p(x_b | y = k) p(y = k) (normalised over k) with a uniform p(y), by importance
+ * sampling per component: gmvae_iw_bound_enum_y's samples and weights (the same log w'_bsk, Philox rows, chunks of dims->S
+ * samples per component, limits and error codes; the GMVAE_OBJ_MARGINAL_Y* bits ignored; GMVAE_E_MODEL for the VAE family) with
+ * the logsumexp kept per component instead of folded over (s, k):
+ *   l_bk = logsumexp_{s < n} log w'_bsk - log n      (an estimate of log p(x_b | y = k); no +/- ln K, as the bound above)
+ *   r_bk = softmax_k l_bk                             (the model's posterior; the uniform p(y) cancels)
+ *   log_joint_out [B][K] (may be NULL): l_bk;
+ *   log_post_out [B][K] (may be NULL): ln r_bk = l_bk - logsumexp_j l_bj (usable as gmvae_cluster_acc's logits: its argmax);
+ *   stats_out [B][4] (may be NULL): [0] bound_b = logsumexp_k l_bk (the value gmvae_iw_bound_enum_y reports),
+ *     [1] H(r_b) = -sum_k r_bk ln r_bk, [2] KL(q_b || r_b) = sum_k q_bk (ln q_bk - ln r_bk), q_b = softmax of encoder_y's logits,
+ *     [3] ESS_b = (sum_{s,k} w)^2 / sum_{s,k} w^2, w = exp(log w'_bsk): the effective sample size, in [1, n K];
+ *   tail [GMVAE_TAIL]: [0] sum_b -bound_b, [1] sum_b H(r_b), [2] sum_b KL(q_b || r_b), [3] sum_b ESS_b, [4] B, [5..7] 0.
+ * Two identities: bound_b is gmvae_iw_bound_enum_y's on the same dims, seed and step; and -L_b = bound_b - KL(q_b || r_b) for
+ * GMVAE_OBJ_MARGINAL_Y_IW's objective L_b at S = n_samples on the same noise (KL(q || r) is exactly the part of that bound's gap
+ * the y-encoder is responsible for).
+ * The workspace (its size from gmvae_posterior_y_workspace_bytes at the same dims; zeroed once) is gmvae_iw_bound_enum_y's plus
+ * the per-(row, component) fp64 running state [B][K][3] (max, sum of exp, sum of exp of twice), which the first chunk writes.
+ * Per chunk: the strided noise fill, the forward, one merge launch; then one finishing launch and the tail.  Results do not
+ * depend on the chunk, the batch or the sharding beyond fp32 summation order; fixed-order reductions, no float atomics: two
+ * calls give the same bits.  GMVAE_E_DIMS if n_samples == 0, (row0 + B) * n_samples * K >= 2^38 or B * S * K > 2^30;
+ * GMVAE_E_ALIGN for unaligned x, params, outputs or workspace; GMVAE_E_NULL for a missing x, params, tail or workspace. */
+int gmvae_posterior_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes);
+int gmvae_posterior_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                      float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace, uint64_t seed,
+                      uint64_t step, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
