@@ -62,6 +62,8 @@ def _load():
         "gmvae_iw_bound_enum_y": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, u64, u64, vp], i32),
         "gmvae_posterior_y_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
         "gmvae_posterior_y": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
+        "gmvae_posterior_component_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
+        "gmvae_posterior_component": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "adam_tf_step": ([vp, vp, vp, vp, u64, f32, f32, f32, f32, u64, vp, f32, vp, vp, vp], i32),
         "gmvae_mlp_forward": ([dp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         "gmvae_noise_fill": ([vp, vp, u64, i32, i32, u64, u64, u64, vp, vp], i32),
@@ -181,6 +183,13 @@ def iw_bound_enum_y_workspace_bytes(dims, model):
 def posterior_y_workspace_bytes(dims, model):
     b = C.c_uint64()
     check(lib.gmvae_posterior_y_workspace_bytes(C.byref(dims), model, C.byref(b)), "gmvae_posterior_y_workspace_bytes")
+    return b.value
+
+
+def posterior_component_workspace_bytes(dims, model):
+    b = C.c_uint64()
+    check(lib.gmvae_posterior_component_workspace_bytes(C.byref(dims), model, C.byref(b)),
+          "gmvae_posterior_component_workspace_bytes")
     return b.value
 
 

@@ -94,6 +94,11 @@ struct EvalArgs {
   float *iw_bound, *iw_mlw;
   unsigned long long iw_n, iw_s0;
   int iw_final;
+  // gmvae_posterior_component (evalf_rows_v<7, 64>; iwbound.hpp iw_merge_comp): pc_side [R][K] = comp_k - log q of the chunk's sample
+  // rows (log w_bsk = log p(x|z) + that), pc_state [B][K][2] fp64 = (max_s log w_bsk, sum_s exp(log w_bsk - max)), pc_ess [B][3]
+  // fp64 = (max_s log w_bs, sum_s exp(log w_bs - max), sum_s exp(2 (log w_bs - max))); the first chunk writes both states.
+  float* pc_side;
+  double *pc_state, *pc_ess;
 };
 
 // Folds one chunk of batch row b (its max, and its sums of exp(log w - max), log w, nll, kl) into the row's fp64 state in a fixed
@@ -118,6 +123,33 @@ __device__ __forceinline__ void iw_fold(const EvalArgs& a, const long long b, co
   } else if (lane == 0) {
     st[0] = mx; st[1] = se; st[2] = slw; st[3] = nl; st[4] = kl;
   }
+}
+
+// gmvae_posterior_component: one chunk's (max, sum of exp(. - max)) of a (batch row, component) pair folded into its fp64 state by
+// the pair's ONE owner lane (plain stores): the first chunk writes the state, later ones rescale and rewrite it.
+__device__ __forceinline__ void pc_fold(double* const st, const bool first, double m, double s1) {
+  if (!first) {
+    const double m0 = st[0], mn = fmax(m0, m);
+    s1 = (st[1] == 0. ? 0. : st[1] * exp(m0 - mn)) + (s1 == 0. ? 0. : s1 * exp(m - mn));      // ((-inf, 0): no weight yet)
+    m = mn;
+  }
+  st[0] = m; st[1] = s1;
+}
+// ... the same for a batch row's own weights w_bs = sum_k w_bsk and their squares (the effective sample size): state [3]
+__device__ __forceinline__ void pc_fold_ess(double* const st, const bool first, double m, double s1, double s2) {
+  if (!first) {
+    const double m0 = st[0], mn = fmax(m0, m), r0 = st[1] == 0. ? 0. : exp(m0 - mn), r1 = s1 == 0. ? 0. : exp(m - mn);
+    s1 = st[1] * r0 + s1 * r1;
+    s2 = st[2] * r0 * r0 + s2 * r1 * r1;
+    m = mn;
+  }
+  st[0] = m; st[1] = s1; st[2] = s2;
+}
+// fixed-order fp64 sum over the wave (the streamed bounds' merges, iwbound.hpp, and the fold below)
+__device__ __forceinline__ double iw_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
 }
 
 // evalf_prep: the operand images from the parameters (one thread per image element) and the arrival counter.
@@ -618,11 +650,22 @@ struct EVV {
   static constexpr int M_c = M_inv + 640;          // [16]
   static constexpr int lds = M_c + 16;
 };
+// MV & 4: POST (gmvae_posterior_component; on top of MODEL = 1 and ACC): the mixture's logsumexp left open.  A sample row's K terms
+// comp_k - log q leave the lane as soon as they exist -- BEFORE the output layer, so that nothing more is live across it (the kernel
+// sits at 239 of 256 registers there) -- for the side buffer EvalArgs::pc_side [R][K] in the workspace, next to rows_ws, whose
+// log p(x|z) completes them after the output layer: log w_bsk = rows_ws[r].x + pc_side[r][k].  A side buffer and not LDS because a
+// pass holds NB S sample rows and the chunk S has no bound; the workgroup that wrote the 40 bytes per row reads them back from L2 after
+// the pass's barrier, as it does rows_ws.  There the pass's rows fold into pc_state per (batch row, component) -- a wave per batch row,
+// lane g K + k (g < 6) walking the samples g, g + 6, ... of component k: 60 of the 64 lanes --, in fp64 from the first exp on (the
+// chunk's sums differ between chunkings by fp64 rounding only: far below what log_joint's fp32 shows), and the row's own weights
+// into pc_ess.  No batch sums here: iw_post_comp_finish and iw_tail follow the last chunk.
 template <int MV, int L>      // MV & 1 = MODEL: 0 VAE (N(0, I) prior), 1 VAE_GMP (K = 10 mixture prior); MV & 2: ACC (as evalf_rows<3>); L = 2 or 64
 __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int MODEL = MV & 1;
   constexpr bool ACC = (MV & 2) != 0;
+  constexpr bool POST = (MV & 4) != 0;
+  static_assert(!POST || (MODEL == 1 && ACC), "POST: the VAE_GMP's streamed bound with the components kept apart");
   constexpr int H = EV::H, D = EV::D, K = 10, L2 = 2 * L, LT = (L + 15) / 16;
   static_assert(L == 2 || L == 64, "latent sizes of the reference's configurations");
   static_assert(MODEL == 0 || L == 64, "VAE_GMP: latent 64");
@@ -756,6 +799,11 @@ __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
 #pragma unroll
             for (int k = 0; k < K; ++k) se += fexp(comp[k] - m);
             lpA[pi] = m + flog(se);
+            if (POST && rv) {                        // (every lk lane holds all K terms: lane lk stores k = lk, lk + 4, lk + 8)
+#pragma unroll
+              for (int k = 0; k < K; ++k)
+                if (lk == (k & 3)) st1o(a.pc_side + row * K + k, comp[k] - lqA[pi]);
+            }
           }
           // ---- decoder hidden layer (vae.py:174)
           f32x4 hd[4];
@@ -794,6 +842,39 @@ __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
     const int cnt = ACC ? (int)min((unsigned long long)S, a.iw_n - a.iw_s0) : S;
     for (int b = wave; b < nb; b += kMW) {
       const float* const rw = a.rows_ws + ((long long)(bb + b) * S) * 4;
+      if (POST) {
+        constexpr int G = 64 / K;                    // sample groups: lane g K + k
+        const float* const sd = a.pc_side + ((long long)(bb + b) * S) * K;
+        const int g = lane / K, k = lane - g * K;
+        const bool on = g < G;
+        float mk = -INFINITY;
+        if (on)
+          for (int s = g; s < cnt; s += G) mk = fmaxf(mk, ld_sc(rw + 4 * s) + ld_sc(sd + (long long)s * K + k));
+#pragma unroll
+        for (int j = 1; j < G; ++j) mk = fmaxf(mk, __shfl(mk, ((g + j) % G) * K + k, 64));      // (max: the same in any order)
+        double p1 = 0.;
+        if (on)
+          for (int s = g; s < cnt; s += G) {
+            const float v = ld_sc(rw + 4 * s) + ld_sc(sd + (long long)s * K + k);
+            if (v > -INFINITY) p1 += exp((double)v - (double)mk);      // (a weight of exactly 0 adds nothing, whatever the maximum)
+          }
+        double s1 = 0.;
+#pragma unroll
+        for (int j = 0; j < G; ++j) s1 += __shfl(p1, j * K + k, 64);                            // (the order g = 0 .. G - 1)
+        if (lane < K) pc_fold(a.pc_state + ((long long)(bb + b) * K + lane) * 2, a.iw_s0 == 0, (double)mk, s1);
+        float mr = -INFINITY;                        // the row's own weights: lanes over s
+        for (int s = lane; s < cnt; s += 64) mr = fmaxf(mr, ld_sc(rw + 4 * s + 3));
+        mr = Wave64::max(mr);
+        double e1 = 0., e2 = 0.;
+        for (int s = lane; s < cnt; s += 64) {
+          const float v = ld_sc(rw + 4 * s + 3);
+          const double e = v > -INFINITY ? exp((double)v - (double)mr) : 0.;
+          e1 += e; e2 += e * e;
+        }
+        e1 = iw_wave_sum(e1); e2 = iw_wave_sum(e2);
+        if (lane == 0) pc_fold_ess(a.pc_ess + (long long)(bb + b) * 3, a.iw_s0 == 0, (double)mr, e1, e2);
+        continue;
+      }
       float mx = -INFINITY, se = 0.f, nl = 0.f, kl = 0.f, slw = 0.f;
       for (int s = lane; s < cnt; s += 64) mx = fmaxf(mx, ld_sc(rw + 4 * s + 3));
       mx = Wave64::max(mx);
@@ -813,7 +894,7 @@ __global__ __launch_bounds__(kMT) void evalf_rows_v(const EvalArgs a) {
       }
     }
   }
-  if (ACC && !a.iw_final) return;
+  if (POST || (ACC && !a.iw_final)) return;
   __syncthreads();
   if (lane == 0) { red[wave * 4] = w_loss; red[wave * 4 + 1] = w_nl; red[wave * 4 + 2] = w_kl; red[wave * 4 + 3] = 0.f; }
   __syncthreads();

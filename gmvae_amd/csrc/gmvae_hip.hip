@@ -1917,6 +1917,7 @@ static void eval_fused_args(const StepArgs& a, const Layout& L, WS& w, EvalArgs&
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<3, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<7, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
   }
 }
 static int eval_fused_grid(const GmvaeDims& d) {
@@ -2750,6 +2751,100 @@ static int run_posterior_y(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const
   return cx.err;
 }
 
+// gmvae_posterior_component (VAE_GMP): gmvae_iw_bound's loop with the mixture's logsumexp left open.  Its own regions behind the
+// IwLay ones: state [B][K][2] fp64, ess [B][3] fp64, side = the chunk's [R][K] component terms (evalf sizes) or its z [R][L] (every
+// other shape), inv [K][L] and cst [K] (gmp_consts, general schedule).
+struct PcLay { uint64_t state, ess, side, inv, cst, bytes; };
+static void pc_lay(const GmvaeDims& d, const IwLay& il, PcLay& o) {
+  uint64_t off = il.bytes;
+  auto take = [&](uint64_t bytes) { const uint64_t r = off; off += (bytes + 255) / 256 * 256; return r; };
+  const uint64_t B = d.B, R = B * (uint64_t)d.S, K = d.K, Lz = d.L;
+  o.state = take(B * K * 16);
+  o.ess = take(B * 24);
+  o.side = take(R * (K > Lz ? K : Lz) * 4);
+  o.inv = take(K * Lz * 4);
+  o.cst = take(K * 4);
+  o.bytes = off;
+}
+// evalf sizes: first layers + operand images once, then ONE evalf_rows_v<7, 64> launch per chunk (the fold inside it); every other
+// shape: iw_noise_fill -> the forward with that noise (z_out: the general schedule) -> iw_merge_comp per chunk.  Then
+// iw_post_comp_finish (log_joint, log_post, the rows' stats and slots) and iw_tail.
+static int run_posterior_component(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
+                                   float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
+  GmvaeDims d = d0;
+  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
+  const int model = GMVAE_MODEL_VAE_GMP;
+  Layout L;
+  build_layout(d, model, L);
+  WS w;
+  carve(d, model, L, workspace, w);
+  IwLay il;
+  iw_lay(d, model, L, il);
+  PcLay pl;
+  pc_lay(d, il, pl);
+  char* const base = static_cast<char*>(workspace);
+  const int B = d.B, S = d.S, K = d.K;
+  const uint64_t nch = (n + S - 1) / S;
+  hipStream_t st = cx.st;
+  double* const state = reinterpret_cast<double*>(base + pl.state);
+  double* const ess = reinterpret_cast<double*>(base + pl.ess);
+  float* const side = reinterpret_cast<float*>(base + pl.side);
+  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
+  const dim3 grid4((unsigned)((B + 3) / 4));
+  if (evalf_ok(d, model) && w.ev_img) {
+    const StepArgs a = {&d, model, x, nullptr, nullptr, params, nullptr, tail, nullptr, nullptr, nullptr, nullptr, workspace,
+                        seed, step, nullptr, false};
+    eval_fused_front(cx, a, L, w, true);
+    EvalArgs ea;
+    eval_fused_args(a, L, w, ea);
+    ea.row_base = d.row0;
+    ea.dbg = nullptr;
+    ea.iw_n = n; ea.pc_side = side; ea.pc_state = state; ea.pc_ess = ess;
+    const int grid = eval_fused_grid(d);
+    for (uint64_t c = 0; c < nch; ++c) {
+      ea.iw_s0 = c * (uint64_t)S; ea.iw_final = c + 1 == nch;
+      hipLaunchKernelGGL((evalf_rows_v<7, 64>), dim3(grid), dim3(kMT), (size_t)EVV::lds * sizeof(float), st, ea);
+      rowk(cx, "evalf_rows_v<7>");
+    }
+  } else {
+    float* const eps = reinterpret_cast<float*>(base + il.eps);
+    float* const rows = reinterpret_cast<float*>(base + il.rows);
+    float* const ftail = reinterpret_cast<float*>(base + il.ftail);
+    float* const inv = reinterpret_cast<float*>(base + pl.inv);
+    float* const cst = reinterpret_cast<float*>(base + pl.cst);
+    hipLaunchKernelGGL(gmp_consts, dim3(K), dim3(256), 0, st, params + L.rawscale, params + L.mixlog, inv, cst, d.L, K);
+    rowk(cx, "gmp_consts");
+    const uint64_t q = noise_items(true, false, (uint64_t)B * S, d.L, K);
+    for (uint64_t c = 0; c < nch; ++c) {
+      hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S, d.L, K,
+                         (unsigned long long)d.row0, (unsigned long long)n, (unsigned long long)(c * S), (unsigned long long)seed,
+                         (unsigned long long)step);
+      rowk(cx, "iw_noise_fill");
+      const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, side, nullptr, nullptr, workspace, seed, step,
+                          nullptr, false};
+      if (int e = run_step(cx, a)) return e;
+      hipLaunchKernelGGL(iw_merge_comp, grid4, dim3(256), 0, st, (const float*)rows, (const float*)side, params + L.loc,
+                         (const float*)inv, (const float*)cst, state, ess, B, S, d.L, K, (unsigned long long)n,
+                         (unsigned long long)(c * S));
+      rowk(cx, "iw_merge_comp");
+    }
+  }
+  hipLaunchKernelGGL(iw_post_comp_finish, grid4, dim3(256), 0, st, (const double*)state, (const double*)ess, params + L.mixlog, B,
+                     K, (unsigned long long)n, lj_out, lp_out, stats_out, rsum);
+  rowk(cx, "iw_post_comp_finish");
+  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
+  rowk(cx, "iw_tail");
+  return cx.err;
+}
+
+// gmvae_posterior_component's checks on the dims: the VAE_GMP's alone, B S rows within 2^30
+static int pc_dims(const GmvaeDims* dims, int model) {
+  if (int e = check_dims(dims, model)) return e;
+  if (model != GMVAE_MODEL_VAE_GMP) return GMVAE_E_MODEL;
+  if (marginal_y(*dims) || (long long)dims->B * dims->S > (1LL << 30)) return GMVAE_E_DIMS;
+  return 0;
+}
+
 }  // namespace
 
 // ================================ C ABI ====================================
@@ -2918,6 +3013,36 @@ int gmvae_posterior_y(const GmvaeDims* dims, int model, const uint8_t* x, const 
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   return run_posterior_y(cx, d, x, params, n_samples, log_joint_out, log_post_out, stats_out, tail, workspace, seed, step);
+}
+
+int gmvae_posterior_component_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
+  if (int e = pc_dims(dims, model)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  Layout L;
+  build_layout(*dims, model, L);
+  IwLay il;
+  iw_lay(*dims, model, L, il);
+  PcLay pl;
+  pc_lay(*dims, il, pl);
+  *bytes = pl.bytes;
+  return 0;
+}
+
+int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                              float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace,
+                              uint64_t seed, uint64_t step, void* stream) {
+  if (int e = pc_dims(dims, model)) return e;
+  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
+  const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
+  if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
+  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) ||
+      (log_joint_out && !aligned16(log_joint_out)) || (log_post_out && !aligned16(log_post_out)) ||
+      (stats_out && !aligned16(stats_out)))
+    return GMVAE_E_ALIGN;
+  Ctx cx;
+  cx.st = static_cast<hipStream_t>(stream);
+  return run_posterior_component(cx, *dims, x, params, n_samples, log_joint_out, log_post_out, stats_out, tail, workspace, seed,
+                                 step);
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

@@ -3,6 +3,8 @@
 // folds the chunk into the fp64 row state (evalf.hpp iw_fold).  The last chunk adds iw_tail: the batch sums in a fixed order.
 // gmvae_iw_bound_enum_y (y summed out over K) is the same loop at S K rows per batch row with iw_merge_enum in iw_merge's place.
 // gmvae_posterior_y is that loop with iw_merge_post in the merge's place (the fold kept per component), then iw_post_finish.
+// gmvae_posterior_component (VAE_GMP) is gmvae_iw_bound's loop with the mixture's logsumexp left open: evalf_rows_v<7, 64> per chunk
+// at the evalf sizes, iw_merge_comp in iw_merge's place everywhere else; then iw_post_comp_finish and iw_tail.
 #pragma once
 #include "evalf.hpp"
 
@@ -35,12 +37,6 @@ __global__ __launch_bounds__(256) void iw_noise_fill(float* eps, float* u, const
     for (int j = 0; j < 4; ++j)
       if ((int)quad * 4 + j < w) dst[j] = o[j];
   }
-}
-
-__device__ __forceinline__ double iw_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // a wave per batch row: the chunk's samples s < n - s0 of rows_ws [B S][4] (log p(x|z), log q, log p, log w) in fp64, folded into
@@ -216,6 +212,107 @@ __global__ __launch_bounds__(256) void iw_post_finish(const double* __restrict__
     const float ess = (float)(a1 * a1 / a2);
     if (stats) *reinterpret_cast<float4*>(stats + 4 * b) = make_float4((float)bound, (float)h, (float)kl, ess);
     *reinterpret_cast<float4*>(slots + 4 * b) = make_float4((float)-bound, (float)h, (float)kl, ess);
+  }
+}
+
+// gmvae_posterior_component on the general schedule: the chunk's rows_ws [B S][4] (log p(x|z), log q, log p(z), log w) and the
+// forward's z [B S][L] folded PER COMPONENT into state [B][K][2] fp64 = (max_s log w_bsk, sum_s exp(log w_bsk - max)), with
+//   log w_bsk = log p(x|z) - log q + comp_k(z),  comp_k = cst[k] - 1/2 sum_l ((z_l - loc_kl) inv_kl)^2
+// recomputed from z in the log domain as mixture_logprob_tiled does (inv, cst: gmp_consts) -- never from the responsibilities, which
+// underflow for far components --, and the row's own weights (.w) into ess [B][3] (evalf.hpp pc_fold_ess).  A wave per batch row;
+// lanes as iw_merge_post: component tiles of Kt = min(64, K - k0), lane g Kt + k walks the samples g, g + G, ... (G = 64 / Kt) with a
+// running (max, sum) pair in fp64, the G pairs of a component meet in lane k in the order g = 0 .. G - 1, and that lane -- the only
+// owner of (b, k) -- writes the state (plain stores).
+__global__ __launch_bounds__(256) void iw_merge_comp(const float* __restrict__ rows_ws, const float* __restrict__ z,
+                                                     const float* __restrict__ loc, const float* __restrict__ inv,
+                                                     const float* __restrict__ cst, double* __restrict__ state,
+                                                     double* __restrict__ ess, const int B, const int S, const int L, const int K,
+                                                     const unsigned long long n, const unsigned long long s0) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int cnt = (int)min((unsigned long long)S, n - s0);
+  const float* const rw = rows_ws + b * S * 4;
+  const float* const zb = z + b * S * L;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int Kt = min(64, K - k0), G = 64 / Kt;
+    const int g = lane / Kt, kl = lane - g * Kt;
+    const bool on = g < G;
+    const float* const lc = loc + (long long)(k0 + kl) * L;
+    const float* const iv = inv + (long long)(k0 + kl) * L;
+    const float ck = cst[k0 + kl];
+    double m = -INFINITY, acc = 0.;
+    if (on)
+      for (int s = g; s < cnt; s += G) {
+        const float* const zs = zb + (long long)s * L;
+        float q = 0.f;
+        for (int l = 0; l < L; ++l) { const float t = (zs[l] - lc[l]) * iv[l]; q = fmaf(t, t, q); }
+        const double lw = (double)((rw[4 * s] - rw[4 * s + 1]) + (ck - 0.5f * q));
+        if (lw > m) { acc = acc * exp(m - lw) + 1.; m = lw; }
+        else if (lw > -INFINITY) acc += exp(lw - m);   // (a weight of exactly 0 adds nothing)
+      }
+    double M = -INFINITY;
+    for (int j = 0; j < G; ++j) M = fmax(M, __shfl(m, j * Kt + kl, 64));
+    double s1 = 0.;
+    for (int j = 0; j < G; ++j) {
+      const double mj = __shfl(m, j * Kt + kl, 64), aj = __shfl(acc, j * Kt + kl, 64);
+      s1 += aj == 0. ? 0. : aj * exp(mj - M);          // (a group without samples: (-inf, 0))
+    }
+    if (lane < Kt) pc_fold(state + (b * K + k0 + lane) * 2, s0 == 0, M, s1);
+  }
+  float mr = -INFINITY;
+  for (int s = lane; s < cnt; s += 64) mr = fmaxf(mr, rw[4 * s + 3]);
+  mr = Wave64::max(mr);
+  double e1 = 0., e2 = 0.;
+  for (int s = lane; s < cnt; s += 64) {
+    const double e = rw[4 * s + 3] > -INFINITY ? exp((double)rw[4 * s + 3] - (double)mr) : 0.;
+    e1 += e; e2 += e * e;
+  }
+  e1 = iw_wave_sum(e1); e2 = iw_wave_sum(e2);
+  if (lane == 0) pc_fold_ess(ess + b * 3, s0 == 0, (double)mr, e1, e2);
+}
+
+// gmvae_posterior_component after the last chunk: a wave per batch row b, lanes over k (any K: strided).  From state [B][K][2], ess
+// [B][3] and ln pi = log_softmax(mixture_logits), all in fp64:  l_k = max_k + ln(sum_k) - ln n -> log_joint (fp32; the rest from it);  bound = logsumexp_k l_k;
+// ln r_k = l_k - bound -> log_post;  H(r) = -sum r ln r;  KL(r || pi) = sum_k r_k (ln r_k - ln pi_k);  ESS = (sum_s w)^2 / sum_s w^2.
+// (bound, H, KL, ESS) -> stats [B][4]; (-bound, H, KL, ESS) -> slots [B][4] for iw_tail.
+__global__ __launch_bounds__(256) void iw_post_comp_finish(const double* __restrict__ state, const double* __restrict__ ess,
+                                                           const float* __restrict__ mixlog, const int B, const int K,
+                                                           const unsigned long long n, float* __restrict__ log_joint,
+                                                           float* __restrict__ log_post, float* __restrict__ stats,
+                                                           float* __restrict__ slots) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const double* const st = state + b * K * 2;
+  const double ln_n = log((double)n);
+  // l_k as log_joint reports it: rounded to fp32 FIRST, so that bound, ln r, H and KL are functions of the call's own log_joint
+  auto lj_of = [&](const int k) { return (double)(float)(st[2 * k] + log(st[2 * k + 1]) - ln_n); };
+  double pm = -INFINITY, M = -INFINITY;
+  for (int k = lane; k < K; k += 64) { pm = fmax(pm, (double)mixlog[k]); M = fmax(M, lj_of(k)); }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { pm = fmax(pm, __shfl_xor(pm, o, 64)); M = fmax(M, __shfl_xor(M, o, 64)); }
+  double pe = 0., a1 = 0.;
+  for (int k = lane; k < K; k += 64) {
+    pe += exp((double)mixlog[k] - pm);
+    a1 += exp(lj_of(k) - M);
+  }
+  pe = iw_wave_sum(pe); a1 = iw_wave_sum(a1);
+  const double plse = pm + log(pe), bound = M + log(a1);
+  double h = 0., kl = 0.;
+  for (int k = lane; k < K; k += 64) {
+    const double lj = lj_of(k), lr = lj - bound, r = exp(lr);
+    h -= r * lr;
+    kl += r * (lr - ((double)mixlog[k] - plse));
+    if (log_joint) log_joint[b * K + k] = (float)lj;
+    if (log_post) log_post[b * K + k] = (float)lr;
+  }
+  h = iw_wave_sum(h); kl = iw_wave_sum(kl);
+  if (lane == 0) {
+    const double* const es = ess + b * 3;
+    const float e = (float)(es[1] * es[1] / es[2]);
+    if (stats) *reinterpret_cast<float4*>(stats + 4 * b) = make_float4((float)bound, (float)h, (float)kl, e);
+    *reinterpret_cast<float4*>(slots + 4 * b) = make_float4((float)-bound, (float)h, (float)kl, e);
   }
 }
 

@@ -106,6 +106,7 @@ class Engine:
         self._iw_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound's workspace
         self._iw_enum_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound_enum_y's workspace
         self._post_y_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_y's workspace
+        self._post_comp_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_component's workspace
         self.init_parameters(random_seed)
 
     # ------------------------------------------------------------ parameters
@@ -410,6 +411,42 @@ class Engine:
         self._keep_iw = x
         return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_q_post=stats[:, 2], ess=stats[:, 3],
                     tail=tail)
+
+    def posterior_component(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
+        """The VAE_GMP's own posterior over the component of its mixture prior, p(k | x) = softmax_k l_k with l_k =
+        logsumexp_s log w_sk - log n an importance-sampling estimate of log p(x, k) (include/gmvae_hip.h
+        gmvae_posterior_component; one sample z ~ q(z|x) serves all K components): dict(log_joint [B, K] = l, log_post [B, K] =
+        ln p(k | x), bound [B] = logsumexp_k l_k -- iw_bound's bound --, entropy [B] of the posterior, kl_post_prior [B] =
+        KL(p(k|x) || pi), ess [B] = the effective sample size of iw_bound's n weights, tail [8] = the batch sums of (-bound,
+        entropy, kl_post_prior, ess), B).  chunk, row0 and the noise keying as iw_bound: the result does not depend on the chunk,
+        the batch size or the sharding."""
+        if self.model != L.MODEL_VAE_GMP:
+            raise ValueError("posterior_component is the posterior over the components of the VAE's learned mixture prior: "
+                             "it needs model 'vae_gmp' (the GMVAE has posterior_y)")
+        x = self._prep_x(x)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        B, n = x.shape[0], int(n_samples)
+        if n < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n}")
+        chunk = max(1, min(n, self.IW_CHUNK_ROWS // B)) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        d = self.dims(B, chunk, row0)
+        nw = L.posterior_component_workspace_bytes(d, self.model) // 4 + 64
+        ws = self._post_comp_ws.get((B, chunk))
+        if ws is None or ws.numel() < nw:
+            ws = self._post_comp_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        lj, lp, stats = torch.empty(B, self.K, **f32), torch.empty(B, self.K, **f32), torch.empty(B, 4, **f32)
+        tail = torch.empty(L.TAIL, **f32)
+        rc = L.lib.gmvae_posterior_component(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(lj), L.ptr(lp),
+                                             L.ptr(stats), L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step,
+                                             L.current_stream())
+        L.check(rc, "gmvae_posterior_component")
+        self._keep_iw = x
+        return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_post_prior=stats[:, 2],
+                    ess=stats[:, 3], tail=tail)
 
     def mlp(self, net: int, inp: torch.Tensor, in2: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One conditional network's MLP on the device (snt.nets.MLP, scripts/base.py:47-60)."""

@@ -36,14 +36,18 @@ def build_parser():
     a("--checkpoint_max_wait", type=float, default=None, help="eval: give up waiting after this many seconds")
     a("--iw_samples", type=int, default=0, help="eval: also report the importance-weighted bound at this many samples per "
       "example, streamed in chunks (Engine.iw_bound); 0 = off")
-    a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples, --iw_enum_samples and "
-      "--posterior_samples (default: ~51,200 rows per pass)")
+    a("--iw_chunk", type=int, default=None, help="eval: samples per chunk of --iw_samples, --iw_enum_samples, "
+      "--posterior_samples and --component_posterior_samples (default: ~51,200 rows per pass)")
     a("--iw_enum_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the importance-weighted "
       "bound with y summed out over the mixture components at this many samples per example and component "
       "(Engine.iw_bound_enum_y); 0 = off")
     a("--posterior_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the model's own "
       "posterior p(y|x) by importance sampling at this many samples per example and component (Engine.posterior_y) -- its "
       "clustering accuracy next to q(y|x)'s, its entropy, KL(q(y|x) || p(y|x)) and the effective sample size; 0 = off")
+    a("--component_posterior_samples", type=int, default=0, help="eval, vae_gmp: also report the model's own posterior "
+      "p(k|x) over the components of its mixture prior by importance sampling at this many samples per example "
+      "(Engine.posterior_component) -- its clustering accuracy, its entropy, KL(p(k|x) || pi) and the effective sample size; "
+      "0 = off")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -56,6 +60,11 @@ def check_args(p, cfg):
         p.error("--iw_enum_samples sums y out over the mixture components: it needs --model=gmvae")
     if cfg.posterior_samples and cfg.model != "gmvae":
         p.error("--posterior_samples is the posterior over the mixture components: it needs --model=gmvae")
+    if cfg.component_posterior_samples:
+        if cfg.model != "vae_gmp":
+            p.error("--component_posterior_samples is the posterior over the VAE's mixture prior: it needs --model=vae_gmp")
+        if cfg.mode != "eval":
+            p.error("--component_posterior_samples needs --mode=eval")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

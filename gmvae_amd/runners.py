@@ -375,7 +375,13 @@ def run_eval(config):
     ie_n, ie_rows = int(getattr(config, "iw_enum_samples", 0) or 0), []
     # --posterior_samples N: the model's own posterior p(y|x) by importance sampling per component (GMVAE), keyed alike
     py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
+    # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
+    pc_n, pc_rows, pc_stats = int(getattr(config, "component_posterior_samples", 0) or 0), [], []
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True):
+        if pc_n > 0:
+            po = eng.posterior_component(images, pc_n, chunk=iw_chunk, row0=first)
+            pc_rows.append(po["log_post"])
+            pc_stats.append(torch.stack([po["bound"], po["entropy"], po["kl_post_prior"], po["ess"]], dim=1))
         if py_n > 0:
             po = eng.posterior_y(images, py_n, chunk=iw_chunk, row0=first)
             py_rows.append(po["log_post"])
@@ -403,6 +409,7 @@ def run_eval(config):
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
+    pc_tot = torch.cat(pc_stats).double().sum(0) if pc_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
     if world > 1:
         parallel.all_reduce_flat(tot)
         parallel.all_reduce_flat(iw_sum)
@@ -410,6 +417,8 @@ def run_eval(config):
             parallel.all_reduce_flat(ie_sum)
         if py_n > 0:
             parallel.all_reduce_flat(py_tot)
+        if pc_n > 0:
+            parallel.all_reduce_flat(pc_tot)
     n = tot[4].item()
     res = {f"{config.split}/loss_per_example": tot[0].item() / n, f"{config.split}/nll": tot[1].item() / n,
            f"{config.split}/kl_div_z": tot[2].item() / n, f"{config.split}/nent": tot[3].item() / n,
@@ -427,6 +436,13 @@ def run_eval(config):
         res[f"{config.split}/posterior_entropy_{py_n}_per_example"] = py_tot[1].item() / n
         res[f"{config.split}/kl_q_posterior_{py_n}_per_example"] = py_tot[2].item() / n
         res[f"{config.split}/ess_{py_n}_per_example"] = py_tot[3].item() / n
+    if pc_n > 0:
+        # clustering accuracy over the WHOLE split (the ranks' histograms add), by the model's posterior over its prior's components
+        res[f"{config.split}/cluster_acc_posterior_{pc_n}"] = utils.cluster_acc(torch.cat(pc_rows), torch.cat(labs),
+                                                                                 int(config.mixture_components), all_reduce=True).item()
+        res[f"{config.split}/posterior_entropy_{pc_n}_per_example"] = pc_tot[1].item() / n
+        res[f"{config.split}/kl_posterior_prior_{pc_n}_per_example"] = pc_tot[2].item() / n
+        res[f"{config.split}/ess_{pc_n}_per_example"] = pc_tot[3].item() / n
     if rank == 0:
         for k, v in res.items():
             print(f"{k}: {v}")
@@ -442,6 +458,9 @@ def run_eval(config):
     if py_n > 0:
         res["log_posterior_y"] = torch.cat(py_rows)                  # [this rank's examples, K], in split order
         res["posterior_y_stats"] = torch.cat(py_stats)               # [..., 4]: bound, entropy, KL(q || p(y|x)), ESS
+    if pc_n > 0:
+        res["log_posterior_component"] = torch.cat(pc_rows)          # [this rank's examples, K], in split order
+        res["posterior_component_stats"] = torch.cat(pc_stats)       # [..., 4]: bound, entropy, KL(p(k|x) || pi), ESS
     res["samples"] = model.generate_samples(num_samples=int(config.num_samples))
     sample_images = utils.unflatten_tensor(model.generate_sample_images(num_samples=int(config.num_generations)), img_shape)
     if config.model == "gmvae":

@@ -81,6 +81,15 @@ class TrainableVAE(VAE):
         a [B] device tensor (Engine.iw_bound)."""
         return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
 
+    def posterior_component(self, images, n_samples, chunk=None):
+        """ln p(k | x) over the components of the learned mixture prior (mixture_components > 1), by importance sampling with
+        n_samples samples of z, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_component)."""
+        return self._need_engine().posterior_component(images, n_samples, chunk)["log_post"]
+
+    def predict_clusters(self, images, n_samples):
+        """The component the model's posterior p(k | x) assigns each example to: an int64 [B] device tensor."""
+        return self.posterior_component(images, n_samples).argmax(dim=1)
+
     @property
     def summaries(self):
         """nll_scalar / kl_div_z / elbo of the last run_model (scripts/vae.py:178,182,186)."""

@@ -261,6 +261,38 @@ int gmvae_posterior_y(const GmvaeDims* dims, int model, const uint8_t* x, const 
                       float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace, uint64_t seed,
                       uint64_t step, void* stream);
 
+/* The VAE_GMP's own posterior over the component k of its learned mixture prior, p(k | x_b) ~ pi_k p(x_b | k), by importance
+ * sampling.  The component enters neither the encoder nor the decoder, so ONE sample z_bs = mu_q(x_b) + sigma_q(x_b) eps_bs serves
+ * all K components: gmvae_iw_bound's samples (the same Philox rows (row0 + b) n + s, chunks of dims->S samples, limits and error
+ * codes) with the mixture's logsumexp left open,
+ *   log w_bsk = log p(x_b | z_bs) + ln pi_k + log N(z_bs; loc_k, s_k) - log q(z_bs | x_b)     (pi = softmax(mixture_logits),
+ *                                                                                              s = softplus(raw_scale_diag))
+ *   l_bk = logsumexp_{s < n} log w_bsk - log n        (an estimate of log p(x_b, k))
+ *   r_bk = softmax_k l_bk                              (the model's posterior)
+ *   log_joint_out [B][K] (may be NULL): l_bk;
+ *   log_post_out [B][K] (may be NULL): ln r_bk (usable as gmvae_cluster_acc's logits: its argmax);
+ *   stats_out [B][4] (may be NULL): [0] bound_b = logsumexp_k l_bk (gmvae_iw_bound's bound: logsumexp_k log w_bsk = log w_bs),
+ *     [1] H(r_b) = -sum_k r_bk ln r_bk, [2] KL(r_b || pi) = sum_k r_bk (ln r_bk - ln pi_k) (its mean over a split estimates the
+ *     mutual information I(x; k)), [3] ESS_b = (sum_s w_bs)^2 / sum_s w_bs^2, w_bs = sum_k w_bsk: the effective sample size of
+ *     gmvae_iw_bound's own weights, in [1, n];
+ *   tail [GMVAE_TAIL]: [0] sum_b -bound_b, [1] sum_b H(r_b), [2] sum_b KL(r_b || pi), [3] sum_b ESS_b, [4] B, [5..7] 0.
+ * Every component term stays in the log domain (never log w_bs + ln of a responsibility, which underflows): l_bk is finite and
+ * accurate for components far from z.  GMVAE_MODEL_VAE_GMP only: GMVAE_E_MODEL for the VAE and the GMVAE.
+ * The workspace (its size from gmvae_posterior_component_workspace_bytes at the same dims; zeroed once) is gmvae_iw_bound's plus
+ * the per-(row, component) fp64 running state [B][K][2] (max, sum of exp), the per-row [3] of the effective sample size and the
+ * chunk's [B S][max(K, L)] component terms or latents.  At the reference's default sizes one launch per chunk (the fold inside
+ * it); elsewhere the strided noise fill, the forward and one merge launch; then one finishing launch and the tail.  One owner per
+ * (row, component), fixed-order reductions, no float atomics: two calls give the same bits; the result does not depend on the
+ * chunk, the batch or the sharding beyond the forward's own summation order and the fp64 rounding of the folds.  (The one-launch
+ * schedule is not taken at S = 1 with more than 8 batch rows per workgroup, as for gmvae_forward: such a call runs the general
+ * loop, whose summation order follows B * S.)  GMVAE_E_DIMS if n_samples == 0,
+ * (row0 + B) * n_samples >= 2^38 or B * S > 2^30; GMVAE_E_ALIGN for unaligned x, params, outputs or workspace; GMVAE_E_NULL for a
+ * missing x, params, tail or workspace.  Every check happens before any launch. */
+int gmvae_posterior_component_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes);
+int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
+                              float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace,
+                              uint64_t seed, uint64_t step, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
