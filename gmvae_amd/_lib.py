@@ -119,6 +119,9 @@ OBJ_MARGINAL_Y = 4    # ... objective: the GMVAE's y summed out exactly over its
 OBJ_MARGINAL_Y_IW = 8  # ... objective: the same, z importance-weighted over S samples per component (R = B*S*K rows; GMVAE)
 # Engine(y_inference=...): one Gumbel-softmax draw of y (the reference), y enumerated, or y enumerated with S importance samples of z
 Y_INFERENCE = ("gumbel", "marginal", "marginal_iw")
+GRAD_DREG = 16        # ... gradient estimator of the inference network: doubly reparameterised (include/gmvae_hip.h GMVAE_GRAD_DREG)
+# Engine(grad_estimator=...): the plain reparameterised gradient, or the doubly reparameterised one (Tucker et al. 2018)
+GRAD_ESTIMATORS = ("standard", "dreg")
 
 
 ACTS = {"relu": 0, "tanh": 1, "sigmoid": 2, "elu": 3}       # GMVAE_ACT_*: GmvaeDims.hidden_act

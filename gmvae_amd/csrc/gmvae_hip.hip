@@ -61,6 +61,9 @@ static bool marginal_iw_obj(const GmvaeDims& d) { return (d.sched_flags & GMVAE_
 // gmvae_iw_bound_enum_y sets it on its chunk of S samples (per-row log w' for iw_merge_enum, no per-example terms, no tail)
 static bool enum_y_chunk(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_MARGINAL_Y) != 0 && d.S > 1; }
 static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K * d.S : d.S; }
+// GMVAE_GRAD_DREG: the doubly reparameterised gradient for the inference network (kernels.hpp z_head_bwd_dreg) -- the backward of
+// the general schedule alone; forward-only passes do not depend on it
+static bool dreg_grad(const GmvaeDims& d) { return (d.sched_flags & GMVAE_GRAD_DREG) != 0; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -165,6 +168,13 @@ static int check_dims(const GmvaeDims* d, int model) {
   }
   return 0;
 }
+// the entry points that run (or size) a training step: GMVAE_GRAD_DREG is refused for the Gumbel GMVAE (its relaxed y is
+// reparameterised too and its bound carries an analytic entropy term: the prior network's backward would have to run twice)
+static int check_step_dims(const GmvaeDims* d, int model) {
+  if (int e = check_dims(d, model)) return e;
+  if (dreg_grad(*d) && model == GMVAE_MODEL_GMVAE && !marginal_y(*d)) return GMVAE_E_DIMS;
+  return 0;
+}
 
 // Variable-creation order of the reference: GMVAE: encoder_y,
 // prior_gmm, encoder_gmm, decoder (gmvae.py:238,243,246,251); VAE: prior
@@ -193,6 +203,7 @@ struct WS {
   float* hg[MAXH + 2];   // encoder_gmm activations [R, dim[i]]
   float* hd[MAXH + 2];   // decoder activations [R, dim[i]]
   float *gx, *logits, *y, *nent, *pp, *qp, *z, *logq, *logp, *logpx, *logw, *rw, *resp, *g, *part;
+  float* vs;               // GMVAE_GRAD_DREG under GMVAE_OBJ_MARGINAL_Y_IW at S > 1: softmax_s(log w'_bsk) per row (ymarg_iw_rows)
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -250,6 +261,8 @@ static bool mega_shape(const GmvaeDims& d, int model) {
   return (size_t)mega_lay(H, d.L, d.K, d.D, model).total * 4 <= 160 * 1024;
 }
 static bool mega_ok(const GmvaeDims& d, int model) {
+  if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
+                                               //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
   const char* e = getenv("GMVAE_NO_MEGA");
   if (e && atoi(e)) return false;
   const char* e2 = getenv("GMVAE_NO_FUSED");
@@ -297,6 +310,7 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
 static bool skinny_ok(const GmvaeDims& d, int model) {
+  if (dreg_grad(d)) return false;
   const char* e = getenv("GMVAE_NO_SKINNY");
   if (e && atoi(e)) return false;
   int maxb = kSkMaxB;
@@ -311,6 +325,7 @@ static bool fused_shape(const GmvaeDims& d, int model) {
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
 }
 static bool fused_ok(const GmvaeDims& d, int model) {
+  if (dreg_grad(d)) return false;
   const char* e = getenv("GMVAE_NO_FUSED");
   if (e && atoi(e)) return false;
   return fused_shape(d, model);
@@ -506,6 +521,7 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.ev_slots = take(4 * 1024 + 64);
     w.ev_dbg = reinterpret_cast<unsigned long long*>(take(2ull * 1024 * 16));
   }
+  if (dreg_grad(d) && marginal_iw_obj(d) && d.S > 1) w.vs = take(R);      // (last: dims without the bit keep their size and every offset)
   w.bytes = off;
 }
 
@@ -1956,7 +1972,16 @@ static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
   return cx.err;
 }
 
+static int run_step_impl(Ctx& cx, const StepArgs& a);
 static int run_step(Ctx& cx, const StepArgs& a) {
+  if (a.backward || !dreg_grad(*a.d)) return run_step_impl(cx, a);
+  GmvaeDims d = *a.d;                            // forward only: the bound, the tail and the outputs do not depend on the estimator
+  d.sched_flags &= ~GMVAE_GRAD_DREG;
+  StepArgs b = a;
+  b.d = &d;
+  return run_step_impl(cx, b);
+}
+static int run_step_impl(Ctx& cx, const StepArgs& a) {
   const GmvaeDims& d = *a.d;
   const int model = a.model;
   Layout L;
@@ -2292,7 +2317,8 @@ static int run_step(Ctx& cx, const StepArgs& a) {
     rowk(cx, "row_terms");
   } else if (marg_iwo && d.S > 1) {      // per example over its S K rows: q(k|x), rw = q softmax_s(log w'), the closed-form dlogits
     hipLaunchKernelGGL(ymarg_iw_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
-                       w.logw, w.lw64, a.row_terms, a.backward ? w.rw : (float*)nullptr, w.dlogits, w.nent, w.pb, B, d.S, K);
+                       w.logw, w.lw64, a.row_terms, a.backward ? w.rw : (float*)nullptr, a.backward ? w.vs : (float*)nullptr,
+                       w.dlogits, w.nent, w.pb, B, d.S, K);
     rowk(cx, "ymarg_iw_rows");
   } else if (marg) {            // per-example terms over the K rows of each batch row: q(k|x), rw = q, the closed-form dlogits
     hipLaunchKernelGGL(ymarg_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, w.logpx,
@@ -2404,9 +2430,19 @@ static int run_step(Ctx& cx, const StepArgs& a) {
     dcur = out;
     pb ^= 1;
   }
+  if (dreg_grad(d)) {
+    // v = softmax_s(log w) of the row's sample group: the VAE family's row weight itself, ymarg_iw_rows' second output under
+    // GMVAE_OBJ_MARGINAL_Y_IW at S > 1, 1 (null) for one sample per group
+    const float* const vS = !gm ? rwS : (marg_iwo && d.S > 1) ? w.vs : (const float*)nullptr;
+    if (gm && marg_iwo && d.S > 1 && !w.vs) return GMVAE_E_DIMS;
+    hipLaunchKernelGGL(z_head_bwd_dreg, dim3(grid_for(R, 4)), dim3(256), 0, st, w.dz, w.qp, qp_div, w.pp, eps, w.z, rwS, vS,
+                       w.resp, P + L.loc, P + L.rawscale, w.dqp, w.dpp, R, Lz, K, prior, c, smin);
+    rowk(cx, "z_head_bwd_dreg");
+  } else {
   hipLaunchKernelGGL(z_head_bwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.dz, w.qp, qp_div, w.pp, eps, w.z, rwS,
                      w.resp, P + L.loc, P + L.rawscale, w.dqp, w.dpp, R, Lz, K, prior, c, smin);
   rowk(cx, "z_head_bwd");
+  }
 
   if (gm) {
     const NetL& G = L.encg;
@@ -2585,7 +2621,7 @@ static void iw_lay(const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
 static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* x, const float* params, uint64_t n,
                         float* bound_out, float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;      // (the operand images are prepared here, once per call)
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG);      // (the operand images are prepared here, once per call)
   Layout L;
   build_layout(d, model, L);
   WS w;
@@ -2696,7 +2732,7 @@ static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, con
 static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
   if (!dims) return GMVAE_E_NULL;
   d = *dims;
-  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW);
+  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG);
   if (int e = check_dims(&d, model)) return e;
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
@@ -2772,7 +2808,7 @@ static void pc_lay(const GmvaeDims& d, const IwLay& il, PcLay& o) {
 static int run_posterior_component(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
                                    float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG);
   const int model = GMVAE_MODEL_VAE_GMP;
   Layout L;
   build_layout(d, model, L);
@@ -2875,7 +2911,7 @@ int gmvae_param_layout(const GmvaeDims* dims, int model, GmvaeParamEntry* out, i
 }
 
 int gmvae_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!bytes) return GMVAE_E_NULL;
   Layout L;
   build_layout(*dims, model, L);
@@ -2888,7 +2924,7 @@ int gmvae_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
 int gmvae_step(const GmvaeDims* dims, int model, const uint8_t* x, const float* eps, const float* u,
                const float* params, float* grads, void* workspace, uint64_t seed, uint64_t step, uint64_t* step_dev,
                void* stream) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !grads || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace) || (eps && !aligned16(eps)) ||
       (u && !aligned16(u)))
@@ -3271,7 +3307,7 @@ int gmvae_gemm_test(const void* A, int a_is_u8, const float* W, const float* bia
 int gmvae_step_profile(const GmvaeDims* dims, int model, const uint8_t* x, const float* eps, const float* u,
                        const float* params, float* grads, void* workspace, uint64_t seed, int iters, int max_levels,
                        int* n_levels, char* names, float* usec, double* flops, void* stream) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !grads || !workspace || !n_levels || !names || !usec || !flops) return GMVAE_E_NULL;
   if (iters < 1) return GMVAE_E_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -3399,7 +3435,7 @@ int gmvae_train_profile(const GmvaeDims* dims, int model, const uint8_t* x, floa
                         float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, int iters,
                         int max_levels, int* n_levels, char* names, float* usec, float* usec_timeline, double* flops,
                         void* stream) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !n_levels || !names || !usec || !flops)
     return GMVAE_E_NULL;
   if (iters < 1) return GMVAE_E_DIMS;
@@ -3511,7 +3547,7 @@ int gmvae_train_profile(const GmvaeDims* dims, int model, const uint8_t* x, floa
 int gmvae_bench_loop(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v,
                      float* grads, void* workspace, uint64_t* step_dev, int iters, int mode, float* usec_per_step,
                      void* stream) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !usec_per_step) return GMVAE_E_NULL;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
@@ -3577,7 +3613,7 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
                               uint8_t* x, int n_steps, float* params, float* m, float* v, float* grads, void* workspace,
                               uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2, float epsilon,
                               float* tail_log, void** graph_out) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3679,7 +3715,7 @@ int gmvae_debug_sk_stamps_free(void) {
 
 /* debugging aid: resident workgroups per CU as the runtime computes them */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!out48) return GMVAE_E_NULL;
   const GmvaeDims& d = *dims;
   Layout L;
@@ -3689,8 +3725,8 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
-           (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+           dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3710,7 +3746,7 @@ int gmvae_kernel_occupancy(int which, int* blocks_per_cu) {
 
 /* debugging aid: byte offset of a named workspace buffer (tests compare intermediates with the oracle) */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!name || !byte_offset) return GMVAE_E_NULL;
   Layout L;
   build_layout(*dims, model, L);
@@ -3825,7 +3861,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
                         void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2,
                         float epsilon, void* comm, hipStream_t st, bool in_graph, bool imgs_ready, float* tail_log = nullptr,
                         int span_slot = -1, Prof* prof = nullptr) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !comm || !g_rccl.h || !step_dev) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace)) return GMVAE_E_ALIGN;
   Layout L;
@@ -3915,7 +3951,7 @@ int gmvae_dp_step(const GmvaeDims* dims, int model, const uint8_t* x, float* par
 int gmvae_dp_profile(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v, float* grads,
                      void* workspace, uint64_t seed, uint64_t* step_dev, float lr, void* comm, int iters, float* out,
                      int max_levels, int* n_levels, char* names, void* stream) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !comm || !out) return GMVAE_E_NULL;
   if (iters < 1) return GMVAE_E_DIMS;
   if (!mega_ok(*dims, model)) return GMVAE_E_DIMS;
@@ -3993,7 +4029,7 @@ int gmvae_dp_profile(const GmvaeDims* dims, int model, const uint8_t* x, float* 
 int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, int n_steps, float* params, float* m, float* v,
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
-  if (int e = check_dims(dims, model)) return e;
+  if (int e = check_step_dims(dims, model)) return e;
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

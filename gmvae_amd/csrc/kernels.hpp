@@ -587,6 +587,55 @@ __global__ void z_head_bwd(const float* __restrict__ dz, const float* __restrict
   }
 }
 
+// z_head_bwd under GMVAE_GRAD_DREG: the doubly reparameterised estimator (Tucker et al. 2018) for the inference network.
+// v = softmax_s(log w) of the row's own sample group (null: 1, the S = 1 "sticking the landing" estimator); w as above:
+//   dmu_q = v*(dz_dec + w*prior_term - w*eps/sig_q) ; dsig_q = dmu_q*eps ; draw_q as above
+// The score of q through its own parameters is dropped (no -w/sig_q); the path through z keeps d log q / dz = -eps/sig_q with the
+// clamped sig_q.  dpp (the prior network's gradient, generative) is z_head_bwd's: weighted by w alone.
+__global__ void z_head_bwd_dreg(const float* __restrict__ dz, const float* __restrict__ qp, int qp_div,
+                                const float* __restrict__ pp, const float* __restrict__ eps,
+                                const float* __restrict__ z, const float* __restrict__ rw, const float* __restrict__ vs,
+                                const float* __restrict__ resp, const float* __restrict__ loc,
+                                const float* __restrict__ raw_scale, float* __restrict__ dqp,
+                                float* __restrict__ dpp, int R, int L, int K, int prior, float c, float smin) {
+  const int lane = threadIdx.x & 63;
+  const int wpb = blockDim.x >> 6;
+  for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < R; r += gridDim.x * wpb) {
+    const float w = rw ? rw[r] : 1.f;
+    const float v = vs ? vs[r] : 1.f;
+    const float* q = qp + (long long)(r / qp_div) * 2 * L;
+    for (int l = lane; l < L; l += 64) {
+      const float rawq = q[L + l] + c;
+      const float spq = softplus_r(rawq);
+      const float sg = fmaxf(spq, smin);
+      const float zz = z[(long long)r * L + l];
+      float pterm;
+      if (prior == PRIOR_COND) {
+        const float* p = pp + (long long)r * 2 * L;
+        const float rawp = p[L + l] + c;
+        const float spp = softplus_r(rawp);
+        const float sp = fmaxf(spp, smin), isp = __builtin_amdgcn_rcpf(sp);
+        const float t = (zz - p[l]) * isp;
+        pterm = t * isp;
+        dpp[(long long)r * 2 * L + l] = -w * pterm;
+        dpp[(long long)r * 2 * L + L + l] = (spp > smin) ? w * (1.f - t * t) * isp * sigmoid_r(rawp) : 0.f;
+      } else if (prior == PRIOR_STD) {
+        pterm = zz;
+      } else {
+        pterm = 0.f;
+        for (int k = 0; k < K; ++k) {
+          const float s = softplusf_(raw_scale[k * L + l]);
+          pterm += resp[(long long)r * K + k] * (zz - loc[k * L + l]) / (s * s);
+        }
+      }
+      const float e = eps[(long long)r * L + l];
+      const float dmu = v * (dz[(long long)r * L + l] + w * (pterm - e * __builtin_amdgcn_rcpf(sg)));
+      dqp[(long long)r * 2 * L + l] = dmu;
+      dqp[(long long)r * 2 * L + L + l] = (spq > smin) ? dmu * e * sigmoid_r(rawq) : 0.f;
+    }
+  }
+}
+
 // Gradients of the learned mixture prior (vae.py:233-244):
 //   dloc_kl = -sum_r w r_k (z-loc)/s^2 ; ds_kl = sum_r w r_k (1-t^2)/s ;
 //   dmix_k = -sum_r w (r_k - softmax(mixture_logits)_k)

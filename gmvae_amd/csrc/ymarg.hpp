@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256) void ymarg_rows(const float* __restrict__ part
 //   l_bk = -(logsumexp_s log w'_bsk - ln S)   (the differences to the maximum over s formed in fp64, as iwae_rows)
 //   q = softmax(logits_b) (row_lse_parts), nent_b = sum_k q ln q,  L_b = sum_k q_bk l_bk + nent_b
 //   rw_r = q_bk softmax_s(log w'_bsk)_s (may be null: forward only) -- the weight every per-row backward epilogue takes
+//   vs_r = softmax_s(log w'_bsk)_s alone (may be null; GMVAE_GRAD_DREG: z_head_bwd_dreg's second weight -- not rw / q, q can be denormal)
 //   dlogits_bj = q_bj (l_bj - sum_k q_bk l_bk) + q_bj (ln q_bj - nent_b)
 //   pb[b] = (-L_b, sum_k q mean_s nll, sum_k q mean_s kl, 0) for loss_tail (S = 1 form), nent[b]
 // terms4 (may be null): [R][4] = logpx, logq, logp, log w'.  dlogits holds l_bk between the two passes over k (the lane that
@@ -123,8 +124,9 @@ __global__ __launch_bounds__(256) void ymarg_rows(const float* __restrict__ part
 __global__ __launch_bounds__(256) void ymarg_iw_rows(const float* __restrict__ part, int nparts, const float* __restrict__ logq,
                                                      const float* __restrict__ logp, const float* __restrict__ logits,
                                                      float* __restrict__ logpx, float* __restrict__ logw, double* __restrict__ lw64,
-                                                     float* __restrict__ terms4, float* __restrict__ rw, float* __restrict__ dlogits,
-                                                     float* __restrict__ nent, float* __restrict__ pb, int B, int S, int K) {
+                                                     float* __restrict__ terms4, float* __restrict__ rw, float* __restrict__ vs,
+                                                     float* __restrict__ dlogits, float* __restrict__ nent, float* __restrict__ pb,
+                                                     int B, int S, int K) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
@@ -166,7 +168,9 @@ __global__ __launch_bounds__(256) void ymarg_iw_rows(const float* __restrict__ p
     if (rw)
       for (int s = 0; s < S; ++s) {
         const long long r = r0 + (long long)s * K;
-        rw[r] = q * expf((float)(lw64[r] - mx) - lrel);
+        const float sm = expf((float)(lw64[r] - mx) - lrel);
+        rw[r] = q * sm;
+        if (vs) vs[r] = sm;
       }
     dlogits[(long long)b * K + k] = lk;
     ne += q * lpi;

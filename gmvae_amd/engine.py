@@ -41,7 +41,7 @@ class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
                  temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
-                 y_inference: str = "gumbel"):
+                 y_inference: str = "gumbel", grad_estimator: str = "standard"):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -49,7 +49,11 @@ class Engine:
         B*K rows: eps is [B*K, L], u is not used, forward() returns rows / z / y of B*K rows; n_samples must be 1.
         "marginal_iw": y summed out and z importance-weighted over n_samples = S samples per component (GMVAE_OBJ_MARGINAL_Y_IW;
         at S = 1 the "marginal" objective).  Its steps have B*S*K rows, row (b*S + s)*K + k: eps is [B*S*K, L], u is not used,
-        forward(n_samples=S') returns rows / z / y of B*S'*K rows."""
+        forward(n_samples=S') returns rows / z / y of B*S'*K rows.
+        grad_estimator: "standard" -- the reparameterised gradient -- or "dreg": the doubly reparameterised gradient for the
+        inference network (include/gmvae_hip.h GMVAE_GRAD_DREG): the same bound and generative gradients, an encoder gradient
+        whose signal-to-noise ratio grows with n_samples.  Every step takes the general schedule.  Not for the GMVAE with
+        y_inference="gumbel".  Parameters and checkpoints are the same under both."""
         if y_inference not in L.Y_INFERENCE:
             raise ValueError(f"y_inference must be one of {L.Y_INFERENCE}, got {y_inference!r}")
         if y_inference == "marginal" and (L.MODEL_IDS.get(model) != L.MODEL_GMVAE or int(n_samples) != 1):
@@ -57,6 +61,11 @@ class Engine:
                              "components instead of sampled)")
         if y_inference == "marginal_iw" and L.MODEL_IDS.get(model) != L.MODEL_GMVAE:
             raise ValueError("y_inference='marginal_iw' sums y out over the GMVAE's mixture components: it needs the GMVAE model")
+        if grad_estimator not in L.GRAD_ESTIMATORS:
+            raise ValueError(f"grad_estimator must be one of {L.GRAD_ESTIMATORS}, got {grad_estimator!r}")
+        if grad_estimator == "dreg" and L.MODEL_IDS.get(model) == L.MODEL_GMVAE and y_inference == "gumbel":
+            raise ValueError("grad_estimator='dreg' is not available for the GMVAE with y_inference='gumbel' (its relaxed y is "
+                             "reparameterised too): use y_inference='marginal' or 'marginal_iw'")
         self.device = L.require_gpu()
         # data parallel: this process's shard index.  Row b of a local batch of B rows is global row rank*B + b for the
         # Philox counters (GmvaeDims.row0), so G ranks draw the noise of ONE step on the global batch of G*B rows.
@@ -83,6 +92,7 @@ class Engine:
         self.y_inference = y_inference
         self.marginal = y_inference in ("marginal", "marginal_iw")      # y enumerated over the K components
         self.marginal_iw = y_inference == "marginal_iw"
+        self.grad_estimator = grad_estimator
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -117,7 +127,8 @@ class Engine:
                            sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | extra_flags, **self.hp)
 
     def _obj_flags(self):
-        return L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
+        obj = L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
+        return obj | (L.GRAD_DREG if self.grad_estimator == "dreg" else 0)
 
     def _rows_per_x(self, S):
         """Sample-dependent rows per batch row at S samples: S K with y summed out over the K components, else S."""

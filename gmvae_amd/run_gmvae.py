@@ -51,6 +51,9 @@ def build_parser():
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
+    a("--grad_estimator", default="standard", choices=["standard", "dreg"], help="gradient of the inference network: the "
+      "reparameterised one, or the doubly reparameterised one (dreg: Tucker et al. 2018; vae, vae_gmp, and gmvae with "
+      "--y_inference=marginal or marginal_iw)")
     return p
 
 
@@ -79,6 +82,9 @@ def check_args(p, cfg):
             p.error("--y_inference=marginal_iw: --n_samples must be >= 1")
         if cfg.iw_samples:
             p.error("--iw_samples is not available with --y_inference=marginal_iw (use --iw_enum_samples)")
+    if cfg.grad_estimator == "dreg" and cfg.model == "gmvae" and cfg.y_inference == "gumbel":
+        p.error("--grad_estimator=dreg is not available for --model=gmvae with --y_inference=gumbel: use "
+                "--y_inference=marginal or marginal_iw")
     return cfg
 
 

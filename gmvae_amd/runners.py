@@ -80,18 +80,19 @@ def create_model(config, data_dim):
     """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0."""
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
+    ge = getattr(config, "grad_estimator", "standard")
     if config.model == "gmvae":
         return gmvae.create_gmvae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0,
                                   random_seed=config.random_seed, n_samples=ns,
-                                  y_inference=getattr(config, "y_inference", "gumbel"))
+                                  y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge)
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
-                              random_seed=config.random_seed, n_samples=ns)
+                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge)
     if config.model == "vae":
         return vae.create_vae(data_dim, config.latent_size, fcnet_hidden_sizes=hidden, sigma_min=0.0,
-                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns)
+                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge)
     raise ValueError(f"unknown model {config.model!r}")
 
 
@@ -178,7 +179,7 @@ def _verify_launch(eng, snap, batches, g, lr):
     gb = eng.gen_bias_vec if eng.gen_bias_vec is not None else hp.pop("gen_bias_init")
     hp.pop("gen_bias_init", None)
     sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0,
-                y_inference=eng.y_inference, **hp)
+                y_inference=eng.y_inference, grad_estimator=eng.grad_estimator, **hp)
     sh.rank, sh.noise_seed = eng.rank, eng.noise_seed
     with torch.no_grad():
         sh.params.copy_(p0); sh.m.copy_(m0); sh.v.copy_(v0)

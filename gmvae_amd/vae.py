@@ -110,15 +110,17 @@ class TrainableVAE(VAE):
 
 def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
-               random_seed=None, n_samples=1):
+               random_seed=None, n_samples=1, grad_estimator="standard"):
     """Factory with the signature of scripts/vae.py:191-200 (+ n_samples, the
-    IWAE extension of SURVEY.md A15; 1 == the reference)."""
+    IWAE extension of SURVEY.md A15; 1 == the reference; + grad_estimator: "dreg" = the doubly
+    reparameterised gradient for the encoder, Engine)."""
     if fcnet_hidden_sizes is None:
         fcnet_hidden_sizes = [latent_size]                     # scripts/vae.py:228-229
     name = "vae_gmp" if mixture_components > 1 else "vae"
     engine = Engine(name, data_size, latent_size, mixture_components, fcnet_hidden_sizes, n_samples=n_samples,
                     sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, gen_bias_init=gen_bias_init,
-                    random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn))
+                    random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
+                    grad_estimator=grad_estimator)
     if mixture_components > 1:
         def prior():
             v = engine.views()

@@ -126,7 +126,30 @@ enum { GMVAE_SCHED_SAFE = 1,
         * (gmvae_step_schedule: "general+marginal_iw"); every entry point that runs a step honours it; gmvae_iw_bound refuses it
         * (GMVAE_E_DIMS); gmvae_iw_bound_enum_y ignores it.  GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS if it is set
         * together with GMVAE_OBJ_MARGINAL_Y, B*S*K > 2^30 or (row0 + B)*S*K >= 2^38. */
-       GMVAE_OBJ_MARGINAL_Y_IW = 8 };
+       GMVAE_OBJ_MARGINAL_Y_IW = 8,
+       /* gradient estimator of the INFERENCE network (encoder / encoder_gmm) on the importance-weighted bounds: the doubly
+        * reparameterised gradient (Tucker et al. 2018, "DReG"; at S == 1 the path-derivative "sticking the landing" estimator
+        * of Roeder et al. 2017) instead of the plain reparameterised one.  Unbiased for the same bound; the bound, the tail and
+        * every generative gradient (decoder, prior network, mixture prior, encoder_y through the closed-form dlogits) are the
+        * standard step's.  With w the row weight of the step (softmax_s(log w) for the VAE family, q_bk softmax_s(log w'_bsk)
+        * under GMVAE_OBJ_MARGINAL_Y_IW, q_bk under GMVAE_OBJ_MARGINAL_Y, 1 at S == 1), dz the decoder's data gradient (scaled
+        * by w), pterm = d(-log p(z))/dz and v = softmax_s(log w) of the row's own sample group (1 at S == 1), loss = -bound:
+        *   standard:  dmu_q = dz + w pterm                       dsig_q = dmu_q eps - w / sig_q
+        *   DReG:      dmu_q = v (dz + w pterm - w eps / sig_q)   dsig_q = dmu_q eps
+        * -- the score of q through its own parameters is dropped, the path through z keeps d log q / dz = -eps / sig_q (the
+        * clamped sig_q where sigma_min is active; draw_q and its sigma_min mask are unchanged).  Total weight on the path:
+        * softmax_s^2 for the VAE family, q_bk softmax_s^2 under GMVAE_OBJ_MARGINAL_Y_IW.
+        * Covers the VAE and VAE_GMP at any S >= 1 and the GMVAE under GMVAE_OBJ_MARGINAL_Y / GMVAE_OBJ_MARGINAL_Y_IW.  REFUSED
+        * (GMVAE_E_DIMS from gmvae_workspace_bytes and every entry point that runs a step, before any launch) for the Gumbel
+        * GMVAE: its relaxed y is reparameterised too, its bound carries an analytic entropy term in place of log q(y), and
+        * the prior network's backward would have to run twice (w for its weights, w v for the y path).
+        * A step with the bit takes the general schedule at every S (gmvae_step_schedule appends "+dreg": "general+dreg",
+        * "general+marginal_iw+dreg"); every entry point that runs a step honours it (gmvae_step, the train and pipeline
+        * graphs, gmvae_dp_step / gmvae_dp_graph_create, the bench and profile loops); forward-only entries ignore it;
+        * gmvae_iw_bound* and gmvae_posterior_* mask it off.  The workspace grows by B*S*K floats under GMVAE_OBJ_MARGINAL_Y_IW
+        * at S > 1 (v, behind every other buffer) and is otherwise the same size and layout.  No atomics: eager and captured
+        * steps give the same bits. */
+       GMVAE_GRAD_DREG = 16 };
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
