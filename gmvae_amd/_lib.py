@@ -122,6 +122,8 @@ Y_INFERENCE = ("gumbel", "marginal", "marginal_iw")
 GRAD_DREG = 16        # ... gradient estimator of the inference network: doubly reparameterised (include/gmvae_hip.h GMVAE_GRAD_DREG)
 # Engine(grad_estimator=...): the plain reparameterised gradient, or the doubly reparameterised one (Tucker et al. 2018)
 GRAD_ESTIMATORS = ("standard", "dreg")
+OBJ_LABELS = 32       # ... objective: observed components clamp y per example (semi-supervised; include/gmvae_hip.h GMVAE_OBJ_LABELS)
+LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph
 
 
 ACTS = {"relu": 0, "tanh": 1, "sigmoid": 2, "elu": 3}       # GMVAE_ACT_*: GmvaeDims.hidden_act
@@ -169,6 +171,13 @@ def workspace_bytes(dims, model):
     b = C.c_uint64()
     check(lib.gmvae_workspace_bytes(C.byref(dims), model, C.byref(b)), "gmvae_workspace_bytes")
     return b.value
+
+
+def workspace_offset(dims, model, name):
+    """Byte offset of a named workspace buffer (include/gmvae_hip.h gmvae_workspace_offset)."""
+    off = C.c_uint64()
+    check(lib.gmvae_workspace_offset(C.byref(dims), int(model), name.encode(), C.byref(off)), f"gmvae_workspace_offset({name})")
+    return off.value
 
 
 def iw_bound_workspace_bytes(dims, model):

@@ -35,6 +35,7 @@
 #include "evalf.hpp"
 #include "iwbound.hpp"
 #include "ymarg.hpp"
+#include "semisup.hpp"
 
 using namespace gmvae;
 
@@ -64,6 +65,8 @@ static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K * d.S : d
 // GMVAE_GRAD_DREG: the doubly reparameterised gradient for the inference network (kernels.hpp z_head_bwd_dreg) -- the backward of
 // the general schedule alone; forward-only passes do not depend on it
 static bool dreg_grad(const GmvaeDims& d) { return (d.sched_flags & GMVAE_GRAD_DREG) != 0; }
+// GMVAE_OBJ_LABELS: observed components clamp y per example (semisup.hpp ymarg_sup_rows in ymarg_rows' / ymarg_iw_rows' place)
+static bool sup_labels(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_LABELS) != 0; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -170,8 +173,15 @@ static int check_dims(const GmvaeDims* d, int model) {
 }
 // the entry points that run (or size) a training step: GMVAE_GRAD_DREG is refused for the Gumbel GMVAE (its relaxed y is
 // reparameterised too and its bound carries an analytic entropy term: the prior network's backward would have to run twice)
+// ... and GMVAE_OBJ_LABELS for everything but the GMVAE with y summed out (check_label_dims: gmvae_forward's check too)
+static int check_label_dims(const GmvaeDims* d, int model) {
+  if (!sup_labels(*d)) return 0;
+  if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
+  return marginal_y(*d) ? 0 : GMVAE_E_DIMS;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
+  if (int e = check_label_dims(d, model)) return e;
   if (dreg_grad(*d) && model == GMVAE_MODEL_GMVAE && !marginal_y(*d)) return GMVAE_E_DIMS;
   return 0;
 }
@@ -204,6 +214,10 @@ struct WS {
   float* hd[MAXH + 2];   // decoder activations [R, dim[i]]
   float *gx, *logits, *y, *nent, *pp, *qp, *z, *logq, *logp, *logpx, *logw, *rw, *resp, *g, *part;
   float* vs;               // GMVAE_GRAD_DREG under GMVAE_OBJ_MARGINAL_Y_IW at S > 1: softmax_s(log w'_bsk) per row (ymarg_iw_rows)
+  // GMVAE_OBJ_LABELS: the caller's label sets [GMVAE_LABEL_SLOTS][pad4(B)] and classification weight (read only), and
+  // ymarg_sup_rows' per-example (-ln q_bc, labelled, hit) for sup_tail
+  int32_t* labels;
+  float *sup_weight, *sup_trip;
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -522,6 +536,11 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.ev_dbg = reinterpret_cast<unsigned long long*>(take(2ull * 1024 * 16));
   }
   if (dreg_grad(d) && marginal_iw_obj(d) && d.S > 1) w.vs = take(R);      // (last: dims without the bit keep their size and every offset)
+  if (sup_labels(d)) {                            // (behind vs: dims without the bit keep their size and every offset)
+    w.labels = reinterpret_cast<int32_t*>(take((uint64_t)GMVAE_LABEL_SLOTS * pad4(B)));
+    w.sup_weight = take(4);
+    w.sup_trip = take(3 * B);
+  }
   w.bytes = off;
 }
 
@@ -893,6 +912,7 @@ struct StepArgs {
   int span_slot = 0;           // ... into this slot of WS::spans (two consecutive steps can be stamped)
   bool dp_images = false;      // data-parallel graph: the Adam launch after the all-reduce scatters the weight images
   float* tail_log = nullptr;   // train graph: this step's slot of the per-step tail log (may be null)
+  int label_slot = 0;          // GMVAE_OBJ_LABELS: which of the workspace's label sets the step reads (step i of a train graph: i)
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -1974,7 +1994,9 @@ static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
 
 static int run_step_impl(Ctx& cx, const StepArgs& a);
 static int run_step(Ctx& cx, const StepArgs& a) {
-  if (a.backward || !dreg_grad(*a.d)) return run_step_impl(cx, a);
+  // (under GMVAE_OBJ_LABELS the bit stays: the label regions lie behind DReG's v in the workspace, and the labelled objectives
+  //  take the general schedule anyway)
+  if (a.backward || !dreg_grad(*a.d) || sup_labels(*a.d)) return run_step_impl(cx, a);
   GmvaeDims d = *a.d;                            // forward only: the bound, the tail and the outputs do not depend on the estimator
   d.sched_flags &= ~GMVAE_GRAD_DREG;
   StepArgs b = a;
@@ -2311,7 +2333,15 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   }
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
   const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
-  if (enum_chunk) {             // log w' = log p(x|z) + log p - log q per row (no nent term: iw_merge_enum weighs the rows by q)
+  const bool sup = sup_labels(d) && marg && !enum_chunk;
+  if (sup && (!w.labels || a.label_slot < 0 || a.label_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  if (sup) {                    // GMVAE_OBJ_LABELS: the per-example terms with observed components clamping y (any S >= 1)
+    hipLaunchKernelGGL(ymarg_sup_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits,
+                       w.labels + (size_t)a.label_slot * pad4((uint64_t)B), w.sup_weight, w.logpx, w.logw, w.lw64, a.row_terms,
+                       a.backward ? w.rw : (float*)nullptr, a.backward ? w.vs : (float*)nullptr, w.dlogits, w.nent, w.pb,
+                       w.sup_trip, B, d.S, K);
+    rowk(cx, "ymarg_sup_rows");
+  } else if (enum_chunk) {      // log w' = log p(x|z) + log p - log q per row (no nent term: iw_merge_enum weighs the rows by q)
     hipLaunchKernelGGL(row_terms, dim3(grid_for(R, 256, 1 << 22)), dim3(256), 0, st, w.part, nparts, w.logq, w.logp,
                        (const float*)nullptr, S, w.logpx, w.logw, a.row_terms, R, (double*)nullptr);
     rowk(cx, "row_terms");
@@ -2343,6 +2373,10 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
                        gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
                        (S > 1 || marg) ? w.pb : (const float*)nullptr);
     rowk(cx, "loss_tail");
+    if (sup) {                   // tail[5..7]: the labelled examples' cross-entropy sum, count and hits
+      hipLaunchKernelGGL(sup_tail, dim3(1), dim3(256), 0, st, w.sup_trip, tail, B);
+      rowk(cx, "sup_tail");
+    }
   }
   if (a.z_out) hipMemcpyAsync(a.z_out, w.z, (size_t)R * Lz * 4, hipMemcpyDeviceToDevice, st);
   if (a.y_out && gm) hipMemcpyAsync(a.y_out, w.y, (size_t)R * K * 4, hipMemcpyDeviceToDevice, st);
@@ -2601,7 +2635,9 @@ static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1
 // ---- gmvae_iw_bound: the workspace is the forward's at these dims (S = the chunk), then the call's own region (byte offsets);
 // gmvae_iw_bound_enum_y: the same at its marginal dims (S K rows per batch row; no u)
 struct IwLay { uint64_t eps, u, rows, ftail, state, rsum, bytes; };
-static void iw_lay(const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
+static void iw_lay(const GmvaeDims& d0, int model, const Layout& L, IwLay& o) {
+  GmvaeDims d = d0;
+  d.sched_flags &= ~GMVAE_OBJ_LABELS;            // (the bounds and posteriors mask the bit: their sizes must not carry the label regions)
   WS w;
   carve(d, model, L, nullptr, w);
   uint64_t off = (w.bytes + 255) / 256 * 256;
@@ -2621,7 +2657,7 @@ static void iw_lay(const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
 static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* x, const float* params, uint64_t n,
                         float* bound_out, float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG);      // (the operand images are prepared here, once per call)
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);      // (the operand images are prepared here, once per call)
   Layout L;
   build_layout(d, model, L);
   WS w;
@@ -2732,7 +2768,7 @@ static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, con
 static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
   if (!dims) return GMVAE_E_NULL;
   d = *dims;
-  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG);
+  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);
   if (int e = check_dims(&d, model)) return e;
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
@@ -2808,7 +2844,7 @@ static void pc_lay(const GmvaeDims& d, const IwLay& il, PcLay& o) {
 static int run_posterior_component(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
                                    float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG);
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);
   const int model = GMVAE_MODEL_VAE_GMP;
   Layout L;
   build_layout(d, model, L);
@@ -2941,7 +2977,8 @@ int gmvae_step(const GmvaeDims* dims, int model, const uint8_t* x, const float* 
 /* internal: gmvae_step with the end-of-step Adam fused in (single device; used by the train graph) */
 static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v,
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float b1,
-                          float b2, float eps_, hipStream_t st, bool imgs_ready = false, float* tail_log = nullptr) {
+                          float b2, float eps_, hipStream_t st, bool imgs_ready = false, float* tail_log = nullptr,
+                          int label_slot = 0) {
   Ctx cx;
   cx.st = st;
   StepArgs a = {dims, model, x, nullptr, nullptr, params, grads, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
@@ -2949,6 +2986,7 @@ static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, fl
   a.adam_p = params; a.adam_m = m; a.adam_v = v; a.lr = lr; a.beta1 = b1; a.beta2 = b2; a.epsilon = eps_;
   a.imgs_ready = imgs_ready;
   a.tail_log = tail_log;
+  a.label_slot = label_slot;
   return run_step(cx, a);
 }
 
@@ -2956,6 +2994,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
                   const float* params, float* tail, float* row_terms, float* z_out, float* y_out, float* logits_out,
                   void* workspace, uint64_t seed, uint64_t step, void* stream) {
   if (int e = check_dims(dims, model)) return e;
+  if (int e = check_label_dims(dims, model)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
@@ -3614,6 +3653,9 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
                               uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2, float epsilon,
                               float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
+  // GMVAE_OBJ_LABELS: step i reads label set i of the workspace; the pipeline graph gathers its batches by index and has no
+  // label gather
+  if (sup_labels(*dims) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3642,7 +3684,7 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
     // weight images written by the step before it (same graph, nothing in between)
     for (int s = 0; s < n_steps && rc == 0; ++s)
       rc = step_with_adam(dims, model, x + s * xstride, params, m, v, grads, workspace, seed, step_dev, lr, beta1, beta2, epsilon, cs,
-                          s > 0, tail_log ? tail_log + (size_t)s * GMVAE_TAIL : nullptr);
+                          s > 0, tail_log ? tail_log + (size_t)s * GMVAE_TAIL : nullptr, s);
     he = hipStreamEndCapture(cs, &tg->graph);
     if (rc == 0 && he != hipSuccess) rc = (int)he;
   }
@@ -3725,8 +3767,8 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
-           dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+           sup_labels(d) ? "+labels" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3760,7 +3802,8 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"dy", w.dy}, {"dlogits", w.dlogits}, {"dbuf0", w.dbuf[0]}, {"dbuf1", w.dbuf[1]}, {"dbuf2", w.dbuf[2]},
       {"slabs", w.slabs}, {"s1", w.s1}, {"s4", w.s4}, {"eps", w.eps}, {"u", w.u},
       {"stamps", reinterpret_cast<float*>(w.stamps)}, {"gstamps", reinterpret_cast<float*>(w.gstamps)},
-      {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)}};
+      {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)},
+      {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;
@@ -3860,7 +3903,7 @@ int gmvae_comm_destroy(void* comm) {
 static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v, float* grads,
                         void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2,
                         float epsilon, void* comm, hipStream_t st, bool in_graph, bool imgs_ready, float* tail_log = nullptr,
-                        int span_slot = -1, Prof* prof = nullptr) {
+                        int span_slot = -1, Prof* prof = nullptr, int label_slot = 0) {
   if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !comm || !g_rccl.h || !step_dev) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace)) return GMVAE_E_ALIGN;
@@ -3884,6 +3927,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   a.dp_images = scatter;
   a.imgs_ready = scatter && imgs_ready;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
+  a.label_slot = label_slot;
   cx.prof = prof;
   int rc = run_step(cx, a);
   if (rc) return rc;
@@ -4030,6 +4074,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
+  if (sup_labels(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;
@@ -4049,7 +4094,8 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
   if (rc == 0) {
     for (int s = 0; s < n_steps && rc == 0; ++s)
       rc = dp_step_impl(dims, model, x + (size_t)s * dims->B * dims->D, params, m, v, grads, workspace, seed, step_dev, lr,
-                        beta1, beta2, epsilon, comm, cs, true, s > 0, tail_log ? tail_log + (size_t)s * GMVAE_TAIL : nullptr);
+                        beta1, beta2, epsilon, comm, cs, true, s > 0, tail_log ? tail_log + (size_t)s * GMVAE_TAIL : nullptr, -1,
+                        nullptr, s);
     he = hipStreamEndCapture(cs, &tg->graph);
     if (rc == 0 && he != hipSuccess) rc = (int)he;
   }

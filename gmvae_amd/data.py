@@ -42,14 +42,18 @@ def binarize(pixels: torch.Tensor, rows: Optional[torch.Tensor] = None, row0: in
 class DeviceDataset:
     """uint8 pixels [N, ...] (+ labels) resident on the GPU; `next_batch(B)` returns a freshly binarised uint8
     [B, D] batch and its labels.  shuffle=True draws a new permutation per epoch on the device; every batch gets
-    new uniforms (step counter), as the reference's `repeat()` after `map()` does."""
+    new uniforms (step counter), as the reference's `repeat()` after `map()` does.  y_observed (optional): int32 [N],
+    resident too -- the component a semi-supervised step may see for each row, -1 = unlabelled."""
 
-    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0):
+    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None):
         dev = L.require_gpu()
         pixels = torch.as_tensor(pixels)
         self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.uint8).contiguous()
         self.labels = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
+        self.y_observed = None if y_observed is None else torch.as_tensor(y_observed).to(dev, torch.int32).contiguous()
         self.N, self.D = self.pixels.shape
+        if self.y_observed is not None and self.y_observed.shape != (self.N,):
+            raise ValueError(f"y_observed must have one entry per row ({self.N}), got {tuple(self.y_observed.shape)}")
         self.shuffle, self.seed = shuffle, int(seed)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(self.seed)

@@ -24,8 +24,8 @@ class _ElboFn(torch.autograd.Function):
     forward+backward (the backward pass has already run when this returns)."""
 
     @staticmethod
-    def forward(ctx, params, engine, x, eps, u):
-        buf = engine.step(x, eps, u)
+    def forward(ctx, params, engine, x, eps, u, y_observed=None):
+        buf = engine.step(x, eps, u, y_observed=y_observed)
         P = engine.P
         ctx.engine_buf = buf
         ctx.P = P
@@ -34,14 +34,27 @@ class _ElboFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         buf, P = ctx.engine_buf, ctx.P
-        return buf[:P] * (grad_out / buf[P + 4]), None, None, None, None
+        return buf[:P] * (grad_out / buf[P + 4]), None, None, None, None, None
+
+
+def check_semi_supervised(model, y_inference, semi_supervised, sup_weight):
+    """The argument check of Engine(semi_supervised=, sup_weight=) (no device needed)."""
+    if not semi_supervised:
+        return
+    if L.MODEL_IDS.get(model) != L.MODEL_GMVAE:
+        raise ValueError("semi_supervised=True clamps the GMVAE's y to observed components: it needs the GMVAE model")
+    if y_inference == "gumbel":
+        raise ValueError("semi_supervised=True needs y summed out: use y_inference='marginal' or 'marginal_iw'")
+    if not float(sup_weight) >= 0.0:
+        raise ValueError(f"sup_weight must be >= 0, got {sup_weight!r}")
 
 
 class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
                  temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
-                 y_inference: str = "gumbel", grad_estimator: str = "standard"):
+                 y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
+                 sup_weight: float = 1.0):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -53,7 +66,12 @@ class Engine:
         grad_estimator: "standard" -- the reparameterised gradient -- or "dreg": the doubly reparameterised gradient for the
         inference network (include/gmvae_hip.h GMVAE_GRAD_DREG): the same bound and generative gradients, an encoder gradient
         whose signal-to-noise ratio grows with n_samples.  Every step takes the general schedule.  Not for the GMVAE with
-        y_inference="gumbel".  Parameters and checkpoints are the same under both."""
+        y_inference="gumbel".  Parameters and checkpoints are the same under both.
+        semi_supervised (GMVAE with y_inference "marginal" or "marginal_iw"; include/gmvae_hip.h GMVAE_OBJ_LABELS): step / loss /
+        forward / train_step / dp_step take y_observed, an int tensor [B] of observed components (-1 or any value outside
+        [0, K): unlabelled).  A labelled example's loss is its own component's term plus sup_weight * (-ln q(y|x)); an
+        unlabelled one's is the marginal objective's.  Parameters and checkpoints are the same with and without it."""
+        check_semi_supervised(model, y_inference, semi_supervised, sup_weight)
         if y_inference not in L.Y_INFERENCE:
             raise ValueError(f"y_inference must be one of {L.Y_INFERENCE}, got {y_inference!r}")
         if y_inference == "marginal" and (L.MODEL_IDS.get(model) != L.MODEL_GMVAE or int(n_samples) != 1):
@@ -93,6 +111,8 @@ class Engine:
         self.marginal = y_inference in ("marginal", "marginal_iw")      # y enumerated over the K components
         self.marginal_iw = y_inference == "marginal_iw"
         self.grad_estimator = grad_estimator
+        self.semi_supervised = bool(semi_supervised)
+        self.sup_weight = float(sup_weight)
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -128,7 +148,7 @@ class Engine:
 
     def _obj_flags(self):
         obj = L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
-        return obj | (L.GRAD_DREG if self.grad_estimator == "dreg" else 0)
+        return obj | (L.GRAD_DREG if self.grad_estimator == "dreg" else 0) | (L.OBJ_LABELS if self.semi_supervised else 0)
 
     def _rows_per_x(self, S):
         """Sample-dependent rows per batch row at S samples: S K with y summed out over the K components, else S."""
@@ -242,7 +262,32 @@ class Engine:
             del self._ws[key]
         if key not in self._ws:
             self._ws[key] = torch.zeros(n, dtype=torch.float32, device=self.device)
+            if self.semi_supervised:
+                # the library only reads these two regions, and zeros would mean "component 0 observed, weight 0"
+                self._label_slots(d, self._ws[key]).fill_(-1)
+                off = L.workspace_offset(d, self.model, "sup_weight") // 4
+                self._ws[key][off:off + 1].fill_(self.sup_weight)
         return d, self._ws[key]
+
+    def _label_slots(self, d, ws) -> torch.Tensor:
+        """int32 view [LABEL_SLOTS, B] of the workspace's label sets (each slot starts 16-byte aligned)."""
+        B4 = (d.B + 3) // 4 * 4
+        off = L.workspace_offset(d, self.model, "labels") // 4
+        return ws.view(torch.int32)[off:off + L.LABEL_SLOTS * B4].view(L.LABEL_SLOTS, B4)[:, :d.B]
+
+    def _set_labels(self, d, ws, y_observed):
+        """Slot 0 of the workspace's label sets <- y_observed (device-side copy, no host sync); None: all unlabelled."""
+        if not self.semi_supervised:
+            if y_observed is not None:
+                raise ValueError("y_observed needs an engine created with semi_supervised=True")
+            return
+        slot = self._label_slots(d, ws)[0]
+        if y_observed is None:
+            slot.fill_(-1)
+            return
+        if y_observed.dtype.is_floating_point or y_observed.dtype == torch.bool or y_observed.numel() != d.B:
+            raise ValueError(f"y_observed must be an int tensor of {d.B} observed components (-1: unlabelled)")
+        slot.copy_(y_observed.reshape(-1), non_blocking=True)
 
     @staticmethod
     def _as_u8(x: torch.Tensor) -> torch.Tensor:
@@ -275,13 +320,15 @@ class Engine:
         return t
 
     # ------------------------------------------------------------------ ops
-    def step(self, x, eps=None, u=None, use_step_dev: bool = False, row0: Optional[int] = None) -> torch.Tensor:
+    def step(self, x, eps=None, u=None, use_step_dev: bool = False, row0: Optional[int] = None,
+             y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Fused forward + backward.  Returns the [P + TAIL] buffer of gradient
         SUMS and loss sums (see include/gmvae_hip.h).  eps/u None -> Philox, keyed by
         (noise_seed, global_step, global row = row0 + b; row0 defaults to rank * B)."""
         x = self._prep_x(x)
         B = x.shape[0]
         d, ws = self._workspace(B, row0=row0)
+        self._set_labels(d, ws, y_observed)
         eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
         u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
@@ -291,11 +338,11 @@ class Engine:
         self._keep = (x, eps, u)
         return self.grads
 
-    def loss(self, x, eps=None, u=None) -> torch.Tensor:
+    def loss(self, x, eps=None, u=None, y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Differentiable scalar: loss.backward() fills params.grad."""
-        return _ElboFn.apply(self.params, self, x, eps, u)
+        return _ElboFn.apply(self.params, self, x, eps, u, y_observed)
 
-    def forward(self, x, eps=None, u=None, n_samples: Optional[int] = None):
+    def forward(self, x, eps=None, u=None, n_samples: Optional[int] = None, y_observed: Optional[torch.Tensor] = None):
         """Forward only.  dict(tail[8], rows[R,4]=(logpx,logq,logp,logw), z, y, logits)."""
         x = self._prep_x(x)
         B = x.shape[0]
@@ -303,6 +350,7 @@ class Engine:
         if self.marginal and not self.marginal_iw and S != 1:
             raise ValueError("y_inference='marginal' enumerates y over the K components: n_samples must be 1")
         d, ws = self._workspace(B, S)
+        self._set_labels(d, ws, y_observed)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
@@ -494,11 +542,11 @@ class Engine:
             self.step_dev.fill_(self.global_step)   # one source of truth: graphs replayed later start from here
 
     def train_step(self, x, eps=None, u=None, lr: float = 1e-3, all_reduce: bool = True,
-                   row0: Optional[int] = None) -> torch.Tensor:
+                   row0: Optional[int] = None, y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One full reference step: fwd + bwd (+ RCCL all-reduce) + Adam.
         Returns the [TAIL] loss sums (device tensor; no host sync)."""
         import torch.distributed as dist
-        self.step(x, eps, u, row0=row0)
+        self.step(x, eps, u, row0=row0, y_observed=y_observed)
         if all_reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             from . import parallel
             parallel.all_reduce_flat(self.grads)     # ONE collective: grads + loss sums + count
@@ -553,10 +601,11 @@ class Engine:
         self.rccl_nranks = n.value
         return comm
 
-    def dp_step(self, x, lr: float = 1e-3):
+    def dp_step(self, x, lr: float = 1e-3, y_observed: Optional[torch.Tensor] = None):
         """gmvae_dp_step: one C call enqueues step + RCCL all-reduce + Adam on the current stream."""
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
+        self._set_labels(d, ws, y_observed)
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
@@ -578,6 +627,8 @@ class Engine:
         do_ar = all_reduce and ((dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
                                 or getattr(self, "_comm", None) is not None)
         n_steps = int(n_steps)
+        if self.semi_supervised and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a semi-supervised train graph holds at most {L.LABEL_SLOTS} steps (one label set per step), got {n_steps}")
         key = (B, lr, do_ar, n_steps)
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)   # eager steps may have run since the capture
@@ -587,6 +638,12 @@ class Engine:
         else:
             static_x = torch.zeros(n_steps, B, self.D, dtype=torch.uint8, device=self.device)
         d, ws = self._workspace(B)
+        # semi-supervised: step i of the graph reads label set i of the workspace; the caller fills replay.y_observed [n_steps, B]
+        # (int32, -1 = unlabelled) next to static_x
+        y_obs = None
+        if self.semi_supervised:
+            y_obs = self._label_slots(d, ws)[:n_steps]
+            y_obs.fill_(-1)
         self.step_dev.fill_(self.global_step)
         # per-step tails of one launch (loss sums + count; all-reduced under data parallelism): replay.tail_log
         tail_log = torch.zeros(n_steps, L.TAIL, dtype=torch.float32, device=self.device)
@@ -608,7 +665,7 @@ class Engine:
                     if rc2:
                         L.check(rc2, "gmvae_train_graph_launch")
                     self.global_step += n_steps
-                replay.tail_log = tail_log
+                replay.tail_log, replay.y_observed = tail_log, y_obs
                 self._graphs[key] = (static_x, replay, handle)
                 return static_x, replay
             if rc == 0:
@@ -618,10 +675,13 @@ class Engine:
             batches = [static_x] if n_steps == 1 else list(static_x.unbind(0))
 
             def replay():
+                ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
                 for i, xb in enumerate(batches):
-                    self.dp_step(xb, lr)
+                    self.dp_step(xb, lr, y_observed=None if ys is None else ys[i])
                     tail_log[i].copy_(self.grads[self.P:])
-            replay.tail_log = tail_log
+                if ys is not None:
+                    y_obs[0].copy_(ys[0])
+            replay.tail_log, replay.y_observed = tail_log, y_obs
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         if do_ar:
@@ -630,13 +690,16 @@ class Engine:
             batches = [static_x] if n_steps == 1 else list(static_x.unbind(0))
 
             def replay():
+                ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
                 for i, xb in enumerate(batches):
-                    self.step(xb, use_step_dev=True)
+                    self.step(xb, use_step_dev=True, y_observed=None if ys is None else ys[i])
                     parallel.all_reduce_flat(self.grads)
                     self.adam(lr, use_step_dev=True)
                     self.global_step += 1
                     tail_log[i].copy_(self.grads[self.P:])
-            replay.tail_log = tail_log
+                if ys is not None:
+                    y_obs[0].copy_(ys[0])
+            replay.tail_log, replay.y_observed = tail_log, y_obs
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         torch.cuda.synchronize()
@@ -655,7 +718,7 @@ class Engine:
                 L.check(rc, "gmvae_train_graph_launch")
             self.global_step += n_steps
 
-        replay.tail_log = tail_log
+        replay.tail_log, replay.y_observed = tail_log, y_obs
         self._graphs[key] = (static_x, replay, handle)
         return static_x, replay
 
@@ -666,6 +729,9 @@ class Engine:
         steps first binarises its own batch on the device (scripts/runners.py:44-47), rows taken from `dataset`
         (gmvae_amd.data.DeviceDataset: resident uint8 pixels + an epoch permutation on the device).  Returns
         replay(): refills the row indices (device-to-device) and launches the graph; nothing crosses PCIe."""
+        if self.semi_supervised:
+            raise ValueError("capture_train_pipeline gathers its batches by index inside the graph and has no label gather: a "
+                             "semi-supervised engine trains through capture_train_step (replay.y_observed)")
         n_steps = int(n_steps)
         key = ("pipeline", id(dataset), B, lr, n_steps)
         if key in self._graphs:

@@ -79,19 +79,21 @@ class TrainableGMVAE(GMVAE):
             raise RuntimeError("run_model needs the fused HIP engine: build the model with create_gmvae()")
         return self._engine
 
-    def run_model(self, images, targets, labels=None, eps=None, u=None):
+    def run_model(self, images, targets, labels=None, eps=None, u=None, y_observed=None):
         """Batch-mean loss = nll + kl_div_z + nent (scripts/gmvae.py:223-274); ELBO = -loss
         (the +ln K constant is omitted, as in the reference).  eps [B*S,L] / u [B*S,K]:
-        optional explicit noise (parity mode); default is in-kernel Philox."""
+        optional explicit noise (parity mode); default is in-kernel Philox.  labels: the ground truth cluster_acc is
+        scored against, never seen by the objective.  y_observed (a model created with semi_supervised=True): int [B],
+        the observed component of each example or -1 -- those examples' y is clamped in the loss (Engine)."""
         self._last_labels = labels
-        return base._targets_guard(self._need_engine().loss(images, eps, u), images, targets)
+        return base._targets_guard(self._need_engine().loss(images, eps, u, y_observed), images, targets)
 
-    def compute_loss(self, images, n_samples=None, labels=None, eps=None, u=None):
+    def compute_loss(self, images, n_samples=None, labels=None, eps=None, u=None, y_observed=None):
         e = self._need_engine()
         if n_samples is not None and n_samples != e.S:
             raise ValueError(f"model was created with n_samples={e.S}")
         self._last_labels = labels
-        return e.loss(images, eps, u)
+        return e.loss(images, eps, u, y_observed)
 
     def iw_bound(self, images, n_samples, chunk=None):
         """Per-example importance-weighted bound at n_samples samples (the A15 bound compute_loss(n_samples=S) reports),
@@ -117,10 +119,13 @@ class TrainableGMVAE(GMVAE):
     def summaries(self):
         """nll_scalar, kl_div_z, nent, elbo, cluster_acc of the last run_model
         (scripts/gmvae.py:255,259,264,268,272).  cluster_acc is evaluated lazily,
-        like TF evaluates it only when the summary is fetched."""
+        like TF evaluates it only when the summary is fetched.  A semi-supervised step with labelled examples adds
+        sup_ce (their mean -ln q(y|x)) and sup_acc (the share whose argmax q(y|x) is the observed component)."""
         e = self._need_engine()
         t = e.grads[e.P:].detach()
         out = {"nll_scalar": t[1] / t[4], "kl_div_z": t[2] / t[4], "nent": t[3] / t[4], "elbo": -t[0] / t[4]}
+        if e.semi_supervised and t[6].item() > 0:
+            out["sup_ce"], out["sup_acc"] = t[5] / t[6], t[7] / t[6]
         if self._last_labels is not None:
             d, ws = e._workspace(int(t[4].item()))
             out["cluster_acc"] = utils.cluster_acc(self.last_logits(), self._last_labels, self.mix_components)
@@ -145,8 +150,10 @@ class TrainableGMVAE(GMVAE):
 
 def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                  hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
-                 temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard"):
-    """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator: Engine).  y_inference="marginal" trains and
+                 temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
+                 semi_supervised=False, sup_weight=1.0):
+    """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
+    sup_weight: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
     importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
     a checkpoint of any loads in the others."""
@@ -155,7 +162,8 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
     engine = Engine("gmvae", data_size, latent_size, mixture_components, fcnet_hidden_sizes, n_samples=n_samples,
                     sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                     gen_bias_init=gen_bias_init, random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
-                    y_inference=y_inference, grad_estimator=grad_estimator)
+                    y_inference=y_inference, grad_estimator=grad_estimator, semi_supervised=semi_supervised,
+                    sup_weight=sup_weight)
     prior_gmm = base.ConditionalNormal(size=latent_size, hidden_layer_sizes=None,
                                        hidden_activation_fn=hidden_activation_fn, sigma_min=sigma_min,
                                        raw_sigma_bias=raw_sigma_bias, name="prior_gmm").bind(engine, L.NET_PRIOR_GMM)

@@ -54,6 +54,10 @@ def build_parser():
     a("--grad_estimator", default="standard", choices=["standard", "dreg"], help="gradient of the inference network: the "
       "reparameterised one, or the doubly reparameterised one (dreg: Tucker et al. 2018; vae, vae_gmp, and gmvae with "
       "--y_inference=marginal or marginal_iw)")
+    a("--labelled_per_class", type=int, default=0, help="gmvae with --y_inference=marginal or marginal_iw: train "
+      "semi-supervised -- this many training examples per class show their label to the objective (0 = off)")
+    a("--sup_weight", type=float, default=1.0, help="--labelled_per_class: weight of the classification term -ln q(y|x) "
+      "of a labelled example")
     return p
 
 
@@ -85,6 +89,10 @@ def check_args(p, cfg):
     if cfg.grad_estimator == "dreg" and cfg.model == "gmvae" and cfg.y_inference == "gumbel":
         p.error("--grad_estimator=dreg is not available for --model=gmvae with --y_inference=gumbel: use "
                 "--y_inference=marginal or marginal_iw")
+    if cfg.labelled_per_class < 0 or cfg.sup_weight < 0:
+        p.error("--labelled_per_class and --sup_weight must be >= 0")
+    if cfg.labelled_per_class > 0 and (cfg.model != "gmvae" or cfg.y_inference == "gumbel"):
+        p.error("--labelled_per_class needs --model=gmvae with --y_inference=marginal or marginal_iw")
     return cfg
 
 

@@ -81,11 +81,15 @@ def create_model(config, data_dim):
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
+    lpc = int(getattr(config, "labelled_per_class", 0) or 0)
+    if lpc > 0 and config.model != "gmvae":
+        raise ValueError("--labelled_per_class trains the GMVAE semi-supervised: it needs --model=gmvae")
     if config.model == "gmvae":
         return gmvae.create_gmvae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0,
                                   random_seed=config.random_seed, n_samples=ns,
-                                  y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge)
+                                  y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge,
+                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)))
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
@@ -142,6 +146,23 @@ def wait_for_checkpoint(path: str, poll_seconds: float = 60.0, max_wait: float |
     return path
 
 
+def select_labelled(labels, per_class: int, seed: int) -> np.ndarray:
+    """--labelled_per_class N: which rows of a split show their label to the semi-supervised objective.  int32 [n]: the label
+    where it is observed, -1 elsewhere.  For each class the first N of its rows in ONE permutation of the whole split seeded by
+    `seed` (a class with fewer rows shows them all).  The choice looks at the whole split, before any rank's shard is cut, so
+    every world size labels the same rows."""
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    out = np.full(labels.shape[0], -1, dtype=np.int32)
+    if per_class <= 0:
+        return out
+    perm = np.random.default_rng(int(seed)).permutation(labels.shape[0])
+    pl = labels[perm]
+    for c in np.unique(labels):
+        rows = perm[pl == c][:per_class]
+        out[rows] = c
+    return out
+
+
 def create_device_dataset(config, split="train", shuffle=True):
     """The input pipeline of scripts/runners.py:21-62 with the raw uint8 pixels resident in HBM (data.DeviceDataset):
     this rank's contiguous shard of the split's rows (+ labels), shuffled per epoch on the device; binarisation happens
@@ -158,7 +179,9 @@ def create_device_dataset(config, split="train", shuffle=True):
     else:
         pix, lab = np.ascontiguousarray(data[0]), data[1]
     a, b = parallel.shard_rows(pix.shape[0], rank, world)
-    return DeviceDataset(pix[a:b], lab[a:b], shuffle=shuffle, seed=(config.random_seed or 0) * 7919 + 17 + rank)
+    lpc = int(getattr(config, "labelled_per_class", 0) or 0)
+    yobs = select_labelled(lab, lpc, config.random_seed or 0)[a:b] if lpc > 0 else None
+    return DeviceDataset(pix[a:b], lab[a:b], shuffle=shuffle, seed=(config.random_seed or 0) * 7919 + 17 + rank, y_observed=yobs)
 
 
 def _graph_steps(every: int, cap: int = 32) -> int:
@@ -179,7 +202,8 @@ def _verify_launch(eng, snap, batches, g, lr):
     gb = eng.gen_bias_vec if eng.gen_bias_vec is not None else hp.pop("gen_bias_init")
     hp.pop("gen_bias_init", None)
     sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0,
-                y_inference=eng.y_inference, grad_estimator=eng.grad_estimator, **hp)
+                y_inference=eng.y_inference, grad_estimator=eng.grad_estimator, semi_supervised=eng.semi_supervised,
+                sup_weight=eng.sup_weight, **hp)
     sh.rank, sh.noise_seed = eng.rank, eng.noise_seed
     with torch.no_grad():
         sh.params.copy_(p0); sh.m.copy_(m0); sh.v.copy_(v0)
@@ -240,7 +264,10 @@ def run_train(config):
         except Exception as e:
             if rank == 0:
                 print(f"[run_train] in-library RCCL unavailable ({e}); torch.distributed all-reduce", flush=True)
-    run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "pipeline-graph")
+    # semi-supervised (--labelled_per_class): the pipeline graph has no label gather, so one device takes the branch that
+    # world > 1 takes -- binarise, fill the graph's label sets, replay
+    sup = eng.semi_supervised
+    run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else "pipeline-graph")
     verify_every = int(os.environ.get("GMVAE_VERIFY_EVERY", "0") or 0)      # debug canary: see _verify_launch
     run_train.launches = run_train.verified_launches = 0
     run_train.degraded = False
@@ -257,9 +284,10 @@ def run_train(config):
             if eager:
                 rows = ds.next_rows(B)
                 x = binarize(ds.pixels, rows=rows, seed=bseed, step=eng.global_step, out_row0=rank * B)
-                logs.append(eng.train_step(x, lr=lr).clone().view(1, -1))
+                yo = ds.y_observed[rows.long()] if sup else None
+                logs.append(eng.train_step(x, lr=lr, y_observed=yo).clone().view(1, -1))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1:
+            elif world == 1 and not sup:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -272,11 +300,13 @@ def run_train(config):
                 logs.append(replay.tail_log.clone())
                 last_x, last_rows = replay.batches[g - 1], replay.rows[g - 1]
             else:
-                sx, replay = eng.capture_train_step(B, lr=lr, all_reduce=True, n_steps=g)
+                sx, replay = eng.capture_train_step(B, lr=lr, all_reduce=world > 1, n_steps=g)
                 xs = sx if g > 1 else sx.unsqueeze(0)
                 for i in range(g):                          # this launch's batches, binarised on the device
                     last_rows = ds.next_rows(B)
                     binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
+                    if sup:
+                        replay.y_observed[i].copy_(ds.y_observed[last_rows.long()])
                 replay()
                 logs.append(replay.tail_log.clone())
                 last_x = xs[g - 1]
@@ -338,6 +368,10 @@ def run_train(config):
         if rank == 0 and (eng.global_step % every == 0 or eng.global_step > config.max_steps):
             rate = (eng.global_step - s0) / max(time.time() - t0, 1e-9)
             msg = f"Step {eng.global_step}, loss: {vals[-1]:f}  ({rate:.1f} global_step/sec)"
+            if sup:                                         # over the summary block's labelled examples (all ranks')
+                blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
+                if blk[1].item() > 0:
+                    msg += f"  sup_acc {blk[2].item() / blk[1].item():.4f}  sup_ce {blk[0].item() / blk[1].item():.4f}"
             if config.model == "gmvae" and ds.labels is not None:
                 q = model.encoder_y(last_x).distribution.logits
                 acc = utils.cluster_acc(q, ds.labels[last_rows.long()], config.mixture_components)
@@ -369,6 +403,7 @@ def run_eval(config):
     eng = model._engine
     tot = torch.zeros(5, device=eng.device)
     ref_sum, n_batches, codes, labs = 0.0, 0, [], []
+    class_hits = torch.zeros(2, dtype=torch.float64, device=eng.device)      # GMVAE: (argmax q(y|x) == label, examples)
     # --iw_samples N: the importance-weighted bound at N samples per example, streamed in chunks; row0 = the example's index in
     # the split, so every example draws its own noise whatever --batch_size or the number of ranks
     iw_n, iw_chunk, iw_rows = int(getattr(config, "iw_samples", 0) or 0), getattr(config, "iw_chunk", None), []
@@ -405,6 +440,9 @@ def run_eval(config):
         else:
             codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
         labs.append(labels)
+        if config.model == "gmvae":
+            class_hits[0] += (o["logits"].argmax(dim=1) == labels.to(eng.device)).sum()
+            class_hits[1] += labels.numel()
         if py_n > 0:
             py_logits.append(o["logits"])
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
@@ -414,6 +452,7 @@ def run_eval(config):
     if world > 1:
         parallel.all_reduce_flat(tot)
         parallel.all_reduce_flat(iw_sum)
+        parallel.all_reduce_flat(class_hits)
         if ie_n > 0:
             parallel.all_reduce_flat(ie_sum)
         if py_n > 0:
@@ -424,6 +463,10 @@ def run_eval(config):
     res = {f"{config.split}/loss_per_example": tot[0].item() / n, f"{config.split}/nll": tot[1].item() / n,
            f"{config.split}/kl_div_z": tot[2].item() / n, f"{config.split}/nent": tot[3].item() / n,
            f"{config.split}/reference_misnormalised_loss_per_example": ref_sum / n, "examples": int(n)}
+    if config.model == "gmvae":
+        # the share of examples whose most probable component under q(y|x) IS their label -- no mode matching: meaningful
+        # where training saw labels (--labelled_per_class), chance level otherwise
+        res[f"{config.split}/class_acc_q"] = class_hits[0].item() / max(class_hits[1].item(), 1.0)
     if iw_n > 0:
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:

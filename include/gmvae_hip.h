@@ -149,7 +149,45 @@ enum { GMVAE_SCHED_SAFE = 1,
         * gmvae_iw_bound* and gmvae_posterior_* mask it off.  The workspace grows by B*S*K floats under GMVAE_OBJ_MARGINAL_Y_IW
         * at S > 1 (v, behind every other buffer) and is otherwise the same size and layout.  No atomics: eager and captured
         * steps give the same bits. */
-       GMVAE_GRAD_DREG = 16 };
+       GMVAE_GRAD_DREG = 16,
+       /* semi-supervised objective (GMVAE only, together with GMVAE_OBJ_MARGINAL_Y or GMVAE_OBJ_MARGINAL_Y_IW): the component of
+        * some examples is OBSERVED and clamps y for them -- the labelled half of Kingma et al.'s M2 objective next to the
+        * unlabelled half the marginal objectives already are.  With l_bk the per-component term of the marginal objective
+        * (nll_bk + kl_bk at S == 1; -(logsumexp_s log w'_bsk - ln S) under GMVAE_OBJ_MARGINAL_Y_IW), q_b = softmax(logits_b),
+        * c_b the observed component of example b (any value outside [0, K) means unlabelled; -1 is conventional) and
+        * alpha >= 0 the classification weight:
+        *   unlabelled:  L_b = sum_k q_bk l_bk + sum_k q_bk ln q_bk      (the marginal objective, the same bits)
+        *   labelled:    L_b = l_bc + alpha (-ln q_bc)                   (no entropy term; the uniform -ln p(y) left out)
+        *     row weights  rw_r = [k == c] at S == 1, [k == c] softmax_s(log w'_bsc)_s at S > 1
+        *     dlogits_bj = alpha (q_bj - [j == c])
+        *     GMVAE_GRAD_DREG's second weight softmax_s(log w'_bsk)_s is unchanged for every k.
+        * Tail: [0] sum_b L_b; [1], [2] the weighted nll / kl sums with [k == c] in place of q_bk for a labelled example; [3] sum_b
+        * nent_b (a labelled example adds 0); [4] B; [5] sum over the labelled examples of -ln q_bc (NOT multiplied by alpha);
+        * [6] the number of labelled examples; [7] the number of labelled examples with argmax_k q_bk == c_b (the argmax of the
+        * logits, lowest index on ties).  At S == 1 [0] = [1] + [2] + [3] + alpha [5] up to rounding (at S > 1 [0] is below it, as
+        * under GMVAE_OBJ_MARGINAL_Y_IW without the bit: [1] and [2] are means over s); the data-parallel all-reduce sums
+        * all eight slots, so [7] / [6] is the classification accuracy on the labelled part of the global batch.
+        * The workspace grows BEHIND every other buffer (behind GMVAE_GRAD_DREG's v too) by three regions, each rounded up to
+        * 256 bytes as every workspace buffer is:
+        *   "labels"      int32 [GMVAE_LABEL_SLOTS][B4], B4 = B rounded up to a multiple of 4 (each slot starts 16-byte aligned)
+        *   "sup_weight"  one float, alpha, at the start of its cell
+        *   (unnamed)     float [B][3]: the per-example (-ln q_bc, labelled, hit) the step's kernels hand to each other
+        * i.e. by r256(4 * GMVAE_LABEL_SLOTS * B4) + 256 + r256(12 * B) bytes; gmvae_workspace_offset answers for the two
+        * names.  The CALLER writes "labels" and "sup_weight"; the library only reads them.  A zeroed workspace therefore means
+        * "component 0 observed for every example, alpha = 0": a caller always fills both before the first step (gmvae_amd.Engine
+        * does: -1 everywhere, its sup_weight).  Without the bit, sizes, layout and the answer for those two names
+        * (GMVAE_E_NET) are what they were.
+        * Who reads which slot: gmvae_step, gmvae_forward, gmvae_dp_step, the bench and profile loops read slot 0; step i of
+        * gmvae_train_graph_create's and gmvae_dp_graph_create's graph reads slot i (n_steps > GMVAE_LABEL_SLOTS: GMVAE_E_DIMS);
+        * gmvae_train_graph_create_pipeline refuses the bit (GMVAE_E_DIMS: it gathers its batches by index inside the graph and
+        * has no label gather); gmvae_iw_bound* and gmvae_posterior_* mask the bit off.  GMVAE_E_MODEL for the VAE family,
+        * GMVAE_E_DIMS for the Gumbel GMVAE -- from gmvae_workspace_bytes and every entry point that runs or sizes a step,
+        * before any launch.  gmvae_step_schedule appends "+labels"; the suffixes come in the fixed order
+        *   <schedule> [+marginal | +marginal_iw] [+labels] [+dreg] [+planes]
+        * ("general+marginal_iw+labels", "general+marginal+labels+dreg").  A step whose labels are all -1 is the step without
+        * the bit, bit for bit.  No atomics: eager and captured steps give the same bits. */
+       GMVAE_OBJ_LABELS = 32 };
+#define GMVAE_LABEL_SLOTS 32  /* label sets a workspace holds under GMVAE_OBJ_LABELS: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -466,7 +504,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -481,7 +519,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW) and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
