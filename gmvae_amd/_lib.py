@@ -123,6 +123,7 @@ GRAD_DREG = 16        # ... gradient estimator of the inference network: doubly 
 # Engine(grad_estimator=...): the plain reparameterised gradient, or the doubly reparameterised one (Tucker et al. 2018)
 GRAD_ESTIMATORS = ("standard", "dreg")
 OBJ_LABELS = 32       # ... objective: observed components clamp y per example (semi-supervised; include/gmvae_hip.h GMVAE_OBJ_LABELS)
+OBJ_WEIGHTS = 64      # ... objective: the KL terms weighted per step from device memory (include/gmvae_hip.h GMVAE_OBJ_WEIGHTS)
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph
 
 

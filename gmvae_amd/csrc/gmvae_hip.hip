@@ -36,6 +36,7 @@
 #include "iwbound.hpp"
 #include "ymarg.hpp"
 #include "semisup.hpp"
+#include "wobj.hpp"
 
 using namespace gmvae;
 
@@ -67,6 +68,9 @@ static int rows_per_x(const GmvaeDims& d) { return marginal_y(d) ? d.K * d.S : d
 static bool dreg_grad(const GmvaeDims& d) { return (d.sched_flags & GMVAE_GRAD_DREG) != 0; }
 // GMVAE_OBJ_LABELS: observed components clamp y per example (semisup.hpp ymarg_sup_rows in ymarg_rows' / ymarg_iw_rows' place)
 static bool sup_labels(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_LABELS) != 0; }
+// GMVAE_OBJ_WEIGHTS: the KL terms weighted per step from device memory (wobj.hpp: its kernels in row_terms' / ymarg_rows' /
+// y_head_bwd's place, wobj_tail behind loss_tail) -- the general schedule only, S == 1
+static bool obj_weights(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_WEIGHTS) != 0; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -179,9 +183,17 @@ static int check_label_dims(const GmvaeDims* d, int model) {
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   return marginal_y(*d) ? 0 : GMVAE_E_DIMS;
 }
+// ... and GMVAE_OBJ_WEIGHTS at S != 1 or together with the importance-weighted marginal objective, DReG or labels
+// (check_weight_dims: gmvae_forward's check too)
+static int check_weight_dims(const GmvaeDims* d) {
+  if (!obj_weights(*d)) return 0;
+  if (d->S != 1) return GMVAE_E_DIMS;
+  return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS)) ? GMVAE_E_DIMS : 0;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
   if (int e = check_label_dims(d, model)) return e;
+  if (int e = check_weight_dims(d)) return e;
   if (dreg_grad(*d) && model == GMVAE_MODEL_GMVAE && !marginal_y(*d)) return GMVAE_E_DIMS;
   return 0;
 }
@@ -218,6 +230,9 @@ struct WS {
   // ymarg_sup_rows' per-example (-ln q_bc, labelled, hit) for sup_tail
   int32_t* labels;
   float *sup_weight, *sup_trip;
+  // GMVAE_OBJ_WEIGHTS: the caller's weight rows [GMVAE_LABEL_SLOTS][4] = (beta_z, beta_y, lambda, 0) (read only), beta_z rw [R]
+  // for the consumers of rw that differentiate the KL part, and a_b [B] (1: the y term's floor is inactive)
+  float *obj_weights, *rwk, *y_floor;
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -275,6 +290,7 @@ static bool mega_shape(const GmvaeDims& d, int model) {
   return (size_t)mega_lay(H, d.L, d.K, d.D, model).total * 4 <= 160 * 1024;
 }
 static bool mega_ok(const GmvaeDims& d, int model) {
+  if (obj_weights(d)) return false;            // (GMVAE_OBJ_WEIGHTS: the general schedule only, as GMVAE_GRAD_DREG below)
   if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
                                                //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
   const char* e = getenv("GMVAE_NO_MEGA");
@@ -324,7 +340,7 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
 static bool skinny_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d)) return false;
+  if (dreg_grad(d) || obj_weights(d)) return false;
   const char* e = getenv("GMVAE_NO_SKINNY");
   if (e && atoi(e)) return false;
   int maxb = kSkMaxB;
@@ -339,7 +355,7 @@ static bool fused_shape(const GmvaeDims& d, int model) {
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
 }
 static bool fused_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d)) return false;
+  if (dreg_grad(d) || obj_weights(d)) return false;
   const char* e = getenv("GMVAE_NO_FUSED");
   if (e && atoi(e)) return false;
   return fused_shape(d, model);
@@ -354,6 +370,7 @@ static bool evalf_shape(const GmvaeDims& d, int model) {
   return d.L == 64 && d.K == 10;                                       // VAE_GMP: configs[1]
 }
 static bool evalf_ok(const GmvaeDims& d, int model) {
+  if (obj_weights(d)) return false;              // (gmvae_forward honours GMVAE_OBJ_WEIGHTS: the general schedule's forward)
   const char* e = getenv("GMVAE_NO_EVALF");
   if (e && atoi(e)) return false;
   if (!evalf_shape(d, model)) return false;
@@ -540,6 +557,12 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.labels = reinterpret_cast<int32_t*>(take((uint64_t)GMVAE_LABEL_SLOTS * pad4(B)));
     w.sup_weight = take(4);
     w.sup_trip = take(3 * B);
+  }
+  if (obj_weights(d)) {                           // (last: dims without the bit keep their size and every offset)
+    w.obj_weights = take((uint64_t)GMVAE_LABEL_SLOTS * 4);
+    w.rwk = take(R);
+    w.y_floor = take(B);
+    if (!marginal_y(d)) w.pb = take(B * 4);       // (S == 1 without y summed out: loss_tail's per-example partials)
   }
   w.bytes = off;
 }
@@ -913,6 +936,7 @@ struct StepArgs {
   bool dp_images = false;      // data-parallel graph: the Adam launch after the all-reduce scatters the weight images
   float* tail_log = nullptr;   // train graph: this step's slot of the per-step tail log (may be null)
   int label_slot = 0;          // GMVAE_OBJ_LABELS: which of the workspace's label sets the step reads (step i of a train graph: i)
+  int weights_slot = 0;        // GMVAE_OBJ_WEIGHTS: which row of the workspace's "obj_weights" the step reads (likewise)
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -2335,7 +2359,23 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
   const bool sup = sup_labels(d) && marg && !enum_chunk;
   if (sup && (!w.labels || a.label_slot < 0 || a.label_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
-  if (sup) {                    // GMVAE_OBJ_LABELS: the per-example terms with observed components clamping y (any S >= 1)
+  // GMVAE_OBJ_WEIGHTS (S == 1: check_weight_dims): this step's (beta_z, beta_y, lambda, 0); rwK = beta_z rw stands in rw's place
+  // wherever the KL part is differentiated
+  const bool wobj = obj_weights(d);
+  if (wobj && (!w.obj_weights || d.S != 1 || enum_chunk || a.weights_slot < 0 || a.weights_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  const float* const wts = wobj ? w.obj_weights + 4 * (size_t)a.weights_slot : nullptr;
+  const float* const rwK = (wobj && a.backward) ? w.rwk : rwS;
+  if (wobj && marg) {           // the per-example terms over the K rows of each batch row, the KL terms weighted
+    hipLaunchKernelGGL(ymarg_wobj_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, wts,
+                       logf((float)K), w.logpx, w.logw, a.row_terms, a.backward ? w.rw : (float*)nullptr,
+                       a.backward ? w.rwk : (float*)nullptr, w.dlogits, w.nent, w.pb, w.y_floor, B, K);
+    rowk(cx, "ymarg_wobj_rows");
+  } else if (wobj) {            // the per-row terms (R == B), the KL terms weighted
+    hipLaunchKernelGGL(wobj_rows, dim3(grid_for(B, 256, 1 << 22)), dim3(256), 0, st, w.part, nparts, w.logq, w.logp,
+                       gm ? w.nent : (const float*)nullptr, wts, logf((float)K), w.logpx, w.logw, a.row_terms,
+                       a.backward ? w.rwk : (float*)nullptr, w.pb, w.y_floor, B);
+    rowk(cx, "wobj_rows");
+  } else if (sup) {                    // GMVAE_OBJ_LABELS: the per-example terms with observed components clamping y (any S >= 1)
     hipLaunchKernelGGL(ymarg_sup_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits,
                        w.labels + (size_t)a.label_slot * pad4((uint64_t)B), w.sup_weight, w.logpx, w.logw, w.lw64, a.row_terms,
                        a.backward ? w.rw : (float*)nullptr, a.backward ? w.vs : (float*)nullptr, w.dlogits, w.nent, w.pb,
@@ -2371,8 +2411,12 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (!enum_chunk) {             // (gmvae_iw_bound_enum_y: iw_tail writes the tail)
     hipLaunchKernelGGL(loss_tail, dim3(1), dim3(1024), 0, st, w.logw, w.logpx, w.logq, w.logp,
                        gm ? w.nent : (const float*)nullptr, (float*)nullptr, tail, B, marg ? 1 : S, a.step_dev,
-                       (S > 1 || marg) ? w.pb : (const float*)nullptr);
+                       (S > 1 || marg || wobj) ? w.pb : (const float*)nullptr);
     rowk(cx, "loss_tail");
+    if (wobj) {                  // tail[5..7]: B beta_z, B beta_y and the examples whose y term sits on its floor
+      hipLaunchKernelGGL(wobj_tail, dim3(1), dim3(256), 0, st, w.y_floor, wts, tail, B);
+      rowk(cx, "wobj_tail");
+    }
     if (sup) {                   // tail[5..7]: the labelled examples' cross-entropy sum, count and hits
       hipLaunchKernelGGL(sup_tail, dim3(1), dim3(256), 0, st, w.sup_trip, tail, B);
       rowk(cx, "sup_tail");
@@ -2473,7 +2517,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
                        w.resp, P + L.loc, P + L.rawscale, w.dqp, w.dpp, R, Lz, K, prior, c, smin);
     rowk(cx, "z_head_bwd_dreg");
   } else {
-  hipLaunchKernelGGL(z_head_bwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.dz, w.qp, qp_div, w.pp, eps, w.z, rwS,
+  hipLaunchKernelGGL(z_head_bwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.dz, w.qp, qp_div, w.pp, eps, w.z, rwK,
                      w.resp, P + L.loc, P + L.rawscale, w.dqp, w.dpp, R, Lz, K, prior, c, smin);
   rowk(cx, "z_head_bwd");
   }
@@ -2575,7 +2619,11 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       }
       }
     }
-    if (!marg) {                  // (marginal: ymarg_rows left dlogits in closed form)
+    if (!marg && wobj) {          // (the entropy term under beta_y a_b)
+      hipLaunchKernelGGL(y_head_bwd_w, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, w.y, w.dy, w.nent, wts, w.y_floor,
+                         w.dlogits, B, S, K, 1.f / d.temperature);
+      rowk(cx, "y_head_bwd_w");
+    } else if (!marg) {           // (marginal: ymarg_rows left dlogits in closed form)
       hipLaunchKernelGGL(y_head_bwd, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, w.y, w.dy, w.nent, w.dlogits, B,
                          S, K, 1.f / d.temperature);
       rowk(cx, "y_head_bwd");
@@ -2583,7 +2631,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
     dcur = w.dlogits;
   } else {
     if (model == GMVAE_MODEL_VAE_GMP) {
-      hipLaunchKernelGGL(gmp_param_bwd, dim3(GMP_PARTS), dim3(256), 0, st, w.z, w.resp, rwS, P + L.loc,
+      hipLaunchKernelGGL(gmp_param_bwd, dim3(GMP_PARTS), dim3(256), 0, st, w.z, w.resp, rwK, P + L.loc,
                          P + L.rawscale, P + L.mixlog, w.gmp_part, R, Lz, K, (int)pad4((uint64_t)K * Lz));
       rowk(cx, "gmp_param_bwd");
     }
@@ -2637,7 +2685,7 @@ static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1
 struct IwLay { uint64_t eps, u, rows, ftail, state, rsum, bytes; };
 static void iw_lay(const GmvaeDims& d0, int model, const Layout& L, IwLay& o) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~GMVAE_OBJ_LABELS;            // (the bounds and posteriors mask the bit: their sizes must not carry the label regions)
+  d.sched_flags &= ~(GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);      // (the bounds and posteriors mask the bits: their sizes must not carry those regions)
   WS w;
   carve(d, model, L, nullptr, w);
   uint64_t off = (w.bytes + 255) / 256 * 256;
@@ -2657,7 +2705,7 @@ static void iw_lay(const GmvaeDims& d0, int model, const Layout& L, IwLay& o) {
 static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* x, const float* params, uint64_t n,
                         float* bound_out, float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);      // (the operand images are prepared here, once per call)
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);      // (the operand images are prepared here, once per call)
   Layout L;
   build_layout(d, model, L);
   WS w;
@@ -2768,7 +2816,7 @@ static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, con
 static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
   if (!dims) return GMVAE_E_NULL;
   d = *dims;
-  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);
+  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);
   if (int e = check_dims(&d, model)) return e;
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
@@ -2844,7 +2892,7 @@ static void pc_lay(const GmvaeDims& d, const IwLay& il, PcLay& o) {
 static int run_posterior_component(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
                                    float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
   GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS);
+  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);
   const int model = GMVAE_MODEL_VAE_GMP;
   Layout L;
   build_layout(d, model, L);
@@ -2986,7 +3034,7 @@ static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, fl
   a.adam_p = params; a.adam_m = m; a.adam_v = v; a.lr = lr; a.beta1 = b1; a.beta2 = b2; a.epsilon = eps_;
   a.imgs_ready = imgs_ready;
   a.tail_log = tail_log;
-  a.label_slot = label_slot;
+  a.label_slot = a.weights_slot = label_slot;    // (step i of a train graph: label set i, weight row i)
   return run_step(cx, a);
 }
 
@@ -2995,6 +3043,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
                   void* workspace, uint64_t seed, uint64_t step, void* stream) {
   if (int e = check_dims(dims, model)) return e;
   if (int e = check_label_dims(dims, model)) return e;
+  if (int e = check_weight_dims(dims)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
@@ -3655,7 +3704,8 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
   if (int e = check_step_dims(dims, model)) return e;
   // GMVAE_OBJ_LABELS: step i reads label set i of the workspace; the pipeline graph gathers its batches by index and has no
   // label gather
-  if (sup_labels(*dims) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  // (GMVAE_OBJ_WEIGHTS likewise: step i reads weight row i)
+  if ((sup_labels(*dims) || obj_weights(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3767,8 +3817,8 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
-           sup_labels(d) ? "+labels" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+           sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3803,7 +3853,8 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"slabs", w.slabs}, {"s1", w.s1}, {"s4", w.s4}, {"eps", w.eps}, {"u", w.u},
       {"stamps", reinterpret_cast<float*>(w.stamps)}, {"gstamps", reinterpret_cast<float*>(w.gstamps)},
       {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)},
-      {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight}};
+      {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight},
+      {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;
@@ -3927,7 +3978,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   a.dp_images = scatter;
   a.imgs_ready = scatter && imgs_ready;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
-  a.label_slot = label_slot;
+  a.label_slot = a.weights_slot = label_slot;
   cx.prof = prof;
   int rc = run_step(cx, a);
   if (rc) return rc;
@@ -4074,7 +4125,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
-  if (sup_labels(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set i)
+  if ((sup_labels(*dims) || obj_weights(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

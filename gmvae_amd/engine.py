@@ -49,12 +49,33 @@ def check_semi_supervised(model, y_inference, semi_supervised, sup_weight):
         raise ValueError(f"sup_weight must be >= 0, got {sup_weight!r}")
 
 
+def check_weighted_objective(model, y_inference, n_samples, grad_estimator, semi_supervised, weighted_objective,
+                             kl_weight, y_weight, y_free_nats):
+    """The argument check of Engine(weighted_objective=, kl_weight=, y_weight=, y_free_nats=) (no device needed)."""
+    for name, v in (("kl_weight", kl_weight), ("y_weight", y_weight), ("y_free_nats", y_free_nats)):
+        if not (float(v) >= 0.0 and math.isfinite(float(v))):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    if not weighted_objective:
+        if (float(kl_weight), float(y_weight), float(y_free_nats)) != (1.0, 1.0, 0.0):
+            raise ValueError("kl_weight, y_weight and y_free_nats need weighted_objective=True")
+        return
+    if int(n_samples) != 1:
+        raise ValueError("weighted_objective=True weights the terms of the one-sample bound: n_samples must be 1")
+    if y_inference == "marginal_iw":
+        raise ValueError("weighted_objective=True is not available with y_inference='marginal_iw': use 'gumbel' or 'marginal'")
+    if grad_estimator == "dreg":
+        raise ValueError("weighted_objective=True is not available with grad_estimator='dreg'")
+    if semi_supervised:
+        raise ValueError("weighted_objective=True is not available with semi_supervised=True")
+
+
 class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
                  temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
                  y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
-                 sup_weight: float = 1.0):
+                 sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
+                 y_free_nats: float = 0.0):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -70,8 +91,15 @@ class Engine:
         semi_supervised (GMVAE with y_inference "marginal" or "marginal_iw"; include/gmvae_hip.h GMVAE_OBJ_LABELS): step / loss /
         forward / train_step / dp_step take y_observed, an int tensor [B] of observed components (-1 or any value outside
         [0, K): unlabelled).  A labelled example's loss is its own component's term plus sup_weight * (-ln q(y|x)); an
-        unlabelled one's is the marginal objective's.  Parameters and checkpoints are the same with and without it."""
+        unlabelled one's is the marginal objective's.  Parameters and checkpoints are the same with and without it.
+        weighted_objective (n_samples = 1; include/gmvae_hip.h GMVAE_OBJ_WEIGHTS): the KL terms carry weights every step reads
+        from device memory -- loss = nll + kl_weight * kl_z + y_weight * max(nent, y_free_nats - ln K) (the y term: GMVAE only;
+        y_free_nats nats of free bits on KL(q(y|x) || uniform), 0 = off).  set_objective_weights changes them between steps
+        without a host sync; a captured train graph reads one row of replay.obj_weights per step (a KL warm-up).  Every step
+        takes the general schedule.  Parameters and checkpoints are the same with and without it."""
         check_semi_supervised(model, y_inference, semi_supervised, sup_weight)
+        check_weighted_objective(model, y_inference, n_samples, grad_estimator, semi_supervised, weighted_objective,
+                                 kl_weight, y_weight, y_free_nats)
         if y_inference not in L.Y_INFERENCE:
             raise ValueError(f"y_inference must be one of {L.Y_INFERENCE}, got {y_inference!r}")
         if y_inference == "marginal" and (L.MODEL_IDS.get(model) != L.MODEL_GMVAE or int(n_samples) != 1):
@@ -113,6 +141,8 @@ class Engine:
         self.grad_estimator = grad_estimator
         self.semi_supervised = bool(semi_supervised)
         self.sup_weight = float(sup_weight)
+        self.weighted_objective = bool(weighted_objective)
+        self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -137,14 +167,23 @@ class Engine:
         self._iw_enum_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound_enum_y's workspace
         self._post_y_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_y's workspace
         self._post_comp_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_component's workspace
+        # weighted objective: the current (kl_weight, y_weight, y_free_nats, 0) on the device; every eager entry copies it into
+        # slot 0 of its workspace's weight rows (device to device: a captured graph may have left its own row there)
+        self._objw_dev = None
+        if self.weighted_objective:
+            self._objw_dev = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self.set_objective_weights(*self.obj_weights)
         self.init_parameters(random_seed)
 
     # ------------------------------------------------------------ parameters
     def dims(self, B: int, S: Optional[int] = None, row0: Optional[int] = None, extra_flags: int = 0):
         """GmvaeDims for a local batch of B rows; row0 = global index of its first row (default rank * B)."""
-        return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=self.S if S is None else S,
+        S = self.S if S is None else S
+        # (the weighted objective is the one-sample bound's: a forward at another number of samples reports the plain bound)
+        wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
+        return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
-                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | extra_flags, **self.hp)
+                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | extra_flags, **self.hp)
 
     def _obj_flags(self):
         obj = L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
@@ -269,6 +308,27 @@ class Engine:
                 self._ws[key][off:off + 1].fill_(self.sup_weight)
         return d, self._ws[key]
 
+    def _weight_slots(self, d, ws) -> torch.Tensor:
+        """View [LABEL_SLOTS, 4] of the workspace's weight rows (kl_weight, y_weight, y_free_nats, 0)."""
+        off = L.workspace_offset(d, self.model, "obj_weights") // 4
+        return ws[off:off + L.LABEL_SLOTS * 4].view(L.LABEL_SLOTS, 4)
+
+    def _set_weights(self, d, ws):
+        """Slot 0 of the workspace's weight rows <- the engine's current weights (device-side copy, no host sync)."""
+        if self.weighted_objective and d.sched_flags & L.OBJ_WEIGHTS:
+            self._weight_slots(d, ws)[0].copy_(self._objw_dev)
+
+    def set_objective_weights(self, kl_weight: float, y_weight: float, y_free_nats: float):
+        """The weights the next eager steps (step / loss / forward / train_step / dp_step) read: device-side writes, no host
+        sync.  A captured train graph reads its own rows (replay.obj_weights), pre-filled at capture with these."""
+        if not self.weighted_objective:
+            raise ValueError("set_objective_weights needs an engine created with weighted_objective=True")
+        check_weighted_objective(self.model_name, self.y_inference, self.S, self.grad_estimator, self.semi_supervised, True,
+                                 kl_weight, y_weight, y_free_nats)
+        self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
+        for i, v in enumerate(self.obj_weights):
+            self._objw_dev[i:i + 1].fill_(v)
+
     def _label_slots(self, d, ws) -> torch.Tensor:
         """int32 view [LABEL_SLOTS, B] of the workspace's label sets (each slot starts 16-byte aligned)."""
         B4 = (d.B + 3) // 4 * 4
@@ -329,6 +389,7 @@ class Engine:
         B = x.shape[0]
         d, ws = self._workspace(B, row0=row0)
         self._set_labels(d, ws, y_observed)
+        self._set_weights(d, ws)
         eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
         u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
@@ -351,6 +412,7 @@ class Engine:
             raise ValueError("y_inference='marginal' enumerates y over the K components: n_samples must be 1")
         d, ws = self._workspace(B, S)
         self._set_labels(d, ws, y_observed)
+        self._set_weights(d, ws)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
@@ -606,6 +668,7 @@ class Engine:
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
         self._set_labels(d, ws, y_observed)
+        self._set_weights(d, ws)
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
@@ -622,13 +685,21 @@ class Engine:
         that many consecutive steps and static_x is [n_steps, B, D] (the next n_steps batches): one
         launch per n_steps steps hides the idle time between graph launches.  With all_reduce (data
         parallel) the RCCL all-reduce is captured too when the library owns the communicator
-        (enable_rccl); otherwise the step is two eager halves around torch.distributed.all_reduce."""
+        (enable_rccl); otherwise the step is two eager halves around torch.distributed.all_reduce.
+        replay.tail_log [n_steps, TAIL]: the per-step tails of the last launch.  replay.y_observed [n_steps, B] (semi-supervised)
+        and replay.obj_weights [n_steps, 4] (weighted objective; pre-filled with the engine's current weights) are VIEWS of
+        the workspace's label sets / weight rows, which step i of the graph reads; the caller fills them before replay().
+        Row 0 of both is also what every eager entry (step / loss / forward / train_step / dp_step) on the same batch size
+        writes before it runs -- the engine's current weights, its y_observed -- so after any eager call row 0 holds that
+        call's values until the caller refills it: fill the rows before EVERY replay (run_train does)."""
         import torch.distributed as dist
         do_ar = all_reduce and ((dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
                                 or getattr(self, "_comm", None) is not None)
         n_steps = int(n_steps)
         if self.semi_supervised and n_steps > L.LABEL_SLOTS:
             raise ValueError(f"a semi-supervised train graph holds at most {L.LABEL_SLOTS} steps (one label set per step), got {n_steps}")
+        if self.weighted_objective and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph of a weighted objective holds at most {L.LABEL_SLOTS} steps (one weight row per step), got {n_steps}")
         key = (B, lr, do_ar, n_steps)
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)   # eager steps may have run since the capture
@@ -644,6 +715,26 @@ class Engine:
         if self.semi_supervised:
             y_obs = self._label_slots(d, ws)[:n_steps]
             y_obs.fill_(-1)
+        # weighted objective: step i reads weight row i; the caller fills replay.obj_weights [n_steps, 4] = (kl_weight, y_weight,
+        # y_free_nats, 0) per step (pre-filled with the engine's current weights)
+        obj_w = None
+        if self.weighted_objective:
+            obj_w = self._weight_slots(d, ws)[:n_steps]
+            obj_w.copy_(self._objw_dev.expand(n_steps, 4))
+
+        def eager_rows(body):
+            """The graph's steps one by one (no graph could be captured): step i's weight row passes through the engine's
+            current weights, which every eager entry copies into slot 0."""
+            if obj_w is None:
+                for i in range(n_steps):
+                    body(i)
+                return
+            rows, cur = obj_w.clone(), self._objw_dev.clone()
+            for i in range(n_steps):
+                self._objw_dev.copy_(rows[i])
+                body(i)
+            self._objw_dev.copy_(cur)
+            obj_w[0].copy_(rows[0])
         self.step_dev.fill_(self.global_step)
         # per-step tails of one launch (loss sums + count; all-reduced under data parallelism): replay.tail_log
         tail_log = torch.zeros(n_steps, L.TAIL, dtype=torch.float32, device=self.device)
@@ -665,7 +756,7 @@ class Engine:
                     if rc2:
                         L.check(rc2, "gmvae_train_graph_launch")
                     self.global_step += n_steps
-                replay.tail_log, replay.y_observed = tail_log, y_obs
+                replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
                 self._graphs[key] = (static_x, replay, handle)
                 return static_x, replay
             if rc == 0:
@@ -676,12 +767,14 @@ class Engine:
 
             def replay():
                 ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
-                for i, xb in enumerate(batches):
-                    self.dp_step(xb, lr, y_observed=None if ys is None else ys[i])
+
+                def body(i):
+                    self.dp_step(batches[i], lr, y_observed=None if ys is None else ys[i])
                     tail_log[i].copy_(self.grads[self.P:])
+                eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
-            replay.tail_log, replay.y_observed = tail_log, y_obs
+            replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         if do_ar:
@@ -691,15 +784,17 @@ class Engine:
 
             def replay():
                 ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
-                for i, xb in enumerate(batches):
-                    self.step(xb, use_step_dev=True, y_observed=None if ys is None else ys[i])
+
+                def body(i):
+                    self.step(batches[i], use_step_dev=True, y_observed=None if ys is None else ys[i])
                     parallel.all_reduce_flat(self.grads)
                     self.adam(lr, use_step_dev=True)
                     self.global_step += 1
                     tail_log[i].copy_(self.grads[self.P:])
+                eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
-            replay.tail_log, replay.y_observed = tail_log, y_obs
+            replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         torch.cuda.synchronize()
@@ -718,7 +813,7 @@ class Engine:
                 L.check(rc, "gmvae_train_graph_launch")
             self.global_step += n_steps
 
-        replay.tail_log, replay.y_observed = tail_log, y_obs
+        replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
         self._graphs[key] = (static_x, replay, handle)
         return static_x, replay
 
@@ -732,6 +827,9 @@ class Engine:
         if self.semi_supervised:
             raise ValueError("capture_train_pipeline gathers its batches by index inside the graph and has no label gather: a "
                              "semi-supervised engine trains through capture_train_step (replay.y_observed)")
+        if self.weighted_objective:
+            raise ValueError("capture_train_pipeline has no per-step weight rows: an engine with weighted_objective=True trains "
+                             "through capture_train_step (replay.obj_weights)")
         n_steps = int(n_steps)
         key = ("pipeline", id(dataset), B, lr, n_steps)
         if key in self._graphs:

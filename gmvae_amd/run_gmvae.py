@@ -58,6 +58,13 @@ def build_parser():
       "semi-supervised -- this many training examples per class show their label to the objective (0 = off)")
     a("--sup_weight", type=float, default=1.0, help="--labelled_per_class: weight of the classification term -ln q(y|x) "
       "of a labelled example")
+    a("--kl_weight", type=float, default=1.0, help="train, --n_samples=1: weight of the z term KL(q(z|.) || p(z|.)) of the "
+      "objective (beta-VAE)")
+    a("--y_weight", type=float, default=1.0, help="train, gmvae, --n_samples=1: weight of the y term KL(q(y|x) || p(y))")
+    a("--y_free_nats", type=float, default=0.0, help="train, gmvae, --n_samples=1: free bits on the y term -- an example "
+      "whose KL(q(y|x) || p(y)) is below this many nats pays the floor and sends no gradient through it (0 = off)")
+    a("--kl_warmup_steps", type=int, default=0, help="train, --n_samples=1: both weights are multiplied by "
+      "min(1, (t + 1) / N) during the step with 0-based index t (0 = off)")
     return p
 
 
@@ -93,6 +100,17 @@ def check_args(p, cfg):
         p.error("--labelled_per_class and --sup_weight must be >= 0")
     if cfg.labelled_per_class > 0 and (cfg.model != "gmvae" or cfg.y_inference == "gumbel"):
         p.error("--labelled_per_class needs --model=gmvae with --y_inference=marginal or marginal_iw")
+    if cfg.kl_weight < 0 or cfg.y_weight < 0 or cfg.y_free_nats < 0 or cfg.kl_warmup_steps < 0:
+        p.error("--kl_weight, --y_weight, --y_free_nats and --kl_warmup_steps must be >= 0")
+    if runners.weighted_flags(cfg):
+        if cfg.n_samples > 1:
+            p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps weight the one-sample bound: --n_samples must be 1")
+        if cfg.y_inference == "marginal_iw":
+            p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps are not available with --y_inference=marginal_iw")
+        if cfg.grad_estimator == "dreg":
+            p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps are not available with --grad_estimator=dreg")
+        if cfg.labelled_per_class > 0:
+            p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps are not available with --labelled_per_class")
     return cfg
 
 

@@ -76,8 +76,31 @@ def create_dataset(config, split="train", shuffle=True, repeat=True, device="cud
 
 
 # ----------------------------------------------------------------- model
-def create_model(config, data_dim):
-    """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0."""
+def kl_warmup(t: int, n: int) -> float:
+    """--kl_warmup_steps N: the factor on both KL weights during the step with 0-based index t -- min(1, (t + 1) / N), 1 for
+    N <= 0.  A pure function of the global step, so a restored checkpoint continues the schedule."""
+    return 1.0 if n <= 0 else min(1.0, (int(t) + 1) / float(n))
+
+
+def weighted_flags(config) -> bool:
+    """Whether any of --kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps leaves its default: the engine is then
+    created with the weighted objective (Engine(weighted_objective=True))."""
+    return (float(getattr(config, "kl_weight", 1.0)) != 1.0 or float(getattr(config, "y_weight", 1.0)) != 1.0 or
+            float(getattr(config, "y_free_nats", 0.0)) != 0.0 or int(getattr(config, "kl_warmup_steps", 0) or 0) != 0)
+
+
+def objective_weights_at(config, t: int):
+    """(kl_weight, y_weight, y_free_nats) of the step with 0-based index t: the flags under the warm-up factor."""
+    f = kl_warmup(t, int(getattr(config, "kl_warmup_steps", 0) or 0))
+    return (float(getattr(config, "kl_weight", 1.0)) * f, float(getattr(config, "y_weight", 1.0)) * f,
+            float(getattr(config, "y_free_nats", 0.0)))
+
+
+def create_model(config, data_dim, weighted=None):
+    """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0.
+    weighted: create the engine with the weighted objective (None: as the flags say; run_eval passes False, so that its
+    numbers stay comparable)."""
+    wobj = dict(weighted_objective=weighted_flags(config) if weighted is None else bool(weighted))
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
@@ -89,14 +112,14 @@ def create_model(config, data_dim):
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0,
                                   random_seed=config.random_seed, n_samples=ns,
                                   y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge,
-                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)))
+                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj)
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
-                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge)
+                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj)
     if config.model == "vae":
         return vae.create_vae(data_dim, config.latent_size, fcnet_hidden_sizes=hidden, sigma_min=0.0,
-                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge)
+                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj)
     raise ValueError(f"unknown model {config.model!r}")
 
 
@@ -267,7 +290,13 @@ def run_train(config):
     # semi-supervised (--labelled_per_class): the pipeline graph has no label gather, so one device takes the branch that
     # world > 1 takes -- binarise, fill the graph's label sets, replay
     sup = eng.semi_supervised
-    run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else "pipeline-graph")
+    # weighted objective (--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps): the same branch -- the graph's weight
+    # rows are filled per launch from the schedule, a pure function of the global step
+    wobj = eng.weighted_objective
+    run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else
+                                                 "graph+weights" if wobj else "pipeline-graph")
+    run_train.weight_log = []                               # weighted objective: (step, tail[5] / tail[4], tail[6] / tail[4]) of the
+                                                            # LAST summary block's steps (replaced per block: it does not grow)
     verify_every = int(os.environ.get("GMVAE_VERIFY_EVERY", "0") or 0)      # debug canary: see _verify_launch
     run_train.launches = run_train.verified_launches = 0
     run_train.degraded = False
@@ -285,9 +314,11 @@ def run_train(config):
                 rows = ds.next_rows(B)
                 x = binarize(ds.pixels, rows=rows, seed=bseed, step=eng.global_step, out_row0=rank * B)
                 yo = ds.y_observed[rows.long()] if sup else None
+                if wobj:
+                    eng.set_objective_weights(*objective_weights_at(config, eng.global_step))
                 logs.append(eng.train_step(x, lr=lr, y_observed=yo).clone().view(1, -1))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1 and not sup:
+            elif world == 1 and not sup and not wobj:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -307,6 +338,10 @@ def run_train(config):
                     binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
                     if sup:
                         replay.y_observed[i].copy_(ds.y_observed[last_rows.long()])
+                if wobj:
+                    rows_w = torch.tensor([objective_weights_at(config, eng.global_step + i) + (0.0,) for i in range(g)],
+                                          dtype=torch.float32)
+                    replay.obj_weights.copy_(rows_w, non_blocking=True)
                 replay()
                 logs.append(replay.tail_log.clone())
                 last_x = xs[g - 1]
@@ -320,6 +355,9 @@ def run_train(config):
         logs = []
         vals = (tails[:, 0] / tails[:, 4]).tolist()
         base = eng.global_step - len(vals)
+        if wobj:
+            run_train.weight_log = [(base + i + 1, (tails[i, 5] / tails[i, 4]).item(), (tails[i, 6] / tails[i, 4]).item())
+                                     for i in range(len(vals))]
         fault = getattr(config, "fault_hook", None)         # (tests: called with the engine after every summary block)
         timed_out = bool(eng.handoff_timeouts())            # the explicit flag of a hand-off that gave up waiting
         nonfinite = not all(np.isfinite(vals))
@@ -368,6 +406,9 @@ def run_train(config):
         if rank == 0 and (eng.global_step % every == 0 or eng.global_step > config.max_steps):
             rate = (eng.global_step - s0) / max(time.time() - t0, 1e-9)
             msg = f"Step {eng.global_step}, loss: {vals[-1]:f}  ({rate:.1f} global_step/sec)"
+            if wobj:
+                msg += (f"  kl_weight {run_train.weight_log[-1][1]:.4f}  y_weight {run_train.weight_log[-1][2]:.4f}"
+                        f"  y_floor_share {(tails[-1, 7] / tails[-1, 4]).item():.4f}")
             if sup:                                         # over the summary block's labelled examples (all ranks')
                 blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
                 if blk[1].item() > 0:
@@ -396,7 +437,7 @@ def run_eval(config):
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(select_device(config, local))
     data_dim = int(getattr(config, "data_dim", 784))
-    model = create_model(config, data_dim)
+    model = create_model(config, data_dim, weighted=False)     # (the weighting flags are training's: the reported terms stay unweighted)
     wait_for_checkpoint(_ckpt(config), float(getattr(config, "checkpoint_poll_seconds", 60.0)),
                         getattr(config, "checkpoint_max_wait", None))
     model.load_state_dict(torch.load(_ckpt(config), map_location="cpu"))

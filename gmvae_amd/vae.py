@@ -95,7 +95,10 @@ class TrainableVAE(VAE):
         """nll_scalar / kl_div_z / elbo of the last run_model (scripts/vae.py:178,182,186)."""
         e = self._need_engine()
         t = e.grads[e.P:].detach()
-        return {"nll_scalar": t[1] / t[4], "kl_div_z": t[2] / t[4], "elbo": -t[0] / t[4]}
+        out = {"nll_scalar": t[1] / t[4], "kl_div_z": t[2] / t[4], "elbo": -t[0] / t[4]}
+        if e.weighted_objective:                   # (nll_scalar and kl_div_z stay unweighted; elbo = -loss carries the weights)
+            out["kl_weight"], out["y_weight"], out["y_floor_share"] = t[5] / t[4], t[6] / t[4], t[7] / t[4]
+        return out
 
     @property
     def params(self):
@@ -110,17 +113,20 @@ class TrainableVAE(VAE):
 
 def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
-               random_seed=None, n_samples=1, grad_estimator="standard"):
+               random_seed=None, n_samples=1, grad_estimator="standard", weighted_objective=False, kl_weight=1.0,
+               y_weight=1.0, y_free_nats=0.0):
     """Factory with the signature of scripts/vae.py:191-200 (+ n_samples, the
     IWAE extension of SURVEY.md A15; 1 == the reference; + grad_estimator: "dreg" = the doubly
-    reparameterised gradient for the encoder, Engine)."""
+    reparameterised gradient for the encoder, Engine; + weighted_objective, kl_weight, y_weight, y_free_nats: the KL weight of
+    Engine's weighted objective -- the VAE family has no y term, so y_weight and y_free_nats are ignored)."""
     if fcnet_hidden_sizes is None:
         fcnet_hidden_sizes = [latent_size]                     # scripts/vae.py:228-229
     name = "vae_gmp" if mixture_components > 1 else "vae"
     engine = Engine(name, data_size, latent_size, mixture_components, fcnet_hidden_sizes, n_samples=n_samples,
                     sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, gen_bias_init=gen_bias_init,
                     random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
-                    grad_estimator=grad_estimator)
+                    grad_estimator=grad_estimator, weighted_objective=weighted_objective, kl_weight=kl_weight,
+                    y_weight=y_weight, y_free_nats=y_free_nats)
     if mixture_components > 1:
         def prior():
             v = engine.views()

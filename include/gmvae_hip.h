@@ -186,8 +186,44 @@ enum { GMVAE_SCHED_SAFE = 1,
         *   <schedule> [+marginal | +marginal_iw] [+labels] [+dreg] [+planes]
         * ("general+marginal_iw+labels", "general+marginal+labels+dreg").  A step whose labels are all -1 is the step without
         * the bit, bit for bit.  No atomics: eager and captured steps give the same bits. */
-       GMVAE_OBJ_LABELS = 32 };
-#define GMVAE_LABEL_SLOTS 32  /* label sets a workspace holds under GMVAE_OBJ_LABELS: the most steps of one train graph */
+       GMVAE_OBJ_LABELS = 32,
+       /* weighted objective (all three models, S == 1 only): the KL terms of the bound carry weights that a step READS FROM
+        * DEVICE MEMORY -- beta_z >= 0 on the z term (beta-VAE), beta_y >= 0 on the y term and lambda >= 0 nats of free bits
+        * on the y term (the minimum-information constraint of Dilokthanakul et al. 2016) -- so that the steps of one captured
+        * graph can follow a KL warm-up.  With nll, kl = log q(z|.) - log p(z|.) and nent_b = sum_k q_bk ln q_bk the terms
+        * of the objective without the bit, KL(q(y|x_b) || uniform) = nent_b + ln K (the ln K stays out of the loss):
+        *   VAE, VAE_GMP:                    L_b = nll_b + beta_z kl_b                        (beta_y and lambda are ignored)
+        *   GMVAE, Gumbel y:                 L_b = nll_b + beta_z kl_b + beta_y ne'_b
+        *   GMVAE, GMVAE_OBJ_MARGINAL_Y:     L_b = sum_k q_bk (nll_bk + beta_z kl_bk) + beta_y ne'_b
+        *   ne'_b = max(nent_b, lambda - ln K),  a_b = [nent_b > lambda - ln K]  (1: the floor is inactive)
+        *   lambda == 0 switches the floor off whatever the rounding: a_b = 1, ne'_b = nent_b.
+        * Gradients: the y term adds beta_y a_b q_bj (ln q_bj - nent_b) to dlogits (under GMVAE_OBJ_MARGINAL_Y the closed form
+        * is dlogits_bj = q_bj (l_bj - sum_k q_bk l_bk) + beta_y a_b q_bj (ln q_bj - nent_b), l_bk = nll_bk + beta_z kl_bk); the
+        * decoder path keeps the row weight rw (1, or q_bk); whatever differentiates the KL part -- the prior term and the
+        * -1/sigma_q of the z head's backward, the prior network's and the mixture prior's gradients -- takes
+        * rwk_r = beta_z rw_r in rw's place.  At weights (1, 1, 0) the objective is the one without the bit (equal at the
+        * parity gates, not bit for bit: the fp64 sum forming l_bk is ordered differently).
+        * Tail: [0] sum_b L_b (weighted, with the floor); [1], [2], [3] the UNWEIGHTED nll, kl and nent sums of the objective
+        * without the bit; [4] B; [5] B beta_z; [6] B beta_y; [7] sum_b (1 - a_b), the examples whose y term sits on its floor
+        * (0 for the VAE family).  The data-parallel all-reduce sums all eight slots: [5] / [4] and [6] / [4] give the weights
+        * back, [7] / [4] the floor's share.  gmvae_forward: row_terms' log w stays the row's unweighted importance weight.
+        * The workspace grows BEHIND every other buffer by regions rounded up to 256 bytes each as every workspace buffer is:
+        *   "obj_weights"  float [GMVAE_LABEL_SLOTS][4] = (beta_z, beta_y, lambda, 0 reserved) per slot
+        *   "rwk"          float [R], R = B (B K under GMVAE_OBJ_MARGINAL_Y): beta_z rw
+        *   "y_floor"      float [B]: a_b
+        * and, where the dims have no per-example partials [B][4] yet (S == 1 without GMVAE_OBJ_MARGINAL_Y), those; all three names
+        * answer through gmvae_workspace_offset.  The CALLER writes "obj_weights"; the library only reads it.  A zeroed
+        * workspace means weights (0, 0, 0): a caller fills the slots before the first step (gmvae_amd.Engine does).
+        * Who reads which slot: gmvae_step, gmvae_forward, gmvae_dp_step, the bench and profile loops read slot 0; step i of
+        * gmvae_train_graph_create's and gmvae_dp_graph_create's graph reads slot i (n_steps > GMVAE_LABEL_SLOTS: GMVAE_E_DIMS);
+        * gmvae_train_graph_create_pipeline refuses the bit (GMVAE_E_DIMS); gmvae_iw_bound* and gmvae_posterior_* mask the bit
+        * off; gmvae_forward honours it.  GMVAE_E_DIMS if S != 1 or together with GMVAE_OBJ_MARGINAL_Y_IW, GMVAE_GRAD_DREG or
+        * GMVAE_OBJ_LABELS -- from gmvae_workspace_bytes and every entry point that runs or sizes a step, before any launch.
+        * Every step with the bit takes the general schedule; gmvae_step_schedule appends "+weights" behind the objective:
+        *   <schedule> [+marginal | +marginal_iw] [+labels] [+weights] [+dreg] [+planes]
+        * ("general+weights", "general+marginal+weights").  No atomics: eager and captured steps give the same bits. */
+       GMVAE_OBJ_WEIGHTS = 64 };
+#define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -504,7 +540,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -519,7 +555,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
