@@ -355,9 +355,11 @@ __global__ void z_head_fwd(const float* __restrict__ qp, int qp_div, const float
     for (int l = lane; l < L; l += 64) {
       const float mu = q[l];
       const float sg = fmaxf(softplus_r(q[L + l] + c), smin);
-      const float zz = mu + sg * eps[(long long)r * L + l];
+      const float e = eps[(long long)r * L + l];
+      const float zz = mu + sg * e;
       z[(long long)r * L + l] = zz;
-      const float e = (zz - mu) * __builtin_amdgcn_rcpf(sg);        // from z, not eps (A7)
+      // (z - mu) / sigma of A7 is eps, taken as it came: formed again from the rounded z it is lost wherever sigma is below
+      // mu's ulp (sigma = 2e-9 beside mu = 0.5 gives 0 or +-30 for every eps), and log q(z) with it; the backward uses eps too
       aq += -0.5f * e * e - 0.5f * kLog2Pi - log_r(sg);
       if (prior == PRIOR_COND) {
         const float* p = pp + (long long)r * 2 * L;

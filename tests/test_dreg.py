@@ -109,14 +109,14 @@ def steps():
 
 
 # ------------------------------------------------------------------------------- 1. parity with the fp64 statement
-@pytest.mark.parametrize("name", list(CASES))
-def test_step_matches_fp64_statement(steps, name):
-    c = steps(name)
+def check_step(name, c, ref=None):
+    """The gates of the step with the bit, c = dict(model, d, B, S, flat, x, eps, dreg = dstep's result); ref: the statement's
+    (C, g) at those parameters where the caller has it already.  Returns the statement's C."""
     model, d, B, S = c["model"], c["d"], c["B"], c["S"]
     got = c["dreg"]
     assert got["schedule"].startswith("general") and got["schedule"].endswith("+dreg"), got["schedule"]
     p32 = O.unpack(model, d, c["flat"].astype(np.float64))
-    Cc, g = DR.loss_and_grads(model, d, p32, c["x"], c["eps"], S)
+    Cc, g = ref or DR.loss_and_grads(model, d, p32, c["x"], c["eps"], S)
     tail = got["tail"]
     assert tail[4] == B
     loss = tail[0] / B
@@ -138,6 +138,14 @@ def test_step_matches_fp64_statement(steps, name):
     if got["dlogits"] is not None:
         ref = Cc["dlogits"] * B
         assert np.abs(got["dlogits"] - ref).max() <= GATE * max(np.abs(ref).max(), 1e-6)
+    return Cc
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_step_matches_fp64_statement(steps, name):
+    c = steps(name)
+    d = c["d"]
+    Cc = check_step(name, c)
     if d.sigma_min > 0:               # the case is about the clamp: some units on it, some off it
         sig = Cc["sig_q"]
         assert (sig == d.sigma_min).any() and (sig > d.sigma_min).any()

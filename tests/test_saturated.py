@@ -31,23 +31,26 @@ ROW_TINY, K_TINY = 396610, 9
 ROW_MAX, K_MAX = 261784, 3
 
 
-def saturate(model, d, p, rng, x, lam=60.0, span=8.0, logit=15.0):
+def saturate(model, d, p, rng, x, lam=60.0, span=8.0, logit=15.0, prior_span=None):
     """Xavier parameters pushed where a trained model (and a diverging one) lives: raw_sigma biases of the q head and the prior
     head spread over [-span, span] per latent dimension, encoder_y's logits scaled to +-logit, the decoder's output layer scaled
-    so that the largest |lambda| on this batch is `lam` (measured with the fp64 oracle on standard noise)."""
+    so that the largest |lambda| on this batch is `lam` (measured with the fp64 oracle on standard noise).  prior_span: the
+    spread of the prior head (the GMVAE's prior_gmm, the VAE_GMP's mixture scales) where it differs from the q head's; None:
+    the same as `span` (the same draws, the same bits)."""
     nl = len(d.hidden)
+    ps = span if prior_span is None else prior_span
     p = {k: np.array(v, np.float64) for k, v in p.items()}
     for k in p:
         if k.endswith("/b"):
             p[k] = rng.normal(0, 0.05, p[k].shape)
-    raws = lambda: rng.permutation(np.linspace(-span, span, d.L))
+    raws = lambda w=span: rng.permutation(np.linspace(-w, w, d.L))
     enc = "encoder_gmm" if model == O.MODEL_GMVAE else "encoder"
     p[f"{enc}_fcnet/linear_{nl}/b"][d.L:] = raws() - d.raw_sigma_bias
     if model == O.MODEL_GMVAE:
-        p["prior_gmm_fcnet/linear_0/b"][d.L:] = raws() - d.raw_sigma_bias
+        p["prior_gmm_fcnet/linear_0/b"][d.L:] = raws(ps) - d.raw_sigma_bias
         p[f"encoder_y_fcnet/linear_{nl}/w"] *= logit / 1.5
     if model == O.MODEL_VAE_GMP:
-        p["raw_scale_diag"] = np.stack([raws() for _ in range(d.K)])
+        p["raw_scale_diag"] = np.stack([raws(ps) for _ in range(d.K)])
         p["mixture_logits"] = rng.normal(0, 4.0, d.K)
         p["loc"] = rng.normal(0, 2.0, (d.K, d.L))
     B = x.shape[0]

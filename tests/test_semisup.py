@@ -116,11 +116,12 @@ def _grad_errs(d, gs, g, B):
     return out
 
 
-def compare_step(d, S, flat, x, eps, y, alpha, what, flags=None, estimator="standard", grad_rtol=1e-4):
+def compare_step(d, S, flat, x, eps, y, alpha, what, flags=None, estimator="standard", grad_rtol=1e-4, ref=None):
+    """ref: the statement's (C, g) on these arguments where the caller holds it already."""
     B = x.shape[0]
     p32 = O.unpack(O.MODEL_GMVAE, d, flat.astype(np.float64))
     gs, tail, masks = sstep(d, S, flat, x, eps, y, alpha, flags=flags)
-    Cc, g = SR.loss_and_grads(d, p32, x, eps, S, y, alpha, estimator=estimator)
+    Cc, g = ref or SR.loss_and_grads(d, p32, x, eps, S, y, alpha, estimator=estimator)
     gap = Cc["top2_gap"][Cc["labelled"]]
     assert gap.size == 0 or gap.min() > TOP2_GAP, (what, gap.min())      # hits is unambiguous at fp32
     _terms_ok(tail, B, Cc, what)

@@ -78,11 +78,13 @@ def _gates(what, tail, B, Cc):
     assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
 
 
-def compare_step(name, weights, what):
-    model, marginal, d, p32, flat, x, eps, u = WR.setup(name)
+def compare_step(name, weights, what, case=None, ref=None):
+    """case, ref: parameters and inputs in WR.setup's form and their statement (C, g), where they are not the case's own Xavier
+    ones (tests/test_objectives_saturated.py)."""
+    model, marginal, d, p32, flat, x, eps, u = case or WR.setup(name)
     B = x.shape[0]
     gs, tail, masks = wstep(model, marginal, d, flat, x, eps, u, weights)
-    Cc, g = _ref(name, weights)
+    Cc, g = ref or _ref(name, weights)
     _gates(what, tail, B, Cc)
     w32 = np.asarray(weights, np.float32)
     assert tail[5] == float(np.float32(B) * w32[0]) and tail[6] == float(np.float32(B) * w32[1]), (what, tail[5:7])

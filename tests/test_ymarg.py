@@ -89,11 +89,12 @@ def _grad_errs(d, gs, g, B):
     return out
 
 
-def compare_step(d, flat, x, eps, what, row0=0, grad_rtol=1e-4):
+def compare_step(d, flat, x, eps, what, row0=0, grad_rtol=1e-4, ref=None):
+    """ref: the statement's (C, g) on these arguments where the caller holds it already."""
     B = x.shape[0]
     p32 = O.unpack(O.MODEL_GMVAE, d, flat.astype(np.float64))
     gs, tail, masks = mstep(d, flat, x, eps, row0=row0)
-    Cc, g = YM.loss_and_grads(d, p32, x, eps)
+    Cc, g = ref or YM.loss_and_grads(d, p32, x, eps)
     _terms_ok(tail, B, Cc, what)
     errs = _grad_errs(d, gs, g, B)
     if max(e for _, e in errs) > grad_rtol and d.act == "relu":
@@ -101,6 +102,7 @@ def compare_step(d, flat, x, eps, what, row0=0, grad_rtol=1e-4):
             _, g = YM.loss_and_grads(d, p32, x, eps, relu_masks=masks)
             errs = _grad_errs(d, gs, g, B)
     for name, err in errs:
+        print(f"{what} {name}: rel-to-max err {err:.3e}")
         assert err <= grad_rtol, f"{what} {name}: rel-to-max err {err:.3e}"
     return gs, tail, Cc
 

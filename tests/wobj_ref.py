@@ -21,7 +21,7 @@ from ymarg_ref import LOG_2PI, _mlp, _mvn_logprob
 def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, weights=(1.0, 1.0, 0.0), marginal=False, relu_masks=None):
     """model: oracle.MODEL_*; x uint8 [B, D]; eps [R, L], R = B (B K with marginal); u [B, K] (Gumbel GMVAE only);
     weights = (beta_z, beta_y, lambda).  Returns (C, g): C = dict(loss, nll, kl, nent -- batch means; nll, kl, nent unweighted --,
-    kl_y [B] = nent_b + ln K, floor [B] = 1 - a_b, pre = per-net pre-activations) and g = {name: d loss / d param}
+    kl_y [B] = nent_b + ln K, floor [B] = 1 - a_b, q [B, K] = softmax(logits) (GMVAE), pre = per-net pre-activations) and g = {name: d loss / d param}
     (loss = mean_b L_b), all float64 numpy."""
     rm = relu_masks or {}
     bz, by, lam = (float(w) for w in weights)
@@ -92,7 +92,8 @@ def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, weights=(1.0, 1.0, 0.0),
     loss.backward()
     g = {k: v.grad.numpy().copy() if v.grad is not None else np.zeros_like(v.detach().numpy()) for k, v in t.items()}
     C = {"loss": loss.item(), "nll": nll_b.mean().item(), "kl": kl_b.mean().item(), "nent": nent.mean().item(),
-         "kl_y": nent.detach().numpy() + (math.log(K) if gm else 0.0), "floor": floor, "pre": pre}
+         "kl_y": nent.detach().numpy() + (math.log(K) if gm else 0.0), "floor": floor, "pre": pre,
+         "q": q.detach().numpy() if gm else None}
     return C, g
 
 
