@@ -181,29 +181,22 @@ def workspace_offset(dims, model, name):
     return off.value
 
 
-def iw_bound_workspace_bytes(dims, model):
-    b = C.c_uint64()
-    check(lib.gmvae_iw_bound_workspace_bytes(C.byref(dims), model, C.byref(b)), "gmvae_iw_bound_workspace_bytes")
-    return b.value
+def _chunked_workspace_bytes(name):
+    """The size query of a chunked importance-sampling evaluator (include/gmvae_hip.h gmvae_<name>_workspace_bytes)."""
+    sym = f"gmvae_{name}_workspace_bytes"
+
+    def query(dims, model):
+        b = C.c_uint64()
+        check(getattr(lib, sym)(C.byref(dims), model, C.byref(b)), sym)
+        return b.value
+    query.__name__ = f"{name}_workspace_bytes"
+    return query
 
 
-def iw_bound_enum_y_workspace_bytes(dims, model):
-    b = C.c_uint64()
-    check(lib.gmvae_iw_bound_enum_y_workspace_bytes(C.byref(dims), model, C.byref(b)), "gmvae_iw_bound_enum_y_workspace_bytes")
-    return b.value
-
-
-def posterior_y_workspace_bytes(dims, model):
-    b = C.c_uint64()
-    check(lib.gmvae_posterior_y_workspace_bytes(C.byref(dims), model, C.byref(b)), "gmvae_posterior_y_workspace_bytes")
-    return b.value
-
-
-def posterior_component_workspace_bytes(dims, model):
-    b = C.c_uint64()
-    check(lib.gmvae_posterior_component_workspace_bytes(C.byref(dims), model, C.byref(b)),
-          "gmvae_posterior_component_workspace_bytes")
-    return b.value
+iw_bound_workspace_bytes = _chunked_workspace_bytes("iw_bound")
+iw_bound_enum_y_workspace_bytes = _chunked_workspace_bytes("iw_bound_enum_y")
+posterior_y_workspace_bytes = _chunked_workspace_bytes("posterior_y")
+posterior_component_workspace_bytes = _chunked_workspace_bytes("posterior_component")
 
 
 def ptr(t):

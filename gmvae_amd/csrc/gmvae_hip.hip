@@ -2680,289 +2680,266 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
 
 static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// ---- gmvae_iw_bound: the workspace is the forward's at these dims (S = the chunk), then the call's own region (byte offsets);
-// gmvae_iw_bound_enum_y: the same at its marginal dims (S K rows per batch row; no u)
-struct IwLay { uint64_t eps, u, rows, ftail, state, rsum, bytes; };
-static void iw_lay(const GmvaeDims& d0, int model, const Layout& L, IwLay& o) {
-  GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);      // (the bounds and posteriors mask the bits: their sizes must not carry those regions)
+// ---- the chunked importance-sampling evaluators (gmvae_iw_bound, gmvae_iw_bound_enum_y, gmvae_posterior_y,
+// gmvae_posterior_component): ONE host path.  A kind is a row of kIwKinds, its own workspace regions in iw_lay and its merge
+// (and finishing) launch in iw_run; the dims, the layout, the argument checks and the two chunk loops are shared.
+enum IwKind { IW_BOUND, IW_BOUND_ENUM_Y, IW_POSTERIOR_Y, IW_POSTERIOR_COMPONENT };
+struct IwKindRow {
+  int model;        // the one model the kind takes, or -1: all three
+  bool enum_y;      // y summed out over K: S K rows per batch row (Philox row ((row0 + b) n + s) K + k), no u
+};
+constexpr IwKindRow kIwKinds[] = {{-1, false}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_VAE_GMP, false}};
+// bits that mean nothing to an evaluator: no gradient, no labels, no weights, and the operand images are prepared here, once
+// per call.  Masked HERE alone, so the size query and the run carve the workspace from the same dims.
+constexpr unsigned kIwMasked = GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS;
+
+// the kind's dims from the caller's (S = the chunk), or the entry point's error: kIwMasked cleared; the enumerating kinds ignore
+// GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW on entry and carry GMVAE_OBJ_MARGINAL_Y on return, the others refuse both
+static int iw_dims(IwKind kind, const GmvaeDims* dims, int model, GmvaeDims& d) {
+  const IwKindRow& k = kIwKinds[kind];
+  if (!dims) return GMVAE_E_NULL;
+  d = *dims;
+  d.sched_flags &= ~kIwMasked;
+  if (k.enum_y) d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW);
+  if (int e = check_dims(&d, model)) return e;
+  if (k.model >= 0 && model != k.model) return GMVAE_E_MODEL;
+  if (marginal_y(d)) return GMVAE_E_DIMS;                            // (y summed out: gmvae_iw_bound_enum_y)
+  if (k.enum_y) {
+    if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
+    d.sched_flags |= GMVAE_OBJ_MARGINAL_Y;
+  }
+  return 0;
+}
+
+// the workspace (byte offsets): the forward's at the kind's dims, then the regions every kind shares, then the kind's own
+struct IwLay {
+  uint64_t eps, u, rows, ftail, state, rsum;
+  uint64_t post;                                      // gmvae_posterior_y: the fold per component, [B][K][3] fp64
+  uint64_t pc_state, pc_ess, pc_side, pc_inv, pc_cst; // gmvae_posterior_component: state [B][K][2] fp64, ess [B][3] fp64, side = the
+                                                      // chunk's [R][K] component terms (evalf sizes) or its z [R][L] (every other
+                                                      // shape), inv [K][L] and cst [K] (gmp_consts, general schedule)
+  uint64_t bytes;
+};
+static void iw_lay(IwKind kind, const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
   WS w;
   carve(d, model, L, nullptr, w);
   uint64_t off = (w.bytes + 255) / 256 * 256;
   auto take = [&](uint64_t bytes) { const uint64_t r = off; off += (bytes + 255) / 256 * 256; return r; };
-  const uint64_t B = d.B, R = (uint64_t)d.B * rows_per_x(d);
-  o.eps = take(pad4(R * d.L) * 4);               // general schedule: the chunk's explicit noise
-  o.u = take(model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? pad4(R * d.K) * 4 : 0);
+  const uint64_t B = d.B, R = (uint64_t)d.B * rows_per_x(d), K = d.K, Lz = d.L;
+  memset(&o, 0, sizeof(o));
+  o.eps = take(pad4(R * Lz) * 4);                // general schedule: the chunk's explicit noise
+  o.u = take(model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? pad4(R * K) * 4 : 0);
   o.rows = take(R * 16);                         // ... its rows (log p(x|z), log q, log p, log w)
   o.ftail = take(GMVAE_TAIL * 4);                // ... the forward's own tail (tail[3]: the batch's nent sum)
   o.state = take(B * 6 * 8);                     // every schedule: the fp64 row state (evalf.hpp iw_fold)
   o.rsum = take(B * 16);                         // general schedule: the rows' (-bound, nll, kl) for iw_tail
+  if (kind == IW_POSTERIOR_Y) o.post = take(B * K * 3 * 8);
+  if (kind == IW_POSTERIOR_COMPONENT) {
+    o.pc_state = take(B * K * 16);
+    o.pc_ess = take(B * 24);
+    o.pc_side = take(R * (K > Lz ? K : Lz) * 4);
+    o.pc_inv = take(K * Lz * 4);
+    o.pc_cst = take(K * 4);
+  }
   o.bytes = off;
 }
 
-// ceil(n / S) chunk passes.  evalf sizes: first layers + operand images once, then ONE evalf_rows<3> / evalf_rows_v<2|3, L> launch per
-// chunk (noise drawn in the kernel); every other shape: iw_noise_fill -> the forward with that noise -> iw_merge per chunk, iw_tail.
-static int run_iw_bound(Ctx& cx, const GmvaeDims& d0, int model, const uint8_t* x, const float* params, uint64_t n,
-                        float* bound_out, float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
-  GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);      // (the operand images are prepared here, once per call)
+static int iw_workspace_bytes(IwKind kind, const GmvaeDims* dims, int model, uint64_t* bytes) {
+  GmvaeDims d;
+  if (int e = iw_dims(kind, dims, model, d)) return e;
+  if (!bytes) return GMVAE_E_NULL;
   Layout L;
   build_layout(d, model, L);
-  WS w;
-  carve(d, model, L, workspace, w);
   IwLay il;
-  iw_lay(d, model, L, il);
-  char* const base = static_cast<char*>(workspace);
-  double* const state = reinterpret_cast<double*>(base + il.state);
-  const int B = d.B, S = d.S;
-  const uint64_t nch = (n + S - 1) / S;
+  iw_lay(kind, d, model, L, il);
+  *bytes = il.bytes;
+  return 0;
+}
+
+// after the dims: NULL, then the range of n, then the alignment of every pointer given (out[]: the kind's outputs, each optional)
+static int iw_check_args(IwKind kind, const GmvaeDims& d, const uint8_t* x, const float* params, uint64_t n, float* const (&out)[3],
+                         const float* tail, const void* workspace) {
+  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
+  // (row0 + B) n [K] < 2^38: the row field of noise_vals
+  const uint64_t end = d.row0 + (uint64_t)d.B, per = kIwKinds[kind].enum_y ? (uint64_t)d.K : 1;
+  if (n == 0 || end < d.row0 || end > ((1ull << 38) - 1) / n / per) return GMVAE_E_DIMS;
+  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail)) return GMVAE_E_ALIGN;
+  for (const float* o : out)
+    if (o && !aligned16(o)) return GMVAE_E_ALIGN;
+  return 0;
+}
+
+// one call: the kind's dims (S = the chunk), the carved workspace and the caller's arguments
+struct IwCall {
+  GmvaeDims d;
+  int model;
+  Layout L;
+  WS w;
+  IwLay il;
+  const uint8_t* x;
+  const float* params;
+  float* tail;
+  void* workspace;
+  uint64_t n, nch, seed, step;
+  template <class T> T* at(uint64_t off) const { return reinterpret_cast<T*>(static_cast<char*>(workspace) + off); }
+};
+static StepArgs iw_step_args(const IwCall& c, const float* eps, const float* u, float* tail, float* rows, float* z_out) {
+  return {&c.d, c.model, c.x, eps, u, c.params, nullptr, tail, rows, z_out, nullptr, nullptr, c.workspace, c.seed, c.step, nullptr,
+          false};
+}
+
+// the general schedule's ceil(n / S) chunk passes: iw_noise_fill -> the forward with that noise (rows [R][4]; z_out when given)
+// -> merge(s0, last), the kind's fold of the chunk's rows
+template <class Merge>
+static int iw_general_chunks(Ctx& cx, const IwCall& c, float* z_out, Merge merge) {
+  const GmvaeDims& d = c.d;
+  const int per = rows_per_x(d) / d.S;             // (rows per sample: K with y summed out)
+  float* const eps = c.at<float>(c.il.eps);
+  float* const u = c.model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? c.at<float>(c.il.u) : nullptr;
+  const StepArgs a = iw_step_args(c, eps, u, c.at<float>(c.il.ftail), c.at<float>(c.il.rows), z_out);
+  const uint64_t S = d.S, q = noise_items(true, u != nullptr, (uint64_t)d.B * S * per, d.L, d.K);
+  for (uint64_t i = 0; i < c.nch; ++i) {
+    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, cx.st, eps, u, d.B, d.S * per, d.L, d.K,
+                       (unsigned long long)d.row0, (unsigned long long)(c.n * per), (unsigned long long)(i * S * per),
+                       (unsigned long long)c.seed, (unsigned long long)c.step);
+    rowk(cx, "iw_noise_fill");
+    if (int e = run_step(cx, a)) return e;
+    merge(i * S, i + 1 == c.nch);
+  }
+  return 0;
+}
+
+// the evalf sizes' chunk passes: first layers + operand images once, then ONE launch(grid, ea) per chunk (noise drawn in the
+// kernel, the fold inside it); ea = the forward's arguments with the chunk's (iw_s0, iw_final) and the fields `extra` adds
+template <class Extra, class Launch>
+static void iw_evalf_chunks(Ctx& cx, IwCall& c, Extra extra, Launch launch) {
+  const StepArgs a = iw_step_args(c, nullptr, nullptr, c.tail, nullptr, nullptr);
+  eval_fused_front(cx, a, c.L, c.w, true);
+  EvalArgs ea;
+  eval_fused_args(a, c.L, c.w, ea);
+  ea.row_base = c.d.row0;                          // (the kernels stride it: Philox row (row0 + b) n + s)
+  ea.dbg = nullptr;
+  ea.iw_n = c.n;
+  extra(ea);
+  const int grid = eval_fused_grid(c.d);
+  for (uint64_t i = 0; i < c.nch; ++i) {
+    ea.iw_s0 = i * (uint64_t)c.d.S; ea.iw_final = i + 1 == c.nch;
+    launch(grid, ea);
+  }
+}
+
+// gmvae_iw_bound: evalf_rows<3> / evalf_rows_v<2|3, L> at the evalf sizes (bound, mean log w and the tail from the last launch);
+//   every other shape iw_merge, the nent sum from the forward's tail
+// gmvae_iw_bound_enum_y: the marginal forward at R = B S K rows (y = e_k on row (b S + s) K + k; row_terms without the nent
+//   term) -> iw_merge_enum (nent in its slots)
+// gmvae_posterior_y: iw_merge_post in iw_merge_enum's place, the fold kept per component; then iw_post_finish (ln r, the row's
+//   stats, slots [B][4])
+// gmvae_posterior_component: gmvae_iw_bound's loops with the mixture's logsumexp left open -- evalf_rows_v<7, 64>, or
+//   gmp_consts once and iw_merge_comp on the forward's z --, then iw_post_comp_finish
+// and iw_tail on the slots.  out[]: (bound, mean_logw) or (log_joint, log_post, stats).
+static int iw_run(IwKind kind, const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n,
+                  float* const (&out)[3], float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream) {
+  IwCall c;
+  if (int e = iw_dims(kind, dims, model, c.d)) return e;
+  if (int e = iw_check_args(kind, c.d, x, params, n, out, tail, workspace)) return e;
+  Ctx cx;
+  cx.st = static_cast<hipStream_t>(stream);
   hipStream_t st = cx.st;
+  const GmvaeDims& d = c.d;
+  c.model = model; c.x = x; c.params = params; c.tail = tail; c.workspace = workspace; c.n = n; c.seed = seed; c.step = step;
+  c.nch = (n + d.S - 1) / d.S;
+  build_layout(d, model, c.L);
+  carve(d, model, c.L, workspace, c.w);
+  iw_lay(kind, d, model, c.L, c.il);
+  const IwLay& il = c.il;
+  const int B = d.B, S = d.S, K = d.K;
   const bool gm = model == GMVAE_MODEL_GMVAE;
-  if (evalf_ok(d, model) && w.ev_img) {
-    const StepArgs a = {&d, model, x, nullptr, nullptr, params, nullptr, tail, nullptr, nullptr, nullptr, nullptr, workspace,
-                        seed, step, nullptr, false};
-    eval_fused_front(cx, a, L, w, true);
-    EvalArgs ea;
-    eval_fused_args(a, L, w, ea);
-    ea.row_base = d.row0;                          // (the kernels stride it: Philox row (row0 + b) n + s)
-    ea.dbg = nullptr;
-    ea.iw_state = state; ea.iw_bound = bound_out; ea.iw_mlw = mlw_out; ea.iw_n = n;
-    const int grid = eval_fused_grid(d);
-    const size_t sh = (size_t)(gm ? EV::lds : EVV::lds) * sizeof(float);
-    for (uint64_t c = 0; c < nch; ++c) {
-      ea.iw_s0 = c * (uint64_t)S; ea.iw_final = c + 1 == nch;
-      if (gm) hipLaunchKernelGGL(evalf_rows<3>, dim3(grid), dim3(kMT), sh, st, ea);
-      else if (model == GMVAE_MODEL_VAE_GMP) hipLaunchKernelGGL((evalf_rows_v<3, 64>), dim3(grid), dim3(kMT), sh, st, ea);
-      else if (d.L == 2) hipLaunchKernelGGL((evalf_rows_v<2, 2>), dim3(grid), dim3(kMT), sh, st, ea);
-      else hipLaunchKernelGGL((evalf_rows_v<2, 64>), dim3(grid), dim3(kMT), sh, st, ea);
-      rowk(cx, gm ? "evalf_rows<3>" : "evalf_rows_v");
-    }
-    return cx.err;
-  }
-  float* const eps = reinterpret_cast<float*>(base + il.eps);
-  float* const u = gm ? reinterpret_cast<float*>(base + il.u) : nullptr;
-  float* const rows = reinterpret_cast<float*>(base + il.rows);
-  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
-  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
-  EvalArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.B = B; ma.S = S; ma.rows_ws = rows; ma.slots = rsum;
-  ma.iw_state = state; ma.iw_bound = bound_out; ma.iw_mlw = mlw_out; ma.iw_n = n;
-  const uint64_t q = noise_items(true, u != nullptr, (uint64_t)B * S, d.L, d.K);
-  for (uint64_t c = 0; c < nch; ++c) {
-    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, u, B, S, d.L, d.K,
-                       (unsigned long long)d.row0, (unsigned long long)n, (unsigned long long)(c * S), (unsigned long long)seed,
-                       (unsigned long long)step);
-    rowk(cx, "iw_noise_fill");
-    const StepArgs a = {&d, model, x, eps, u, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed, step,
-                        nullptr, false};
-    if (int e = run_step(cx, a)) return e;
-    ma.iw_s0 = c * (uint64_t)S; ma.iw_final = c + 1 == nch;
-    hipLaunchKernelGGL(iw_merge, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, ma);
-    rowk(cx, "iw_merge");
-  }
-  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, ftail, tail);
-  rowk(cx, "iw_tail");
-  return cx.err;
-}
-
-// gmvae_iw_bound_enum_y, d = the caller's dims with GMVAE_OBJ_MARGINAL_Y set (S = the chunk): per chunk iw_noise_fill at S K rows
-// per batch row (Philox row ((row0 + b) n + s0 + s) K + k) -> the marginal forward at R = B S K rows (y = e_k on row
-// (b S + s) K + k; row_terms without the nent term) -> iw_merge_enum; iw_tail once (nent from iw_merge_enum's slots).
-static int run_iw_bound_enum(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* bound_out,
-                             float* mlw_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
-  GmvaeDims d = d0;
-  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
-  const int model = GMVAE_MODEL_GMVAE;
-  Layout L;
-  build_layout(d, model, L);
-  WS w;
-  carve(d, model, L, workspace, w);
-  IwLay il;
-  iw_lay(d, model, L, il);
-  char* const base = static_cast<char*>(workspace);
-  const int B = d.B, S = d.S, K = d.K;
-  const uint64_t nch = (n + S - 1) / S;
-  hipStream_t st = cx.st;
-  float* const eps = reinterpret_cast<float*>(base + il.eps);
-  float* const rows = reinterpret_cast<float*>(base + il.rows);
-  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
-  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
-  EvalArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  ma.B = B; ma.S = S; ma.rows_ws = rows; ma.slots = rsum;
-  ma.iw_state = reinterpret_cast<double*>(base + il.state); ma.iw_bound = bound_out; ma.iw_mlw = mlw_out; ma.iw_n = n;
-  const uint64_t q = noise_items(true, false, (uint64_t)B * S * K, d.L, K);
-  for (uint64_t c = 0; c < nch; ++c) {
-    // (iw_noise_fill at S K samples of n K per batch row from s0 K: sample s of component k is Philox row ((row0 + b) n + s0 + s) K + k)
-    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S * K, d.L, K,
-                       (unsigned long long)d.row0, (unsigned long long)(n * K), (unsigned long long)(c * S * K),
-                       (unsigned long long)seed, (unsigned long long)step);
-    rowk(cx, "iw_noise_fill");
-    const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed,
-                        step, nullptr, false};
-    if (int e = run_step(cx, a)) return e;
-    ma.iw_s0 = c * (uint64_t)S; ma.iw_final = c + 1 == nch;
-    hipLaunchKernelGGL(iw_merge_enum, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, ma, (const float*)w.logits, K);
-    rowk(cx, "iw_merge_enum");
-  }
-  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
-  rowk(cx, "iw_tail");
-  return cx.err;
-}
-
-// gmvae_iw_bound_enum_y's dims: the caller's with GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW ignored on entry and
-// GMVAE_OBJ_MARGINAL_Y set on return (S K rows per batch row)
-static int iw_enum_dims(const GmvaeDims* dims, int model, GmvaeDims& d) {
-  if (!dims) return GMVAE_E_NULL;
-  d = *dims;
-  d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);
-  if (int e = check_dims(&d, model)) return e;
-  if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
-  if ((long long)d.B * d.S * d.K > (1LL << 30)) return GMVAE_E_DIMS;
-  d.sched_flags |= GMVAE_OBJ_MARGINAL_Y;
-  return 0;
-}
-
-
-// gmvae_posterior_y: run_iw_bound_enum's loop with iw_merge_post in iw_merge_enum's place -- the fold kept per component in
-// post [B][K][3] fp64, the call's own region behind the IwLay ones (post_y_bytes) --, then iw_post_finish (ln r, the row's
-// stats, slots [B][4]) and iw_tail on those slots.
-static uint64_t post_y_bytes(const GmvaeDims& d) { return ((uint64_t)d.B * d.K * 3 * 8 + 255) / 256 * 256; }
-static int run_posterior_y(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
-                           float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
-  GmvaeDims d = d0;
-  d.sched_flags &= ~GMVAE_SCHED_EVAL_IMAGES_VALID;
-  const int model = GMVAE_MODEL_GMVAE;
-  Layout L;
-  build_layout(d, model, L);
-  WS w;
-  carve(d, model, L, workspace, w);
-  IwLay il;
-  iw_lay(d, model, L, il);
-  char* const base = static_cast<char*>(workspace);
-  const int B = d.B, S = d.S, K = d.K;
-  const uint64_t nch = (n + S - 1) / S;
-  hipStream_t st = cx.st;
-  float* const eps = reinterpret_cast<float*>(base + il.eps);
-  float* const rows = reinterpret_cast<float*>(base + il.rows);
-  float* const ftail = reinterpret_cast<float*>(base + il.ftail);
-  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
-  double* const post = reinterpret_cast<double*>(base + il.bytes);
-  const uint64_t q = noise_items(true, false, (uint64_t)B * S * K, d.L, K);
-  const dim3 grid((unsigned)((B + 3) / 4));
-  for (uint64_t c = 0; c < nch; ++c) {
-    hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S * K, d.L, K,
-                       (unsigned long long)d.row0, (unsigned long long)(n * K), (unsigned long long)(c * S * K),
-                       (unsigned long long)seed, (unsigned long long)step);
-    rowk(cx, "iw_noise_fill");
-    const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, nullptr, nullptr, nullptr, workspace, seed,
-                        step, nullptr, false};
-    if (int e = run_step(cx, a)) return e;
-    hipLaunchKernelGGL(iw_merge_post, grid, dim3(256), 0, st, (const float*)rows, post, B, S, K, (unsigned long long)n,
-                       (unsigned long long)(c * S));
-    rowk(cx, "iw_merge_post");
-  }
-  hipLaunchKernelGGL(iw_post_finish, grid, dim3(256), 0, st, (const double*)post, (const float*)w.logits, B, K,
-                     (unsigned long long)n, lj_out, lp_out, stats_out, rsum);
-  rowk(cx, "iw_post_finish");
-  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
-  rowk(cx, "iw_tail");
-  return cx.err;
-}
-
-// gmvae_posterior_component (VAE_GMP): gmvae_iw_bound's loop with the mixture's logsumexp left open.  Its own regions behind the
-// IwLay ones: state [B][K][2] fp64, ess [B][3] fp64, side = the chunk's [R][K] component terms (evalf sizes) or its z [R][L] (every
-// other shape), inv [K][L] and cst [K] (gmp_consts, general schedule).
-struct PcLay { uint64_t state, ess, side, inv, cst, bytes; };
-static void pc_lay(const GmvaeDims& d, const IwLay& il, PcLay& o) {
-  uint64_t off = il.bytes;
-  auto take = [&](uint64_t bytes) { const uint64_t r = off; off += (bytes + 255) / 256 * 256; return r; };
-  const uint64_t B = d.B, R = B * (uint64_t)d.S, K = d.K, Lz = d.L;
-  o.state = take(B * K * 16);
-  o.ess = take(B * 24);
-  o.side = take(R * (K > Lz ? K : Lz) * 4);
-  o.inv = take(K * Lz * 4);
-  o.cst = take(K * 4);
-  o.bytes = off;
-}
-// evalf sizes: first layers + operand images once, then ONE evalf_rows_v<7, 64> launch per chunk (the fold inside it); every other
-// shape: iw_noise_fill -> the forward with that noise (z_out: the general schedule) -> iw_merge_comp per chunk.  Then
-// iw_post_comp_finish (log_joint, log_post, the rows' stats and slots) and iw_tail.
-static int run_posterior_component(Ctx& cx, const GmvaeDims& d0, const uint8_t* x, const float* params, uint64_t n, float* lj_out,
-                                   float* lp_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step) {
-  GmvaeDims d = d0;
-  d.sched_flags &= ~(GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS);
-  const int model = GMVAE_MODEL_VAE_GMP;
-  Layout L;
-  build_layout(d, model, L);
-  WS w;
-  carve(d, model, L, workspace, w);
-  IwLay il;
-  iw_lay(d, model, L, il);
-  PcLay pl;
-  pc_lay(d, il, pl);
-  char* const base = static_cast<char*>(workspace);
-  const int B = d.B, S = d.S, K = d.K;
-  const uint64_t nch = (n + S - 1) / S;
-  hipStream_t st = cx.st;
-  double* const state = reinterpret_cast<double*>(base + pl.state);
-  double* const ess = reinterpret_cast<double*>(base + pl.ess);
-  float* const side = reinterpret_cast<float*>(base + pl.side);
-  float* const rsum = reinterpret_cast<float*>(base + il.rsum);
+  const bool evalf = !kIwKinds[kind].enum_y && evalf_ok(d, model) && c.w.ev_img;
   const dim3 grid4((unsigned)((B + 3) / 4));
-  if (evalf_ok(d, model) && w.ev_img) {
-    const StepArgs a = {&d, model, x, nullptr, nullptr, params, nullptr, tail, nullptr, nullptr, nullptr, nullptr, workspace,
-                        seed, step, nullptr, false};
-    eval_fused_front(cx, a, L, w, true);
-    EvalArgs ea;
-    eval_fused_args(a, L, w, ea);
-    ea.row_base = d.row0;
-    ea.dbg = nullptr;
-    ea.iw_n = n; ea.pc_side = side; ea.pc_state = state; ea.pc_ess = ess;
-    const int grid = eval_fused_grid(d);
-    for (uint64_t c = 0; c < nch; ++c) {
-      ea.iw_s0 = c * (uint64_t)S; ea.iw_final = c + 1 == nch;
-      hipLaunchKernelGGL((evalf_rows_v<7, 64>), dim3(grid), dim3(kMT), (size_t)EVV::lds * sizeof(float), st, ea);
-      rowk(cx, "evalf_rows_v<7>");
+  float* const rows = c.at<float>(il.rows);
+  float* const rsum = c.at<float>(il.rsum);
+  const float* nent_tail = nullptr;                // (iw_tail: the nent sum from the forward's tail, or from the slots)
+  EvalArgs ma;                                     // iw_merge / iw_merge_enum
+  memset(&ma, 0, sizeof(ma));
+  ma.B = B; ma.S = S; ma.rows_ws = rows; ma.slots = rsum;
+  ma.iw_state = c.at<double>(il.state); ma.iw_bound = out[0]; ma.iw_mlw = out[1]; ma.iw_n = n;
+  switch (kind) {
+    case IW_BOUND:
+      if (evalf) {
+        const size_t sh = (size_t)(gm ? EV::lds : EVV::lds) * sizeof(float);
+        iw_evalf_chunks(
+            cx, c, [&](EvalArgs& ea) { ea.iw_state = ma.iw_state; ea.iw_bound = out[0]; ea.iw_mlw = out[1]; },
+            [&](int grid, const EvalArgs& ea) {
+              if (gm) hipLaunchKernelGGL(evalf_rows<3>, dim3(grid), dim3(kMT), sh, st, ea);
+              else if (model == GMVAE_MODEL_VAE_GMP) hipLaunchKernelGGL((evalf_rows_v<3, 64>), dim3(grid), dim3(kMT), sh, st, ea);
+              else if (d.L == 2) hipLaunchKernelGGL((evalf_rows_v<2, 2>), dim3(grid), dim3(kMT), sh, st, ea);
+              else hipLaunchKernelGGL((evalf_rows_v<2, 64>), dim3(grid), dim3(kMT), sh, st, ea);
+              rowk(cx, gm ? "evalf_rows<3>" : "evalf_rows_v");
+            });
+        return cx.err;
+      }
+      nent_tail = c.at<float>(il.ftail);
+      if (int e = iw_general_chunks(cx, c, nullptr, [&](uint64_t s0, bool last) {
+            ma.iw_s0 = s0; ma.iw_final = last;
+            hipLaunchKernelGGL(iw_merge, grid4, dim3(256), 0, st, ma);
+            rowk(cx, "iw_merge");
+          }))
+        return e;
+      break;
+    case IW_BOUND_ENUM_Y:
+      if (int e = iw_general_chunks(cx, c, nullptr, [&](uint64_t s0, bool last) {
+            ma.iw_s0 = s0; ma.iw_final = last;
+            hipLaunchKernelGGL(iw_merge_enum, grid4, dim3(256), 0, st, ma, (const float*)c.w.logits, K);
+            rowk(cx, "iw_merge_enum");
+          }))
+        return e;
+      break;
+    case IW_POSTERIOR_Y: {
+      double* const post = c.at<double>(il.post);
+      if (int e = iw_general_chunks(cx, c, nullptr, [&](uint64_t s0, bool) {
+            hipLaunchKernelGGL(iw_merge_post, grid4, dim3(256), 0, st, (const float*)rows, post, B, S, K, (unsigned long long)n,
+                               (unsigned long long)s0);
+            rowk(cx, "iw_merge_post");
+          }))
+        return e;
+      hipLaunchKernelGGL(iw_post_finish, grid4, dim3(256), 0, st, (const double*)post, (const float*)c.w.logits, B, K,
+                         (unsigned long long)n, out[0], out[1], out[2], rsum);
+      rowk(cx, "iw_post_finish");
+      break;
     }
-  } else {
-    float* const eps = reinterpret_cast<float*>(base + il.eps);
-    float* const rows = reinterpret_cast<float*>(base + il.rows);
-    float* const ftail = reinterpret_cast<float*>(base + il.ftail);
-    float* const inv = reinterpret_cast<float*>(base + pl.inv);
-    float* const cst = reinterpret_cast<float*>(base + pl.cst);
-    hipLaunchKernelGGL(gmp_consts, dim3(K), dim3(256), 0, st, params + L.rawscale, params + L.mixlog, inv, cst, d.L, K);
-    rowk(cx, "gmp_consts");
-    const uint64_t q = noise_items(true, false, (uint64_t)B * S, d.L, K);
-    for (uint64_t c = 0; c < nch; ++c) {
-      hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, eps, (float*)nullptr, B, S, d.L, K,
-                         (unsigned long long)d.row0, (unsigned long long)n, (unsigned long long)(c * S), (unsigned long long)seed,
-                         (unsigned long long)step);
-      rowk(cx, "iw_noise_fill");
-      const StepArgs a = {&d, model, x, eps, nullptr, params, nullptr, ftail, rows, side, nullptr, nullptr, workspace, seed, step,
-                          nullptr, false};
-      if (int e = run_step(cx, a)) return e;
-      hipLaunchKernelGGL(iw_merge_comp, grid4, dim3(256), 0, st, (const float*)rows, (const float*)side, params + L.loc,
-                         (const float*)inv, (const float*)cst, state, ess, B, S, d.L, K, (unsigned long long)n,
-                         (unsigned long long)(c * S));
-      rowk(cx, "iw_merge_comp");
+    case IW_POSTERIOR_COMPONENT: {
+      double* const state = c.at<double>(il.pc_state);
+      double* const ess = c.at<double>(il.pc_ess);
+      float* const side = c.at<float>(il.pc_side);
+      if (evalf) {
+        iw_evalf_chunks(
+            cx, c, [&](EvalArgs& ea) { ea.pc_side = side; ea.pc_state = state; ea.pc_ess = ess; },
+            [&](int grid, const EvalArgs& ea) {
+              hipLaunchKernelGGL((evalf_rows_v<7, 64>), dim3(grid), dim3(kMT), (size_t)EVV::lds * sizeof(float), st, ea);
+              rowk(cx, "evalf_rows_v<7>");
+            });
+      } else {
+        float* const inv = c.at<float>(il.pc_inv);
+        float* const cst = c.at<float>(il.pc_cst);
+        hipLaunchKernelGGL(gmp_consts, dim3(K), dim3(256), 0, st, params + c.L.rawscale, params + c.L.mixlog, inv, cst, d.L, K);
+        rowk(cx, "gmp_consts");
+        if (int e = iw_general_chunks(cx, c, side, [&](uint64_t s0, bool) {
+              hipLaunchKernelGGL(iw_merge_comp, grid4, dim3(256), 0, st, (const float*)rows, (const float*)side, params + c.L.loc,
+                                 (const float*)inv, (const float*)cst, state, ess, B, S, d.L, K, (unsigned long long)n,
+                                 (unsigned long long)s0);
+              rowk(cx, "iw_merge_comp");
+            }))
+          return e;
+      }
+      hipLaunchKernelGGL(iw_post_comp_finish, grid4, dim3(256), 0, st, (const double*)state, (const double*)ess,
+                         params + c.L.mixlog, B, K, (unsigned long long)n, out[0], out[1], out[2], rsum);
+      rowk(cx, "iw_post_comp_finish");
+      break;
     }
   }
-  hipLaunchKernelGGL(iw_post_comp_finish, grid4, dim3(256), 0, st, (const double*)state, (const double*)ess, params + L.mixlog, B,
-                     K, (unsigned long long)n, lj_out, lp_out, stats_out, rsum);
-  rowk(cx, "iw_post_comp_finish");
-  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, (const float*)nullptr, tail);
+  hipLaunchKernelGGL(iw_tail, dim3(1), dim3(256), 0, st, rsum, B, nent_tail, tail);
   rowk(cx, "iw_tail");
   return cx.err;
-}
-
-// gmvae_posterior_component's checks on the dims: the VAE_GMP's alone, B S rows within 2^30
-static int pc_dims(const GmvaeDims* dims, int model) {
-  if (int e = check_dims(dims, model)) return e;
-  if (model != GMVAE_MODEL_VAE_GMP) return GMVAE_E_MODEL;
-  if (marginal_y(*dims) || (long long)dims->B * dims->S > (1LL << 30)) return GMVAE_E_DIMS;
-  return 0;
 }
 
 }  // namespace
@@ -3055,118 +3032,47 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
 }
 
 int gmvae_iw_bound_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
-  if (int e = check_dims(dims, model)) return e;
-  if (marginal_y(*dims)) return GMVAE_E_DIMS;
-  if (!bytes) return GMVAE_E_NULL;
-  Layout L;
-  build_layout(*dims, model, L);
-  IwLay il;
-  iw_lay(*dims, model, L, il);
-  *bytes = il.bytes;
-  return 0;
+  return iw_workspace_bytes(IW_BOUND, dims, model, bytes);
 }
 
 int gmvae_iw_bound(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
                    float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                    void* stream) {
-  if (int e = check_dims(dims, model)) return e;
-  if (marginal_y(*dims)) return GMVAE_E_DIMS;                       // (y summed out: gmvae_iw_bound_enum_y)
-  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
-  const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
-  if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
-  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) || (bound_out && !aligned16(bound_out)) ||
-      (mean_logw_out && !aligned16(mean_logw_out)))
-    return GMVAE_E_ALIGN;
-  Ctx cx;
-  cx.st = static_cast<hipStream_t>(stream);
-  return run_iw_bound(cx, *dims, model, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
+  return iw_run(IW_BOUND, dims, model, x, params, n_samples, {bound_out, mean_logw_out, nullptr}, tail, workspace, seed, step,
+                stream);
 }
 
 int gmvae_iw_bound_enum_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
-  GmvaeDims d;
-  if (int e = iw_enum_dims(dims, model, d)) return e;
-  if (!bytes) return GMVAE_E_NULL;
-  Layout L;
-  build_layout(d, model, L);
-  IwLay il;
-  iw_lay(d, model, L, il);
-  *bytes = il.bytes;
-  return 0;
+  return iw_workspace_bytes(IW_BOUND_ENUM_Y, dims, model, bytes);
 }
 
 int gmvae_iw_bound_enum_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
                           float* bound_out, float* mean_logw_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
                           void* stream) {
-  GmvaeDims d;
-  if (int e = iw_enum_dims(dims, model, d)) return e;
-  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
-  const uint64_t end = d.row0 + (uint64_t)d.B;             // (row0 + B) n K < 2^38: the row field of noise_vals
-  if (n_samples == 0 || end < d.row0 || end > ((1ull << 38) - 1) / n_samples / (uint64_t)d.K) return GMVAE_E_DIMS;
-  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) || (bound_out && !aligned16(bound_out)) ||
-      (mean_logw_out && !aligned16(mean_logw_out)))
-    return GMVAE_E_ALIGN;
-  Ctx cx;
-  cx.st = static_cast<hipStream_t>(stream);
-  return run_iw_bound_enum(cx, d, x, params, n_samples, bound_out, mean_logw_out, tail, workspace, seed, step);
+  return iw_run(IW_BOUND_ENUM_Y, dims, model, x, params, n_samples, {bound_out, mean_logw_out, nullptr}, tail, workspace, seed,
+                step, stream);
 }
 
 int gmvae_posterior_y_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
-  GmvaeDims d;
-  if (int e = iw_enum_dims(dims, model, d)) return e;
-  if (!bytes) return GMVAE_E_NULL;
-  Layout L;
-  build_layout(d, model, L);
-  IwLay il;
-  iw_lay(d, model, L, il);
-  *bytes = il.bytes + post_y_bytes(d);
-  return 0;
+  return iw_workspace_bytes(IW_POSTERIOR_Y, dims, model, bytes);
 }
 
 int gmvae_posterior_y(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
                       float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace, uint64_t seed,
                       uint64_t step, void* stream) {
-  GmvaeDims d;
-  if (int e = iw_enum_dims(dims, model, d)) return e;
-  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
-  const uint64_t end = d.row0 + (uint64_t)d.B;             // (row0 + B) n K < 2^38: the row field of noise_vals
-  if (n_samples == 0 || end < d.row0 || end > ((1ull << 38) - 1) / n_samples / (uint64_t)d.K) return GMVAE_E_DIMS;
-  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) ||
-      (log_joint_out && !aligned16(log_joint_out)) || (log_post_out && !aligned16(log_post_out)) ||
-      (stats_out && !aligned16(stats_out)))
-    return GMVAE_E_ALIGN;
-  Ctx cx;
-  cx.st = static_cast<hipStream_t>(stream);
-  return run_posterior_y(cx, d, x, params, n_samples, log_joint_out, log_post_out, stats_out, tail, workspace, seed, step);
+  return iw_run(IW_POSTERIOR_Y, dims, model, x, params, n_samples, {log_joint_out, log_post_out, stats_out}, tail, workspace, seed,
+                step, stream);
 }
 
 int gmvae_posterior_component_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
-  if (int e = pc_dims(dims, model)) return e;
-  if (!bytes) return GMVAE_E_NULL;
-  Layout L;
-  build_layout(*dims, model, L);
-  IwLay il;
-  iw_lay(*dims, model, L, il);
-  PcLay pl;
-  pc_lay(*dims, il, pl);
-  *bytes = pl.bytes;
-  return 0;
+  return iw_workspace_bytes(IW_POSTERIOR_COMPONENT, dims, model, bytes);
 }
 
 int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples,
                               float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace,
                               uint64_t seed, uint64_t step, void* stream) {
-  if (int e = pc_dims(dims, model)) return e;
-  if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
-  const uint64_t end = dims->row0 + (uint64_t)dims->B;             // (row0 + B) n < 2^38: the row field of noise_vals
-  if (n_samples == 0 || end < dims->row0 || end > ((1ull << 38) - 1) / n_samples) return GMVAE_E_DIMS;
-  if (!aligned16(x) || !aligned16(params) || !aligned16(workspace) || !aligned16(tail) ||
-      (log_joint_out && !aligned16(log_joint_out)) || (log_post_out && !aligned16(log_post_out)) ||
-      (stats_out && !aligned16(stats_out)))
-    return GMVAE_E_ALIGN;
-  Ctx cx;
-  cx.st = static_cast<hipStream_t>(stream);
-  return run_posterior_component(cx, *dims, x, params, n_samples, log_joint_out, log_post_out, stats_out, tail, workspace, seed,
-                                 step);
+  return iw_run(IW_POSTERIOR_COMPONENT, dims, model, x, params, n_samples, {log_joint_out, log_post_out, stats_out}, tail,
+                workspace, seed, step, stream);
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

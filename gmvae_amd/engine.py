@@ -163,10 +163,7 @@ class Engine:
         self._graph_gen = 0                     # bumped by drop_graphs: replay closures of dropped graphs raise
         self._param_epoch = 0                   # bumped by every Engine call that enqueues a writer of the parameter buffer
         self._eval_imgs: Dict[tuple, tuple] = {}   # (B, S) -> the state of the parameters a forward-only pass left images for
-        self._iw_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound's workspace
-        self._iw_enum_ws: Dict[tuple, torch.Tensor] = {}  # (B, chunk) -> gmvae_iw_bound_enum_y's workspace
-        self._post_y_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_y's workspace
-        self._post_comp_ws: Dict[tuple, torch.Tensor] = {}   # (B, chunk) -> gmvae_posterior_component's workspace
+        self._chunked_ws: Dict[tuple, torch.Tensor] = {}  # (kind, B, chunk) -> the workspace of a chunked evaluator (_CHUNKED)
         # weighted objective: the current (kl_weight, y_weight, y_free_nats, 0) on the device; every eager entry copies it into
         # slot 0 of its workspace's weight rows (device to device: a captured graph may have left its own row there)
         self._objw_dev = None
@@ -435,6 +432,39 @@ class Engine:
 
     IW_CHUNK_ROWS = 51200          # default B * chunk of iw_bound: the rows of bench.py's eval_iwae pass (B = 1024, S = 50)
 
+    # the chunked importance-sampling evaluators, gmvae_<kind> and gmvae_<kind>_workspace_bytes of include/gmvae_hip.h:
+    # kind -> (y enumerated: K rows per sample in the default chunk; outputs per component: log_joint [B, K], log_post [B, K]
+    # and stats [B, 4] in place of bound [B] and mean_logw [B])
+    _CHUNKED = {"iw_bound": (False, False), "iw_bound_enum_y": (True, False), "posterior_y": (True, True),
+                "posterior_component": (False, True)}
+
+    def _chunked_eval(self, kind: str, x, n_samples: int, chunk: Optional[int], row0: Optional[int]):
+        """One call of a chunked evaluator: (its output tensors in the order of the C signature, tail [8])."""
+        enum_y, per_component = self._CHUNKED[kind]
+        x = self._prep_x(x)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        B, n = x.shape[0], int(n_samples)
+        if n < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n}")
+        chunk = max(1, min(n, self.IW_CHUNK_ROWS // (B * self.K if enum_y else B))) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        d = self.dims(B, chunk, row0)
+        nw = getattr(L, f"{kind}_workspace_bytes")(d, self.model) // 4 + 64
+        ws = self._chunked_ws.get((kind, B, chunk))
+        if ws is None or ws.numel() < nw:
+            ws = self._chunked_ws[(kind, B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        shapes = ((B, self.K), (B, self.K), (B, 4)) if per_component else ((B,), (B,))
+        outs = [torch.empty(*shape, **f32) for shape in shapes]
+        tail = torch.empty(L.TAIL, **f32)
+        rc = getattr(L.lib, f"gmvae_{kind}")(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, *map(L.ptr, outs),
+                                             L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step, L.current_stream())
+        L.check(rc, f"gmvae_{kind}")
+        self._keep_iw = x
+        return outs, tail
+
     def iw_bound(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
         """The importance-weighted bound at any number of samples, streamed in chunks (include/gmvae_hip.h gmvae_iw_bound):
         dict(bound [B] = logsumexp_s log w - log n, mean_logw [B], tail [8] as forward's at S = n).  chunk: samples per pass
@@ -444,28 +474,8 @@ class Engine:
         if self.marginal:
             raise ValueError(f"iw_bound: the importance-weighted bound is not available with y_inference={self.y_inference!r} "
                              "(it is the Gumbel objective's bound)")
-        x = self._prep_x(x)
-        if x.data_ptr() % 16:
-            x = x.clone()
-        B, n = x.shape[0], int(n_samples)
-        if n < 1:
-            raise ValueError(f"n_samples must be >= 1, got {n}")
-        chunk = max(1, min(n, self.IW_CHUNK_ROWS // B)) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"chunk must be >= 1, got {chunk}")
-        d = self.dims(B, chunk, row0)
-        nw = L.iw_bound_workspace_bytes(d, self.model) // 4 + 64
-        ws = self._iw_ws.get((B, chunk))
-        if ws is None or ws.numel() < nw:
-            ws = self._iw_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        o = dict(bound=torch.empty(B, **f32), mean_logw=torch.empty(B, **f32), tail=torch.empty(L.TAIL, **f32))
-        rc = L.lib.gmvae_iw_bound(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(o["bound"]),
-                                  L.ptr(o["mean_logw"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
-                                  L.current_stream())
-        L.check(rc, "gmvae_iw_bound")
-        self._keep_iw = x
-        return o
+        (bound, mean_logw), tail = self._chunked_eval("iw_bound", x, n_samples, chunk, row0)
+        return dict(bound=bound, mean_logw=mean_logw, tail=tail)
 
     def iw_bound_enum_y(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
         """The GMVAE's importance-weighted bound with y summed out exactly over its K components, streamed in chunks
@@ -477,28 +487,8 @@ class Engine:
         the result does not depend on the chunk, the batch size or the sharding."""
         if self.model != L.MODEL_GMVAE:
             raise ValueError("iw_bound_enum_y sums y out over the GMVAE's mixture components: not available for the VAE family")
-        x = self._prep_x(x)
-        if x.data_ptr() % 16:
-            x = x.clone()
-        B, n = x.shape[0], int(n_samples)
-        if n < 1:
-            raise ValueError(f"n_samples must be >= 1, got {n}")
-        chunk = max(1, min(n, self.IW_CHUNK_ROWS // (B * self.K))) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"chunk must be >= 1, got {chunk}")
-        d = self.dims(B, chunk, row0)
-        nw = L.iw_bound_enum_y_workspace_bytes(d, self.model) // 4 + 64
-        ws = self._iw_enum_ws.get((B, chunk))
-        if ws is None or ws.numel() < nw:
-            ws = self._iw_enum_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        o = dict(bound=torch.empty(B, **f32), mean_logw=torch.empty(B, **f32), tail=torch.empty(L.TAIL, **f32))
-        rc = L.lib.gmvae_iw_bound_enum_y(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(o["bound"]),
-                                         L.ptr(o["mean_logw"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
-                                         L.current_stream())
-        L.check(rc, "gmvae_iw_bound_enum_y")
-        self._keep_iw = x
-        return o
+        (bound, mean_logw), tail = self._chunked_eval("iw_bound_enum_y", x, n_samples, chunk, row0)
+        return dict(bound=bound, mean_logw=mean_logw, tail=tail)
 
     def posterior_y(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
         """The GMVAE's own posterior over its component, p(y = k | x) = softmax_k l_k with l_k = logsumexp_s log w'_sk - log n
@@ -509,27 +499,7 @@ class Engine:
         keying as iw_bound_enum_y: the result does not depend on the chunk, the batch size or the sharding."""
         if self.model != L.MODEL_GMVAE:
             raise ValueError("posterior_y is the posterior over the GMVAE's mixture components: not available for the VAE family")
-        x = self._prep_x(x)
-        if x.data_ptr() % 16:
-            x = x.clone()
-        B, n = x.shape[0], int(n_samples)
-        if n < 1:
-            raise ValueError(f"n_samples must be >= 1, got {n}")
-        chunk = max(1, min(n, self.IW_CHUNK_ROWS // (B * self.K))) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"chunk must be >= 1, got {chunk}")
-        d = self.dims(B, chunk, row0)
-        nw = L.posterior_y_workspace_bytes(d, self.model) // 4 + 64
-        ws = self._post_y_ws.get((B, chunk))
-        if ws is None or ws.numel() < nw:
-            ws = self._post_y_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        lj, lp, stats = torch.empty(B, self.K, **f32), torch.empty(B, self.K, **f32), torch.empty(B, 4, **f32)
-        tail = torch.empty(L.TAIL, **f32)
-        rc = L.lib.gmvae_posterior_y(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(lj), L.ptr(lp), L.ptr(stats),
-                                     L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step, L.current_stream())
-        L.check(rc, "gmvae_posterior_y")
-        self._keep_iw = x
+        (lj, lp, stats), tail = self._chunked_eval("posterior_y", x, n_samples, chunk, row0)
         return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_q_post=stats[:, 2], ess=stats[:, 3],
                     tail=tail)
 
@@ -544,28 +514,7 @@ class Engine:
         if self.model != L.MODEL_VAE_GMP:
             raise ValueError("posterior_component is the posterior over the components of the VAE's learned mixture prior: "
                              "it needs model 'vae_gmp' (the GMVAE has posterior_y)")
-        x = self._prep_x(x)
-        if x.data_ptr() % 16:
-            x = x.clone()
-        B, n = x.shape[0], int(n_samples)
-        if n < 1:
-            raise ValueError(f"n_samples must be >= 1, got {n}")
-        chunk = max(1, min(n, self.IW_CHUNK_ROWS // B)) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"chunk must be >= 1, got {chunk}")
-        d = self.dims(B, chunk, row0)
-        nw = L.posterior_component_workspace_bytes(d, self.model) // 4 + 64
-        ws = self._post_comp_ws.get((B, chunk))
-        if ws is None or ws.numel() < nw:
-            ws = self._post_comp_ws[(B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        lj, lp, stats = torch.empty(B, self.K, **f32), torch.empty(B, self.K, **f32), torch.empty(B, 4, **f32)
-        tail = torch.empty(L.TAIL, **f32)
-        rc = L.lib.gmvae_posterior_component(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, L.ptr(lj), L.ptr(lp),
-                                             L.ptr(stats), L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step,
-                                             L.current_stream())
-        L.check(rc, "gmvae_posterior_component")
-        self._keep_iw = x
+        (lj, lp, stats), tail = self._chunked_eval("posterior_component", x, n_samples, chunk, row0)
         return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_post_prior=stats[:, 2],
                     ess=stats[:, 3], tail=tail)
 

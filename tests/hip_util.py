@@ -1,5 +1,6 @@
 """Helpers for the -m gpu parity tests: call the C ABI with torch device buffers."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -107,6 +108,58 @@ def hip_forward(model, d: O.Dims, flat, x, eps, u, want_rows=True):
     L.check(rc, "gmvae_forward")
     torch.cuda.synchronize()
     return tail.cpu().numpy(), rows.cpu().numpy(), z.cpu().numpy(), y.cpu().numpy(), lg.cpu().numpy()
+
+
+def forward_call(model, d: O.Dims, flat, x, S, eps=None, u=None, row0=0, flags=0, seed=0, step=0, logits=False):
+    """gmvae_forward at S samples under sched_flags `flags` (in-kernel noise when eps is None): (tail [8], rows [R, 4], logits
+    [B, K] or None) as numpy, R = B S rows, B S K with y summed out.  Every output starts as NaN."""
+    B = x.shape[0]
+    cd = dims_of(dataclasses.replace(d, S=S), B)
+    cd.row0, cd.sched_flags = row0, flags
+    R = B * S * (d.K if flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW) else 1)
+    ws = workspace(cd, model)
+    tail = torch.full((L.TAIL,), float("nan"), device="cuda")
+    rows = torch.full((R, 4), float("nan"), device="cuda")
+    lg = torch.full((B, d.K), float("nan"), device="cuda") if logits else None
+    xd, params = dev(x, torch.uint8), dev(flat, torch.float32)          # (held until the kernels have run)
+    ed = None if eps is None else dev(eps, torch.float32)
+    ud = None if u is None else dev(u, torch.float32)
+    rc = L.lib.gmvae_forward(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(tail), L.ptr(rows), None,
+                             None, L.ptr(lg), L.ptr(ws), seed, step, L.current_stream())
+    L.check(rc, "gmvae_forward")
+    torch.cuda.synchronize()
+    return tail.cpu().numpy(), rows.cpu().numpy(), None if lg is None else lg.cpu().numpy()
+
+
+# the chunked importance-sampling evaluators (include/gmvae_hip.h gmvae_<kind>): the names of their outputs, in the C signature's order
+CHUNKED_OUTPUTS = {"iw_bound": ("bound", "mean_logw"), "iw_bound_enum_y": ("bound", "mean_logw"),
+                   "posterior_y": ("log_joint", "log_post", "stats"), "posterior_component": ("log_joint", "log_post", "stats")}
+
+
+def chunked_call(kind, model, d: O.Dims, flat, x, n, chunk, row0=0, flags=0, seed=0, step=0, omit=()):
+    """One gmvae_<kind> call at n samples in passes of `chunk`: dict of its outputs (CHUNKED_OUTPUTS; bound and mean_logw [B],
+    log_joint and log_post [B, K], stats [B, 4]) and tail [8] as numpy.  Every output starts as NaN; the ones named in `omit`
+    are passed as NULL and left out."""
+    B = x.shape[0]
+    cd = dims_of(dataclasses.replace(d, S=chunk), B)
+    cd.row0, cd.sched_flags = row0, flags
+    ws = torch.zeros(getattr(L, f"{kind}_workspace_bytes")(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
+    shape = {"bound": (B,), "mean_logw": (B,), "log_joint": (B, d.K), "log_post": (B, d.K), "stats": (B, 4)}
+    out = {k: None if k in omit else torch.full(shape[k], float("nan"), device="cuda") for k in CHUNKED_OUTPUTS[kind]}
+    out["tail"] = torch.full((L.TAIL,), float("nan"), device="cuda")
+    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
+    rc = getattr(L.lib, f"gmvae_{kind}")(C.byref(cd), model, L.ptr(xd), L.ptr(params), n, *(L.ptr(t) for t in out.values()),
+                                         L.ptr(ws), seed, step, L.current_stream())
+    L.check(rc, f"gmvae_{kind}")
+    torch.cuda.synchronize()
+    return {k: t.cpu().numpy() for k, t in out.items() if t is not None}
+
+
+def lse(v, axis=None):
+    """logsumexp in fp64 over `axis` (everything by default)."""
+    v = np.asarray(v, np.float64)
+    m = v.max(axis=axis, keepdims=True)
+    return np.squeeze(m + np.log(np.exp(v - m).sum(axis=axis, keepdims=True)), axis=axis)
 
 
 MARGINS = []      # (what, worst error / its gate) of every compare_step call: tests/test_hip_parity.py prints the maxima

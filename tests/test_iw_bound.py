@@ -1,14 +1,14 @@
 """gmvae_iw_bound (include/gmvae_hip.h): the importance-weighted bound at any number of samples, streamed in chunks -- against the
 fp64 oracle on its own Philox noise, against the one-shot gmvae_forward, and invariant under the chunk, the batch and the sharding,
 on both schedules (evalf.hpp's one launch per chunk at the reference's default sizes; noise fill + forward + iw_merge elsewhere)."""
-import ctypes as C
 import dataclasses
 
 import numpy as np
 import pytest
 
 import oracle as O
-from hip_util import dev, dims_of
+import hip_util
+from hip_util import dims_of
 
 pytestmark = pytest.mark.gpu
 
@@ -38,47 +38,17 @@ def _setup(name, B, seed=0):
 
 def iw(model, d, flat, x, n, chunk, row0=0, seed=SEED, step=STEP):
     """One gmvae_iw_bound call: (bound [B], mean_logw [B], tail [8]) as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.iw_bound_workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
-    bound = torch.full((B,), float("nan"), device="cuda")
-    mlw = torch.full((B,), float("nan"), device="cuda")
-    tail = torch.full((L.TAIL,), float("nan"), device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    rc = L.lib.gmvae_iw_bound(C.byref(cd), model, L.ptr(xd), L.ptr(params), n, L.ptr(bound), L.ptr(mlw), L.ptr(tail),
-                              L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_iw_bound")
-    torch.cuda.synchronize()
-    return bound.cpu().numpy(), mlw.cpu().numpy(), tail.cpu().numpy()
+    o = hip_util.chunked_call("iw_bound", model, d, flat, x, n, chunk, row0, seed=seed, step=step)
+    return o["bound"], o["mean_logw"], o["tail"]
 
 
 def forward(model, d, flat, x, S, eps=None, u=None, row0=0, seed=SEED, step=STEP):
     """gmvae_forward at S samples (in-kernel noise when eps is None): (tail [8], rows [B S, 4])."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=S), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
-    tail = torch.zeros(L.TAIL, device="cuda")
-    rows = torch.zeros(B * S, 4, device="cuda")
-    xd, params = dev(x, torch.uint8), dev(flat, torch.float32)          # (held until the kernels have run)
-    ed = None if eps is None else dev(eps, torch.float32)
-    ud = None if u is None else dev(u, torch.float32)
-    rc = L.lib.gmvae_forward(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(tail), L.ptr(rows), None,
-                             None, None, L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_forward")
-    torch.cuda.synchronize()
-    return tail.cpu().numpy(), rows.cpu().numpy()
+    return hip_util.forward_call(model, d, flat, x, S, eps, u, row0, seed=seed, step=step)[:2]
 
 
 def lse(lw):
-    lw = np.asarray(lw, np.float64)
-    m = lw.max(axis=-1, keepdims=True)
-    return m[..., 0] + np.log(np.exp(lw - m).sum(axis=-1)) - np.log(lw.shape[-1])
+    return hip_util.lse(lw, axis=-1) - np.log(np.shape(lw)[-1])
 
 
 _REF = {}

@@ -10,7 +10,8 @@ import pytest
 
 import oracle as O
 import ymarg_ref as YM
-from hip_util import dev, dims_of
+import hip_util
+from hip_util import dev, dims_of, lse
 
 pytestmark = pytest.mark.gpu
 
@@ -42,27 +43,8 @@ def _setup(d, B, seed=0):
 
 def enum(d, flat, x, n, chunk, row0=0, flags=0, seed=SEED, step=STEP):
     """One gmvae_iw_bound_enum_y call: (bound [B], mean_logw [B], tail [8]) as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0, cd.sched_flags = row0, flags
-    ws = torch.zeros(L.iw_bound_enum_y_workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    bound = torch.full((B,), float("nan"), device="cuda")
-    mlw = torch.full((B,), float("nan"), device="cuda")
-    tail = torch.full((L.TAIL,), float("nan"), device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    rc = L.lib.gmvae_iw_bound_enum_y(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(params), n, L.ptr(bound), L.ptr(mlw),
-                                     L.ptr(tail), L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_iw_bound_enum_y")
-    torch.cuda.synchronize()
-    return bound.cpu().numpy(), mlw.cpu().numpy(), tail.cpu().numpy()
-
-
-def lse(v):
-    v = np.asarray(v, np.float64)
-    m = v.max()
-    return m + np.log(np.exp(v - m).sum())
+    o = hip_util.chunked_call("iw_bound_enum_y", O.MODEL_GMVAE, d, flat, x, n, chunk, row0, flags, seed, step)
+    return o["bound"], o["mean_logw"], o["tail"]
 
 
 _REF = {}
@@ -102,21 +84,8 @@ def test_enum_bound_matches_the_fp64_statement(name, n):
 
 def _marginal_forward(d, flat, x, row0, seed=SEED, step=STEP):
     """gmvae_forward under GMVAE_OBJ_MARGINAL_Y with in-kernel noise: (tail [8], rows [B K, 4], logits [B, K])."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=1), B)
-    cd.row0, cd.sched_flags = row0, L.OBJ_MARGINAL_Y
-    ws = torch.zeros(L.workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    tail = torch.zeros(L.TAIL, device="cuda")
-    rows = torch.zeros(B * d.K, 4, device="cuda")
-    logits = torch.zeros(B, d.K, device="cuda")
-    xd, params = dev(x, torch.uint8), dev(flat, torch.float32)
-    rc = L.lib.gmvae_forward(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), None, None, L.ptr(params), L.ptr(tail), L.ptr(rows), None,
-                             None, L.ptr(logits), L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_forward")
-    torch.cuda.synchronize()
-    return tail.cpu().numpy(), rows.cpu().numpy(), logits.cpu().numpy()
+    return hip_util.forward_call(O.MODEL_GMVAE, d, flat, x, 1, row0=row0, flags=_L().OBJ_MARGINAL_Y, seed=seed, step=step,
+                                 logits=True)
 
 
 @pytest.mark.parametrize("name", ["h24x2", "defaults", "tanh"])

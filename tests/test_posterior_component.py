@@ -18,6 +18,7 @@ import pytest
 
 import oracle as O
 import post_comp_ref as R
+import hip_util
 from hip_util import dev, dims_of
 
 pytestmark = pytest.mark.gpu
@@ -55,54 +56,17 @@ def _setup(d, B, seed=0):
 
 def post(d, flat, x, n, chunk, row0=0, seed=SEED, step=STEP):
     """One gmvae_posterior_component call: dict(log_joint [B, K], log_post [B, K], stats [B, 4], tail [8]) as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.posterior_component_workspace_bytes(cd, M) // 4 + 64, dtype=torch.float32, device="cuda")
-    lj = torch.full((B, d.K), float("nan"), device="cuda")
-    lp = torch.full((B, d.K), float("nan"), device="cuda")
-    stats = torch.full((B, 4), float("nan"), device="cuda")
-    tail = torch.full((L.TAIL,), float("nan"), device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    rc = L.lib.gmvae_posterior_component(C.byref(cd), M, L.ptr(xd), L.ptr(params), n, L.ptr(lj), L.ptr(lp), L.ptr(stats),
-                                         L.ptr(tail), L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_posterior_component")
-    torch.cuda.synchronize()
-    return dict(log_joint=lj.cpu().numpy(), log_post=lp.cpu().numpy(), stats=stats.cpu().numpy(), tail=tail.cpu().numpy())
+    return hip_util.chunked_call("posterior_component", M, d, flat, x, n, chunk, row0, seed=seed, step=step)
 
 
 def iw_bound(d, flat, x, n, chunk, row0=0, seed=SEED, step=STEP):
     """gmvae_iw_bound's bound_out [B] at the same dims."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.iw_bound_workspace_bytes(cd, M) // 4 + 64, dtype=torch.float32, device="cuda")
-    bound, tail = torch.zeros(B, device="cuda"), torch.zeros(L.TAIL, device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    L.check(L.lib.gmvae_iw_bound(C.byref(cd), M, L.ptr(xd), L.ptr(params), n, L.ptr(bound), None, L.ptr(tail), L.ptr(ws), seed,
-                                 step, L.current_stream()), "gmvae_iw_bound")
-    torch.cuda.synchronize()
-    return bound.cpu().numpy()
+    return hip_util.chunked_call("iw_bound", M, d, flat, x, n, chunk, row0, seed=seed, step=step, omit=("mean_logw",))["bound"]
 
 
 def forward_rows(d, flat, x, row0=0, seed=SEED, step=STEP):
     """gmvae_forward at S = 1 with in-kernel noise (Philox row row0 + b): rows [B, 4] as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=1), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.workspace_bytes(cd, M) // 4 + 64, dtype=torch.float32, device="cuda")
-    tail, rows = torch.zeros(L.TAIL, device="cuda"), torch.zeros(B, 4, device="cuda")
-    xd, params = dev(x, torch.uint8), dev(flat, torch.float32)
-    L.check(L.lib.gmvae_forward(C.byref(cd), M, L.ptr(xd), None, None, L.ptr(params), L.ptr(tail), L.ptr(rows), None, None, None,
-                                L.ptr(ws), seed, step, L.current_stream()), "gmvae_forward")
-    torch.cuda.synchronize()
-    return rows.cpu().numpy()
+    return hip_util.forward_call(M, d, flat, x, 1, row0=row0, seed=seed, step=step)[1]
 
 
 _REF = {}

@@ -12,7 +12,8 @@ import pytest
 
 import oracle as O
 import ymarg_ref as YM
-from hip_util import dev, dims_of
+import hip_util
+from hip_util import dev, dims_of, lse
 
 pytestmark = pytest.mark.gpu
 
@@ -47,64 +48,19 @@ def _setup(d, B, seed=0):
 
 def post(d, flat, x, n, chunk, row0=0, flags=0, seed=SEED, step=STEP):
     """One gmvae_posterior_y call: dict(log_joint [B, K], log_post [B, K], stats [B, 4], tail [8]) as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0, cd.sched_flags = row0, flags
-    ws = torch.zeros(L.posterior_y_workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    lj = torch.full((B, d.K), float("nan"), device="cuda")
-    lp = torch.full((B, d.K), float("nan"), device="cuda")
-    stats = torch.full((B, 4), float("nan"), device="cuda")
-    tail = torch.full((L.TAIL,), float("nan"), device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    rc = L.lib.gmvae_posterior_y(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(params), n, L.ptr(lj), L.ptr(lp), L.ptr(stats),
-                                 L.ptr(tail), L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_posterior_y")
-    torch.cuda.synchronize()
-    return dict(log_joint=lj.cpu().numpy(), log_post=lp.cpu().numpy(), stats=stats.cpu().numpy(), tail=tail.cpu().numpy())
+    return hip_util.chunked_call("posterior_y", O.MODEL_GMVAE, d, flat, x, n, chunk, row0, flags, seed, step)
 
 
 def enum_bound(d, flat, x, n, chunk, row0=0, seed=SEED, step=STEP):
     """gmvae_iw_bound_enum_y's bound_out [B] at the same dims."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=chunk), B)
-    cd.row0 = row0
-    ws = torch.zeros(L.iw_bound_enum_y_workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    bound, tail = torch.zeros(B, device="cuda"), torch.zeros(L.TAIL, device="cuda")
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    L.check(L.lib.gmvae_iw_bound_enum_y(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(params), n, L.ptr(bound), None,
-                                        L.ptr(tail), L.ptr(ws), seed, step, L.current_stream()), "gmvae_iw_bound_enum_y")
-    torch.cuda.synchronize()
-    return bound.cpu().numpy()
+    return hip_util.chunked_call("iw_bound_enum_y", O.MODEL_GMVAE, d, flat, x, n, chunk, row0, seed=seed, step=step,
+                                 omit=("mean_logw",))["bound"]
 
 
 def forward(d, flat, x, S, flag, row0=0, seed=SEED, step=STEP):
     """gmvae_forward under an objective bit (GMVAE_OBJ_MARGINAL_Y at S = 1, GMVAE_OBJ_MARGINAL_Y_IW at any S) with in-kernel
     noise: (tail [8], rows [B S K, 4], logits [B, K]) as numpy."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=S), B)
-    cd.row0, cd.sched_flags = row0, flag
-    ws = torch.zeros(L.workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    tail = torch.zeros(L.TAIL, device="cuda")
-    rows = torch.zeros(B * S * d.K, 4, device="cuda")
-    logits = torch.zeros(B, d.K, device="cuda")
-    xd, params = dev(x, torch.uint8), dev(flat, torch.float32)
-    rc = L.lib.gmvae_forward(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), None, None, L.ptr(params), L.ptr(tail), L.ptr(rows), None,
-                             None, L.ptr(logits), L.ptr(ws), seed, step, L.current_stream())
-    L.check(rc, "gmvae_forward")
-    torch.cuda.synchronize()
-    return tail.cpu().numpy(), rows.cpu().numpy(), logits.cpu().numpy()
-
-
-def lse(v, axis=None):
-    v = np.asarray(v, np.float64)
-    m = v.max(axis=axis, keepdims=True)
-    return np.squeeze(m + np.log(np.exp(v - m).sum(axis=axis, keepdims=True)), axis=axis)
+    return hip_util.forward_call(O.MODEL_GMVAE, d, flat, x, S, row0=row0, flags=flag, seed=seed, step=step, logits=True)
 
 
 def log_softmax(v):
