@@ -280,8 +280,15 @@ static int fwd_splits(int D) {
 // x rows, its LDS budget, and (VAE_GMP) one prior-gradient partial per workgroup
 // (the *_shape predicates read the dims only: carve() sizes the workspace with them, so that its layout never depends on an
 //  environment switch; the *_ok forms add the switches and choose the schedule)
+// image tasks of the first launch's auxiliary workgroups (plan_images): the small-weight image's tensors + two per decoder chunk
+// of kCW columns.  Aux carries kMaxImgTasks of them as kernel arguments: D <= 1280 (GMVAE), 1536 (VAE_GMP), 1664 (VAE)
+static int mega_img_tasks(int model, int D) {
+  const int small = model == GMVAE_MODEL_GMVAE ? 11 : (model == GMVAE_MODEL_VAE_GMP ? 8 : 5);
+  return small + 2 * ((D + kCW - 1) / kCW);
+}
 static bool mega_shape(const GmvaeDims& d, int model) {
   if (marginal_y(d)) return false;             // (the enumerated objective runs the general schedule only)
+  if (mega_img_tasks(model, d.D) > kMaxImgTasks) return false;
   if (d.n_hidden != 1 || d.S != 1 || d.D % 16 || d.hidden_act != GMVAE_ACT_RELU) return false;
   if (d.gen_bias_vec) return false;            // the vector bias_init is applied by the grouped GEMM's epilogue (Problem::bias2)
   const int H = d.hidden[0];
@@ -959,13 +966,17 @@ static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS
   const int K = d.K, Lz = d.L, D = d.D, H = d.hidden[0];
   const NetL &E = gm ? L.ency : L.enc, &G = L.encg, &Dn = L.dec;
   float* im = w.img_m;
+  if (mega_img_tasks(model, D) > kMaxImgTasks) { pl.map_ok = false; return; }      // (mega_shape refuses such a D: never past task[])
   auto add_map = [&](long long begin, long long n, int cols, int kind, int base, int ld, int which, int chunk = -1) {
     if (pl.nmap >= kMaxImgMap || (unsigned long long)n * (unsigned long long)cols >= (1ull << 32)) { pl.map_ok = false; return; }
     ImgMap& m = pl.map[pl.nmap++];
     m.begin = (int)begin; m.end = (int)(begin + n); m.cols = cols; m.kind = kind; m.base = base; m.ld = ld;
     m.cw = kCW; m.chunk = chunk < 0 ? ml.chunk : chunk; m.magic = (unsigned)((1ull << 32) / (unsigned)cols) + 1u; m.which = which;
   };
+  // (every task() / chunk task below counts in mega_img_tasks, which mega_shape gates on; the bounds here keep the list inside
+  //  task[] even if the two ever disagree: the plan is then unusable (map_ok false) instead of written past its end)
   auto task = [&](float* dst, int ld, const float* src, int rows, int cols) {      // dense source rows
+    if (pl.nt >= kMaxImgTasks) { pl.map_ok = false; return; }
     ImgTask& t = pl.task[pl.nt++];
     t.dst = dst; t.ld = ld; t.src = src; t.rows = rows; t.cols = cols; t.src_ld = cols; t.trans = 0;
     add_map(src - P, (long long)rows * cols, cols, 0, (int)(dst - im), ld, 0);
@@ -993,6 +1004,7 @@ static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS
   task(im + ml.b_d0, H, P + Dn.b[0], 1, H);
   for (int c = 0; c < ml.nch; ++c) {             // decoder chunk images: [H rows of Wd1 | bias row]
     const int nc = (D - c * kCW) < kCW ? (D - c * kCW) : kCW;
+    if (pl.nt + 2 > kMaxImgTasks) { pl.map_ok = false; break; }
     ImgTask& t0 = pl.task[pl.nt++];
     t0.dst = w.dimg + (uint64_t)c * ml.chunk; t0.ld = ml.ldc; t0.src = P + Dn.w[1] + c * kCW; t0.rows = H; t0.cols = nc;
     t0.src_ld = D; t0.trans = 0;
