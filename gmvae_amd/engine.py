@@ -553,15 +553,16 @@ class Engine:
             self.step_dev.fill_(self.global_step)   # one source of truth: graphs replayed later start from here
 
     def train_step(self, x, eps=None, u=None, lr: float = 1e-3, all_reduce: bool = True,
-                   row0: Optional[int] = None, y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One full reference step: fwd + bwd (+ RCCL all-reduce) + Adam.
+                   row0: Optional[int] = None, y_observed: Optional[torch.Tensor] = None,
+                   beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8) -> torch.Tensor:
+        """One full reference step: fwd + bwd (+ RCCL all-reduce) + Adam (beta1, beta2, epsilon: tf.train.AdamOptimizer's).
         Returns the [TAIL] loss sums (device tensor; no host sync)."""
         import torch.distributed as dist
         self.step(x, eps, u, row0=row0, y_observed=y_observed)
         if all_reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             from . import parallel
             parallel.all_reduce_flat(self.grads)     # ONE collective: grads + loss sums + count
-        self.adam(lr)
+        self.adam(lr, beta1, beta2, epsilon)
         return self.grads[self.P:]
 
     # -------------------------------------------------- data parallel over RCCL inside the C library
@@ -612,7 +613,8 @@ class Engine:
         self.rccl_nranks = n.value
         return comm
 
-    def dp_step(self, x, lr: float = 1e-3, y_observed: Optional[torch.Tensor] = None):
+    def dp_step(self, x, lr: float = 1e-3, y_observed: Optional[torch.Tensor] = None,
+                beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
         """gmvae_dp_step: one C call enqueues step + RCCL all-reduce + Adam on the current stream."""
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
@@ -621,20 +623,22 @@ class Engine:
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
-                                 L.ptr(self.grads), L.ptr(ws), self.noise_seed, L.ptr(self.step_dev), lr, 0.9, 0.999,
-                                 1e-8, self._comm, L.current_stream())
+                                 L.ptr(self.grads), L.ptr(ws), self.noise_seed, L.ptr(self.step_dev), lr, beta1, beta2,
+                                 epsilon, self._comm, L.current_stream())
         L.check(rc, "gmvae_dp_step")
         self.global_step += 1
         return self.grads[self.P:]
 
     # -------------------------------------------------- hipGraph fast path
-    def capture_train_step(self, B: int, lr: float = 1e-3, all_reduce: bool = False, n_steps: int = 1):
+    def capture_train_step(self, B: int, lr: float = 1e-3, all_reduce: bool = False, n_steps: int = 1,
+                           beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
         """One hipGraph for noise + fwd + bwd + Adam at batch size B, captured and owned by the HIP
         library (gmvae_train_graph_*).  Returns (static_x, replay).  With n_steps > 1 the graph holds
         that many consecutive steps and static_x is [n_steps, B, D] (the next n_steps batches): one
         launch per n_steps steps hides the idle time between graph launches.  With all_reduce (data
         parallel) the RCCL all-reduce is captured too when the library owns the communicator
         (enable_rccl); otherwise the step is two eager halves around torch.distributed.all_reduce.
+        beta1, beta2, epsilon: tf.train.AdamOptimizer's, baked into the graph like lr (and part of the key it is cached under).
         replay.tail_log [n_steps, TAIL]: the per-step tails of the last launch.  replay.y_observed [n_steps, B] (semi-supervised)
         and replay.obj_weights [n_steps, 4] (weighted objective; pre-filled with the engine's current weights) are VIEWS of
         the workspace's label sets / weight rows, which step i of the graph reads; the caller fills them before replay().
@@ -649,7 +653,8 @@ class Engine:
             raise ValueError(f"a semi-supervised train graph holds at most {L.LABEL_SLOTS} steps (one label set per step), got {n_steps}")
         if self.weighted_objective and n_steps > L.LABEL_SLOTS:
             raise ValueError(f"a train graph of a weighted objective holds at most {L.LABEL_SLOTS} steps (one weight row per step), got {n_steps}")
-        key = (B, lr, do_ar, n_steps)
+        adam_hp = (float(beta1), float(beta2), float(epsilon))
+        key = (B, lr, do_ar, n_steps) + adam_hp
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)   # eager steps may have run since the capture
             return self._graphs[key][:2]
@@ -692,7 +697,7 @@ class Engine:
             handle = C.c_void_p()
             rc = L.lib.gmvae_dp_graph_create(C.byref(d), self.model, L.ptr(static_x), n_steps, L.ptr(self.params), L.ptr(self.m),
                                              L.ptr(self.v), L.ptr(self.grads), L.ptr(ws), self.noise_seed,
-                                             L.ptr(self.step_dev), lr, 0.9, 0.999, 1e-8, self._comm, L.ptr(tail_log),
+                                             L.ptr(self.step_dev), lr, *adam_hp, self._comm, L.ptr(tail_log),
                                              C.byref(handle))
             if self._agree(rc == 0):                # all ranks jointly: the graph, or (below) the eager C-side step
                 launch = L.lib.gmvae_train_graph_launch
@@ -718,7 +723,7 @@ class Engine:
                 ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
 
                 def body(i):
-                    self.dp_step(batches[i], lr, y_observed=None if ys is None else ys[i])
+                    self.dp_step(batches[i], lr, None if ys is None else ys[i], *adam_hp)
                     tail_log[i].copy_(self.grads[self.P:])
                 eager_rows(body)
                 if ys is not None:
@@ -737,7 +742,7 @@ class Engine:
                 def body(i):
                     self.step(batches[i], use_step_dev=True, y_observed=None if ys is None else ys[i])
                     parallel.all_reduce_flat(self.grads)
-                    self.adam(lr, use_step_dev=True)
+                    self.adam(lr, *adam_hp, use_step_dev=True)
                     self.global_step += 1
                     tail_log[i].copy_(self.grads[self.P:])
                 eager_rows(body)
@@ -750,7 +755,7 @@ class Engine:
         handle = C.c_void_p()
         rc = L.lib.gmvae_train_graph_create(C.byref(d), self.model, L.ptr(static_x), n_steps, L.ptr(self.params), L.ptr(self.m),
                                             L.ptr(self.v), L.ptr(self.grads), L.ptr(ws), self.noise_seed,
-                                            L.ptr(self.step_dev), lr, 0.9, 0.999, 1e-8, L.ptr(tail_log), C.byref(handle))
+                                            L.ptr(self.step_dev), lr, *adam_hp, L.ptr(tail_log), C.byref(handle))
         L.check(rc, "gmvae_train_graph_create")
         launch = L.lib.gmvae_train_graph_launch
         gen = self._graph_gen
@@ -768,7 +773,8 @@ class Engine:
 
     BINARIZE_SEED_XOR = 0x62696E6172697A65      # the pipeline graph keys its binarisation uniforms by noise_seed ^ this
 
-    def capture_train_pipeline(self, dataset, B: int, lr: float = 1e-3, n_steps: int = 16):
+    def capture_train_pipeline(self, dataset, B: int, lr: float = 1e-3, n_steps: int = 16,
+                               beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
         """A train graph that starts from the RAW pixels (gmvae_train_graph_create_pipeline): each of its n_steps
         steps first binarises its own batch on the device (scripts/runners.py:44-47), rows taken from `dataset`
         (gmvae_amd.data.DeviceDataset: resident uint8 pixels + an epoch permutation on the device).  Returns
@@ -780,7 +786,7 @@ class Engine:
             raise ValueError("capture_train_pipeline has no per-step weight rows: an engine with weighted_objective=True trains "
                              "through capture_train_step (replay.obj_weights)")
         n_steps = int(n_steps)
-        key = ("pipeline", id(dataset), B, lr, n_steps)
+        key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon))
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)
             return self._graphs[key][1]
@@ -796,7 +802,7 @@ class Engine:
         rc = L.lib.gmvae_train_graph_create_pipeline(C.byref(d), self.model, L.ptr(dataset.pixels), dataset.N, L.ptr(idx),
                                                      L.ptr(xs), n_steps, L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
                                                      L.ptr(self.grads), L.ptr(ws), self.noise_seed, L.ptr(self.step_dev), lr,
-                                                     0.9, 0.999, 1e-8, L.ptr(tail_log), C.byref(handle))
+                                                     beta1, beta2, epsilon, L.ptr(tail_log), C.byref(handle))
         L.check(rc, "gmvae_train_graph_create_pipeline")
         launch = L.lib.gmvae_train_graph_launch
         gen = self._graph_gen
