@@ -113,15 +113,21 @@ class RelaxedOneHotCategorical:
     """tfd.RelaxedOneHotCategorical(temperature, logits) subset; ``.distribution.logits``
     is what scripts/gmvae.py:263,271 reads."""
 
-    def __init__(self, temperature, logits, name="RelaxedOneHotCategorical"):
+    def __init__(self, temperature, logits, name="RelaxedOneHotCategorical", straight_through=False):
         self.temperature, self.logits, self.name = temperature, logits, name
+        self.straight_through = bool(straight_through)
         self.distribution = _Categorical(logits)
 
     def sample(self, seed=None, uniform=None):
+        """softmax((logits + g) / temperature); with straight_through the one-hot row at the argmax of logits + g (lowest
+        index on ties) -- what a step under GMVAE_Y_STRAIGHT_THROUGH consumes (include/gmvae_hip.h)."""
         if uniform is None:
             uniform = torch.rand(self.logits.shape, device=self.logits.device,
                                  generator=_gen(seed, self.logits.device)).clamp_min(TINY)
         g = -torch.log(-torch.log(uniform))
+        if self.straight_through:
+            k = (self.logits + g).argmax(-1)        # (the first maximal index on ties)
+            return F.one_hot(k, self.logits.shape[-1]).to(self.logits.dtype)
         return torch.softmax((self.logits + g) / self.temperature, -1)
 
 
@@ -236,7 +242,12 @@ class ConditionalCategorical(_Conditional):
         return self._mlp(tensor_list)
 
     def __call__(self, *args, **kwargs):
-        return RelaxedOneHotCategorical(self._temperature, logits=self.condition(args, **kwargs), name=self._name)
+        # bound to an Engine: its CURRENT temperature (Engine.set_temperature) and its y estimator, so that transform and
+        # reconstruct_images draw y as the training step does
+        e = self._engine
+        t = self._temperature if e is None else e.temperature
+        st = e is not None and e.y_estimator == "straight_through"
+        return RelaxedOneHotCategorical(t, logits=self.condition(args, **kwargs), name=self._name, straight_through=st)
 
 
 def _targets_guard(loss, images, targets):

@@ -37,6 +37,7 @@
 #include "ymarg.hpp"
 #include "semisup.hpp"
 #include "wobj.hpp"
+#include "ytemp.hpp"
 
 using namespace gmvae;
 
@@ -71,6 +72,12 @@ static bool sup_labels(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_L
 // GMVAE_OBJ_WEIGHTS: the KL terms weighted per step from device memory (wobj.hpp: its kernels in row_terms' / ymarg_rows' /
 // y_head_bwd's place, wobj_tail behind loss_tail) -- the general schedule only, S == 1
 static bool obj_weights(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_WEIGHTS) != 0; }
+// GMVAE_Y_TEMP_DEV / GMVAE_Y_STRAIGHT_THROUGH: the Gumbel-softmax temperature read from device memory per step / the one-hot y
+// with the relaxed sample's Jacobian (ytemp.hpp: its kernels in y_head_fwd's / y_head_bwd's / y_head_bwd_w's place) -- the
+// general schedule only
+static bool y_temp_dev(const GmvaeDims& d) { return (d.sched_flags & GMVAE_Y_TEMP_DEV) != 0; }
+static bool y_straight(const GmvaeDims& d) { return (d.sched_flags & GMVAE_Y_STRAIGHT_THROUGH) != 0; }
+static bool y_head_bits(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH)) != 0; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -190,10 +197,18 @@ static int check_weight_dims(const GmvaeDims* d) {
   if (d->S != 1) return GMVAE_E_DIMS;
   return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS)) ? GMVAE_E_DIMS : 0;
 }
+// ... and GMVAE_Y_TEMP_DEV / GMVAE_Y_STRAIGHT_THROUGH for everything but the GMVAE's Gumbel draw: the VAE family has no y, the
+// y-summed-out objectives draw none (so neither do labels or DReG, which need them)  (check_ytemp_dims: gmvae_forward's check too)
+static int check_ytemp_dims(const GmvaeDims* d, int model) {
+  if (!y_head_bits(*d)) return 0;
+  if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
+  return (marginal_y(*d) || sup_labels(*d) || dreg_grad(*d)) ? GMVAE_E_DIMS : 0;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
   if (int e = check_label_dims(d, model)) return e;
   if (int e = check_weight_dims(d)) return e;
+  if (int e = check_ytemp_dims(d, model)) return e;
   if (dreg_grad(*d) && model == GMVAE_MODEL_GMVAE && !marginal_y(*d)) return GMVAE_E_DIMS;
   return 0;
 }
@@ -233,6 +248,9 @@ struct WS {
   // GMVAE_OBJ_WEIGHTS: the caller's weight rows [GMVAE_LABEL_SLOTS][4] = (beta_z, beta_y, lambda, 0) (read only), beta_z rw [R]
   // for the consumers of rw that differentiate the KL part, and a_b [B] (1: the y term's floor is inactive)
   float *obj_weights, *rwk, *y_floor;
+  // GMVAE_Y_TEMP_DEV: the caller's temperatures [GMVAE_LABEL_SLOTS] (read only); GMVAE_Y_STRAIGHT_THROUGH: the relaxed sample
+  // [R][K] behind the one-hot y the step consumes
+  float *y_temperature, *y_soft;
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -297,7 +315,7 @@ static bool mega_shape(const GmvaeDims& d, int model) {
   return (size_t)mega_lay(H, d.L, d.K, d.D, model).total * 4 <= 160 * 1024;
 }
 static bool mega_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d)) return false;            // (GMVAE_OBJ_WEIGHTS: the general schedule only, as GMVAE_GRAD_DREG below)
+  if (obj_weights(d) || y_head_bits(d)) return false;      // (GMVAE_OBJ_WEIGHTS, GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH: the general schedule only, as GMVAE_GRAD_DREG below)
   if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
                                                //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
   const char* e = getenv("GMVAE_NO_MEGA");
@@ -347,7 +365,7 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
 static bool skinny_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d)) return false;
   const char* e = getenv("GMVAE_NO_SKINNY");
   if (e && atoi(e)) return false;
   int maxb = kSkMaxB;
@@ -362,7 +380,7 @@ static bool fused_shape(const GmvaeDims& d, int model) {
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
 }
 static bool fused_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d)) return false;
   const char* e = getenv("GMVAE_NO_FUSED");
   if (e && atoi(e)) return false;
   return fused_shape(d, model);
@@ -377,7 +395,7 @@ static bool evalf_shape(const GmvaeDims& d, int model) {
   return d.L == 64 && d.K == 10;                                       // VAE_GMP: configs[1]
 }
 static bool evalf_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d)) return false;              // (gmvae_forward honours GMVAE_OBJ_WEIGHTS: the general schedule's forward)
+  if (obj_weights(d) || y_head_bits(d)) return false;      // (gmvae_forward honours GMVAE_OBJ_WEIGHTS and the y head's bits: the general schedule's forward)
   const char* e = getenv("GMVAE_NO_EVALF");
   if (e && atoi(e)) return false;
   if (!evalf_shape(d, model)) return false;
@@ -571,6 +589,8 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.y_floor = take(B);
     if (!marginal_y(d)) w.pb = take(B * 4);       // (S == 1 without y summed out: loss_tail's per-example partials)
   }
+  if (y_temp_dev(d)) w.y_temperature = take(GMVAE_LABEL_SLOTS);      // (behind everything, as above: one float per slot)
+  if (y_straight(d)) w.y_soft = take(R * K);
   w.bytes = off;
 }
 
@@ -944,6 +964,7 @@ struct StepArgs {
   float* tail_log = nullptr;   // train graph: this step's slot of the per-step tail log (may be null)
   int label_slot = 0;          // GMVAE_OBJ_LABELS: which of the workspace's label sets the step reads (step i of a train graph: i)
   int weights_slot = 0;        // GMVAE_OBJ_WEIGHTS: which row of the workspace's "obj_weights" the step reads (likewise)
+  int temp_slot = 0;           // GMVAE_Y_TEMP_DEV: which float of the workspace's "y_temperature" the step reads (likewise)
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -2077,6 +2098,11 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (!a.backward && evalf_ok(d, model) && w.ev_img) return run_eval_fused(cx, a, L, w);
   if (fused_ok(d, model) && !a.z_out && !a.y_out && !a.logits_out)
     return run_step_fused(cx, a, L, w, eps, u, ge, gu);
+  // GMVAE_Y_TEMP_DEV: this step's temperature slot (null: T by value); GMVAE_Y_STRAIGHT_THROUGH: w.y_soft is carved
+  if (y_head_bits(d) && (!gm || marg || (y_temp_dev(d) && (!w.y_temperature || a.temp_slot < 0 || a.temp_slot >= GMVAE_LABEL_SLOTS)) ||
+                         (y_straight(d) && !w.y_soft)))
+    return GMVAE_E_DIMS;
+  const float* const ytau = y_temp_dev(d) ? w.y_temperature + a.temp_slot : nullptr;
   // (general schedule: the Philox fill rides as auxiliary workgroups of the first GEMM launch below)
   const bool noise_aux = ge || gu;
   const bool relu_act = d.hidden_act == GMVAE_ACT_RELU;      // (tanh / sigmoid / ELU: the grouped GEMM's epilogues only)
@@ -2202,9 +2228,15 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
                          ((enum_chunk || marg_iwo) && !a.y_out) ? (float*)nullptr : w.y, B, K, S);
       rowk(cx, "ymarg_y_layers");
     } else {
+    if (y_head_bits(d)) {       // T from the step's slot and / or the one-hot y with the relaxed sample kept (ytemp.hpp)
+      hipLaunchKernelGGL(y_head_fwd_t, dim3(grid_for(R, 4)), dim3(256), 0, st, w.logits, u, ytau, w.y, w.y_soft, w.nent, R, S, K,
+                         1.f / d.temperature);
+      rowk(cx, "y_head_fwd_t");
+    } else {
     hipLaunchKernelGGL(y_head_fwd, dim3(grid_for(R, 4)), dim3(256), 0, st, w.logits, u, w.y, w.nent, R, S, K,
                        1.f / d.temperature);
     rowk(cx, "y_head_fwd");
+    }
     if (rws_on && K == 64 && G.dim[1] % 64 == 0 && (2 * Lz) % 64 == 0 && rws_fits((G.dim[1] + 2 * Lz) / 64)) {
       RwsArgs ra;
       memset(&ra, 0, sizeof(ra));
@@ -2631,7 +2663,16 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       }
       }
     }
-    if (!marg && wobj) {          // (the entropy term under beta_y a_b)
+    if (!marg && y_head_bits(d)) {      // (ytemp.hpp: T from the slot; under straight-through the relaxed sample's Jacobian)
+      const float* const ysrc = y_straight(d) ? w.y_soft : w.y;
+      if (wobj)
+        hipLaunchKernelGGL(y_head_bwd_t<true>, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, ysrc, w.dy, w.nent, wts,
+                           w.y_floor, ytau, w.dlogits, B, S, K, 1.f / d.temperature);
+      else
+        hipLaunchKernelGGL(y_head_bwd_t<false>, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, ysrc, w.dy, w.nent,
+                           (const float*)nullptr, (const float*)nullptr, ytau, w.dlogits, B, S, K, 1.f / d.temperature);
+      rowk(cx, wobj ? "y_head_bwd_w_t" : "y_head_bwd_t");
+    } else if (!marg && wobj) {          // (the entropy term under beta_y a_b)
       hipLaunchKernelGGL(y_head_bwd_w, dim3(grid_for(B, 1)), dim3(512), 0, st, w.logits, w.y, w.dy, w.nent, wts, w.y_floor,
                          w.dlogits, B, S, K, 1.f / d.temperature);
       rowk(cx, "y_head_bwd_w");
@@ -2703,7 +2744,8 @@ struct IwKindRow {
 constexpr IwKindRow kIwKinds[] = {{-1, false}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_VAE_GMP, false}};
 // bits that mean nothing to an evaluator: no gradient, no labels, no weights, and the operand images are prepared here, once
 // per call.  Masked HERE alone, so the size query and the run carve the workspace from the same dims.
-constexpr unsigned kIwMasked = GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS;
+constexpr unsigned kIwMasked = GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
+                               GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH;      // (the evaluators draw y at dims->temperature, relaxed)
 
 // the kind's dims from the caller's (S = the chunk), or the entry point's error: kIwMasked cleared; the enumerating kinds ignore
 // GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW on entry and carry GMVAE_OBJ_MARGINAL_Y on return, the others refuse both
@@ -3023,7 +3065,7 @@ static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, fl
   a.adam_p = params; a.adam_m = m; a.adam_v = v; a.lr = lr; a.beta1 = b1; a.beta2 = b2; a.epsilon = eps_;
   a.imgs_ready = imgs_ready;
   a.tail_log = tail_log;
-  a.label_slot = a.weights_slot = label_slot;    // (step i of a train graph: label set i, weight row i)
+  a.label_slot = a.weights_slot = a.temp_slot = label_slot;    // (step i of a train graph: label set i, weight row i, temperature i)
   return run_step(cx, a);
 }
 
@@ -3033,6 +3075,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (int e = check_dims(dims, model)) return e;
   if (int e = check_label_dims(dims, model)) return e;
   if (int e = check_weight_dims(dims)) return e;
+  if (int e = check_ytemp_dims(dims, model)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
@@ -3623,7 +3666,8 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
   // GMVAE_OBJ_LABELS: step i reads label set i of the workspace; the pipeline graph gathers its batches by index and has no
   // label gather
   // (GMVAE_OBJ_WEIGHTS likewise: step i reads weight row i)
-  if ((sup_labels(*dims) || obj_weights(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  // (GMVAE_Y_TEMP_DEV likewise: step i reads temperature i)
+  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3735,8 +3779,9 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
-           sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+  snprintf(out48, 48, "%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+           sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
+           y_straight(d) ? "+st" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3772,7 +3817,8 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"stamps", reinterpret_cast<float*>(w.stamps)}, {"gstamps", reinterpret_cast<float*>(w.gstamps)},
       {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)},
       {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight},
-      {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor}};
+      {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor},
+      {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;
@@ -3896,7 +3942,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   a.dp_images = scatter;
   a.imgs_ready = scatter && imgs_ready;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
-  a.label_slot = a.weights_slot = label_slot;
+  a.label_slot = a.weights_slot = a.temp_slot = label_slot;
   cx.prof = prof;
   int rc = run_step(cx, a);
   if (rc) return rc;
@@ -4043,7 +4089,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
-  if ((sup_labels(*dims) || obj_weights(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row i)
+  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row / temperature i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

@@ -69,13 +69,29 @@ def check_weighted_objective(model, y_inference, n_samples, grad_estimator, semi
         raise ValueError("weighted_objective=True is not available with semi_supervised=True")
 
 
+def check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator):
+    """The argument check of Engine(temperature=, temperature_on_device=, y_estimator=) (no device needed)."""
+    if y_estimator not in L.Y_ESTIMATORS:
+        raise ValueError(f"y_estimator must be one of {L.Y_ESTIMATORS}, got {y_estimator!r}")
+    t = float(temperature)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    if not temperature_on_device and y_estimator == "relaxed":
+        return
+    what = "temperature_on_device=True" if temperature_on_device else f"y_estimator={y_estimator!r}"
+    if L.MODEL_IDS.get(model) != L.MODEL_GMVAE:
+        raise ValueError(f"{what} belongs to the GMVAE's Gumbel-softmax draw of y: it needs the GMVAE model")
+    if y_inference != "gumbel":
+        raise ValueError(f"{what} needs y_inference='gumbel': y_inference={y_inference!r} sums y out and draws none")
+
+
 class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
                  temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
                  y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
-                 y_free_nats: float = 0.0):
+                 y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed"):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -96,7 +112,15 @@ class Engine:
         from device memory -- loss = nll + kl_weight * kl_z + y_weight * max(nent, y_free_nats - ln K) (the y term: GMVAE only;
         y_free_nats nats of free bits on KL(q(y|x) || uniform), 0 = off).  set_objective_weights changes them between steps
         without a host sync; a captured train graph reads one row of replay.obj_weights per step (a KL warm-up).  Every step
-        takes the general schedule.  Parameters and checkpoints are the same with and without it."""
+        takes the general schedule.  Parameters and checkpoints are the same with and without it.
+        temperature_on_device (GMVAE, y_inference "gumbel"; include/gmvae_hip.h GMVAE_Y_TEMP_DEV): every step reads the
+        Gumbel-softmax temperature from device memory.  set_temperature changes it between steps without a host sync; a
+        captured train graph reads one value of replay.y_temperature per step (annealing).  General schedule.
+        y_estimator (same domain; GMVAE_Y_STRAIGHT_THROUGH): "relaxed" -- y = softmax((logits + g) / T), the default -- or
+        "straight_through": the step consumes the one-hot argmax of logits + g and differentiates through the relaxed
+        sample, so that training feeds prior_gmm and encoder_gmm the one-hot y that generation and the enumerating
+        evaluators (iw_bound_enum_y, posterior_y) feed them.  General schedule.  Parameters and checkpoints are the same."""
+        check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator)
         check_semi_supervised(model, y_inference, semi_supervised, sup_weight)
         check_weighted_objective(model, y_inference, n_samples, grad_estimator, semi_supervised, weighted_objective,
                                  kl_weight, y_weight, y_free_nats)
@@ -143,8 +167,10 @@ class Engine:
         self.sup_weight = float(sup_weight)
         self.weighted_objective = bool(weighted_objective)
         self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
+        self.temperature_on_device = bool(temperature_on_device)
+        self.y_estimator = y_estimator
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
-        self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=temperature,
+        self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
         self.safe_schedule = False              # use_safe_schedule(): the schedules without mutual waits (per engine)
         d0 = self.dims(1)
@@ -170,7 +196,16 @@ class Engine:
         if self.weighted_objective:
             self._objw_dev = torch.zeros(4, dtype=torch.float32, device=self.device)
             self.set_objective_weights(*self.obj_weights)
+        # temperature on the device: the current T; every eager entry copies it into slot 0 of its workspace's temperatures
+        self._tau_dev = None
+        if self.temperature_on_device:
+            self._tau_dev = torch.full((1,), float(temperature), dtype=torch.float32, device=self.device)
         self.init_parameters(random_seed)
+
+    @property
+    def temperature(self) -> float:
+        """The Gumbel-softmax temperature the next eager calls use (set_temperature)."""
+        return self.hp["temperature"]
 
     # ------------------------------------------------------------ parameters
     def dims(self, B: int, S: Optional[int] = None, row0: Optional[int] = None, extra_flags: int = 0):
@@ -178,9 +213,10 @@ class Engine:
         S = self.S if S is None else S
         # (the weighted objective is the one-sample bound's: a forward at another number of samples reports the plain bound)
         wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
+        yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
-                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | extra_flags, **self.hp)
+                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | extra_flags, **self.hp)
 
     def _obj_flags(self):
         obj = L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
@@ -298,6 +334,9 @@ class Engine:
             del self._ws[key]
         if key not in self._ws:
             self._ws[key] = torch.zeros(n, dtype=torch.float32, device=self.device)
+            if self.temperature_on_device:
+                # the library only reads the region, and zeros would mean T = 0
+                self._temp_slots(d, self._ws[key]).fill_(self.hp["temperature"])
             if self.semi_supervised:
                 # the library only reads these two regions, and zeros would mean "component 0 observed, weight 0"
                 self._label_slots(d, self._ws[key]).fill_(-1)
@@ -325,6 +364,29 @@ class Engine:
         self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
         for i, v in enumerate(self.obj_weights):
             self._objw_dev[i:i + 1].fill_(v)
+
+    def _temp_slots(self, d, ws) -> torch.Tensor:
+        """View [LABEL_SLOTS] of the workspace's temperatures."""
+        off = L.workspace_offset(d, self.model, "y_temperature") // 4
+        return ws[off:off + L.LABEL_SLOTS]
+
+    def _set_temp(self, d, ws):
+        """Slot 0 of the workspace's temperatures <- the engine's current temperature (device-side copy, no host sync)."""
+        if self.temperature_on_device and d.sched_flags & L.Y_TEMP_DEV:
+            self._temp_slots(d, ws)[0:1].copy_(self._tau_dev)
+
+    def set_temperature(self, t: float):
+        """The Gumbel-softmax temperature of the next eager calls (step / loss / forward / train_step / dp_step, the
+        evaluators, ConditionalCategorical.sample).  With temperature_on_device: a device-side write, no host sync, and a
+        captured train graph keeps reading its own values (replay.y_temperature).  Without: the value travels in the dims,
+        and the captured graphs, which baked the old one, are dropped."""
+        check_y_head(self.model_name, self.y_inference, t, self.temperature_on_device, self.y_estimator)
+        changed = float(t) != self.hp["temperature"]
+        self.hp["temperature"] = float(t)
+        if self.temperature_on_device:
+            self._tau_dev.fill_(float(t))
+        elif changed:
+            self.drop_graphs(clear_handoff_errors=False)
 
     def _label_slots(self, d, ws) -> torch.Tensor:
         """int32 view [LABEL_SLOTS, B] of the workspace's label sets (each slot starts 16-byte aligned)."""
@@ -387,6 +449,7 @@ class Engine:
         d, ws = self._workspace(B, row0=row0)
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
+        self._set_temp(d, ws)
         eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
         u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
@@ -410,6 +473,7 @@ class Engine:
         d, ws = self._workspace(B, S)
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
+        self._set_temp(d, ws)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
@@ -620,6 +684,7 @@ class Engine:
         d, ws = self._workspace(x.shape[0])
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
+        self._set_temp(d, ws)
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
@@ -644,7 +709,9 @@ class Engine:
         the workspace's label sets / weight rows, which step i of the graph reads; the caller fills them before replay().
         Row 0 of both is also what every eager entry (step / loss / forward / train_step / dp_step) on the same batch size
         writes before it runs -- the engine's current weights, its y_observed -- so after any eager call row 0 holds that
-        call's values until the caller refills it: fill the rows before EVERY replay (run_train does)."""
+        call's values until the caller refills it: fill the rows before EVERY replay (run_train does).
+        replay.y_temperature [n_steps] (temperature_on_device; pre-filled with the engine's current temperature) likewise:
+        a view of the workspace's temperatures, step i reads value i, slot 0 is also every eager entry's."""
         import torch.distributed as dist
         do_ar = all_reduce and ((dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
                                 or getattr(self, "_comm", None) is not None)
@@ -653,6 +720,8 @@ class Engine:
             raise ValueError(f"a semi-supervised train graph holds at most {L.LABEL_SLOTS} steps (one label set per step), got {n_steps}")
         if self.weighted_objective and n_steps > L.LABEL_SLOTS:
             raise ValueError(f"a train graph of a weighted objective holds at most {L.LABEL_SLOTS} steps (one weight row per step), got {n_steps}")
+        if self.temperature_on_device and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph with the temperature on the device holds at most {L.LABEL_SLOTS} steps (one temperature per step), got {n_steps}")
         adam_hp = (float(beta1), float(beta2), float(epsilon))
         key = (B, lr, do_ar, n_steps) + adam_hp
         if key in self._graphs:
@@ -676,19 +745,29 @@ class Engine:
             obj_w = self._weight_slots(d, ws)[:n_steps]
             obj_w.copy_(self._objw_dev.expand(n_steps, 4))
 
+        # temperature on the device: step i reads temperature i; the caller fills replay.y_temperature [n_steps]
+        y_temp = None
+        if self.temperature_on_device:
+            y_temp = self._temp_slots(d, ws)[:n_steps]
+            y_temp.copy_(self._tau_dev.expand(n_steps))
+
         def eager_rows(body):
-            """The graph's steps one by one (no graph could be captured): step i's weight row passes through the engine's
-            current weights, which every eager entry copies into slot 0."""
-            if obj_w is None:
-                for i in range(n_steps):
-                    body(i)
-                return
-            rows, cur = obj_w.clone(), self._objw_dev.clone()
+            """The graph's steps one by one (no graph could be captured): step i's weight row and temperature pass through
+            the engine's current ones, which every eager entry copies into slot 0."""
+            rows = None if obj_w is None else (obj_w.clone(), self._objw_dev.clone())
+            taus = None if y_temp is None else (y_temp.clone(), self._tau_dev.clone())
             for i in range(n_steps):
-                self._objw_dev.copy_(rows[i])
+                if rows is not None:
+                    self._objw_dev.copy_(rows[0][i])
+                if taus is not None:
+                    self._tau_dev.copy_(taus[0][i:i + 1])
                 body(i)
-            self._objw_dev.copy_(cur)
-            obj_w[0].copy_(rows[0])
+            if rows is not None:
+                self._objw_dev.copy_(rows[1])
+                obj_w[0].copy_(rows[0][0])
+            if taus is not None:
+                self._tau_dev.copy_(taus[1])
+                y_temp[0:1].copy_(taus[0][0:1])
         self.step_dev.fill_(self.global_step)
         # per-step tails of one launch (loss sums + count; all-reduced under data parallelism): replay.tail_log
         tail_log = torch.zeros(n_steps, L.TAIL, dtype=torch.float32, device=self.device)
@@ -710,7 +789,7 @@ class Engine:
                     if rc2:
                         L.check(rc2, "gmvae_train_graph_launch")
                     self.global_step += n_steps
-                replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
+                replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
                 self._graphs[key] = (static_x, replay, handle)
                 return static_x, replay
             if rc == 0:
@@ -728,7 +807,7 @@ class Engine:
                 eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
-            replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
+            replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         if do_ar:
@@ -748,7 +827,7 @@ class Engine:
                 eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
-            replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
+            replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         torch.cuda.synchronize()
@@ -767,7 +846,7 @@ class Engine:
                 L.check(rc, "gmvae_train_graph_launch")
             self.global_step += n_steps
 
-        replay.tail_log, replay.y_observed, replay.obj_weights = tail_log, y_obs, obj_w
+        replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
         self._graphs[key] = (static_x, replay, handle)
         return static_x, replay
 
@@ -785,6 +864,9 @@ class Engine:
         if self.weighted_objective:
             raise ValueError("capture_train_pipeline has no per-step weight rows: an engine with weighted_objective=True trains "
                              "through capture_train_step (replay.obj_weights)")
+        if self.temperature_on_device:
+            raise ValueError("capture_train_pipeline has no per-step temperatures: an engine with temperature_on_device=True "
+                             "trains through capture_train_step (replay.y_temperature)")
         n_steps = int(n_steps)
         key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon))
         if key in self._graphs:

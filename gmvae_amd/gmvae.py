@@ -154,9 +154,10 @@ class TrainableGMVAE(GMVAE):
 def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                  hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
-                 semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0):
+                 semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0,
+                 temperature_on_device=False, y_estimator="relaxed"):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
-    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats: Engine).  y_inference="marginal" trains and
+    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
     importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
     a checkpoint of any loads in the others."""
@@ -167,7 +168,7 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                     gen_bias_init=gen_bias_init, random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
                     y_inference=y_inference, grad_estimator=grad_estimator, semi_supervised=semi_supervised,
                     sup_weight=sup_weight, weighted_objective=weighted_objective, kl_weight=kl_weight, y_weight=y_weight,
-                    y_free_nats=y_free_nats)
+                    y_free_nats=y_free_nats, temperature_on_device=temperature_on_device, y_estimator=y_estimator)
     prior_gmm = base.ConditionalNormal(size=latent_size, hidden_layer_sizes=None,
                                        hidden_activation_fn=hidden_activation_fn, sigma_min=sigma_min,
                                        raw_sigma_bias=raw_sigma_bias, name="prior_gmm").bind(engine, L.NET_PRIOR_GMM)

@@ -65,6 +65,15 @@ def build_parser():
       "whose KL(q(y|x) || p(y)) is below this many nats pays the floor and sends no gradient through it (0 = off)")
     a("--kl_warmup_steps", type=int, default=0, help="train, --n_samples=1: both weights are multiplied by "
       "min(1, (t + 1) / N) during the step with 0-based index t (0 = off)")
+    a("--temperature", type=float, default=1.0, help="gmvae, --y_inference=gumbel: the Gumbel-softmax temperature (tau_0 of "
+      "the annealing schedule)")
+    a("--temperature_min", type=float, default=0.0, help="the schedule's floor tau_min")
+    a("--temperature_anneal_rate", type=float, default=0.0, help="r of tau = max(tau_min, tau_0 exp(-r N floor(t / N))) during "
+      "the step with 0-based index t (Jang et al. 2017)")
+    a("--temperature_anneal_every", type=int, default=0, help="N of the schedule: the temperature changes every N steps "
+      "(0 = no annealing)")
+    a("--y_estimator", default="relaxed", choices=["relaxed", "straight_through"], help="gmvae, --y_inference=gumbel: the "
+      "step consumes the relaxed sample of y, or (straight_through) its one-hot argmax with the relaxed sample's gradient")
     return p
 
 
@@ -111,6 +120,14 @@ def check_args(p, cfg):
             p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps are not available with --grad_estimator=dreg")
         if cfg.labelled_per_class > 0:
             p.error("--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps are not available with --labelled_per_class")
+    if runners.temperature_flags(cfg) or cfg.y_estimator != "relaxed":
+        if cfg.model != "gmvae" or cfg.y_inference != "gumbel":
+            p.error("--temperature, --temperature_min, --temperature_anneal_rate, --temperature_anneal_every and --y_estimator "
+                    "belong to the Gumbel-softmax draw of y: they need --model=gmvae with --y_inference=gumbel")
+    if not cfg.temperature > 0 or cfg.temperature_min < 0 or cfg.temperature_anneal_rate < 0 or cfg.temperature_anneal_every < 0:
+        p.error("--temperature must be > 0; --temperature_min, --temperature_anneal_rate and --temperature_anneal_every >= 0")
+    if cfg.temperature_anneal_rate > 0 and cfg.temperature_anneal_every > 0 and not cfg.temperature_min > 0:
+        p.error("an annealed temperature needs a floor: --temperature_min must be > 0")
     return cfg
 
 

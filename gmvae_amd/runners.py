@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import glob
 import gzip
+import math
 import os
 import time
 from typing import Iterator, Tuple
@@ -96,11 +97,35 @@ def objective_weights_at(config, t: int):
             float(getattr(config, "y_free_nats", 0.0)))
 
 
-def create_model(config, data_dim, weighted=None):
-    """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0.
+def temperature_flags(config) -> bool:
+    """Whether any of --temperature / --temperature_min / --temperature_anneal_rate / --temperature_anneal_every leaves its
+    default: training then creates the engine with the temperature on the device (Engine(temperature_on_device=True))."""
+    return (float(getattr(config, "temperature", 1.0)) != 1.0 or float(getattr(config, "temperature_min", 0.0)) != 0.0 or
+            float(getattr(config, "temperature_anneal_rate", 0.0)) != 0.0 or
+            int(getattr(config, "temperature_anneal_every", 0) or 0) != 0)
+
+
+def temperature_at(config, t: int) -> float:
+    """The Gumbel-softmax temperature of the step with 0-based index t: max(tau_min, tau_0 exp(-r N floor(t / N))) with
+    tau_0 = --temperature, tau_min = --temperature_min, r = --temperature_anneal_rate, N = --temperature_anneal_every (Jang
+    et al. 2017: the temperature is updated every N steps); N <= 0: no annealing, max(tau_min, tau_0).  A pure function of the
+    global step, so a restored checkpoint continues the schedule."""
+    t0, tmin = float(getattr(config, "temperature", 1.0)), float(getattr(config, "temperature_min", 0.0))
+    r, n = float(getattr(config, "temperature_anneal_rate", 0.0)), int(getattr(config, "temperature_anneal_every", 0) or 0)
+    if n <= 0:
+        return max(tmin, t0)
+    return max(tmin, t0 * math.exp(-r * n * (int(t) // n)))
+
+
+def create_model(config, data_dim, weighted=None, temperature_on_device=None):
+    """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5 (and temperature=1.0 unless
+    --temperature says otherwise).
     weighted: create the engine with the weighted objective (None: as the flags say; run_eval passes False, so that its
-    numbers stay comparable)."""
+    numbers stay comparable).  temperature_on_device: likewise for the temperature flags (run_eval passes False: it sets one
+    temperature, which travels in the dims)."""
     wobj = dict(weighted_objective=weighted_flags(config) if weighted is None else bool(weighted))
+    yhead = dict(temperature_on_device=temperature_flags(config) if temperature_on_device is None else bool(temperature_on_device),
+                 y_estimator=getattr(config, "y_estimator", "relaxed"))
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
@@ -109,10 +134,12 @@ def create_model(config, data_dim, weighted=None):
         raise ValueError("--labelled_per_class trains the GMVAE semi-supervised: it needs --model=gmvae")
     if config.model == "gmvae":
         return gmvae.create_gmvae(data_dim, config.latent_size, mixture_components=config.mixture_components,
-                                  fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5, temperature=1.0,
-                                  random_seed=config.random_seed, n_samples=ns,
+                                  fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
+                                  temperature=temperature_at(config, 0), random_seed=config.random_seed, n_samples=ns,
                                   y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge,
-                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj)
+                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj, **yhead)
+    if temperature_flags(config) or yhead["y_estimator"] != "relaxed":
+        raise ValueError("--temperature* and --y_estimator belong to the GMVAE's Gumbel-softmax draw: they need --model=gmvae")
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
@@ -226,7 +253,7 @@ def _verify_launch(eng, snap, batches, g, lr):
     hp.pop("gen_bias_init", None)
     sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0,
                 y_inference=eng.y_inference, grad_estimator=eng.grad_estimator, semi_supervised=eng.semi_supervised,
-                sup_weight=eng.sup_weight, **hp)
+                sup_weight=eng.sup_weight, y_estimator=eng.y_estimator, **hp)
     sh.rank, sh.noise_seed = eng.rank, eng.noise_seed
     with torch.no_grad():
         sh.params.copy_(p0); sh.m.copy_(m0); sh.v.copy_(v0)
@@ -293,8 +320,13 @@ def run_train(config):
     # weighted objective (--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps): the same branch -- the graph's weight
     # rows are filled per launch from the schedule, a pure function of the global step
     wobj = eng.weighted_objective
+    # temperature on the device (--temperature / --temperature_min / --temperature_anneal_rate / --temperature_anneal_every):
+    # the same branch again -- the graph's temperatures are filled per launch from temperature_at
+    ytd = eng.temperature_on_device
     run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else
-                                                 "graph+weights" if wobj else "pipeline-graph")
+                                                 "graph+weights" if wobj else "graph+temp" if ytd else "pipeline-graph")
+    run_train.temperature_log = []                          # temperature on the device: (0-based step index, temperature) of the
+                                                            # LAST launch's steps, as placed in replay.y_temperature
     run_train.weight_log = []                               # weighted objective: (step, tail[5] / tail[4], tail[6] / tail[4]) of the
                                                             # LAST summary block's steps (replaced per block: it does not grow)
     verify_every = int(os.environ.get("GMVAE_VERIFY_EVERY", "0") or 0)      # debug canary: see _verify_launch
@@ -316,9 +348,12 @@ def run_train(config):
                 yo = ds.y_observed[rows.long()] if sup else None
                 if wobj:
                     eng.set_objective_weights(*objective_weights_at(config, eng.global_step))
+                if ytd:
+                    run_train.temperature_log = [(eng.global_step, temperature_at(config, eng.global_step))]
+                    eng.set_temperature(run_train.temperature_log[0][1])
                 logs.append(eng.train_step(x, lr=lr, y_observed=yo).clone().view(1, -1))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1 and not sup and not wobj:
+            elif world == 1 and not sup and not wobj and not ytd:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -342,6 +377,10 @@ def run_train(config):
                     rows_w = torch.tensor([objective_weights_at(config, eng.global_step + i) + (0.0,) for i in range(g)],
                                           dtype=torch.float32)
                     replay.obj_weights.copy_(rows_w, non_blocking=True)
+                if ytd:
+                    run_train.temperature_log = [(eng.global_step + i, temperature_at(config, eng.global_step + i)) for i in range(g)]
+                    replay.y_temperature.copy_(torch.tensor([v for _, v in run_train.temperature_log], dtype=torch.float32),
+                                               non_blocking=True)
                 replay()
                 logs.append(replay.tail_log.clone())
                 last_x = xs[g - 1]
@@ -409,6 +448,8 @@ def run_train(config):
             if wobj:
                 msg += (f"  kl_weight {run_train.weight_log[-1][1]:.4f}  y_weight {run_train.weight_log[-1][2]:.4f}"
                         f"  y_floor_share {(tails[-1, 7] / tails[-1, 4]).item():.4f}")
+            if ytd:                                         # (of the last step taken)
+                msg += f"  temperature {temperature_at(config, eng.global_step - 1):.4f}"
             if sup:                                         # over the summary block's labelled examples (all ranks')
                 blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
                 if blk[1].item() > 0:
@@ -437,11 +478,14 @@ def run_eval(config):
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(select_device(config, local))
     data_dim = int(getattr(config, "data_dim", 784))
-    model = create_model(config, data_dim, weighted=False)     # (the weighting flags are training's: the reported terms stay unweighted)
+    model = create_model(config, data_dim, weighted=False,     # (the weighting flags are training's: the reported terms stay unweighted)
+                         temperature_on_device=False)
     wait_for_checkpoint(_ckpt(config), float(getattr(config, "checkpoint_poll_seconds", 60.0)),
                         getattr(config, "checkpoint_max_wait", None))
     model.load_state_dict(torch.load(_ckpt(config), map_location="cpu"))
     eng = model._engine
+    if config.model == "gmvae" and temperature_flags(config):
+        eng.set_temperature(temperature_at(config, eng.global_step))      # the schedule's value where training stopped
     tot = torch.zeros(5, device=eng.device)
     ref_sum, n_batches, codes, labs = 0.0, 0, [], []
     class_hits = torch.zeros(2, dtype=torch.float64, device=eng.device)      # GMVAE: (argmax q(y|x) == label, examples)

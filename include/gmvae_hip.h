@@ -222,8 +222,43 @@ enum { GMVAE_SCHED_SAFE = 1,
         * Every step with the bit takes the general schedule; gmvae_step_schedule appends "+weights" behind the objective:
         *   <schedule> [+marginal | +marginal_iw] [+labels] [+weights] [+dreg] [+planes]
         * ("general+weights", "general+marginal+weights").  No atomics: eager and captured steps give the same bits. */
-       GMVAE_OBJ_WEIGHTS = 64 };
-#define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) a workspace holds: the most steps of one train graph */
+       GMVAE_OBJ_WEIGHTS = 64,
+       /* Gumbel-softmax temperature from DEVICE MEMORY (GMVAE with the Gumbel draw only, any S >= 1): the step ignores
+        * dims->temperature and reads T of y = softmax((logits + g) / T) (scripts/gmvae.py:238-240) from the workspace, so that
+        * the steps of one captured graph can anneal it (Jang et al. 2017, Maddison et al. 2017).  The workspace grows BEHIND
+        * every other buffer by one region rounded up to 256 bytes:
+        *   "y_temperature"  float [GMVAE_LABEL_SLOTS]: one temperature per slot
+        * (gmvae_workspace_offset answers for the name).  The CALLER writes it; the library only reads it.  A zeroed workspace
+        * means T = 0 (1 / T = inf: NaN everywhere): a caller fills the slots before the first step (gmvae_amd.Engine does).
+        * The kernel forms 1.f / T as the host does without the bit: a slot that holds the same float as dims->temperature gives
+        * the step without the bit on the general schedule, bit for bit.
+        * Who reads which slot: gmvae_step, gmvae_forward, gmvae_dp_step, the bench and profile loops read slot 0; step i of
+        * gmvae_train_graph_create's and gmvae_dp_graph_create's graph reads slot i (n_steps > GMVAE_LABEL_SLOTS: GMVAE_E_DIMS);
+        * gmvae_train_graph_create_pipeline refuses the bit (GMVAE_E_DIMS); gmvae_forward honours it; gmvae_iw_bound* and
+        * gmvae_posterior_* mask it off and draw at dims->temperature.  GMVAE_E_MODEL for the VAE family; GMVAE_E_DIMS together
+        * with GMVAE_OBJ_MARGINAL_Y or GMVAE_OBJ_MARGINAL_Y_IW (those objectives draw no y; GMVAE_OBJ_LABELS and GMVAE_GRAD_DREG
+        * therefore cannot co-occur) -- from gmvae_workspace_bytes and every entry point that runs or sizes a step, before any
+        * launch.  Combines with GMVAE_OBJ_WEIGHTS (S == 1) and with GMVAE_Y_STRAIGHT_THROUGH.  Every step with the bit takes the
+        * general schedule; gmvae_step_schedule appends "+temp" behind "+weights":
+        *   <schedule> [+marginal | +marginal_iw] [+labels] [+weights] [+temp] [+st] [+dreg] [+planes]
+        * ("general+temp", "general+weights+temp+st").  Without the bit, sizes, layout and the answer for the name (GMVAE_E_NET)
+        * are what they were.  No atomics: eager and captured steps give the same bits. */
+       GMVAE_Y_TEMP_DEV = 128,
+       /* straight-through y (same domain and refusals as GMVAE_Y_TEMP_DEV; independent of it: without that bit T is
+        * dims->temperature): with a_rk = (logits_bk + g_rk) / T and the relaxed sample y_soft = softmax_k a_rk, the step
+        * CONSUMES the one-hot y_hard = e_{argmax_k (logits_bk + g_rk)} (lowest index on ties; the argmax does not depend on T):
+        * encoder_gmm's first layer, prior_gmm, their weight gradients, y_out and the workspace's "y" all hold one-hot rows -- what
+        * generate_samples, gmvae_iw_bound_enum_y and gmvae_posterior_y feed those networks.  Backward: dy, the data gradient at
+        * y_hard, is pulled through the relaxed sample, da = y_soft (dy - sum_k y_soft dy), dlogits_b = sum_s da / T + the entropy
+        * term -- autograd of y = y_soft + stopgrad(y_hard - y_soft) (Jang et al. 2017's ST Gumbel-softmax).  The analytic entropy
+        * term and the tail are unchanged.  The workspace grows BEHIND every other buffer ("y_temperature" too) by
+        *   "y_soft"  float [R][K], R = B S: the relaxed sample, rounded up to 256 bytes
+        * present only under this bit (else GMVAE_E_NET).  gmvae_forward honours the bit (y_out one-hot); gmvae_iw_bound and the
+        * posteriors mask it off -- for a straight-through model the estimators that match its one-hot y are
+        * gmvae_iw_bound_enum_y and gmvae_posterior_y.  The pipeline graph takes it (without GMVAE_Y_TEMP_DEV).  General
+        * schedule; gmvae_step_schedule appends "+st" behind "+temp".  No atomics: eager and captured steps give the same bits. */
+       GMVAE_Y_STRAIGHT_THROUGH = 256 };
+#define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -540,7 +575,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -555,7 +590,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
