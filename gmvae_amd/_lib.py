@@ -126,6 +126,7 @@ OBJ_LABELS = 32       # ... objective: observed components clamp y per example (
 OBJ_WEIGHTS = 64      # ... objective: the KL terms weighted per step from device memory (include/gmvae_hip.h GMVAE_OBJ_WEIGHTS)
 Y_TEMP_DEV = 128      # ... the Gumbel-softmax temperature read per step from device memory (include/gmvae_hip.h GMVAE_Y_TEMP_DEV)
 Y_STRAIGHT_THROUGH = 256   # ... one-hot y forward, the relaxed sample's Jacobian backward (include/gmvae_hip.h GMVAE_Y_STRAIGHT_THROUGH)
+OBJ_PIXEL_MASK = 512  # ... objective: a per-example observation mask read from the workspace (include/gmvae_hip.h GMVAE_OBJ_PIXEL_MASK)
 # Engine(y_estimator=...): the relaxed Gumbel-softmax sample, or its straight-through form (Jang et al. 2017)
 Y_ESTIMATORS = ("relaxed", "straight_through")
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph

@@ -259,3 +259,12 @@ def _targets_guard(loss, images, targets):
         raise NotImplementedError("targets != images is not used by the reference and not supported")
     bad = (targets.reshape(images.shape).to(images.device) != images).any()
     return loss + torch.where(bad, torch.full_like(loss, float("nan")), torch.zeros_like(loss))
+
+
+def impute(model, images, mask):
+    """mask * images + (1 - mask) * model.reconstruct_images(mask * images): the one imputation rule of VAE.impute and
+    GMVAE.impute (mask: uint8 / bool of the images' shape, non-zero = observed)."""
+    m = (torch.as_tensor(mask).to(images.device) != 0).reshape(images.shape)
+    xm = torch.where(m, images, torch.zeros_like(images))
+    rec = model.reconstruct_images(xm).reshape(images.shape)
+    return torch.where(m, images.to(rec.dtype), rec)

@@ -94,6 +94,8 @@ struct Problem {
   const float* rowscale;
   const unsigned char* x;  // Bernoulli targets
   float* part;             // Bernoulli row partial sums [M][nparts]
+  const unsigned char* xmask;   // GMVAE_OBJ_PIXEL_MASK: observed iff non-zero, x's layout (ldx, x_div); fp32 C, no planes.  The masked
+  float* part2;                 // epilogue: part sums the observed columns, part2 [M][nparts] the held-out ones, C = m (sigmoid - x)
   Segment seg[2];
 };
 
@@ -1833,8 +1835,10 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
     unsigned short* const C3 = L.p[pi].C3;         // (only set for launches whose tiles are all interior: planes_eligible)
     const long long c3s = L.p[pi].c3_stride;
     const float c3sc = L.p[pi].c3_scale;
+    const unsigned char* const xmp = L.p[pi].xmask;      // GMVAE_OBJ_PIXEL_MASK (else null): observed iff non-zero, x's layout
+    float* const part2 = L.p[pi].part2;
     if (m0 + C::BM <= M && (n0 + C::BN <= N || ((N & 3) == 0 && !C3)) && (ldc & 3) == 0 && (!Cout || al16(Cout)) && al16(bias) && (!bias2 || al16(bias2)) &&
-        (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(xp) & 3) == 0) {
+        (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(xp) & 3) == 0 && (reinterpret_cast<uintptr_t>(xmp) & 3) == 0) {
       // (also the LAST column tile of an N that is no multiple of the tile -- 784 = 6 x 128 + 16: a seventh of the tiles of every
       //  Bernoulli launch at the reference's D --: column quads beyond N are predicated off instead of sending the whole tile
       //  down the element-by-element path below)
@@ -1848,12 +1852,21 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
       float4 b4 = nv ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
       if (bias2 && nv) { const float4 c4v = *reinterpret_cast<const float4*>(bias2 + nb); b4.x += c4v.x; b4.y += c4v.y; b4.z += c4v.z; b4.w += c4v.w; }
       const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+      // (MK: the masked form, GMVAE_OBJ_PIXEL_MASK -- a constexpr switch around the whole tile, so that the unmasked instantiation
+      //  keeps its code: the mask word of a pass is requested beside its target word, in the same round trip)
+      auto interior = [&](auto mk_c) __attribute__((always_inline)) {
+      constexpr bool MK = decltype(mk_c)::value;
       unsigned xw[PASSES];
       f32x4 vv[PASSES];
 #pragma unroll
       for (int q = 0; q < PASSES; ++q) {
         const int m = m0 + r0 + RPP * q;
         xw[q] = nv ? *reinterpret_cast<const unsigned*>(xp + (long long)(m / x_div) * ldx + nb) : 0u;
+        if constexpr (MK) {
+          // (the mask rides in bit 7 of its target byte -- x is 0 or 1 --: one word per pass stays live beside the staged quads)
+          const unsigned mw = nv ? *reinterpret_cast<const unsigned*>(xmp + (long long)(m / x_div) * ldx + nb) : 0u;
+          xw[q] = (xw[q] & 0x7f7f7f7fu) | ((((mw & 0x7f7f7f7fu) + 0x7f7f7f7fu) | mw) & 0x80808080u);
+        }
       }
 #pragma unroll
       for (int q = 0; q < PASSES; ++q) {
@@ -1884,19 +1897,32 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
           // as matrix-pipe cycles in its 32 rounds, and the two do not overlap on a SIMD.)
           float v[4];
           f32x2_t brk = {0.f, 0.f}, prod = {1.f, 1.f};
+          // (masked: the held-out columns' bracket sums and (1 + e) products as a second pair of chains; with m in {0, 1} as a
+          //  float, m e + 1 is the observed chain's factor -- (1 + e) or exactly 1 -- and (1 - m) e + 1 the held-out chain's: one
+          //  log per chain and pass, no branch)
+          f32x2_t brk2 = {0.f, 0.f}, prod2 = {1.f, 1.f};
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const f32x2_t lam = f32x2_t{vv[q][2 * h], vv[q][2 * h + 1]} + f32x2_t{bc[2 * h], bc[2 * h + 1]};
-            const f32x2_t xf = {(float)((xw[q] >> (16 * h)) & 0xffu), (float)((xw[q] >> (16 * h + 8)) & 0xffu)};
+            const f32x2_t xf = {(float)((xw[q] >> (16 * h)) & (MK ? 0x7fu : 0xffu)), (float)((xw[q] >> (16 * h + 8)) & (MK ? 0x7fu : 0xffu))};
             const f32x2_t mx = {fmaxf(lam[0], 0.f), fmaxf(lam[1], 0.f)};
-            brk += xf * lam - mx;
             const f32x2_t e = {__builtin_amdgcn_exp2f(fabsf(lam[0]) * -1.44269504088896341f), __builtin_amdgcn_exp2f(fabsf(lam[1]) * -1.44269504088896341f)};
             const f32x2_t ope = e + 1.f;
-            prod *= ope;
             const f32x2_t rcp = {__builtin_amdgcn_rcpf(ope[0]), __builtin_amdgcn_rcpf(ope[1])};       // (only the sigmoid needs it)
             const f32x2_t er = e * rcp;
             const f32x2_t sg = f32x2_t{lam[0] >= 0.f ? rcp[0] : er[0], lam[1] >= 0.f ? rcp[1] : er[1]} - xf;
+            if constexpr (MK) {
+              const bool o0 = ((xw[q] >> (16 * h)) & 0x80u) != 0u, o1 = ((xw[q] >> (16 * h + 8)) & 0x80u) != 0u;
+              const f32x2_t mf = {o0 ? 1.f : 0.f, o1 ? 1.f : 0.f}, nf = {o0 ? 0.f : 1.f, o1 ? 0.f : 1.f};
+              const f32x2_t t = xf * lam - mx;
+              brk += mf * t; brk2 += nf * t;
+              prod *= mf * e + 1.f; prod2 *= nf * e + 1.f;
+              v[2 * h] = o0 ? sg[0] : 0.f; v[2 * h + 1] = o1 ? sg[1] : 0.f;      // (a clean +0: x at a missing pixel leaves no trace)
+            } else {
+            brk += xf * lam - mx;
+            prod *= ope;
             v[2 * h] = sg[0]; v[2 * h + 1] = sg[1];
+            }
           }
           const float rsum = (brk[0] + brk[1]) - __builtin_amdgcn_logf(prod[0] * prod[1]) * 0.693147180559945309f;
           if constexpr (CO) { if (nv) *reinterpret_cast<float4*>(Cout + (long long)(m0 + row) * ldc + nb) = make_float4(v[0], v[1], v[2], v[3]); }
@@ -1917,11 +1943,17 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
             *reinterpret_cast<uint2*>(d3 + 2 * c3s) = make_uint2(lo[0], lo[1]);
           }
           lds[row * C::LDC + 4 * c4] = nv ? rsum : 0.f;          // (this thread's own, already consumed, slot of the staged tile)
+          if constexpr (MK) {                                    // (the held-out row sum in the second float of the same quad)
+            const float rsum2 = (brk2[0] + brk2[1]) - __builtin_amdgcn_logf(prod2[0] * prod2[1]) * 0.693147180559945309f;
+            lds[row * C::LDC + 4 * c4 + 1] = nv ? rsum2 : 0.f;
+          }
         }
       };
       {
         typedef std::integral_constant<int, 0> M0; typedef std::integral_constant<int, 1> M1; typedef std::integral_constant<int, 2> M2;
         const int mode = !C3 ? 0 : (c3sc != 0.f ? 2 : 1);
+        if constexpr (MK) { if (Cout) passes(M0{}, std::true_type{}); else passes(M0{}, std::false_type{}); }      // (fp32 C or none, no planes)
+        else
         if (Cout) { if (mode == 2) passes(M2{}, std::true_type{}); else if (mode == 1) passes(M1{}, std::true_type{}); else passes(M0{}, std::true_type{}); }
         else { if (mode == 2) passes(M2{}, std::false_type{}); else if (mode == 1) passes(M1{}, std::false_type{}); else passes(M0{}, std::false_type{}); }
       }
@@ -1933,7 +1965,15 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
 #pragma unroll
         for (int c = 0; c < GPR; ++c) t += (double)lds[tid * C::LDC + 4 * c];
         part[(long long)(m0 + tid) * nparts + tn] = (float)t;
+        if constexpr (MK) {
+          double t2 = 0.0;
+#pragma unroll
+          for (int c = 0; c < GPR; ++c) t2 += (double)lds[tid * C::LDC + 4 * c + 1];
+          part2[(long long)(m0 + tid) * nparts + tn] = (float)t2;
+        }
       }
+      };
+      if (xmp) interior(std::true_type{}); else interior(std::false_type{});
     } else
 #pragma unroll 1
     for (int ps = 0; ps < PASSES; ++ps) {
@@ -1946,10 +1986,11 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
         v4.x += o.x; v4.y += o.y; v4.z += o.z; v4.w += o.w;
       }
       const int m = m0 + row, nb = n0 + 4 * c4;
-      float rsum = 0.f;
+      float rsum = 0.f, rsum2 = 0.f;
       if (m < M && nb < N) {
         float v[4] = {v4.x, v4.y, v4.z, v4.w};
         const unsigned char* xr = xp + (long long)(m / x_div) * ldx;
+        const unsigned char* mr = xmp ? xmp + (long long)(m / x_div) * ldx : nullptr;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int n = min(nb + j, N - 1);
@@ -1961,8 +2002,10 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
           const float e = fexp(-fabsf(lam));
           const float rcp = __builtin_amdgcn_rcpf(1.f + e);
           const float sp = fmaxf(lam, 0.f) - flog(rcp);
-          rsum += (nb + j < N) ? xv * lam - sp : 0.f;
-          v[j] = (lam >= 0.f ? rcp : e * rcp) - xv;
+          const bool ob = !mr || mr[n] != 0;              // (masked: the held-out columns to their own sum, their gradient a clean 0)
+          rsum += (nb + j < N && ob) ? xv * lam - sp : 0.f;
+          rsum2 += (nb + j < N && !ob) ? xv * lam - sp : 0.f;
+          v[j] = ob ? (lam >= 0.f ? rcp : e * rcp) - xv : 0.f;
         }
         if (Cout) {
           float* dst = Cout + (long long)m * ldc + nb;
@@ -1979,6 +2022,11 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
 #pragma unroll
       for (int o = GPR / 2; o > 0; o >>= 1) rsum += __shfl_xor(rsum, o, 64);
       if (m < M && c4 == 0) part[(long long)m * nparts + tn] = rsum;
+      if (xmp) {
+#pragma unroll
+        for (int o = GPR / 2; o > 0; o >>= 1) rsum2 += __shfl_xor(rsum2, o, 64);
+        if (m < M && c4 == 0) part2[(long long)m * nparts + tn] = rsum2;
+      }
     }
   }
   GMVAE_GSTAMP(4);

@@ -38,6 +38,7 @@
 #include "semisup.hpp"
 #include "wobj.hpp"
 #include "ytemp.hpp"
+#include "pmask.hpp"
 
 using namespace gmvae;
 
@@ -78,6 +79,9 @@ static bool obj_weights(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_
 static bool y_temp_dev(const GmvaeDims& d) { return (d.sched_flags & GMVAE_Y_TEMP_DEV) != 0; }
 static bool y_straight(const GmvaeDims& d) { return (d.sched_flags & GMVAE_Y_STRAIGHT_THROUGH) != 0; }
 static bool y_head_bits(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH)) != 0; }
+// GMVAE_OBJ_PIXEL_MASK: a per-example observation mask (pmask.hpp: x~ = m x for every network that reads x, the masked Bernoulli
+// epilogue of gemm.hpp, pmask_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes
+static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_PIXEL_MASK) != 0; }
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -204,8 +208,16 @@ static int check_ytemp_dims(const GmvaeDims* d, int model) {
   if (model != GMVAE_MODEL_GMVAE) return GMVAE_E_MODEL;
   return (marginal_y(*d) || sup_labels(*d) || dreg_grad(*d)) ? GMVAE_E_DIMS : 0;
 }
+// ... and GMVAE_OBJ_PIXEL_MASK together with any other objective or estimator bit: the three models' standard objectives (the
+// GMVAE's Gumbel draw) at any S only; the combinations are follow-ups  (check_pmask_dims: gmvae_forward's check too)
+static int check_pmask_dims(const GmvaeDims* d) {
+  if (!pixel_mask(*d)) return 0;
+  return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
+                            GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH)) ? GMVAE_E_DIMS : 0;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
+  if (int e = check_pmask_dims(d)) return e;
   if (int e = check_label_dims(d, model)) return e;
   if (int e = check_weight_dims(d)) return e;
   if (int e = check_ytemp_dims(d, model)) return e;
@@ -251,6 +263,10 @@ struct WS {
   // GMVAE_Y_TEMP_DEV: the caller's temperatures [GMVAE_LABEL_SLOTS] (read only); GMVAE_Y_STRAIGHT_THROUGH: the relaxed sample
   // [R][K] behind the one-hot y the step consumes
   float *y_temperature, *y_soft;
+  // GMVAE_OBJ_PIXEL_MASK: the caller's masks [GMVAE_LABEL_SLOTS][r256(B D)] (read only), x~ = m x [B D], the held-out Bernoulli
+  // partials [R][nparts] beside part, and the per-example (missing, observed) counts [B][2]
+  unsigned char *pixel_mask, *xm;
+  float *hpart, *mcnt;
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -315,7 +331,7 @@ static bool mega_shape(const GmvaeDims& d, int model) {
   return (size_t)mega_lay(H, d.L, d.K, d.D, model).total * 4 <= 160 * 1024;
 }
 static bool mega_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d) || y_head_bits(d)) return false;      // (GMVAE_OBJ_WEIGHTS, GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH: the general schedule only, as GMVAE_GRAD_DREG below)
+  if (obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;      // (GMVAE_OBJ_WEIGHTS, GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH, GMVAE_OBJ_PIXEL_MASK: the general schedule only, as GMVAE_GRAD_DREG below)
   if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
                                                //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
   const char* e = getenv("GMVAE_NO_MEGA");
@@ -365,7 +381,7 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
 static bool skinny_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;
   const char* e = getenv("GMVAE_NO_SKINNY");
   if (e && atoi(e)) return false;
   int maxb = kSkMaxB;
@@ -380,7 +396,7 @@ static bool fused_shape(const GmvaeDims& d, int model) {
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
 }
 static bool fused_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;
   const char* e = getenv("GMVAE_NO_FUSED");
   if (e && atoi(e)) return false;
   return fused_shape(d, model);
@@ -395,7 +411,7 @@ static bool evalf_shape(const GmvaeDims& d, int model) {
   return d.L == 64 && d.K == 10;                                       // VAE_GMP: configs[1]
 }
 static bool evalf_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d) || y_head_bits(d)) return false;      // (gmvae_forward honours GMVAE_OBJ_WEIGHTS and the y head's bits: the general schedule's forward)
+  if (obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;      // (gmvae_forward honours GMVAE_OBJ_WEIGHTS, the y head's bits and GMVAE_OBJ_PIXEL_MASK: the general schedule's forward)
   const char* e = getenv("GMVAE_NO_EVALF");
   if (e && atoi(e)) return false;
   if (!evalf_shape(d, model)) return false;
@@ -432,6 +448,7 @@ static int num_splits_small(long long R) {
 static bool planes_ok(const GmvaeDims& d, const Layout& L) {
   const char* e = getenv("GMVAE_NO_PLANES");
   if (e && atoi(e)) return false;
+  if (pixel_mask(d)) return false;                      // (the masked Bernoulli epilogue writes fp32 C alone)
   if (d.hidden_act != GMVAE_ACT_RELU) return false;     // (the plane producers' epilogues are the ReLU ones)
   const long long R = (long long)d.B * rows_per_x(d);
   const int Ht = L.dec.dim[L.dec.nl - 1];
@@ -591,6 +608,13 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
   }
   if (y_temp_dev(d)) w.y_temperature = take(GMVAE_LABEL_SLOTS);      // (behind everything, as above: one float per slot)
   if (y_straight(d)) w.y_soft = take(R * K);
+  if (pixel_mask(d)) {                            // (behind everything, as above; a slot is r256(B D) bytes: each starts 256-byte aligned)
+    const uint64_t slot = (B * D + 255) / 256 * 256;
+    w.pixel_mask = reinterpret_cast<unsigned char*>(take((uint64_t)GMVAE_LABEL_SLOTS * slot / 4));
+    w.xm = reinterpret_cast<unsigned char*>(take((B * D + 3) / 4));
+    w.hpart = take(R * ((D + 31) / 32));
+    w.mcnt = take(2 * B);
+  }
   w.bytes = off;
 }
 
@@ -603,6 +627,7 @@ static bool fwd_pairs_ok(const GmvaeDims& d, const Layout& L) {
   if (e && atoi(e)) return false;
   const char* x = getenv("GMVAE_PLANES_EXACT");
   if (x && atoi(x)) return false;
+  if (pixel_mask(d)) return false;
   if (d.hidden_act != GMVAE_ACT_RELU || L.dec.nl < 2) return false;
   const long long R = (long long)d.B * rows_per_x(d);
   const int Ht = L.dec.dim[L.dec.nl - 1];
@@ -965,6 +990,8 @@ struct StepArgs {
   int label_slot = 0;          // GMVAE_OBJ_LABELS: which of the workspace's label sets the step reads (step i of a train graph: i)
   int weights_slot = 0;        // GMVAE_OBJ_WEIGHTS: which row of the workspace's "obj_weights" the step reads (likewise)
   int temp_slot = 0;           // GMVAE_Y_TEMP_DEV: which float of the workspace's "y_temperature" the step reads (likewise)
+  int mask_slot = 0;           // GMVAE_OBJ_PIXEL_MASK: which of the workspace's masks the step reads (likewise)
+  bool iw_chunk = false;       // a chunk pass of gmvae_iw_bound: iw_tail writes the tail, [5..7] = 0 -- no pmask_tail
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -2103,6 +2130,16 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
                          (y_straight(d) && !w.y_soft)))
     return GMVAE_E_DIMS;
   const float* const ytau = y_temp_dev(d) ? w.y_temperature + a.temp_slot : nullptr;
+  // GMVAE_OBJ_PIXEL_MASK: this step's mask; xin = x~ = m x is what the first layers and their weight gradients read, a.x itself
+  // only the Bernoulli epilogue's target
+  const bool pmask = pixel_mask(d);
+  if (pmask && (marg || !w.pixel_mask || !w.xm || !w.hpart || !w.mcnt || a.mask_slot < 0 || a.mask_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  const unsigned char* const pm = pmask ? w.pixel_mask + (size_t)a.mask_slot * (((size_t)B * D + 255) / 256 * 256) : nullptr;
+  const uint8_t* const xin = pmask ? w.xm : a.x;
+  if (pmask) {
+    hipLaunchKernelGGL(pmask_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, pm, w.xm, w.mcnt, B, D);
+    rowk(cx, "pmask_rows");
+  }
   // (general schedule: the Philox fill rides as auxiliary workgroups of the first GEMM launch below)
   const bool noise_aux = ge || gu;
   const bool relu_act = d.hidden_act == GMVAE_ACT_RELU;      // (tanh / sigmoid / ELU: the grouped GEMM's epilogues only)
@@ -2171,7 +2208,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
     // first layers over the uint8 batch as exact bf16 piece products (skinny.hpp first_layers_u8bf); the Philox fill in a
     // launch of its own
     FlxArgs f;
-    f.x = a.x; f.W0 = P + E.w[0]; f.b0 = P + E.b[0]; f.out0 = w.he[1]; f.H0 = flx_h0; f.relu0 = 1;
+    f.x = xin; f.W0 = P + E.w[0]; f.b0 = P + E.b[0]; f.out0 = w.he[1]; f.H0 = flx_h0; f.relu0 = 1;
     f.W1 = gm ? P + L.encg.w[0] : nullptr; f.out1 = gm ? w.gx : nullptr; f.H1 = flx_h1;
     f.B = B; f.D = D;
     const int nct = (flx_h0 + flx_h1) / 64, nrt = (B + 15) / 16;
@@ -2193,9 +2230,9 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   {  // first layers over the uint8 batch: enc_y layer 0 and the x-part of enc_gmm layer 0
     Group g;
     float* out = (E.nl == 1) ? (gm ? w.logits : w.qp) : w.he[1];
-    g.add(p_nn(a.x, true, D, P + E.w[0], E.dim[1], B, E.dim[1], D, out, E.dim[1], P + E.b[0], E.nl > 1));
+    g.add(p_nn(xin, true, D, P + E.w[0], E.dim[1], B, E.dim[1], D, out, E.dim[1], P + E.b[0], E.nl > 1));
     if (gm)
-      g.add(p_nn(a.x, true, D, P + L.encg.w[0], L.encg.dim[1], B, L.encg.dim[1], D, w.gx, L.encg.dim[1], nullptr,
+      g.add(p_nn(xin, true, D, P + L.encg.w[0], L.encg.dim[1], B, L.encg.dim[1], D, w.gx, L.encg.dim[1], nullptr,
                  false));
     if (noise_aux) {
       Aux& ax = g.L.aux;
@@ -2349,6 +2386,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       p.addconst = d.gen_bias_init;
       p.bias2 = d.gen_bias_vec;
       p.x = a.x; p.ldx = D; p.x_div = S; p.part = w.part;
+      p.xmask = pm; p.part2 = pmask ? w.hpart : nullptr;      // (the masked form: observed columns to part, held-out ones to part2)
       if (fwdp) {
         // forward only: both operands as f16 pairs, the weight's planes zero-padded to whole 128-column tiles
         const int Dp = (D + 127) / 128 * 128;
@@ -2464,6 +2502,10 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
     if (sup) {                   // tail[5..7]: the labelled examples' cross-entropy sum, count and hits
       hipLaunchKernelGGL(sup_tail, dim3(1), dim3(256), 0, st, w.sup_trip, tail, B);
       rowk(cx, "sup_tail");
+    }
+    if (pmask && !a.iw_chunk) {  // tail[5..7]: the held-out pixels' -log-likelihood (mean over s), the missing and the observed counts
+      hipLaunchKernelGGL(pmask_tail, dim3(1), dim3(1024), 0, st, w.hpart, nparts, w.mcnt, tail, B, S);
+      rowk(cx, "pmask_tail");
     }
   }
   if (a.z_out) hipMemcpyAsync(a.z_out, w.z, (size_t)R * Lz * 4, hipMemcpyDeviceToDevice, st);
@@ -2616,7 +2658,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       const float* Wy = P + G.w[0] + (uint64_t)D * G.dim[1];
       const int nsx = (S > 1 && sxb.n + 2 <= kSlabRanges) ? NSB : NS;
       if (nsx != NS) { brange(G.w[0], (uint64_t)D * G.dim[1], nsx); brange(G.b[0], G.dim[1], nsx); }
-      g.add(p_tn(a.x, true, D, 1, dg, G.dim[1], D, G.dim[1], B, sl + G.w[0], sl + G.b[0], nsx, PP, nullptr));
+      g.add(p_tn(xin, true, D, 1, dg, G.dim[1], D, G.dim[1], B, sl + G.w[0], sl + G.b[0], nsx, PP, nullptr));
       if (marg) {
         // y = e_k: the y rows of the first layer's weight and the prior's weight take segmented column sums over the batch
         // (ymarg_dw, slabs as the split-K GEMMs write them); no data gradient of y
@@ -2699,7 +2741,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   }
   for (int i = E.nl - 1; i >= 0; --i) {   // enc_y (GMVAE) / encoder (VAE): rows = B
     Group g;
-    const void* act = (i == 0) ? (const void*)a.x : (const void*)w.he[i];
+    const void* act = (i == 0) ? (const void*)xin : (const void*)w.he[i];
     const int nse = (S > 1 && sxb.n + 2 <= kSlabRanges) ? NSB : NS;
     if (nse != NS) { brange(E.w[i], (uint64_t)E.dim[i] * E.dim[i + 1], nse); brange(E.b[i], E.dim[i + 1], nse); }
     g.add(p_tn(act, i == 0, E.dim[i], 1, dcur, E.dim[i + 1], E.dim[i], E.dim[i + 1], B, sl + E.w[i], sl + E.b[i], nse,
@@ -2753,6 +2795,11 @@ static int iw_dims(IwKind kind, const GmvaeDims* dims, int model, GmvaeDims& d) 
   const IwKindRow& k = kIwKinds[kind];
   if (!dims) return GMVAE_E_NULL;
   d = *dims;
+  // GMVAE_OBJ_PIXEL_MASK: gmvae_iw_bound honours it (mask slot 0, the general chunk passes: the bound on log p(x_observed)); the
+  // other kinds refuse it -- masking it off would silently score the unobserved pixels.  Its refusals hold before the other
+  // bits are masked off.
+  if (int e = check_pmask_dims(dims)) return e;
+  if (pixel_mask(d) && kind != IW_BOUND) return GMVAE_E_DIMS;
   d.sched_flags &= ~kIwMasked;
   if (k.enum_y) d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW);
   if (int e = check_dims(&d, model)) return e;
@@ -2850,7 +2897,8 @@ static int iw_general_chunks(Ctx& cx, const IwCall& c, float* z_out, Merge merge
   const int per = rows_per_x(d) / d.S;             // (rows per sample: K with y summed out)
   float* const eps = c.at<float>(c.il.eps);
   float* const u = c.model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? c.at<float>(c.il.u) : nullptr;
-  const StepArgs a = iw_step_args(c, eps, u, c.at<float>(c.il.ftail), c.at<float>(c.il.rows), z_out);
+  StepArgs a = iw_step_args(c, eps, u, c.at<float>(c.il.ftail), c.at<float>(c.il.rows), z_out);
+  a.iw_chunk = true;
   const uint64_t S = d.S, q = noise_items(true, u != nullptr, (uint64_t)d.B * S * per, d.L, d.K);
   for (uint64_t i = 0; i < c.nch; ++i) {
     hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, cx.st, eps, u, d.B, d.S * per, d.L, d.K,
@@ -3065,7 +3113,7 @@ static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, fl
   a.adam_p = params; a.adam_m = m; a.adam_v = v; a.lr = lr; a.beta1 = b1; a.beta2 = b2; a.epsilon = eps_;
   a.imgs_ready = imgs_ready;
   a.tail_log = tail_log;
-  a.label_slot = a.weights_slot = a.temp_slot = label_slot;    // (step i of a train graph: label set i, weight row i, temperature i)
+  a.label_slot = a.weights_slot = a.temp_slot = a.mask_slot = label_slot;    // (step i of a train graph: label set i, weight row i, temperature i, mask i)
   return run_step(cx, a);
 }
 
@@ -3076,6 +3124,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (int e = check_label_dims(dims, model)) return e;
   if (int e = check_weight_dims(dims)) return e;
   if (int e = check_ytemp_dims(dims, model)) return e;
+  if (int e = check_pmask_dims(dims)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
@@ -3667,7 +3716,8 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
   // label gather
   // (GMVAE_OBJ_WEIGHTS likewise: step i reads weight row i)
   // (GMVAE_Y_TEMP_DEV likewise: step i reads temperature i)
-  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  // (GMVAE_OBJ_PIXEL_MASK likewise: step i reads mask i)
+  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims) || pixel_mask(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3779,9 +3829,9 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
-           y_straight(d) ? "+st" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+           y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3818,7 +3868,7 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)},
       {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight},
       {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor},
-      {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}};
+      {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}, {"pixel_mask", reinterpret_cast<float*>(w.pixel_mask)}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;
@@ -3942,7 +3992,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   a.dp_images = scatter;
   a.imgs_ready = scatter && imgs_ready;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
-  a.label_slot = a.weights_slot = a.temp_slot = label_slot;
+  a.label_slot = a.weights_slot = a.temp_slot = a.mask_slot = label_slot;
   cx.prof = prof;
   int rc = run_step(cx, a);
   if (rc) return rc;
@@ -4089,7 +4139,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
-  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row / temperature i)
+  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims) || pixel_mask(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row / temperature / mask i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

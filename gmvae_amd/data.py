@@ -43,15 +43,22 @@ class DeviceDataset:
     """uint8 pixels [N, ...] (+ labels) resident on the GPU; `next_batch(B)` returns a freshly binarised uint8
     [B, D] batch and its labels.  shuffle=True draws a new permutation per epoch on the device; every batch gets
     new uniforms (step counter), as the reference's `repeat()` after `map()` does.  y_observed (optional): int32 [N],
-    resident too -- the component a semi-supervised step may see for each row, -1 = unlabelled."""
+    resident too -- the component a semi-supervised step may see for each row, -1 = unlabelled.  pixel_mask (optional): uint8
+    [N, D], resident too -- the row's observation mask (non-zero: observed) of a step with a pixel mask."""
 
-    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None):
+    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None, pixel_mask=None):
         dev = L.require_gpu()
         pixels = torch.as_tensor(pixels)
         self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.uint8).contiguous()
         self.labels = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
         self.y_observed = None if y_observed is None else torch.as_tensor(y_observed).to(dev, torch.int32).contiguous()
         self.N, self.D = self.pixels.shape
+        self.pixel_mask = None
+        if pixel_mask is not None:
+            pm = torch.as_tensor(pixel_mask)
+            if pm.numel() != self.N * self.D:
+                raise ValueError(f"pixel_mask must have one entry per pixel ({self.N} x {self.D}), got {tuple(pm.shape)}")
+            self.pixel_mask = (pm.reshape(self.N, self.D) != 0).to(dev, torch.uint8).contiguous()
         if self.y_observed is not None and self.y_observed.shape != (self.N,):
             raise ValueError(f"y_observed must have one entry per row ({self.N}), got {tuple(self.y_observed.shape)}")
         self.shuffle, self.seed = shuffle, int(seed)

@@ -24,8 +24,8 @@ class _ElboFn(torch.autograd.Function):
     forward+backward (the backward pass has already run when this returns)."""
 
     @staticmethod
-    def forward(ctx, params, engine, x, eps, u, y_observed=None):
-        buf = engine.step(x, eps, u, y_observed=y_observed)
+    def forward(ctx, params, engine, x, eps, u, y_observed=None, mask=None):
+        buf = engine.step(x, eps, u, y_observed=y_observed, mask=mask)
         P = engine.P
         ctx.engine_buf = buf
         ctx.P = P
@@ -34,7 +34,7 @@ class _ElboFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         buf, P = ctx.engine_buf, ctx.P
-        return buf[:P] * (grad_out / buf[P + 4]), None, None, None, None, None
+        return buf[:P] * (grad_out / buf[P + 4]), None, None, None, None, None, None
 
 
 def check_semi_supervised(model, y_inference, semi_supervised, sup_weight):
@@ -85,13 +85,33 @@ def check_y_head(model, y_inference, temperature, temperature_on_device, y_estim
         raise ValueError(f"{what} needs y_inference='gumbel': y_inference={y_inference!r} sums y out and draws none")
 
 
+def check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                     y_estimator, pixel_mask):
+    """The argument check of Engine(pixel_mask=) (no device needed): the library's refusals of GMVAE_OBJ_PIXEL_MASK."""
+    if not pixel_mask:
+        return
+    if L.MODEL_IDS.get(model) == L.MODEL_GMVAE and y_inference != "gumbel":
+        raise ValueError(f"pixel_mask=True is not available with y_inference={y_inference!r}: use 'gumbel'")
+    if grad_estimator == "dreg":
+        raise ValueError("pixel_mask=True is not available with grad_estimator='dreg'")
+    if semi_supervised:
+        raise ValueError("pixel_mask=True is not available with semi_supervised=True")
+    if weighted_objective:
+        raise ValueError("pixel_mask=True is not available with weighted_objective=True")
+    if temperature_on_device:
+        raise ValueError("pixel_mask=True is not available with temperature_on_device=True")
+    if y_estimator != "relaxed":
+        raise ValueError(f"pixel_mask=True is not available with y_estimator={y_estimator!r}")
+
+
 class Engine:
     def __init__(self, model: str, data_size: int, latent_size: int, mixture_components: int,
                  hidden: Sequence[int], n_samples: int = 1, sigma_min: float = 0.0, raw_sigma_bias: float = 0.5,
                  temperature: float = 1.0, gen_bias_init=0.0, random_seed: Optional[int] = None, hidden_act: str = "relu",
                  y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
-                 y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed"):
+                 y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed",
+                 pixel_mask: bool = False):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -119,7 +139,14 @@ class Engine:
         y_estimator (same domain; GMVAE_Y_STRAIGHT_THROUGH): "relaxed" -- y = softmax((logits + g) / T), the default -- or
         "straight_through": the step consumes the one-hot argmax of logits + g and differentiates through the relaxed
         sample, so that training feeds prior_gmm and encoder_gmm the one-hot y that generation and the enumerating
-        evaluators (iw_bound_enum_y, posterior_y) feed them.  General schedule.  Parameters and checkpoints are the same."""
+        evaluators (iw_bound_enum_y, posterior_y) feed them.  General schedule.  Parameters and checkpoints are the same.
+        pixel_mask (all three models, the GMVAE with y_inference "gumbel"; include/gmvae_hip.h GMVAE_OBJ_PIXEL_MASK): step /
+        loss / forward / train_step / dp_step / iw_bound take mask=, a uint8 / bool tensor [B, D] (non-zero: observed; None:
+        all observed).  The networks that read x see mask * x, the likelihood and every gradient count the observed pixels
+        alone, and tail [5..7] report the held-out pixels' -log-likelihood and the missing / observed counts.  General
+        schedule.  Parameters and checkpoints are the same with and without it."""
+        check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                         y_estimator, pixel_mask)
         check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator)
         check_semi_supervised(model, y_inference, semi_supervised, sup_weight)
         check_weighted_objective(model, y_inference, n_samples, grad_estimator, semi_supervised, weighted_objective,
@@ -169,6 +196,7 @@ class Engine:
         self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
         self.temperature_on_device = bool(temperature_on_device)
         self.y_estimator = y_estimator
+        self.pixel_mask = bool(pixel_mask)
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -214,9 +242,10 @@ class Engine:
         # (the weighted objective is the one-sample bound's: a forward at another number of samples reports the plain bound)
         wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
         yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
+        pmask = L.OBJ_PIXEL_MASK if self.pixel_mask else 0
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
-                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | extra_flags, **self.hp)
+                           sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | pmask | extra_flags, **self.hp)
 
     def _obj_flags(self):
         obj = L.OBJ_MARGINAL_Y_IW if self.marginal_iw else L.OBJ_MARGINAL_Y if self.marginal else 0
@@ -337,6 +366,9 @@ class Engine:
             if self.temperature_on_device:
                 # the library only reads the region, and zeros would mean T = 0
                 self._temp_slots(d, self._ws[key]).fill_(self.hp["temperature"])
+            if self.pixel_mask:
+                # the library only reads the region, and zeros would mean "nothing observed"
+                self._mask_slots(d, self._ws[key]).fill_(1)
             if self.semi_supervised:
                 # the library only reads these two regions, and zeros would mean "component 0 observed, weight 0"
                 self._label_slots(d, self._ws[key]).fill_(-1)
@@ -387,6 +419,31 @@ class Engine:
             self._tau_dev.fill_(float(t))
         elif changed:
             self.drop_graphs(clear_handoff_errors=False)
+
+    def _mask_slots(self, d, ws) -> torch.Tensor:
+        """uint8 view [LABEL_SLOTS, B, D] of the workspace's masks (a slot is B D bytes rounded up to 256)."""
+        n = d.B * d.D
+        slot = (n + 255) // 256 * 256
+        off = L.workspace_offset(d, self.model, "pixel_mask")
+        return ws.view(torch.uint8)[off:off + L.LABEL_SLOTS * slot].view(L.LABEL_SLOTS, slot)[:, :n].view(L.LABEL_SLOTS, d.B, d.D)
+
+    def _prep_mask(self, mask, B):
+        mask = mask.to(self.device)
+        if mask.dtype.is_floating_point or mask.numel() != B * self.D:
+            raise ValueError(f"mask must be a uint8 / bool tensor [{B}, {self.D}] (non-zero: observed)")
+        return (mask != 0).reshape(B, self.D)
+
+    def _set_mask(self, d, ws, mask):
+        """Slot 0 of the workspace's masks <- mask (device-side copy, no host sync); None: all observed."""
+        if not self.pixel_mask:
+            if mask is not None:
+                raise ValueError("mask needs an engine created with pixel_mask=True")
+            return
+        slot = self._mask_slots(d, ws)[0]
+        if mask is None:
+            slot.fill_(1)
+            return
+        slot.copy_(self._prep_mask(mask, d.B), non_blocking=True)
 
     def _label_slots(self, d, ws) -> torch.Tensor:
         """int32 view [LABEL_SLOTS, B] of the workspace's label sets (each slot starts 16-byte aligned)."""
@@ -440,7 +497,7 @@ class Engine:
 
     # ------------------------------------------------------------------ ops
     def step(self, x, eps=None, u=None, use_step_dev: bool = False, row0: Optional[int] = None,
-             y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
+             y_observed: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Fused forward + backward.  Returns the [P + TAIL] buffer of gradient
         SUMS and loss sums (see include/gmvae_hip.h).  eps/u None -> Philox, keyed by
         (noise_seed, global_step, global row = row0 + b; row0 defaults to rank * B)."""
@@ -450,6 +507,7 @@ class Engine:
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
         self._set_temp(d, ws)
+        self._set_mask(d, ws, mask)
         eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
         u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
@@ -459,11 +517,13 @@ class Engine:
         self._keep = (x, eps, u)
         return self.grads
 
-    def loss(self, x, eps=None, u=None, y_observed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def loss(self, x, eps=None, u=None, y_observed: Optional[torch.Tensor] = None,
+             mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Differentiable scalar: loss.backward() fills params.grad."""
-        return _ElboFn.apply(self.params, self, x, eps, u, y_observed)
+        return _ElboFn.apply(self.params, self, x, eps, u, y_observed, mask)
 
-    def forward(self, x, eps=None, u=None, n_samples: Optional[int] = None, y_observed: Optional[torch.Tensor] = None):
+    def forward(self, x, eps=None, u=None, n_samples: Optional[int] = None, y_observed: Optional[torch.Tensor] = None,
+                mask: Optional[torch.Tensor] = None):
         """Forward only.  dict(tail[8], rows[R,4]=(logpx,logq,logp,logw), z, y, logits)."""
         x = self._prep_x(x)
         B = x.shape[0]
@@ -474,6 +534,7 @@ class Engine:
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
         self._set_temp(d, ws)
+        self._set_mask(d, ws, mask)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
@@ -502,9 +563,11 @@ class Engine:
     _CHUNKED = {"iw_bound": (False, False), "iw_bound_enum_y": (True, False), "posterior_y": (True, True),
                 "posterior_component": (False, True)}
 
-    def _chunked_eval(self, kind: str, x, n_samples: int, chunk: Optional[int], row0: Optional[int]):
+    def _chunked_eval(self, kind: str, x, n_samples: int, chunk: Optional[int], row0: Optional[int], mask=None):
         """One call of a chunked evaluator: (its output tensors in the order of the C signature, tail [8])."""
         enum_y, per_component = self._CHUNKED[kind]
+        if self.pixel_mask and kind != "iw_bound":
+            raise ValueError(f"{kind} is not available with pixel_mask=True (it would score the unobserved pixels): use iw_bound")
         x = self._prep_x(x)
         if x.data_ptr() % 16:
             x = x.clone()
@@ -519,6 +582,7 @@ class Engine:
         ws = self._chunked_ws.get((kind, B, chunk))
         if ws is None or ws.numel() < nw:
             ws = self._chunked_ws[(kind, B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        self._set_mask(d, ws, mask)      # (the forward's workspace opens the evaluator's: the same offset)
         f32 = dict(dtype=torch.float32, device=self.device)
         shapes = ((B, self.K), (B, self.K), (B, 4)) if per_component else ((B,), (B,))
         outs = [torch.empty(*shape, **f32) for shape in shapes]
@@ -529,16 +593,18 @@ class Engine:
         self._keep_iw = x
         return outs, tail
 
-    def iw_bound(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
+    def iw_bound(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None,
+                 mask: Optional[torch.Tensor] = None):
         """The importance-weighted bound at any number of samples, streamed in chunks (include/gmvae_hip.h gmvae_iw_bound):
         dict(bound [B] = logsumexp_s log w - log n, mean_logw [B], tail [8] as forward's at S = n).  chunk: samples per pass
         (default: B * chunk near IW_CHUNK_ROWS, at most n_samples); the memory depends on B * chunk, not on n_samples.
         Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step), row0 defaulting to
-        rank * B: the result does not depend on the chunk, the batch size or the sharding."""
+        rank * B: the result does not depend on the chunk, the batch size or the sharding.
+        mask (pixel_mask=True): the bound on log p(x_observed)."""
         if self.marginal:
             raise ValueError(f"iw_bound: the importance-weighted bound is not available with y_inference={self.y_inference!r} "
                              "(it is the Gumbel objective's bound)")
-        (bound, mean_logw), tail = self._chunked_eval("iw_bound", x, n_samples, chunk, row0)
+        (bound, mean_logw), tail = self._chunked_eval("iw_bound", x, n_samples, chunk, row0, mask)
         return dict(bound=bound, mean_logw=mean_logw, tail=tail)
 
     def iw_bound_enum_y(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
@@ -618,11 +684,12 @@ class Engine:
 
     def train_step(self, x, eps=None, u=None, lr: float = 1e-3, all_reduce: bool = True,
                    row0: Optional[int] = None, y_observed: Optional[torch.Tensor] = None,
-                   beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8) -> torch.Tensor:
+                   beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8,
+                   mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One full reference step: fwd + bwd (+ RCCL all-reduce) + Adam (beta1, beta2, epsilon: tf.train.AdamOptimizer's).
         Returns the [TAIL] loss sums (device tensor; no host sync)."""
         import torch.distributed as dist
-        self.step(x, eps, u, row0=row0, y_observed=y_observed)
+        self.step(x, eps, u, row0=row0, y_observed=y_observed, mask=mask)
         if all_reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             from . import parallel
             parallel.all_reduce_flat(self.grads)     # ONE collective: grads + loss sums + count
@@ -678,13 +745,14 @@ class Engine:
         return comm
 
     def dp_step(self, x, lr: float = 1e-3, y_observed: Optional[torch.Tensor] = None,
-                beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8):
+                beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8, mask: Optional[torch.Tensor] = None):
         """gmvae_dp_step: one C call enqueues step + RCCL all-reduce + Adam on the current stream."""
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
         self._set_labels(d, ws, y_observed)
         self._set_weights(d, ws)
         self._set_temp(d, ws)
+        self._set_mask(d, ws, mask)
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
@@ -711,7 +779,9 @@ class Engine:
         writes before it runs -- the engine's current weights, its y_observed -- so after any eager call row 0 holds that
         call's values until the caller refills it: fill the rows before EVERY replay (run_train does).
         replay.y_temperature [n_steps] (temperature_on_device; pre-filled with the engine's current temperature) likewise:
-        a view of the workspace's temperatures, step i reads value i, slot 0 is also every eager entry's."""
+        a view of the workspace's temperatures, step i reads value i, slot 0 is also every eager entry's.
+        replay.pixel_mask [n_steps, B, D] (pixel_mask; uint8, pre-filled with ones = all observed) likewise: a view of the
+        workspace's masks, step i reads mask i, slot 0 is also every eager entry's."""
         import torch.distributed as dist
         do_ar = all_reduce and ((dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
                                 or getattr(self, "_comm", None) is not None)
@@ -722,6 +792,8 @@ class Engine:
             raise ValueError(f"a train graph of a weighted objective holds at most {L.LABEL_SLOTS} steps (one weight row per step), got {n_steps}")
         if self.temperature_on_device and n_steps > L.LABEL_SLOTS:
             raise ValueError(f"a train graph with the temperature on the device holds at most {L.LABEL_SLOTS} steps (one temperature per step), got {n_steps}")
+        if self.pixel_mask and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph with a pixel mask holds at most {L.LABEL_SLOTS} steps (one mask per step), got {n_steps}")
         adam_hp = (float(beta1), float(beta2), float(epsilon))
         key = (B, lr, do_ar, n_steps) + adam_hp
         if key in self._graphs:
@@ -750,6 +822,12 @@ class Engine:
         if self.temperature_on_device:
             y_temp = self._temp_slots(d, ws)[:n_steps]
             y_temp.copy_(self._tau_dev.expand(n_steps))
+
+        # pixel mask: step i reads mask i; the caller fills replay.pixel_mask [n_steps, B, D] (pre-filled: all observed)
+        pmask = None
+        if self.pixel_mask:
+            pmask = self._mask_slots(d, ws)[:n_steps]
+            pmask.fill_(1)
 
         def eager_rows(body):
             """The graph's steps one by one (no graph could be captured): step i's weight row and temperature pass through
@@ -790,6 +868,7 @@ class Engine:
                         L.check(rc2, "gmvae_train_graph_launch")
                     self.global_step += n_steps
                 replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
+                replay.pixel_mask = pmask
                 self._graphs[key] = (static_x, replay, handle)
                 return static_x, replay
             if rc == 0:
@@ -800,14 +879,18 @@ class Engine:
 
             def replay():
                 ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
+                ms = None if pmask is None else pmask.clone()
 
                 def body(i):
-                    self.dp_step(batches[i], lr, None if ys is None else ys[i], *adam_hp)
+                    self.dp_step(batches[i], lr, None if ys is None else ys[i], *adam_hp, mask=None if ms is None else ms[i])
                     tail_log[i].copy_(self.grads[self.P:])
                 eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
+                if ms is not None:
+                    pmask[0].copy_(ms[0])
             replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
+            replay.pixel_mask = pmask
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         if do_ar:
@@ -817,9 +900,11 @@ class Engine:
 
             def replay():
                 ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
+                ms = None if pmask is None else pmask.clone()
 
                 def body(i):
-                    self.step(batches[i], use_step_dev=True, y_observed=None if ys is None else ys[i])
+                    self.step(batches[i], use_step_dev=True, y_observed=None if ys is None else ys[i],
+                              mask=None if ms is None else ms[i])
                     parallel.all_reduce_flat(self.grads)
                     self.adam(lr, *adam_hp, use_step_dev=True)
                     self.global_step += 1
@@ -827,7 +912,10 @@ class Engine:
                 eager_rows(body)
                 if ys is not None:
                     y_obs[0].copy_(ys[0])
+                if ms is not None:
+                    pmask[0].copy_(ms[0])
             replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
+            replay.pixel_mask = pmask
             self._graphs[key] = (static_x, replay, None)
             return static_x, replay
         torch.cuda.synchronize()
@@ -847,6 +935,7 @@ class Engine:
             self.global_step += n_steps
 
         replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
+        replay.pixel_mask = pmask
         self._graphs[key] = (static_x, replay, handle)
         return static_x, replay
 
@@ -867,6 +956,9 @@ class Engine:
         if self.temperature_on_device:
             raise ValueError("capture_train_pipeline has no per-step temperatures: an engine with temperature_on_device=True "
                              "trains through capture_train_step (replay.y_temperature)")
+        if self.pixel_mask:
+            raise ValueError("capture_train_pipeline has no per-step masks: an engine with pixel_mask=True trains through "
+                             "capture_train_step (replay.pixel_mask)")
         n_steps = int(n_steps)
         key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon))
         if key in self._graphs:

@@ -45,6 +45,12 @@ class GMVAE:
             z = self.generate_samples(num_samples)
         return self.decoder(z).mean(name=name)
 
+    def impute(self, images, mask):
+        """Fills in the missing pixels: mask * images + (1 - mask) * reconstruct_images(mask * images) -- the observed pixels
+        exactly as given, the others the decoder's mean from the zero-imputed input the networks were trained on (a model
+        created with pixel_mask=True).  A float tensor of the images' shape."""
+        return base.impute(self, images, mask)
+
     def transform(self, inputs):
         """SAMPLED latent code (scripts/gmvae.py:140-149; the VAE returns the mean)."""
         y = self.encoder_y(inputs).sample(seed=self.random_seed)
@@ -79,26 +85,27 @@ class TrainableGMVAE(GMVAE):
             raise RuntimeError("run_model needs the fused HIP engine: build the model with create_gmvae()")
         return self._engine
 
-    def run_model(self, images, targets, labels=None, eps=None, u=None, y_observed=None):
+    def run_model(self, images, targets, labels=None, eps=None, u=None, y_observed=None, mask=None):
         """Batch-mean loss = nll + kl_div_z + nent (scripts/gmvae.py:223-274); ELBO = -loss
         (the +ln K constant is omitted, as in the reference).  eps [B*S,L] / u [B*S,K]:
         optional explicit noise (parity mode); default is in-kernel Philox.  labels: the ground truth cluster_acc is
         scored against, never seen by the objective.  y_observed (a model created with semi_supervised=True): int [B],
-        the observed component of each example or -1 -- those examples' y is clamped in the loss (Engine)."""
+        the observed component of each example or -1 -- those examples' y is clamped in the loss (Engine).  mask (a model
+        created with pixel_mask=True): uint8 / bool [B, D], non-zero = observed; the loss counts the observed pixels alone."""
         self._last_labels = labels
-        return base._targets_guard(self._need_engine().loss(images, eps, u, y_observed), images, targets)
+        return base._targets_guard(self._need_engine().loss(images, eps, u, y_observed, mask), images, targets)
 
-    def compute_loss(self, images, n_samples=None, labels=None, eps=None, u=None, y_observed=None):
+    def compute_loss(self, images, n_samples=None, labels=None, eps=None, u=None, y_observed=None, mask=None):
         e = self._need_engine()
         if n_samples is not None and n_samples != e.S:
             raise ValueError(f"model was created with n_samples={e.S}")
         self._last_labels = labels
-        return e.loss(images, eps, u, y_observed)
+        return e.loss(images, eps, u, y_observed, mask)
 
-    def iw_bound(self, images, n_samples, chunk=None):
+    def iw_bound(self, images, n_samples, chunk=None, mask=None):
         """Per-example importance-weighted bound at n_samples samples (the A15 bound compute_loss(n_samples=S) reports),
-        streamed in chunks of `chunk` samples: a [B] device tensor (Engine.iw_bound)."""
-        return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
+        streamed in chunks of `chunk` samples: a [B] device tensor (Engine.iw_bound).  mask: the bound on log p(x_observed)."""
+        return self._need_engine().iw_bound(images, n_samples, chunk, mask=mask)["bound"]
 
     def iw_bound_enum_y(self, images, n_samples, chunk=None):
         """Per-example importance-weighted bound with y summed out exactly over the K components (log p(x) + ln K for a
@@ -129,6 +136,10 @@ class TrainableGMVAE(GMVAE):
             out["sup_ce"], out["sup_acc"] = t[5] / t[6], t[7] / t[6]
         if e.weighted_objective:                   # (nll_scalar, kl_div_z and nent stay unweighted; elbo = -loss carries the weights)
             out["kl_weight"], out["y_weight"], out["y_floor_share"] = t[5] / t[4], t[6] / t[4], t[7] / t[4]
+        if e.pixel_mask:                           # (nll_scalar counts the observed pixels; the held-out ones per missing pixel)
+            if t[6].item() > 0:
+                out["imputation_nll"] = t[5] / t[6]
+            out["observed_share"] = t[7] / (t[6] + t[7])
         if self._last_labels is not None:
             d, ws = e._workspace(int(t[4].item()))
             out["cluster_acc"] = utils.cluster_acc(self.last_logits(), self._last_labels, self.mix_components)
@@ -155,9 +166,9 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                  hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
                  semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0,
-                 temperature_on_device=False, y_estimator="relaxed"):
+                 temperature_on_device=False, y_estimator="relaxed", pixel_mask=False):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
-    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator: Engine).  y_inference="marginal" trains and
+    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
     importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
     a checkpoint of any loads in the others."""
@@ -168,7 +179,8 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                     gen_bias_init=gen_bias_init, random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
                     y_inference=y_inference, grad_estimator=grad_estimator, semi_supervised=semi_supervised,
                     sup_weight=sup_weight, weighted_objective=weighted_objective, kl_weight=kl_weight, y_weight=y_weight,
-                    y_free_nats=y_free_nats, temperature_on_device=temperature_on_device, y_estimator=y_estimator)
+                    y_free_nats=y_free_nats, temperature_on_device=temperature_on_device, y_estimator=y_estimator,
+                    pixel_mask=pixel_mask)
     prior_gmm = base.ConditionalNormal(size=latent_size, hidden_layer_sizes=None,
                                        hidden_activation_fn=hidden_activation_fn, sigma_min=sigma_min,
                                        raw_sigma_bias=raw_sigma_bias, name="prior_gmm").bind(engine, L.NET_PRIOR_GMM)

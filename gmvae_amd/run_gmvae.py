@@ -74,6 +74,10 @@ def build_parser():
       "(0 = no annealing)")
     a("--y_estimator", default="relaxed", choices=["relaxed", "straight_through"], help="gmvae, --y_inference=gumbel: the "
       "step consumes the relaxed sample of y, or (straight_through) its one-hot argmax with the relaxed sample's gradient")
+    a("--missing_rate", type=float, default=0.0, help="train and eval with missing pixels: every pixel of every dataset row is "
+      "missing independently with this probability -- ONE fixed mask per row, the same in train and eval; the loss, the "
+      "gradients and --iw_samples count the observed pixels alone, the missing ones are scored as imputation_nll (0 = off)")
+    a("--missing_seed", type=int, default=0, help="seed of --missing_rate's masks")
     return p
 
 
@@ -128,6 +132,22 @@ def check_args(p, cfg):
         p.error("--temperature must be > 0; --temperature_min, --temperature_anneal_rate and --temperature_anneal_every >= 0")
     if cfg.temperature_anneal_rate > 0 and cfg.temperature_anneal_every > 0 and not cfg.temperature_min > 0:
         p.error("an annealed temperature needs a floor: --temperature_min must be > 0")
+    if not 0.0 <= cfg.missing_rate < 1.0:
+        p.error("--missing_rate must be in [0, 1)")
+    if cfg.missing_rate > 0:
+        if cfg.model == "gmvae" and cfg.y_inference != "gumbel":
+            p.error("--missing_rate is not available with --y_inference=marginal or marginal_iw")
+        if cfg.grad_estimator == "dreg":
+            p.error("--missing_rate is not available with --grad_estimator=dreg")
+        if cfg.labelled_per_class > 0:
+            p.error("--missing_rate is not available with --labelled_per_class")
+        if runners.weighted_flags(cfg):
+            p.error("--missing_rate is not available with --kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps")
+        if runners.temperature_flags(cfg) or cfg.y_estimator != "relaxed":
+            p.error("--missing_rate is not available with --temperature* or --y_estimator=straight_through")
+        if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
+            p.error("--missing_rate is not available with --iw_enum_samples, --posterior_samples or "
+                    "--component_posterior_samples (they would score the unobserved pixels): use --iw_samples")
     return cfg
 
 

@@ -117,6 +117,17 @@ def temperature_at(config, t: int) -> float:
     return max(tmin, t0 * math.exp(-r * n * (int(t) // n)))
 
 
+def missing_mask(config, split: str, n_rows: int, data_dim: int):
+    """--missing_rate p: the observation mask of a split, uint8 [n_rows, data_dim] (1 = observed), or None for p = 0.  ONE
+    fixed mask per dataset row, each pixel missing independently with probability p, drawn once from --missing_seed and the
+    split's name over the WHOLE split (before any rank's shard is cut): training and evaluation see the same mask for a row."""
+    p = float(getattr(config, "missing_rate", 0.0) or 0.0)
+    if p <= 0.0:
+        return None
+    rng = np.random.default_rng([int(getattr(config, "missing_seed", 0) or 0), 0 if split == "train" else 1])
+    return (rng.random((int(n_rows), int(data_dim)), dtype=np.float32) >= p).astype(np.uint8)
+
+
 def create_model(config, data_dim, weighted=None, temperature_on_device=None):
     """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5 (and temperature=1.0 unless
     --temperature says otherwise).
@@ -126,6 +137,7 @@ def create_model(config, data_dim, weighted=None, temperature_on_device=None):
     wobj = dict(weighted_objective=weighted_flags(config) if weighted is None else bool(weighted))
     yhead = dict(temperature_on_device=temperature_flags(config) if temperature_on_device is None else bool(temperature_on_device),
                  y_estimator=getattr(config, "y_estimator", "relaxed"))
+    pmask = dict(pixel_mask=float(getattr(config, "missing_rate", 0.0) or 0.0) > 0.0)      # (--missing_rate: train AND eval)
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
@@ -137,16 +149,16 @@ def create_model(config, data_dim, weighted=None, temperature_on_device=None):
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
                                   temperature=temperature_at(config, 0), random_seed=config.random_seed, n_samples=ns,
                                   y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge,
-                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj, **yhead)
+                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj, **yhead, **pmask)
     if temperature_flags(config) or yhead["y_estimator"] != "relaxed":
         raise ValueError("--temperature* and --y_estimator belong to the GMVAE's Gumbel-softmax draw: they need --model=gmvae")
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
-                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj)
+                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask)
     if config.model == "vae":
         return vae.create_vae(data_dim, config.latent_size, fcnet_hidden_sizes=hidden, sigma_min=0.0,
-                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj)
+                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask)
     raise ValueError(f"unknown model {config.model!r}")
 
 
@@ -231,7 +243,9 @@ def create_device_dataset(config, split="train", shuffle=True):
     a, b = parallel.shard_rows(pix.shape[0], rank, world)
     lpc = int(getattr(config, "labelled_per_class", 0) or 0)
     yobs = select_labelled(lab, lpc, config.random_seed or 0)[a:b] if lpc > 0 else None
-    return DeviceDataset(pix[a:b], lab[a:b], shuffle=shuffle, seed=(config.random_seed or 0) * 7919 + 17 + rank, y_observed=yobs)
+    pm = missing_mask(config, split, pix.shape[0], pix.shape[1] if pix.ndim == 2 else int(np.prod(pix.shape[1:])))
+    return DeviceDataset(pix[a:b], lab[a:b], shuffle=shuffle, seed=(config.random_seed or 0) * 7919 + 17 + rank, y_observed=yobs,
+                         pixel_mask=None if pm is None else pm[a:b])
 
 
 def _graph_steps(every: int, cap: int = 32) -> int:
@@ -323,8 +337,11 @@ def run_train(config):
     # temperature on the device (--temperature / --temperature_min / --temperature_anneal_rate / --temperature_anneal_every):
     # the same branch again -- the graph's temperatures are filled per launch from temperature_at
     ytd = eng.temperature_on_device
+    # pixel mask (--missing_rate): the same branch once more -- the graph's masks are gathered per launch by the batch's rows
+    pmk = eng.pixel_mask
     run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else
-                                                 "graph+weights" if wobj else "graph+temp" if ytd else "pipeline-graph")
+                                                 "graph+weights" if wobj else "graph+temp" if ytd else
+                                                 "graph+mask" if pmk else "pipeline-graph")
     run_train.temperature_log = []                          # temperature on the device: (0-based step index, temperature) of the
                                                             # LAST launch's steps, as placed in replay.y_temperature
     run_train.weight_log = []                               # weighted objective: (step, tail[5] / tail[4], tail[6] / tail[4]) of the
@@ -351,9 +368,10 @@ def run_train(config):
                 if ytd:
                     run_train.temperature_log = [(eng.global_step, temperature_at(config, eng.global_step))]
                     eng.set_temperature(run_train.temperature_log[0][1])
-                logs.append(eng.train_step(x, lr=lr, y_observed=yo).clone().view(1, -1))
+                mk = ds.pixel_mask[rows.long()] if pmk else None
+                logs.append(eng.train_step(x, lr=lr, y_observed=yo, mask=mk).clone().view(1, -1))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1 and not sup and not wobj and not ytd:
+            elif world == 1 and not sup and not wobj and not ytd and not pmk:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -373,6 +391,8 @@ def run_train(config):
                     binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
                     if sup:
                         replay.y_observed[i].copy_(ds.y_observed[last_rows.long()])
+                    if pmk:
+                        replay.pixel_mask[i].copy_(ds.pixel_mask[last_rows.long()])
                 if wobj:
                     rows_w = torch.tensor([objective_weights_at(config, eng.global_step + i) + (0.0,) for i in range(g)],
                                           dtype=torch.float32)
@@ -450,12 +470,17 @@ def run_train(config):
                         f"  y_floor_share {(tails[-1, 7] / tails[-1, 4]).item():.4f}")
             if ytd:                                         # (of the last step taken)
                 msg += f"  temperature {temperature_at(config, eng.global_step - 1):.4f}"
+            if pmk:                                         # (of the last step taken)
+                if tails[-1, 6].item() > 0:
+                    msg += f"  imputation_nll {(tails[-1, 5] / tails[-1, 6]).item():.4f}"
+                msg += f"  observed_share {(tails[-1, 7] / (tails[-1, 6] + tails[-1, 7])).item():.4f}"
             if sup:                                         # over the summary block's labelled examples (all ranks')
                 blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
                 if blk[1].item() > 0:
                     msg += f"  sup_acc {blk[2].item() / blk[1].item():.4f}  sup_ce {blk[0].item() / blk[1].item():.4f}"
             if config.model == "gmvae" and ds.labels is not None:
-                q = model.encoder_y(last_x).distribution.logits
+                # (--missing_rate: q(y|x) of what the step saw, m x)
+                q = model.encoder_y(last_x * ds.pixel_mask[last_rows.long()] if pmk else last_x).distribution.logits
                 acc = utils.cluster_acc(q, ds.labels[last_rows.long()], config.mixture_components)
                 msg += f"  cluster_acc {acc.item():.4f}"
             print(msg, flush=True)
@@ -487,6 +512,12 @@ def run_eval(config):
     if config.model == "gmvae" and temperature_flags(config):
         eng.set_temperature(temperature_at(config, eng.global_step))      # the schedule's value where training stopped
     tot = torch.zeros(5, device=eng.device)
+    # --missing_rate: the split's fixed masks (missing_mask), resident; a batch's rows are first .. first + B of the split
+    pmask_all, pm_tot = None, torch.zeros(3, dtype=torch.float64, device=eng.device)
+    if eng.pixel_mask:
+        data = _load_mnist(config.data_dir, config.split) if getattr(config, "data_dir", None) else None
+        n_split = data[0].shape[0] if data is not None else int(getattr(config, "synthetic_size", 8192))
+        pmask_all = torch.from_numpy(missing_mask(config, config.split, n_split, data_dim)).to(eng.device)
     ref_sum, n_batches, codes, labs = 0.0, 0, [], []
     class_hits = torch.zeros(2, dtype=torch.float64, device=eng.device)      # GMVAE: (argmax q(y|x) == label, examples)
     # --iw_samples N: the importance-weighted bound at N samples per example, streamed in chunks; row0 = the example's index in
@@ -507,12 +538,14 @@ def run_eval(config):
             po = eng.posterior_y(images, py_n, chunk=iw_chunk, row0=first)
             py_rows.append(po["log_post"])
             py_stats.append(torch.stack([po["bound"], po["entropy"], po["kl_q_post"], po["ess"]], dim=1))
+        mk = None if pmask_all is None else pmask_all[first:first + images.shape[0]]
         if iw_n > 0:
-            iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first)["bound"])
+            iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
         if ie_n > 0:
             ie_rows.append(eng.iw_bound_enum_y(images, ie_n, chunk=iw_chunk, row0=first)["bound"])
-        o = eng.forward(images)
+        o = eng.forward(images, mask=mk)
         tot += o["tail"][:5]
+        pm_tot += o["tail"][5:8].double()
         ref_sum += (o["tail"][0] / o["tail"][4]).item()
         n_batches += 1
         # z = model.transform(flat_inputs) (runners.py:274): the VAE's MEAN code (vae.py:108-114), the GMVAE's SAMPLED
@@ -523,7 +556,7 @@ def run_eval(config):
             z = o["z"].view(B, eng.rows_per_x // eng.K, eng.K, eng.Lz)[:, 0]
             codes.append(z[torch.arange(B, device=eng.device), o["logits"].argmax(dim=1)])
         else:
-            codes.append(o["z"] if config.model == "gmvae" else model.transform(images))
+            codes.append(o["z"] if config.model == "gmvae" else model.transform(images if mk is None else images * mk))
         labs.append(labels)
         if config.model == "gmvae":
             class_hits[0] += (o["logits"].argmax(dim=1) == labels.to(eng.device)).sum()
@@ -538,6 +571,7 @@ def run_eval(config):
         parallel.all_reduce_flat(tot)
         parallel.all_reduce_flat(iw_sum)
         parallel.all_reduce_flat(class_hits)
+        parallel.all_reduce_flat(pm_tot)
         if ie_n > 0:
             parallel.all_reduce_flat(ie_sum)
         if py_n > 0:
@@ -552,6 +586,11 @@ def run_eval(config):
         # the share of examples whose most probable component under q(y|x) IS their label -- no mode matching: meaningful
         # where training saw labels (--labelled_per_class), chance level otherwise
         res[f"{config.split}/class_acc_q"] = class_hits[0].item() / max(class_hits[1].item(), 1.0)
+    if eng.pixel_mask:
+        # loss_per_example and nll above count the observed pixels alone; the held-out ones are scored per missing pixel
+        if pm_tot[1].item() > 0:
+            res[f"{config.split}/imputation_nll"] = pm_tot[0].item() / pm_tot[1].item()
+        res[f"{config.split}/observed_share"] = pm_tot[2].item() / (pm_tot[1].item() + pm_tot[2].item())
     if iw_n > 0:
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:

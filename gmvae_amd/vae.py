@@ -42,6 +42,12 @@ class VAE:
             z = self.generate_samples(num_samples)
         return self.decoder(z).mean(name="sample_images")
 
+    def impute(self, images, mask):
+        """Fills in the missing pixels: mask * images + (1 - mask) * reconstruct_images(mask * images) -- the observed pixels
+        exactly as given, the others the decoder's mean from the zero-imputed input the networks were trained on (a model
+        created with pixel_mask=True).  A float tensor of the images' shape."""
+        return base.impute(self, images, mask)
+
     def transform(self, inputs):
         """MEAN latent code (scripts/vae.py:108-114)."""
         return self.encoder(inputs).mean(name="code")
@@ -64,22 +70,23 @@ class TrainableVAE(VAE):
             raise RuntimeError("run_model needs the fused HIP engine: build the model with create_vae()")
         return self._engine
 
-    def run_model(self, images, targets, eps=None):
+    def run_model(self, images, targets, eps=None, mask=None):
         """Batch-mean loss = nll + kl_div_z (scripts/vae.py:153-188); ELBO = -loss.
         ``targets`` must be ``images`` (every reference call site passes the same
-        tensor, scripts/runners.py:130).  eps: optional N(0,1) noise [B*S, L]."""
-        return base._targets_guard(self._need_engine().loss(images, eps, None), images, targets)
+        tensor, scripts/runners.py:130).  eps: optional N(0,1) noise [B*S, L].  mask (a model created with pixel_mask=True):
+        uint8 / bool [B, D], non-zero = observed; the loss counts the observed pixels alone (Engine)."""
+        return base._targets_guard(self._need_engine().loss(images, eps, None, mask=mask), images, targets)
 
-    def compute_loss(self, images, n_samples=None, eps=None):
+    def compute_loss(self, images, n_samples=None, eps=None, mask=None):
         e = self._need_engine()
         if n_samples is not None and n_samples != e.S:
             raise ValueError(f"model was created with n_samples={e.S}")
-        return e.loss(images, eps, None)
+        return e.loss(images, eps, None, mask=mask)
 
-    def iw_bound(self, images, n_samples, chunk=None):
+    def iw_bound(self, images, n_samples, chunk=None, mask=None):
         """Per-example IWAE estimate of log p(x) at n_samples samples (Burda et al.), streamed in chunks of `chunk` samples:
-        a [B] device tensor (Engine.iw_bound)."""
-        return self._need_engine().iw_bound(images, n_samples, chunk)["bound"]
+        a [B] device tensor (Engine.iw_bound).  mask: the bound on log p(x_observed)."""
+        return self._need_engine().iw_bound(images, n_samples, chunk, mask=mask)["bound"]
 
     def posterior_component(self, images, n_samples, chunk=None):
         """ln p(k | x) over the components of the learned mixture prior (mixture_components > 1), by importance sampling with
@@ -98,6 +105,10 @@ class TrainableVAE(VAE):
         out = {"nll_scalar": t[1] / t[4], "kl_div_z": t[2] / t[4], "elbo": -t[0] / t[4]}
         if e.weighted_objective:                   # (nll_scalar and kl_div_z stay unweighted; elbo = -loss carries the weights)
             out["kl_weight"], out["y_weight"], out["y_floor_share"] = t[5] / t[4], t[6] / t[4], t[7] / t[4]
+        if e.pixel_mask:                           # (nll_scalar counts the observed pixels; the held-out ones per missing pixel)
+            if t[6].item() > 0:
+                out["imputation_nll"] = t[5] / t[6]
+            out["observed_share"] = t[7] / (t[6] + t[7])
         return out
 
     @property
@@ -114,8 +125,9 @@ class TrainableVAE(VAE):
 def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                random_seed=None, n_samples=1, grad_estimator="standard", weighted_objective=False, kl_weight=1.0,
-               y_weight=1.0, y_free_nats=0.0):
-    """Factory with the signature of scripts/vae.py:191-200 (+ n_samples, the
+               y_weight=1.0, y_free_nats=0.0, pixel_mask=False):
+    """Factory with the signature of scripts/vae.py:191-200 (+ pixel_mask: run_model / compute_loss / iw_bound take mask=,
+    Engine; + n_samples, the
     IWAE extension of SURVEY.md A15; 1 == the reference; + grad_estimator: "dreg" = the doubly
     reparameterised gradient for the encoder, Engine; + weighted_objective, kl_weight, y_weight, y_free_nats: the KL weight of
     Engine's weighted objective -- the VAE family has no y term, so y_weight and y_free_nats are ignored)."""
@@ -126,7 +138,7 @@ def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=
                     sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, gen_bias_init=gen_bias_init,
                     random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
                     grad_estimator=grad_estimator, weighted_objective=weighted_objective, kl_weight=kl_weight,
-                    y_weight=y_weight, y_free_nats=y_free_nats)
+                    y_weight=y_weight, y_free_nats=y_free_nats, pixel_mask=pixel_mask)
     if mixture_components > 1:
         def prior():
             v = engine.views()

@@ -257,8 +257,45 @@ enum { GMVAE_SCHED_SAFE = 1,
         * posteriors mask it off -- for a straight-through model the estimators that match its one-hot y are
         * gmvae_iw_bound_enum_y and gmvae_posterior_y.  The pipeline graph takes it (without GMVAE_Y_TEMP_DEV).  General
         * schedule; gmvae_step_schedule appends "+st" behind "+temp".  No atomics: eager and captured steps give the same bits. */
-       GMVAE_Y_STRAIGHT_THROUGH = 256 };
-#define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) a workspace holds: the most steps of one train graph */
+       GMVAE_Y_STRAIGHT_THROUGH = 256,
+       /* per-example observation mask (all three models; the GMVAE with the Gumbel draw only; any S >= 1, any hidden_act, with
+        * or without gen_bias_vec, any D >= 1): m_bd in {0, 1}, uint8 with x's layout and stride, OBSERVED iff the byte is
+        * non-zero; row r = b S + s belongs to example b.
+        *   networks that read x (encoder_y, encoder_gmm, encoder, and their first layers' weight gradients) read
+        *     x~_bd = m_bd x_bd                                         (zero imputation)
+        *   logpx_r = sum_d m_bd (x_bd lambda_rd - softplus lambda_rd)   (a bound on log p(x_observed))
+        *   g_rd    = m_bd (sigmoid(lambda_rd) - x_bd)                   (the gradient at the logits)
+        *   hid_r   = sum_d (1 - m_bd)(x_bd lambda_rd - softplus lambda_rd)   (held out: in no gradient, not part of the loss)
+        * and everything downstream -- log q, log p, nent, the IWAE weights, every backward GEMM, TF-Adam -- is the step's own.
+        * x at a missing pixel is read by hid alone: a caller who knows the truth there gets the imputation score, one who does
+        * not a meaningless but finite tail[5]; the loss, the gradients and tail[0..4] do not depend on it, bit for bit.
+        * Tail: [0..4] as without the bit, on the masked terms; [5] sum_b mean_s (-hid_bs); [6] sum_b sum_d (1 - m_bd), the missing
+        * pixels; [7] sum_b sum_d m_bd, the observed ones (both exact while B D < 2^24); the data-parallel all-reduce sums all
+        * eight slots: [5] / [6] is the imputation -log-likelihood per missing pixel.  gmvae_forward's row_terms carry the masked
+        * logpx, and log w is built from it.
+        * The workspace grows BEHIND every other buffer by regions rounded up to 256 bytes each:
+        *   "pixel_mask"  uint8 [GMVAE_LABEL_SLOTS][r256(B D)], r256 = rounded up to a multiple of 256: one mask per slot
+        *   (unnamed)     uint8 [B D]: x~;  float [R][nparts]: the held-out partials beside the epilogue's own;  float [B][2]: the counts
+        * (gmvae_workspace_offset answers for the name; GMVAE_E_NET without the bit).  The CALLER writes "pixel_mask"; the library
+        * only reads it.  A zeroed workspace means "nothing observed": a caller fills the slots before the first step
+        * (gmvae_amd.Engine does: all ones).
+        * Who reads which slot: gmvae_step, gmvae_forward, gmvae_dp_step, gmvae_iw_bound, the bench and profile loops read slot 0;
+        * step i of gmvae_train_graph_create's and gmvae_dp_graph_create's graph reads slot i (n_steps > GMVAE_LABEL_SLOTS:
+        * GMVAE_E_DIMS); gmvae_train_graph_create_pipeline refuses the bit (GMVAE_E_DIMS).  gmvae_iw_bound honours it -- the bound
+        * on log p(x_observed), through the general chunk passes at every size, noise keying unchanged, tail[5..7] = 0 --;
+        * gmvae_iw_bound_enum_y, gmvae_posterior_y and gmvae_posterior_component return GMVAE_E_DIMS (masking the bit off would
+        * silently score the unobserved pixels).
+        * REFUSED (GMVAE_E_DIMS from gmvae_workspace_bytes and every entry point that runs or sizes a step, before any launch)
+        * together with GMVAE_OBJ_MARGINAL_Y, GMVAE_OBJ_MARGINAL_Y_IW, GMVAE_GRAD_DREG, GMVAE_OBJ_LABELS, GMVAE_OBJ_WEIGHTS,
+        * GMVAE_Y_TEMP_DEV or GMVAE_Y_STRAIGHT_THROUGH.
+        * Every step with the bit takes the general schedule -- no one-launch, skinny, chain, evalf or plane path -- and
+        * gmvae_step_schedule gives "general+mask".  At the config-5 sizes, where the step without the bit runs its top decoder
+        * layer as bf16 piece products ("+planes"), the masked step runs those GEMMs on the fp32 MFMA loop: the sizes then
+        * multiply there.  The masked Bernoulli epilogue (fp32 C, interior and edge tiles) keeps the observed and the held-out
+        * sums as two chains; nothing assumes D % 4 == 0 (the 4-byte interior path's alignment conditions extend to the mask).
+        * No atomics: eager and captured steps give the same bits. */
+       GMVAE_OBJ_PIXEL_MASK = 512 };
+#define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) / masks (GMVAE_OBJ_PIXEL_MASK) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
 /* One tensor of the flat parameter buffer.  Names are the reference's TF
@@ -575,7 +612,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -590,7 +627,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);

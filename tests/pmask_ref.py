@@ -1,0 +1,182 @@
+"""fp64 statement of the objective under a per-example observation mask (include/gmvae_hip.h GMVAE_OBJ_PIXEL_MASK), in torch
+with autograd -- test infrastructure, the checker of tests/test_pmask*.py.
+
+m_bd in {0, 1} (observed iff non-zero), rows r = b S + s:
+    the networks that read x (encoder_y, encoder_gmm, encoder) read x~ = m x               (zero imputation)
+    logpx_r = sum_d m_bd (x_bd lambda_rd - softplus lambda_rd)                              (observed pixels)
+    hid_r   = sum_d (1 - m_bd)(x_bd lambda_rd - softplus lambda_rd)                         (held out: detached, not in the loss)
+    log w_r = logpx_r + logp_r - logq_r - nent_b,   L_b = -(logsumexp_s log w_bs - ln S)    (oracle.forward's, on the masked logpx)
+Parameters as oracle.unpack gives them; per-net ReLU masks as oracle.loss_and_grads takes them.  The module also holds the
+mask recipe and the shapes of the device tests."""
+import dataclasses
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import oracle as O
+from ymarg_ref import LOG_2PI, _mlp, _mvn_logprob
+
+
+def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, mask=None, relu_masks=None, encoder_sees_mask=True):
+    """model: oracle.MODEL_*; x uint8 [B, D]; eps [B S, L]; u [B S, K] (GMVAE only); mask uint8 / bool [B, D] (None: all observed).
+    encoder_sees_mask=False is the WRONG variant "likelihood masked, encoder fed the unmasked x" (tests/test_pmask_cpu.py shows
+    that the gates tell it apart).  Returns (C, g): C = dict(loss, nll, kl, nent -- batch means, nll / kl averaged over s --,
+    hid = sum_b mean_s(-hid_bs), n_missing, n_observed, rows [R, 4] = logpx, logq, logp, log w, bound [B], pre = per-net
+    pre-activations) and g = {name: d loss / d param} (loss = mean_b L_b), all float64 numpy."""
+    rm = relu_masks or {}
+    t = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in p.items()}
+    B, S, K, L = x.shape[0], d.S, d.K, d.L
+    R = B * S
+    nl = len(d.hidden) + 1
+    c, smin = float(d.raw_sigma_bias), float(d.sigma_min)
+    xf = torch.tensor(np.asarray(x), dtype=torch.float64)
+    mf = torch.ones_like(xf) if mask is None else torch.tensor((np.asarray(mask) != 0).astype(np.float64))
+    xe = mf * xf if encoder_sees_mask else xf
+    eps = torch.tensor(np.asarray(eps, np.float64).reshape(R, L))
+    gm = model == O.MODEL_GMVAE
+    nent = torch.zeros(B, dtype=torch.float64)
+    if gm:
+        pre = {"encoder_y": [], "encoder_gmm": [], "decoder": []}
+        logits = _mlp(t, "encoder_y", nl, xe, d.act, rm.get("encoder_y"), pre["encoder_y"])
+        lnq = torch.log_softmax(logits, dim=1)
+        nent = (lnq.exp() * lnq).sum(dim=1)
+        ut = torch.tensor(np.asarray(u, np.float64).reshape(R, K))
+        y = torch.softmax((logits.repeat_interleave(S, dim=0) - torch.log(-torch.log(ut))) / float(d.temperature), dim=1)
+        pp = y @ t["prior_gmm_fcnet/linear_0/w"] + t["prior_gmm_fcnet/linear_0/b"]
+        qp = _mlp(t, "encoder_gmm", nl, torch.cat([xe.repeat_interleave(S, dim=0), y], dim=1), d.act, rm.get("encoder_gmm"),
+                  pre["encoder_gmm"])
+    else:
+        pre = {"encoder": [], "decoder": []}
+        qp = _mlp(t, "encoder", nl, xe, d.act, rm.get("encoder"), pre["encoder"]).repeat_interleave(S, dim=0)
+    mu_q, sig_q = qp[:, :L], torch.clamp(F.softplus(qp[:, L:] + c), min=smin)
+    z = mu_q + sig_q * eps
+    logq = _mvn_logprob(z, mu_q, sig_q)
+    if gm:
+        mu_p, sig_p = pp[:, :L], torch.clamp(F.softplus(pp[:, L:] + c), min=smin)
+        logp = _mvn_logprob(z, mu_p, sig_p)
+    elif model == O.MODEL_VAE:
+        logp = (-0.5 * z * z - 0.5 * LOG_2PI).sum(dim=1)
+    else:
+        loc, s = t["loc"], F.softplus(t["raw_scale_diag"])
+        lnw = torch.log_softmax(t["mixture_logits"], dim=0)
+        tt = (z[:, None, :] - loc[None]) / s[None]
+        lnN = (-0.5 * tt * tt - 0.5 * LOG_2PI).sum(dim=2) - torch.log(s).sum(dim=1)[None]
+        logp = torch.logsumexp(lnw[None] + lnN, dim=1)
+    lam = _mlp(t, "decoder", nl, z, d.act, rm.get("decoder"), pre["decoder"])
+    lam = lam + torch.as_tensor(np.asarray(d.gen_bias_init, np.float64))
+    el = xf.repeat_interleave(S, dim=0) * lam - F.softplus(lam)
+    mr = mf.repeat_interleave(S, dim=0)
+    logpx = (mr * el).sum(dim=1)
+    hid = ((1.0 - mr) * el).sum(dim=1).detach()
+    logw = logpx + logp - logq - nent.repeat_interleave(S)
+    bound = torch.logsumexp(logw.view(B, S), dim=1) - math.log(S)
+    loss = -bound.mean()
+    loss.backward()
+    g = {k: v.grad.numpy().copy() if v.grad is not None else np.zeros_like(v.detach().numpy()) for k, v in t.items()}
+    C = {"loss": loss.item(), "nll": -logpx.mean().item(), "kl": (logq - logp).mean().item(), "nent": nent.mean().item(),
+         "hid": -hid.view(B, S).mean(dim=1).sum().item(), "n_missing": float((1.0 - mf).sum().item()),
+         "n_observed": float(mf.sum().item()), "bound": bound.detach().numpy(), "pre": pre,
+         "rows": torch.stack([logpx, logq, logp, logw], dim=1).detach().numpy()}
+    return C, g
+
+
+# ---- the mask recipe of every case
+RATE = 0.3                       # each pixel missing independently at this rate, then the four conditions are forced
+
+
+def dead_columns(D):
+    """The two columns missing in EVERY row: the last one and one inside the first column quad."""
+    return (2 % D, D - 1) if D > 2 else (D - 1,)
+
+
+def live_column(D):
+    """The column observed from row 2 on."""
+    return 1 if D > 3 else 0
+
+
+def make_mask(B, D, seed=77, single_pixel_row=None):
+    """uint8 [B, D], 1 = observed.  Drawn at RATE from `seed`, then: row 0 observes nothing; row 1 everything but the dead
+    columns; the dead columns are missing in every row; live_column(D) is observed from row 2 on.  single_pixel_row (>= 2): that
+    row observes live_column(D) alone."""
+    assert B >= 3
+    m = (np.random.default_rng(seed).random((B, D)) >= RATE).astype(np.uint8)
+    m[1, :] = 1
+    m[2:, live_column(D)] = 1
+    if single_pixel_row is not None:
+        assert single_pixel_row >= 2
+        m[single_pixel_row, :] = 0
+        m[single_pixel_row, live_column(D)] = 1
+    m[:, list(dead_columns(D))] = 0
+    m[0, :] = 0
+    return m
+
+
+def check_mask(m):
+    """The recipe's four conditions (tests/test_pmask_cpu.py asserts them for every case)."""
+    B, D = m.shape
+    dead = list(dead_columns(D))
+    assert m[0].sum() == 0
+    assert (m[:, dead] == 0).all() and len(dead) >= 2 and D - 1 in dead
+    assert m[1].sum() == D - len(dead)
+    assert (m[2:, live_column(D)] == 1).all()
+    assert live_column(D) not in dead
+
+
+def flip_missing(x, m):
+    """x with every missing pixel flipped: what the device tests feed, so that any use of x there shows."""
+    return np.where(m != 0, x, 1 - x).astype(np.uint8)
+
+
+# ---- the shapes of tests/test_pmask.py: (model name, Dims, B) and the options of setup()
+@dataclasses.dataclass(frozen=True)
+class Case:
+    mname: str
+    d: object
+    B: int
+    bias_vec: bool = False       # gen_bias_init as a [D] vector (GmvaeDims::gen_bias_vec)
+    lam_scale: float = None      # the decoder's last layer scaled so that max |lambda| is about this
+    single_pixel_row: int = None
+
+
+CASES = {
+    "vae": Case("vae", O.Dims(D=100, L=5, K=1, hidden=(24,)), 9),
+    "vae_gmp": Case("vae_gmp", O.Dims(D=100, L=5, K=3, hidden=(24,), sigma_min=0.5), 9),
+    "gumbel": Case("gmvae", O.Dims(D=100, L=5, K=7, hidden=(24, 24), temperature=0.7), 8),
+    "gmvae-s3": Case("gmvae", O.Dims(D=96, L=4, K=6, hidden=(16,), S=3), 4),
+    "vae-s3": Case("vae", O.Dims(D=96, L=4, K=1, hidden=(16,), S=3), 4),
+    "gumbel-d99": Case("gmvae", O.Dims(D=99, L=5, K=7, hidden=(24,)), 5),                  # unaligned rows: the element path
+    "gumbel-784": Case("gmvae", O.Dims(D=784, L=64, K=10, hidden=(64,)), 16),              # interior tiles + the 16-column last tile
+    "vae_gmp-tanh": Case("vae_gmp", O.Dims(D=100, L=5, K=3, hidden=(24,), act="tanh"), 9),
+    "gumbel-bias-vec": Case("gmvae", O.Dims(D=100, L=5, K=7, hidden=(24,)), 8, bias_vec=True),
+    "vae-saturated": Case("vae", O.Dims(D=100, L=5, K=1, hidden=(24,)), 9, lam_scale=60.0, single_pixel_row=3),
+}
+
+
+def setup(name, seed=0):
+    """(model id, Dims, p as the device sees it, flat fp32, x with the missing pixels flipped, eps, u, mask, the unflipped x)."""
+    c = CASES[name]
+    model = O.MODEL_NAMES[c.mname]
+    d = c.d
+    rng = np.random.default_rng(seed)
+    if c.bias_vec:
+        d = dataclasses.replace(d, gen_bias_init=np.linspace(-1.5, 1.5, d.D).astype(np.float32))
+    p = O.init_params(model, d, rng)
+    x, eps, u = O.make_inputs(d, c.B, model)
+    m = make_mask(c.B, d.D, single_pixel_row=c.single_pixel_row)
+    if c.lam_scale:
+        nl = len(d.hidden)
+        wn, bn = f"decoder_fcnet/linear_{nl}/w", f"decoder_fcnet/linear_{nl}/b"
+        z = _decoder_logits(model, d, p, x, eps, u, m)
+        f = c.lam_scale / np.abs(z).max()
+        p = dict(p)
+        p[wn], p[bn] = p[wn] * f, p[bn] * f
+    flat = O.pack(model, d, p, np.float32)
+    p32 = O.unpack(model, d, flat.astype(np.float64))
+    return model, d, p32, flat, flip_missing(x, m), eps, (u if model == O.MODEL_GMVAE else None), m, x
+
+
+def _decoder_logits(model, d, p, x, eps, u, m):
+    """The decoder's logits of the masked forward (oracle.forward on x~: the networks that read x see m x)."""
+    return O.forward(model, d, p, (x * (m != 0)).astype(np.uint8), eps, u)["lam"]
