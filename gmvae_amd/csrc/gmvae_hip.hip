@@ -82,6 +82,13 @@ static bool y_head_bits(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_Y_T
 // GMVAE_OBJ_PIXEL_MASK: a per-example observation mask (pmask.hpp: x~ = m x for every network that reads x, the masked Bernoulli
 // epilogue of gemm.hpp, pmask_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes
 static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_PIXEL_MASK) != 0; }
+// The per-step inputs -- label sets, weight rows, temperatures, masks: each a read-only workspace region of GMVAE_LABEL_SLOTS
+// slots that the CALLER writes.  A step reads slot StepArgs::slot of every region its dims carry: 0 from the eager entry
+// points, i for step i of a train graph, which therefore holds at most GMVAE_LABEL_SLOTS steps; the pipeline graph, which
+// gathers its batches by index and has no gather for them, refuses the four bits.
+static bool step_inputs(const GmvaeDims& d) {
+  return (d.sched_flags & (GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS | GMVAE_Y_TEMP_DEV | GMVAE_OBJ_PIXEL_MASK)) != 0;
+}
 // compute units of the CURRENT device (cached per device id; 256 on an unpartitioned MI355X): the hand-offs inside a launch
 // need every workgroup of the grid resident at once, one per CU
 static int device_cus() {
@@ -987,10 +994,7 @@ struct StepArgs {
   int span_slot = 0;           // ... into this slot of WS::spans (two consecutive steps can be stamped)
   bool dp_images = false;      // data-parallel graph: the Adam launch after the all-reduce scatters the weight images
   float* tail_log = nullptr;   // train graph: this step's slot of the per-step tail log (may be null)
-  int label_slot = 0;          // GMVAE_OBJ_LABELS: which of the workspace's label sets the step reads (step i of a train graph: i)
-  int weights_slot = 0;        // GMVAE_OBJ_WEIGHTS: which row of the workspace's "obj_weights" the step reads (likewise)
-  int temp_slot = 0;           // GMVAE_Y_TEMP_DEV: which float of the workspace's "y_temperature" the step reads (likewise)
-  int mask_slot = 0;           // GMVAE_OBJ_PIXEL_MASK: which of the workspace's masks the step reads (likewise)
+  int slot = 0;                // which slot of the per-step inputs' regions the step reads (step_inputs; step i of a train graph: i)
   bool iw_chunk = false;       // a chunk pass of gmvae_iw_bound: iw_tail writes the tail, [5..7] = 0 -- no pmask_tail
 };
 
@@ -2125,16 +2129,15 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (!a.backward && evalf_ok(d, model) && w.ev_img) return run_eval_fused(cx, a, L, w);
   if (fused_ok(d, model) && !a.z_out && !a.y_out && !a.logits_out)
     return run_step_fused(cx, a, L, w, eps, u, ge, gu);
+  if (step_inputs(d) && (a.slot < 0 || a.slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   // GMVAE_Y_TEMP_DEV: this step's temperature slot (null: T by value); GMVAE_Y_STRAIGHT_THROUGH: w.y_soft is carved
-  if (y_head_bits(d) && (!gm || marg || (y_temp_dev(d) && (!w.y_temperature || a.temp_slot < 0 || a.temp_slot >= GMVAE_LABEL_SLOTS)) ||
-                         (y_straight(d) && !w.y_soft)))
-    return GMVAE_E_DIMS;
-  const float* const ytau = y_temp_dev(d) ? w.y_temperature + a.temp_slot : nullptr;
+  if (y_head_bits(d) && (!gm || marg || (y_temp_dev(d) && !w.y_temperature) || (y_straight(d) && !w.y_soft))) return GMVAE_E_DIMS;
+  const float* const ytau = y_temp_dev(d) ? w.y_temperature + a.slot : nullptr;
   // GMVAE_OBJ_PIXEL_MASK: this step's mask; xin = x~ = m x is what the first layers and their weight gradients read, a.x itself
   // only the Bernoulli epilogue's target
   const bool pmask = pixel_mask(d);
-  if (pmask && (marg || !w.pixel_mask || !w.xm || !w.hpart || !w.mcnt || a.mask_slot < 0 || a.mask_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
-  const unsigned char* const pm = pmask ? w.pixel_mask + (size_t)a.mask_slot * (((size_t)B * D + 255) / 256 * 256) : nullptr;
+  if (pmask && (marg || !w.pixel_mask || !w.xm || !w.hpart || !w.mcnt)) return GMVAE_E_DIMS;
+  const unsigned char* const pm = pmask ? w.pixel_mask + (size_t)a.slot * (((size_t)B * D + 255) / 256 * 256) : nullptr;
   const uint8_t* const xin = pmask ? w.xm : a.x;
   if (pmask) {
     hipLaunchKernelGGL(pmask_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, pm, w.xm, w.mcnt, B, D);
@@ -2440,12 +2443,12 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
   const float* rwS = ((S > 1 || marg) && a.backward) ? w.rw : nullptr;
   const bool sup = sup_labels(d) && marg && !enum_chunk;
-  if (sup && (!w.labels || a.label_slot < 0 || a.label_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  if (sup && !w.labels) return GMVAE_E_DIMS;
   // GMVAE_OBJ_WEIGHTS (S == 1: check_weight_dims): this step's (beta_z, beta_y, lambda, 0); rwK = beta_z rw stands in rw's place
   // wherever the KL part is differentiated
   const bool wobj = obj_weights(d);
-  if (wobj && (!w.obj_weights || d.S != 1 || enum_chunk || a.weights_slot < 0 || a.weights_slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
-  const float* const wts = wobj ? w.obj_weights + 4 * (size_t)a.weights_slot : nullptr;
+  if (wobj && (!w.obj_weights || d.S != 1 || enum_chunk)) return GMVAE_E_DIMS;
+  const float* const wts = wobj ? w.obj_weights + 4 * (size_t)a.slot : nullptr;
   const float* const rwK = (wobj && a.backward) ? w.rwk : rwS;
   if (wobj && marg) {           // the per-example terms over the K rows of each batch row, the KL terms weighted
     hipLaunchKernelGGL(ymarg_wobj_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits, wts,
@@ -2459,7 +2462,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
     rowk(cx, "wobj_rows");
   } else if (sup) {                    // GMVAE_OBJ_LABELS: the per-example terms with observed components clamping y (any S >= 1)
     hipLaunchKernelGGL(ymarg_sup_rows, dim3((B + 3) / 4), dim3(256), 0, st, w.part, nparts, w.logq, w.logp, w.logits,
-                       w.labels + (size_t)a.label_slot * pad4((uint64_t)B), w.sup_weight, w.logpx, w.logw, w.lw64, a.row_terms,
+                       w.labels + (size_t)a.slot * pad4((uint64_t)B), w.sup_weight, w.logpx, w.logw, w.lw64, a.row_terms,
                        a.backward ? w.rw : (float*)nullptr, a.backward ? w.vs : (float*)nullptr, w.dlogits, w.nent, w.pb,
                        w.sup_trip, B, d.S, K);
     rowk(cx, "ymarg_sup_rows");
@@ -3105,7 +3108,7 @@ int gmvae_step(const GmvaeDims* dims, int model, const uint8_t* x, const float* 
 static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v,
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float b1,
                           float b2, float eps_, hipStream_t st, bool imgs_ready = false, float* tail_log = nullptr,
-                          int label_slot = 0) {
+                          int slot = 0) {
   Ctx cx;
   cx.st = st;
   StepArgs a = {dims, model, x, nullptr, nullptr, params, grads, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
@@ -3113,7 +3116,7 @@ static int step_with_adam(const GmvaeDims* dims, int model, const uint8_t* x, fl
   a.adam_p = params; a.adam_m = m; a.adam_v = v; a.lr = lr; a.beta1 = b1; a.beta2 = b2; a.epsilon = eps_;
   a.imgs_ready = imgs_ready;
   a.tail_log = tail_log;
-  a.label_slot = a.weights_slot = a.temp_slot = a.mask_slot = label_slot;    // (step i of a train graph: label set i, weight row i, temperature i, mask i)
+  a.slot = slot;
   return run_step(cx, a);
 }
 
@@ -3712,12 +3715,7 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
                               uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2, float epsilon,
                               float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
-  // GMVAE_OBJ_LABELS: step i reads label set i of the workspace; the pipeline graph gathers its batches by index and has no
-  // label gather
-  // (GMVAE_OBJ_WEIGHTS likewise: step i reads weight row i)
-  // (GMVAE_Y_TEMP_DEV likewise: step i reads temperature i)
-  // (GMVAE_OBJ_PIXEL_MASK likewise: step i reads mask i)
-  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims) || pixel_mask(*dims)) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  if (step_inputs(*dims) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;      // (step i reads slot i)
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3968,7 +3966,7 @@ int gmvae_comm_destroy(void* comm) {
 static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, float* params, float* m, float* v, float* grads,
                         void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1, float beta2,
                         float epsilon, void* comm, hipStream_t st, bool in_graph, bool imgs_ready, float* tail_log = nullptr,
-                        int span_slot = -1, Prof* prof = nullptr, int label_slot = 0) {
+                        int span_slot = -1, Prof* prof = nullptr, int slot = 0) {
   if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !comm || !g_rccl.h || !step_dev) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace)) return GMVAE_E_ALIGN;
@@ -3992,7 +3990,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   a.dp_images = scatter;
   a.imgs_ready = scatter && imgs_ready;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
-  a.label_slot = a.weights_slot = a.temp_slot = a.mask_slot = label_slot;
+  a.slot = slot;
   cx.prof = prof;
   int rc = run_step(cx, a);
   if (rc) return rc;
@@ -4139,7 +4137,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float* grads, void* workspace, uint64_t seed, uint64_t* step_dev, float lr, float beta1,
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
-  if ((sup_labels(*dims) || obj_weights(*dims) || y_temp_dev(*dims) || pixel_mask(*dims)) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads label set / weight row / temperature / mask i)
+  if (step_inputs(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads slot i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

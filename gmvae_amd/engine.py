@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -102,6 +102,57 @@ def check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weight
         raise ValueError("pixel_mask=True is not available with temperature_on_device=True")
     if y_estimator != "relaxed":
         raise ValueError(f"pixel_mask=True is not available with y_estimator={y_estimator!r}")
+
+
+def _check_labels(engine, y_observed, B):
+    if y_observed.dtype.is_floating_point or y_observed.dtype == torch.bool or y_observed.numel() != B:
+        raise ValueError(f"y_observed must be an int tensor of {B} observed components (-1: unlabelled)")
+    return y_observed
+
+
+def _check_mask(engine, mask, B):
+    mask = mask.to(engine.device)
+    if mask.dtype.is_floating_point or mask.numel() != B * engine.D:
+        raise ValueError(f"mask must be a uint8 / bool tensor [{B}, {engine.D}] (non-zero: observed)")
+    return mask != 0
+
+
+class StepInput(NamedTuple):
+    """A per-step side input of the training step (DESIGN.md "Per-step inputs"): a read-only workspace region of LABEL_SLOTS
+    slots.  Step i of a train graph reads slot i; every eager entry writes slot 0 before it runs; a captured graph hands the
+    caller the view [:n_steps] of the region as replay.<replay>."""
+    option: str                             # the Engine attribute (and constructor argument) that enables it
+    bit: int                                # the sched_flags bit the dims carry for a step to read it
+    region: str                             # the workspace region (gmvae_workspace_offset)
+    replay: str                             # the attribute of a captured graph's replay
+    dtype: torch.dtype
+    stride: Callable[[int, int], int]       # (B, D) -> elements from one slot to the next
+    shape: Callable[[int, int], tuple]      # (B, D) -> the visible part of a slot
+    held: Optional[str]                     # an eager call's slot 0: this engine-held device tensor (also a fresh region's value)
+    arg: Optional[str]                      # ... or this call argument,
+    check: Optional[Callable]               #     validated by check(engine, value, B),
+    absent: Optional[int]                   #     None (and a fresh region) meaning this value
+    noun: str                               # what a slot holds, for the refusals
+    tag: str                                # gmvae_step_schedule's suffix, run_train.last_path's "graph+<tag>"
+
+
+STEP_INPUTS: Tuple[StepInput, ...] = (
+    StepInput(option="semi_supervised", bit=L.OBJ_LABELS, region="labels", replay="y_observed", dtype=torch.int32,
+              stride=lambda B, D: (B + 3) // 4 * 4, shape=lambda B, D: (B,),
+              held=None, arg="y_observed", check=_check_labels, absent=-1, noun="label set", tag="labels"),
+    StepInput(option="weighted_objective", bit=L.OBJ_WEIGHTS, region="obj_weights", replay="obj_weights", dtype=torch.float32,
+              stride=lambda B, D: 4, shape=lambda B, D: (4,),
+              held="_objw_dev", arg=None, check=None, absent=None, noun="weight row", tag="weights"),
+    StepInput(option="temperature_on_device", bit=L.Y_TEMP_DEV, region="y_temperature", replay="y_temperature",
+              dtype=torch.float32, stride=lambda B, D: 1, shape=lambda B, D: (),
+              held="_tau_dev", arg=None, check=None, absent=None, noun="temperature", tag="temp"),
+    StepInput(option="pixel_mask", bit=L.OBJ_PIXEL_MASK, region="pixel_mask", replay="pixel_mask", dtype=torch.uint8,
+              stride=lambda B, D: (B * D + 255) // 256 * 256, shape=lambda B, D: (B, D),
+              held=None, arg="mask", check=_check_mask, absent=1, noun="mask", tag="mask"),
+)
+# The part of the library's kIwMasked (csrc/gmvae_hip.hip) that names per-step inputs: gmvae_iw_bound* and gmvae_posterior_*
+# clear these bits on entry, so their workspaces hold no such region and _chunked_eval clears them before it binds slot 0.
+_EVAL_MASKED = L.OBJ_LABELS | L.OBJ_WEIGHTS | L.Y_TEMP_DEV
 
 
 class Engine:
@@ -363,28 +414,51 @@ class Engine:
             del self._ws[key]
         if key not in self._ws:
             self._ws[key] = torch.zeros(n, dtype=torch.float32, device=self.device)
-            if self.temperature_on_device:
-                # the library only reads the region, and zeros would mean T = 0
-                self._temp_slots(d, self._ws[key]).fill_(self.hp["temperature"])
-            if self.pixel_mask:
-                # the library only reads the region, and zeros would mean "nothing observed"
-                self._mask_slots(d, self._ws[key]).fill_(1)
+            # the library only reads the per-step inputs' regions (and the classification weight), and zeros would mean
+            # "component 0 observed, weights 0, T = 0, nothing observed"
+            for inp in STEP_INPUTS:
+                if d.sched_flags & inp.bit:
+                    self._fill(inp, self._slots(inp, d, self._ws[key]))
             if self.semi_supervised:
-                # the library only reads these two regions, and zeros would mean "component 0 observed, weight 0"
-                self._label_slots(d, self._ws[key]).fill_(-1)
                 off = L.workspace_offset(d, self.model, "sup_weight") // 4
                 self._ws[key][off:off + 1].fill_(self.sup_weight)
         return d, self._ws[key]
 
-    def _weight_slots(self, d, ws) -> torch.Tensor:
-        """View [LABEL_SLOTS, 4] of the workspace's weight rows (kl_weight, y_weight, y_free_nats, 0)."""
-        off = L.workspace_offset(d, self.model, "obj_weights") // 4
-        return ws[off:off + L.LABEL_SLOTS * 4].view(L.LABEL_SLOTS, 4)
+    # ------------------------------------------------------- per-step inputs (STEP_INPUTS)
+    @property
+    def step_inputs(self) -> Tuple[str, ...]:
+        """The options of this engine's per-step inputs, in the order of STEP_INPUTS."""
+        return tuple(inp.option for inp in STEP_INPUTS if getattr(self, inp.option))
 
-    def _set_weights(self, d, ws):
-        """Slot 0 of the workspace's weight rows <- the engine's current weights (device-side copy, no host sync)."""
-        if self.weighted_objective and d.sched_flags & L.OBJ_WEIGHTS:
-            self._weight_slots(d, ws)[0].copy_(self._objw_dev)
+    def _slots(self, inp: StepInput, d, ws) -> torch.Tensor:
+        """View [LABEL_SLOTS, *inp.shape] of the input's region of the workspace (slot i starts i * inp.stride elements in)."""
+        shape, stride = inp.shape(d.B, d.D), inp.stride(d.B, d.D)
+        off = L.workspace_offset(d, self.model, inp.region) // inp.dtype.itemsize
+        slots = ws.view(inp.dtype)[off:off + L.LABEL_SLOTS * stride].view(L.LABEL_SLOTS, stride)
+        return slots[:, :math.prod(shape)].view(L.LABEL_SLOTS, *shape)
+
+    def _fill(self, inp: StepInput, slots: torch.Tensor, value=None):
+        """Every slot of the view <- value (a device-side write, no host sync); None: the engine-held tensor, or inp.absent."""
+        if value is None:
+            value = getattr(self, inp.held) if inp.held else inp.absent
+        if isinstance(value, torch.Tensor):
+            slots.copy_(value.reshape(slots.shape[1:]).expand_as(slots), non_blocking=True)
+        else:
+            slots.fill_(value)
+
+    def _bind_step_inputs(self, d, ws, y_observed: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+        """Slot 0 of every per-step input these dims carry <- what this eager call reads: the engine's current weights and
+        temperature, the call's y_observed (None: all unlabelled) and mask (None: all observed)."""
+        args = dict(y_observed=y_observed, mask=mask)
+        for inp in STEP_INPUTS:
+            value = args[inp.arg] if inp.arg else None
+            if not getattr(self, inp.option):
+                if value is not None:
+                    raise ValueError(f"{inp.arg} needs an engine created with {inp.option}=True")
+            elif d.sched_flags & inp.bit:       # (not the weights of a forward at S != 1: dims() leaves their bit out)
+                if value is not None:
+                    value = inp.check(self, value, d.B)
+                self._fill(inp, self._slots(inp, d, ws)[:1], value)
 
     def set_objective_weights(self, kl_weight: float, y_weight: float, y_free_nats: float):
         """The weights the next eager steps (step / loss / forward / train_step / dp_step) read: device-side writes, no host
@@ -396,16 +470,6 @@ class Engine:
         self.obj_weights = (float(kl_weight), float(y_weight), float(y_free_nats))
         for i, v in enumerate(self.obj_weights):
             self._objw_dev[i:i + 1].fill_(v)
-
-    def _temp_slots(self, d, ws) -> torch.Tensor:
-        """View [LABEL_SLOTS] of the workspace's temperatures."""
-        off = L.workspace_offset(d, self.model, "y_temperature") // 4
-        return ws[off:off + L.LABEL_SLOTS]
-
-    def _set_temp(self, d, ws):
-        """Slot 0 of the workspace's temperatures <- the engine's current temperature (device-side copy, no host sync)."""
-        if self.temperature_on_device and d.sched_flags & L.Y_TEMP_DEV:
-            self._temp_slots(d, ws)[0:1].copy_(self._tau_dev)
 
     def set_temperature(self, t: float):
         """The Gumbel-softmax temperature of the next eager calls (step / loss / forward / train_step / dp_step, the
@@ -419,51 +483,6 @@ class Engine:
             self._tau_dev.fill_(float(t))
         elif changed:
             self.drop_graphs(clear_handoff_errors=False)
-
-    def _mask_slots(self, d, ws) -> torch.Tensor:
-        """uint8 view [LABEL_SLOTS, B, D] of the workspace's masks (a slot is B D bytes rounded up to 256)."""
-        n = d.B * d.D
-        slot = (n + 255) // 256 * 256
-        off = L.workspace_offset(d, self.model, "pixel_mask")
-        return ws.view(torch.uint8)[off:off + L.LABEL_SLOTS * slot].view(L.LABEL_SLOTS, slot)[:, :n].view(L.LABEL_SLOTS, d.B, d.D)
-
-    def _prep_mask(self, mask, B):
-        mask = mask.to(self.device)
-        if mask.dtype.is_floating_point or mask.numel() != B * self.D:
-            raise ValueError(f"mask must be a uint8 / bool tensor [{B}, {self.D}] (non-zero: observed)")
-        return (mask != 0).reshape(B, self.D)
-
-    def _set_mask(self, d, ws, mask):
-        """Slot 0 of the workspace's masks <- mask (device-side copy, no host sync); None: all observed."""
-        if not self.pixel_mask:
-            if mask is not None:
-                raise ValueError("mask needs an engine created with pixel_mask=True")
-            return
-        slot = self._mask_slots(d, ws)[0]
-        if mask is None:
-            slot.fill_(1)
-            return
-        slot.copy_(self._prep_mask(mask, d.B), non_blocking=True)
-
-    def _label_slots(self, d, ws) -> torch.Tensor:
-        """int32 view [LABEL_SLOTS, B] of the workspace's label sets (each slot starts 16-byte aligned)."""
-        B4 = (d.B + 3) // 4 * 4
-        off = L.workspace_offset(d, self.model, "labels") // 4
-        return ws.view(torch.int32)[off:off + L.LABEL_SLOTS * B4].view(L.LABEL_SLOTS, B4)[:, :d.B]
-
-    def _set_labels(self, d, ws, y_observed):
-        """Slot 0 of the workspace's label sets <- y_observed (device-side copy, no host sync); None: all unlabelled."""
-        if not self.semi_supervised:
-            if y_observed is not None:
-                raise ValueError("y_observed needs an engine created with semi_supervised=True")
-            return
-        slot = self._label_slots(d, ws)[0]
-        if y_observed is None:
-            slot.fill_(-1)
-            return
-        if y_observed.dtype.is_floating_point or y_observed.dtype == torch.bool or y_observed.numel() != d.B:
-            raise ValueError(f"y_observed must be an int tensor of {d.B} observed components (-1: unlabelled)")
-        slot.copy_(y_observed.reshape(-1), non_blocking=True)
 
     @staticmethod
     def _as_u8(x: torch.Tensor) -> torch.Tensor:
@@ -504,10 +523,7 @@ class Engine:
         x = self._prep_x(x)
         B = x.shape[0]
         d, ws = self._workspace(B, row0=row0)
-        self._set_labels(d, ws, y_observed)
-        self._set_weights(d, ws)
-        self._set_temp(d, ws)
-        self._set_mask(d, ws, mask)
+        self._bind_step_inputs(d, ws, y_observed, mask)
         eps = self._prep_noise(eps, B * self.rows_per_x, self.Lz)
         u = self._prep_u(u, B * self.S)
         rc = L.lib.gmvae_step(C.byref(d), self.model, L.ptr(x), L.ptr(eps), L.ptr(u), L.ptr(self.params),
@@ -531,10 +547,7 @@ class Engine:
         if self.marginal and not self.marginal_iw and S != 1:
             raise ValueError("y_inference='marginal' enumerates y over the K components: n_samples must be 1")
         d, ws = self._workspace(B, S)
-        self._set_labels(d, ws, y_observed)
-        self._set_weights(d, ws)
-        self._set_temp(d, ws)
-        self._set_mask(d, ws, mask)
+        self._bind_step_inputs(d, ws, y_observed, mask)
         # an evaluation walks a split batch by batch on fixed parameters (scripts/runners.py:320-333): the operand images the
         # previous pass left in this workspace are reused while nothing has written the parameters since
         state = self._params_state() + (ws.data_ptr(),)
@@ -578,11 +591,12 @@ class Engine:
         if chunk < 1:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
         d = self.dims(B, chunk, row0)
+        d.sched_flags &= ~_EVAL_MASKED      # (as the library's iw_dims does: the same size query, the same run)
         nw = getattr(L, f"{kind}_workspace_bytes")(d, self.model) // 4 + 64
         ws = self._chunked_ws.get((kind, B, chunk))
         if ws is None or ws.numel() < nw:
             ws = self._chunked_ws[(kind, B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
-        self._set_mask(d, ws, mask)      # (the forward's workspace opens the evaluator's: the same offset)
+        self._bind_step_inputs(d, ws, mask=mask)      # (the forward's workspace opens the evaluator's: the same offsets)
         f32 = dict(dtype=torch.float32, device=self.device)
         shapes = ((B, self.K), (B, self.K), (B, 4)) if per_component else ((B,), (B,))
         outs = [torch.empty(*shape, **f32) for shape in shapes]
@@ -749,10 +763,7 @@ class Engine:
         """gmvae_dp_step: one C call enqueues step + RCCL all-reduce + Adam on the current stream."""
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
-        self._set_labels(d, ws, y_observed)
-        self._set_weights(d, ws)
-        self._set_temp(d, ws)
-        self._set_mask(d, ws, mask)
+        self._bind_step_inputs(d, ws, y_observed, mask)
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
@@ -772,28 +783,22 @@ class Engine:
         parallel) the RCCL all-reduce is captured too when the library owns the communicator
         (enable_rccl); otherwise the step is two eager halves around torch.distributed.all_reduce.
         beta1, beta2, epsilon: tf.train.AdamOptimizer's, baked into the graph like lr (and part of the key it is cached under).
-        replay.tail_log [n_steps, TAIL]: the per-step tails of the last launch.  replay.y_observed [n_steps, B] (semi-supervised)
-        and replay.obj_weights [n_steps, 4] (weighted objective; pre-filled with the engine's current weights) are VIEWS of
-        the workspace's label sets / weight rows, which step i of the graph reads; the caller fills them before replay().
-        Row 0 of both is also what every eager entry (step / loss / forward / train_step / dp_step) on the same batch size
-        writes before it runs -- the engine's current weights, its y_observed -- so after any eager call row 0 holds that
-        call's values until the caller refills it: fill the rows before EVERY replay (run_train does).
-        replay.y_temperature [n_steps] (temperature_on_device; pre-filled with the engine's current temperature) likewise:
-        a view of the workspace's temperatures, step i reads value i, slot 0 is also every eager entry's.
-        replay.pixel_mask [n_steps, B, D] (pixel_mask; uint8, pre-filled with ones = all observed) likewise: a view of the
-        workspace's masks, step i reads mask i, slot 0 is also every eager entry's."""
+        replay.tail_log [n_steps, TAIL]: the per-step tails of the last launch.  Per-step inputs (STEP_INPUTS; None where the
+        engine has none): replay.y_observed [n_steps, B] (int32; pre-filled -1 = unlabelled), replay.obj_weights [n_steps, 4]
+        (kl_weight, y_weight, y_free_nats, 0; pre-filled with the engine's current weights), replay.y_temperature [n_steps]
+        (pre-filled with the engine's current temperature) and replay.pixel_mask [n_steps, B, D] (uint8; pre-filled 1 = all
+        observed) are VIEWS of the workspace's regions: step i of the graph reads row i, the caller fills them before replay().
+        Row 0 is also what every eager entry (step / loss / forward / train_step / dp_step) on the same batch size writes
+        before it runs -- the engine's current weights and temperature, its y_observed and mask -- so after any eager call
+        row 0 holds that call's values until the caller refills it: fill the rows before EVERY replay (run_train does)."""
         import torch.distributed as dist
         do_ar = all_reduce and ((dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
                                 or getattr(self, "_comm", None) is not None)
         n_steps = int(n_steps)
-        if self.semi_supervised and n_steps > L.LABEL_SLOTS:
-            raise ValueError(f"a semi-supervised train graph holds at most {L.LABEL_SLOTS} steps (one label set per step), got {n_steps}")
-        if self.weighted_objective and n_steps > L.LABEL_SLOTS:
-            raise ValueError(f"a train graph of a weighted objective holds at most {L.LABEL_SLOTS} steps (one weight row per step), got {n_steps}")
-        if self.temperature_on_device and n_steps > L.LABEL_SLOTS:
-            raise ValueError(f"a train graph with the temperature on the device holds at most {L.LABEL_SLOTS} steps (one temperature per step), got {n_steps}")
-        if self.pixel_mask and n_steps > L.LABEL_SLOTS:
-            raise ValueError(f"a train graph with a pixel mask holds at most {L.LABEL_SLOTS} steps (one mask per step), got {n_steps}")
+        active = [inp for inp in STEP_INPUTS if getattr(self, inp.option)]
+        if active and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph of an engine with {active[0].option}=True holds at most {L.LABEL_SLOTS} steps (one "
+                             f"{active[0].noun} per step), got {n_steps}")
         adam_hp = (float(beta1), float(beta2), float(epsilon))
         key = (B, lr, do_ar, n_steps) + adam_hp
         if key in self._graphs:
@@ -804,51 +809,56 @@ class Engine:
         else:
             static_x = torch.zeros(n_steps, B, self.D, dtype=torch.uint8, device=self.device)
         d, ws = self._workspace(B)
-        # semi-supervised: step i of the graph reads label set i of the workspace; the caller fills replay.y_observed [n_steps, B]
-        # (int32, -1 = unlabelled) next to static_x
-        y_obs = None
-        if self.semi_supervised:
-            y_obs = self._label_slots(d, ws)[:n_steps]
-            y_obs.fill_(-1)
-        # weighted objective: step i reads weight row i; the caller fills replay.obj_weights [n_steps, 4] = (kl_weight, y_weight,
-        # y_free_nats, 0) per step (pre-filled with the engine's current weights)
-        obj_w = None
-        if self.weighted_objective:
-            obj_w = self._weight_slots(d, ws)[:n_steps]
-            obj_w.copy_(self._objw_dev.expand(n_steps, 4))
-
-        # temperature on the device: step i reads temperature i; the caller fills replay.y_temperature [n_steps]
-        y_temp = None
-        if self.temperature_on_device:
-            y_temp = self._temp_slots(d, ws)[:n_steps]
-            y_temp.copy_(self._tau_dev.expand(n_steps))
-
-        # pixel mask: step i reads mask i; the caller fills replay.pixel_mask [n_steps, B, D] (pre-filled: all observed)
-        pmask = None
-        if self.pixel_mask:
-            pmask = self._mask_slots(d, ws)[:n_steps]
-            pmask.fill_(1)
-
-        def eager_rows(body):
-            """The graph's steps one by one (no graph could be captured): step i's weight row and temperature pass through
-            the engine's current ones, which every eager entry copies into slot 0."""
-            rows = None if obj_w is None else (obj_w.clone(), self._objw_dev.clone())
-            taus = None if y_temp is None else (y_temp.clone(), self._tau_dev.clone())
-            for i in range(n_steps):
-                if rows is not None:
-                    self._objw_dev.copy_(rows[0][i])
-                if taus is not None:
-                    self._tau_dev.copy_(taus[0][i:i + 1])
-                body(i)
-            if rows is not None:
-                self._objw_dev.copy_(rows[1])
-                obj_w[0].copy_(rows[0][0])
-            if taus is not None:
-                self._tau_dev.copy_(taus[1])
-                y_temp[0:1].copy_(taus[0][0:1])
+        rows = {inp: self._slots(inp, d, ws)[:n_steps] for inp in active}      # step i reads row i; the caller fills them
+        for inp, view in rows.items():
+            self._fill(inp, view)
         self.step_dev.fill_(self.global_step)
         # per-step tails of one launch (loss sums + count; all-reduced under data parallelism): replay.tail_log
         tail_log = torch.zeros(n_steps, L.TAIL, dtype=torch.float32, device=self.device)
+
+        def hand_out(replay, handle):
+            replay.tail_log = tail_log
+            for inp in STEP_INPUTS:
+                setattr(replay, inp.replay, rows.get(inp))
+            self._graphs[key] = (static_x, replay, handle)
+            return static_x, replay
+
+        def graph_replay(handle):
+            launch = L.lib.gmvae_train_graph_launch
+            gen = self._graph_gen
+
+            def replay():
+                self._check_alive(gen)
+                rc2 = launch(handle, L.current_stream())
+                if rc2:
+                    L.check(rc2, "gmvae_train_graph_launch")
+                self.global_step += n_steps
+            return hand_out(replay, handle)
+
+        def eager_replay(step):
+            """The graph's steps one by one (no graph could be captured): an eager step reads slot 0, so row i of every input
+            passes through it -- as step(i, y_observed=, mask=)'s arguments, or through the engine-held tensor that every eager
+            entry copies there.  Afterwards row 0 and the engine's own current values are what they were."""
+            batches = [static_x] if n_steps == 1 else list(static_x.unbind(0))
+
+            def replay():
+                saved = {inp: view.clone() for inp, view in rows.items()}
+                own = {inp: getattr(self, inp.held).clone() for inp in rows if inp.held}
+                for i in range(n_steps):
+                    args = {}
+                    for inp, r in saved.items():
+                        if inp.held:
+                            getattr(self, inp.held).copy_(r[i].reshape(own[inp].shape))
+                        else:
+                            args[inp.arg] = r[i]
+                    step(batches[i], **args)
+                    tail_log[i].copy_(self.grads[self.P:])
+                for inp, r in saved.items():
+                    rows[inp][0].copy_(r[0])
+                    if inp.held:
+                        getattr(self, inp.held).copy_(own[inp])
+            return hand_out(replay, None)
+
         if do_ar and getattr(self, "_comm", None):
             torch.cuda.synchronize()
             handle = C.c_void_p()
@@ -857,87 +867,30 @@ class Engine:
                                              L.ptr(self.step_dev), lr, *adam_hp, self._comm, L.ptr(tail_log),
                                              C.byref(handle))
             if self._agree(rc == 0):                # all ranks jointly: the graph, or (below) the eager C-side step
-                launch = L.lib.gmvae_train_graph_launch
                 self.dp_mode = "rccl-in-hipgraph"
-                gen = self._graph_gen
-
-                def replay():
-                    self._check_alive(gen)
-                    rc2 = launch(handle, L.current_stream())
-                    if rc2:
-                        L.check(rc2, "gmvae_train_graph_launch")
-                    self.global_step += n_steps
-                replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
-                replay.pixel_mask = pmask
-                self._graphs[key] = (static_x, replay, handle)
-                return static_x, replay
+                return graph_replay(handle)
             if rc == 0:
                 L.lib.gmvae_train_graph_destroy(handle)
             self.step_dev.fill_(self.global_step)   # capture refused somewhere: eager C-side step instead
             self.dp_mode = "rccl-eager-c"
-            batches = [static_x] if n_steps == 1 else list(static_x.unbind(0))
-
-            def replay():
-                ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
-                ms = None if pmask is None else pmask.clone()
-
-                def body(i):
-                    self.dp_step(batches[i], lr, None if ys is None else ys[i], *adam_hp, mask=None if ms is None else ms[i])
-                    tail_log[i].copy_(self.grads[self.P:])
-                eager_rows(body)
-                if ys is not None:
-                    y_obs[0].copy_(ys[0])
-                if ms is not None:
-                    pmask[0].copy_(ms[0])
-            replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
-            replay.pixel_mask = pmask
-            self._graphs[key] = (static_x, replay, None)
-            return static_x, replay
+            return eager_replay(lambda x, y_observed=None, mask=None: self.dp_step(x, lr, y_observed, *adam_hp, mask=mask))
         if do_ar:
             from . import parallel
             self.dp_mode = "torch.distributed"
-            batches = [static_x] if n_steps == 1 else list(static_x.unbind(0))
 
-            def replay():
-                ys = None if y_obs is None else y_obs.clone()      # (an eager step reads slot 0: step i's set passes through it)
-                ms = None if pmask is None else pmask.clone()
-
-                def body(i):
-                    self.step(batches[i], use_step_dev=True, y_observed=None if ys is None else ys[i],
-                              mask=None if ms is None else ms[i])
-                    parallel.all_reduce_flat(self.grads)
-                    self.adam(lr, *adam_hp, use_step_dev=True)
-                    self.global_step += 1
-                    tail_log[i].copy_(self.grads[self.P:])
-                eager_rows(body)
-                if ys is not None:
-                    y_obs[0].copy_(ys[0])
-                if ms is not None:
-                    pmask[0].copy_(ms[0])
-            replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
-            replay.pixel_mask = pmask
-            self._graphs[key] = (static_x, replay, None)
-            return static_x, replay
+            def step(x, **args):
+                self.step(x, use_step_dev=True, **args)
+                parallel.all_reduce_flat(self.grads)
+                self.adam(lr, *adam_hp, use_step_dev=True)
+                self.global_step += 1
+            return eager_replay(step)
         torch.cuda.synchronize()
         handle = C.c_void_p()
         rc = L.lib.gmvae_train_graph_create(C.byref(d), self.model, L.ptr(static_x), n_steps, L.ptr(self.params), L.ptr(self.m),
                                             L.ptr(self.v), L.ptr(self.grads), L.ptr(ws), self.noise_seed,
                                             L.ptr(self.step_dev), lr, *adam_hp, L.ptr(tail_log), C.byref(handle))
         L.check(rc, "gmvae_train_graph_create")
-        launch = L.lib.gmvae_train_graph_launch
-        gen = self._graph_gen
-
-        def replay():
-            self._check_alive(gen)
-            rc = launch(handle, L.current_stream())
-            if rc:
-                L.check(rc, "gmvae_train_graph_launch")
-            self.global_step += n_steps
-
-        replay.tail_log, replay.y_observed, replay.obj_weights, replay.y_temperature = tail_log, y_obs, obj_w, y_temp
-        replay.pixel_mask = pmask
-        self._graphs[key] = (static_x, replay, handle)
-        return static_x, replay
+        return graph_replay(handle)
 
     BINARIZE_SEED_XOR = 0x62696E6172697A65      # the pipeline graph keys its binarisation uniforms by noise_seed ^ this
 
@@ -947,18 +900,11 @@ class Engine:
         steps first binarises its own batch on the device (scripts/runners.py:44-47), rows taken from `dataset`
         (gmvae_amd.data.DeviceDataset: resident uint8 pixels + an epoch permutation on the device).  Returns
         replay(): refills the row indices (device-to-device) and launches the graph; nothing crosses PCIe."""
-        if self.semi_supervised:
-            raise ValueError("capture_train_pipeline gathers its batches by index inside the graph and has no label gather: a "
-                             "semi-supervised engine trains through capture_train_step (replay.y_observed)")
-        if self.weighted_objective:
-            raise ValueError("capture_train_pipeline has no per-step weight rows: an engine with weighted_objective=True trains "
-                             "through capture_train_step (replay.obj_weights)")
-        if self.temperature_on_device:
-            raise ValueError("capture_train_pipeline has no per-step temperatures: an engine with temperature_on_device=True "
-                             "trains through capture_train_step (replay.y_temperature)")
-        if self.pixel_mask:
-            raise ValueError("capture_train_pipeline has no per-step masks: an engine with pixel_mask=True trains through "
-                             "capture_train_step (replay.pixel_mask)")
+        for inp in STEP_INPUTS:
+            if getattr(self, inp.option):
+                raise ValueError("capture_train_pipeline gathers its batches by index inside the graph and has no label gather, "
+                                 f"nor one for weight rows, temperatures or masks: an engine with {inp.option}=True trains "
+                                 f"through capture_train_step (replay.{inp.replay})")
         n_steps = int(n_steps)
         key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon))
         if key in self._graphs:

@@ -303,7 +303,7 @@ def run_train(config):
     loss from the log (scripts/utils.py:13-57), the checkpoint timer (save_checkpoint_secs=120, runners.py:226).
     `config.eager = True` (or GMVAE_EAGER_TRAIN=1) runs the same batches through eager launches instead."""
     from .data import binarize
-    from .engine import Engine
+    from .engine import STEP_INPUTS, Engine
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(select_device(config, local))
     data_dim = int(getattr(config, "data_dim", 784))
@@ -328,20 +328,14 @@ def run_train(config):
         except Exception as e:
             if rank == 0:
                 print(f"[run_train] in-library RCCL unavailable ({e}); torch.distributed all-reduce", flush=True)
-    # semi-supervised (--labelled_per_class): the pipeline graph has no label gather, so one device takes the branch that
-    # world > 1 takes -- binarise, fill the graph's label sets, replay
-    sup = eng.semi_supervised
-    # weighted objective (--kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps): the same branch -- the graph's weight
-    # rows are filled per launch from the schedule, a pure function of the global step
-    wobj = eng.weighted_objective
-    # temperature on the device (--temperature / --temperature_min / --temperature_anneal_rate / --temperature_anneal_every):
-    # the same branch again -- the graph's temperatures are filled per launch from temperature_at
-    ytd = eng.temperature_on_device
-    # pixel mask (--missing_rate): the same branch once more -- the graph's masks are gathered per launch by the batch's rows
-    pmk = eng.pixel_mask
-    run_train.last_path = "eager" if eager else ("dp-graph" if world > 1 else "graph+labels" if sup else
-                                                 "graph+weights" if wobj else "graph+temp" if ytd else
-                                                 "graph+mask" if pmk else "pipeline-graph")
+    # per-step inputs (engine.STEP_INPUTS): the pipeline graph has no gather for them, so one device takes the branch that
+    # world > 1 takes -- binarise, fill the graph's rows, replay.  Per launch: the label sets (--labelled_per_class) and the masks
+    # (--missing_rate) are gathered by the batch's rows; the weight rows (--kl_weight / --y_weight / --y_free_nats /
+    # --kl_warmup_steps) and the temperatures (--temperature / --temperature_min / --temperature_anneal_rate /
+    # --temperature_anneal_every) are pure functions of the global step
+    inputs = eng.step_inputs
+    tags = [inp.tag for inp in STEP_INPUTS if inp.option in inputs]
+    run_train.last_path = ("eager" if eager else "dp-graph" if world > 1 else f"graph+{tags[0]}" if tags else "pipeline-graph")
     run_train.temperature_log = []                          # temperature on the device: (0-based step index, temperature) of the
                                                             # LAST launch's steps, as placed in replay.y_temperature
     run_train.weight_log = []                               # weighted objective: (step, tail[5] / tail[4], tail[6] / tail[4]) of the
@@ -362,16 +356,16 @@ def run_train(config):
             if eager:
                 rows = ds.next_rows(B)
                 x = binarize(ds.pixels, rows=rows, seed=bseed, step=eng.global_step, out_row0=rank * B)
-                yo = ds.y_observed[rows.long()] if sup else None
-                if wobj:
+                yo = ds.y_observed[rows.long()] if "semi_supervised" in inputs else None
+                if "weighted_objective" in inputs:
                     eng.set_objective_weights(*objective_weights_at(config, eng.global_step))
-                if ytd:
+                if "temperature_on_device" in inputs:
                     run_train.temperature_log = [(eng.global_step, temperature_at(config, eng.global_step))]
                     eng.set_temperature(run_train.temperature_log[0][1])
-                mk = ds.pixel_mask[rows.long()] if pmk else None
+                mk = ds.pixel_mask[rows.long()] if "pixel_mask" in inputs else None
                 logs.append(eng.train_step(x, lr=lr, y_observed=yo, mask=mk).clone().view(1, -1))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1 and not sup and not wobj and not ytd and not pmk:
+            elif world == 1 and not inputs:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -389,15 +383,15 @@ def run_train(config):
                 for i in range(g):                          # this launch's batches, binarised on the device
                     last_rows = ds.next_rows(B)
                     binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
-                    if sup:
+                    if replay.y_observed is not None:
                         replay.y_observed[i].copy_(ds.y_observed[last_rows.long()])
-                    if pmk:
+                    if replay.pixel_mask is not None:
                         replay.pixel_mask[i].copy_(ds.pixel_mask[last_rows.long()])
-                if wobj:
+                if replay.obj_weights is not None:
                     rows_w = torch.tensor([objective_weights_at(config, eng.global_step + i) + (0.0,) for i in range(g)],
                                           dtype=torch.float32)
                     replay.obj_weights.copy_(rows_w, non_blocking=True)
-                if ytd:
+                if replay.y_temperature is not None:
                     run_train.temperature_log = [(eng.global_step + i, temperature_at(config, eng.global_step + i)) for i in range(g)]
                     replay.y_temperature.copy_(torch.tensor([v for _, v in run_train.temperature_log], dtype=torch.float32),
                                                non_blocking=True)
@@ -414,7 +408,7 @@ def run_train(config):
         logs = []
         vals = (tails[:, 0] / tails[:, 4]).tolist()
         base = eng.global_step - len(vals)
-        if wobj:
+        if "weighted_objective" in inputs:
             run_train.weight_log = [(base + i + 1, (tails[i, 5] / tails[i, 4]).item(), (tails[i, 6] / tails[i, 4]).item())
                                      for i in range(len(vals))]
         fault = getattr(config, "fault_hook", None)         # (tests: called with the engine after every summary block)
@@ -465,22 +459,22 @@ def run_train(config):
         if rank == 0 and (eng.global_step % every == 0 or eng.global_step > config.max_steps):
             rate = (eng.global_step - s0) / max(time.time() - t0, 1e-9)
             msg = f"Step {eng.global_step}, loss: {vals[-1]:f}  ({rate:.1f} global_step/sec)"
-            if wobj:
+            if "weighted_objective" in inputs:
                 msg += (f"  kl_weight {run_train.weight_log[-1][1]:.4f}  y_weight {run_train.weight_log[-1][2]:.4f}"
                         f"  y_floor_share {(tails[-1, 7] / tails[-1, 4]).item():.4f}")
-            if ytd:                                         # (of the last step taken)
+            if "temperature_on_device" in inputs:           # (of the last step taken)
                 msg += f"  temperature {temperature_at(config, eng.global_step - 1):.4f}"
-            if pmk:                                         # (of the last step taken)
+            if "pixel_mask" in inputs:                      # (of the last step taken)
                 if tails[-1, 6].item() > 0:
                     msg += f"  imputation_nll {(tails[-1, 5] / tails[-1, 6]).item():.4f}"
                 msg += f"  observed_share {(tails[-1, 7] / (tails[-1, 6] + tails[-1, 7])).item():.4f}"
-            if sup:                                         # over the summary block's labelled examples (all ranks')
+            if "semi_supervised" in inputs:                 # over the summary block's labelled examples (all ranks')
                 blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
                 if blk[1].item() > 0:
                     msg += f"  sup_acc {blk[2].item() / blk[1].item():.4f}  sup_ce {blk[0].item() / blk[1].item():.4f}"
             if config.model == "gmvae" and ds.labels is not None:
                 # (--missing_rate: q(y|x) of what the step saw, m x)
-                q = model.encoder_y(last_x * ds.pixel_mask[last_rows.long()] if pmk else last_x).distribution.logits
+                q = model.encoder_y(last_x * ds.pixel_mask[last_rows.long()] if "pixel_mask" in inputs else last_x).distribution.logits
                 acc = utils.cluster_acc(q, ds.labels[last_rows.long()], config.mixture_components)
                 msg += f"  cluster_acc {acc.item():.4f}"
             print(msg, flush=True)

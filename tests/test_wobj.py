@@ -255,41 +255,7 @@ def test_dp_step_and_dp_graph_with_a_one_rank_communicator():
         _drop_comm(b)
 
 
-def test_eager_fallback_of_a_refused_dp_graph_reads_one_weight_row_per_step(monkeypatch):
-    """capture_train_step(all_reduce=True) where the library refuses the data-parallel graph: replay() runs the steps one by
-    one through gmvae_dp_step, step i's weight row passing through the engine's current weights.  Same bits as eager steps
-    that set those rows; afterwards the engine's own weights and row 0 of replay.obj_weights are what they were."""
-    import torch
-    _need_rccl()
-    L = _L()
-    name = "gumbel"
-    d, B = WR.CASES[name][2], 16
-    xs = torch.from_numpy((np.random.default_rng(12).random((3, B, d.D)) < 0.87).astype(np.uint8)).cuda()
-    own = (0.5, 0.75, 0.1)
-    kw = dict(kl_weight=own[0], y_weight=own[1], y_free_nats=own[2])
-    a, b = _engine(name, 17, **kw), _engine(name, 17, **kw)
-    b.enable_rccl()
-    try:
-        tails = []
-        for t in range(3):
-            a.set_objective_weights(*ROWS8[t + 2])
-            tails.append(a.train_step(xs[t], lr=LR).clone())
-        monkeypatch.setattr(L.lib, "gmvae_dp_graph_create", lambda *args: -2)      # the refusal: no graph, no handle
-        sb, rb = b.capture_train_step(B, lr=LR, all_reduce=True, n_steps=3)
-        assert b.dp_mode == "rccl-eager-c"
-        sb.copy_(xs)
-        rows = torch.tensor([ROWS8[t + 2] + (0.0,) for t in range(3)], dtype=torch.float32)
-        rb.obj_weights.copy_(rows)
-        rb()
-        torch.cuda.synchronize()
-        assert a.global_step == b.global_step == 3
-        for u, v in ((a.params, b.params), (a.m, b.m), (a.v, b.v)):
-            assert torch.equal(u.detach(), v.detach())
-        assert torch.equal(rb.tail_log, torch.stack(tails))
-        assert torch.equal(rb.obj_weights.cpu(), rows)                             # row 0 restored after the eager calls
-        assert torch.equal(b._objw_dev.cpu(), torch.tensor(own + (0.0,), dtype=torch.float32)) and b.obj_weights == own
-    finally:
-        _drop_comm(b)
+# (the eager fallback of a refused data-parallel graph: tests/test_step_inputs.py, for all four per-step inputs)
 
 
 # 6 --------------------------------------------------------------------------------------------------------------
