@@ -65,6 +65,8 @@ def _load():
         "gmvae_posterior_component_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
         "gmvae_posterior_component": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "adam_tf_step": ([vp, vp, vp, vp, u64, f32, f32, f32, f32, u64, vp, f32, vp, vp, vp], i32),
+        "gmvae_grad_clip_scratch_bytes": ([u64, C.POINTER(u64)], i32),
+        "gmvae_grad_clip": ([vp, u64, vp, vp, vp, vp], i32),
         "gmvae_mlp_forward": ([dp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         "gmvae_noise_fill": ([vp, vp, u64, i32, i32, u64, u64, u64, vp, vp], i32),
         "gmvae_cluster_acc": ([vp, vp, i32, i32, i32, vp, vp, vp], i32),
@@ -127,6 +129,7 @@ OBJ_WEIGHTS = 64      # ... objective: the KL terms weighted per step from devic
 Y_TEMP_DEV = 128      # ... the Gumbel-softmax temperature read per step from device memory (include/gmvae_hip.h GMVAE_Y_TEMP_DEV)
 Y_STRAIGHT_THROUGH = 256   # ... one-hot y forward, the relaxed sample's Jacobian backward (include/gmvae_hip.h GMVAE_Y_STRAIGHT_THROUGH)
 OBJ_PIXEL_MASK = 512  # ... objective: a per-example observation mask read from the workspace (include/gmvae_hip.h GMVAE_OBJ_PIXEL_MASK)
+OPT_CLIP_NORM = 1024  # ... optimizer: the gradient clipped by its global norm in front of TF-Adam (include/gmvae_hip.h GMVAE_OPT_CLIP_NORM)
 # Engine(y_estimator=...): the relaxed Gumbel-softmax sample, or its straight-through form (Jang et al. 2017)
 Y_ESTIMATORS = ("relaxed", "straight_through")
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph
@@ -184,6 +187,13 @@ def workspace_offset(dims, model, name):
     off = C.c_uint64()
     check(lib.gmvae_workspace_offset(C.byref(dims), int(model), name.encode(), C.byref(off)), f"gmvae_workspace_offset({name})")
     return off.value
+
+
+def grad_clip_scratch_bytes(P):
+    """Bytes of gmvae_grad_clip's scratch for a gradient buffer of P (padded) elements."""
+    b = C.c_uint64()
+    check(lib.gmvae_grad_clip_scratch_bytes(int(P), C.byref(b)), "gmvae_grad_clip_scratch_bytes")
+    return b.value
 
 
 def _chunked_workspace_bytes(name):

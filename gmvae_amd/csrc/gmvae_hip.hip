@@ -39,6 +39,7 @@
 #include "wobj.hpp"
 #include "ytemp.hpp"
 #include "pmask.hpp"
+#include "gclip.hpp"
 
 using namespace gmvae;
 
@@ -82,6 +83,10 @@ static bool y_head_bits(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_Y_T
 // GMVAE_OBJ_PIXEL_MASK: a per-example observation mask (pmask.hpp: x~ = m x for every network that reads x, the masked Bernoulli
 // epilogue of gemm.hpp, pmask_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes
 static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_PIXEL_MASK) != 0; }
+// GMVAE_OPT_CLIP_NORM: the gradient clipped by its global norm in front of TF-Adam (gclip.hpp: finalize_grads_ss in
+// finalize_grads' place, gclip_finish_adam behind it) -- a training step with the bit takes the general schedule; forward-only
+// passes do not depend on it (run_step clears it for them)
+static bool clip_norm(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OPT_CLIP_NORM) != 0; }
 // The per-step inputs -- label sets, weight rows, temperatures, masks: each a read-only workspace region of GMVAE_LABEL_SLOTS
 // slots that the CALLER writes.  A step reads slot StepArgs::slot of every region its dims carry: 0 from the eager entry
 // points, i for step i of a train graph, which therefore holds at most GMVAE_LABEL_SLOTS steps; the pipeline graph, which
@@ -274,6 +279,10 @@ struct WS {
   // partials [R][nparts] beside part, and the per-example (missing, observed) counts [B][2]
   unsigned char *pixel_mask, *xm;
   float *hpart, *mcnt;
+  // GMVAE_OPT_CLIP_NORM: the caller's threshold (one float, read only), the records [GMVAE_LABEL_SLOTS][4] the library writes
+  // and the fp64 partials of the sum of squares, one per 1024 elements of the gradient buffer
+  float *clip_norm, *grad_clip;
+  double* clip_part;
   float *dbuf[3], *dz, *dqp, *dpp, *dy, *dlogits, *dqb, *slabs, *gmp_part;
   unsigned* sk_cnt;                  // skinny schedule, sk_dwc: arrived batch shares per weight-gradient tile
   float *sk_s1, *sk_lqp, *sk_part;   // skinny schedule: first-layer slabs [ns1][B][2H]; log q / log p partials [2][L/16][B]; logpx partials [B][D/16]
@@ -339,6 +348,7 @@ static bool mega_shape(const GmvaeDims& d, int model) {
 }
 static bool mega_ok(const GmvaeDims& d, int model) {
   if (obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;      // (GMVAE_OBJ_WEIGHTS, GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH, GMVAE_OBJ_PIXEL_MASK: the general schedule only, as GMVAE_GRAD_DREG below)
+  if (clip_norm(d)) return false;              // (GMVAE_OPT_CLIP_NORM: no update may start before the whole gradient's norm is known)
   if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
                                                //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
   const char* e = getenv("GMVAE_NO_MEGA");
@@ -388,7 +398,7 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
 static bool skinny_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d) || clip_norm(d)) return false;
   const char* e = getenv("GMVAE_NO_SKINNY");
   if (e && atoi(e)) return false;
   int maxb = kSkMaxB;
@@ -403,7 +413,7 @@ static bool fused_shape(const GmvaeDims& d, int model) {
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
 }
 static bool fused_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;
+  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d) || clip_norm(d)) return false;
   const char* e = getenv("GMVAE_NO_FUSED");
   if (e && atoi(e)) return false;
   return fused_shape(d, model);
@@ -467,6 +477,7 @@ static bool planes_ok(const GmvaeDims& d, const Layout& L) {
   return L.dec.nl >= 2 && big && R >= minr && R % 128 == 0 && d.D % 128 == 0 && Ht % 128 == 0 && R * d.D < (1ll << 32);
 }
 
+static uint64_t clip_parts(uint64_t P) { return (P + kClipSpan - 1) / kClipSpan; }      // gclip.hpp: one partial per 1024 elements
 static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS& w) {
   uint64_t off = 0;
   auto take = [&](uint64_t nfloats) -> float* {
@@ -621,6 +632,11 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.xm = reinterpret_cast<unsigned char*>(take((B * D + 3) / 4));
     w.hpart = take(R * ((D + 31) / 32));
     w.mcnt = take(2 * B);
+  }
+  if (clip_norm(d)) {                             // (behind everything, as above: dims without the bit keep their size and every offset)
+    w.clip_norm = take(4);
+    w.grad_clip = take((uint64_t)GMVAE_LABEL_SLOTS * 4);
+    w.clip_part = reinterpret_cast<double*>(take(2 * clip_parts(L.P_pad)));
   }
   w.bytes = off;
 }
@@ -2084,9 +2100,14 @@ static int run_step_impl(Ctx& cx, const StepArgs& a);
 static int run_step(Ctx& cx, const StepArgs& a) {
   // (under GMVAE_OBJ_LABELS the bit stays: the label regions lie behind DReG's v in the workspace, and the labelled objectives
   //  take the general schedule anyway)
-  if (a.backward || !dreg_grad(*a.d) || sup_labels(*a.d)) return run_step_impl(cx, a);
+  // (GMVAE_OPT_CLIP_NORM belongs to the optimizer: its regions lie behind every other buffer, a forward-only pass takes the
+  //  schedule it takes without the bit)
+  unsigned drop = 0;
+  if (!a.backward && clip_norm(*a.d)) drop |= GMVAE_OPT_CLIP_NORM;
+  if (!a.backward && dreg_grad(*a.d) && !sup_labels(*a.d)) drop |= GMVAE_GRAD_DREG;
+  if (!drop) return run_step_impl(cx, a);
   GmvaeDims d = *a.d;                            // forward only: the bound, the tail and the outputs do not depend on the estimator
-  d.sched_flags &= ~GMVAE_GRAD_DREG;
+  d.sched_flags &= ~drop;
   StepArgs b = a;
   b.d = &d;
   return run_step_impl(cx, b);
@@ -2130,6 +2151,8 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (fused_ok(d, model) && !a.z_out && !a.y_out && !a.logits_out)
     return run_step_fused(cx, a, L, w, eps, u, ge, gu);
   if (step_inputs(d) && (a.slot < 0 || a.slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
+  // GMVAE_OPT_CLIP_NORM: step i of a train graph writes record i
+  if (clip_norm(d) && a.backward && (a.slot < 0 || a.slot >= GMVAE_LABEL_SLOTS || !w.clip_part)) return GMVAE_E_DIMS;
   // GMVAE_Y_TEMP_DEV: this step's temperature slot (null: T by value); GMVAE_Y_STRAIGHT_THROUGH: w.y_soft is carved
   if (y_head_bits(d) && (!gm || marg || (y_temp_dev(d) && !w.y_temperature) || (y_straight(d) && !w.y_soft))) return GMVAE_E_DIMS;
   const float* const ytau = y_temp_dev(d) ? w.y_temperature + a.slot : nullptr;
@@ -2762,6 +2785,22 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   {
     const bool gmp = model == GMVAE_MODEL_VAE_GMP;
     const int KLp = (int)pad4((uint64_t)K * Lz);
+    if (clip_norm(d)) {
+      // GMVAE_OPT_CLIP_NORM: no update before the whole gradient's norm is known -- the slab sums and the fp64 partials of their
+      // squares in this launch, the record and TF-Adam on it in the next (one launch more than finalize_grads_adam)
+      const unsigned nb = (unsigned)clip_parts((uint64_t)PP);
+      hipLaunchKernelGGL(finalize_grads_ss, dim3(nb), dim3(kClipBlock), 0, st, sl, NS, PP, a.grads,
+                         gmp ? w.gmp_part : (const float*)nullptr, GMP_PARTS, gmp ? 2 * KLp + (int)pad4(K) : 0, (long long)L.loc,
+                         sxb, w.clip_part);
+      rowk(cx, "finalize_grads_ss");
+      if (a.adam_p && a.step_dev) {
+        hipLaunchKernelGGL(gclip_finish_adam, dim3(nb), dim3(kClipBlock), 0, st, a.adam_p, a.adam_m, a.adam_v, a.grads, PP, a.lr,
+                           a.beta1, a.beta2, a.epsilon, a.step_dev, w.clip_part, (int)nb, w.clip_norm,
+                           w.grad_clip + 4 * (size_t)a.slot, a.tail_log);
+        rowk(cx, "gclip_finish_adam");
+      }
+      return cx.err;
+    }
     AdamTail adt;
     memset(&adt, 0, sizeof(adt));
     if (a.adam_p && a.step_dev) {                 // train graph / gmvae_train_step: the optimizer in the same launch
@@ -2790,7 +2829,7 @@ constexpr IwKindRow kIwKinds[] = {{-1, false}, {GMVAE_MODEL_GMVAE, true}, {GMVAE
 // bits that mean nothing to an evaluator: no gradient, no labels, no weights, and the operand images are prepared here, once
 // per call.  Masked HERE alone, so the size query and the run carve the workspace from the same dims.
 constexpr unsigned kIwMasked = GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
-                               GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH;      // (the evaluators draw y at dims->temperature, relaxed)
+                               GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH | GMVAE_OPT_CLIP_NORM;      // (the evaluators draw y at dims->temperature, relaxed)
 
 // the kind's dims from the caller's (S = the chunk), or the entry point's error: kIwMasked cleared; the enumerating kinds ignore
 // GMVAE_OBJ_MARGINAL_Y and GMVAE_OBJ_MARGINAL_Y_IW on entry and carry GMVAE_OBJ_MARGINAL_Y on return, the others refuse both
@@ -3192,6 +3231,26 @@ int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t
   hipLaunchKernelGGL(adam_tf, dim3((unsigned)(((P + 3) / 4 + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), params, m, v, grads, (long long)P, lr, beta1, beta2, epsilon, t,
                      t_dev, grad_scale, grad_scale_dev, loss_sum_dev);
+  return (int)hipGetLastError();
+}
+
+int gmvae_grad_clip_scratch_bytes(uint64_t P, uint64_t* bytes) {
+  if (!bytes) return GMVAE_E_NULL;
+  if (P == 0 || (P & 3)) return GMVAE_E_DIMS;
+  *bytes = (clip_parts(P) * 8 + 255) / 256 * 256;
+  return 0;
+}
+
+int gmvae_grad_clip(const float* grads, uint64_t P, const float* clip_norm_dev, float* rec_out, void* scratch, void* stream) {
+  if (!grads || !clip_norm_dev || !rec_out || !scratch) return GMVAE_E_NULL;
+  if (P == 0 || (P & 3) || clip_parts(P) > 0x7fffffffull) return GMVAE_E_DIMS;
+  if (!aligned16(grads) || !aligned16(scratch)) return GMVAE_E_ALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned nb = (unsigned)clip_parts(P);
+  double* const part = static_cast<double*>(scratch);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(gclip_partials, dim3(nb), dim3(kClipBlock), 0, st, grads, (long long)P, part);
+  hipLaunchKernelGGL(gclip_finish, dim3(1), dim3(64), 0, st, part, (int)nb, grads + P, clip_norm_dev, rec_out);
   return (int)hipGetLastError();
 }
 
@@ -3653,9 +3712,19 @@ int gmvae_bench_loop(const GmvaeDims* dims, int model, const uint8_t* x, float* 
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
   build_layout(*dims, model, L);
+  WS w;
+  carve(*dims, model, L, workspace, w);
   auto one = [&](hipStream_t s) -> int {
     int rc = gmvae_step(dims, model, x, nullptr, nullptr, params, grads, workspace, 1234, 0, step_dev, s);
     if (rc) return rc;
+    if (clip_norm(*dims)) {                        // (the step left the partials: record 0, then the optimizer on it)
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(gclip_finish, dim3(1), dim3(64), 0, s, w.clip_part, (int)clip_parts(L.P_pad), grads + L.P_pad, w.clip_norm,
+                         w.grad_clip);
+      if (hipError_t he = hipGetLastError()) return (int)he;
+      return adam_tf_step(params, m, v, grads, L.P_pad, 1e-3f, 0.9f, 0.999f, 1e-8f, 0, step_dev, 1.f, w.grad_clip + 1,
+                          w.grad_clip + 3, s);
+    }
     return adam_tf_step(params, m, v, grads, L.P_pad, 1e-3f, 0.9f, 0.999f, 1e-8f, 0, step_dev, 1.f,
                         grads + L.P_pad + 4, grads + L.P_pad, s);
   };
@@ -3716,6 +3785,7 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
                               float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
   if (step_inputs(*dims) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;      // (step i reads slot i)
+  if (clip_norm(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i writes record i; the pipeline graph takes the bit)
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
@@ -3827,9 +3897,10 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   else if (skinny_ok(d, model)) nm = "skinny";
   else if (fused_ok(d, model)) nm = "fused";
   const bool gen = !strcmp(nm, "general");
-  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
-           y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "", dreg_grad(d) ? "+dreg" : "", (gen && planes_ok(d, L)) ? "+planes" : "");
+           y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
+           (gen && planes_ok(d, L)) ? "+planes" : "");
   return 0;
 }
 
@@ -3866,7 +3937,8 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"sync", reinterpret_cast<float*>(w.sync)}, {"ev_dbg", reinterpret_cast<float*>(w.ev_dbg)},
       {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight},
       {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor},
-      {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}, {"pixel_mask", reinterpret_cast<float*>(w.pixel_mask)}};
+      {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}, {"pixel_mask", reinterpret_cast<float*>(w.pixel_mask)},
+      {"clip_norm", w.clip_norm}, {"grad_clip", w.grad_clip}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;
@@ -3996,6 +4068,17 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   if (rc) return rc;
   const int nrc = g_rccl.AllReduce(grads, grads, (size_t)L.P_pad + GMVAE_TAIL, /*ncclFloat*/ 7, /*ncclSum*/ 0, comm, st);
   if (nrc) return 1000 + nrc;
+  if (clip_norm(*dims)) {
+    // GMVAE_OPT_CLIP_NORM: the norm of the ALL-REDUCED buffer with the global count -- its own partials pass, then the record and
+    // TF-Adam in one launch; every rank forms the same bits
+    if (slot < 0 || slot >= GMVAE_LABEL_SLOTS || !w.clip_part) return GMVAE_E_DIMS;
+    const unsigned nb = (unsigned)clip_parts(L.P_pad);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(gclip_partials, dim3(nb), dim3(kClipBlock), 0, st, grads, (long long)L.P_pad, w.clip_part);
+    hipLaunchKernelGGL(gclip_finish_adam, dim3(nb), dim3(kClipBlock), 0, st, params, m, v, grads, (long long)L.P_pad, lr, beta1,
+                       beta2, epsilon, step_dev, w.clip_part, (int)nb, w.clip_norm, w.grad_clip + 4 * (size_t)slot, tail_log);
+    return (int)hipGetLastError();
+  }
   if (!scatter) {
     if (tail_log) hipMemcpyAsync(tail_log, grads + L.P_pad, GMVAE_TAIL * sizeof(float), hipMemcpyDeviceToDevice, st);
     return adam_tf_step(params, m, v, grads, L.P_pad, lr, beta1, beta2, epsilon, 0, step_dev, 1.f, grads + L.P_pad + 4,
@@ -4138,6 +4221,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
   if (step_inputs(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i reads slot i)
+  if (clip_norm(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;        // (step i writes record i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   hipStream_t cs;

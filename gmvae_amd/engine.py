@@ -104,6 +104,20 @@ def check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weight
         raise ValueError(f"pixel_mask=True is not available with y_estimator={y_estimator!r}")
 
 
+def check_clip_norm(clip_norm):
+    """The argument check of Engine(clip_norm=) and set_clip_norm (no device needed): None (off) or a threshold > 0; inf reports
+    the norm and never clips.  Returns the value as a float, or None."""
+    if clip_norm is None:
+        return None
+    try:
+        c = float(clip_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"clip_norm must be None or a number > 0, got {clip_norm!r}") from None
+    if not c > 0.0:                              # (NaN fails the comparison too)
+        raise ValueError(f"clip_norm must be None or a number > 0 (inf: report only), got {clip_norm!r}")
+    return c
+
+
 def _check_labels(engine, y_observed, B):
     if y_observed.dtype.is_floating_point or y_observed.dtype == torch.bool or y_observed.numel() != B:
         raise ValueError(f"y_observed must be an int tensor of {B} observed components (-1: unlabelled)")
@@ -162,7 +176,7 @@ class Engine:
                  y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
                  y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed",
-                 pixel_mask: bool = False):
+                 pixel_mask: bool = False, clip_norm: Optional[float] = None):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -195,7 +209,14 @@ class Engine:
         loss / forward / train_step / dp_step / iw_bound take mask=, a uint8 / bool tensor [B, D] (non-zero: observed; None:
         all observed).  The networks that read x see mask * x, the likelihood and every gradient count the observed pixels
         alone, and tail [5..7] report the held-out pixels' -log-likelihood and the missing / observed counts.  General
-        schedule.  Parameters and checkpoints are the same with and without it."""
+        schedule.  Parameters and checkpoints are the same with and without it.
+        clip_norm (every model and objective; include/gmvae_hip.h GMVAE_OPT_CLIP_NORM): None -- off, nothing changes -- or a
+        threshold C > 0: every optimizer step clips the batch-mean gradient by its global norm (tf.clip_by_global_norm in front
+        of apply_gradients; behind the all-reduce under data parallelism) and skips the update when the gradient or the loss is
+        not finite; float("inf") only reports.  grad_clip [4] = (norm before clipping, divisor, clipped 0 / 1, guard: the loss
+        sum or NaN where the step was skipped) of the last eager step; a captured graph hands out replay.grad_clip [n_steps, 4].
+        set_clip_norm changes C between steps and between replays without a host sync or a recapture.  General schedule."""
+        clip_norm = check_clip_norm(clip_norm)
         check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
                          y_estimator, pixel_mask)
         check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator)
@@ -248,6 +269,7 @@ class Engine:
         self.temperature_on_device = bool(temperature_on_device)
         self.y_estimator = y_estimator
         self.pixel_mask = bool(pixel_mask)
+        self.clip_norm = clip_norm
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -279,6 +301,14 @@ class Engine:
         self._tau_dev = None
         if self.temperature_on_device:
             self._tau_dev = torch.full((1,), float(temperature), dtype=torch.float32, device=self.device)
+        # gradient clipping: the current threshold on the device (every workspace's "clip_norm" cell is a copy of it), the record
+        # of the last eager step and the partials' scratch of gmvae_grad_clip
+        self._clip_dev = self.grad_clip = self._clip_scratch = None
+        self._clip_cells: Dict[tuple, torch.Tensor] = {}
+        if self.clip_norm is not None:
+            self._clip_dev = torch.full((1,), self.clip_norm, dtype=torch.float32, device=self.device)
+            self.grad_clip = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self._clip_scratch = torch.zeros(L.grad_clip_scratch_bytes(self.P) // 8, dtype=torch.float64, device=self.device)
         self.init_parameters(random_seed)
 
     @property
@@ -293,7 +323,7 @@ class Engine:
         # (the weighted objective is the one-sample bound's: a forward at another number of samples reports the plain bound)
         wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
         yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
-        pmask = L.OBJ_PIXEL_MASK if self.pixel_mask else 0
+        pmask = (L.OBJ_PIXEL_MASK if self.pixel_mask else 0) | (L.OPT_CLIP_NORM if self.clip_norm is not None else 0)
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
                            sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | pmask | extra_flags, **self.hp)
@@ -412,6 +442,7 @@ class Engine:
         if key in self._ws and self._ws[key].numel() < n:
             self.drop_graphs(clear_handoff_errors=False)      # captured graphs hold pointers into the old allocation
             del self._ws[key]
+            self._clip_cells.pop(key, None)
         if key not in self._ws:
             self._ws[key] = torch.zeros(n, dtype=torch.float32, device=self.device)
             # the library only reads the per-step inputs' regions (and the classification weight), and zeros would mean
@@ -422,7 +453,34 @@ class Engine:
             if self.semi_supervised:
                 off = L.workspace_offset(d, self.model, "sup_weight") // 4
                 self._ws[key][off:off + 1].fill_(self.sup_weight)
+            if d.sched_flags & L.OPT_CLIP_NORM:     # (a zeroed cell means C = 0: every step skipped)
+                off = L.workspace_offset(d, self.model, "clip_norm") // 4
+                self._clip_cells[key] = self._ws[key][off:off + 1]
+                self._clip_cells[key].copy_(self._clip_dev, non_blocking=True)
         return d, self._ws[key]
+
+    # ------------------------------------------------------- gradient clipping (clip_norm)
+    def _push_clip_norm(self):
+        """Every workspace's "clip_norm" cell <- the engine's threshold (device to device: a caller may have written a cell)."""
+        for cell in self._clip_cells.values():
+            cell.copy_(self._clip_dev, non_blocking=True)
+
+    def _clip_records(self, d, ws) -> torch.Tensor:
+        """View [LABEL_SLOTS, 4] of the workspace's "grad_clip" region: step i of a train graph writes row i."""
+        off = L.workspace_offset(d, self.model, "grad_clip") // 4
+        return ws[off:off + 4 * L.LABEL_SLOTS].view(L.LABEL_SLOTS, 4)
+
+    def set_clip_norm(self, clip_norm: float):
+        """The threshold the next optimizer steps read, eager or replayed: device-side writes, no host sync, no recapture."""
+        if self.clip_norm is None:
+            raise ValueError("set_clip_norm needs an engine created with clip_norm=")
+        c = check_clip_norm(clip_norm)
+        if c is None:
+            raise ValueError("set_clip_norm takes a number > 0: clipping cannot be switched off on an engine created with it "
+                             "(float('inf') never clips)")
+        self.clip_norm = c
+        self._clip_dev.fill_(c)
+        self._push_clip_norm()
 
     # ------------------------------------------------------- per-step inputs (STEP_INPUTS)
     @property
@@ -689,6 +747,14 @@ class Engine:
             self.global_step += 1
         count = g[self.P + 4:self.P + 5]
         loss_sum = g[self.P:self.P + 1]          # non-finite (poisoned step, on any rank) -> the update is skipped
+        if self.clip_norm is not None:
+            # the record of THIS buffer (behind train_step's all-reduce: the global gradient): its divisor stands where the count
+            # stood, its guard where the loss sum stood
+            self._push_clip_norm()
+            rc = L.lib.gmvae_grad_clip(L.ptr(g), self.P, L.ptr(self._clip_dev), L.ptr(self.grad_clip),
+                                       L.ptr(self._clip_scratch), L.current_stream())
+            L.check(rc, "gmvae_grad_clip")
+            count, loss_sum = self.grad_clip[1:2], self.grad_clip[3:4]
         rc = L.lib.adam_tf_step(L.ptr(self.params), L.ptr(self.m), L.ptr(self.v), L.ptr(g), self.P, lr, beta1, beta2,
                                 epsilon, self.global_step, L.ptr(self.step_dev) if use_step_dev else None, 1.0,
                                 L.ptr(count), L.ptr(loss_sum), L.current_stream())
@@ -764,12 +830,16 @@ class Engine:
         x = self._prep_x(x)
         d, ws = self._workspace(x.shape[0])
         self._bind_step_inputs(d, ws, y_observed, mask)
+        if self.clip_norm is not None:
+            self._push_clip_norm()
         self._keep = (x, None, None)
         self._param_epoch += 1
         rc = L.lib.gmvae_dp_step(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v),
                                  L.ptr(self.grads), L.ptr(ws), self.noise_seed, L.ptr(self.step_dev), lr, beta1, beta2,
                                  epsilon, self._comm, L.current_stream())
         L.check(rc, "gmvae_dp_step")
+        if self.clip_norm is not None:
+            self.grad_clip.copy_(self._clip_records(d, ws)[0], non_blocking=True)      # (gmvae_dp_step writes record 0)
         self.global_step += 1
         return self.grads[self.P:]
 
@@ -787,7 +857,8 @@ class Engine:
         engine has none): replay.y_observed [n_steps, B] (int32; pre-filled -1 = unlabelled), replay.obj_weights [n_steps, 4]
         (kl_weight, y_weight, y_free_nats, 0; pre-filled with the engine's current weights), replay.y_temperature [n_steps]
         (pre-filled with the engine's current temperature) and replay.pixel_mask [n_steps, B, D] (uint8; pre-filled 1 = all
-        observed) are VIEWS of the workspace's regions: step i of the graph reads row i, the caller fills them before replay().
+        observed) are VIEWS of the workspace's regions; replay.grad_clip [n_steps, 4] (clip_norm; None without it) is the view of
+        the records the launch WRITES (norm, divisor, clipped, guard per step): step i of the graph reads row i, the caller fills them before replay().
         Row 0 is also what every eager entry (step / loss / forward / train_step / dp_step) on the same batch size writes
         before it runs -- the engine's current weights and temperature, its y_observed and mask -- so after any eager call
         row 0 holds that call's values until the caller refills it: fill the rows before EVERY replay (run_train does)."""
@@ -799,8 +870,12 @@ class Engine:
         if active and n_steps > L.LABEL_SLOTS:
             raise ValueError(f"a train graph of an engine with {active[0].option}=True holds at most {L.LABEL_SLOTS} steps (one "
                              f"{active[0].noun} per step), got {n_steps}")
+        clip = self.clip_norm is not None
+        if clip and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph of an engine with clip_norm holds at most {L.LABEL_SLOTS} steps (one clip record "
+                             f"per step), got {n_steps}")
         adam_hp = (float(beta1), float(beta2), float(epsilon))
-        key = (B, lr, do_ar, n_steps) + adam_hp
+        key = (B, lr, do_ar, n_steps) + adam_hp + (clip,)
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)   # eager steps may have run since the capture
             return self._graphs[key][:2]
@@ -815,9 +890,11 @@ class Engine:
         self.step_dev.fill_(self.global_step)
         # per-step tails of one launch (loss sums + count; all-reduced under data parallelism): replay.tail_log
         tail_log = torch.zeros(n_steps, L.TAIL, dtype=torch.float32, device=self.device)
+        records = self._clip_records(d, ws)[:n_steps] if clip else None      # step i writes row i
 
         def hand_out(replay, handle):
             replay.tail_log = tail_log
+            replay.grad_clip = records
             for inp in STEP_INPUTS:
                 setattr(replay, inp.replay, rows.get(inp))
             self._graphs[key] = (static_x, replay, handle)
@@ -844,6 +921,7 @@ class Engine:
             def replay():
                 saved = {inp: view.clone() for inp, view in rows.items()}
                 own = {inp: getattr(self, inp.held).clone() for inp in rows if inp.held}
+                recs = []
                 for i in range(n_steps):
                     args = {}
                     for inp, r in saved.items():
@@ -853,6 +931,10 @@ class Engine:
                             args[inp.arg] = r[i]
                     step(batches[i], **args)
                     tail_log[i].copy_(self.grads[self.P:])
+                    if clip:
+                        recs.append(self.grad_clip.clone())      # (an eager C-side step writes row 0 itself: rows go in last)
+                if recs:
+                    records.copy_(torch.stack(recs))
                 for inp, r in saved.items():
                     rows[inp][0].copy_(r[0])
                     if inp.held:
@@ -906,7 +988,11 @@ class Engine:
                                  f"nor one for weight rows, temperatures or masks: an engine with {inp.option}=True trains "
                                  f"through capture_train_step (replay.{inp.replay})")
         n_steps = int(n_steps)
-        key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon))
+        clip = self.clip_norm is not None
+        if clip and n_steps > L.LABEL_SLOTS:
+            raise ValueError(f"a train graph of an engine with clip_norm holds at most {L.LABEL_SLOTS} steps (one clip record "
+                             f"per step), got {n_steps}")
+        key = ("pipeline", id(dataset), B, lr, n_steps, float(beta1), float(beta2), float(epsilon), clip)
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)
             return self._graphs[key][1]
@@ -936,6 +1022,7 @@ class Engine:
             self.global_step += n_steps
 
         replay.rows, replay.batches, replay.tail_log = idx, xs, tail_log   # the buffers of the last launch (tests, summaries)
+        replay.grad_clip = self._clip_records(d, ws)[:n_steps] if clip else None
         self._graphs[key] = (xs, replay, handle)
         return replay
 

@@ -78,6 +78,9 @@ def build_parser():
       "missing independently with this probability -- ONE fixed mask per row, the same in train and eval; the loss, the "
       "gradients and --iw_samples count the observed pixels alone, the missing ones are scored as imputation_nll (0 = off)")
     a("--missing_seed", type=int, default=0, help="seed of --missing_rate's masks")
+    a("--clip_norm", type=float, default=0.0, help="train: clip the batch-mean gradient by its global norm to this threshold "
+      "in front of Adam and skip the steps whose gradient or loss is not finite; the log reports the norm's mean and maximum "
+      "and the clipped and skipped shares per summary window (inf: report only; 0 = off)")
     return p
 
 
@@ -132,6 +135,8 @@ def check_args(p, cfg):
         p.error("--temperature must be > 0; --temperature_min, --temperature_anneal_rate and --temperature_anneal_every >= 0")
     if cfg.temperature_anneal_rate > 0 and cfg.temperature_anneal_every > 0 and not cfg.temperature_min > 0:
         p.error("an annealed temperature needs a floor: --temperature_min must be > 0")
+    if not cfg.clip_norm >= 0:
+        p.error("--clip_norm must be >= 0 (0 = off)")
     if not 0.0 <= cfg.missing_rate < 1.0:
         p.error("--missing_rate must be in [0, 1)")
     if cfg.missing_rate > 0:

@@ -128,12 +128,19 @@ def missing_mask(config, split: str, n_rows: int, data_dim: int):
     return (rng.random((int(n_rows), int(data_dim)), dtype=np.float32) >= p).astype(np.uint8)
 
 
-def create_model(config, data_dim, weighted=None, temperature_on_device=None):
+def clip_norm_of(config):
+    """--clip_norm C: Engine's clip_norm -- None for 0 (off), else the threshold (inf: report only)."""
+    c = float(getattr(config, "clip_norm", 0.0) or 0.0)
+    return c if c > 0.0 else None
+
+
+def create_model(config, data_dim, weighted=None, temperature_on_device=None, clip=None):
     """scripts/runners.py:65-103: binds the flags and FIXES sigma_min=0.0, raw_sigma_bias=0.5 (and temperature=1.0 unless
     --temperature says otherwise).
     weighted: create the engine with the weighted objective (None: as the flags say; run_eval passes False, so that its
     numbers stay comparable).  temperature_on_device: likewise for the temperature flags (run_eval passes False: it sets one
-    temperature, which travels in the dims)."""
+    temperature, which travels in the dims).  clip: likewise for --clip_norm (run_eval passes False: it runs no optimizer)."""
+    pclip = dict(clip_norm=clip_norm_of(config) if clip is None or clip else None)
     wobj = dict(weighted_objective=weighted_flags(config) if weighted is None else bool(weighted))
     yhead = dict(temperature_on_device=temperature_flags(config) if temperature_on_device is None else bool(temperature_on_device),
                  y_estimator=getattr(config, "y_estimator", "relaxed"))
@@ -149,16 +156,16 @@ def create_model(config, data_dim, weighted=None, temperature_on_device=None):
                                   fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
                                   temperature=temperature_at(config, 0), random_seed=config.random_seed, n_samples=ns,
                                   y_inference=getattr(config, "y_inference", "gumbel"), grad_estimator=ge,
-                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj, **yhead, **pmask)
+                                  semi_supervised=lpc > 0, sup_weight=float(getattr(config, "sup_weight", 1.0)), **wobj, **yhead, **pmask, **pclip)
     if temperature_flags(config) or yhead["y_estimator"] != "relaxed":
         raise ValueError("--temperature* and --y_estimator belong to the GMVAE's Gumbel-softmax draw: they need --model=gmvae")
     if config.model == "vae_gmp":
         return vae.create_vae(data_dim, config.latent_size, mixture_components=config.mixture_components,
                               fcnet_hidden_sizes=hidden, sigma_min=0.0, raw_sigma_bias=0.5,
-                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask)
+                              random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask, **pclip)
     if config.model == "vae":
         return vae.create_vae(data_dim, config.latent_size, fcnet_hidden_sizes=hidden, sigma_min=0.0,
-                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask)
+                              raw_sigma_bias=0.5, random_seed=config.random_seed, n_samples=ns, grad_estimator=ge, **wobj, **pmask, **pclip)
     raise ValueError(f"unknown model {config.model!r}")
 
 
@@ -267,7 +274,7 @@ def _verify_launch(eng, snap, batches, g, lr):
     hp.pop("gen_bias_init", None)
     sh = Engine(eng.model_name, eng.D, eng.Lz, eng.K, eng.hidden, n_samples=eng.S, gen_bias_init=gb, random_seed=0,
                 y_inference=eng.y_inference, grad_estimator=eng.grad_estimator, semi_supervised=eng.semi_supervised,
-                sup_weight=eng.sup_weight, y_estimator=eng.y_estimator, **hp)
+                sup_weight=eng.sup_weight, y_estimator=eng.y_estimator, clip_norm=eng.clip_norm, **hp)
     sh.rank, sh.noise_seed = eng.rank, eng.noise_seed
     with torch.no_grad():
         sh.params.copy_(p0); sh.m.copy_(m0); sh.v.copy_(v0)
@@ -346,6 +353,9 @@ def run_train(config):
     hook = utils.EarlyStoppingHook(config.early_stop_rounds, config.early_stop_threshold)
     last_save, t0, s0 = time.time(), time.time(), eng.global_step
     logs = []                                               # device tensors [n, TAIL]: no host sync until a summary
+    clips = []                                              # --clip_norm: device tensors [n, 4], the steps' clip records
+    clip = eng.clip_norm is not None
+    run_train.clip_log = []                                 # per summary window: dict(mean, max, clipped_share, skipped_share, steps)
     last_x = last_rows = None
 
     def run(n):
@@ -364,6 +374,8 @@ def run_train(config):
                     eng.set_temperature(run_train.temperature_log[0][1])
                 mk = ds.pixel_mask[rows.long()] if "pixel_mask" in inputs else None
                 logs.append(eng.train_step(x, lr=lr, y_observed=yo, mask=mk).clone().view(1, -1))
+                if clip:
+                    clips.append(eng.grad_clip.clone().view(1, 4))
                 last_x, last_rows, g = x, rows, 1
             elif world == 1 and not inputs:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
@@ -376,6 +388,8 @@ def run_train(config):
                     _verify_launch(eng, snap, replay.batches.clone(), g, lr)
                     run_train.verified_launches += 1
                 logs.append(replay.tail_log.clone())
+                if clip:
+                    clips.append(replay.grad_clip.clone())
                 last_x, last_rows = replay.batches[g - 1], replay.rows[g - 1]
             else:
                 sx, replay = eng.capture_train_step(B, lr=lr, all_reduce=world > 1, n_steps=g)
@@ -397,6 +411,8 @@ def run_train(config):
                                                non_blocking=True)
                 replay()
                 logs.append(replay.tail_log.clone())
+                if clip:
+                    clips.append(replay.grad_clip.clone())      # (read once per launch, next to tail_log)
                 last_x = xs[g - 1]
             n -= g
 
@@ -406,6 +422,20 @@ def run_train(config):
         run(n)
         tails = torch.cat(logs).cpu()                       # the summary's host sync
         logs = []
+        clip_msg = ""
+        if clip:
+            # the window's clip records: the norm's mean and maximum over the applied steps, the clipped share of those, and the
+            # share the optimizer skipped (guard NaN: a gradient or a loss that is not finite, or a threshold that is not > 0)
+            recs = torch.cat(clips).cpu().double()
+            clips = []
+            applied = recs[torch.isfinite(recs[:, 3])]
+            win = dict(steps=int(recs.shape[0]), skipped_share=1.0 - applied.shape[0] / max(recs.shape[0], 1),
+                       mean=applied[:, 0].mean().item() if len(applied) else float("nan"),
+                       max=applied[:, 0].max().item() if len(applied) else float("nan"),
+                       clipped_share=applied[:, 2].mean().item() if len(applied) else 0.0)
+            run_train.clip_log.append(win)
+            clip_msg = (f"  grad_norm mean {win['mean']:.4g} max {win['max']:.4g}  clipped {win['clipped_share']:.3f}"
+                        f"  skipped {win['skipped_share']:.3f}")
         vals = (tails[:, 0] / tails[:, 4]).tolist()
         base = eng.global_step - len(vals)
         if "weighted_objective" in inputs:
@@ -458,7 +488,7 @@ def run_train(config):
             continue
         if rank == 0 and (eng.global_step % every == 0 or eng.global_step > config.max_steps):
             rate = (eng.global_step - s0) / max(time.time() - t0, 1e-9)
-            msg = f"Step {eng.global_step}, loss: {vals[-1]:f}  ({rate:.1f} global_step/sec)"
+            msg = f"Step {eng.global_step}, loss: {vals[-1]:f}  ({rate:.1f} global_step/sec)" + clip_msg
             if "weighted_objective" in inputs:
                 msg += (f"  kl_weight {run_train.weight_log[-1][1]:.4f}  y_weight {run_train.weight_log[-1][2]:.4f}"
                         f"  y_floor_share {(tails[-1, 7] / tails[-1, 4]).item():.4f}")
@@ -497,7 +527,7 @@ def run_eval(config):
     rank, world, local = parallel.init_from_env()
     torch.cuda.set_device(select_device(config, local))
     data_dim = int(getattr(config, "data_dim", 784))
-    model = create_model(config, data_dim, weighted=False,     # (the weighting flags are training's: the reported terms stay unweighted)
+    model = create_model(config, data_dim, clip=False, weighted=False,     # (the weighting flags are training's: the reported terms stay unweighted)
                          temperature_on_device=False)
     wait_for_checkpoint(_ckpt(config), float(getattr(config, "checkpoint_poll_seconds", 60.0)),
                         getattr(config, "checkpoint_max_wait", None))

@@ -294,7 +294,47 @@ enum { GMVAE_SCHED_SAFE = 1,
         * multiply there.  The masked Bernoulli epilogue (fp32 C, interior and edge tiles) keeps the observed and the held-out
         * sums as two chains; nothing assumes D % 4 == 0 (the 4-byte interior path's alignment conditions extend to the mask).
         * No atomics: eager and captured steps give the same bits. */
-       GMVAE_OBJ_PIXEL_MASK = 512 };
+       GMVAE_OBJ_PIXEL_MASK = 512,
+       /* optimizer (all three models, any S, together with every combination of the bits above that is legal without it): the
+        * gradient is clipped by its GLOBAL NORM in front of TF-Adam -- tf.clip_by_global_norm on the batch-mean gradient, written so
+        * that nothing is divided by the norm.  With g the gradient SUMS grads[0, P_padded), count = grads[P_padded + 4],
+        * SS = sum_i g_i^2 and C the threshold:
+        *   norm = sqrt(SS) / count                 the global norm of the mean gradient, before clipping
+        *   d    = max(count, sqrt(SS) / C)         g_i / d = (g_i / count) min(1, C / norm)
+        * and Adam applies g_i (1 / d): adam_tf_step's statement with d where the count stood.  SS = 0 gives d = count (no 0 / 0);
+        * C = +inf never clips and only reports.  The step is SKIPPED -- params, m and v keep their bits, the step counter advances,
+        * as for a poisoned step -- unless C > 0 (zero, negative, NaN: skipped), SS is finite (any NaN or +-inf gradient element:
+        * skipped) and the loss sum grads[P_padded] is finite.
+        * SS is a two-stage fixed-order reduction without float atomics: partial k covers elements [1024 k, 1024 (k + 1)), every
+        * square exact in fp64, fp64 sums in a fixed order inside the block, the partials added in index order; sqrt, the division by
+        * (double)C and the max in fp64, ONE rounding to fp32.  The padding words of the gradient buffer count towards SS: they are
+        * zero after every step (the split-K slabs' padding is never written).  The record, 4 floats:
+        *   [0] norm   [1] d   [2] 1.0 if d > count (the step was clipped) else 0.0   [3] the guard: the loss sum, or NaN where the
+        *   step is skipped
+        * shaped for adam_tf_step(..., grad_scale_dev = &rec[1], loss_sum_dev = &rec[3]).
+        * The workspace grows BEHIND every other buffer by three regions, each rounded up to 256 bytes:
+        *   "clip_norm"  one float, C, at the start of its cell
+        *   "grad_clip"  float [GMVAE_LABEL_SLOTS][4]: the records
+        *   (unnamed)    double [ceil(P_padded / 1024)]: the partials
+        * (gmvae_workspace_offset answers for the two names; GMVAE_E_NET without the bit).  The CALLER writes "clip_norm"; the library
+        * only reads it.  A zeroed workspace means C = 0, every step skipped: a caller fills it before the first step
+        * (gmvae_amd.Engine does).  The library writes "grad_clip".
+        * Who writes which record: gmvae_dp_step and gmvae_bench_loop write record 0; step i of gmvae_train_graph_create's,
+        * gmvae_train_graph_create_pipeline's and gmvae_dp_graph_create's graph writes record i (n_steps > GMVAE_LABEL_SLOTS:
+        * GMVAE_E_DIMS from all three; the pipeline graph ACCEPTS the bit -- it has nothing to gather).  In the data-parallel forms
+        * the norm is taken on the ALL-REDUCED buffer with the global count: every rank forms the same bits, the replicas stay
+        * identical.  gmvae_step sizes and schedules by the bit but runs no optimizer and writes no record (the eager path is
+        * gmvae_grad_clip on its buffer, then adam_tf_step on the record).  The forward-only entries take the schedule they take
+        * without the bit; gmvae_iw_bound* and gmvae_posterior_* mask it off.  gmvae_train_profile and gmvae_dp_profile return
+        * GMVAE_E_DIMS (they stamp the fused optimizer launches); gmvae_step_profile honours it.
+        * A training step with the bit takes the general schedule: finalize_grads leaves the partials (it holds every gradient
+        * element in registers), one launch forms the record and applies TF-Adam -- ONE launch more than the same step without the
+        * bit; behind an all-reduce the reduced buffer gets a partials pass of its own.  gmvae_step_schedule appends "+clip" behind
+        * "+dreg":
+        *   <schedule> [+marginal | +marginal_iw] [+labels] [+weights] [+temp] [+st] [+mask] [+dreg] [+clip] [+planes]
+        * ("general+clip", "general+marginal_iw+labels+dreg+clip").  The eager call, the 1-step graph, the n-step graph and the
+        * one-rank data-parallel forms of a step give the same record and the same update, bit for bit. */
+       GMVAE_OPT_CLIP_NORM = 1024 };
 #define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) / masks (GMVAE_OBJ_PIXEL_MASK) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
@@ -475,6 +515,14 @@ int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t
                  float beta2, float epsilon, uint64_t t, const uint64_t* t_dev, float grad_scale,
                  const float* grad_scale_dev, const float* loss_sum_dev, void* stream);
 
+/* GMVAE_OPT_CLIP_NORM's statement on a gradient buffer, for the eager path: grads [P + GMVAE_TAIL] (P a multiple of 4: P_padded)
+ * holds gradient sums and the tail, clip_norm_dev one float C, rec_out float[4] receives the record (norm, d, clipped, guard),
+ * scratch holds the fp64 partials (gmvae_grad_clip_scratch_bytes(P) bytes, 16-byte aligned).  Two launches on `stream`; then
+ * adam_tf_step(..., grad_scale_dev = rec_out + 1, loss_sum_dev = rec_out + 3) applies the clipped update or skips it.
+ * GMVAE_E_NULL; GMVAE_E_DIMS (P == 0 or P % 4); GMVAE_E_ALIGN (grads, scratch). */
+int gmvae_grad_clip_scratch_bytes(uint64_t P, uint64_t* bytes);
+int gmvae_grad_clip(const float* grads, uint64_t P, const float* clip_norm_dev, float* rec_out, void* scratch, void* stream);
+
 /* One conditional network's MLP (scripts/base.py:66-67,133-135,196-198):
  * out[rows, out_dim] = MLP(concat(in, in2)) (+ gen_bias_init for the decoder).
  * `in` is uint8 when in_is_u8 else fp32.  in2 is y for ENCODER_GMM, else NULL.
@@ -612,7 +660,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "clip_norm" and "grad_clip" under GMVAE_OPT_CLIP_NORM; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -627,7 +675,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+dreg" under GMVAE_GRAD_DREG, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
