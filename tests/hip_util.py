@@ -1,4 +1,8 @@
-"""Helpers for the -m gpu parity tests: call the C ABI with torch device buffers."""
+"""Helpers for the -m gpu parity tests: call the C ABI with torch device buffers.
+
+hip_step, hip_forward, forward_call, chunked_call and compare_step take an optional alloc= (tests/arena.py): every device buffer
+of the call, dims_of's gen_bias_vec included, then lies in that arena at its exact size -- the workspace at exactly the bytes its
+size query answers, zeroed; every output 0xFF -- and the arena's check() runs before the results come back."""
 import ctypes as C
 import dataclasses
 
@@ -9,9 +13,11 @@ import oracle as O
 from gmvae_amd import _lib as L
 
 
-def dims_of(d: O.Dims, B: int):
+def dims_of(d: O.Dims, B: int, alloc=None):
     gb = np.asarray(d.gen_bias_init, np.float32)
     vec = torch.from_numpy(gb.copy()).cuda() if gb.ndim else None        # vector bias_init (ABI v3)
+    if alloc is not None and gb.ndim:
+        vec = put(alloc, "gen_bias_vec", gb, torch.float32, 4 * d.D)
     cd = L.make_dims(B, d.D, d.L, d.K, d.hidden, S=d.S, sigma_min=d.sigma_min, raw_sigma_bias=d.raw_sigma_bias,
                      temperature=d.temperature, gen_bias_init=0.0 if gb.ndim else float(gb), gen_bias_vec=vec,
                      hidden_act=getattr(d, "act", "relu"))
@@ -28,6 +34,110 @@ def dev(a, dtype=None):
 
 def workspace(cd, model):
     return torch.zeros(L.workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
+
+
+# ---- alloc=: the same calls with every device buffer inside a guarded arena (tests/arena.py; tests/test_memory_contract.py) ----
+def pitch_of(d):
+    """The longest row, in bytes, of any fp32 matrix a call of these dims stores: the arena's guard bands follow it."""
+    return 4 * max(d.D, 2 * d.L, d.K, *d.hidden)
+
+
+def put(alloc, name, a, dtype, pitch):
+    """A read-only input placed in `alloc` and filled from the host array `a`."""
+    t = torch.as_tensor(np.ascontiguousarray(a)).to(dtype).reshape(-1)
+    v = alloc.place(name, t.numel() * t.element_size(), pitch, False, dtype=dtype)
+    v.copy_(t)
+    return v
+
+
+def out(alloc, name, shape, pitch):
+    """A writable fp32 output placed in `alloc`: every byte 0xFF (a NaN) until the call writes it."""
+    return alloc.place(name, 4 * int(np.prod(shape)), pitch, True, dtype=torch.float32).view(*shape)
+
+
+def exact_workspace(alloc, nbytes, pitch, name="workspace"):
+    """The workspace at exactly the bytes its size query answered, zeroed, writable, as a float32 view."""
+    assert nbytes % 4 == 0
+    ws = alloc.place(name, nbytes, pitch, True, dtype=torch.float32)
+    ws.zero_()
+    return ws
+
+
+def run_checked(alloc, what, call):
+    """snapshot, the call, check: GuardHit if a byte changed outside the writable set."""
+    alloc.snapshot()
+    L.check(call(), what)
+    alloc.check()
+
+
+def _hip_step_in(alloc, model, d, flat, x, eps, u, seed, step, want_masks):
+    alloc.reset()
+    B = x.shape[0]
+    cd = dims_of(d, B, alloc)
+    P, _ = L.param_count(cd, model)
+    pitch = pitch_of(d)
+    params = put(alloc, "params", flat, torch.float32, pitch)
+    xd = put(alloc, "x", x, torch.uint8, d.D)
+    ed = None if eps is None else put(alloc, "eps", eps, torch.float32, 4 * d.L)
+    ud = None if u is None else put(alloc, "u", u, torch.float32, 4 * d.K)
+    grads = out(alloc, "grads", (P + L.TAIL,), pitch)                     # writable: grads[0, P_padded + 8)
+    ws = exact_workspace(alloc, L.workspace_bytes(cd, model), pitch)
+    run_checked(alloc, "gmvae_step", lambda: L.lib.gmvae_step(
+        C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws), seed, step, None,
+        L.current_stream()))
+    g = grads.cpu().numpy().astype(np.float64)
+    if want_masks:
+        return g[:P], g[P:], device_masks(ws, cd, model, d, B)
+    return g[:P], g[P:]
+
+
+FORWARD_OUTPUTS = ("rows", "z", "y", "logits")
+
+
+def forward_in(alloc, model, d, flat, x, eps, u, row0=0, flags=0, seed=0, step=0, outputs=FORWARD_OUTPUTS, prepare=None):
+    """gmvae_forward at d.S samples with every buffer in `alloc`: dict of tail [8] and the optional outputs named in `outputs`
+    (rows [R, 4], z [R, L], y [R, K], logits [B, K]; the others are passed as NULL) as numpy.  prepare(cd, ws): fills the
+    caller-written workspace regions and narrows the writable set before the call."""
+    alloc.reset()
+    B = x.shape[0]
+    cd = dims_of(d, B, alloc)
+    cd.row0, cd.sched_flags = row0, flags
+    R = B * d.S * (d.K if flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW) else 1)
+    pitch = pitch_of(d)
+    params = put(alloc, "params", flat, torch.float32, pitch)
+    xd = put(alloc, "x", x, torch.uint8, d.D)
+    ed = None if eps is None else put(alloc, "eps", eps, torch.float32, 4 * d.L)
+    ud = None if u is None else put(alloc, "u", u, torch.float32, 4 * d.K)
+    shapes = {"rows": (R, 4), "z": (R, d.L), "y": (R, d.K), "logits": (B, d.K)}
+    o = {"tail": out(alloc, "tail", (L.TAIL,), 4 * L.TAIL)}
+    for k in FORWARD_OUTPUTS:
+        o[k] = out(alloc, k, shapes[k], 4 * shapes[k][1]) if k in outputs else None
+    ws = exact_workspace(alloc, L.workspace_bytes(cd, model), pitch)
+    if prepare is not None:
+        prepare(cd, ws)
+    run_checked(alloc, "gmvae_forward", lambda: L.lib.gmvae_forward(
+        C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(o["tail"]), L.ptr(o["rows"]), L.ptr(o["z"]),
+        L.ptr(o["y"]), L.ptr(o["logits"]), L.ptr(ws), seed, step, L.current_stream()))
+    return {k: t.cpu().numpy() for k, t in o.items() if t is not None}
+
+
+def chunked_in(alloc, kind, model, d, flat, x, n, chunk, row0=0, flags=0, seed=0, step=0, omit=()):
+    """chunked_call with every buffer in `alloc`, the workspace at exactly gmvae_<kind>_workspace_bytes."""
+    alloc.reset()
+    B = x.shape[0]
+    cd = dims_of(dataclasses.replace(d, S=chunk), B, alloc)
+    cd.row0, cd.sched_flags = row0, flags
+    pitch = pitch_of(d)
+    shape = {"bound": (B,), "mean_logw": (B,), "log_joint": (B, d.K), "log_post": (B, d.K), "stats": (B, 4)}
+    o = {k: None if k in omit else out(alloc, k, shape[k], 4 * shape[k][-1]) for k in CHUNKED_OUTPUTS[kind]}
+    o["tail"] = out(alloc, "tail", (L.TAIL,), 4 * L.TAIL)
+    params = put(alloc, "params", flat, torch.float32, pitch)
+    xd = put(alloc, "x", x, torch.uint8, d.D)
+    ws = exact_workspace(alloc, getattr(L, f"{kind}_workspace_bytes")(cd, model), pitch)
+    run_checked(alloc, f"gmvae_{kind}", lambda: getattr(L.lib, f"gmvae_{kind}")(
+        C.byref(cd), model, L.ptr(xd), L.ptr(params), n, *(L.ptr(t) for t in o.values()), L.ptr(ws), seed, step,
+        L.current_stream()))
+    return {k: t.cpu().numpy() for k, t in o.items() if t is not None}
 
 
 NETS = {O.MODEL_GMVAE: (("encoder_y", "he", False), ("encoder_gmm", "hg", True), ("decoder", "hd", True)),
@@ -69,8 +179,10 @@ def check_masks(masks, pres, what):
     return n
 
 
-def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False):
+def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False, alloc=None):
     """Returns (grads_sum[P_pad] float64 numpy, tail[8]) (+ the step's ReLU masks with want_masks)."""
+    if alloc is not None:
+        return _hip_step_in(alloc, model, d, flat, x, eps, u, seed, step, want_masks)
     B = x.shape[0]
     cd = dims_of(d, B)
     P, _ = L.param_count(cd, model)
@@ -90,7 +202,10 @@ def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False
     return g[:P], g[P:]
 
 
-def hip_forward(model, d: O.Dims, flat, x, eps, u, want_rows=True):
+def hip_forward(model, d: O.Dims, flat, x, eps, u, want_rows=True, alloc=None):
+    if alloc is not None:
+        o = forward_in(alloc, model, d, flat, x, eps, u)
+        return o["tail"], o["rows"], o["z"], o["y"], o["logits"]
     B = x.shape[0]
     cd = dims_of(d, B)
     R = B * d.S
@@ -110,9 +225,13 @@ def hip_forward(model, d: O.Dims, flat, x, eps, u, want_rows=True):
     return tail.cpu().numpy(), rows.cpu().numpy(), z.cpu().numpy(), y.cpu().numpy(), lg.cpu().numpy()
 
 
-def forward_call(model, d: O.Dims, flat, x, S, eps=None, u=None, row0=0, flags=0, seed=0, step=0, logits=False):
+def forward_call(model, d: O.Dims, flat, x, S, eps=None, u=None, row0=0, flags=0, seed=0, step=0, logits=False, alloc=None):
     """gmvae_forward at S samples under sched_flags `flags` (in-kernel noise when eps is None): (tail [8], rows [R, 4], logits
     [B, K] or None) as numpy, R = B S rows, B S K with y summed out.  Every output starts as NaN."""
+    if alloc is not None:
+        o = forward_in(alloc, model, dataclasses.replace(d, S=S), flat, x, eps, u, row0, flags, seed, step,
+                       ("rows", "logits") if logits else ("rows",))
+        return o["tail"], o["rows"], o.get("logits")
     B = x.shape[0]
     cd = dims_of(dataclasses.replace(d, S=S), B)
     cd.row0, cd.sched_flags = row0, flags
@@ -136,10 +255,12 @@ CHUNKED_OUTPUTS = {"iw_bound": ("bound", "mean_logw"), "iw_bound_enum_y": ("boun
                    "posterior_y": ("log_joint", "log_post", "stats"), "posterior_component": ("log_joint", "log_post", "stats")}
 
 
-def chunked_call(kind, model, d: O.Dims, flat, x, n, chunk, row0=0, flags=0, seed=0, step=0, omit=()):
+def chunked_call(kind, model, d: O.Dims, flat, x, n, chunk, row0=0, flags=0, seed=0, step=0, omit=(), alloc=None):
     """One gmvae_<kind> call at n samples in passes of `chunk`: dict of its outputs (CHUNKED_OUTPUTS; bound and mean_logw [B],
     log_joint and log_post [B, K], stats [B, 4]) and tail [8] as numpy.  Every output starts as NaN; the ones named in `omit`
     are passed as NULL and left out."""
+    if alloc is not None:
+        return chunked_in(alloc, kind, model, d, flat, x, n, chunk, row0, flags, seed, step, omit)
     B = x.shape[0]
     cd = dims_of(dataclasses.replace(d, S=chunk), B)
     cd.row0, cd.sched_flags = row0, flags
@@ -165,7 +286,7 @@ def lse(v, axis=None):
 MARGINS = []      # (what, worst error / its gate) of every compare_step call: tests/test_hip_parity.py prints the maxima
 
 
-def compare_step(model, d, p, x, eps, u, loss_rtol=1e-4, grad_rtol=1e-4):
+def compare_step(model, d, p, x, eps, u, loss_rtol=1e-4, grad_rtol=1e-4, alloc=None):
     """HIP step vs the fp64 oracle on identical (params, x, eps, u).  Gates: the ELBO at loss_rtol
     relative (north_star's 1e-4), and EACH term relative to ITSELF -- |d nll| <= 1e-4 |nll|, |d kl| <= 1e-4 max(|kl|, 1),
     |d nent| <= 1e-4 max(|nent|, 1) -- so that the O(1-10) kl and entropy terms cannot hide inside the budget of an
@@ -179,7 +300,7 @@ def compare_step(model, d, p, x, eps, u, loss_rtol=1e-4, grad_rtol=1e-4):
     flat = O.pack(model, d, p, np.float32)
     p32 = O.unpack(model, d, flat.astype(np.float64))            # the values the GPU actually sees
     Cc, g = O.loss_and_grads(model, d, p32, x, eps, u, np.float64)
-    gs, tail, masks = hip_step(model, d, flat, x, eps, u, want_masks=True)
+    gs, tail, masks = hip_step(model, d, flat, x, eps, u, want_masks=True, alloc=alloc)
     assert tail[4] == B
     loss = tail[0] / B
     assert abs(loss - Cc["loss"]) <= loss_rtol * abs(Cc["loss"]), (loss, Cc["loss"])
