@@ -179,12 +179,38 @@ def check_masks(masks, pres, what):
     return n
 
 
-def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False, alloc=None):
-    """Returns (grads_sum[P_pad] float64 numpy, tail[8]) (+ the step's ReLU masks with want_masks)."""
+INPUT_DTYPES = {"labels": np.int32, "pixel_mask": np.uint8}        # of the per-step inputs' regions; every other one is fp32
+
+
+def write_inputs(ws, cd, model, inputs):
+    """Slot 0 of the caller-written workspace regions: inputs = {region name (gmvae_workspace_offset's: labels, sup_weight,
+    obj_weights, y_temperature, pixel_mask): host array}.  Every other label set is -1 (unlabelled); the other slots of the other
+    regions stay 0 (a kernel reading another temperature slot gives NaN)."""
+    raw = ws.view(torch.uint8)
+    nbytes = ws.numel() * ws.element_size()
+    for name, a in inputs.items():
+        off = L.workspace_offset(cd, model, name)
+        if name == "labels":
+            n = 4 * L.LABEL_SLOTS * ((cd.B + 3) // 4 * 4)
+            assert off + n <= nbytes
+            raw[off:off + n].fill_(255)
+        h = torch.from_numpy(np.ascontiguousarray(a, INPUT_DTYPES.get(name, np.float32)).reshape(-1).view(np.uint8))
+        assert off + h.numel() <= nbytes, (name, off, h.numel(), nbytes)
+        raw[off:off + h.numel()].copy_(h)
+
+
+def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False, alloc=None, flags=0, row0=0, mask_rows=None,
+             inputs=None, want_ws=False):
+    """One gmvae_step under sched_flags `flags` at row0 (in-kernel noise where eps / u is None).  Returns (grads_sum[P_pad]
+    float64 numpy, tail[8]) (+ the step's ReLU masks with want_masks: mask_rows = the rows per example of the per-sample nets,
+    d.S by default, S K with y summed out) (+ the workspace as a float32 device tensor and the dims with want_ws).  inputs:
+    write_inputs' mapping.  The alloc= arena form takes the first nine arguments only."""
     if alloc is not None:
+        assert not flags and not row0 and mask_rows is None and inputs is None and not want_ws
         return _hip_step_in(alloc, model, d, flat, x, eps, u, seed, step, want_masks)
     B = x.shape[0]
     cd = dims_of(d, B)
+    cd.sched_flags, cd.row0 = flags, row0
     P, _ = L.param_count(cd, model)
     params = dev(flat, torch.float32)
     xd = dev(x, torch.uint8)
@@ -192,14 +218,17 @@ def hip_step(model, d: O.Dims, flat, x, eps, u, seed=0, step=0, want_masks=False
     ud = None if u is None else dev(u, torch.float32)
     grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
     ws = workspace(cd, model)
+    if inputs:
+        write_inputs(ws, cd, model, inputs)
     rc = L.lib.gmvae_step(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws),
                           seed, step, None, L.current_stream())
     L.check(rc, "gmvae_step")
     torch.cuda.synchronize()
     g = grads.cpu().numpy().astype(np.float64)
+    out = (g[:P], g[P:])
     if want_masks:
-        return g[:P], g[P:], device_masks(ws, cd, model, d, B)
-    return g[:P], g[P:]
+        out += (device_masks(ws, cd, model, dataclasses.replace(d, S=mask_rows or d.S), B),)
+    return out + ((ws, cd) if want_ws else ())
 
 
 def hip_forward(model, d: O.Dims, flat, x, eps, u, want_rows=True, alloc=None):
@@ -283,6 +312,68 @@ def lse(v, axis=None):
     return np.squeeze(m + np.log(np.exp(v - m).sum(axis=axis, keepdims=True)), axis=axis)
 
 
+def _L():
+    """The ctypes binding (gmvae_amd._lib), for the test modules that reach it through a call."""
+    return L
+
+
+def grad_errs(model, d, gs, g, B):
+    """[(tensor name, max |gs / B - g| / max(max |g|, 1e-6))]: a step's gradient sums gs [P] against the statement's g."""
+    lay, _, _ = O.param_layout(model, d)
+    out = []
+    for name, shape, off in lay:
+        n = int(np.prod(shape))
+        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
+        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
+    return out
+
+
+def tail_gates(what, tail, B, Cc, rtol=1e-4):
+    """The step's tail[0..4] against the statement's batch means: the loss and nll at rtol relative, kl and nent at rtol of
+    max(|.|, 1) -- each term relative to itself (compare_step's reasons)."""
+    print(f"{what}: tail {tail.tolist()} ref loss {Cc['loss']} nll {Cc['nll']} kl {Cc['kl']} nent {Cc['nent']}")
+    print(f"{what}: rel err loss {abs(tail[0] / B - Cc['loss']) / abs(Cc['loss']):.3e}")
+    assert tail[4] == B
+    assert abs(tail[0] / B - Cc["loss"]) <= rtol * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
+    assert abs(tail[1] / B - Cc["nll"]) <= rtol * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
+    assert abs(tail[2] / B - Cc["kl"]) <= rtol * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
+    assert abs(tail[3] / B - Cc["nent"]) <= rtol * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
+
+
+def check_grads(what, model, d, gs, g, B, masks, pre, recompute, rtol=1e-4):
+    """Every gradient tensor at rtol of its own max.  A tensor outside it under ReLU: the device's ReLU took another side than
+    fp64 somewhere?  Legitimate only at units that are numerically zero in fp64 (check_masks asserts it); recompute(masks) then
+    gives the statement's g under the device's subgradients and the gates apply to that.  Returns the errors."""
+    errs = grad_errs(model, d, gs, g, B)
+    if max(e for _, e in errs) > rtol and getattr(d, "act", "relu") == "relu":
+        if check_masks(masks, pre, what):
+            errs = grad_errs(model, d, gs, recompute(masks), B)
+    for name, err in errs:
+        print(f"{what} {name}: rel-to-max err {err:.3e}")
+    for name, err in errs:
+        assert err <= rtol, f"{what} {name}: rel-to-max err {err:.3e}"
+    return errs
+
+
+def need_rccl():
+    """The one narrow precondition of the one-rank communicator tests, decided before any work: the RCCL shared library itself
+    loads in this process.  Everything after it -- the project's own communicator code included -- fails the test if it fails."""
+    import pytest
+    try:
+        C.CDLL(L.rccl_path().decode())
+    except OSError as e:
+        pytest.skip(f"the RCCL shared library does not load here: {e}")
+
+
+def drop_comm(b):
+    """The end of a one-rank communicator test: the engine's graphs, then its communicator."""
+    torch.cuda.synchronize()
+    b.drop_graphs()
+    if getattr(b, "_comm", None):
+        L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
+        b._comm = None
+
+
 MARGINS = []      # (what, worst error / its gate) of every compare_step call: tests/test_hip_parity.py prints the maxima
 
 
@@ -311,27 +402,8 @@ def compare_step(model, d, p, x, eps, u, loss_rtol=1e-4, grad_rtol=1e-4, alloc=N
     for nm, (got, ref, gate) in terms.items():
         MARGINS.append((nm, abs(got - ref) / gate))
         assert abs(got - ref) <= gate, f"{nm}: {got} vs {ref} (gate {gate:.2e})"
-    lay, P, _ = O.param_layout(model, d)
-
-    def grad_errs(g):
-        out = []
-        for name, shape, off in lay:
-            n = int(np.prod(shape))
-            got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-            out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-        return out
-
-    errs = grad_errs(g)
-    if max(e for _, e in errs) > grad_rtol and getattr(d, "act", "relu") == "relu":
-        # a gradient outside its gate: the device's ReLU took another side than fp64 somewhere?  Legitimate only at units that are
-        # numerically zero in fp64 (check_masks asserts it); the oracle then takes the device's subgradients and the gates apply
-        who = [k for k, v in O.MODEL_NAMES.items() if v == model][0]
-        if check_masks(masks, Cc["pre"], f"{who} B={B} D={d.D} L={d.L} K={d.K} H={d.hidden} S={d.S}"):
-            _, g = O.loss_and_grads(model, d, p32, x, eps, u, np.float64, relu_masks=masks)
-            errs = grad_errs(g)
-    worst = 0.0
-    for name, err in errs:
-        worst = max(worst, err)
-        MARGINS.append(("grad S>1" if d.S > 1 else "grad", err / grad_rtol))
-        assert err <= grad_rtol, f"{name}: rel-to-max err {err:.3e}"
-    return loss, worst
+    who = [k for k, v in O.MODEL_NAMES.items() if v == model][0]
+    errs = check_grads(f"{who} B={B} D={d.D} L={d.L} K={d.K} H={d.hidden} S={d.S}", model, d, gs, g, B, masks, Cc["pre"],
+                       lambda m: O.loss_and_grads(model, d, p32, x, eps, u, np.float64, relu_masks=m)[1], grad_rtol)
+    MARGINS.extend(("grad S>1" if d.S > 1 else "grad", err / grad_rtol) for _, err in errs)
+    return loss, max(err for _, err in errs)

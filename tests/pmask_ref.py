@@ -9,14 +9,11 @@ m_bd in {0, 1} (observed iff non-zero), rows r = b S + s:
 Parameters as oracle.unpack gives them; per-net ReLU masks as oracle.loss_and_grads takes them.  The module also holds the
 mask recipe and the shapes of the device tests."""
 import dataclasses
-import math
 
 import numpy as np
-import torch
-import torch.nn.functional as F
 
+import objective_ref as OR
 import oracle as O
-from ymarg_ref import LOG_2PI, _mlp, _mvn_logprob
 
 
 def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, mask=None, relu_masks=None, encoder_sees_mask=True):
@@ -25,60 +22,14 @@ def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, mask=None, relu_masks=No
     that the gates tell it apart).  Returns (C, g): C = dict(loss, nll, kl, nent -- batch means, nll / kl averaged over s --,
     hid = sum_b mean_s(-hid_bs), n_missing, n_observed, rows [R, 4] = logpx, logq, logp, log w, bound [B], pre = per-net
     pre-activations) and g = {name: d loss / d param} (loss = mean_b L_b), all float64 numpy."""
-    rm = relu_masks or {}
-    t = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in p.items()}
-    B, S, K, L = x.shape[0], d.S, d.K, d.L
-    R = B * S
-    nl = len(d.hidden) + 1
-    c, smin = float(d.raw_sigma_bias), float(d.sigma_min)
-    xf = torch.tensor(np.asarray(x), dtype=torch.float64)
-    mf = torch.ones_like(xf) if mask is None else torch.tensor((np.asarray(mask) != 0).astype(np.float64))
-    xe = mf * xf if encoder_sees_mask else xf
-    eps = torch.tensor(np.asarray(eps, np.float64).reshape(R, L))
-    gm = model == O.MODEL_GMVAE
-    nent = torch.zeros(B, dtype=torch.float64)
-    if gm:
-        pre = {"encoder_y": [], "encoder_gmm": [], "decoder": []}
-        logits = _mlp(t, "encoder_y", nl, xe, d.act, rm.get("encoder_y"), pre["encoder_y"])
-        lnq = torch.log_softmax(logits, dim=1)
-        nent = (lnq.exp() * lnq).sum(dim=1)
-        ut = torch.tensor(np.asarray(u, np.float64).reshape(R, K))
-        y = torch.softmax((logits.repeat_interleave(S, dim=0) - torch.log(-torch.log(ut))) / float(d.temperature), dim=1)
-        pp = y @ t["prior_gmm_fcnet/linear_0/w"] + t["prior_gmm_fcnet/linear_0/b"]
-        qp = _mlp(t, "encoder_gmm", nl, torch.cat([xe.repeat_interleave(S, dim=0), y], dim=1), d.act, rm.get("encoder_gmm"),
-                  pre["encoder_gmm"])
-    else:
-        pre = {"encoder": [], "decoder": []}
-        qp = _mlp(t, "encoder", nl, xe, d.act, rm.get("encoder"), pre["encoder"]).repeat_interleave(S, dim=0)
-    mu_q, sig_q = qp[:, :L], torch.clamp(F.softplus(qp[:, L:] + c), min=smin)
-    z = mu_q + sig_q * eps
-    logq = _mvn_logprob(z, mu_q, sig_q)
-    if gm:
-        mu_p, sig_p = pp[:, :L], torch.clamp(F.softplus(pp[:, L:] + c), min=smin)
-        logp = _mvn_logprob(z, mu_p, sig_p)
-    elif model == O.MODEL_VAE:
-        logp = (-0.5 * z * z - 0.5 * LOG_2PI).sum(dim=1)
-    else:
-        loc, s = t["loc"], F.softplus(t["raw_scale_diag"])
-        lnw = torch.log_softmax(t["mixture_logits"], dim=0)
-        tt = (z[:, None, :] - loc[None]) / s[None]
-        lnN = (-0.5 * tt * tt - 0.5 * LOG_2PI).sum(dim=2) - torch.log(s).sum(dim=1)[None]
-        logp = torch.logsumexp(lnw[None] + lnN, dim=1)
-    lam = _mlp(t, "decoder", nl, z, d.act, rm.get("decoder"), pre["decoder"])
-    lam = lam + torch.as_tensor(np.asarray(d.gen_bias_init, np.float64))
-    el = xf.repeat_interleave(S, dim=0) * lam - F.softplus(lam)
-    mr = mf.repeat_interleave(S, dim=0)
-    logpx = (mr * el).sum(dim=1)
-    hid = ((1.0 - mr) * el).sum(dim=1).detach()
-    logw = logpx + logp - logq - nent.repeat_interleave(S)
-    bound = torch.logsumexp(logw.view(B, S), dim=1) - math.log(S)
-    loss = -bound.mean()
-    loss.backward()
-    g = {k: v.grad.numpy().copy() if v.grad is not None else np.zeros_like(v.detach().numpy()) for k, v in t.items()}
-    C = {"loss": loss.item(), "nll": -logpx.mean().item(), "kl": (logq - logp).mean().item(), "nent": nent.mean().item(),
-         "hid": -hid.view(B, S).mean(dim=1).sum().item(), "n_missing": float((1.0 - mf).sum().item()),
-         "n_observed": float(mf.sum().item()), "bound": bound.detach().numpy(), "pre": pre,
-         "rows": torch.stack([logpx, logq, logp, logw], dim=1).detach().numpy()}
+    B, S = x.shape[0], d.S
+    kw = dict(u=u) if model == O.MODEL_GMVAE else {}
+    c, g = OR.loss_and_grads(model, d, p, x, eps, OR.iwae, S=S, mask=np.ones(x.shape) if mask is None else mask,
+                             encoder_sees_mask=encoder_sees_mask, relu_masks=relu_masks, **kw)
+    C = {"loss": c["loss"], "nll": -c["logpx"].mean().item(), "kl": (c["logq"] - c["logp"]).mean().item(),
+         "nent": c["nent"].mean().item(), "hid": -c["hid"].view(B, S).mean(dim=1).sum().item(), "n_missing": c["n_missing"],
+         "n_observed": c["n_observed"], "bound": -c["Lb"].numpy(), "pre": c["pre"],
+         "rows": OR.row_terms({**c, "lw": c["logw"]})}
     return C, g
 
 
@@ -178,5 +129,6 @@ def setup(name, seed=0):
 
 
 def _decoder_logits(model, d, p, x, eps, u, m):
-    """The decoder's logits of the masked forward (oracle.forward on x~: the networks that read x see m x)."""
-    return O.forward(model, d, p, (x * (m != 0)).astype(np.uint8), eps, u)["lam"]
+    """The decoder's logits of the masked forward (the networks that read x see m x)."""
+    kw = dict(u=u) if model == O.MODEL_GMVAE else {}
+    return OR.forward(model, d, OR.leaves(p), x, eps, S=d.S, mask=m, **kw)["lam"].detach().numpy()

@@ -10,7 +10,7 @@ import pytest
 
 import dreg_ref as DR
 import oracle as O
-from hip_util import check_masks, dev, device_masks, dims_of
+from hip_util import _L, check_grads, dev, dims_of, hip_step, tail_gates
 
 pytestmark = pytest.mark.gpu
 
@@ -33,11 +33,6 @@ CASES = {       # name: (model, Dims, B, S, objective flags)
 MODELS = {"vae": O.MODEL_VAE, "vae_gmp": O.MODEL_VAE_GMP, "gmvae": O.MODEL_GMVAE}
 
 
-def _L():
-    from gmvae_amd import _lib
-    return _lib
-
-
 def _rows_per_x(model, d, S):
     return S * d.K if model == O.MODEL_GMVAE else S
 
@@ -56,39 +51,23 @@ def _setup(model, d, B, S, seed=0):
 def dstep(model, d, S, flat, x, eps, flags, seed=5, step=3):
     """One gmvae_step with sched_flags = flags: dict(g [P] float64 gradient sums, tail [8], masks, dlogits [B, K] | None,
     schedule)."""
-    import torch
     L = _L()
     B = x.shape[0]
-    cd = dims_of(dataclasses.replace(d, S=S), B)
-    cd.sched_flags = flags
-    P, _ = L.param_count(cd, model)
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    ed = None if eps is None else dev(eps, torch.float32)
     u = None
     if model == O.MODEL_GMVAE and not flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW):
-        u = dev(np.random.default_rng(9).uniform(0.05, 0.95, (B * S, d.K)), torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
-    L.check(L.lib.gmvae_step(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(u), L.ptr(params), L.ptr(grads), L.ptr(ws), seed, step,
-                             None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    masks = device_masks(ws, cd, model, dataclasses.replace(d, S=_rows_per_x(model, d, S)), B)
+        u = np.random.default_rng(9).uniform(0.05, 0.95, (B * S, d.K))
+    g, tail, masks, ws, cd = hip_step(model, dataclasses.replace(d, S=S), flat, x, eps, u, seed, step, want_masks=True, flags=flags,
+                                      mask_rows=_rows_per_x(model, d, S), want_ws=True)
     dlogits = None
     if model == O.MODEL_GMVAE:
-        off = C.c_uint64()
-        L.check(L.lib.gmvae_workspace_offset(C.byref(cd), model, b"dlogits", C.byref(off)), "offset dlogits")
-        dlogits = ws[off.value // 4: off.value // 4 + B * d.K].view(B, d.K).cpu().numpy().copy()
-    return dict(g=g[:P], tail=g[P:], masks=masks, dlogits=dlogits, schedule=L.step_schedule(cd, model))
+        off = L.workspace_offset(cd, model, "dlogits") // 4
+        dlogits = ws[off:off + B * d.K].view(B, d.K).cpu().numpy().copy()
+    return dict(g=g, tail=tail, masks=masks, dlogits=dlogits, schedule=L.step_schedule(cd, model))
 
 
 def _tensors(model, d, gs):
     lay, _, _ = O.param_layout(model, d)
     return {name: gs[off:off + int(np.prod(shape))].reshape(shape) for name, shape, off in lay}
-
-
-def _grad_errs(model, d, gs, g, B):
-    return [(name, np.abs(got / B - g[name]).max() / max(np.abs(g[name]).max(), 1e-6)) for name, got in _tensors(model, d, gs).items()]
 
 
 @pytest.fixture(scope="module")
@@ -117,24 +96,10 @@ def check_step(name, c, ref=None):
     assert got["schedule"].startswith("general") and got["schedule"].endswith("+dreg"), got["schedule"]
     p32 = O.unpack(model, d, c["flat"].astype(np.float64))
     Cc, g = ref or DR.loss_and_grads(model, d, p32, c["x"], c["eps"], S)
-    tail = got["tail"]
-    assert tail[4] == B
-    loss = tail[0] / B
-    print(f"{name}: loss {loss:.6f} vs {Cc['loss']:.6f}; nll {tail[1] / B:.6f} vs {Cc['nll']:.6f}; kl {tail[2] / B:.6f} vs {Cc['kl']:.6f}")
-    assert abs(loss - Cc["loss"]) <= GATE * abs(Cc["loss"]), (loss, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= GATE * abs(Cc["nll"]), (tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (tail[3] / B, Cc["nent"])
-    errs = _grad_errs(model, d, got["g"], g, B)
-    if max(e for _, e in errs) > GATE and d.act == "relu":
-        # the device's ReLU on the other side of a pre-activation that is zero to rounding: the statement takes its subgradient
-        if check_masks(got["masks"], Cc["pre"], name):
-            _, g = DR.loss_and_grads(model, d, p32, c["x"], c["eps"], S, relu_masks=got["masks"])
-            errs = _grad_errs(model, d, got["g"], g, B)
-    for tname, err in errs:
-        print(f"  {tname}: rel-to-max err {err:.2e}")
-    for tname, err in errs:
-        assert err <= GATE, f"{name} {tname}: rel-to-max err {err:.3e}"
+    tail_gates(name, got["tail"], B, Cc)
+    # (the device's ReLU on the other side of a pre-activation that is zero to rounding: the statement takes its subgradient)
+    check_grads(name, model, d, got["g"], g, B, got["masks"], Cc["pre"],
+                lambda m: DR.loss_and_grads(model, d, p32, c["x"], c["eps"], S, relu_masks=m)[1], GATE)
     if got["dlogits"] is not None:
         ref = Cc["dlogits"] * B
         assert np.abs(got["dlogits"] - ref).max() <= GATE * max(np.abs(ref).max(), 1e-6)

@@ -11,19 +11,13 @@ import pytest
 
 import oracle as O
 import pmask_ref as PR
-from hip_util import check_masks, dev, device_masks, dims_of
-from test_wobj import _gates, _grad_errs
+from hip_util import _L, check_grads, dev, dims_of, drop_comm, hip_step, need_rccl, tail_gates, write_inputs
 
 pytestmark = pytest.mark.gpu
 
 LR = 1e-3
 SEED, STEP = 11, 3
 _REF = {}          # case -> the fp64 statement's (C, g): computed once, shared, left unchanged
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _ref(name):
@@ -39,33 +33,15 @@ def _cdims(d, B, bit=True):
     return cd
 
 
-def _fill_mask(ws, cd, model, mask, slot=0):
-    """mask (uint8 [B, D]) into slot `slot` of the workspace's "pixel_mask" region."""
-    import torch
-    L = _L()
-    n = cd.B * cd.D
-    off = L.workspace_offset(cd, model, "pixel_mask") + slot * ((n + 255) // 256 * 256)
-    ws.view(torch.uint8)[off:off + n].copy_(torch.from_numpy(np.ascontiguousarray(mask).reshape(-1)).cuda())
+def _fill_mask(ws, cd, model, mask):
+    """mask (uint8 [B, D]) into slot 0 of the workspace's "pixel_mask" region."""
+    write_inputs(ws, cd, model, {"pixel_mask": mask})
 
 
 def pstep(model, d, flat, x, eps, u, mask, bit=True):
     """One gmvae_step (slot 0 of the masks = mask): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = _cdims(d, B, bit)
-    P, _ = L.param_count(cd, model)
-    params, xd, ed = dev(flat, torch.float32), dev(x, torch.uint8), dev(eps, torch.float32)
-    ud = None if u is None else dev(u, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
-    if bit:
-        _fill_mask(ws, cd, model, mask)
-    L.check(L.lib.gmvae_step(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             5, 3, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    return g[:P], g[P:], device_masks(ws, cd, model, d, B)
+    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=_L().OBJ_PIXEL_MASK if bit else 0,
+                    inputs={"pixel_mask": mask} if bit else None)
 
 
 def _dead_zeros(model, d, gs, what):
@@ -101,21 +77,15 @@ def test_step_matches_fp64_statement(name):
         assert L.step_schedule(_cdims(d, B, bit=False), model) != "general"
     gs, tail, masks = pstep(model, d, flat, xf, eps, u, m)
     Cc, g = _ref(name)
-    _gates(name, tail, B, Cc)
+    tail_gates(name, tail, B, Cc)
     print(f"{name}: tail[5..7] {tail[5:].tolist()} ref hid {Cc['hid']} missing {Cc['n_missing']} observed {Cc['n_observed']}")
     assert abs(tail[5] - Cc["hid"]) <= 1e-4 * abs(Cc["hid"]), (tail[5], Cc["hid"])
     assert tail[6] == Cc["n_missing"] and tail[7] == Cc["n_observed"]
     if PR.CASES[name].lam_scale:
         lam = PR._decoder_logits(model, d, p32, x, eps, u, m)
         assert 50.0 <= np.abs(lam).max() <= 70.0
-    errs = _grad_errs(model, d, gs, g, B)
-    if max(e for _, e in errs) > 1e-4 and d.act == "relu":
-        if check_masks(masks, Cc["pre"], name):
-            _, g = PR.loss_and_grads(model, d, p32, xf, eps, u, m, relu_masks=masks)
-            errs = _grad_errs(model, d, gs, g, B)
-    for pname, err in errs:
-        print(f"{name} {pname}: rel-to-max err {err:.3e}")
-        assert err <= 1e-4, f"{name} {pname}: rel-to-max err {err:.3e}"
+    check_grads(name, model, d, gs, g, B, masks, Cc["pre"],
+                lambda mk: PR.loss_and_grads(model, d, p32, xf, eps, u, m, relu_masks=mk)[1])
     _dead_zeros(model, d, gs, name)
 
 
@@ -167,7 +137,7 @@ def test_forward_row_terms(name):
     torch.cuda.synchronize()
     Cc, _ = _ref(name)
     rows, tail = rows.cpu().numpy().astype(np.float64), tail.cpu().numpy().astype(np.float64)
-    _gates(name, tail, B, Cc)
+    tail_gates(name, tail, B, Cc)
     assert abs(tail[5] - Cc["hid"]) <= 1e-4 * abs(Cc["hid"]) and tail[6] == Cc["n_missing"] and tail[7] == Cc["n_observed"]
     ref = Cc["rows"]
     for j, what in enumerate(("logpx", "logq", "logp", "logw")):
@@ -259,19 +229,9 @@ def test_train_graph_reads_one_mask_per_step(name):
 
 
 # 7 --------------------------------------------------------------------------------------------------------------
-def _need_rccl():
-    """The one narrow precondition of the one-rank communicator test, decided before any work: the RCCL shared library itself
-    loads in this process.  Everything after it -- the project's own communicator code included -- fails the test if it fails."""
-    L = _L()
-    try:
-        C.CDLL(L.rccl_path().decode())
-    except OSError as e:
-        pytest.skip(f"the RCCL shared library does not load here: {e}")
-
-
 def test_dp_graph_with_a_one_rank_communicator():
     import torch
-    _need_rccl()
+    need_rccl()
     L = _L()
     name = "gumbel"
     d, B = PR.CASES[name].d, 16
@@ -292,11 +252,7 @@ def test_dp_graph_with_a_one_rank_communicator():
             assert torch.equal(u.detach(), v.detach())
         assert torch.equal(rb.tail_log, torch.stack(tails[:2])) and torch.equal(t3, tails[2])
     finally:
-        torch.cuda.synchronize()
-        b.drop_graphs()
-        if getattr(b, "_comm", None):
-            L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-            b._comm = None
+        drop_comm(b)
 
 
 # 8 --------------------------------------------------------------------------------------------------------------

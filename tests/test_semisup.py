@@ -11,7 +11,7 @@ import pytest
 
 import oracle as O
 import semisup_ref as SR
-from hip_util import check_masks, dev, device_masks, dims_of
+from hip_util import _L, check_grads, dev, dims_of, drop_comm, hip_step, tail_gates, workspace, write_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +26,6 @@ CASES = {       # name: (Dims, B, S)
 }
 SEEDS = {"a": 1, "b": 2, "c": 3, "d": 4, "e": 5}      # every labelled example's two largest q differ by > 1e-3 in fp64 (asserted)
 TOP2_GAP = 1e-3
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _labels(K, B, seed):
@@ -60,60 +55,27 @@ def _sdims(d, B, S, row0=0, flags=None):
     return cd
 
 
-def _workspace(cd, y, alpha, slot=0):
-    """A zeroed workspace with the caller's two regions filled: every label set -1, set `slot` = y, the classification weight."""
-    import torch
-    L = _L()
-    ws = torch.zeros(L.workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    if cd.sched_flags & L.OBJ_LABELS:
-        B4 = (cd.B + 3) // 4 * 4
-        lo, so = L.workspace_offset(cd, O.MODEL_GMVAE, "labels") // 4, L.workspace_offset(cd, O.MODEL_GMVAE, "sup_weight") // 4
-        slots = ws.view(torch.int32)[lo:lo + L.LABEL_SLOTS * B4].view(L.LABEL_SLOTS, B4)
-        slots.fill_(-1)
-        slots[slot, :cd.B].copy_(torch.from_numpy(np.asarray(y, np.int32)))
-        ws[so] = alpha
+def _workspace(cd, y, alpha):
+    """A zeroed workspace with the caller's two regions filled: every label set -1, set 0 = y, the classification weight."""
+    ws = workspace(cd, O.MODEL_GMVAE)
+    if cd.sched_flags & _L().OBJ_LABELS:
+        write_inputs(ws, cd, O.MODEL_GMVAE, {"labels": y, "sup_weight": alpha})
     return ws
 
 
 def sstep(d, S, flat, x, eps, y, alpha, row0=0, seed=5, step=3, flags=None):
     """One gmvae_step with the bit: (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    import torch
     L = _L()
-    B = x.shape[0]
-    cd = _sdims(d, B, S, row0, flags)
-    P, _ = L.param_count(cd, O.MODEL_GMVAE)
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    ed = None if eps is None else dev(eps, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = _workspace(cd, y, alpha)
-    L.check(L.lib.gmvae_step(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(ed), None, L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             seed, step, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    masks = device_masks(ws, cd, O.MODEL_GMVAE, dataclasses.replace(d, S=S * d.K), B)
-    return g[:P], g[P:], masks
+    flags = (L.OBJ_MARGINAL_Y_IW | L.OBJ_LABELS) if flags is None else flags
+    return hip_step(O.MODEL_GMVAE, dataclasses.replace(d, S=S), flat, x, eps, None, seed, step, want_masks=True, flags=flags,
+                    row0=row0, mask_rows=S * d.K, inputs={"labels": y, "sup_weight": alpha} if flags & L.OBJ_LABELS else None)
 
 
 def _terms_ok(tail, B, Cc, what, hits=True):
-    print(f"{what}: tail {tail.tolist()} ref loss {Cc['loss']} nll {Cc['nll']} kl {Cc['kl']} nent {Cc['nent']} ce {Cc['ce']} "
-          f"n {Cc['n_labelled']} hits {Cc['hits']}")
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
+    print(f"{what}: ref ce {Cc['ce']} n {Cc['n_labelled']} hits {Cc['hits']}")
+    tail_gates(what, tail, B, Cc)
     assert abs(tail[5] - Cc["ce"]) <= 1e-4 * max(abs(Cc["ce"]), 1.0), (what, tail[5], Cc["ce"])
     assert tail[6] == Cc["n_labelled"] and (tail[7] == Cc["hits"] or not hits), (what, tail[6:], Cc["n_labelled"], Cc["hits"])
-
-
-def _grad_errs(d, gs, g, B):
-    lay, _, _ = O.param_layout(O.MODEL_GMVAE, d)
-    out = []
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-    return out
 
 
 def compare_step(d, S, flat, x, eps, y, alpha, what, flags=None, estimator="standard", grad_rtol=1e-4, ref=None):
@@ -125,14 +87,8 @@ def compare_step(d, S, flat, x, eps, y, alpha, what, flags=None, estimator="stan
     gap = Cc["top2_gap"][Cc["labelled"]]
     assert gap.size == 0 or gap.min() > TOP2_GAP, (what, gap.min())      # hits is unambiguous at fp32
     _terms_ok(tail, B, Cc, what)
-    errs = _grad_errs(d, gs, g, B)
-    if max(e for _, e in errs) > grad_rtol and d.act == "relu":
-        if check_masks(masks, Cc["pre"], what):
-            _, g = SR.loss_and_grads(d, p32, x, eps, S, y, alpha, relu_masks=masks, estimator=estimator)
-            errs = _grad_errs(d, gs, g, B)
-    for name, err in errs:
-        print(f"{what} {name}: rel-to-max err {err:.3e}")
-        assert err <= grad_rtol, f"{what} {name}: rel-to-max err {err:.3e}"
+    check_grads(what, O.MODEL_GMVAE, d, gs, g, B, masks, Cc["pre"],
+                lambda m: SR.loss_and_grads(d, p32, x, eps, S, y, alpha, relu_masks=m, estimator=estimator)[1], grad_rtol)
     return gs, tail, Cc
 
 
@@ -294,12 +250,7 @@ def test_dp_graph_one_rank_reads_one_label_set_per_step():
             assert torch.equal(u.detach(), v.detach())
         assert torch.equal(rb.tail_log, torch.stack(tails[:3])) and torch.equal(t4, tails[3])
     finally:
-        torch.cuda.synchronize()
-        b.drop_graphs()
-        L = _L()
-        if getattr(b, "_comm", None):
-            L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-            b._comm = None
+        drop_comm(b)
 
 
 # 8 --------------------------------------------------------------------------------------------------------------

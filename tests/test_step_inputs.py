@@ -4,13 +4,13 @@ import numpy as np
 import pytest
 
 import pmask_ref as PR
+from hip_util import drop_comm, need_rccl
 import test_pmask
 import test_semisup
 import test_wobj
 import test_ytemp
 import wobj_ref as WR
 import ytemp_ref as TR
-from test_wobj import _drop_comm, _need_rccl
 
 pytestmark = pytest.mark.gpu
 
@@ -74,7 +74,7 @@ def test_eager_fallback_of_a_refused_dp_graph_reads_one_row_per_step(name, monke
     import torch
     from gmvae_amd import _lib as L
     from gmvae_amd.engine import STEP_INPUTS
-    _need_rccl()
+    need_rccl()
     d, make, rows, eager, unchanged = CASES[name](17)
     assert rows.shape[0] == N and len({tuple(r.flatten().tolist()) for r in rows.cpu()}) == N      # (three distinct rows)
     xs = torch.from_numpy((np.random.default_rng(12).random((N, B, d.D)) < 0.87).astype(np.uint8)).cuda()
@@ -102,4 +102,4 @@ def test_eager_fallback_of_a_refused_dp_graph_reads_one_row_per_step(name, monke
         if unchanged is not None:
             unchanged(b)
     finally:
-        _drop_comm(b)
+        drop_comm(b)

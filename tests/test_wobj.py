@@ -1,25 +1,17 @@
 """The weighted objective (GMVAE_OBJ_WEIGHTS) on the device: the step through the C ABI on explicit noise against the fp64
 statement (tests/wobj_ref.py) at the project's gates -- loss at 1e-4 relative, nll / kl / nent each relative to itself, every
 gradient tensor at 1e-4 of its own max, tail[5..7] exact -- then the graph, data-parallel, runner and model-API paths."""
-import ctypes as C
-import dataclasses
-
 import numpy as np
 import pytest
 
 import oracle as O
 import wobj_ref as WR
-from hip_util import check_masks, dev, device_masks, dims_of
+from hip_util import _L, check_grads, dims_of, drop_comm, grad_errs, hip_step, need_rccl, tail_gates
 
 pytestmark = pytest.mark.gpu
 
 LR = 1e-3
 _REF = {}          # (case, weights) -> the fp64 statement's (C, g): computed once, shared, left unchanged
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _ref(name, weights):
@@ -39,43 +31,8 @@ def _cdims(model, marginal, d, B, bit=True):
 
 def wstep(model, marginal, d, flat, x, eps, u, weights, bit=True):
     """One gmvae_step (slot 0 of the weight rows = weights): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = _cdims(model, marginal, d, B, bit)
-    P, _ = L.param_count(cd, model)
-    params, xd, ed = dev(flat, torch.float32), dev(x, torch.uint8), dev(eps, torch.float32)
-    ud = None if u is None else dev(u, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, model) // 4 + 64, dtype=torch.float32, device="cuda")
-    if bit:
-        off = L.workspace_offset(cd, model, "obj_weights") // 4
-        ws[off:off + 4].copy_(torch.tensor(list(weights) + [0.0], dtype=torch.float32))
-    L.check(L.lib.gmvae_step(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             5, 3, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    masks = device_masks(ws, cd, model, dataclasses.replace(d, S=d.K if marginal else 1), B)
-    return g[:P], g[P:], masks
-
-
-def _grad_errs(model, d, gs, g, B):
-    lay, _, _ = O.param_layout(model, d)
-    out = []
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-    return out
-
-
-def _gates(what, tail, B, Cc):
-    print(f"{what}: tail {tail.tolist()} ref loss {Cc['loss']} nll {Cc['nll']} kl {Cc['kl']} nent {Cc['nent']}")
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
+    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=_cdims(model, marginal, d, x.shape[0], bit).sched_flags,
+                    mask_rows=d.K if marginal else 1, inputs={"obj_weights": list(weights) + [0.0]} if bit else None)
 
 
 def compare_step(name, weights, what, case=None, ref=None):
@@ -85,18 +42,12 @@ def compare_step(name, weights, what, case=None, ref=None):
     B = x.shape[0]
     gs, tail, masks = wstep(model, marginal, d, flat, x, eps, u, weights)
     Cc, g = ref or _ref(name, weights)
-    _gates(what, tail, B, Cc)
+    tail_gates(what, tail, B, Cc)
     w32 = np.asarray(weights, np.float32)
     assert tail[5] == float(np.float32(B) * w32[0]) and tail[6] == float(np.float32(B) * w32[1]), (what, tail[5:7])
     assert tail[7] == Cc["floor"].sum(), (what, tail[7], Cc["floor"])
-    errs = _grad_errs(model, d, gs, g, B)
-    if max(e for _, e in errs) > 1e-4 and d.act == "relu":
-        if check_masks(masks, Cc["pre"], what):
-            _, g = WR.loss_and_grads(model, d, p32, x, eps, u, weights, marginal, relu_masks=masks)
-            errs = _grad_errs(model, d, gs, g, B)
-    for pname, err in errs:
-        print(f"{what} {pname}: rel-to-max err {err:.3e}")
-        assert err <= 1e-4, f"{what} {pname}: rel-to-max err {err:.3e}"
+    check_grads(what, model, d, gs, g, B, masks, Cc["pre"],
+                lambda m: WR.loss_and_grads(model, d, p32, x, eps, u, weights, marginal, relu_masks=m)[1])
     return gs, tail
 
 
@@ -204,29 +155,9 @@ def test_train_graph_reads_one_weight_row_per_step(name):
 
 
 # 5 --------------------------------------------------------------------------------------------------------------
-def _need_rccl():
-    """The one narrow precondition of the one-rank communicator tests, decided before any work: the RCCL shared library itself
-    loads in this process.  Everything after it -- the project's own communicator code included -- fails the test if it fails."""
-    L = _L()
-    try:
-        C.CDLL(L.rccl_path().decode())
-    except OSError as e:
-        pytest.skip(f"the RCCL shared library does not load here: {e}")
-
-
-def _drop_comm(b):
-    import torch
-    torch.cuda.synchronize()
-    b.drop_graphs()
-    L = _L()
-    if getattr(b, "_comm", None):
-        L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-        b._comm = None
-
-
 def test_dp_step_and_dp_graph_with_a_one_rank_communicator():
     import torch
-    _need_rccl()
+    need_rccl()
     name = "marginal"
     d, B = WR.CASES[name][2], 16
     xs = torch.from_numpy((np.random.default_rng(10).random((2, B, d.D)) < 0.87).astype(np.uint8)).cuda()
@@ -252,7 +183,7 @@ def test_dp_step_and_dp_graph_with_a_one_rank_communicator():
         assert torch.equal(rb.tail_log, torch.stack(tails[:2])) and torch.equal(t3, tails[2])
         assert t3[5].item() == B * np.float32(ROWS8[5][0])
     finally:
-        _drop_comm(b)
+        drop_comm(b)
 
 
 # (the eager fallback of a refused data-parallel graph: tests/test_step_inputs.py, for all four per-step inputs)
@@ -319,6 +250,6 @@ def test_model_api_matches_fp64_statement(name):
     assert s["kl_weight"] == float(np.float32(weights[0])) and s["y_weight"] == float(np.float32(weights[1]))
     assert s["y_floor_share"] == Cc["floor"].mean()
     gs = e.params.grad.detach().cpu().numpy().astype(np.float64) * B
-    for pname, err in _grad_errs(model, d, gs, g, B):
+    for pname, err in grad_errs(model, d, gs, g, B):
         print(f"{name} {pname}: rel-to-max err {err:.3e}")
         assert err <= 1e-4, (pname, err)

@@ -12,7 +12,7 @@ import pytest
 
 import oracle as O
 import ymarg_ref as YM
-from hip_util import check_masks, dev, device_masks, dims_of
+from hip_util import _L, check_grads, dev, dims_of, drop_comm, hip_step, tail_gates
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +27,6 @@ SIZES = {       # name: (Dims, B)
     "h24x2_relu": (O.Dims(D=100, L=5, K=7, hidden=(24, 24)), 8),
     "bias_vec": (O.Dims(D=784, L=8, K=10, hidden=(64,), gen_bias_init=np.linspace(-2.0, 1.0, 784)), 16),
 }
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _mdims(d, B, row0=0):
@@ -54,39 +49,8 @@ def _setup(d, B, seed=0):
 
 def mstep(d, flat, x, eps, row0=0, seed=5, step=3):
     """One marginal gmvae_step: (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = _mdims(d, B, row0)
-    P, _ = L.param_count(cd, O.MODEL_GMVAE)
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    ed = None if eps is None else dev(eps, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    L.check(L.lib.gmvae_step(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(ed), None, L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             seed, step, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    masks = device_masks(ws, cd, O.MODEL_GMVAE, dataclasses.replace(d, S=d.K), B)
-    return g[:P], g[P:], masks
-
-
-def _terms_ok(tail, B, Cc, what):
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
-
-
-def _grad_errs(d, gs, g, B):
-    lay, _, _ = O.param_layout(O.MODEL_GMVAE, d)
-    out = []
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-    return out
+    return hip_step(O.MODEL_GMVAE, dataclasses.replace(d, S=1), flat, x, eps, None, seed, step, want_masks=True,
+                    flags=_L().OBJ_MARGINAL_Y, row0=row0, mask_rows=d.K)
 
 
 def compare_step(d, flat, x, eps, what, row0=0, grad_rtol=1e-4, ref=None):
@@ -95,15 +59,9 @@ def compare_step(d, flat, x, eps, what, row0=0, grad_rtol=1e-4, ref=None):
     p32 = O.unpack(O.MODEL_GMVAE, d, flat.astype(np.float64))
     gs, tail, masks = mstep(d, flat, x, eps, row0=row0)
     Cc, g = ref or YM.loss_and_grads(d, p32, x, eps)
-    _terms_ok(tail, B, Cc, what)
-    errs = _grad_errs(d, gs, g, B)
-    if max(e for _, e in errs) > grad_rtol and d.act == "relu":
-        if check_masks(masks, Cc["pre"], what):
-            _, g = YM.loss_and_grads(d, p32, x, eps, relu_masks=masks)
-            errs = _grad_errs(d, gs, g, B)
-    for name, err in errs:
-        print(f"{what} {name}: rel-to-max err {err:.3e}")
-        assert err <= grad_rtol, f"{what} {name}: rel-to-max err {err:.3e}"
+    tail_gates(what, tail, B, Cc)
+    check_grads(what, O.MODEL_GMVAE, d, gs, g, B, masks, Cc["pre"], lambda m: YM.loss_and_grads(d, p32, x, eps, relu_masks=m)[1],
+                grad_rtol)
     return gs, tail, Cc
 
 
@@ -166,7 +124,7 @@ def test_forward_outputs():
     tail, rows, z, y, lg = (t.cpu().numpy().astype(np.float64) for t in (tail, rows, z, y, lg))
     _, ts, Cc = compare_step(d, flat, x, eps, "forward")
     np.testing.assert_allclose(tail[:5], ts[:5], rtol=1e-6)
-    _terms_ok(tail, B, Cc, "forward")
+    tail_gates("forward", tail, B, Cc)
     np.testing.assert_allclose(rows, Cc["rows"], rtol=1e-4, atol=1e-3)
     np.testing.assert_allclose(z, Cc["z"], rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(lg, Cc["logits"], rtol=1e-4, atol=1e-4)
@@ -286,12 +244,7 @@ def test_dp_graph_one_rank_is_the_single_device_graph():
         torch.cuda.synchronize()
         assert torch.equal(a.params.detach(), b.params.detach()) and torch.equal(a.v, b.v)
     finally:
-        torch.cuda.synchronize()
-        b.drop_graphs()
-        from gmvae_amd import _lib as L
-        if getattr(b, "_comm", None):
-            L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-            b._comm = None
+        drop_comm(b)
 
 
 def test_trajectory_follows_fp64_statement():
@@ -312,7 +265,7 @@ def test_trajectory_follows_fp64_statement():
         pre = e.params.detach().cpu().numpy().astype(np.float64)
         tail = e.train_step(torch.from_numpy(xs[t]).cuda(), eps=torch.from_numpy(epss[t]).cuda(), lr=LR).cpu().numpy()
         Cd, _ = YM.loss_and_grads(d, O.unpack(O.MODEL_GMVAE, d, pre), xs[t], epss[t])
-        _terms_ok(tail.astype(np.float64), B, Cd, f"step {t}")
+        tail_gates(f"step {t}", tail.astype(np.float64), B, Cd)
         _, g = YM.loss_and_grads(d, O.unpack(O.MODEL_GMVAE, d, ref), xs[t], epss[t])
         ref, m, v = O.adam_tf_step(ref, m, v, O.pack(O.MODEL_GMVAE, d, g, np.float64), t + 1, lr=LR, dtype=np.float64)
     fin = e.params.detach().cpu().numpy().astype(np.float64)

@@ -14,7 +14,7 @@ import pytest
 
 import oracle as O
 import ymarg_iw_ref as YI
-from hip_util import check_masks, dev, device_masks, dims_of, hip_step
+from hip_util import _L, check_grads, dev, dims_of, drop_comm, hip_step, tail_gates
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +30,6 @@ SIZES = {       # name: (Dims, B, S)
     "bias_vec": (O.Dims(D=784, L=8, K=10, hidden=(64,), gen_bias_init=np.linspace(-2.0, 1.0, 784)), 16, 2),
 }
 DEF = O.Dims(D=784, L=8, K=10, hidden=(64,))
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _idims(d, B, S, row0=0, flags=None):
@@ -57,39 +52,8 @@ def _setup(d, B, S, seed=0):
 
 def istep(d, S, flat, x, eps, row0=0, seed=5, step=3, flags=None):
     """One gmvae_step with the objective bit: (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    import torch
-    L = _L()
-    B = x.shape[0]
-    cd = _idims(d, B, S, row0, flags)
-    P, _ = L.param_count(cd, O.MODEL_GMVAE)
-    params, xd = dev(flat, torch.float32), dev(x, torch.uint8)
-    ed = None if eps is None else dev(eps, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, O.MODEL_GMVAE) // 4 + 64, dtype=torch.float32, device="cuda")
-    L.check(L.lib.gmvae_step(C.byref(cd), O.MODEL_GMVAE, L.ptr(xd), L.ptr(ed), None, L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             seed, step, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    g = grads.cpu().numpy().astype(np.float64)
-    masks = device_masks(ws, cd, O.MODEL_GMVAE, dataclasses.replace(d, S=S * d.K), B)
-    return g[:P], g[P:], masks
-
-
-def _terms_ok(tail, B, Cc, what):
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= 1e-4 * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= 1e-4 * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= 1e-4 * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= 1e-4 * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
-
-
-def _grad_errs(d, gs, g, B):
-    lay, _, _ = O.param_layout(O.MODEL_GMVAE, d)
-    out = []
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-    return out
+    return hip_step(O.MODEL_GMVAE, dataclasses.replace(d, S=S), flat, x, eps, None, seed, step, want_masks=True,
+                    flags=_L().OBJ_MARGINAL_Y_IW if flags is None else flags, row0=row0, mask_rows=S * d.K)
 
 
 def compare_step(d, S, flat, x, eps, what, row0=0, grad_rtol=1e-4):
@@ -97,14 +61,9 @@ def compare_step(d, S, flat, x, eps, what, row0=0, grad_rtol=1e-4):
     p32 = O.unpack(O.MODEL_GMVAE, d, flat.astype(np.float64))
     gs, tail, masks = istep(d, S, flat, x, eps, row0=row0)
     Cc, g = YI.loss_and_grads(d, p32, x, eps, S)
-    _terms_ok(tail, B, Cc, what)
-    errs = _grad_errs(d, gs, g, B)
-    if max(e for _, e in errs) > grad_rtol and d.act == "relu":
-        if check_masks(masks, Cc["pre"], what):
-            _, g = YI.loss_and_grads(d, p32, x, eps, S, relu_masks=masks)
-            errs = _grad_errs(d, gs, g, B)
-    for name, err in errs:
-        assert err <= grad_rtol, f"{what} {name}: rel-to-max err {err:.3e}"
+    tail_gates(what, tail, B, Cc)
+    check_grads(what, O.MODEL_GMVAE, d, gs, g, B, masks, Cc["pre"], lambda m: YI.loss_and_grads(d, p32, x, eps, S, relu_masks=m)[1],
+                grad_rtol)
     return gs, tail, Cc
 
 
@@ -202,7 +161,7 @@ def test_forward_outputs():
     tail, rows, z, y, lg = (t.cpu().numpy().astype(np.float64) for t in (tail, rows, z, y, lg))
     _, ts, Cc = compare_step(d, S, flat, x, eps, "forward")
     np.testing.assert_allclose(tail[:5], ts[:5], rtol=1e-6)
-    _terms_ok(tail, B, Cc, "forward")
+    tail_gates("forward", tail, B, Cc)
     np.testing.assert_allclose(rows, Cc["rows"], rtol=1e-4, atol=1e-3)
     np.testing.assert_allclose(z, Cc["z"], rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(lg, Cc["logits"], rtol=1e-4, atol=1e-4)
@@ -365,12 +324,7 @@ def test_dp_graph_one_rank_is_the_single_device_graph():
         torch.cuda.synchronize()
         assert torch.equal(a.params.detach(), b.params.detach()) and torch.equal(a.v, b.v)
     finally:
-        torch.cuda.synchronize()
-        b.drop_graphs()
-        from gmvae_amd import _lib as L
-        if getattr(b, "_comm", None):
-            L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-            b._comm = None
+        drop_comm(b)
 
 
 def test_trajectory_follows_fp64_statement():
@@ -390,7 +344,7 @@ def test_trajectory_follows_fp64_statement():
         pre = e.params.detach().cpu().numpy().astype(np.float64)
         tail = e.train_step(torch.from_numpy(xs[t]).cuda(), eps=torch.from_numpy(epss[t]).cuda(), lr=LR).cpu().numpy()
         Cd, _ = YI.loss_and_grads(d, O.unpack(O.MODEL_GMVAE, d, pre), xs[t], epss[t], S)
-        _terms_ok(tail.astype(np.float64), B, Cd, f"step {t}")
+        tail_gates(f"step {t}", tail.astype(np.float64), B, Cd)
         _, g = YI.loss_and_grads(d, O.unpack(O.MODEL_GMVAE, d, ref), xs[t], epss[t], S)
         ref, m, v = O.adam_tf_step(ref, m, v, O.pack(O.MODEL_GMVAE, d, g, np.float64), t + 1, lr=LR, dtype=np.float64)
     fin = e.params.detach().cpu().numpy().astype(np.float64)

@@ -16,18 +16,13 @@ import pytest
 
 import oracle as O
 import ytemp_ref as TR
-from hip_util import check_masks, dev, device_masks, dims_of
+from hip_util import _L, check_grads, dev, dims_of, drop_comm, hip_step, need_rccl, tail_gates, write_inputs
 
 pytestmark = pytest.mark.gpu
 
 LR = 1e-3
 GM = O.MODEL_GMVAE
 _REF = {}          # (case, tau, straight-through) -> the fp64 statement's (C, g): computed once, shared, left unchanged
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def _ref(name, tau, st):
@@ -47,79 +42,40 @@ def _cdims(name, B, temp_dev, st, temperature):
     return cd
 
 
-def _fill(cd, ws, name, tau):
+def _inputs(cd, name, tau):
     """The caller's regions: slot 0 of the temperatures (the other slots stay 0: a kernel reading another slot gives NaN) and of
     the weight rows."""
-    import torch
     L = _L()
+    inputs = {}
     if cd.sched_flags & L.Y_TEMP_DEV:
-        off = L.workspace_offset(cd, GM, "y_temperature") // 4
-        ws[off:off + 1].fill_(float(tau))
+        inputs["y_temperature"] = [tau]
     if cd.sched_flags & L.OBJ_WEIGHTS:
-        off = L.workspace_offset(cd, GM, "obj_weights") // 4
-        ws[off:off + 4].copy_(torch.tensor(list(TR.case_weights(name)) + [0.0], dtype=torch.float32))
+        inputs["obj_weights"] = list(TR.case_weights(name)) + [0.0]
+    return inputs
 
 
 def ystep(name, tau, st, temp_dev=True, temperature=1.0):
     """One gmvae_step of a case.  temp_dev: slot 0 holds tau and dims->temperature the decoy `temperature`; else
-    dims->temperature = tau.  Returns (the whole gradient buffer [P + TAIL] as a device tensor, P, the workspace, its dims)."""
-    import torch
-    L = _L()
+    dims->temperature = tau.  Returns (grad sums [P] float64, tail [8], the step's ReLU masks, the workspace, its dims)."""
     d, p32, flat, x, eps, u = TR.setup(name)
-    B = x.shape[0]
-    cd = _cdims(name, B, temp_dev, st, temperature if temp_dev else tau)
-    P, _ = L.param_count(cd, GM)
-    params, xd, ed, ud = dev(flat, torch.float32), dev(x, torch.uint8), dev(eps, torch.float32), dev(u, torch.float32)
-    grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
-    ws = torch.zeros(L.workspace_bytes(cd, GM) // 4 + 64, dtype=torch.float32, device="cuda")
-    _fill(cd, ws, name, tau)
-    L.check(L.lib.gmvae_step(C.byref(cd), GM, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws),
-                             5, 3, None, L.current_stream()), "gmvae_step")
-    torch.cuda.synchronize()
-    return grads, P, ws, cd
-
-
-def _grad_errs(d, gs, g, B):
-    lay, _, _ = O.param_layout(GM, d)
-    out = []
-    for name, shape, off in lay:
-        n = int(np.prod(shape))
-        got, ref = gs[off:off + n].reshape(shape) / B, g[name]
-        out.append((name, np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-6)))
-    return out
-
-
-def _gates(what, tail, B, Cc, rtol=1e-4):
-    print(f"{what}: tail {tail.tolist()} ref loss {Cc['loss']} nll {Cc['nll']} kl {Cc['kl']} nent {Cc['nent']}")
-    print(f"{what}: rel err loss {abs(tail[0] / B - Cc['loss']) / abs(Cc['loss']):.3e}")
-    assert tail[4] == B
-    assert abs(tail[0] / B - Cc["loss"]) <= rtol * abs(Cc["loss"]), (what, tail[0] / B, Cc["loss"])
-    assert abs(tail[1] / B - Cc["nll"]) <= rtol * abs(Cc["nll"]), (what, tail[1] / B, Cc["nll"])
-    assert abs(tail[2] / B - Cc["kl"]) <= rtol * max(abs(Cc["kl"]), 1.0), (what, tail[2] / B, Cc["kl"])
-    assert abs(tail[3] / B - Cc["nent"]) <= rtol * max(abs(Cc["nent"]), 1.0), (what, tail[3] / B, Cc["nent"])
+    temperature = temperature if temp_dev else tau
+    cd = _cdims(name, x.shape[0], temp_dev, st, temperature)
+    return hip_step(GM, dataclasses.replace(d, temperature=temperature), flat, x, eps, u, 5, 3, want_masks=True, flags=cd.sched_flags,
+                    inputs=_inputs(cd, name, tau), want_ws=True)
 
 
 def compare_step(name, tau, st, rtol=1e-4):
     d, p32, flat, x, eps, u = TR.setup(name)
     B = x.shape[0]
     what = f"{name} tau={tau} {'straight-through' if st else 'relaxed'}"
-    grads, P, ws, cd = ystep(name, tau, st)
-    g_all = grads.cpu().numpy().astype(np.float64)
-    gs, tail = g_all[:P], g_all[P:]
+    gs, tail, masks, ws, cd = ystep(name, tau, st)
     Cc, g = _ref(name, tau, st)
     if st:
         assert Cc["gap"].min() > TR.MIN_GAP
-    _gates(what, tail, B, Cc, rtol)
-    errs = _grad_errs(d, gs, g, B)
-    if max(e for _, e in errs) > rtol and d.act == "relu":
-        masks = device_masks(ws, cd, GM, d, B)
-        if check_masks(masks, Cc["pre"], what):
-            _, g = TR.loss_and_grads(d, p32, x, eps, u, tau, straight_through=st, weights=TR.case_weights(name),
-                                     relu_masks=masks)
-            errs = _grad_errs(d, gs, g, B)
-    for pname, err in errs:
-        print(f"{what} {pname}: rel-to-max err {err:.3e}")
-        assert err <= rtol, f"{what} {pname}: rel-to-max err {err:.3e}"
+    tail_gates(what, tail, B, Cc, rtol)
+    check_grads(what, GM, d, gs, g, B, masks, Cc["pre"],
+                lambda m: TR.loss_and_grads(d, p32, x, eps, u, tau, straight_through=st, weights=TR.case_weights(name),
+                                            relu_masks=m)[1], rtol)
     return ws, cd, Cc
 
 
@@ -146,15 +102,14 @@ def test_step_matches_fp64_statement(name, tau, st):
 def test_slot_temperature_gives_the_bits_of_the_step_without_the_bit(tau):
     """K = 65 (the three-pass head): GMVAE_Y_TEMP_DEV with slot tau against the step without the bit at dims->temperature =
     tau, on the general schedule both: the tail and every gradient, bit for bit."""
-    import torch
     L = _L()
     name = "K65-S2"
-    g0, P, _, cd0 = ystep(name, tau, False, temp_dev=False)
+    g0, t0, _, _, cd0 = ystep(name, tau, False, temp_dev=False)
     assert L.step_schedule(cd0, GM) == "general"
-    g1, _, _, cd1 = ystep(name, tau, False, temp_dev=True, temperature=1.0)
+    g1, t1, _, _, cd1 = ystep(name, tau, False, temp_dev=True, temperature=1.0)
     assert L.step_schedule(cd1, GM) == "general+temp"
-    assert torch.isfinite(g0).all()
-    assert torch.equal(g0, g1)
+    assert np.isfinite(g0).all() and np.isfinite(t0).all()
+    assert np.array_equal(g0, g1) and np.array_equal(t0, t1)
 
 
 @pytest.mark.parametrize("name", ["K7-S3", "K17"])
@@ -163,22 +118,21 @@ def test_slot_temperature_identity_in_the_other_k_regimes(name):
     or samples the one-launch steps do not take) -- K <= 16 with a ragged last wave -- and, for K = 17, under the library's
     own switches."""
     import os
-    import torch
     L = _L()
     env = {"GMVAE_NO_MEGA": "1", "GMVAE_NO_SKINNY": "1", "GMVAE_NO_FUSED": "1"} if name == "K17" else {}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        g0, P, _, cd0 = ystep(name, 0.7, False, temp_dev=False)
+        g0, t0, _, _, cd0 = ystep(name, 0.7, False, temp_dev=False)
         assert L.step_schedule(cd0, GM) == "general"
-        g1, _, _, _ = ystep(name, 0.7, False, temp_dev=True)
+        g1, t1, _, _, _ = ystep(name, 0.7, False, temp_dev=True)
     finally:
         for k, v in old.items():
             if v is None:
                 del os.environ[k]
             else:
                 os.environ[k] = v
-    assert torch.isfinite(g0).all() and torch.equal(g0, g1)
+    assert np.isfinite(g0).all() and np.isfinite(t0).all() and np.array_equal(g0, g1) and np.array_equal(t0, t1)
 
 
 @pytest.mark.parametrize("name", list(TR.CASES))
@@ -198,7 +152,7 @@ def test_forward_under_straight_through(name):
     cd = _cdims(name, B, True, True, 1.0)
     params, xd, ed, ud = dev(flat, torch.float32), dev(x, torch.uint8), dev(eps, torch.float32), dev(u, torch.float32)
     ws = torch.zeros(L.workspace_bytes(cd, GM) // 4 + 64, dtype=torch.float32, device="cuda")
-    _fill(cd, ws, name, tau)
+    write_inputs(ws, cd, GM, _inputs(cd, name, tau))
     nan = lambda *s: torch.full(s, float("nan"), device="cuda")
     tail, rows, z, y, lg = nan(L.TAIL), nan(R, 4), nan(R, d.L), nan(R, K), nan(B, K)
     L.check(L.lib.gmvae_forward(C.byref(cd), GM, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(tail), L.ptr(rows),
@@ -210,8 +164,8 @@ def test_forward_under_straight_through(name):
     ys = ws[off:off + R * K].view(R, K).cpu().numpy().astype(np.float64)
     assert np.abs(ys.sum(axis=1) - 1.0).max() <= 1e-6
     assert np.abs(ys - Cc["y_soft"]).max() <= 1e-5
-    grads, P, _, _ = ystep(name, tau, True)
-    assert torch.equal(tail[:5], grads[P:P + 5])                          # the step's tail, bit for bit
+    _, ts, _, _, _ = ystep(name, tau, True)
+    assert np.array_equal(tail[:5].cpu().numpy().astype(np.float64), ts[:5])      # the step's tail, bit for bit
     assert np.abs(lg.cpu().numpy() - Cc["logits"]).max() <= 1e-4 * max(np.abs(Cc["logits"]).max(), 1.0)
 
 
@@ -265,19 +219,9 @@ def test_train_graph_reads_one_temperature_per_step(y_estimator):
             b.set_temperature(bad)
 
 
-def _need_rccl():
-    """The one narrow precondition of the one-rank communicator test, decided before any work: the RCCL shared library itself
-    loads in this process.  Everything after it -- the project's own communicator code included -- fails the test if it fails."""
-    L = _L()
-    try:
-        C.CDLL(L.rccl_path().decode())
-    except OSError as e:
-        pytest.skip(f"the RCCL shared library does not load here: {e}")
-
-
 def test_dp_graph_with_a_one_rank_communicator():
     import torch
-    _need_rccl()
+    need_rccl()
     L = _L()
     d, B = TR.CASES["K7-weights"][0], 16
     xs = torch.from_numpy((np.random.default_rng(10).random((6, B, d.D)) < 0.87).astype(np.uint8)).cuda()
@@ -302,11 +246,7 @@ def test_dp_graph_with_a_one_rank_communicator():
         torch.cuda.synchronize()
         assert torch.equal(t_a, t_b) and torch.equal(a.params.detach(), b.params.detach())
     finally:
-        torch.cuda.synchronize()
-        b.drop_graphs()
-        if getattr(b, "_comm", None):
-            L.check(L.lib.gmvae_comm_destroy(b._comm), "gmvae_comm_destroy")
-            b._comm = None
+        drop_comm(b)
 
 
 # (e) ------------------------------------------------------------------------------------------------------------

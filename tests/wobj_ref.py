@@ -11,11 +11,9 @@ Parameters as oracle.unpack gives them; per-net ReLU masks as oracle.loss_and_gr
 import math
 
 import numpy as np
-import torch
-import torch.nn.functional as F
 
+import objective_ref as OR
 import oracle as O
-from ymarg_ref import LOG_2PI, _mlp, _mvn_logprob
 
 
 def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, weights=(1.0, 1.0, 0.0), marginal=False, relu_masks=None):
@@ -23,77 +21,13 @@ def loss_and_grads(model, d: O.Dims, p, x, eps, u=None, weights=(1.0, 1.0, 0.0),
     weights = (beta_z, beta_y, lambda).  Returns (C, g): C = dict(loss, nll, kl, nent -- batch means; nll, kl, nent unweighted --,
     kl_y [B] = nent_b + ln K, floor [B] = 1 - a_b, q [B, K] = softmax(logits) (GMVAE), pre = per-net pre-activations) and g = {name: d loss / d param}
     (loss = mean_b L_b), all float64 numpy."""
-    rm = relu_masks or {}
-    bz, by, lam = (float(w) for w in weights)
-    t = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in p.items()}
-    B, K, L = x.shape[0], d.K, d.L
-    nl = len(d.hidden) + 1
-    c, smin = float(d.raw_sigma_bias), float(d.sigma_min)
-    xf = torch.tensor(np.asarray(x), dtype=torch.float64)
     gm = model == O.MODEL_GMVAE
     assert gm or not marginal
-    rpx = K if marginal else 1
-    R = B * rpx
-    eps = torch.tensor(np.asarray(eps, np.float64).reshape(R, L))
-    pre = {}
-    q = None
-    nent = torch.zeros(B, dtype=torch.float64)
-    if gm:
-        pre = {"encoder_y": [], "encoder_gmm": [], "decoder": []}
-        logits = _mlp(t, "encoder_y", nl, xf, d.act, rm.get("encoder_y"), pre["encoder_y"])
-        lnq = torch.log_softmax(logits, dim=1)
-        q = lnq.exp()
-        nent = (q * lnq).sum(dim=1)
-        if marginal:
-            y = torch.eye(K, dtype=torch.float64).repeat(B, 1)
-        else:
-            ut = torch.tensor(np.asarray(u, np.float64).reshape(B, K))
-            y = torch.softmax((logits - torch.log(-torch.log(ut))) / float(d.temperature), dim=1)
-        xr = xf.repeat_interleave(rpx, dim=0)
-        pp = y @ t["prior_gmm_fcnet/linear_0/w"] + t["prior_gmm_fcnet/linear_0/b"]
-        qp = _mlp(t, "encoder_gmm", nl, torch.cat([xr, y], dim=1), d.act, rm.get("encoder_gmm"), pre["encoder_gmm"])
-    else:
-        pre = {"encoder": [], "decoder": []}
-        xr = xf
-        qp = _mlp(t, "encoder", nl, xf, d.act, rm.get("encoder"), pre["encoder"])
-    mu_q, sig_q = qp[:, :L], torch.clamp(F.softplus(qp[:, L:] + c), min=smin)
-    z = mu_q + sig_q * eps
-    logq = _mvn_logprob(z, mu_q, sig_q)
-    if gm:
-        mu_p, sig_p = pp[:, :L], torch.clamp(F.softplus(pp[:, L:] + c), min=smin)
-        logp = _mvn_logprob(z, mu_p, sig_p)
-    elif model == O.MODEL_VAE:
-        logp = (-0.5 * z * z - 0.5 * LOG_2PI).sum(dim=1)
-    else:
-        loc, s = t["loc"], F.softplus(t["raw_scale_diag"])
-        lnw = torch.log_softmax(t["mixture_logits"], dim=0)
-        tt = (z[:, None, :] - loc[None]) / s[None]
-        lnN = (-0.5 * tt * tt - 0.5 * LOG_2PI).sum(dim=2) - torch.log(s).sum(dim=1)[None]
-        logp = torch.logsumexp(lnw[None] + lnN, dim=1)
-    lam_d = _mlp(t, "decoder", nl, z, d.act, rm.get("decoder"), pre["decoder"])
-    lam_d = lam_d + torch.as_tensor(np.asarray(d.gen_bias_init, np.float64))
-    logpx = (xr * lam_d - F.softplus(lam_d)).sum(dim=1)
-    nll_r, kl_r = -logpx, logq - logp
-    if marginal:
-        nll_b, kl_b = (q * nll_r.view(B, K)).sum(dim=1), (q * kl_r.view(B, K)).sum(dim=1)
-    else:
-        nll_b, kl_b = nll_r, kl_r
-    Lb = nll_b + bz * kl_b
-    floor = np.zeros(B)
-    if gm:
-        thr = lam - math.log(K)
-        if lam == 0.0:
-            nef = nent
-        else:
-            nef = torch.clamp(nent, min=thr)                       # (autograd through the max: no gradient below the floor)
-            floor = (nent.detach().numpy() <= thr).astype(np.float64)
-        Lb = Lb + by * nef
-    loss = Lb.mean()
-    loss.backward()
-    g = {k: v.grad.numpy().copy() if v.grad is not None else np.zeros_like(v.detach().numpy()) for k, v in t.items()}
-    C = {"loss": loss.item(), "nll": nll_b.mean().item(), "kl": kl_b.mean().item(), "nent": nent.mean().item(),
-         "kl_y": nent.detach().numpy() + (math.log(K) if gm else 0.0), "floor": floor, "pre": pre,
-         "q": q.detach().numpy() if gm else None}
+    kw = dict(y="summed" if marginal else "gumbel", u=u) if gm else {}
+    c, g = OR.loss_and_grads(model, d, p, x, eps, lambda o: OR.weighted(o, weights, marginal), relu_masks=relu_masks, **kw)
+    C = {"loss": c["loss"], "nll": c["nll_b"].mean().item(), "kl": c["kl_b"].mean().item(), "nent": c["nent"].mean().item(),
+         "kl_y": c["nent"].numpy() + (math.log(d.K) if gm else 0.0), "floor": c["floor"], "pre": c["pre"],
+         "q": c["q"].numpy() if gm else None}
     return C, g
 
 

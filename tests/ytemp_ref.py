@@ -7,14 +7,11 @@ With g = -ln(-ln u), a_rk = (logits_bk + g_rk) / tau and y_soft = softmax_k a_rk
     log w_r = log p(x_b|z_r) + log p(z_r|y_r) - log q(z_r|x_b,y_r) - nent_b,  nent_b = sum_k q_bk ln q_bk
     L_b = -(logsumexp_s log w_bs - ln S);   at S = 1 with weights (beta_z, beta_y, 0): L_b = nll_b + beta_z kl_b + beta_y nent_b
 Parameters as oracle.unpack gives them; per-net ReLU masks as oracle.loss_and_grads takes them."""
-import math
-
 import numpy as np
 import torch
-import torch.nn.functional as F
 
+import objective_ref as OR
 import oracle as O
-from ymarg_ref import _mlp, _mvn_logprob
 
 
 def loss_and_grads(d: O.Dims, p, x, eps, u, tau, straight_through=False, weights=None, relu_masks=None, y_leaf=False):
@@ -24,57 +21,17 @@ def loss_and_grads(d: O.Dims, p, x, eps, u, tau, straight_through=False, weights
     Returns (C, g): C = dict(loss, nll, kl, nent -- batch means, nll and kl means over s too --, logits [B, K], dlogits [B, K] =
     d loss / d logits, y [R, K] as consumed, y_soft [R, K], argmax [R], gap [R] = the top-two gap of logits + g per row, pre =
     per-net pre-activations) and g = {name: d loss / d param} (loss = mean_b L_b), all float64 numpy."""
-    rm = relu_masks or {}
-    t = {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True) for k, v in p.items()}
-    B, K, L, S = x.shape[0], d.K, d.L, d.S
-    R = B * S
-    nl = len(d.hidden) + 1
-    c, smin = float(d.raw_sigma_bias), float(d.sigma_min)
-    xf = torch.tensor(np.asarray(x), dtype=torch.float64)
-    eps = torch.tensor(np.asarray(eps, np.float64).reshape(R, L))
-    ut = torch.tensor(np.asarray(u, np.float64).reshape(R, K))
-    pre = {"encoder_y": [], "encoder_gmm": [], "decoder": []}
-    logits = _mlp(t, "encoder_y", nl, xf, d.act, rm.get("encoder_y"), pre["encoder_y"])
-    logits.retain_grad()
-    lnq = torch.log_softmax(logits, dim=1)
-    q = lnq.exp()
-    nent = (q * lnq).sum(dim=1)
-    pert = logits.repeat_interleave(S, dim=0) - torch.log(-torch.log(ut))
-    y_soft = torch.softmax(pert / float(tau), dim=1)
-    top2 = torch.topk(pert.detach(), 2, dim=1).values
-    am = pert.detach().argmax(dim=1)                                # (the first maximal index on ties)
-    y_hard = F.one_hot(am, K).to(torch.float64)
-    if y_leaf:
-        y = y_hard.clone().requires_grad_(True)
-    elif straight_through:
-        y = y_soft + (y_hard - y_soft).detach()
-    else:
-        y = y_soft
-    xr = xf.repeat_interleave(S, dim=0)
-    pp = y @ t["prior_gmm_fcnet/linear_0/w"] + t["prior_gmm_fcnet/linear_0/b"]
-    qp = _mlp(t, "encoder_gmm", nl, torch.cat([xr, y], dim=1), d.act, rm.get("encoder_gmm"), pre["encoder_gmm"])
-    mu_q, sig_q = qp[:, :L], torch.clamp(F.softplus(qp[:, L:] + c), min=smin)
-    z = mu_q + sig_q * eps
-    logq = _mvn_logprob(z, mu_q, sig_q)
-    mu_p, sig_p = pp[:, :L], torch.clamp(F.softplus(pp[:, L:] + c), min=smin)
-    logp = _mvn_logprob(z, mu_p, sig_p)
-    lam_d = _mlp(t, "decoder", nl, z, d.act, rm.get("decoder"), pre["decoder"])
-    lam_d = lam_d + torch.as_tensor(np.asarray(d.gen_bias_init, np.float64))
-    logpx = (xr * lam_d - F.softplus(lam_d)).sum(dim=1)
-    nll_r, kl_r = -logpx, logq - logp
+    objective = OR.iwae
     if weights is not None:
-        assert S == 1 and float(weights[2]) == 0.0
-        Lb = nll_r + float(weights[0]) * kl_r + float(weights[1]) * nent
-    else:
-        logw = (logpx + logp - logq - nent.repeat_interleave(S)).view(B, S)
-        Lb = -(torch.logsumexp(logw, dim=1) - math.log(S))
-    loss = Lb.mean()
-    loss.backward()
-    g = {k: v.grad.numpy().copy() if v.grad is not None else np.zeros_like(v.detach().numpy()) for k, v in t.items()}
-    C = {"loss": loss.item(), "nll": nll_r.mean().item(), "kl": kl_r.mean().item(), "nent": nent.mean().item(),
-         "logits": logits.detach().numpy(), "dlogits": logits.grad.numpy().copy(), "y": y.detach().numpy(),
-         "y_soft": y_soft.detach().numpy(), "argmax": am.numpy(), "gap": (top2[:, 0] - top2[:, 1]).numpy(), "pre": pre,
-         "dy": y.grad.numpy().copy() if y_leaf else None}
+        assert d.S == 1 and float(weights[2]) == 0.0
+        objective = lambda o: OR.weighted(o, weights)
+    c, g = OR.loss_and_grads(O.MODEL_GMVAE, d, p, x, eps, objective, S=d.S, y="leaf" if y_leaf else "gumbel", u=u, tau=tau,
+                             straight_through=straight_through, relu_masks=relu_masks)
+    top2 = torch.topk(c["pert"], 2, dim=1).values
+    C = {"loss": c["loss"], "nll": -c["logpx"].mean().item(), "kl": (c["logq"] - c["logp"]).mean().item(),
+         "nent": c["nent"].mean().item(), "logits": c["logits"].numpy(), "dlogits": c["dlogits"], "y": c["y"].numpy(),
+         "y_soft": c["y_soft"].numpy(), "argmax": c["pert"].argmax(dim=1).numpy(), "gap": (top2[:, 0] - top2[:, 1]).numpy(),
+         "pre": c["pre"], "dy": c["dy"]}
     return C, g
 
 
