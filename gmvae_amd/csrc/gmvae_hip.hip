@@ -52,8 +52,6 @@ constexpr int GMP_PARTS = 64;
 constexpr int kMegaQMax = 4;
 constexpr int kSkNs1 = 4;        // slabs of the skinny schedule's first layer (contraction split); <= skinny.hpp kSkNs1x
 
-// Workgroups that share one 16-row panel of mega_fwd_bwd (they split its decoder chunks): as many as keep the
-// whole grid co-resident on the chip's 256 CUs (one 150 KB-LDS workgroup per CU).
 // GmvaeDims::sched_flags & GMVAE_SCHED_SAFE: the schedules in which no workgroup waits for another of its own launch
 // (one workgroup per panel, the first layer as a launch of its own) -- what a caller degrades to after a hand-off timeout
 static bool sched_safe(const GmvaeDims& d) { return (d.sched_flags & GMVAE_SCHED_SAFE) != 0; }
@@ -125,15 +123,6 @@ static bool first_on_device(bool (&seen)[64]) {
   seen[dev] = true;
   return true;
 }
-static int mega_q(const GmvaeDims& d) {
-  const int panels = (d.B + 15) / 16, cus = device_cus();
-  int q = panels * 4 <= cus ? 4 : panels * 2 <= cus ? 2 : 1;
-  const char* e = getenv("GMVAE_MEGA_Q");          // (tests / diagnostics)
-  if (e && atoi(e) >= 1 && atoi(e) <= kMegaQMax) q = atoi(e);
-  if (sched_safe(d)) q = 1;
-  return q;
-}
-
 // ------------------------------------------------------------------ layout
 struct NetL {
   int nl = 0;                 // number of Linear layers
@@ -329,7 +318,7 @@ static int fwd_splits(int D) {
 // the single-launch per-row kernel (mega.hpp), all three models: one hidden layer <= 64, S = 1, 16-byte aligned
 // x rows, its LDS budget, and (VAE_GMP) one prior-gradient partial per workgroup
 // (the *_shape predicates read the dims only: carve() sizes the workspace with them, so that its layout never depends on an
-//  environment switch; the *_ok forms add the switches and choose the schedule)
+//  environment switch; plan_step adds the switches and the bits and chooses the schedule)
 // image tasks of the first launch's auxiliary workgroups (plan_images): the small-weight image's tensors + two per decoder chunk
 // of kCW columns.  Aux carries kMaxImgTasks of them as kernel arguments: D <= 1280 (GMVAE), 1536 (VAE_GMP), 1664 (VAE)
 static int mega_img_tasks(int model, int D) {
@@ -346,23 +335,9 @@ static bool mega_shape(const GmvaeDims& d, int model) {
   if (model == GMVAE_MODEL_VAE_GMP && (d.B + kPanel - 1) / kPanel > GMP_PARTS) return false;
   return (size_t)mega_lay(H, d.L, d.K, d.D, model).total * 4 <= 160 * 1024;
 }
-static bool mega_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;      // (GMVAE_OBJ_WEIGHTS, GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH, GMVAE_OBJ_PIXEL_MASK: the general schedule only, as GMVAE_GRAD_DREG below)
-  if (clip_norm(d)) return false;              // (GMVAE_OPT_CLIP_NORM: no update may start before the whole gradient's norm is known)
-  if (dreg_grad(d)) return false;              // (GMVAE_GRAD_DREG: the general schedule only -- here and not in mega_shape, so
-                                               //  that the workspace layout does not depend on the estimator; so mega2 / mega2v / mega3 / mega3v)
-  const char* e = getenv("GMVAE_NO_MEGA");
-  if (e && atoi(e)) return false;
-  const char* e2 = getenv("GMVAE_NO_FUSED");
-  if (e2 && atoi(e2)) return false;
-  return mega_shape(d, model);
-}
 // mega2_fwd_bwd (mega2.hpp): the steady-state launch specialised for the reference's default sizes
-static bool mega2_ok(const GmvaeDims& d, int model) {
-  const char* e = getenv("GMVAE_NO_MEGA2");
-  if (e && atoi(e)) return false;
-  return model == GMVAE_MODEL_GMVAE && mega_ok(d, model) && d.hidden[0] == M2::H && d.L == M2::L && d.K == M2::K &&
-         d.D == M2::D && d.B <= 1024;
+static bool mega2_shape(const GmvaeDims& d, int model) {
+  return model == GMVAE_MODEL_GMVAE && d.hidden[0] == M2::H && d.L == M2::L && d.K == M2::K && d.D == M2::D && d.B <= 1024;
 }
 // mega2v_fwd_bwd (mega2v.hpp): the same design for the VAE family at small batches, SEVEN workgroups per panel -- the plain
 // VAE at latent 2 (BASELINE configs[0]) and VAE_GMP at latent 64, K = 10 (configs[1]), hidden 64, D = 784
@@ -376,12 +351,6 @@ static int mega2v_kind(const GmvaeDims& d, int model) {       // 0: not these si
 }
 typedef M2V<0, 2, 1> MV0;
 typedef M2V<1, 64, 10> MV1;
-static bool mega2v_ok(const GmvaeDims& d, int model) {
-  const char* e = getenv("GMVAE_NO_MEGA2");
-  if (e && atoi(e)) return false;
-  return mega_ok(d, model) && mega2v_kind(d, model) != 0 && (d.B + kPanel - 1) / kPanel * 7 <= device_cus() && !sched_safe(d) &&
-         !getenv("GMVAE_MEGA_Q");
-}
 // the skinny schedule (skinny.hpp): GMVAE, one WIDE hidden layer, a SMALL batch -- bin/run_train.sh's sizes
 constexpr int kSkMaxB = 4096;       // hard bound of the skinny schedule's batch (its buffers are carved up to here)
 static bool skinny_shape(const GmvaeDims& d, int model) {
@@ -397,26 +366,12 @@ static bool skinny_shape(const GmvaeDims& d, int model) {
   return H % 64 == 0 && H <= 1024 && d.D % 16 == 0 && d.L % 4 == 0 && d.L >= 4 && d.L <= 256 &&
          (model != GMVAE_MODEL_GMVAE || d.K <= 16) && d.B <= kSkMaxB;
 }
-static bool skinny_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d) || clip_norm(d)) return false;
-  const char* e = getenv("GMVAE_NO_SKINNY");
-  if (e && atoi(e)) return false;
-  int maxb = kSkMaxB;
-  if (const char* mb = getenv("GMVAE_SKINNY_MAXB")) maxb = atoi(mb) < kSkMaxB ? atoi(mb) : kSkMaxB;     // (tools/sk_sweep.py)
-  return skinny_shape(d, model) && d.B <= maxb;
-}
 static bool fused_shape(const GmvaeDims& d, int model) {
   if (model != GMVAE_MODEL_GMVAE || marginal_y(d) || d.n_hidden != 1 || d.S != 1 || d.hidden_act != GMVAE_ACT_RELU) return false;
   const int H = d.hidden[0];
   if (H % 16 || H > 64 || d.L % 8 || d.L > 128 || d.K > 64) return false;
   const int f = fwd_lay(H, d.L, d.K).total, b = bwd_lay(H, d.L, d.K).total;
   return (size_t)(f > b ? f : b) * 4 <= 156 * 1024;
-}
-static bool fused_ok(const GmvaeDims& d, int model) {
-  if (dreg_grad(d) || obj_weights(d) || y_head_bits(d) || pixel_mask(d) || clip_norm(d)) return false;
-  const char* e = getenv("GMVAE_NO_FUSED");
-  if (e && atoi(e)) return false;
-  return fused_shape(d, model);
 }
 
 // evalf_rows (evalf.hpp): the forward-only pass of the GMVAE at the reference's default sizes, any batch, any number of samples
@@ -427,18 +382,12 @@ static bool evalf_shape(const GmvaeDims& d, int model) {
   if (model == GMVAE_MODEL_VAE) return d.L == 2 || d.L == 64;          // (evalf_rows_v: BASELINE configs[0]'s latent size, and 64)
   return d.L == 64 && d.K == 10;                                       // VAE_GMP: configs[1]
 }
-static bool evalf_ok(const GmvaeDims& d, int model) {
-  if (obj_weights(d) || y_head_bits(d) || pixel_mask(d)) return false;      // (gmvae_forward honours GMVAE_OBJ_WEIGHTS, the y head's bits and GMVAE_OBJ_PIXEL_MASK: the general schedule's forward)
-  const char* e = getenv("GMVAE_NO_EVALF");
-  if (e && atoi(e)) return false;
-  if (!evalf_shape(d, model)) return false;
-  // a workgroup stages 8 batch rows per table pass: with ONE sample per row and more than 8 batch rows per workgroup a pass is half
-  // a panel on one wave (measured, tools/eval_time.py: B = 8192, S = 1: 110 / 139 us against 115 / 81 on the chain / general
-  // schedules; every other shape tried is 1.0 - 2.4x faster here)
+// its grid: a workgroup per compute unit, at most one per batch row
+static int eval_fused_grid(const GmvaeDims& d) {
   int grid = device_cus();
   if (grid > d.B) grid = d.B;
   if (grid > 1024) grid = 1024;
-  return !(d.S == 1 && (d.B + grid - 1) / grid > EV::NB);
+  return grid;
 }
 
 static int num_splits(long long R) {
@@ -457,24 +406,6 @@ static int num_splits_small(long long R) {
   const char* e = getenv("GMVAE_NSPLIT_SMALL");      // (tests: the many-splits path at sizes the oracle covers)
   if (e && atoi(e) >= 1 && atoi(e) <= NS_SMALL_MAX) ns = atoi(e);
   return (int)ns;
-}
-
-// The top decoder layer's three GEMMs (logits, data gradient, weight gradient) on the bf16 matrix cores from operands split
-// once by their producers (gemm.hpp plane_rounds): interior 128-tiles in every orientation, and enough rows to pay for the
-// split launches (measured at the config-5 shard, tools/gemm_planes.py: 1.45 - 1.65x the fp32 MFMA instance per GEMM).
-static bool planes_ok(const GmvaeDims& d, const Layout& L) {
-  const char* e = getenv("GMVAE_NO_PLANES");
-  if (e && atoi(e)) return false;
-  if (pixel_mask(d)) return false;                      // (the masked Bernoulli epilogue writes fp32 C alone)
-  if (d.hidden_act != GMVAE_ACT_RELU) return false;     // (the plane producers' epilogues are the ReLU ones)
-  const long long R = (long long)d.B * rows_per_x(d);
-  const int Ht = L.dec.dim[L.dec.nl - 1];
-  long long minr = 4096;
-  if (const char* m = getenv("GMVAE_PLANES_MINROWS")) minr = atoll(m);     // (tests: the plane path at sizes the oracle covers)
-  // (below ~4096 rows, or with a contraction of a few rounds, the split launches and the tile prologues eat the gain: measured
-  //  only at the config-5 shard's 25600 x 3072 x 512; the forced test sizes set GMVAE_PLANES_MINROWS)
-  const bool big = getenv("GMVAE_PLANES_MINROWS") != nullptr || (Ht >= 256 && d.D >= 512);
-  return L.dec.nl >= 2 && big && R >= minr && R % 128 == 0 && d.D % 128 == 0 && Ht % 128 == 0 && R * d.D < (1ll << 32);
 }
 
 static uint64_t clip_parts(uint64_t P) { return (P + kClipSpan - 1) / kClipSpan; }      // gclip.hpp: one partial per 1024 elements
@@ -543,7 +474,7 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
       w.xfl = reinterpret_cast<unsigned long long*>(take(2ull * ((B + 15) / 16 + 1) * 4 * kPanel * 2 * d.hidden[0]));      // (+ 1: mega2 pairs panels)
     w.gstamps = reinterpret_cast<unsigned long long*>(take(2ull * 4 * 2048 * 8));
     w.spans = reinterpret_cast<unsigned long long*>(take(2ull * 2 * 3 * 2048 * 2));
-    if (model == GMVAE_MODEL_GMVAE && d.hidden[0] == M2::H && d.L == M2::L && d.K == M2::K && d.D == M2::D && d.B <= 1024) {
+    if (mega2_shape(d, model)) {
       w.m3flags = reinterpret_cast<unsigned*>(take((uint64_t)kM3FlagReplicas * kM3FlagRepLd));      // mega3_step's flag replicas
       w.img2f = take(M2::imgF);                  // (not gated by GMVAE_NO_MEGA2: the workspace layout must not depend on a switch)
       w.img2b = take(M2::imgB);
@@ -639,24 +570,6 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.clip_part = reinterpret_cast<double*>(take(2 * clip_parts(L.P_pad)));
   }
   w.bytes = off;
-}
-
-// forward-only steps (evaluation: S importance samples per row) whose logits GEMM is worth running on f16 pairs: the plane path
-// proper (planes_ok) needs D % 128 == 0 and a wide hidden layer because its BACKWARD GEMMs read (sigmoid - x) planes; forward
-// only, the one GEMM takes any D % 8 == 0 (weight planes zero-padded to the tile) and any hidden width % 32.  (eval_iwae:
-// 51200 x 784 x 64 -- as fp32 MFMA the launch is half matrix time, half Bernoulli epilogue.)
-static bool fwd_pairs_ok(const GmvaeDims& d, const Layout& L) {
-  const char* e = getenv("GMVAE_NO_PLANES");
-  if (e && atoi(e)) return false;
-  const char* x = getenv("GMVAE_PLANES_EXACT");
-  if (x && atoi(x)) return false;
-  if (pixel_mask(d)) return false;
-  if (d.hidden_act != GMVAE_ACT_RELU || L.dec.nl < 2) return false;
-  const long long R = (long long)d.B * rows_per_x(d);
-  const int Ht = L.dec.dim[L.dec.nl - 1];
-  long long minr = 8192;
-  if (const char* m = getenv("GMVAE_PLANES_MINROWS")) minr = atoll(m);
-  return R >= minr && R % 128 == 0 && Ht % 32 == 0 && d.D % 8 == 0 && R * ((d.D + 127) / 128 * 128) < (1ll << 32);
 }
 
 // ----------------------------------------------------------- GEMM building
@@ -988,6 +901,7 @@ static int grid_for(long long items, int per_block, int cap) {
 }
 
 // -------------------------------------------------------------- the step
+struct StepPlan;
 struct StepArgs {
   const GmvaeDims* d;
   int model;
@@ -1008,10 +922,11 @@ struct StepArgs {
   bool imgs_ready = false;
   bool want_spans = false;     // measurement: every launch of the step records per-workgroup wall-clock stamps
   int span_slot = 0;           // ... into this slot of WS::spans (two consecutive steps can be stamped)
-  bool dp_images = false;      // data-parallel graph: the Adam launch after the all-reduce scatters the weight images
+  bool dp_graph = false;       // data-parallel graph: the Adam launch after the all-reduce can scatter the weight images
   float* tail_log = nullptr;   // train graph: this step's slot of the per-step tail log (may be null)
   int slot = 0;                // which slot of the per-step inputs' regions the step reads (step_inputs; step i of a train graph: i)
   bool iw_chunk = false;       // a chunk pass of gmvae_iw_bound: iw_tail writes the tail, [5..7] = 0 -- no pmask_tail
+  const StepPlan* plan = nullptr;      // the caller has taken the step's plan already (dp_step_impl)
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -1029,7 +944,7 @@ struct ImgPlan {
   bool map_ok = true;
 };
 static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS& w, const MegaLay& ml, const float* P,
-                        ImgPlan& pl) {
+                        bool m2, int vk, ImgPlan& pl) {
   const bool gm = model == GMVAE_MODEL_GMVAE, gmp = model == GMVAE_MODEL_VAE_GMP;
   const int K = d.K, Lz = d.L, D = d.D, H = d.hidden[0];
   const NetL &E = gm ? L.ency : L.enc, &G = L.encg, &Dn = L.dec;
@@ -1082,7 +997,7 @@ static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS
   }
   add_map(Dn.w[1], (long long)H * D, D, 1, 0, ml.ldc, 1);
   add_map(Dn.b[1], D, D, 1, H * ml.ldc, ml.ldc, 1);
-  if (mega2_ok(d, model) && w.img2f) {
+  if (m2) {
     // the steady-state launch is mega2_fwd_bwd: the optimiser scatters into ITS operand images instead (every weight of a
     // matrix product twice: forward and transposed orientation; kernels.hpp img_dst kinds 2..6)
     pl.nmap = 0; pl.map_ok = true;
@@ -1107,9 +1022,8 @@ static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS
     add_map(Dn.w[1], (long long)H * D, D, 5, M2::dB, 64, 4, M2::dBq);
     add_map(Dn.b[1], D, D, 6, M2::dbias, 0, 4, M2::dbq);
   }
-  if (mega2v_ok(d, model) && w.img2f) {
+  if (vk) {
     // mega2v_fwd_bwd's operand images (mega2v.hpp M2V): the same kinds; the decoder layer dealt to seven workgroups (7..9)
-    const int vk = mega2v_kind(d, model);
     pl.nmap = 0; pl.map_ok = true;
 #define GMVAE_MV(f) (vk == 1 ? MV0::f : MV1::f)
     add_map(E.b[0], H, H, 0, GMVAE_MV(b_e0), H, 2);
@@ -1136,8 +1050,146 @@ static void plan_images(const GmvaeDims& d, int model, const Layout& L, const WS
   }
 }
 
+// ---- the step's plan: which kernels a step runs is decided HERE and nowhere else -- once per step, from the dims, the few
+// facts of the call that are neither dims nor workspace (StepCtx), the device and the GMVAE_* switches.  The switches are read on
+// every call (tests flip them between two calls of one process: nothing is cached).  run_step_impl dispatches on the plan, the
+// schedules read its fields, gmvae_step_schedule formats it, dp_step_impl chooses its optimizer launch by it.  The *_shape
+// predicates above say what a schedule's kernels can run (carve sizes the workspace by them); the gates proper -- mega_ok, mega2_ok,
+// mega2v_ok, skinny_ok, evalf_ok, fused_ok, planes_ok, fwd_pairs_ok -- are plan_step's locals; a new objective bit is gated in
+// the two masks below.
+enum StepKind { STEP_GENERAL, STEP_MEGA, STEP_SKINNY, STEP_FUSED, STEP_EVALF };
+struct StepCtx {
+  bool backward = false;     // forward and backward (a training step) / forward only
+  bool outputs = false;      // z / y / logits are wanted (the chain kernels do not write them)
+  bool adam_own = false;     // the optimizer runs on this device on the step's own parameters (StepArgs::adam_p == params)
+  bool step_dev = false;     // the step counter lives on the device (a graph's step)
+  bool dp_graph = false;     // StepArgs::dp_graph
+  bool imgs_ready = false;   // StepArgs::imgs_ready
+  bool gen_noise = false;    // eps comes from the in-kernel Philox
+  const float* params = nullptr;      // (null: no image plan -- gmvae_step_schedule and the profiles' admission)
+};
+struct StepPlan {
+  StepKind kind = STEP_GENERAL;
+  StepCtx c;
+  // mega: mega2_fwd_bwd's sizes / mega2v_fwd_bwd's instance (mega2v_kind; either runs where fl), workgroups per panel, the first
+  // layer inside the launch, the step as ONE launch (mega3_step / mega3v_step), the first launch skipped, who leaves the next
+  // step's weight images behind: finalize_adam (on_update), the Adam launch behind the all-reduce (dp_images; in tile shape)
+  bool m2 = false, fl = false, one_launch = false, imgs_ready = false, imgs_on_update = false, dp_images = false, adam_tiles = false;
+  int vk = 0, Q = 1;
+  ImgPlan img;
+  // general: the top decoder layer on planes (f16 pairs / exact bf16 triples), the forward-only logits GEMM on pairs, rowsws.hpp
+  bool planes = false, pairs = false, fwdp = false, rws = false;
+};
+// The bits that only the general schedule implements.  A forward-only pass that carries one of kGeneralOnlyFwd, a training step
+// that carries one of kGeneralOnlyTrain, takes it -- decided here and not in the *_shape predicates, so that the workspace layout
+// does not depend on them (so mega2 / mega2v / mega3 / mega3v too).
+constexpr unsigned kGeneralOnlyFwd =
+    GMVAE_OBJ_WEIGHTS |               // wobj.hpp's kernels in row_terms' / ymarg_rows' / y_head_bwd's place, wobj_tail behind loss_tail
+    GMVAE_Y_TEMP_DEV |                // ytemp.hpp's kernels in y_head_fwd's / y_head_bwd's / y_head_bwd_w's place
+    GMVAE_Y_STRAIGHT_THROUGH |        // (the same)
+    GMVAE_OBJ_PIXEL_MASK;             // pmask.hpp: x~ = m x, the masked Bernoulli epilogue of gemm.hpp, pmask_tail behind loss_tail
+constexpr unsigned kGeneralOnlyTrain = kGeneralOnlyFwd |
+    GMVAE_GRAD_DREG |                 // kernels.hpp z_head_bwd_dreg: the backward of the general schedule alone
+    GMVAE_OPT_CLIP_NORM;              // no update may start before the whole gradient's norm is known
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static bool env_on(const char* name) { const char* e = getenv(name); return e && atoi(e); }
+static StepPlan plan_step(const GmvaeDims& d, int model, const Layout& L, const WS& w, const StepCtx& c) {
+  StepPlan p;
+  p.c = c;
+  const int B = d.B, panels = (B + kPanel - 1) / kPanel, cus = device_cus();
+  const bool safe = sched_safe(d), bits_ok = !(d.sched_flags & (c.backward ? kGeneralOnlyTrain : kGeneralOnlyFwd));
+  int sk_maxb = kSkMaxB;
+  if (const char* mb = getenv("GMVAE_SKINNY_MAXB")) sk_maxb = atoi(mb) < kSkMaxB ? atoi(mb) : kSkMaxB;      // (tools/sk_sweep.py)
+  const bool mega_ok = bits_ok && c.backward && !env_on("GMVAE_NO_MEGA") && !env_on("GMVAE_NO_FUSED") && mega_shape(d, model);
+  const bool skinny_ok = bits_ok && c.backward && !env_on("GMVAE_NO_SKINNY") && skinny_shape(d, model) && B <= sk_maxb;
+  // evalf: a workgroup stages 8 batch rows per table pass: with ONE sample per row and more than 8 batch rows per workgroup a pass
+  // is half a panel on one wave (measured, tools/eval_time.py: B = 8192, S = 1: 110 / 139 us against 115 / 81 on the chain /
+  // general schedules; every other shape tried is 1.0 - 2.4x faster here)
+  const bool evalf_ok = bits_ok && !c.backward && !env_on("GMVAE_NO_EVALF") && evalf_shape(d, model) &&
+                        !(d.S == 1 && (B + eval_fused_grid(d) - 1) / eval_fused_grid(d) > EV::NB);
+  const bool fused_ok = bits_ok && !c.outputs && !env_on("GMVAE_NO_FUSED") && fused_shape(d, model);
+  p.kind = mega_ok ? STEP_MEGA : skinny_ok ? STEP_SKINNY : evalf_ok ? STEP_EVALF : fused_ok ? STEP_FUSED : STEP_GENERAL;
+  if (p.kind == STEP_MEGA) {
+    const char* q = getenv("GMVAE_MEGA_Q");           // (tests / diagnostics)
+    const bool mega2_ok = !env_on("GMVAE_NO_MEGA2") && mega2_shape(d, model);
+    const bool mega2v_ok = !env_on("GMVAE_NO_MEGA2") && mega2v_kind(d, model) != 0 && panels * 7 <= cus && !safe && !q;
+    p.m2 = mega2_ok;
+    p.vk = mega2v_ok ? mega2v_kind(d, model) : 0;
+    // Workgroups that share one 16-row panel of mega_fwd_bwd (they split its decoder chunks): as many as keep the whole grid
+    // co-resident on the chip's 256 CUs (one 150 KB-LDS workgroup per CU); mega2v_fwd_bwd: seven
+    p.Q = panels * 4 <= cus ? 4 : panels * 2 <= cus ? 2 : 1;
+    if (q && atoi(q) >= 1 && atoi(q) <= kMegaQMax) p.Q = atoi(q);
+    if (safe) p.Q = 1;
+    if (p.vk) p.Q = 7;
+    const MegaLay ml = mega_lay(d.hidden[0], d.L, d.K, d.D, model);
+    if (c.params) plan_images(d, model, L, w, ml, c.params, p.m2, p.vk, p.img);
+    const bool scatter_ok = c.params && p.img.map_ok && ml.fl_ok;      // every parameter an image holds has its place in the map
+    const bool fl_on = scatter_ok && !env_set("GMVAE_NO_FL") && !safe;
+    // (VAE_GMP's prior variables come as per-panel partials: the data-parallel graph keeps its plain Adam launch)
+    p.dp_images = c.dp_graph && model != GMVAE_MODEL_VAE_GMP && fl_on;
+    p.adam_tiles = p.dp_images && p.m2 && !env_set("GMVAE_NO_ADAM_TILES");
+    p.imgs_on_update = c.adam_own && scatter_ok;
+    p.imgs_ready = c.imgs_ready && (!c.dp_graph || p.dp_images);
+    // The first layer runs inside the launch where the previous step's optimizer leaves the images behind (or img_build builds
+    // them) and a panel's workgroups are all resident for their exchange, one per CU (mega2 pairs panels: an even number of them)
+    p.fl = fl_on && (p.Q == 4 || p.vk) && (p.m2 ? (panels + 1) & ~1 : panels) * p.Q <= cus && (c.adam_own || p.dp_images) &&
+           c.step_dev && c.gen_noise;
+    // mega3_step (B = 1024: 256 workgroups for the 241 tile slots and the register-resident contraction forms; measured at smaller
+    // batches -- fewer workgroups than slots -- the one-launch form loses: B = 512 43.2 against 33.8 us, profiles/round5_notes.md.
+    // GMVAE_FUSE=1 forces it for any batch: tools/fuse_check.py) / mega3v_step (where the optimizer runs on this device; its grid
+    // is 256 workgroups whatever the batch -- the role-less workers --, one per CU: all of them must be resident).  Either reads
+    // hand-off buffers with plain loads: device_is_gfx950
+    if (p.fl && !env_set("GMVAE_NO_FUSE") && (p.m2 ? B == 1024 || env_set("GMVAE_FUSE") : p.vk && c.adam_own && cus >= 256))
+      p.one_launch = device_is_gfx950();
+  }
+  if (p.kind == STEP_GENERAL) {
+    // The top decoder layer's three GEMMs (logits, data gradient, weight gradient) on the bf16 matrix cores from operands split
+    // once by their producers (gemm.hpp plane_rounds): interior 128-tiles in every orientation, and enough rows to pay for the
+    // split launches (measured at the config-5 shard, tools/gemm_planes.py: 1.45 - 1.65x the fp32 MFMA instance per GEMM; below
+    // ~4096 rows, or with a contraction of a few rounds, the split launches and the tile prologues eat the gain: measured only at
+    // the config-5 shard's 25600 x 3072 x 512; the forced test sizes set GMVAE_PLANES_MINROWS).  The piece form: f16 pairs (3 piece
+    // products, <= 3 x 2^-22 per product) unless GMVAE_PLANES_EXACT=1 asks for the bf16 triples (6 piece products, every one exact).
+    // Forward only (evaluation: S importance samples per row), the one logits GEMM runs on f16 pairs from 8192 rows, at any
+    // D % 8 == 0 (weight planes zero-padded to the tile) and any hidden width % 32: the BACKWARD GEMMs are what need D % 128 == 0
+    // and a wide layer, they read (sigmoid - x) planes.  (eval_iwae: 51200 x 784 x 64 -- as fp32 MFMA the launch is half matrix
+    // time, half Bernoulli epilogue.)  No planes under GMVAE_OBJ_PIXEL_MASK (the masked Bernoulli epilogue writes fp32 C alone) or
+    // another activation (the plane producers' epilogues are the ReLU ones).
+    const long long R = (long long)B * rows_per_x(d);
+    const int Ht = L.dec.dim[L.dec.nl - 1];
+    const char* mr = getenv("GMVAE_PLANES_MINROWS");          // (tests: the plane paths at sizes the oracle covers)
+    const bool exact = env_on("GMVAE_PLANES_EXACT");
+    const bool any = !env_on("GMVAE_NO_PLANES") && !pixel_mask(d) && d.hidden_act == GMVAE_ACT_RELU && L.dec.nl >= 2 && R % 128 == 0;
+    const bool planes_ok = any && (mr || (Ht >= 256 && d.D >= 512)) && R >= (mr ? atoll(mr) : 4096) && d.D % 128 == 0 &&
+                           Ht % 128 == 0 && R * d.D < (1ll << 32);
+    const bool fwd_pairs_ok = any && !exact && R >= (mr ? atoll(mr) : 8192) && Ht % 32 == 0 && d.D % 8 == 0 &&
+                              R * ((d.D + 127) / 128 * 128) < (1ll << 32);
+    p.planes = planes_ok;
+    p.pairs = planes_ok && !exact;
+    p.fwdp = !planes_ok && !c.backward && fwd_pairs_ok;
+    p.rws = d.hidden_act == GMVAE_ACT_RELU && R >= 2048 && !env_set("GMVAE_NO_RWS");
+  }
+  return p;
+}
+static StepCtx step_ctx(const StepArgs& a) {
+  StepCtx c;
+  c.backward = a.backward; c.outputs = a.z_out || a.y_out || a.logits_out;
+  c.adam_own = a.adam_p && a.adam_p == a.params; c.step_dev = a.step_dev != nullptr;
+  c.dp_graph = a.dp_graph; c.imgs_ready = a.imgs_ready; c.gen_noise = !a.eps; c.params = a.params;
+  return c;
+}
+// the plan of a training step as gmvae_step runs it, from the dims alone (gmvae_step_schedule, the profiles' admission)
+static StepPlan plan_train_step(const GmvaeDims& d, int model) {
+  Layout L;
+  build_layout(d, model, L);
+  WS w;
+  carve(d, model, L, nullptr, w);
+  StepCtx c;
+  c.backward = true;
+  return plan_step(d, model, L, w, c);
+}
+
 // end of the fused schedules: slab reduce + loss tail (+ TF-Adam in the graph path)
-static int finish_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, float* tail, int NS, int B,
+static int finish_fused(Ctx& cx, const StepArgs& a, const StepPlan& pn, const Layout& L, WS& w, float* tail, int NS, int B,
                         const SlabX* sxp = nullptr) {
   SlabX sx;
   memset(&sx, 0, sizeof(sx));
@@ -1148,7 +1200,8 @@ static int finish_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, floa
   float* sl = w.slabs;
   const bool gmp = a.model == GMVAE_MODEL_VAE_GMP;
   const float* nent = a.model == GMVAE_MODEL_GMVAE ? w.nent : nullptr;
-  if ((!gmp || mega_ok(d, a.model)) && (!a.adam_p || a.step_dev)) {   // slab reduce + loss tail (+ TF-Adam) in one launch
+  const bool mega = pn.kind == STEP_MEGA;
+  if ((!gmp || mega) && (!a.adam_p || a.step_dev)) {   // slab reduce + loss tail (+ TF-Adam) in one launch
     FinalArgs fa;
     memset(&fa, 0, sizeof(fa));
     fa.slabs = sl; fa.nslab = NS; fa.P = PP; fa.grads = a.grads; fa.p = a.adam_p; fa.m = a.adam_m; fa.v = a.adam_v;
@@ -1156,19 +1209,17 @@ static int finish_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, floa
     fa.logw = w.logw; fa.logpx = w.logpx; fa.logq = w.logq; fa.logp = w.logp; fa.nent = nent;
     fa.tail = tail; fa.B = B; fa.step_dev = reinterpret_cast<unsigned long long*>(a.step_dev); fa.tail_log = a.tail_log;
     fa.nmap = 0; fa.map_lo = fa.map_hi = 0; fa.epoch_word = nullptr;
-    fa.err_word = (mega_ok(d, a.model) && w.sync) ? w.sync + 1 : nullptr;
+    fa.err_word = (mega && w.sync) ? w.sync + 1 : nullptr;
     fa.sx = sx;
     if (gmp) {                               // (mega schedule only: one partial per panel)
       const int KLp = (int)pad4((uint64_t)d.K * d.L);
       fa.gmp_part = w.gmp_part; fa.gmp_n = (B + kPanel - 1) / kPanel; fa.gmp_len = 2 * KLp + (int)pad4(d.K); fa.gmp_off = (long long)L.loc;
     }
     fa.span = (a.want_spans && w.spans) ? w.spans + (size_t)a.span_slot * 3 * 2048 * 2 + 2048 * 2 : nullptr;
-    if (mega_ok(d, a.model) && a.adam_p && a.adam_p == a.params) {      // the next step's weight images ride on the update
-      const MegaLay ml = mega_lay(d.hidden[0], d.L, d.K, d.D, a.model);
-      ImgPlan pl;
-      plan_images(d, a.model, L, w, ml, a.params, pl);
+    if (mega && pn.c.adam_own) {      // the next step's weight images ride on the update
+      const ImgPlan& pl = pn.img;
       fa.epoch_word = w.sync;
-      if (pl.map_ok && ml.fl_ok) {
+      if (pn.imgs_on_update) {
         fa.nmap = pl.nmap; fa.map_lo = pl.lo; fa.map_hi = pl.hi;
         fa.img[0] = w.img_m; fa.img[1] = w.dimg; fa.img[2] = w.img2f; fa.img[3] = w.img2b; fa.img[4] = w.dimg2;
         int n = 0;
@@ -1266,7 +1317,7 @@ static void dw_tensors(const GmvaeDims& d, const int model, const Layout& L, con
 }
 
 // ---- the mega schedule (all three models): first-layer split-K GEMM (+ aux) -> mega_fwd_bwd -> all dW -> finish
-static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, const float* eps, const float* u,
+static int run_step_mega(Ctx& cx, const StepArgs& a, const StepPlan& pn, const Layout& L, WS& w, const float* eps, const float* u,
                          float* gen_eps, float* gen_u) {
   const GmvaeDims& d = *a.d;
   const int model = a.model;
@@ -1282,30 +1333,21 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
   const MegaLay ml = mega_lay(H, Lz, K, D, model);
   const int H2 = gm ? 2 * H : H;
   // The first launch (first layer as split-K partials + noise + weight images) is skipped when the previous step
-  // of the same graph left the images behind (finalize_adam) and the launch below can run the first layer itself:
-  // a panel's 4 workgroups must all be resident for their exchange, i.e. one workgroup per CU.
-  const int n_cu = device_cus();
-  const int vk = (mega2v_ok(d, model) && w.img2f) ? mega2v_kind(d, model) : 0;
-  const int Qm = vk ? 7 : mega_q(d);
-  const int np_grid = (!vk && mega2_ok(d, model)) ? (((B + kPanel - 1) / kPanel + 1) & ~1) : (B + kPanel - 1) / kPanel;   // (mega2 pairs panels)
-  bool fl = ml.fl_ok && (Qm == 4 || vk) && np_grid * Qm <= n_cu &&
-            (a.adam_p == a.params || a.dp_images) && a.step_dev && gen_eps && w.xfl && !getenv("GMVAE_NO_FL") && !sched_safe(d);
-  if (fl && !a.imgs_ready) {
+  // of the same graph left the images behind (finalize_adam) and the launch below can run the first layer itself (plan_step).
+  const int vk = pn.vk, Qm = pn.Q;
+  const bool fl = pn.fl;
+  const ImgPlan& pl = pn.img;
+  if (fl && !pn.imgs_ready) {
     // first step of a train graph / an eager step: the weight images straight from the parameters (kernels.hpp img_build),
     // then the same launches as every later step
-    ImgPlan pl;
-    plan_images(d, model, L, w, ml, P, pl);
-    if (!pl.map_ok) fl = false;
-    else {
-      ImgScatter sc;
-      memset(&sc, 0, sizeof(sc));
-      sc.nmap = pl.nmap; sc.lo = pl.lo; sc.hi = pl.hi; sc.epoch_word = w.sync;
-      sc.img[0] = w.img_m; sc.img[1] = w.dimg; sc.img[2] = w.img2f; sc.img[3] = w.img2b; sc.img[4] = w.dimg2;
-      for (int i = 0; i < pl.nmap; ++i) { sc.map[i] = pl.map[i]; sc.mbegin[i] = pl.map[i].begin; sc.mend[i] = pl.map[i].end; }
-      hipLaunchKernelGGL(img_build, dim3((unsigned)((L.P_pad / 4 + 255) / 256)), dim3(256), 0, st, P, (long long)L.P_pad, sc);
-      cx.check();
-      cx.mark("img_build", 0);
-    }
+    ImgScatter sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.nmap = pl.nmap; sc.lo = pl.lo; sc.hi = pl.hi; sc.epoch_word = w.sync;
+    sc.img[0] = w.img_m; sc.img[1] = w.dimg; sc.img[2] = w.img2f; sc.img[3] = w.img2b; sc.img[4] = w.dimg2;
+    for (int i = 0; i < pl.nmap; ++i) { sc.map[i] = pl.map[i]; sc.mbegin[i] = pl.map[i].begin; sc.mend[i] = pl.map[i].end; }
+    hipLaunchKernelGGL(img_build, dim3((unsigned)((L.P_pad / 4 + 255) / 256)), dim3(256), 0, st, P, (long long)L.P_pad, sc);
+    cx.check();
+    cx.mark("img_build", 0);
   }
   if (!fl) {  // P1: first layer(s) over the uint8 batch as single-round split-K partials + auxiliary workgroups
     Group g;
@@ -1323,8 +1365,6 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
     ax.step_dev = reinterpret_cast<unsigned long long*>(a.step_dev);
     ax.epoch_word = w.sync;
     ax.noise_blocks = (int)((noise_items(gen_eps, gen_u, ax.n_rows, Lz, K) + kThreads - 1) / kThreads);
-    ImgPlan pl;
-    plan_images(d, model, L, w, ml, P, pl);
     const int nt = pl.nt;
     for (int i = 0; i < nt; ++i) ax.task[i] = pl.task[i];
     ax.ntasks = nt;
@@ -1336,9 +1376,7 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
   // arguments are kept until the tile list below is built
   MegaArgs c3;
   bool fuse_pending = false, fusev_pending = false;
-  int vkind = 0;
   double m2_flops = 0;
-  const bool dw_upd_ = a.adam_p && a.adam_p == a.params;
   {  // the whole per-row forward + backward in one launch
     MegaArgs c;
     memset(&c, 0, sizeof(c));
@@ -1377,7 +1415,7 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
       for (int i = 0; i < 8; ++i)
         hipFuncSetAttribute(reinterpret_cast<const void*>(fns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
-    const bool m2 = fl && mega2_ok(d, model) && w.img2f;
+    const bool m2 = fl && pn.m2;
     const bool m2v = fl && vk != 0;
     m2_ran = m2 || m2v;
     if (m2) {
@@ -1388,11 +1426,7 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
       if (first_on_device(m2attr)) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(mega2_fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       }
-      // (B = 1024: 256 workgroups for the 241 tile slots and the register-resident contraction forms; measured at smaller
-      //  batches -- fewer workgroups than slots -- the one-launch form loses: B = 512 43.2 against 33.8 us, profiles/round5_notes.md.
-      //  GMVAE_FUSE=1 forces it for any batch: tools/fuse_check.py)
-      fuse_pending = (dw_upd_ || a.dp_images) && a.step_dev && !getenv("GMVAE_NO_FUSE") && (B == 1024 || getenv("GMVAE_FUSE")) &&
-                     device_is_gfx950();
+      fuse_pending = pn.one_launch;
       c3 = c;
       // (an even number of panels: the first layer works on pairs of them, mega2.hpp)
       if (!fuse_pending)
@@ -1408,9 +1442,7 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
       }
       const unsigned grid = (unsigned)((B + kPanel - 1) / kPanel * 7);
       // (mega3v_step: the step as ONE launch where the optimizer runs on this device; the data-parallel graph keeps two launches)
-      // (its grid is 256 workgroups whatever the batch -- the role-less workers --, one per CU: all of them must be resident)
-      fusev_pending = dw_upd_ && a.step_dev && !getenv("GMVAE_NO_FUSE") && grid <= 256 && n_cu >= 256 && device_is_gfx950();
-      vkind = vk;
+      fusev_pending = pn.one_launch;
       c3 = c;
       if (fusev_pending) { /* launched below, with the tile list */ }
       else if (vk == 1) hipLaunchKernelGGL((mega2v_fwd_bwd<0, 2, 1>), dim3(grid), dim3(kMT), (size_t)MV0::total * sizeof(float), st, c);
@@ -1430,206 +1462,188 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
   }
   // Single device, steady state of a train graph at the specialised sizes: weight gradients AND the optimizer in one
   // launch (dwadam.hpp) -- no split-K slabs, no finalize_adam.
-  const bool dw_upd = a.adam_p && a.adam_p == a.params;     // single device: the optimizer runs in the same launch
+  const bool dw_upd = pn.c.adam_own;     // single device: the optimizer runs in the same launch
   // (every model of the mega schedule whose gradients are all matrix products: the learned mixture prior's variables of
   //  VAE_GMP come as per-panel partials and keep the split-K launch + finalize_adam)
-  if (fl && (dw_upd || a.dp_images) && a.step_dev) {
-    ImgPlan pl;
-    plan_images(d, model, L, w, ml, a.params, pl);
-    if (pl.map_ok) {
-      std::vector<DwArgs> da_store(1);           // (4 KB of host scratch per call: engines may step from several host threads)
-      DwArgs& da = da_store[0];
-      memset(&da, 0, sizeof(da));
-      da.B = B;
-      da.u8x3 = 1;
-      da.dbg = getenv("GMVAE_STAMPS") ? w.gstamps + 3 * 2048 * 8 : nullptr;
-      da.lr_t = m2_ran ? reinterpret_cast<const float*>(w.sync + 2) : nullptr;
-      da.ln_b1 = (float)log((double)a.beta1); da.ln_b2 = (float)log((double)a.beta2);
-      dw_tensors(d, model, L, w, a.x, pl, da);
-      {  // XCD-aware order: slot b runs on XCD b % 8 (observed round-robin placement; speed only)
-        std::vector<int> cls(kDwMaxTiles);       // the XCD a tile would like: the one that shares its larger operand
-        bool used[kDwMaxTiles];
-        const int nt = da.total_tiles <= kDwMaxTiles ? da.total_tiles : 0;
+  if (fl) {          // (the optimizer, here or behind the all-reduce, leaves every image behind: the tiles know their places in them)
+    std::vector<DwArgs> da_store(1);           // (4 KB of host scratch per call: engines may step from several host threads)
+    DwArgs& da = da_store[0];
+    memset(&da, 0, sizeof(da));
+    da.B = B;
+    da.u8x3 = 1;
+    da.dbg = getenv("GMVAE_STAMPS") ? w.gstamps + 3 * 2048 * 8 : nullptr;
+    da.lr_t = m2_ran ? reinterpret_cast<const float*>(w.sync + 2) : nullptr;
+    da.ln_b1 = (float)log((double)a.beta1); da.ln_b2 = (float)log((double)a.beta2);
+    dw_tensors(d, model, L, w, a.x, pl, da);
+    {  // XCD-aware order: slot b runs on XCD b % 8 (observed round-robin placement; speed only)
+      std::vector<int> cls(kDwMaxTiles);       // the XCD a tile would like: the one that shares its larger operand
+      bool used[kDwMaxTiles];
+      const int nt = da.total_tiles <= kDwMaxTiles ? da.total_tiles : 0;
+      for (int i = 0; i < da.ntens; ++i) {
+        const DwTensor& T = da.t[i];
+        const int tiles_m = ((T.M + 16 * T.mu - 1) / (16 * T.mu));
+        for (int tm = 0; tm < tiles_m; ++tm)
+          for (int tn = 0; tn < T.tiles_n; ++tn) {
+            const int t = T.tile_begin + tm * T.tiles_n + tn;
+            if (t < kDwMaxTiles) cls[t] = (tiles_m >= T.tiles_n ? tm : tn) & 7;      // share the operand with more blocks
+          }
+      }
+      for (int t = 0; t < nt; ++t) used[t] = false;
+      const bool xcd = nt > 0;
+      int next_any = 0;
+      for (int b = 0; b < da.total_tiles && b < kDwMaxTiles; ++b) {
+        int pick = -1;
+        if (xcd) {
+          for (int t = 0; t < nt; ++t)
+            if (!used[t] && cls[t] == (b & 7)) { pick = t; break; }
+          if (pick < 0) { while (next_any < nt && used[next_any]) ++next_any; pick = next_any; }
+          used[pick] = true;
+        } else {
+          pick = b;
+        }
+        int pt = 0;                             // (tensor << 10) | tile inside the tensor (dwadam.hpp)
+        for (int i = 1; i < da.ntens; ++i)
+          if (pick >= da.t[i].tile_begin) pt = i;
+        da.perm[b] = (unsigned short)((pt << 10) | (pick - da.t[pt].tile_begin));
+      }
+      if (da.total_tiles > kDwMaxTiles) { /* cannot happen at these sizes; the launch below is guarded */ }
+    }
+    FinalArgs& fa = da.fa;
+    fa.P = (long long)L.P_pad; fa.grads = a.grads; fa.p = a.adam_p; fa.m = a.adam_m; fa.v = a.adam_v;
+    fa.lr = a.lr; fa.b1 = a.beta1; fa.b2 = a.beta2; fa.eps = a.epsilon; fa.do_adam = dw_upd ? 1 : 0; fa.count = (float)B;
+    fa.logw = w.logw; fa.logpx = w.logpx; fa.logq = w.logq; fa.logp = w.logp; fa.nent = gm ? w.nent : nullptr;
+    fa.tail = tail; fa.B = B; fa.step_dev = reinterpret_cast<unsigned long long*>(a.step_dev); fa.tail_log = a.tail_log;
+    fa.epoch_word = dw_upd ? w.sync : nullptr;   // (data parallel: adam_tf_img, after the all-reduce, bumps the hand-off tag)
+    fa.err_word = w.sync + 1;
+    fa.img[0] = w.img_m; fa.img[1] = w.dimg; fa.img[2] = w.img2f; fa.img[3] = w.img2b; fa.img[4] = w.dimg2;
+    fa.span = (a.want_spans && w.spans) ? w.spans + (size_t)a.span_slot * 3 * 2048 * 2 + 2048 * 2 : nullptr;
+    if (gmp) {                                 // the prior variables: per-panel partials of mega_fwd_bwd
+      const int KLp = (int)pad4((uint64_t)K * Lz);
+      fa.gmp_part = w.gmp_part; fa.gmp_n = (B + kPanel - 1) / kPanel; fa.gmp_len = 2 * KLp + (int)pad4(K); fa.gmp_off = (long long)L.loc;
+      da.gmp_blocks = (fa.gmp_len + kDwThreads - 1) / kDwThreads;
+      for (int i = 0; i < pl.nmap && da.gmp_nmap < 3; ++i)
+        if (pl.map[i].begin >= fa.gmp_off && pl.map[i].end <= fa.gmp_off + fa.gmp_len) da.gmp_map[da.gmp_nmap++] = pl.map[i];
+    }
+    // the padding words of the flat gradient buffer are never written by the tiles: the buffer is all-reduced / read whole
+    if (da.total_tiles > kDwMaxTiles) return GMVAE_E_DIMS;
+    double fl_ = 0;
+    for (int i = 0; i < da.ntens; ++i) fl_ += 2.0 * da.t[i].M * da.t[i].N * B;
+    const unsigned m2_grid = (unsigned)((((B + kPanel - 1) / kPanel + 1) & ~1) * 4);
+    if ((fuse_pending || fusev_pending) && da.ntens <= kM3MaxT) {
+      const bool vfam = fusev_pending;           // the VAE family: mega3v_step (seven workgroups per panel + role-less workers)
+      std::vector<M3Args> m3_store(1);
+      M3Args& m3 = m3_store[0];
+      memset(&m3, 0, sizeof(m3));
+      m3.m = c3;
+      m3.m.lr_t_out = nullptr;
+      m3.ntens = da.ntens;
+      m3.flags = w.m3flags;
+      m3.lr_next = w.sync + 4;
+      m3.dbg = getenv("GMVAE_M3_STAMPS") ? w.gstamps + 3 * 2048 * 8 : nullptr;
+      m3.fault_pnl = getenv("GMVAE_DEBUG_LEAD_FAULT") ? atoi(getenv("GMVAE_DEBUG_LEAD_FAULT")) : -1;
+      const int nPr = (B + kPanel - 1) / kPanel;
+      const unsigned grid3 = vfam ? 256u : m2_grid;
+      {
+        // The slot list (mega3.hpp): workgroup `rank` takes slots rank, rank + workers, ...  Phase P first -- the decoder
+        // output layer's gradient over the PRODUCERS' column tiles: it waits for the producers' flags only and runs under the
+        // leads' hand-off and backward chain --, then phase F: the fp32 tiles (longer), the uint8-batch tiles, the mixture
+        // prior's blocks, the loss tail.  GMVAE at B = 1024: ranks 0..191 are the producers (done first), 192..255 the leads:
+        // P on producers 0..95, F on producers 96..191 and on the leads.  VAE family: ranks below 6 panels are producers,
+        // the next `panels` ranks the leads -- they get NO slot --, the rest of the 256 workgroups have no per-row role and
+        // wait from the launch's start.  Inside a group, slot b (XCD b % 8 under round-robin placement) prefers a tile of
+        // its operand class (speed only).
+        const int nt = da.total_tiles;
+        std::vector<int> tile_cls(nt), tile_grp(nt), tile_pt(nt);
         for (int i = 0; i < da.ntens; ++i) {
           const DwTensor& T = da.t[i];
           const int tiles_m = ((T.M + 16 * T.mu - 1) / (16 * T.mu));
           for (int tm = 0; tm < tiles_m; ++tm)
             for (int tn = 0; tn < T.tiles_n; ++tn) {
               const int t = T.tile_begin + tm * T.tiles_n + tn;
-              if (t < kDwMaxTiles) cls[t] = (tiles_m >= T.tiles_n ? tm : tn) & 7;      // share the operand with more blocks
-            }
-        }
-        for (int t = 0; t < nt; ++t) used[t] = false;
-        const bool xcd = nt > 0;
-        int next_any = 0;
-        for (int b = 0; b < da.total_tiles && b < kDwMaxTiles; ++b) {
-          int pick = -1;
-          if (xcd) {
-            for (int t = 0; t < nt; ++t)
-              if (!used[t] && cls[t] == (b & 7)) { pick = t; break; }
-            if (pick < 0) { while (next_any < nt && used[next_any]) ++next_any; pick = next_any; }
-            used[pick] = true;
-          } else {
-            pick = b;
-          }
-          int pt = 0;                             // (tensor << 10) | tile inside the tensor (dwadam.hpp)
-          for (int i = 1; i < da.ntens; ++i)
-            if (pick >= da.t[i].tile_begin) pt = i;
-          da.perm[b] = (unsigned short)((pt << 10) | (pick - da.t[pt].tile_begin));
-        }
-        if (da.total_tiles > kDwMaxTiles) { /* cannot happen at these sizes; the launch below is guarded */ }
-      }
-      FinalArgs& fa = da.fa;
-      fa.P = (long long)L.P_pad; fa.grads = a.grads; fa.p = a.adam_p; fa.m = a.adam_m; fa.v = a.adam_v;
-      fa.lr = a.lr; fa.b1 = a.beta1; fa.b2 = a.beta2; fa.eps = a.epsilon; fa.do_adam = dw_upd ? 1 : 0; fa.count = (float)B;
-      fa.logw = w.logw; fa.logpx = w.logpx; fa.logq = w.logq; fa.logp = w.logp; fa.nent = gm ? w.nent : nullptr;
-      fa.tail = tail; fa.B = B; fa.step_dev = reinterpret_cast<unsigned long long*>(a.step_dev); fa.tail_log = a.tail_log;
-      fa.epoch_word = dw_upd ? w.sync : nullptr;   // (data parallel: adam_tf_img, after the all-reduce, bumps the hand-off tag)
-      fa.err_word = w.sync + 1;
-      fa.img[0] = w.img_m; fa.img[1] = w.dimg; fa.img[2] = w.img2f; fa.img[3] = w.img2b; fa.img[4] = w.dimg2;
-      fa.span = (a.want_spans && w.spans) ? w.spans + (size_t)a.span_slot * 3 * 2048 * 2 + 2048 * 2 : nullptr;
-      if (gmp) {                                 // the prior variables: per-panel partials of mega_fwd_bwd
-        const int KLp = (int)pad4((uint64_t)K * Lz);
-        fa.gmp_part = w.gmp_part; fa.gmp_n = (B + kPanel - 1) / kPanel; fa.gmp_len = 2 * KLp + (int)pad4(K); fa.gmp_off = (long long)L.loc;
-        da.gmp_blocks = (fa.gmp_len + kDwThreads - 1) / kDwThreads;
-        for (int i = 0; i < pl.nmap && da.gmp_nmap < 3; ++i)
-          if (pl.map[i].begin >= fa.gmp_off && pl.map[i].end <= fa.gmp_off + fa.gmp_len) da.gmp_map[da.gmp_nmap++] = pl.map[i];
-      }
-      // the padding words of the flat gradient buffer are never written by the tiles: the buffer is all-reduced / read whole
-      if (da.total_tiles > kDwMaxTiles) return GMVAE_E_DIMS;
-      double fl_ = 0;
-      for (int i = 0; i < da.ntens; ++i) fl_ += 2.0 * da.t[i].M * da.t[i].N * B;
-      const unsigned m2_grid = (unsigned)((((B + kPanel - 1) / kPanel + 1) & ~1) * 4);
-      if ((fuse_pending || fusev_pending) && da.ntens <= kM3MaxT) {
-        const bool vfam = fusev_pending;           // the VAE family: mega3v_step (seven workgroups per panel + role-less workers)
-        std::vector<M3Args> m3_store(1);
-        M3Args& m3 = m3_store[0];
-        memset(&m3, 0, sizeof(m3));
-        m3.m = c3;
-        m3.m.lr_t_out = nullptr;
-        m3.ntens = da.ntens;
-        m3.flags = w.m3flags;
-        m3.lr_next = w.sync + 4;
-        m3.dbg = getenv("GMVAE_M3_STAMPS") ? w.gstamps + 3 * 2048 * 8 : nullptr;
-        m3.fault_pnl = getenv("GMVAE_DEBUG_LEAD_FAULT") ? atoi(getenv("GMVAE_DEBUG_LEAD_FAULT")) : -1;
-        const int nPr = (B + kPanel - 1) / kPanel;
-        const unsigned grid3 = vfam ? 256u : m2_grid;
-        {
-          // The slot list (mega3.hpp): workgroup `rank` takes slots rank, rank + workers, ...  Phase P first -- the decoder
-          // output layer's gradient over the PRODUCERS' column tiles: it waits for the producers' flags only and runs under the
-          // leads' hand-off and backward chain --, then phase F: the fp32 tiles (longer), the uint8-batch tiles, the mixture
-          // prior's blocks, the loss tail.  GMVAE at B = 1024: ranks 0..191 are the producers (done first), 192..255 the leads:
-          // P on producers 0..95, F on producers 96..191 and on the leads.  VAE family: ranks below 6 panels are producers,
-          // the next `panels` ranks the leads -- they get NO slot --, the rest of the 256 workgroups have no per-row role and
-          // wait from the launch's start.  Inside a group, slot b (XCD b % 8 under round-robin placement) prefers a tile of
-          // its operand class (speed only).
-          const int nt = da.total_tiles;
-          std::vector<int> tile_cls(nt), tile_grp(nt), tile_pt(nt);
-          for (int i = 0; i < da.ntens; ++i) {
-            const DwTensor& T = da.t[i];
-            const int tiles_m = ((T.M + 16 * T.mu - 1) / (16 * T.mu));
-            for (int tm = 0; tm < tiles_m; ++tm)
-              for (int tn = 0; tn < T.tiles_n; ++tn) {
-                const int t = T.tile_begin + tm * T.tiles_n + tn;
-                int q_ = 1, lt_ = 0;
-                if (T.dY == w.g) {                                                          // whose g columns: a producer's or the lead's
-                  if (vfam) q_ = tn % 7;                                                     // (mega2v.hpp: column tile 7 wave + quarter)
-                  else m2_dec_part(tn, q_, lt_);
-                }
-                const bool phP = T.dY == w.g && q_ != 0;
-                tile_cls[t] = (tiles_m >= T.tiles_n ? tm : tn) & 7;
-                tile_grp[t] = phP ? 0 : (T.a_u8 ? 2 : 1);
-                tile_pt[t] = (i << 10) | (t - T.tile_begin) | (phP ? 0 : kM3PhaseF);
+              int q_ = 1, lt_ = 0;
+              if (T.dY == w.g) {                                                          // whose g columns: a producer's or the lead's
+                if (vfam) q_ = tn % 7;                                                     // (mega2v.hpp: column tile 7 wave + quarter)
+                else m2_dec_part(tn, q_, lt_);
               }
-          }
-          const int lead_lo = vfam ? 6 * nPr : -1, lead_hi = vfam ? 7 * nPr : -1;          // ranks that take no slot
-          std::vector<char> used(nt, 0);
-          int slot = 0;
-          auto skip_leads = [&]() {
-            while (slot < kM3MaxSlots && (int)(slot % grid3) >= lead_lo && (int)(slot % grid3) < lead_hi) m3.perm[slot++] = kM3None;
-          };
-          for (int grp = 0; grp < 3; ++grp) {
-            int left = 0;
-            for (int t = 0; t < nt; ++t) left += tile_grp[t] == grp;
-            for (; left > 0; --left, ++slot) {
-              skip_leads();
-              int pick = -1, any = -1;
-              for (int t = 0; t < nt && pick < 0; ++t)
-                if (!used[t] && tile_grp[t] == grp) {
-                  if (any < 0) any = t;
-                  if (tile_cls[t] == (slot & 7)) pick = t;
-                }
-              if (pick < 0) pick = any;
-              used[pick] = 1;
-              if (slot < kM3MaxSlots) m3.perm[slot] = (unsigned short)tile_pt[pick];
+              const bool phP = T.dY == w.g && q_ != 0;
+              tile_cls[t] = (tiles_m >= T.tiles_n ? tm : tn) & 7;
+              tile_grp[t] = phP ? 0 : (T.a_u8 ? 2 : 1);
+              tile_pt[t] = (i << 10) | (t - T.tile_begin) | (phP ? 0 : kM3PhaseF);
             }
-          }
-          for (int gb = 0; gb < da.gmp_blocks; ++gb, ++slot) {
+        }
+        const int lead_lo = vfam ? 6 * nPr : -1, lead_hi = vfam ? 7 * nPr : -1;          // ranks that take no slot
+        std::vector<char> used(nt, 0);
+        int slot = 0;
+        auto skip_leads = [&]() {
+          while (slot < kM3MaxSlots && (int)(slot % grid3) >= lead_lo && (int)(slot % grid3) < lead_hi) m3.perm[slot++] = kM3None;
+        };
+        for (int grp = 0; grp < 3; ++grp) {
+          int left = 0;
+          for (int t = 0; t < nt; ++t) left += tile_grp[t] == grp;
+          for (; left > 0; --left, ++slot) {
             skip_leads();
-            if (slot < kM3MaxSlots) m3.perm[slot] = (unsigned short)(kM3Gmp + gb);
+            int pick = -1, any = -1;
+            for (int t = 0; t < nt && pick < 0; ++t)
+              if (!used[t] && tile_grp[t] == grp) {
+                if (any < 0) any = t;
+                if (tile_cls[t] == (slot & 7)) pick = t;
+              }
+            if (pick < 0) pick = any;
+            used[pick] = 1;
+            if (slot < kM3MaxSlots) m3.perm[slot] = (unsigned short)tile_pt[pick];
           }
+        }
+        for (int gb = 0; gb < da.gmp_blocks; ++gb, ++slot) {
           skip_leads();
-          if (slot < kM3MaxSlots) m3.perm[slot] = kM3Tail;
-          m3.total_slots = ++slot;
+          if (slot < kM3MaxSlots) m3.perm[slot] = (unsigned short)(kM3Gmp + gb);
         }
-        for (int i = 0; i < da.ntens; ++i) m3.t[i] = da.t[i];
-        M3Fin& f3 = m3.fa;
-        f3.grads = fa.grads; f3.p = fa.p; f3.m = fa.m; f3.v = fa.v; f3.lr = fa.lr; f3.b1 = fa.b1; f3.b2 = fa.b2; f3.eps = fa.eps;
-        f3.do_adam = fa.do_adam; f3.count = fa.count; f3.logw = fa.logw; f3.logpx = fa.logpx; f3.logq = fa.logq; f3.logp = fa.logp;
-        f3.nent = fa.nent; f3.tail = fa.tail; f3.B = fa.B; f3.tail_log = fa.tail_log; f3.epoch_word = fa.epoch_word;
-        f3.gmp_part = fa.gmp_part; f3.gmp_n = fa.gmp_n; f3.gmp_len = fa.gmp_len; f3.gmp_off = fa.gmp_off;
-        m3.gmp_nmap = da.gmp_nmap;
-        for (int i = 0; i < 3; ++i) m3.gmp_map[i] = da.gmp_map[i];
-        for (int i = 0; i < kImgBufs; ++i) f3.img[i] = fa.img[i];
-        static bool m3attr[64];
-        if (first_on_device(m3attr)) {
-          hipFuncSetAttribute(reinterpret_cast<const void*>(mega3_step), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          hipFuncSetAttribute(reinterpret_cast<const void*>(mega3v_step<0, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          hipFuncSetAttribute(reinterpret_cast<const void*>(mega3v_step<1, 64, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-        // (the meeting area of a worker's tile: 34 KB at the bottom of the dynamic LDS, whatever the per-row part's map)
-        if (m3.total_slots <= kM3MaxSlots && (!gmp || da.gmp_blocks < 0xfe)) {
-          if (!vfam) hipLaunchKernelGGL(mega3_step, dim3(grid3), dim3(kMT), (size_t)M2::total * sizeof(float), st, m3);
-          else if (vkind == 1) hipLaunchKernelGGL((mega3v_step<0, 2, 1>), dim3(grid3), dim3(kMT), (size_t)MV0::total * sizeof(float), st, m3);
-          else hipLaunchKernelGGL((mega3v_step<1, 64, 10>), dim3(grid3), dim3(kMT), (size_t)MV1::total * sizeof(float), st, m3);
-          cx.check();
-          cx.mark(vfam ? (dw_upd ? "mega3v_step" : "mega3v_grads") : (dw_upd ? "mega3_step" : "mega3_grads"), m2_flops + fl_);
-          return cx.err;
-        }
+        skip_leads();
+        if (slot < kM3MaxSlots) m3.perm[slot] = kM3Tail;
+        m3.total_slots = ++slot;
       }
-      if (fusev_pending) {                       // the two-launch form after all
-        const unsigned gridv = (unsigned)((B + kPanel - 1) / kPanel * 7);
-        if (vkind == 1) hipLaunchKernelGGL((mega2v_fwd_bwd<0, 2, 1>), dim3(gridv), dim3(kMT), (size_t)MV0::total * sizeof(float), st, c3);
-        else hipLaunchKernelGGL((mega2v_fwd_bwd<1, 64, 10>), dim3(gridv), dim3(kMT), (size_t)MV1::total * sizeof(float), st, c3);
+      for (int i = 0; i < da.ntens; ++i) m3.t[i] = da.t[i];
+      M3Fin& f3 = m3.fa;
+      f3.grads = fa.grads; f3.p = fa.p; f3.m = fa.m; f3.v = fa.v; f3.lr = fa.lr; f3.b1 = fa.b1; f3.b2 = fa.b2; f3.eps = fa.eps;
+      f3.do_adam = fa.do_adam; f3.count = fa.count; f3.logw = fa.logw; f3.logpx = fa.logpx; f3.logq = fa.logq; f3.logp = fa.logp;
+      f3.nent = fa.nent; f3.tail = fa.tail; f3.B = fa.B; f3.tail_log = fa.tail_log; f3.epoch_word = fa.epoch_word;
+      f3.gmp_part = fa.gmp_part; f3.gmp_n = fa.gmp_n; f3.gmp_len = fa.gmp_len; f3.gmp_off = fa.gmp_off;
+      m3.gmp_nmap = da.gmp_nmap;
+      for (int i = 0; i < 3; ++i) m3.gmp_map[i] = da.gmp_map[i];
+      for (int i = 0; i < kImgBufs; ++i) f3.img[i] = fa.img[i];
+      static bool m3attr[64];
+      if (first_on_device(m3attr)) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(mega3_step), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(mega3v_step<0, 2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(mega3v_step<1, 64, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      }
+      // (the meeting area of a worker's tile: 34 KB at the bottom of the dynamic LDS, whatever the per-row part's map)
+      if (m3.total_slots <= kM3MaxSlots && (!gmp || da.gmp_blocks < 0xfe)) {
+        if (!vfam) hipLaunchKernelGGL(mega3_step, dim3(grid3), dim3(kMT), (size_t)M2::total * sizeof(float), st, m3);
+        else if (vk == 1) hipLaunchKernelGGL((mega3v_step<0, 2, 1>), dim3(grid3), dim3(kMT), (size_t)MV0::total * sizeof(float), st, m3);
+        else hipLaunchKernelGGL((mega3v_step<1, 64, 10>), dim3(grid3), dim3(kMT), (size_t)MV1::total * sizeof(float), st, m3);
         cx.check();
-        cx.mark("mega2v_fwd_bwd", m2_flops);
-        fusev_pending = false;
+        cx.mark(vfam ? (dw_upd ? "mega3v_step" : "mega3v_grads") : (dw_upd ? "mega3_step" : "mega3_grads"), m2_flops + fl_);
+        return cx.err;
       }
-      if (fuse_pending) {                        // (cannot happen at mega2's sizes: the tile list fits) the two-launch form
-        hipLaunchKernelGGL(mega2_fwd_bwd, dim3(m2_grid), dim3(kMT), (size_t)M2::total * sizeof(float), st, c3);
-        cx.check();
-        cx.mark("mega2_fwd_bwd", m2_flops);
-        fuse_pending = false;
-      }
-      hipLaunchKernelGGL(dw_adam, dim3(da.total_tiles + 1 + da.gmp_blocks), dim3(kDwThreads), 0, st, da);
-      cx.check();
-      cx.mark(dw_upd ? "dw_adam" : "dw_grads", fl_);
-      return cx.err;
     }
-  }
-  if (fusev_pending) {
-    const unsigned gridv = (unsigned)((B + kPanel - 1) / kPanel * 7);
-    if (vkind == 1) hipLaunchKernelGGL((mega2v_fwd_bwd<0, 2, 1>), dim3(gridv), dim3(kMT), (size_t)MV0::total * sizeof(float), st, c3);
-    else hipLaunchKernelGGL((mega2v_fwd_bwd<1, 64, 10>), dim3(gridv), dim3(kMT), (size_t)MV1::total * sizeof(float), st, c3);
+    if (fusev_pending) {                       // the two-launch form after all
+      const unsigned gridv = (unsigned)((B + kPanel - 1) / kPanel * 7);
+      if (vk == 1) hipLaunchKernelGGL((mega2v_fwd_bwd<0, 2, 1>), dim3(gridv), dim3(kMT), (size_t)MV0::total * sizeof(float), st, c3);
+      else hipLaunchKernelGGL((mega2v_fwd_bwd<1, 64, 10>), dim3(gridv), dim3(kMT), (size_t)MV1::total * sizeof(float), st, c3);
+      cx.check();
+      cx.mark("mega2v_fwd_bwd", m2_flops);
+      fusev_pending = false;
+    }
+    if (fuse_pending) {                        // (cannot happen at mega2's sizes: the tile list fits) the two-launch form
+      hipLaunchKernelGGL(mega2_fwd_bwd, dim3(m2_grid), dim3(kMT), (size_t)M2::total * sizeof(float), st, c3);
+      cx.check();
+      cx.mark("mega2_fwd_bwd", m2_flops);
+      fuse_pending = false;
+    }
+    hipLaunchKernelGGL(dw_adam, dim3(da.total_tiles + 1 + da.gmp_blocks), dim3(kDwThreads), 0, st, da);
     cx.check();
-    cx.mark("mega2v_fwd_bwd", m2_flops);
-    fusev_pending = false;
-  }
-  if (fuse_pending) {                            // the tile list could not be built: mega2_fwd_bwd as a launch of its own
-    hipLaunchKernelGGL(mega2_fwd_bwd, dim3((unsigned)((((B + kPanel - 1) / kPanel + 1) & ~1) * 4)), dim3(kMT), (size_t)M2::total * sizeof(float), st, c3);
-    cx.check();
-    cx.mark("mega2_fwd_bwd", m2_flops);
-    fuse_pending = false;
+    cx.mark(dw_upd ? "dw_adam" : "dw_grads", fl_);
+    return cx.err;
   }
   // Every weight gradient in one grouped launch.  The uint8-activation problems (bf16 matrix cores) take NS splits
   // of two 64-row staging rounds; the fp32 problems take 2 NS splits of ONE round each: their workgroups, the
@@ -1663,14 +1677,14 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, con
     launch_group(cx, g, "bwd_dw_all", B >= 512 ? (NS2 != NS ? 3 : 1) : 0,
                  (getenv("GMVAE_STAMPS") || a.want_spans) ? w.gstamps + 2048 * 8 : nullptr);
   }
-  return finish_fused(cx, a, L, w, tail, NS2, B, &sx);
+  return finish_fused(cx, a, pn, L, w, tail, NS2, B, &sx);
 }
 
 // The fused schedule: 9 launches instead of 21 for GMVAE with one hidden layer at sizes whose
 // small-layer weights fit in LDS.  Every GEMM launch is a single staging round per workgroup
 // (split-K into slabs that the consumer reduces), so the chip is filled and no workgroup
 // waits on more than ~2 dependent memory round trips.
-static int run_step_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, const float* eps, const float* u,
+static int run_step_fused(Ctx& cx, const StepArgs& a, const StepPlan& pn, const Layout& L, WS& w, const float* eps, const float* u,
                           float* gen_eps, float* gen_u) {
   const GmvaeDims& d = *a.d;
   const int B = d.B, K = d.K, Lz = d.L, D = d.D, H = d.hidden[0];
@@ -1804,7 +1818,7 @@ static int run_step_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w, co
     g.add(p_tn(w.z, false, Lz, 1, w.dbuf[0], H, Lz, H, B, sl + Dn.w[0], sl + Dn.b[0], NS, PP, nullptr));        // dWd0
     launch_group(cx, g, "bwd_dw_all", 0);
   }
-  return finish_fused(cx, a, L, w, tail, NS, B);
+  return finish_fused(cx, a, pn, L, w, tail, NS, B);
 }
 
 static unsigned long long* g_sk_dbg = nullptr;
@@ -2060,12 +2074,6 @@ static void eval_fused_args(const StepArgs& a, const Layout& L, WS& w, EvalArgs&
     hipFuncSetAttribute(reinterpret_cast<const void*>(evalf_rows_v<7, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, EVV::lds * (int)sizeof(float));
   }
 }
-static int eval_fused_grid(const GmvaeDims& d) {
-  int grid = device_cus();
-  if (grid > d.B) grid = d.B;
-  if (grid > 1024) grid = 1024;
-  return grid;
-}
 static int run_eval_fused(Ctx& cx, const StepArgs& a, const Layout& L, WS& w) {
   const GmvaeDims& d = *a.d;
   const int B = d.B, S = d.S, D = d.D;
@@ -2128,12 +2136,8 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   const bool gm = model == GMVAE_MODEL_GMVAE;
   const float c = d.raw_sigma_bias, smin = d.sigma_min;
   hipStream_t st = cx.st;
-  const bool planes = planes_ok(d, L) && w.hd3 != nullptr;
-  // the piece form of the plane GEMMs: f16 pairs (3 piece products, <= 3 x 2^-22 per product) unless GMVAE_PLANES_EXACT=1 asks for
-  // the bf16 triples (6 piece products, every product exact)
-  const char* const exact_env = getenv("GMVAE_PLANES_EXACT");
-  const bool pairs = planes && !(exact_env && atoi(exact_env));
-  const bool fwdp = !planes && !a.backward && w.hd2f != nullptr && fwd_pairs_ok(d, L);      // forward only: the logits GEMM on pairs
+  const StepPlan pn = a.plan ? *a.plan : plan_step(d, model, L, w, step_ctx(a));
+  const bool planes = pn.planes, pairs = pn.pairs, fwdp = pn.fwdp;      // (the general schedule's flags)
   constexpr float kGScale = 32768.f;            // (sigmoid - x) in [-1, 1]: a fixed scale for its pairs
 
   // ---- noise (fast mode): Philox for eps and u -- its own launch in the general schedule, auxiliary
@@ -2145,11 +2149,13 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (ge) eps = ge;
   if (gu) u = gu;
   tl_hact = 1 + d.hidden_act;                  // (every Problem built below for this step: its epilogue's activation kind)
-  if (a.backward && mega_ok(d, model)) return run_step_mega(cx, a, L, w, eps, u, ge, gu);
-  if (a.backward && skinny_ok(d, model)) return run_step_skinny(cx, a, L, w, eps, u, ge, gu);
-  if (!a.backward && evalf_ok(d, model) && w.ev_img) return run_eval_fused(cx, a, L, w);
-  if (fused_ok(d, model) && !a.z_out && !a.y_out && !a.logits_out)
-    return run_step_fused(cx, a, L, w, eps, u, ge, gu);
+  switch (pn.kind) {
+    case STEP_MEGA: return run_step_mega(cx, a, pn, L, w, eps, u, ge, gu);
+    case STEP_SKINNY: return run_step_skinny(cx, a, L, w, eps, u, ge, gu);
+    case STEP_EVALF: return run_eval_fused(cx, a, L, w);
+    case STEP_FUSED: return run_step_fused(cx, a, pn, L, w, eps, u, ge, gu);
+    case STEP_GENERAL: break;
+  }
   if (step_inputs(d) && (a.slot < 0 || a.slot >= GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;
   // GMVAE_OPT_CLIP_NORM: step i of a train graph writes record i
   if (clip_norm(d) && a.backward && (a.slot < 0 || a.slot >= GMVAE_LABEL_SLOTS || !w.clip_part)) return GMVAE_E_DIMS;
@@ -2193,7 +2199,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   };
   // the same layers with the weight stationary (rowsws.hpp) where a wave's slice of it fits 96 registers: K = 64 (NN) / 128 (NT)
   // in a wave, K = 512 x N = 64 (NT) over the eight waves of a workgroup; one resident wave of workgroups
-  const bool rws_on = relu_act && R >= 2048 && !getenv("GMVAE_NO_RWS");
+  const bool rws_on = pn.rws;
   auto rws_grid = [&]() { const int cu = device_cus(); return cu * kSkWaves > kRwsMaxWaves ? kRwsMaxWaves / kSkWaves : cu; };
   auto rws_fits = [&](long long slices) { return slices >= 1 && slices <= (long long)rws_grid() * kSkWaves; };      // (a wave per column slice at least)
   auto rws_prob = [&](const float* W, int ldw, const float* bias, float* out, int N, bool relu) {
@@ -2998,7 +3004,7 @@ static int iw_run(IwKind kind, const GmvaeDims* dims, int model, const uint8_t* 
   const IwLay& il = c.il;
   const int B = d.B, S = d.S, K = d.K;
   const bool gm = model == GMVAE_MODEL_GMVAE;
-  const bool evalf = !kIwKinds[kind].enum_y && evalf_ok(d, model) && c.w.ev_img;
+  const bool evalf = !kIwKinds[kind].enum_y && plan_step(d, model, c.L, c.w, StepCtx()).kind == STEP_EVALF;
   const dim3 grid4((unsigned)((B + 3) / 4));
   float* const rows = c.at<float>(il.rows);
   float* const rsum = c.at<float>(il.rsum);
@@ -3599,7 +3605,7 @@ int gmvae_train_profile(const GmvaeDims* dims, int model, const uint8_t* x, floa
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !n_levels || !names || !usec || !flops)
     return GMVAE_E_NULL;
   if (iters < 1) return GMVAE_E_DIMS;
-  if (!mega_ok(*dims, model)) return GMVAE_E_DIMS;
+  if (plan_train_step(*dims, model).kind != STEP_MEGA) return GMVAE_E_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Prof* pr = new Prof();
   double acc[MAX_LEVELS] = {0}, acc_tl[MAX_LEVELS] = {0};
@@ -3890,17 +3896,13 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   if (int e = check_step_dims(dims, model)) return e;
   if (!out48) return GMVAE_E_NULL;
   const GmvaeDims& d = *dims;
-  Layout L;
-  build_layout(d, model, L);
-  const char* nm = "general";
-  if (mega_ok(d, model)) nm = mega2_ok(d, model) ? "mega2" : (mega2v_ok(d, model) ? "mega2v" : "mega");
-  else if (skinny_ok(d, model)) nm = "skinny";
-  else if (fused_ok(d, model)) nm = "fused";
-  const bool gen = !strcmp(nm, "general");
+  const StepPlan pn = plan_train_step(d, model);
+  const char* const kinds[] = {"general", pn.m2 ? "mega2" : (pn.vk ? "mega2v" : "mega"), "skinny", "fused"};
+  const char* nm = kinds[pn.kind];
   snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
            y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
-           (gen && planes_ok(d, L)) ? "+planes" : "");
+           pn.planes ? "+planes" : "");
   return 0;
 }
 
@@ -4046,21 +4048,15 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   build_layout(*dims, model, L);
   WS w;
   carve(*dims, model, L, workspace, w);
-  const bool mega = mega_ok(*dims, model) && model != GMVAE_MODEL_VAE_GMP;
-  ImgPlan pl;
-  MegaLay ml;
-  bool scatter = false;
-  if (in_graph && mega) {
-    ml = mega_lay(dims->hidden[0], dims->L, dims->K, dims->D, model);
-    plan_images(*dims, model, L, w, ml, params, pl);
-    scatter = pl.map_ok && ml.fl_ok && !getenv("GMVAE_NO_FL") && !sched_safe(*dims);
-  }
   Ctx cx;
   cx.st = st;
   StepArgs a = {dims, model, x, nullptr, nullptr, params, grads, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
                 seed, 0, step_dev, true};
-  a.dp_images = scatter;
-  a.imgs_ready = scatter && imgs_ready;
+  a.dp_graph = in_graph;
+  a.imgs_ready = imgs_ready;
+  const StepPlan pn = plan_step(*dims, model, L, w, step_ctx(a));
+  const ImgPlan& pl = pn.img;
+  a.plan = &pn;
   if (span_slot >= 0) { a.want_spans = true; a.span_slot = span_slot; }
   a.slot = slot;
   cx.prof = prof;
@@ -4079,12 +4075,12 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
                        beta2, epsilon, step_dev, w.clip_part, (int)nb, w.clip_norm, w.grad_clip + 4 * (size_t)slot, tail_log);
     return (int)hipGetLastError();
   }
-  if (!scatter) {
+  if (!pn.dp_images) {
     if (tail_log) hipMemcpyAsync(tail_log, grads + L.P_pad, GMVAE_TAIL * sizeof(float), hipMemcpyDeviceToDevice, st);
     return adam_tf_step(params, m, v, grads, L.P_pad, lr, beta1, beta2, epsilon, 0, step_dev, 1.f, grads + L.P_pad + 4,
                         grads + L.P_pad, st);
   }
-  if (mega2_ok(*dims, model) && w.img2f && !getenv("GMVAE_NO_ADAM_TILES")) {
+  if (pn.adam_tiles) {
     // at mega2's sizes every parameter is a tile of one of the step's weight tensors: the optimizer in tile shape (mega3.hpp)
     std::vector<DwArgs> da_store(1);
     DwArgs& da = da_store[0];
@@ -4144,7 +4140,7 @@ int gmvae_dp_profile(const GmvaeDims* dims, int model, const uint8_t* x, float* 
   if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !comm || !out) return GMVAE_E_NULL;
   if (iters < 1) return GMVAE_E_DIMS;
-  if (!mega_ok(*dims, model)) return GMVAE_E_DIMS;
+  if (plan_train_step(*dims, model).kind != STEP_MEGA) return GMVAE_E_DIMS;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
   build_layout(*dims, model, L);
