@@ -130,6 +130,11 @@ Y_TEMP_DEV = 128      # ... the Gumbel-softmax temperature read per step from de
 Y_STRAIGHT_THROUGH = 256   # ... one-hot y forward, the relaxed sample's Jacobian backward (include/gmvae_hip.h GMVAE_Y_STRAIGHT_THROUGH)
 OBJ_PIXEL_MASK = 512  # ... objective: a per-example observation mask read from the workspace (include/gmvae_hip.h GMVAE_OBJ_PIXEL_MASK)
 OPT_CLIP_NORM = 1024  # ... optimizer: the gradient clipped by its global norm in front of TF-Adam (include/gmvae_hip.h GMVAE_OPT_CLIP_NORM)
+# ... the decoder's likelihood on grey-level bytes, a two-bit field (include/gmvae_hip.h GMVAE_LIK_*); 0: the Bernoulli on {0, 1}
+LIK_GREY_BERNOULLI, LIK_CONT_BERNOULLI, LIK_GAUSSIAN, LIK_MASK = 1 << 11, 2 << 11, 3 << 11, 3 << 11
+# Engine(likelihood=...)
+LIKELIHOODS = {"bernoulli": 0, "grey_bernoulli": LIK_GREY_BERNOULLI, "continuous_bernoulli": LIK_CONT_BERNOULLI,
+               "gaussian": LIK_GAUSSIAN}
 # Engine(y_estimator=...): the relaxed Gumbel-softmax sample, or its straight-through form (Jang et al. 2017)
 Y_ESTIMATORS = ("relaxed", "straight_through")
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph

@@ -100,8 +100,71 @@ class IndependentBernoulli:
         return torch.rand(p.shape, device=p.device, generator=_gen(seed, p.device)) < p
 
     def log_prob(self, x):
+        """x in {0, 1}, or soft targets in [0, 1] (the grey Bernoulli's cross-entropy: no normalised density there)."""
         x = x.to(self.logits.dtype)
         return (x * self.logits - F.softplus(self.logits)).sum(-1)
+
+
+Bernoulli = IndependentBernoulli
+
+
+def _cb_terms(logits):
+    """(A, A') of the continuous Bernoulli, A = log((e^l - 1) / l): series in h = l / 2 below |l| = 1 (both closed forms cancel
+    around 0; 0 itself is 0 / 0), forms in exp(-|l|) above -- finite at l = 0 and at |l| = 100 and beyond, no inf - inf."""
+    l = logits
+    h = 0.5 * l
+    h2 = h * h
+    a_s = h + h2 * (1.0 / 6.0 + h2 * (-1.0 / 180.0 + h2 * (1.0 / 2835.0 + h2 * (-1.0 / 37800.0))))
+    m_s = 0.5 + 0.5 * h * (1.0 / 3.0 + h2 * (-1.0 / 45.0 + h2 * (2.0 / 945.0 + h2 * (-1.0 / 4725.0))))
+    a = l.abs().clamp(min=1.0)                     # (the closed forms' argument where the series is taken: finite)
+    om = -torch.expm1(-a)
+    a_c = l.clamp(min=0.0) + torch.log(om / a)
+    p = 1.0 / om - 1.0 / a
+    m_c = torch.where(l > 0, p, 1.0 - p)
+    small = l.abs() < 1.0
+    return torch.where(small, a_s, a_c), torch.where(small, m_s, m_c)
+
+
+class ContinuousBernoulli:
+    """Independent continuous Bernoulli on [0, 1]^D (Loaiza-Ganem & Cunningham 2019): p(t | l) = exp(t l - A(l))."""
+
+    def __init__(self, logits, name="ContinuousBernoulli"):
+        self.logits, self.name = logits, name
+
+    def mean(self, name=None):
+        return _cb_terms(self.logits)[1]
+
+    def sample(self, seed=None):
+        """Inverse CDF: t = log1p(u (e^l - 1)) / l, written in exp(-|l|); t = u around l = 0."""
+        l = self.logits
+        u = torch.rand(l.shape, device=l.device, dtype=l.dtype, generator=_gen(seed, l.device))
+        a = l.abs().clamp(min=1e-3)
+        v = torch.where(l > 0, u, 1.0 - u)                            # (l < 0: the mirrored draw, t -> 1 - t)
+        t = 1.0 + torch.log(v + (1.0 - v) * torch.exp(-a)) / a        # log(1 + v (e^a - 1)) / a
+        t = torch.where(l > 0, t, 1.0 - t)
+        return torch.where(l.abs() < 1e-3, u, t).clamp(0.0, 1.0)
+
+    def log_prob(self, x):
+        x = x.to(self.logits.dtype)
+        return (x * self.logits - _cb_terms(self.logits)[0]).sum(-1)
+
+
+class NormalFixedScale:
+    """Independent Normal(loc, sigma) with one fixed scale: the Gaussian likelihood's decoder distribution."""
+
+    def __init__(self, loc, sigma, name="NormalFixedScale"):
+        self.loc, self.sigma, self.name = loc, float(sigma), name
+
+    def mean(self, name=None):
+        return self.loc
+
+    def sample(self, seed=None):
+        return self.loc + self.sigma * torch.randn(self.loc.shape, device=self.loc.device, dtype=self.loc.dtype,
+                                                   generator=_gen(seed, self.loc.device))
+
+    def log_prob(self, x):
+        e = (x.to(self.loc.dtype) - self.loc) / self.sigma
+        return (-0.5 * e * e - math.log(self.sigma) - 0.5 * math.log(2 * math.pi)).sum(-1)
 
 
 class _Categorical:
@@ -229,7 +292,15 @@ class ConditionalBernoulli(_Conditional):
         return self._mlp(tensor_list)
 
     def __call__(self, *args, **kwargs):
-        return IndependentBernoulli(self.condition(args, **kwargs), name=self._name)
+        # the distribution of the model's likelihood (Engine(likelihood=)): its mean() is A'(lambda), so reconstruct_images and
+        # generate_sample_images return the mean image under every likelihood
+        lam = self.condition(args, **kwargs)
+        lik = "bernoulli" if self._engine is None else self._engine.likelihood
+        if lik == "continuous_bernoulli":
+            return ContinuousBernoulli(lam, name=self._name)
+        if lik == "gaussian":
+            return NormalFixedScale(lam, self._engine.likelihood_sigma, name=self._name)
+        return IndependentBernoulli(lam, name=self._name)
 
 
 class ConditionalCategorical(_Conditional):

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "aux.hpp"
+#include "lik.hpp"
 
 namespace gmvae {
 
@@ -32,7 +33,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MAXP = 8;         // problems per launch
 
-enum { EPI_STORE = 0, EPI_BERNOULLI = 1 };
+enum { EPI_STORE = 0, EPI_BERNOULLI = 1, EPI_LIK = 2 };
 
 // One GEMM operand as seen by the kernel: a logical [mn][k] matrix.
 //   k_contig: element(mn,k) = ptr[(mn/row_div)*ld + k]      (row-major [mn][k])
@@ -96,6 +97,9 @@ struct Problem {
   float* part;             // Bernoulli row partial sums [M][nparts]
   const unsigned char* xmask;   // GMVAE_OBJ_PIXEL_MASK: observed iff non-zero, x's layout (ldx, x_div); fp32 C, no planes.  The masked
   float* part2;                 // epilogue: part sums the observed columns, part2 [M][nparts] the held-out ones, C = m (sigmoid - x)
+  int lik;                      // EPI_LIK (lik.hpp, GMVAE_LIK_*): the likelihood's kind, 1 grey Bernoulli / 2 continuous Bernoulli / 3 Gaussian,
+  const float* lik_sigma;       // on the grey-level bytes x; fp32 C = (A' - t) / phi, no planes; part sums the log-probability terms, part2
+                                // the squared errors (A' - t)^2; lik_sigma: the Gaussian's device cell (read once per workgroup)
   Segment seg[2];
 };
 
@@ -1827,6 +1831,116 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
           }
         }
       }
+    }
+  } else if (epi == EPI_LIK) {  // lambda -> ((A'(lambda) - t) / phi, sum_d (t lambda - A(lambda)) / phi + c(t), sum_d (A' - t)^2), t = x / 255
+    // The likelihood form of the decoder's epilogue (lik.hpp) beside the Bernoulli one below, which keeps its code: the same tile
+    // paths -- interior, the last column tile of an N that is no multiple of the tile, element by element at the edges --, fp32 C
+    // only, two chains per row, the row sums finished in fp64.
+    const unsigned char* xp = L.p[pi].x;
+    float* part = L.p[pi].part;
+    float* const part2 = L.p[pi].part2;
+    const int ldx = L.p[pi].ldx, x_div = L.p[pi].x_div, nparts = L.p[pi].nparts, kind = L.p[pi].lik;
+    const LikConst lk = lik_const(kind, L.p[pi].lik_sigma);
+    if (m0 + C::BM <= M && (n0 + C::BN <= N || (N & 3) == 0) && (ldc & 3) == 0 && (!Cout || al16(Cout)) && al16(bias) && (!bias2 || al16(bias2)) &&
+        (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(xp) & 3) == 0) {
+      constexpr int RPP = C::THREADS / GPR;
+      const int c4 = tid % GPR, r0 = tid / GPR, nb = n0 + 4 * c4;
+      const bool nv = nb < N;                      // (this thread's column quad exists)
+      float4 b4 = nv ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bias2 && nv) { const float4 c4v = *reinterpret_cast<const float4*>(bias2 + nb); b4.x += c4v.x; b4.y += c4v.y; b4.z += c4v.z; b4.w += c4v.w; }
+      const float bc[4] = {b4.x + addconst, b4.y + addconst, b4.z + addconst, b4.w + addconst};
+      unsigned xw[PASSES];
+      f32x4 vv[PASSES];
+#pragma unroll
+      for (int q = 0; q < PASSES; ++q) {
+        const int m = m0 + r0 + RPP * q;
+        xw[q] = nv ? *reinterpret_cast<const unsigned*>(xp + (long long)(m / x_div) * ldx + nb) : 0u;
+      }
+#pragma unroll
+      for (int q = 0; q < PASSES; ++q) {
+        const int row = r0 + RPP * q;
+        vv[q] = *reinterpret_cast<const f32x4*>(lds + row * C::LDC + 4 * c4);
+#pragma unroll
+        for (int w = 1; w < C::WK; ++w) vv[q] += *reinterpret_cast<const f32x4*>(lds + (w * C::BM + row) * C::LDC + 4 * c4);
+      }
+      // (the passes once per likelihood and output, with no branch inside -- as the Bernoulli passes below: the transcendental
+      //  chains of a thread's elements interleave only inside one basic block)
+      auto passes = [&](auto kind_c, auto cout_c) {
+        constexpr int KIND = decltype(kind_c)::value;
+        constexpr bool CO = decltype(cout_c)::value;
+#pragma unroll
+        for (int q = 0; q < PASSES; ++q) {
+          const int row = r0 + RPP * q;
+          float v[4], lps = 0.f, sqs = 0.f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float lp, df;
+            lik_term<KIND>(vv[q][j] + bc[j], lik_t((xw[q] >> (8 * j)) & 0xffu), lk, lp, df);
+            lps += lp; sqs = fmaf(df, df, sqs);
+            v[j] = df * lk.is2;
+          }
+          if constexpr (CO) { if (nv) *reinterpret_cast<float4*>(Cout + (long long)(m0 + row) * ldc + nb) = make_float4(v[0], v[1], v[2], v[3]); }
+          // (this thread's own, already consumed, slot of the staged tile: the two row sums in the first two floats of its quad)
+          *reinterpret_cast<float2*>(lds + row * C::LDC + 4 * c4) = nv ? make_float2(lps, sqs) : make_float2(0.f, 0.f);
+        }
+      };
+      {
+        typedef std::integral_constant<int, LIK_GREY> K1; typedef std::integral_constant<int, LIK_CB> K2; typedef std::integral_constant<int, LIK_GAUSS> K3;
+        if (Cout) { if (kind == LIK_CB) passes(K2{}, std::true_type{}); else if (kind == LIK_GAUSS) passes(K3{}, std::true_type{}); else passes(K1{}, std::true_type{}); }
+        else { if (kind == LIK_CB) passes(K2{}, std::false_type{}); else if (kind == LIK_GAUSS) passes(K3{}, std::false_type{}); else passes(K1{}, std::false_type{}); }
+      }
+      __syncthreads();
+      if (tid < C::BM) {
+        double t = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < GPR; ++c) { t += (double)lds[tid * C::LDC + 4 * c]; t2 += (double)lds[tid * C::LDC + 4 * c + 1]; }
+        part[(long long)(m0 + tid) * nparts + tn] = (float)t;
+        part2[(long long)(m0 + tid) * nparts + tn] = (float)t2;
+      }
+    } else
+#pragma unroll 1
+    for (int ps = 0; ps < PASSES; ++ps) {
+      const int gidx = tid + ps * C::THREADS;
+      const int row = gidx / GPR, c4 = gidx % GPR;
+      float4 v4 = *reinterpret_cast<const float4*>(lds + row * C::LDC + 4 * c4);
+#pragma unroll
+      for (int w = 1; w < C::WK; ++w) {
+        const float4 o = *reinterpret_cast<const float4*>(lds + (w * C::BM + row) * C::LDC + 4 * c4);
+        v4.x += o.x; v4.y += o.y; v4.z += o.z; v4.w += o.w;
+      }
+      const int m = m0 + row, nb = n0 + 4 * c4;
+      float rsum = 0.f, rsum2 = 0.f;
+      if (m < M && nb < N) {
+        float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        const unsigned char* xr = xp + (long long)(m / x_div) * ldx;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = min(nb + j, N - 1);
+          const float lam = v[j] + bias[n] + (bias2 ? bias2[n] : 0.f) + addconst;
+          const float tv = lik_t(xr[n]);
+          float lp, df;
+          if (kind == LIK_CB) lik_term<LIK_CB>(lam, tv, lk, lp, df);
+          else if (kind == LIK_GAUSS) lik_term<LIK_GAUSS>(lam, tv, lk, lp, df);
+          else lik_term<LIK_GREY>(lam, tv, lk, lp, df);
+          rsum += (nb + j < N) ? lp : 0.f;
+          rsum2 += (nb + j < N) ? df * df : 0.f;
+          v[j] = df * lk.is2;
+        }
+        if (Cout) {
+          float* dst = Cout + (long long)m * ldc + nb;
+          if (nb + 3 < N && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+          } else {
+            dst[0] = v[0];
+            if (nb + 1 < N) dst[1] = v[1];
+            if (nb + 2 < N) dst[2] = v[2];
+            if (nb + 3 < N) dst[3] = v[3];
+          }
+        }
+      }
+#pragma unroll
+      for (int o = GPR / 2; o > 0; o >>= 1) { rsum += __shfl_xor(rsum, o, 64); rsum2 += __shfl_xor(rsum2, o, 64); }
+      if (m < M && c4 == 0) { part[(long long)m * nparts + tn] = rsum; part2[(long long)m * nparts + tn] = rsum2; }
     }
   } else {  // EPI_BERNOULLI: lambda -> (sigmoid(lambda) - x, sum_d x*lambda - softplus(lambda))
     const unsigned char* xp = L.p[pi].x;

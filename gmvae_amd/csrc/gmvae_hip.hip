@@ -39,6 +39,7 @@
 #include "wobj.hpp"
 #include "ytemp.hpp"
 #include "pmask.hpp"
+#include "lik.hpp"
 #include "gclip.hpp"
 
 using namespace gmvae;
@@ -81,6 +82,10 @@ static bool y_head_bits(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_Y_T
 // GMVAE_OBJ_PIXEL_MASK: a per-example observation mask (pmask.hpp: x~ = m x for every network that reads x, the masked Bernoulli
 // epilogue of gemm.hpp, pmask_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes
 static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_PIXEL_MASK) != 0; }
+// GMVAE_LIK_*: the decoder's likelihood on grey-level bytes (lik.hpp: t = x / 255 as fp32 for every network that reads x, the
+// likelihood epilogue of gemm.hpp, lik_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes.
+// 0: the Bernoulli on {0, 1}; else LIK_GREY / LIK_CB / LIK_GAUSS
+static int lik_kind(const GmvaeDims& d) { return (int)((d.sched_flags & GMVAE_LIK_MASK) >> 11); }
 // GMVAE_OPT_CLIP_NORM: the gradient clipped by its global norm in front of TF-Adam (gclip.hpp: finalize_grads_ss in
 // finalize_grads' place, gclip_finish_adam behind it) -- a training step with the bit takes the general schedule; forward-only
 // passes do not depend on it (run_step clears it for them)
@@ -216,8 +221,16 @@ static int check_pmask_dims(const GmvaeDims* d) {
   return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
                             GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH)) ? GMVAE_E_DIMS : 0;
 }
+// ... and GMVAE_LIK_* together with any other objective or estimator bit (GMVAE_OPT_CLIP_NORM combines): the three models'
+// standard objectives (the GMVAE's Gumbel draw) at any S only; the combinations are follow-ups  (gmvae_forward's check too)
+static int check_lik_dims(const GmvaeDims* d) {
+  if (!lik_kind(*d)) return 0;
+  return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
+                            GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH | GMVAE_OBJ_PIXEL_MASK)) ? GMVAE_E_DIMS : 0;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
+  if (int e = check_lik_dims(d)) return e;
   if (int e = check_pmask_dims(d)) return e;
   if (int e = check_label_dims(d, model)) return e;
   if (int e = check_weight_dims(d)) return e;
@@ -268,6 +281,9 @@ struct WS {
   // partials [R][nparts] beside part, and the per-example (missing, observed) counts [B][2]
   unsigned char *pixel_mask, *xm;
   float *hpart, *mcnt;
+  // GMVAE_LIK_*: the Gaussian's sigma (one float, the caller's, read only), t = x / 255 as fp32 [B D], the squared-error partials
+  // [R][nparts] beside part
+  float *lik_sigma, *lik_t, *lik_part;
   // GMVAE_OPT_CLIP_NORM: the caller's threshold (one float, read only), the records [GMVAE_LABEL_SLOTS][4] the library writes
   // and the fp64 partials of the sum of squares, one per 1024 elements of the gradient buffer
   float *clip_norm, *grad_clip;
@@ -563,6 +579,11 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.xm = reinterpret_cast<unsigned char*>(take((B * D + 3) / 4));
     w.hpart = take(R * ((D + 31) / 32));
     w.mcnt = take(2 * B);
+  }
+  if (lik_kind(d)) {                              // (behind everything, as above; in front of the clip regions: a field of its own)
+    if (lik_kind(d) == LIK_GAUSS) w.lik_sigma = take(4);
+    w.lik_t = take(B * D);
+    w.lik_part = take(R * ((D + 31) / 32));
   }
   if (clip_norm(d)) {                             // (behind everything, as above: dims without the bit keep their size and every offset)
     w.clip_norm = take(4);
@@ -1087,7 +1108,8 @@ constexpr unsigned kGeneralOnlyFwd =
     GMVAE_OBJ_WEIGHTS |               // wobj.hpp's kernels in row_terms' / ymarg_rows' / y_head_bwd's place, wobj_tail behind loss_tail
     GMVAE_Y_TEMP_DEV |                // ytemp.hpp's kernels in y_head_fwd's / y_head_bwd's / y_head_bwd_w's place
     GMVAE_Y_STRAIGHT_THROUGH |        // (the same)
-    GMVAE_OBJ_PIXEL_MASK;             // pmask.hpp: x~ = m x, the masked Bernoulli epilogue of gemm.hpp, pmask_tail behind loss_tail
+    GMVAE_OBJ_PIXEL_MASK |            // pmask.hpp: x~ = m x, the masked Bernoulli epilogue of gemm.hpp, pmask_tail behind loss_tail
+    GMVAE_LIK_MASK;                   // lik.hpp: t = x / 255 as fp32, the likelihood epilogue of gemm.hpp, lik_tail behind loss_tail
 constexpr unsigned kGeneralOnlyTrain = kGeneralOnlyFwd |
     GMVAE_GRAD_DREG |                 // kernels.hpp z_head_bwd_dreg: the backward of the general schedule alone
     GMVAE_OPT_CLIP_NORM;              // no update may start before the whole gradient's norm is known
@@ -1152,13 +1174,14 @@ static StepPlan plan_step(const GmvaeDims& d, int model, const Layout& L, const 
     // Forward only (evaluation: S importance samples per row), the one logits GEMM runs on f16 pairs from 8192 rows, at any
     // D % 8 == 0 (weight planes zero-padded to the tile) and any hidden width % 32: the BACKWARD GEMMs are what need D % 128 == 0
     // and a wide layer, they read (sigmoid - x) planes.  (eval_iwae: 51200 x 784 x 64 -- as fp32 MFMA the launch is half matrix
-    // time, half Bernoulli epilogue.)  No planes under GMVAE_OBJ_PIXEL_MASK (the masked Bernoulli epilogue writes fp32 C alone) or
+    // time, half Bernoulli epilogue.)  No planes under GMVAE_OBJ_PIXEL_MASK (the masked Bernoulli epilogue writes fp32 C alone), under GMVAE_LIK_*
+    // (the likelihood epilogue likewise; the Gaussian's gradient is not bounded by 1, the planes' fixed scale assumes it) or
     // another activation (the plane producers' epilogues are the ReLU ones).
     const long long R = (long long)B * rows_per_x(d);
     const int Ht = L.dec.dim[L.dec.nl - 1];
     const char* mr = getenv("GMVAE_PLANES_MINROWS");          // (tests: the plane paths at sizes the oracle covers)
     const bool exact = env_on("GMVAE_PLANES_EXACT");
-    const bool any = !env_on("GMVAE_NO_PLANES") && !pixel_mask(d) && d.hidden_act == GMVAE_ACT_RELU && L.dec.nl >= 2 && R % 128 == 0;
+    const bool any = !env_on("GMVAE_NO_PLANES") && !pixel_mask(d) && !lik_kind(d) && d.hidden_act == GMVAE_ACT_RELU && L.dec.nl >= 2 && R % 128 == 0;
     const bool planes_ok = any && (mr || (Ht >= 256 && d.D >= 512)) && R >= (mr ? atoll(mr) : 4096) && d.D % 128 == 0 &&
                            Ht % 128 == 0 && R * d.D < (1ll << 32);
     const bool fwd_pairs_ok = any && !exact && R >= (mr ? atoll(mr) : 8192) && Ht % 32 == 0 && d.D % 8 == 0 &&
@@ -2168,6 +2191,16 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   if (pmask && (marg || !w.pixel_mask || !w.xm || !w.hpart || !w.mcnt)) return GMVAE_E_DIMS;
   const unsigned char* const pm = pmask ? w.pixel_mask + (size_t)a.slot * (((size_t)B * D + 255) / 256 * 256) : nullptr;
   const uint8_t* const xin = pmask ? w.xm : a.x;
+  // GMVAE_LIK_*: t = x / 255 as fp32 is what the first layers and their weight gradients read (a float operand), a.x itself only
+  // the likelihood epilogue's target
+  const int lik = lik_kind(d);
+  if (lik && (marg || pmask || !w.lik_t || !w.lik_part || (lik == LIK_GAUSS && !w.lik_sigma))) return GMVAE_E_DIMS;
+  const void* const xop = lik ? (const void*)w.lik_t : (const void*)xin;      // (the first layers' operand: bytes, or t)
+  const bool xu8 = !lik;
+  if (lik) {
+    hipLaunchKernelGGL(lik_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, w.lik_t, B, D);
+    rowk(cx, "lik_rows");
+  }
   if (pmask) {
     hipLaunchKernelGGL(pmask_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, pm, w.xm, w.mcnt, B, D);
     rowk(cx, "pmask_rows");
@@ -2236,7 +2269,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   // ================================ forward ================================
   const NetL& E = gm ? L.ency : L.enc;
   const int flx_h0 = E.dim[1], flx_h1 = gm ? L.encg.dim[1] : 0;
-  if (relu_act && D % 16 == 0 && flx_h0 % 64 == 0 && flx_h1 % 64 == 0 && E.nl > 1) {
+  if (!lik && relu_act && D % 16 == 0 && flx_h0 % 64 == 0 && flx_h1 % 64 == 0 && E.nl > 1) {
     // first layers over the uint8 batch as exact bf16 piece products (skinny.hpp first_layers_u8bf); the Philox fill in a
     // launch of its own
     FlxArgs f;
@@ -2262,9 +2295,9 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   {  // first layers over the uint8 batch: enc_y layer 0 and the x-part of enc_gmm layer 0
     Group g;
     float* out = (E.nl == 1) ? (gm ? w.logits : w.qp) : w.he[1];
-    g.add(p_nn(xin, true, D, P + E.w[0], E.dim[1], B, E.dim[1], D, out, E.dim[1], P + E.b[0], E.nl > 1));
+    g.add(p_nn(xop, xu8, D, P + E.w[0], E.dim[1], B, E.dim[1], D, out, E.dim[1], P + E.b[0], E.nl > 1));
     if (gm)
-      g.add(p_nn(xin, true, D, P + L.encg.w[0], L.encg.dim[1], B, L.encg.dim[1], D, w.gx, L.encg.dim[1], nullptr,
+      g.add(p_nn(xop, xu8, D, P + L.encg.w[0], L.encg.dim[1], B, L.encg.dim[1], D, w.gx, L.encg.dim[1], nullptr,
                  false));
     if (noise_aux) {
       Aux& ax = g.L.aux;
@@ -2419,6 +2452,9 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       p.bias2 = d.gen_bias_vec;
       p.x = a.x; p.ldx = D; p.x_div = S; p.part = w.part;
       p.xmask = pm; p.part2 = pmask ? w.hpart : nullptr;      // (the masked form: observed columns to part, held-out ones to part2)
+      if (lik) {      // (the likelihood form: the log-probability terms to part, the squared errors to part2, (A' - t) / phi to C)
+        p.epi = EPI_LIK; p.lik = lik; p.lik_sigma = w.lik_sigma; p.part2 = w.lik_part;
+      }
       if (fwdp) {
         // forward only: both operands as f16 pairs, the weight's planes zero-padded to whole 128-column tiles
         const int Dp = (D + 127) / 128 * 128;
@@ -2538,6 +2574,10 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
     if (pmask && !a.iw_chunk) {  // tail[5..7]: the held-out pixels' -log-likelihood (mean over s), the missing and the observed counts
       hipLaunchKernelGGL(pmask_tail, dim3(1), dim3(1024), 0, st, w.hpart, nparts, w.mcnt, tail, B, S);
       rowk(cx, "pmask_tail");
+    }
+    if (lik && !a.iw_chunk) {    // tail[5..7]: the squared reconstruction error (mean over s), B D, 0
+      hipLaunchKernelGGL(lik_tail, dim3(1), dim3(1024), 0, st, w.lik_part, nparts, tail, B, S, D);
+      rowk(cx, "lik_tail");
     }
   }
   if (a.z_out) hipMemcpyAsync(a.z_out, w.z, (size_t)R * Lz * 4, hipMemcpyDeviceToDevice, st);
@@ -2690,7 +2730,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       const float* Wy = P + G.w[0] + (uint64_t)D * G.dim[1];
       const int nsx = (S > 1 && sxb.n + 2 <= kSlabRanges) ? NSB : NS;
       if (nsx != NS) { brange(G.w[0], (uint64_t)D * G.dim[1], nsx); brange(G.b[0], G.dim[1], nsx); }
-      g.add(p_tn(xin, true, D, 1, dg, G.dim[1], D, G.dim[1], B, sl + G.w[0], sl + G.b[0], nsx, PP, nullptr));
+      g.add(p_tn(xop, xu8, D, 1, dg, G.dim[1], D, G.dim[1], B, sl + G.w[0], sl + G.b[0], nsx, PP, nullptr));
       if (marg) {
         // y = e_k: the y rows of the first layer's weight and the prior's weight take segmented column sums over the batch
         // (ymarg_dw, slabs as the split-K GEMMs write them); no data gradient of y
@@ -2773,10 +2813,10 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   }
   for (int i = E.nl - 1; i >= 0; --i) {   // enc_y (GMVAE) / encoder (VAE): rows = B
     Group g;
-    const void* act = (i == 0) ? (const void*)xin : (const void*)w.he[i];
+    const void* act = (i == 0) ? xop : (const void*)w.he[i];
     const int nse = (S > 1 && sxb.n + 2 <= kSlabRanges) ? NSB : NS;
     if (nse != NS) { brange(E.w[i], (uint64_t)E.dim[i] * E.dim[i + 1], nse); brange(E.b[i], E.dim[i + 1], nse); }
-    g.add(p_tn(act, i == 0, E.dim[i], 1, dcur, E.dim[i + 1], E.dim[i], E.dim[i + 1], B, sl + E.w[i], sl + E.b[i], nse,
+    g.add(p_tn(act, i == 0 && xu8, E.dim[i], 1, dcur, E.dim[i + 1], E.dim[i], E.dim[i + 1], B, sl + E.w[i], sl + E.b[i], nse,
                PP, nullptr));
     float* out = nullptr;
     if (i > 0) {
@@ -2848,6 +2888,10 @@ static int iw_dims(IwKind kind, const GmvaeDims* dims, int model, GmvaeDims& d) 
   // bits are masked off.
   if (int e = check_pmask_dims(dims)) return e;
   if (pixel_mask(d) && kind != IW_BOUND) return GMVAE_E_DIMS;
+  // GMVAE_LIK_* likewise: gmvae_iw_bound honours it (the bound on log p(t) under the likelihood), the other kinds refuse it --
+  // masking it off would silently score Bernoulli
+  if (int e = check_lik_dims(dims)) return e;
+  if (lik_kind(d) && kind != IW_BOUND) return GMVAE_E_DIMS;
   d.sched_flags &= ~kIwMasked;
   if (k.enum_y) d.sched_flags &= ~(GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW);
   if (int e = check_dims(&d, model)) return e;
@@ -3172,6 +3216,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (int e = check_label_dims(dims, model)) return e;
   if (int e = check_weight_dims(dims)) return e;
   if (int e = check_ytemp_dims(dims, model)) return e;
+  if (int e = check_lik_dims(dims)) return e;
   if (int e = check_pmask_dims(dims)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
@@ -3791,6 +3836,7 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
                               float* tail_log, void** graph_out) {
   if (int e = check_step_dims(dims, model)) return e;
   if (step_inputs(*dims) && (pixels || n_steps > GMVAE_LABEL_SLOTS)) return GMVAE_E_DIMS;      // (step i reads slot i)
+  if (lik_kind(*dims) && pixels) return GMVAE_E_DIMS;      // (GMVAE_LIK_*: the pipeline graph binarises inside)
   if (clip_norm(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;      // (step i writes record i; the pipeline graph takes the bit)
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
@@ -3899,9 +3945,10 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   const StepPlan pn = plan_train_step(d, model);
   const char* const kinds[] = {"general", pn.m2 ? "mega2" : (pn.vk ? "mega2v" : "mega"), "skinny", "fused"};
   const char* nm = kinds[pn.kind];
-  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
-           y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
+           y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "",
+           lik_kind(d) == LIK_GREY ? "+grey" : lik_kind(d) == LIK_CB ? "+cb" : lik_kind(d) == LIK_GAUSS ? "+gauss" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
            pn.planes ? "+planes" : "");
   return 0;
 }
@@ -3940,7 +3987,7 @@ int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, u
       {"vs", w.vs}, {"labels", reinterpret_cast<float*>(w.labels)}, {"sup_weight", w.sup_weight},
       {"obj_weights", w.obj_weights}, {"rwk", w.rwk}, {"y_floor", w.y_floor},
       {"y_temperature", w.y_temperature}, {"y_soft", w.y_soft}, {"pixel_mask", reinterpret_cast<float*>(w.pixel_mask)},
-      {"clip_norm", w.clip_norm}, {"grad_clip", w.grad_clip}};
+      {"clip_norm", w.clip_norm}, {"grad_clip", w.grad_clip}, {"lik_sigma", w.lik_sigma}};
   for (auto& t : tab)
     if (!strcmp(t.n, name)) {
       if (!t.p) return GMVAE_E_NET;

@@ -44,9 +44,13 @@ class DeviceDataset:
     [B, D] batch and its labels.  shuffle=True draws a new permutation per epoch on the device; every batch gets
     new uniforms (step counter), as the reference's `repeat()` after `map()` does.  y_observed (optional): int32 [N],
     resident too -- the component a semi-supervised step may see for each row, -1 = unlabelled.  pixel_mask (optional): uint8
-    [N, D], resident too -- the row's observation mask (non-zero: observed) of a step with a pixel mask."""
+    [N, D], resident too -- the row's observation mask (non-zero: observed) of a step with a pixel mask.
+    binarize=False: `next_batch` returns the gathered GREY rows as they are (a torch gather, off the hot path), for a model
+    with a likelihood on grey levels.  The two paths do not feed the same picture: the binarising one sets a pixel with
+    probability 1 - intensity, the grey one feeds the intensity itself, t = pixel / 255."""
 
-    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None, pixel_mask=None):
+    def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None, pixel_mask=None,
+                 binarize: bool = True):
         dev = L.require_gpu()
         pixels = torch.as_tensor(pixels)
         self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.uint8).contiguous()
@@ -62,6 +66,7 @@ class DeviceDataset:
         if self.y_observed is not None and self.y_observed.shape != (self.N,):
             raise ValueError(f"y_observed must have one entry per row ({self.N}), got {tuple(self.y_observed.shape)}")
         self.shuffle, self.seed = shuffle, int(seed)
+        self.binarize = bool(binarize)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(self.seed)
         self._perm = None
@@ -90,6 +95,12 @@ class DeviceDataset:
 
     def next_batch(self, B: int, out: Optional[torch.Tensor] = None):
         rows = self.next_rows(B)
-        x = binarize(self.pixels, rows=rows, seed=self.seed, step=self._step, out=out)
+        if not self.binarize:
+            x = self.pixels[rows.long()]
+            if out is not None:
+                out.copy_(x)
+                x = out
+        else:
+            x = binarize(self.pixels, rows=rows, seed=self.seed, step=self._step, out=out)
         self._step += 1
         return x, (None if self.labels is None else self.labels[rows.long()])

@@ -104,6 +104,38 @@ def check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weight
         raise ValueError(f"pixel_mask=True is not available with y_estimator={y_estimator!r}")
 
 
+def check_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                     y_estimator, pixel_mask, likelihood, likelihood_sigma=1.0):
+    """The argument check of Engine(likelihood=, likelihood_sigma=) and set_likelihood_sigma (no device needed): the library's
+    refusals of GMVAE_LIK_*.  Returns sigma as a float."""
+    if likelihood not in L.LIKELIHOODS:
+        raise ValueError(f"likelihood must be one of {tuple(L.LIKELIHOODS)}, got {likelihood!r}")
+    try:
+        sigma = float(likelihood_sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"likelihood_sigma must be a finite number > 0, got {likelihood_sigma!r}") from None
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"likelihood_sigma must be a finite number > 0, got {likelihood_sigma!r}")
+    if likelihood == "bernoulli":
+        return sigma
+    what = f"likelihood={likelihood!r}"
+    if L.MODEL_IDS.get(model) == L.MODEL_GMVAE and y_inference != "gumbel":
+        raise ValueError(f"{what} is not available with y_inference={y_inference!r}: use 'gumbel'")
+    if grad_estimator == "dreg":
+        raise ValueError(f"{what} is not available with grad_estimator='dreg'")
+    if semi_supervised:
+        raise ValueError(f"{what} is not available with semi_supervised=True")
+    if weighted_objective:
+        raise ValueError(f"{what} is not available with weighted_objective=True")
+    if temperature_on_device:
+        raise ValueError(f"{what} is not available with temperature_on_device=True")
+    if y_estimator != "relaxed":
+        raise ValueError(f"{what} is not available with y_estimator={y_estimator!r}")
+    if pixel_mask:
+        raise ValueError(f"{what} is not available with pixel_mask=True")
+    return sigma
+
+
 def check_clip_norm(clip_norm):
     """The argument check of Engine(clip_norm=) and set_clip_norm (no device needed): None (off) or a threshold > 0; inf reports
     the norm and never clips.  Returns the value as a float, or None."""
@@ -176,7 +208,8 @@ class Engine:
                  y_inference: str = "gumbel", grad_estimator: str = "standard", semi_supervised: bool = False,
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
                  y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed",
-                 pixel_mask: bool = False, clip_norm: Optional[float] = None):
+                 pixel_mask: bool = False, clip_norm: Optional[float] = None, likelihood: str = "bernoulli",
+                 likelihood_sigma: float = 1.0):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -215,8 +248,17 @@ class Engine:
         of apply_gradients; behind the all-reduce under data parallelism) and skips the update when the gradient or the loss is
         not finite; float("inf") only reports.  grad_clip [4] = (norm before clipping, divisor, clipped 0 / 1, guard: the loss
         sum or NaN where the step was skipped) of the last eager step; a captured graph hands out replay.grad_clip [n_steps, 4].
-        set_clip_norm changes C between steps and between replays without a host sync or a recapture.  General schedule."""
+        set_clip_norm changes C between steps and between replays without a host sync or a recapture.  General schedule.
+        likelihood (all three models, the GMVAE with y_inference "gumbel"; include/gmvae_hip.h GMVAE_LIK_*): "bernoulli" -- x in
+        {0, 1}, the default, nothing changes -- or, on GREY LEVELS t = x / 255, "grey_bernoulli" (Bernoulli cross-entropy on soft
+        targets: no normalised density), "continuous_bernoulli" (Loaiza-Ganem & Cunningham 2019) or "gaussian" (mean = the
+        decoder's output, fixed scale likelihood_sigma; set_likelihood_sigma changes it between steps and replays, a device-side
+        write).  x is then taken as uint8 grey levels as given; a float tensor must lie in [0, 1] and is rounded to the nearest
+        k / 255.  Every network that reads x reads t; tail[5] / tail[6] is the per-pixel squared reconstruction error.  General
+        schedule; combines with clip_norm alone.  Parameters and checkpoints have the same layout under every likelihood."""
         clip_norm = check_clip_norm(clip_norm)
+        likelihood_sigma = check_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective,
+                                            temperature_on_device, y_estimator, pixel_mask, likelihood, likelihood_sigma)
         check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
                          y_estimator, pixel_mask)
         check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator)
@@ -270,6 +312,8 @@ class Engine:
         self.y_estimator = y_estimator
         self.pixel_mask = bool(pixel_mask)
         self.clip_norm = clip_norm
+        self.likelihood = likelihood
+        self.likelihood_sigma = likelihood_sigma
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -309,6 +353,11 @@ class Engine:
             self._clip_dev = torch.full((1,), self.clip_norm, dtype=torch.float32, device=self.device)
             self.grad_clip = torch.zeros(4, dtype=torch.float32, device=self.device)
             self._clip_scratch = torch.zeros(L.grad_clip_scratch_bytes(self.P) // 8, dtype=torch.float64, device=self.device)
+        # the Gaussian likelihood's sigma on the device: every workspace's "lik_sigma" cell is a copy of it
+        self._sigma_dev = None
+        self._sigma_cells: Dict[tuple, torch.Tensor] = {}
+        if self.likelihood == "gaussian":
+            self._sigma_dev = torch.full((1,), self.likelihood_sigma, dtype=torch.float32, device=self.device)
         self.init_parameters(random_seed)
 
     @property
@@ -324,6 +373,7 @@ class Engine:
         wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
         yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
         pmask = (L.OBJ_PIXEL_MASK if self.pixel_mask else 0) | (L.OPT_CLIP_NORM if self.clip_norm is not None else 0)
+        pmask |= L.LIKELIHOODS[self.likelihood]
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
                            sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | pmask | extra_flags, **self.hp)
@@ -443,6 +493,7 @@ class Engine:
             self.drop_graphs(clear_handoff_errors=False)      # captured graphs hold pointers into the old allocation
             del self._ws[key]
             self._clip_cells.pop(key, None)
+            self._sigma_cells.pop(key, None)
         if key not in self._ws:
             self._ws[key] = torch.zeros(n, dtype=torch.float32, device=self.device)
             # the library only reads the per-step inputs' regions (and the classification weight), and zeros would mean
@@ -457,7 +508,26 @@ class Engine:
                 off = L.workspace_offset(d, self.model, "clip_norm") // 4
                 self._clip_cells[key] = self._ws[key][off:off + 1]
                 self._clip_cells[key].copy_(self._clip_dev, non_blocking=True)
+            self._bind_sigma(key, d, self._ws[key])
         return d, self._ws[key]
+
+    # ------------------------------------------------------- the Gaussian likelihood's sigma (likelihood_sigma)
+    def _bind_sigma(self, key, d, ws):
+        """The workspace's "lik_sigma" cell <- the engine's sigma (a zeroed cell means sigma = 0: a non-finite step)."""
+        if (d.sched_flags & L.LIK_MASK) == L.LIK_GAUSSIAN:
+            off = L.workspace_offset(d, self.model, "lik_sigma") // 4
+            self._sigma_cells[key] = ws[off:off + 1]
+            self._sigma_cells[key].copy_(self._sigma_dev, non_blocking=True)
+
+    def set_likelihood_sigma(self, sigma: float):
+        """The Gaussian likelihood's scale the next steps read, eager or replayed: device-side writes, no host sync, no recapture."""
+        if self.likelihood != "gaussian":
+            raise ValueError("set_likelihood_sigma needs an engine created with likelihood='gaussian'")
+        self.likelihood_sigma = check_likelihood(self.model_name, "gumbel", "standard", False, False, False, "relaxed", False,
+                                                 "gaussian", sigma)
+        self._sigma_dev.fill_(self.likelihood_sigma)
+        for cell in self._sigma_cells.values():
+            cell.copy_(self._sigma_dev, non_blocking=True)
 
     # ------------------------------------------------------- gradient clipping (clip_norm)
     def _push_clip_norm(self):
@@ -551,7 +621,13 @@ class Engine:
         return x.contiguous()
 
     def _prep_x(self, x: torch.Tensor) -> torch.Tensor:
-        x = self._as_u8(x.to(self.device))
+        x = x.to(self.device)
+        if self.likelihood != "bernoulli" and x.dtype.is_floating_point:
+            # grey levels: a float image in [0, 1] -> the nearest k / 255 (uint8 tensors are taken as grey levels as given)
+            if x.numel() and not bool(((x >= 0) & (x <= 1)).all()):
+                raise ValueError(f"likelihood={self.likelihood!r} takes uint8 grey levels or floats in [0, 1]")
+            x = torch.round(x.to(torch.float32) * 255.0).to(torch.uint8)
+        x = self._as_u8(x)
         x = x.reshape(x.shape[0], -1)           # utils.flatten_tensor (scripts/utils.py:140-141)
         if x.shape[1] != self.D:
             raise ValueError(f"expected [B,{self.D}] inputs, got {tuple(x.shape)}")
@@ -639,6 +715,8 @@ class Engine:
         enum_y, per_component = self._CHUNKED[kind]
         if self.pixel_mask and kind != "iw_bound":
             raise ValueError(f"{kind} is not available with pixel_mask=True (it would score the unobserved pixels): use iw_bound")
+        if self.likelihood != "bernoulli" and kind != "iw_bound":
+            raise ValueError(f"{kind} is not available with likelihood={self.likelihood!r} (it would score Bernoulli): use iw_bound")
         x = self._prep_x(x)
         if x.data_ptr() % 16:
             x = x.clone()
@@ -654,6 +732,7 @@ class Engine:
         ws = self._chunked_ws.get((kind, B, chunk))
         if ws is None or ws.numel() < nw:
             ws = self._chunked_ws[(kind, B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+            self._bind_sigma((kind, B, chunk), d, ws)      # (the forward's workspace opens the evaluator's: the same offsets)
         self._bind_step_inputs(d, ws, mask=mask)      # (the forward's workspace opens the evaluator's: the same offsets)
         f32 = dict(dtype=torch.float32, device=self.device)
         shapes = ((B, self.K), (B, self.K), (B, 4)) if per_component else ((B,), (B,))
@@ -722,6 +801,8 @@ class Engine:
 
     def mlp(self, net: int, inp: torch.Tensor, in2: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One conditional network's MLP on the device (snt.nets.MLP, scripts/base.py:47-60)."""
+        if self.likelihood != "bernoulli" and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
+            inp = self._prep_x(inp).to(torch.float32) / 255.0       # (the networks that read x read t = x / 255 as fp32)
         is_u8 = inp.dtype in (torch.uint8, torch.bool)
         inp = self._as_u8(inp.to(self.device)) if is_u8 else inp.to(self.device, torch.float32).contiguous()
         inp = inp.reshape(inp.shape[0], -1)
@@ -987,6 +1068,9 @@ class Engine:
                 raise ValueError("capture_train_pipeline gathers its batches by index inside the graph and has no label gather, "
                                  f"nor one for weight rows, temperatures or masks: an engine with {inp.option}=True trains "
                                  f"through capture_train_step (replay.{inp.replay})")
+        if self.likelihood != "bernoulli":
+            raise ValueError(f"capture_train_pipeline binarises its batches inside the graph: an engine with "
+                             f"likelihood={self.likelihood!r} trains through capture_train_step on grey batches")
         n_steps = int(n_steps)
         clip = self.clip_norm is not None
         if clip and n_steps > L.LABEL_SLOTS:

@@ -129,7 +129,7 @@ class TrainableGMVAE(GMVAE):
         like TF evaluates it only when the summary is fetched.  A semi-supervised step with labelled examples adds
         sup_ce (their mean -ln q(y|x)) and sup_acc (the share whose argmax q(y|x) is the observed component); a weighted
         objective adds kl_weight, y_weight and y_floor_share (the share of examples whose y term sits on its free-bits floor);
-        clip_norm adds grad_norm and clipped (0 / 1) of the last optimizer step."""
+        clip_norm adds grad_norm and clipped (0 / 1) of the last optimizer step; a likelihood on grey levels adds recon_mse."""
         e = self._need_engine()
         t = e.grads[e.P:].detach()
         out = {"nll_scalar": t[1] / t[4], "kl_div_z": t[2] / t[4], "nent": t[3] / t[4], "elbo": -t[0] / t[4]}
@@ -141,6 +141,8 @@ class TrainableGMVAE(GMVAE):
             if t[6].item() > 0:
                 out["imputation_nll"] = t[5] / t[6]
             out["observed_share"] = t[7] / (t[6] + t[7])
+        if e.likelihood != "bernoulli":            # (the per-pixel squared error of the mean image A'(lambda) against t = x / 255)
+            out["recon_mse"] = t[5] / t[6]
         if e.clip_norm is not None:                # (of the last eager optimizer step: the norm before clipping, clipped 0 / 1)
             out["grad_norm"], out["clipped"] = e.grad_clip[0], e.grad_clip[2]
         if self._last_labels is not None:
@@ -169,9 +171,10 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                  hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
                  semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0,
-                 temperature_on_device=False, y_estimator="relaxed", pixel_mask=False, clip_norm=None):
+                 temperature_on_device=False, y_estimator="relaxed", pixel_mask=False, clip_norm=None, likelihood="bernoulli",
+                 likelihood_sigma=1.0):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
-    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask, clip_norm: Engine).  y_inference="marginal" trains and
+    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask, clip_norm, likelihood, likelihood_sigma: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
     importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
     a checkpoint of any loads in the others."""
@@ -183,7 +186,7 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                     y_inference=y_inference, grad_estimator=grad_estimator, semi_supervised=semi_supervised,
                     sup_weight=sup_weight, weighted_objective=weighted_objective, kl_weight=kl_weight, y_weight=y_weight,
                     y_free_nats=y_free_nats, temperature_on_device=temperature_on_device, y_estimator=y_estimator,
-                    pixel_mask=pixel_mask, clip_norm=clip_norm)
+                    pixel_mask=pixel_mask, clip_norm=clip_norm, likelihood=likelihood, likelihood_sigma=likelihood_sigma)
     prior_gmm = base.ConditionalNormal(size=latent_size, hidden_layer_sizes=None,
                                        hidden_activation_fn=hidden_activation_fn, sigma_min=sigma_min,
                                        raw_sigma_bias=raw_sigma_bias, name="prior_gmm").bind(engine, L.NET_PRIOR_GMM)

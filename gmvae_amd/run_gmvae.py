@@ -81,6 +81,11 @@ def build_parser():
     a("--clip_norm", type=float, default=0.0, help="train: clip the batch-mean gradient by its global norm to this threshold "
       "in front of Adam and skip the steps whose gradient or loss is not finite; the log reports the norm's mean and maximum "
       "and the clipped and skipped shares per summary window (inf: report only; 0 = off)")
+    a("--likelihood", default="bernoulli", choices=["bernoulli", "grey_bernoulli", "continuous_bernoulli", "gaussian"],
+      help="the decoder's likelihood: bernoulli on binarised pixels (the reference), or on the GREY levels t = pixel / 255 the "
+      "Bernoulli cross-entropy on soft targets (grey_bernoulli), the continuous Bernoulli or a Gaussian with the fixed scale "
+      "--likelihood_sigma; train and eval then report recon_mse, the per-pixel squared error of the mean image")
+    a("--likelihood_sigma", type=float, default=1.0, help="--likelihood=gaussian: the fixed scale sigma")
     return p
 
 
@@ -153,6 +158,25 @@ def check_args(p, cfg):
         if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
             p.error("--missing_rate is not available with --iw_enum_samples, --posterior_samples or "
                     "--component_posterior_samples (they would score the unobserved pixels): use --iw_samples")
+    if not (cfg.likelihood_sigma > 0 and cfg.likelihood_sigma < float("inf")):
+        p.error("--likelihood_sigma must be a finite number > 0")
+    if cfg.likelihood != "bernoulli":
+        what = f"--likelihood={cfg.likelihood}"
+        if cfg.model == "gmvae" and cfg.y_inference != "gumbel":
+            p.error(f"{what} is not available with --y_inference=marginal or marginal_iw")
+        if cfg.grad_estimator == "dreg":
+            p.error(f"{what} is not available with --grad_estimator=dreg")
+        if cfg.labelled_per_class > 0:
+            p.error(f"{what} is not available with --labelled_per_class")
+        if runners.weighted_flags(cfg):
+            p.error(f"{what} is not available with --kl_weight / --y_weight / --y_free_nats / --kl_warmup_steps")
+        if runners.temperature_flags(cfg) or cfg.y_estimator != "relaxed":
+            p.error(f"{what} is not available with --temperature* or --y_estimator=straight_through")
+        if cfg.missing_rate > 0:
+            p.error(f"{what} is not available with --missing_rate")
+        if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
+            p.error(f"{what} is not available with --iw_enum_samples, --posterior_samples or --component_posterior_samples "
+                    "(they would score Bernoulli): use --iw_samples")
     return cfg
 
 

@@ -51,23 +51,29 @@ def create_dataset(config, split="train", shuffle=True, repeat=True, device="cud
     rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
     gen = torch.Generator(device=device)
     gen.manual_seed((config.random_seed or 0) * 7919 + 17 + rank)
+    grey = None                                                    # --likelihood on grey levels: the uint8 rows as they are
     if data is None:
         n = int(getattr(config, "synthetic_size", 8192))
         D = int(getattr(config, "data_dim", 784))
         inten = torch.full((n, D), 0.13, device=device)            # 1 - 0.87: P(1) = 0.87 after inversion
         labels = torch.randint(0, 10, (n,), generator=torch.Generator().manual_seed(3)).to(device)
+        if grey_levels(config):
+            grey = torch.from_numpy(synthetic_grey(n, D)).to(device)
     else:
         inten = torch.from_numpy(np.ascontiguousarray(data[0])).to(device).float() / 255.0
         labels = torch.from_numpy(data[1]).to(device)
+        if grey_levels(config):
+            grey = torch.from_numpy(np.ascontiguousarray(data[0])).to(device).reshape(inten.shape[0], -1)
     a, b = parallel.shard_rows(inten.shape[0], rank, world)
     inten, labels = inten[a:b], labels[a:b]
+    grey = None if grey is None else grey[a:b]
     n = inten.shape[0]
     B = int(config.batch_size)
 
     def it() -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         while True:
             order = torch.randperm(n, device=device, generator=gen) if shuffle else torch.arange(n, device=device)
-            binar = (inten < torch.rand(inten.shape, device=device, generator=gen)).to(torch.uint8)
+            binar = grey if grey is not None else (inten < torch.rand(inten.shape, device=device, generator=gen)).to(torch.uint8)
             for s in range(0, n, B):
                 idx = order[s:s + B]
                 yield (binar[idx], labels[idx], a + s) if with_index else (binar[idx], labels[idx])
@@ -128,6 +134,26 @@ def missing_mask(config, split: str, n_rows: int, data_dim: int):
     return (rng.random((int(n_rows), int(data_dim)), dtype=np.float32) >= p).astype(np.uint8)
 
 
+def likelihood_of(config):
+    """--likelihood / --likelihood_sigma: (Engine's likelihood, its sigma)."""
+    return getattr(config, "likelihood", "bernoulli") or "bernoulli", float(getattr(config, "likelihood_sigma", 1.0) or 1.0)
+
+
+def grey_levels(config) -> bool:
+    """The model reads grey levels t = pixel / 255 (--likelihood other than bernoulli): no binarisation anywhere."""
+    return likelihood_of(config)[0] != "bernoulli"
+
+
+def synthetic_grey(n: int, D: int) -> np.ndarray:
+    """The synthetic stand-in of a grey-level run: uint8 [n, D], a smooth ramp per row plus noise, about a third of the pixels
+    exactly 0 (train and eval see the same rows)."""
+    rng = np.random.default_rng(4)
+    ramp = np.linspace(0.0, 1.0, D)[None, :] * rng.uniform(0.3, 1.0, (n, 1))
+    pix = np.clip(ramp + rng.normal(0.0, 0.05, (n, D)), 0.0, 1.0)
+    pix[rng.random((n, D)) < 0.3] = 0.0
+    return np.round(pix * 255.0).astype(np.uint8)
+
+
 def clip_norm_of(config):
     """--clip_norm C: Engine's clip_norm -- None for 0 (off), else the threshold (inf: report only)."""
     c = float(getattr(config, "clip_norm", 0.0) or 0.0)
@@ -145,6 +171,7 @@ def create_model(config, data_dim, weighted=None, temperature_on_device=None, cl
     yhead = dict(temperature_on_device=temperature_flags(config) if temperature_on_device is None else bool(temperature_on_device),
                  y_estimator=getattr(config, "y_estimator", "relaxed"))
     pmask = dict(pixel_mask=float(getattr(config, "missing_rate", 0.0) or 0.0) > 0.0)      # (--missing_rate: train AND eval)
+    pmask.update(likelihood=likelihood_of(config)[0], likelihood_sigma=likelihood_of(config)[1])      # (--likelihood: likewise)
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
@@ -197,10 +224,27 @@ def _ckpt(config):
 
 
 def _save_checkpoint(model, path: str):
-    """Atomic: a reader (run_eval's wait_for_checkpoint, a restart) never sees a half-written file."""
+    """Atomic: a reader (run_eval's wait_for_checkpoint, a restart) never sees a half-written file.  The metadata records the
+    likelihood the parameters were trained under (the tensors have the same names and shapes under every one)."""
     tmp = path + ".tmp"
-    torch.save(model.state_dict(), tmp)
+    sd = model.state_dict()
+    sd["likelihood"] = model._engine.likelihood
+    sd["likelihood_sigma"] = torch.tensor(model._engine.likelihood_sigma, dtype=torch.float64)
+    torch.save(sd, tmp)
     os.replace(tmp, path)
+
+
+def _restore_checkpoint(model, path: str):
+    """load_state_dict from the file -- an error if it was written under another likelihood (or another sigma of the
+    Gaussian): the parameters would load, and mean something else.  A file without the metadata is a Bernoulli one."""
+    sd = torch.load(path, map_location="cpu")
+    eng = model._engine
+    lik, sigma = sd.pop("likelihood", "bernoulli"), float(sd.pop("likelihood_sigma", eng.likelihood_sigma))
+    if lik != eng.likelihood or (lik == "gaussian" and sigma != eng.likelihood_sigma):
+        raise ValueError(f"{path} was trained with --likelihood={lik}" + (f" --likelihood_sigma={sigma:g}" if lik == "gaussian" else "")
+                         + f": it cannot be restored under --likelihood={eng.likelihood}"
+                         + (f" --likelihood_sigma={eng.likelihood_sigma:g}" if eng.likelihood == "gaussian" else ""))
+    model.load_state_dict(sd)
 
 
 def wait_for_checkpoint(path: str, poll_seconds: float = 60.0, max_wait: float | None = None) -> str:
@@ -243,7 +287,7 @@ def create_device_dataset(config, split="train", shuffle=True):
     if data is None:
         n = int(getattr(config, "synthetic_size", 8192))
         D = int(getattr(config, "data_dim", 784))
-        pix = np.full((n, D), 33, dtype=np.uint8)
+        pix = synthetic_grey(n, D) if grey_levels(config) else np.full((n, D), 33, dtype=np.uint8)
         lab = np.random.default_rng(3).integers(0, 10, n)
     else:
         pix, lab = np.ascontiguousarray(data[0]), data[1]
@@ -252,7 +296,7 @@ def create_device_dataset(config, split="train", shuffle=True):
     yobs = select_labelled(lab, lpc, config.random_seed or 0)[a:b] if lpc > 0 else None
     pm = missing_mask(config, split, pix.shape[0], pix.shape[1] if pix.ndim == 2 else int(np.prod(pix.shape[1:])))
     return DeviceDataset(pix[a:b], lab[a:b], shuffle=shuffle, seed=(config.random_seed or 0) * 7919 + 17 + rank, y_observed=yobs,
-                         pixel_mask=None if pm is None else pm[a:b])
+                         pixel_mask=None if pm is None else pm[a:b], binarize=not grey_levels(config))
 
 
 def _graph_steps(every: int, cap: int = 32) -> int:
@@ -318,7 +362,7 @@ def run_train(config):
     eng = model._engine
     os.makedirs(_logdir(config), exist_ok=True)
     if os.path.exists(_ckpt(config)):                      # MonitoredTrainingSession auto-restore
-        model.load_state_dict(torch.load(_ckpt(config), map_location="cpu"))
+        _restore_checkpoint(model, _ckpt(config))
         if rank == 0:
             print(f"restored {_ckpt(config)} at step {eng.global_step}")
     eng.sync_replicas()            # default --random_seed=None: every process drew its own init; rank 0's wins
@@ -342,6 +386,9 @@ def run_train(config):
     # --temperature_anneal_every) are pure functions of the global step
     inputs = eng.step_inputs
     tags = [inp.tag for inp in STEP_INPUTS if inp.option in inputs]
+    grey = eng.likelihood != "bernoulli"                    # grey batches are gathered, never binarised: capture_train_step's branch
+    if grey:
+        tags = tags + ["grey"]
     run_train.last_path = ("eager" if eager else "dp-graph" if world > 1 else f"graph+{tags[0]}" if tags else "pipeline-graph")
     run_train.temperature_log = []                          # temperature on the device: (0-based step index, temperature) of the
                                                             # LAST launch's steps, as placed in replay.y_temperature
@@ -365,7 +412,8 @@ def run_train(config):
             g = G if n >= G else 1
             if eager:
                 rows = ds.next_rows(B)
-                x = binarize(ds.pixels, rows=rows, seed=bseed, step=eng.global_step, out_row0=rank * B)
+                x = (ds.pixels[rows.long()] if grey else
+                     binarize(ds.pixels, rows=rows, seed=bseed, step=eng.global_step, out_row0=rank * B))
                 yo = ds.y_observed[rows.long()] if "semi_supervised" in inputs else None
                 if "weighted_objective" in inputs:
                     eng.set_objective_weights(*objective_weights_at(config, eng.global_step))
@@ -377,7 +425,7 @@ def run_train(config):
                 if clip:
                     clips.append(eng.grad_clip.clone().view(1, 4))
                 last_x, last_rows, g = x, rows, 1
-            elif world == 1 and not inputs:
+            elif world == 1 and not inputs and not grey:
                 replay = eng.capture_train_pipeline(ds, B, lr=lr, n_steps=g)
                 run_train.launches += 1
                 snap = None
@@ -396,7 +444,10 @@ def run_train(config):
                 xs = sx if g > 1 else sx.unsqueeze(0)
                 for i in range(g):                          # this launch's batches, binarised on the device
                     last_rows = ds.next_rows(B)
-                    binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
+                    if grey:
+                        xs[i].copy_(ds.pixels[last_rows.long()])
+                    else:
+                        binarize(ds.pixels, rows=last_rows, seed=bseed, step=eng.global_step + i, out=xs[i], out_row0=rank * B)
                     if replay.y_observed is not None:
                         replay.y_observed[i].copy_(ds.y_observed[last_rows.long()])
                     if replay.pixel_mask is not None:
@@ -498,6 +549,8 @@ def run_train(config):
                 if tails[-1, 6].item() > 0:
                     msg += f"  imputation_nll {(tails[-1, 5] / tails[-1, 6]).item():.4f}"
                 msg += f"  observed_share {(tails[-1, 7] / (tails[-1, 6] + tails[-1, 7])).item():.4f}"
+            if grey:                                        # (of the last step taken)
+                msg += f"  recon_mse {(tails[-1, 5] / tails[-1, 6]).item():.6f}"
             if "semi_supervised" in inputs:                 # over the summary block's labelled examples (all ranks')
                 blk = tails[torch.isfinite(tails[:, 0])][:, 5:8].double().sum(0)
                 if blk[1].item() > 0:
@@ -531,7 +584,7 @@ def run_eval(config):
                          temperature_on_device=False)
     wait_for_checkpoint(_ckpt(config), float(getattr(config, "checkpoint_poll_seconds", 60.0)),
                         getattr(config, "checkpoint_max_wait", None))
-    model.load_state_dict(torch.load(_ckpt(config), map_location="cpu"))
+    _restore_checkpoint(model, _ckpt(config))
     eng = model._engine
     if config.model == "gmvae" and temperature_flags(config):
         eng.set_temperature(temperature_at(config, eng.global_step))      # the schedule's value where training stopped
@@ -615,6 +668,9 @@ def run_eval(config):
         if pm_tot[1].item() > 0:
             res[f"{config.split}/imputation_nll"] = pm_tot[0].item() / pm_tot[1].item()
         res[f"{config.split}/observed_share"] = pm_tot[2].item() / (pm_tot[1].item() + pm_tot[2].item())
+    if eng.likelihood != "bernoulli":
+        # the per-pixel squared error of the mean image A'(lambda) against t = pixel / 255 (tail[5] / tail[6] over the split)
+        res[f"{config.split}/recon_mse"] = pm_tot[0].item() / max(pm_tot[1].item(), 1.0)
     if iw_n > 0:
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:

@@ -24,7 +24,7 @@
  *     which waits no longer block; re-zero the workspace to clear it);
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*), is
  *     asynchronous and graph-capturable; no global state;
- *   - all float tensors are fp32 row-major; x is uint8/bool {0,1} [B,D];
+ *   - all float tensors are fp32 row-major; x is uint8/bool {0,1} [B,D] (uint8 grey levels 0..255 under GMVAE_LIK_*);
  *   - sample-dependent tensors have R = B*S rows, row r = b*S + s.
  */
 #ifndef GMVAE_HIP_H_
@@ -334,7 +334,53 @@ enum { GMVAE_SCHED_SAFE = 1,
         *   <schedule> [+marginal | +marginal_iw] [+labels] [+weights] [+temp] [+st] [+mask] [+dreg] [+clip] [+planes]
         * ("general+clip", "general+marginal_iw+labels+dreg+clip").  The eager call, the 1-step graph, the n-step graph and the
         * one-rank data-parallel forms of a step give the same record and the same update, bit for bit. */
-       GMVAE_OPT_CLIP_NORM = 1024 };
+       GMVAE_OPT_CLIP_NORM = 1024,
+       /* the decoder's likelihood, a two-bit FIELD (all three models; the GMVAE with the Gumbel draw only; any S >= 1, any
+        * hidden_act, with or without gen_bias_vec, any D >= 1).  0 is the Bernoulli on x in {0, 1}, untouched.  With the field x
+        * stays uint8 [B, D] but carries the GREY LEVEL 0..255: t_bd = x_bd / 255; row r = b S + s belongs to example b; lambda_rd
+        * is the decoder's output, MLP(z) + gen_bias_init + gen_bias_vec[d].  A one-parameter exponential family,
+        *   log p(t | lambda) = (t lambda - A(lambda)) / phi + c(t):
+        *   GMVAE_LIK_GREY_BERNOULLI   A = softplus               A' = sigmoid                 phi = 1        c = 0
+        *                              Bernoulli cross-entropy on soft targets: NOT a normalised density on [0, 1]
+        *   GMVAE_LIK_CONT_BERNOULLI   A = log((e^l - 1) / l)      A' = 1/(1 - e^-l) - 1/l      phi = 1        c = 0
+        *                              (A(0) = 0, A'(0) = 1/2; Loaiza-Ganem & Cunningham 2019: a density on [0, 1])
+        *   GMVAE_LIK_GAUSSIAN         A = l^2 / 2                 A' = l                       phi = sigma^2
+        *                              c = -t^2 / (2 sigma^2) - ln sigma - ln(2 pi) / 2         (mean lambda, fixed scale sigma)
+        *   networks that read x (encoder_y, encoder_gmm, encoder, and their first layers' weight gradients) read t as fp32
+        *   logpx_r = sum_d [(t_bd lambda_rd - A(lambda_rd)) / phi + c(t_bd)]
+        *   g_rd    = (A'(lambda_rd) - t_bd) / phi                    (the gradient at the logits; A'(lambda) is the mean image)
+        * and everything downstream -- log q, log p, nent, the IWAE weights, every backward GEMM, TF-Adam -- is the step's own.
+        * The continuous Bernoulli's A and A' come from series in lambda / 2 below |lambda| = 1 (both closed forms cancel around
+        * 0, where Xavier-initialised logits sit) and from forms in exp(-|lambda|) above, finite at |lambda| = 100 and beyond.
+        * Tail: [0..4] keep their meanings ([1] = sum_b mean_s (-logpx), constants included: it may be negative);
+        * [5] sum_b mean_s sum_d (A'(lambda_rd) - t_bd)^2, the squared reconstruction error; [6] B D; [7] 0: [5] / [6] is the
+        * per-pixel MSE; the data-parallel all-reduce sums all eight slots.  gmvae_forward's row_terms carry the new logpx, and
+        * log w is built from it.
+        * The workspace grows BEHIND every other buffer but GMVAE_OPT_CLIP_NORM's by regions rounded up to 256 bytes each:
+        *   "lik_sigma"   under GMVAE_LIK_GAUSSIAN alone: one float, sigma, at the start of its cell
+        *   (unnamed)     float [B D]: t;  float [R][nparts]: the squared-error partials beside the epilogue's own
+        * (gmvae_workspace_offset answers for the name under the Gaussian; GMVAE_E_NET otherwise; "clip_norm" and "grad_clip" keep
+        * resolving when both features are on).  The CALLER writes "lik_sigma"; the library only reads it, from device memory, once
+        * per workgroup of the logits launch (which forms 1 / sigma^2 and ln sigma itself): a captured graph follows the cell.  A
+        * zeroed workspace means sigma = 0, a non-finite step: a caller fills it before the first step (gmvae_amd.Engine does).
+        * Who honours the field: gmvae_step, gmvae_forward, gmvae_train_graph_create, gmvae_dp_step, gmvae_dp_graph_create, the
+        * bench and profile loops; gmvae_iw_bound -- the bound on log p(t) under the likelihood, through the general chunk passes
+        * at every size, noise keying unchanged, tail[5..7] = 0 --; gmvae_train_graph_create_pipeline refuses it (GMVAE_E_DIMS:
+        * that graph binarises inside); gmvae_iw_bound_enum_y, gmvae_posterior_y and gmvae_posterior_component return GMVAE_E_DIMS
+        * (masking the field off would silently score Bernoulli).
+        * REFUSED (GMVAE_E_DIMS from gmvae_workspace_bytes and every entry point that runs or sizes a step, before any launch)
+        * together with GMVAE_OBJ_MARGINAL_Y, GMVAE_OBJ_MARGINAL_Y_IW, GMVAE_GRAD_DREG, GMVAE_OBJ_LABELS, GMVAE_OBJ_WEIGHTS,
+        * GMVAE_Y_TEMP_DEV, GMVAE_Y_STRAIGHT_THROUGH or GMVAE_OBJ_PIXEL_MASK; GMVAE_OPT_CLIP_NORM combines.
+        * Every step with the field takes the general schedule -- no one-launch, skinny, chain, evalf or plane path (under the
+        * Gaussian the gradient at the logits is not bounded by 1, the planes' fixed scale assumes it is: at the config-5 sizes the
+        * top decoder layer runs the fp32 MFMA loop, as the masked step does) -- and gmvae_step_schedule appends "+grey", "+cb" or
+        * "+gauss" behind where "+mask" stands: "general+cb", "general+gauss+clip".  The likelihood epilogue (gemm.hpp EPI_LIK:
+        * fp32 C, interior and edge tiles) keeps the log-probability terms and the squared errors as two chains per row, finished
+        * in fp64; nothing assumes D % 4 == 0.  No atomics: eager and captured steps give the same bits. */
+       GMVAE_LIK_GREY_BERNOULLI = 1 << 11,
+       GMVAE_LIK_CONT_BERNOULLI = 2 << 11,
+       GMVAE_LIK_GAUSSIAN = 3 << 11,
+       GMVAE_LIK_MASK = 3 << 11 };
 #define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) / masks (GMVAE_OBJ_PIXEL_MASK) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
@@ -660,7 +706,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "clip_norm" and "grad_clip" under GMVAE_OPT_CLIP_NORM; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "clip_norm" and "grad_clip" under GMVAE_OPT_CLIP_NORM; "lik_sigma" under GMVAE_LIK_GAUSSIAN; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -675,7 +721,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+grey" / "+cb" / "+gauss" under GMVAE_LIK_*, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
