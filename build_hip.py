@@ -26,8 +26,11 @@ def build(force: bool = False, verbose: bool = True) -> str:
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    # -amdgpu-kernarg-preload-count: leading scalar kernel parameters arrive in SGPRs at wave start (mega2.hpp M2_HEAD_PARAMS: the
+    # first layer's addresses need no round trip into the cold argument block); translation-unit wide, and a kernel keeps a
+    # prologue of ordinary loads for firmware that does not preload
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
-           "-o", OUT, SRC]
+           "-mllvm", "-amdgpu-kernarg-preload-count=14", "-o", OUT, SRC]
     # PyTorch-ROCm ships its own libamdhip64.so (soname without the .7).  Link against THAT
     # copy so that the process holds one HIP runtime: streams and device pointers handed over
     # by torch are then valid inside this library whatever the import order.

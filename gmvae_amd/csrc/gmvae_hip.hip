@@ -1453,7 +1453,8 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const StepPlan& pn, const L
       c3 = c;
       // (an even number of panels: the first layer works on pairs of them, mega2.hpp)
       if (!fuse_pending)
-        hipLaunchKernelGGL(mega2_fwd_bwd, dim3((((B + kPanel - 1) / kPanel + 1) & ~1) * 4), dim3(kMT), (size_t)M2::total * sizeof(float), st, c);
+        hipLaunchKernelGGL(mega2_fwd_bwd, dim3((((B + kPanel - 1) / kPanel + 1) & ~1) * 4), dim3(kMT), (size_t)M2::total * sizeof(float), st,
+                           M2_HEAD_ARGS(c, w.sync, 0), c);
     } else if (m2v) {
       c.img2f = w.img2f; c.img2b = w.img2b; c.dimg2 = w.dimg2;
       c.lr = a.lr; c.b1 = a.beta1; c.b2 = a.beta2;
@@ -1641,7 +1642,8 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const StepPlan& pn, const L
       }
       // (the meeting area of a worker's tile: 34 KB at the bottom of the dynamic LDS, whatever the per-row part's map)
       if (m3.total_slots <= kM3MaxSlots && (!gmp || da.gmp_blocks < 0xfe)) {
-        if (!vfam) hipLaunchKernelGGL(mega3_step, dim3(grid3), dim3(kMT), (size_t)M2::total * sizeof(float), st, m3);
+        if (!vfam)
+          hipLaunchKernelGGL(mega3_step, dim3(grid3), dim3(kMT), (size_t)M2::total * sizeof(float), st, M2_HEAD_ARGS(m3.m, w.sync, m3.dbg ? 4 : 0), m3);
         else if (vk == 1) hipLaunchKernelGGL((mega3v_step<0, 2, 1>), dim3(grid3), dim3(kMT), (size_t)MV0::total * sizeof(float), st, m3);
         else hipLaunchKernelGGL((mega3v_step<1, 64, 10>), dim3(grid3), dim3(kMT), (size_t)MV1::total * sizeof(float), st, m3);
         cx.check();
@@ -1658,7 +1660,7 @@ static int run_step_mega(Ctx& cx, const StepArgs& a, const StepPlan& pn, const L
       fusev_pending = false;
     }
     if (fuse_pending) {                        // (cannot happen at mega2's sizes: the tile list fits) the two-launch form
-      hipLaunchKernelGGL(mega2_fwd_bwd, dim3(m2_grid), dim3(kMT), (size_t)M2::total * sizeof(float), st, c3);
+      hipLaunchKernelGGL(mega2_fwd_bwd, dim3(m2_grid), dim3(kMT), (size_t)M2::total * sizeof(float), st, M2_HEAD_ARGS(c3, w.sync, 0), c3);
       cx.check();
       cx.mark("mega2_fwd_bwd", m2_flops);
       fuse_pending = false;

@@ -165,15 +165,40 @@ __device__ __forceinline__ void st1o(float* p, const float v) {
 // workgroups go on to the weight-gradient tiles: the body then leaves alpha_t and the closing span stamp to the caller.  Returns
 // what the workgroup was: 0 a phantom panel's (its share of the pair's first layer is out), 1 a producer (partials published),
 // 2 the panel's lead (backward chain done, every output stored write-through).
+//
+// The head: what the first-layer block needs BEFORE its first weight burst goes out.  The kernels take these as leading scalar
+// parameters in front of the by-value argument struct (M2_HEAD_PARAMS): the compiler preloads leading scalar parameters into
+// SGPRs at wave start (build_hip.py: -amdgpu-kernarg-preload-count; a by-value struct is never preloaded), so no scalar round
+// trip into the cold kernel-argument block stands in front of the first vector load -- as struct fields they cost eight dependent
+// ones there (argument pointers, then *epoch_word / *err_word / step_dev[0] / lr_next[], then the diagnostic pointers, then w0a / w0b).
+// The launch's start state (hand-off tag, error word, step counter) is read through the preloaded pointers by the kernel's first
+// instructions -- scalar loads that nothing waits for until the bursts are out.  `sync` is the workspace's control block:
+// [0] the hand-off tag (MegaArgs::epoch_word), [1] the error word (err_word), [4..7] mega3_step's lr_next.
+// diag: bit 0 MegaArgs::span is set, bit 1 MegaArgs::dbg, bit 2 M3Args::dbg -- the diagnostic pointers themselves stay in the struct.
+#define M2_HEAD_PARAMS                                                                                                        \
+  const float *const w0a, const float *const w0b, const unsigned char *const x, const float *const img2f, const unsigned *const sync, \
+      const unsigned long long *const step_dev, const int B, const int diag
+// (the body takes them as scalars too: as members of a struct behind a reference the choice between w0a and w0b became an
+//  indexed load from a stack copy)
+#define M2_BODY_PARAMS                                                                                                        \
+  const float *const w0a, const float *const w0b, const unsigned char *const x, const float *const img2f, const int B_, const int diag, \
+      const unsigned epoch_, const unsigned err_, const unsigned long long step_
+#define M2_BODY_ARGS() w0a, w0b, x, img2f, B, diag, sync[0], sync[1], step_dev[0]
+// (host) the head of a launch whose MegaArgs is c; sync_: the control block c.epoch_word / c.err_word point into
+#define M2_HEAD_ARGS(c, sync_, extra)                                                                                         \
+  (c).w0a, (c).w0b, (c).x, (c).img2f, (const unsigned*)(sync_), (const unsigned long long*)(c).step_dev, (c).B,               \
+      (((c).span ? 1 : 0) | ((c).dbg ? 2 : 0) | (extra))
+static_assert(6 * 8 + 2 * 4 == 14 * 4, "the head fills the 14 user SGPRs left beside the kernel-argument pointer");
+
 template <int FUSE>
-__device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, unsigned* const m3_flags = nullptr) {
+__device__ __forceinline__ int mega2_body(M2_BODY_PARAMS, const MegaArgs& a, float* const sm) {
   constexpr int H = M2::H, L = M2::L, K = M2::K, D = M2::D, L2 = M2::L2, K2 = M2::K2;
   constexpr int Q = 4, H2f = 2 * H;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ln = lane & 15, lk = lane >> 4;
   // (the grid covers an EVEN number of panels: the first layer works on pairs of them; with an odd count the last pair's
   //  second panel is a phantom whose four workgroups take their part in the first layer and leave)
-  const int B = a.B, nP = ((B + kPanel - 1) / kPanel + 1) & ~1;
+  const int B = B_, nP = ((B + kPanel - 1) / kPanel + 1) & ~1;
   const int bid = blockIdx.x;
   // producers (quarters 1..3) take the LOWER block ids: a consumer can then never keep its producers off the chip
   const int q = bid < nP * (Q - 1) ? 1 + bid / nP : 0;
@@ -184,20 +209,21 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
   // who stores the panel's forward activations (kept for the weight gradients; every quarter holds the same bits): the lead,
   // or -- mega3_step -- quarter 1, whose end-of-role flag then covers them and who is off the launch's critical path
   const bool act = FUSE ? q == 1 : lead;
-  if (a.span && tid == 0) a.span[2 * bid] = wall_clock64();
+  if ((diag & 1) && tid == 0) a.span[2 * bid] = wall_clock64();
 #define M2_SPAN_END() if (!FUSE && a.span && threadIdx.x == 0) a.span[2 * blockIdx.x + 1] = wall_clock64()
-  const unsigned spin_limit = *a.err_word ? 0u : (1u << 19);       // bounded spins (see mega.hpp)
-  const unsigned epoch0 = *a.epoch_word;           // tag of this step's hand-offs
+  const unsigned spin_limit = err_ ? 0u : (1u << 19);            // bounded spins (see mega.hpp)
+  const unsigned epoch0 = epoch_;                 // tag of this step's hand-offs
   float* const img = sm + M2::IMG;
   float *P_h1 = sm + M2::P_h1, *P_y = sm + M2::P_y, *P_hg = sm + M2::P_hg, *P_pp = sm + M2::P_pp, *P_qp = sm + M2::P_qp;
   float *P_z = sm + M2::P_z, *P_sp = sm + M2::P_sp, *P_hd = sm + M2::P_hd, *P_eps = sm + M2::P_eps, *P_u = sm + M2::P_u;
   float *P_lg = sm + M2::P_lg, *nllp = sm + M2::nll, *rsum = sm + M2::rsum, *red = sm + M2::red, *dred = sm + M2::dred;
   float* P_dhd = sm + M2::P_dhd;
-  GMVAE_STAMP(0);
+  // (the diagnostic pointers are tested through `diag`: a test of a.dbg itself is a kernel-argument load with its wait here)
+  if ((diag & 2) && tid == 0) a.dbg[(size_t)bid * 16] = __builtin_amdgcn_s_memtime();      // GMVAE_STAMP(0)
   // diagnostics (tools/handoff_clock.py, GMVAE_STAMPS=5): device wall clock around the two in-launch hand-offs
-#define M2_WC(i) if (a.dbg && a.fine == 5 && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 16 + 8 + (i)] = wall_clock64()
+#define M2_WC(i) if ((diag & 2) && a.fine == 5 && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 16 + 8 + (i)] = wall_clock64()
   // GMVAE_STAMPS=6 (tools/flstamps.py): shader-clock stamps inside the first-layer stage
-#define M2_FC(i) if (a.dbg && a.fine == 6 && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 16 + 8 + (i)] = __builtin_amdgcn_s_memtime()
+#define M2_FC(i) if ((diag & 2) && a.fine == 6 && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 16 + 8 + (i)] = __builtin_amdgcn_s_memtime()
 
   // ======================================================================= FL: first layer over this quarter's columns
   // (the staging of mega_fwd_bwd's specialised instance: 49 bursts of 4 weight rows per tensor in two sub-chunks)
@@ -209,9 +235,9 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
     const int k0 = q * KQ;
     const int sp = pnl >> 1, hh = pnl & 1;         // the pair of panels; this workgroup's weight tensor (and its own row tile)
     const int rs0 = sp * 2 * kPanel;               // first of the pair's 32 rows
-    const float* const W0 = (hh ? a.w0b : a.w0a) + (long long)k0 * H;
+    const float* const W0 = (hh ? w0b : w0a) + (long long)k0 * H;
     const unsigned epoch_fl = epoch0;
-    const unsigned long long step = a.step_dev[0];
+    const unsigned long long step = step_;
     constexpr int qer = L / 4, qur = (K + 3) / 4, qe = kPanel * qer, qu = kPanel * qur;
     float nz[4] = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -228,7 +254,7 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
     for (int it = 0; it < 4; ++it) {               // always four loads per thread (clamped): uniform vmcnt accounting
       const int i = min(tid + it * kMT, 2 * kPanel * kq4 - 1);
       const int row = i / kq4, k4 = (i - row * kq4) * 4;
-      const unsigned wv = *reinterpret_cast<const unsigned*>(a.x + (long long)min(rs0 + row, B - 1) * D + k0 + k4);
+      const unsigned wv = *reinterpret_cast<const unsigned*>(x + (long long)min(rs0 + row, B - 1) * D + k0 + k4);
       xw[it] = rs0 + row < B ? wv : 0u;
     }
 #pragma unroll
@@ -240,7 +266,7 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
 #pragma unroll
     for (int j = 0; j < M2::imgF_pieces; ++j) {
       const int c = min(wave * 256 + j * 2048, M2::imgF - 256);
-      __builtin_amdgcn_global_load_lds(a.img2f + c + lane * 4, img + c, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(img2f + c + lane * 4, img + c, 16, 0, 0);
     }
     M2_FC(0);
     if (tid < qe + qu && nrow > 0) {               // this panel's rows of the Philox streams (= gmvae_noise_fill's)
@@ -372,7 +398,7 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
         for (int ht = 0; ht < 4; ++ht) wb[it][ht] = ld4(dbq + (((lt * 4 + lk) * 64 + ht * 16 + ln) << 2));
         bias4[it] = ld4(bq + lt * 16 + 4 * lk);
         const int c0 = m2_dec_tile(q, lt) * 16;
-        xb[it] = *reinterpret_cast<const unsigned*>(a.x + (long long)min(r0 + ln, B - 1) * D + c0 + 4 * lk);
+        xb[it] = *reinterpret_cast<const unsigned*>(x + (long long)min(r0 + ln, B - 1) * D + c0 + 4 * lk);
       }
     }
   }
@@ -827,9 +853,9 @@ __device__ __forceinline__ int mega2_body(const MegaArgs& a, float* const sm, un
   return 2;
 }
 
-__global__ __launch_bounds__(kMT) void mega2_fwd_bwd(const MegaArgs a) {
+__global__ __launch_bounds__(kMT) void mega2_fwd_bwd(M2_HEAD_PARAMS, const MegaArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  mega2_body<0>(a, sm);
+  mega2_body<0>(M2_BODY_ARGS(), a, sm);
 }
 
 }  // namespace gmvae

@@ -444,24 +444,24 @@ __device__ __forceinline__ void m3_worker_phase(const M3Args& aa, float* const s
 }
 
 
-__global__ __launch_bounds__(kMT) void mega3_step(const M3Args aa) {
+__global__ __launch_bounds__(kMT) void mega3_step(M2_HEAD_PARAMS, const M3Args aa) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const MegaArgs& a = aa.m;
-  const M3Fin& fa = aa.fa;
-  // what the worker phase needs of the launch's start state (read before anything can have changed it)
-  const unsigned epoch = *a.epoch_word;
-  const unsigned long long step = a.step_dev[0];
-  const unsigned spin_limit = *a.err_word ? 0u : (1u << 19);
-  const unsigned lr_bits = aa.lr_next[0];
-  const bool lr_hit = aa.lr_next[1] == (unsigned)(a.step_dev[0] + 1ull) && aa.lr_next[2] == __float_as_uint(aa.fa.lr) &&
-                      aa.lr_next[3] == alpha_key(aa.fa.b1, aa.fa.b2);
-  if (aa.dbg && threadIdx.x == 0) aa.dbg[(size_t)blockIdx.x * 8 + 7] = wall_clock64();
+  // what the launch needs of its start state (read before anything can have changed it): scalar loads through the PRELOADED
+  // pointers (mega2.hpp, the head), issued by the kernel's first instructions; nothing looks at them before the first layer's
+  // bursts are out -- alpha_t's tag (lr_next = sync + 4) is compared only behind the per-row role
+  const unsigned epoch = sync[0], err = sync[1];
+  const unsigned long long step = step_dev[0];
+  const unsigned lrn0 = sync[4], lrn1 = sync[5], lrn2 = sync[6], lrn3 = sync[7];
+  if ((diag & 4) && threadIdx.x == 0) aa.dbg[(size_t)blockIdx.x * 8 + 7] = wall_clock64();
   // (measured and dropped: pulling the worker phase's kernel-argument lines into the scalar cache here -- the dependent scalar
   //  loads delay the first layer, the launch's critical path: 32.4 against 31.9 us)
-  const int role = mega2_body<1>(a, sm);
-  const int nPr_ = (a.B + kPanel - 1) / kPanel, nP_ = (nPr_ + 1) & ~1, bid_ = blockIdx.x;
+  const int role = mega2_body<1>(w0a, w0b, x, img2f, B, diag, epoch, err, step, a, sm);
+  const unsigned spin_limit = err ? 0u : (1u << 19);
+  const bool lr_hit = lrn1 == (unsigned)(step + 1ull) && lrn2 == __float_as_uint(aa.fa.lr) && lrn3 == alpha_key(aa.fa.b1, aa.fa.b2);
+  const int nPr_ = (B + kPanel - 1) / kPanel, nP_ = (nPr_ + 1) & ~1, bid_ = blockIdx.x;
   const int q_ = bid_ < nP_ * 3 ? 1 + bid_ / nP_ : 0, pnl_ = bid_ < nP_ * 3 ? bid_ % nP_ : bid_ - nP_ * 3;
-  m3_worker_phase<3>(aa, sm, role, q_, pnl_, (q_ == 0 ? 3 * nPr_ : (q_ - 1) * nPr_) + pnl_, 4 * nPr_, epoch, step, spin_limit, lr_bits, lr_hit);
+  m3_worker_phase<3>(aa, sm, role, q_, pnl_, (q_ == 0 ? 3 * nPr_ : (q_ - 1) * nPr_) + pnl_, 4 * nPr_, epoch, step, spin_limit, lrn0, lr_hit);
 }
 
 // mega3v_step: the same for the VAE family at small batches (mega2v.hpp: seven workgroups per panel; BASELINE configs[0] / [1]).
