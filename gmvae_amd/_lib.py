@@ -135,6 +135,9 @@ LIK_GREY_BERNOULLI, LIK_CONT_BERNOULLI, LIK_GAUSSIAN, LIK_MASK = 1 << 11, 2 << 1
 # Engine(likelihood=...)
 LIKELIHOODS = {"bernoulli": 0, "grey_bernoulli": LIK_GREY_BERNOULLI, "continuous_bernoulli": LIK_CONT_BERNOULLI,
                "gaussian": LIK_GAUSSIAN}
+# ... x as float [B][D] / the Gaussian's scale per dimension and learned (include/gmvae_hip.h GMVAE_X_F32, GMVAE_LIK_SCALE_LEARNED)
+X_F32, LIK_SCALE_LEARNED = 1 << 13, 1 << 14
+LOG_SIGMA = "decoder/log_sigma"      # ... its parameter rho [1, D], the layout's last entry
 # Engine(y_estimator=...): the relaxed Gumbel-softmax sample, or its straight-through form (Jang et al. 2017)
 Y_ESTIMATORS = ("relaxed", "straight_through")
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph

@@ -167,6 +167,25 @@ class NormalFixedScale:
         return (-0.5 * e * e - math.log(self.sigma) - 0.5 * math.log(2 * math.pi)).sum(-1)
 
 
+class NormalDiagScale:
+    """Independent Normal(loc, sigma_d) with one scale per dimension: the Gaussian likelihood's decoder distribution under
+    likelihood_scale="learned" (sigma = exp of the parameter decoder/log_sigma, a tensor [D])."""
+
+    def __init__(self, loc, sigma, name="NormalDiagScale"):
+        self.loc, self.sigma, self.name = loc, sigma.to(loc.device, loc.dtype), name
+
+    def mean(self, name=None):
+        return self.loc
+
+    def sample(self, seed=None):
+        return self.loc + self.sigma * torch.randn(self.loc.shape, device=self.loc.device, dtype=self.loc.dtype,
+                                                   generator=_gen(seed, self.loc.device))
+
+    def log_prob(self, x):
+        e = (x.to(self.loc.dtype) - self.loc) / self.sigma
+        return (-0.5 * e * e - torch.log(self.sigma) - 0.5 * math.log(2 * math.pi)).sum(-1)
+
+
 class _Categorical:
     def __init__(self, logits):
         self.logits = logits
@@ -298,6 +317,8 @@ class ConditionalBernoulli(_Conditional):
         lik = "bernoulli" if self._engine is None else self._engine.likelihood
         if lik == "continuous_bernoulli":
             return ContinuousBernoulli(lam, name=self._name)
+        if lik == "gaussian" and self._engine.likelihood_scale == "learned":
+            return NormalDiagScale(lam, torch.exp(self._engine.views()["decoder/log_sigma"]), name=self._name)
         if lik == "gaussian":
             return NormalFixedScale(lam, self._engine.likelihood_sigma, name=self._name)
         return IndependentBernoulli(lam, name=self._name)

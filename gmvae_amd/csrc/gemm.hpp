@@ -100,6 +100,7 @@ struct Problem {
   int lik;                      // EPI_LIK (lik.hpp, GMVAE_LIK_*): the likelihood's kind, 1 grey Bernoulli / 2 continuous Bernoulli / 3 Gaussian,
   const float* lik_sigma;       // on the grey-level bytes x; fp32 C = (A' - t) / phi, no planes; part sums the log-probability terms, part2
                                 // the squared errors (A' - t)^2; lik_sigma: the Gaussian's device cell (read once per workgroup)
+                                // lik | LIK_XF32: x is float [.][ldx], the target itself; lik | LIK_RHO: lik_sigma is rho [N], sigma_n = exp(rho_n)
   Segment seg[2];
 };
 
@@ -1839,10 +1840,66 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
     const unsigned char* xp = L.p[pi].x;
     float* part = L.p[pi].part;
     float* const part2 = L.p[pi].part2;
-    const int ldx = L.p[pi].ldx, x_div = L.p[pi].x_div, nparts = L.p[pi].nparts, kind = L.p[pi].lik;
-    const LikConst lk = lik_const(kind, L.p[pi].lik_sigma);
-    if (m0 + C::BM <= M && (n0 + C::BN <= N || (N & 3) == 0) && (ldc & 3) == 0 && (!Cout || al16(Cout)) && al16(bias) && (!bias2 || al16(bias2)) &&
-        (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(xp) & 3) == 0) {
+    const int ldx = L.p[pi].ldx, x_div = L.p[pi].x_div, nparts = L.p[pi].nparts, kind = L.p[pi].lik & LIK_KIND_MASK;
+    // The Gaussian's two further forms (lik.hpp): LIK_XF32 -- the target is read as a float from x itself, ldx floats per row
+    // (GMVAE_X_F32); LIK_RHO -- lik_sigma points to rho [N], loaded per column quad as the bias is (GMVAE_LIK_SCALE_LEARNED).
+    // They take an interior block of their own below (the Gaussian term has no transcendental chain to interleave); the block of
+    // the byte targets under one scale keeps its code.
+    const bool xf32 = (L.p[pi].lik & LIK_XF32) != 0, rho = (L.p[pi].lik & LIK_RHO) != 0;
+    const float* const xf = reinterpret_cast<const float*>(xp);
+    const float* const sg = L.p[pi].lik_sigma;
+    const LikConst lk = rho ? LikConst{1.f, 0.f} : lik_const(kind, sg);
+    const bool tile_ok = m0 + C::BM <= M && (n0 + C::BN <= N || (N & 3) == 0) && (ldc & 3) == 0 && (!Cout || al16(Cout)) && al16(bias) &&
+                         (!bias2 || al16(bias2)) && (ldx & 3) == 0;
+    if (tile_ok && (xf32 || rho) && (reinterpret_cast<uintptr_t>(xp) & (xf32 ? 15 : 3)) == 0 && (!rho || al16(sg))) {
+      constexpr int RPP = C::THREADS / GPR;
+      const int c4 = tid % GPR, r0 = tid / GPR, nb = n0 + 4 * c4;
+      const bool nv = nb < N;                      // (this thread's column quad exists)
+      float4 b4 = nv ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bias2 && nv) { const float4 c4v = *reinterpret_cast<const float4*>(bias2 + nb); b4.x += c4v.x; b4.y += c4v.y; b4.z += c4v.z; b4.w += c4v.w; }
+      const float bc[4] = {b4.x + addconst, b4.y + addconst, b4.z + addconst, b4.w + addconst};
+      LikConst k0 = lk, k1 = lk, k2 = lk, k3 = lk;      // (per column: 1 / sigma_d^2 and -rho_d - ln(2 pi) / 2)
+      if (rho && nv) {
+        const float4 r4 = *reinterpret_cast<const float4*>(sg + nb);
+        k0 = lik_const_rho(r4.x); k1 = lik_const_rho(r4.y); k2 = lik_const_rho(r4.z); k3 = lik_const_rho(r4.w);
+      }
+      const LikConst kc[4] = {k0, k1, k2, k3};
+#pragma unroll
+      for (int q = 0; q < PASSES; ++q) {
+        const int row = r0 + RPP * q;
+        const long long xo = (long long)((m0 + row) / x_div) * ldx + nb;
+        f32x4 tv = {0.f, 0.f, 0.f, 0.f};
+        if (nv) {
+          if (xf32) {
+            tv = *reinterpret_cast<const f32x4*>(xf + xo);
+          } else {
+            const unsigned w = *reinterpret_cast<const unsigned*>(xp + xo);
+            tv = f32x4{lik_t(w & 0xffu), lik_t((w >> 8) & 0xffu), lik_t((w >> 16) & 0xffu), lik_t(w >> 24)};
+          }
+        }
+        f32x4 acc = *reinterpret_cast<const f32x4*>(lds + row * C::LDC + 4 * c4);
+#pragma unroll
+        for (int w = 1; w < C::WK; ++w) acc += *reinterpret_cast<const f32x4*>(lds + (w * C::BM + row) * C::LDC + 4 * c4);
+        float v[4], lps = 0.f, sqs = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float lp, df;
+          lik_term<LIK_GAUSS>(acc[j] + bc[j], tv[j], kc[j], lp, df);
+          lps += lp; sqs = fmaf(df, df, sqs);
+          v[j] = df * kc[j].is2;
+        }
+        if (Cout && nv) *reinterpret_cast<float4*>(Cout + (long long)(m0 + row) * ldc + nb) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float2*>(lds + row * C::LDC + 4 * c4) = nv ? make_float2(lps, sqs) : make_float2(0.f, 0.f);
+      }
+      __syncthreads();
+      if (tid < C::BM) {
+        double t = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < GPR; ++c) { t += (double)lds[tid * C::LDC + 4 * c]; t2 += (double)lds[tid * C::LDC + 4 * c + 1]; }
+        part[(long long)(m0 + tid) * nparts + tn] = (float)t;
+        part2[(long long)(m0 + tid) * nparts + tn] = (float)t2;
+      }
+    } else if (tile_ok && !xf32 && !rho && (reinterpret_cast<uintptr_t>(xp) & 3) == 0) {
       constexpr int RPP = C::THREADS / GPR;
       const int c4 = tid % GPR, r0 = tid / GPR, nb = n0 + 4 * c4;
       const bool nv = nb < N;                      // (this thread's column quad exists)
@@ -1917,14 +1974,15 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
         for (int j = 0; j < 4; ++j) {
           const int n = min(nb + j, N - 1);
           const float lam = v[j] + bias[n] + (bias2 ? bias2[n] : 0.f) + addconst;
-          const float tv = lik_t(xr[n]);
+          const float tv = xf32 ? xf[(long long)(m / x_div) * ldx + n] : lik_t(xr[n]);
+          const LikConst le = rho ? lik_const_rho(sg[n]) : lk;
           float lp, df;
-          if (kind == LIK_CB) lik_term<LIK_CB>(lam, tv, lk, lp, df);
-          else if (kind == LIK_GAUSS) lik_term<LIK_GAUSS>(lam, tv, lk, lp, df);
-          else lik_term<LIK_GREY>(lam, tv, lk, lp, df);
+          if (kind == LIK_CB) lik_term<LIK_CB>(lam, tv, le, lp, df);
+          else if (kind == LIK_GAUSS) lik_term<LIK_GAUSS>(lam, tv, le, lp, df);
+          else lik_term<LIK_GREY>(lam, tv, le, lp, df);
           rsum += (nb + j < N) ? lp : 0.f;
           rsum2 += (nb + j < N) ? df * df : 0.f;
-          v[j] = df * lk.is2;
+          v[j] = df * le.is2;
         }
         if (Cout) {
           float* dst = Cout + (long long)m * ldc + nb;

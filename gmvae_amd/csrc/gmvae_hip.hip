@@ -40,6 +40,7 @@
 #include "ytemp.hpp"
 #include "pmask.hpp"
 #include "lik.hpp"
+#include "liksig.hpp"
 #include "gclip.hpp"
 
 using namespace gmvae;
@@ -86,6 +87,12 @@ static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_P
 // likelihood epilogue of gemm.hpp, lik_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes.
 // 0: the Bernoulli on {0, 1}; else LIK_GREY / LIK_CB / LIK_GAUSS
 static int lik_kind(const GmvaeDims& d) { return (int)((d.sched_flags & GMVAE_LIK_MASK) >> 11); }
+// GMVAE_X_F32: x is float [B][D] behind the ABI's const uint8_t* -- the first layers' fp32 operand and the epilogue's target
+// itself, no lik_rows pass.  GMVAE_LIK_SCALE_LEARNED: sigma_d = exp(rho_d), rho the layout's last entry (liksig.hpp has its
+// gradient).  Both under LIK_GAUSS alone (check_lik_dims).
+static bool x_f32(const GmvaeDims& d) { return (d.sched_flags & GMVAE_X_F32) != 0; }
+static bool lik_learned(const GmvaeDims& d) { return (d.sched_flags & GMVAE_LIK_SCALE_LEARNED) != 0; }
+static size_t x_elem_bytes(const GmvaeDims& d) { return x_f32(d) ? 4 : 1; }
 // GMVAE_OPT_CLIP_NORM: the gradient clipped by its global norm in front of TF-Adam (gclip.hpp: finalize_grads_ss in
 // finalize_grads' place, gclip_finish_adam behind it) -- a training step with the bit takes the general schedule; forward-only
 // passes do not depend on it (run_step clears it for them)
@@ -136,7 +143,7 @@ struct NetL {
 };
 struct Layout {
   NetL ency, prior, encg, dec, enc;
-  uint64_t loc = 0, rawscale = 0, mixlog = 0, P_pad = 0, P_real = 0;
+  uint64_t loc = 0, rawscale = 0, mixlog = 0, logsig = 0, P_pad = 0, P_real = 0;      // (logsig: GMVAE_LIK_SCALE_LEARNED's rho [1, D])
   int n = 0;
   GmvaeParamEntry e[64];
 };
@@ -224,6 +231,7 @@ static int check_pmask_dims(const GmvaeDims* d) {
 // ... and GMVAE_LIK_* together with any other objective or estimator bit (GMVAE_OPT_CLIP_NORM combines): the three models'
 // standard objectives (the GMVAE's Gumbel draw) at any S only; the combinations are follow-ups  (gmvae_forward's check too)
 static int check_lik_dims(const GmvaeDims* d) {
+  if ((x_f32(*d) || lik_learned(*d)) && lik_kind(*d) != LIK_GAUSS) return GMVAE_E_DIMS;      // (either bit without the Gaussian)
   if (!lik_kind(*d)) return 0;
   return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
                             GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH | GMVAE_OBJ_PIXEL_MASK)) ? GMVAE_E_DIMS : 0;
@@ -257,6 +265,7 @@ static void build_layout(const GmvaeDims& d, int model, Layout& L) {
     add_net(L, L.enc, "encoder", d.D, d.hidden, d.n_hidden, 2 * d.L);
     add_net(L, L.dec, "decoder", d.L, d.hidden, d.n_hidden, d.D);
   }
+  if (lik_learned(d)) add_entry(L, "decoder/log_sigma", 1, d.D, L.logsig);      // (the last entry: without the bit the layout is unchanged)
 }
 
 // --------------------------------------------------------------- workspace
@@ -284,6 +293,8 @@ struct WS {
   // GMVAE_LIK_*: the Gaussian's sigma (one float, the caller's, read only), t = x / 255 as fp32 [B D], the squared-error partials
   // [R][nparts] beside part
   float *lik_sigma, *lik_t, *lik_part;
+  // GMVAE_LIK_SCALE_LEARNED: liksig_partial's slab partials [liksig_slabs(R)][pad4(D)] (no lik_sigma); GMVAE_X_F32: no lik_t
+  float* lsig_part;
   // GMVAE_OPT_CLIP_NORM: the caller's threshold (one float, read only), the records [GMVAE_LABEL_SLOTS][4] the library writes
   // and the fp64 partials of the sum of squares, one per 1024 elements of the gradient buffer
   float *clip_norm, *grad_clip;
@@ -581,9 +592,10 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
     w.mcnt = take(2 * B);
   }
   if (lik_kind(d)) {                              // (behind everything, as above; in front of the clip regions: a field of its own)
-    if (lik_kind(d) == LIK_GAUSS) w.lik_sigma = take(4);
-    w.lik_t = take(B * D);
+    if (lik_kind(d) == LIK_GAUSS && !lik_learned(d)) w.lik_sigma = take(4);
+    if (!x_f32(d)) w.lik_t = take(B * D);
     w.lik_part = take(R * ((D + 31) / 32));
+    if (lik_learned(d)) w.lsig_part = take((uint64_t)liksig_slabs((long long)R) * pad4(D));
   }
   if (clip_norm(d)) {                             // (behind everything, as above: dims without the bit keep their size and every offset)
     w.clip_norm = take(4);
@@ -2196,10 +2208,14 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   // GMVAE_LIK_*: t = x / 255 as fp32 is what the first layers and their weight gradients read (a float operand), a.x itself only
   // the likelihood epilogue's target
   const int lik = lik_kind(d);
-  if (lik && (marg || pmask || !w.lik_t || !w.lik_part || (lik == LIK_GAUSS && !w.lik_sigma))) return GMVAE_E_DIMS;
-  const void* const xop = lik ? (const void*)w.lik_t : (const void*)xin;      // (the first layers' operand: bytes, or t)
+  const bool xf = x_f32(d), lsig = lik_learned(d);       // (check_lik_dims: under LIK_GAUSS alone)
+  if ((xf || lsig) && lik != LIK_GAUSS) return GMVAE_E_DIMS;
+  if (lik && (marg || pmask || (!xf && !w.lik_t) || !w.lik_part || (lik == LIK_GAUSS && !lsig && !w.lik_sigma) || (lsig && !w.lsig_part)))
+    return GMVAE_E_DIMS;
+  // (the first layers' operand: bytes, t, or under GMVAE_X_F32 the caller's floats themselves)
+  const void* const xop = lik ? (xf ? (const void*)a.x : (const void*)w.lik_t) : (const void*)xin;
   const bool xu8 = !lik;
-  if (lik) {
+  if (lik && !xf) {
     hipLaunchKernelGGL(lik_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, w.lik_t, B, D);
     rowk(cx, "lik_rows");
   }
@@ -2455,7 +2471,8 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       p.x = a.x; p.ldx = D; p.x_div = S; p.part = w.part;
       p.xmask = pm; p.part2 = pmask ? w.hpart : nullptr;      // (the masked form: observed columns to part, held-out ones to part2)
       if (lik) {      // (the likelihood form: the log-probability terms to part, the squared errors to part2, (A' - t) / phi to C)
-        p.epi = EPI_LIK; p.lik = lik; p.lik_sigma = w.lik_sigma; p.part2 = w.lik_part;
+        p.epi = EPI_LIK; p.lik = lik | (xf ? LIK_XF32 : 0) | (lsig ? LIK_RHO : 0); p.part2 = w.lik_part;
+        p.lik_sigma = lsig ? P + L.logsig : w.lik_sigma;      // (the cell, or rho [D])
       }
       if (fwdp) {
         // forward only: both operands as f16 pairs, the weight's planes zero-padded to whole 128-column tiles
@@ -2605,6 +2622,13 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   auto small_ns = [&](long long outs) { return (NSS != NS && outs <= 131072 && sxb.n + 2 <= kSlabRanges) ? NSS : NS; };
   const long long PP = (long long)L.P_pad;
   float* sl = w.slabs;
+  if (lsig) {      // GMVAE_LIK_SCALE_LEARNED: rho's gradient from the stored g and the row weights, into rho's range of the slabs
+    const int Dp = (int)pad4((uint64_t)D), nsl = liksig_slabs(R);
+    hipLaunchKernelGGL(liksig_partial, dim3((D + kLsigCols - 1) / kLsigCols, nsl), dim3(256), 0, st, w.g, rwS, P + L.logsig,
+                       w.lsig_part, R, D, Dp, liksig_slab_rows(R));
+    hipLaunchKernelGGL(liksig_finish, dim3((Dp + 255) / 256), dim3(256), 0, st, w.lsig_part, nsl, sl, PP, NS, (long long)L.logsig, Dp);
+    rowk(cx, "liksig");
+  }
   int pb = 0;
   const float* dcur = w.g;
   for (int i = Dn.nl - 1; i >= 0; --i) {   // decoder: dW_i (+db_i) and dX_i in one launch
@@ -2864,6 +2888,8 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
 }
 
 static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// GMVAE_X_F32: x is read as float [B][D] -- its base 16-byte aligned (behind the NULL checks of every entry point that takes x)
+static int check_x_align(const GmvaeDims* d, const void* x) { return (x_f32(*d) && !aligned16(x)) ? GMVAE_E_ALIGN : 0; }
 
 // ---- the chunked importance-sampling evaluators (gmvae_iw_bound, gmvae_iw_bound_enum_y, gmvae_posterior_y,
 // gmvae_posterior_component): ONE host path.  A kind is a row of kIwKinds, its own workspace regions in iw_lay and its merge
@@ -3186,6 +3212,7 @@ int gmvae_step(const GmvaeDims* dims, int model, const uint8_t* x, const float* 
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace) || (eps && !aligned16(eps)) ||
       (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
+  if (int e = check_x_align(dims, x)) return e;
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   const char* fc = getenv("GMVAE_FORCE_CFG");
@@ -3223,6 +3250,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;
+  if (int e = check_x_align(dims, x)) return e;
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   StepArgs a = {dims, model, x, eps, u, params, nullptr, tail, row_terms, z_out, y_out, logits_out, workspace, seed,
@@ -3843,7 +3871,8 @@ static int train_graph_create(const GmvaeDims* dims, int model, const uint8_t* p
   if (!x || !params || !m || !v || !grads || !workspace || !step_dev || !graph_out) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
   if (pixels && (!idx || n_rows < 1 || (dims->D & 3))) return GMVAE_E_DIMS;
-  const size_t xstride = (size_t)dims->B * dims->D;
+  if (int e = check_x_align(dims, x)) return e;
+  const size_t xstride = (size_t)dims->B * dims->D * x_elem_bytes(*dims);      // (bytes: floats under GMVAE_X_F32)
   Layout L;
   build_layout(*dims, model, L);
   hipStream_t cs;
@@ -3947,10 +3976,11 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   const StepPlan pn = plan_train_step(d, model);
   const char* const kinds[] = {"general", pn.m2 ? "mega2" : (pn.vk ? "mega2v" : "mega"), "skinny", "fused"};
   const char* nm = kinds[pn.kind];
-  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
+  snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
            y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "",
-           lik_kind(d) == LIK_GREY ? "+grey" : lik_kind(d) == LIK_CB ? "+cb" : lik_kind(d) == LIK_GAUSS ? "+gauss" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
+           lik_kind(d) == LIK_GREY ? "+grey" : lik_kind(d) == LIK_CB ? "+cb" : lik_kind(d) == LIK_GAUSS ? "+gauss" : "",
+           x_f32(d) ? "+f32" : "", lik_learned(d) ? "+lsig" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
            pn.planes ? "+planes" : "");
   return 0;
 }
@@ -4093,6 +4123,7 @@ static int dp_step_impl(const GmvaeDims* dims, int model, const uint8_t* x, floa
   if (int e = check_step_dims(dims, model)) return e;
   if (!x || !params || !m || !v || !grads || !workspace || !comm || !g_rccl.h || !step_dev) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(grads) || !aligned16(workspace)) return GMVAE_E_ALIGN;
+  if (int e = check_x_align(dims, x)) return e;
   Layout L;
   build_layout(*dims, model, L);
   WS w;
@@ -4269,6 +4300,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
   if (clip_norm(*dims) && n_steps > GMVAE_LABEL_SLOTS) return GMVAE_E_DIMS;        // (step i writes record i)
   if (!graph_out || !comm) return GMVAE_E_NULL;
   if (n_steps < 1 || n_steps > 1024) return GMVAE_E_DIMS;
+  if (x) { if (int e = check_x_align(dims, x)) return e; }
   hipStream_t cs;
   hipError_t he = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
   if (he != hipSuccess) return (int)he;
@@ -4285,7 +4317,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
   }
   if (rc == 0) {
     for (int s = 0; s < n_steps && rc == 0; ++s)
-      rc = dp_step_impl(dims, model, x + (size_t)s * dims->B * dims->D, params, m, v, grads, workspace, seed, step_dev, lr,
+      rc = dp_step_impl(dims, model, x + (size_t)s * dims->B * dims->D * x_elem_bytes(*dims), params, m, v, grads, workspace, seed, step_dev, lr,
                         beta1, beta2, epsilon, comm, cs, true, s > 0, tail_log ? tail_log + (size_t)s * GMVAE_TAIL : nullptr, -1,
                         nullptr, s);
     he = hipStreamEndCapture(cs, &tg->graph);

@@ -34,6 +34,16 @@ __device__ __forceinline__ LikConst lik_const(const int kind, const float* __res
   }
   return k;
 }
+// Problem::lik carries two further bits beside the kind: the target is x itself as fp32 (GMVAE_X_F32), and the Gaussian's scale
+// is per column and learned, sigma_d = exp(rho_d) (GMVAE_LIK_SCALE_LEARNED; liksig.hpp has rho's gradient)
+enum { LIK_KIND_MASK = 3, LIK_RHO = 4, LIK_XF32 = 8 };
+// ... the same two constants of one column from rho_d: exp(-2 rho) and -rho - ln(2 pi) / 2
+__device__ __forceinline__ LikConst lik_const_rho(const float rho) {
+  LikConst k;
+  k.is2 = expf(-2.f * rho);
+  k.cst = -rho - 0.918938533204672742f;
+  return k;
+}
 
 // Continuous Bernoulli: (A, A') of one logit, no branch.
 //   |l| < 1    the series in h = l / 2:  A = h + log(sinh h / h) = h + h^2/6 - h^4/180 + h^6/2835 - h^8/37800

@@ -47,13 +47,15 @@ class DeviceDataset:
     [N, D], resident too -- the row's observation mask (non-zero: observed) of a step with a pixel mask.
     binarize=False: `next_batch` returns the gathered GREY rows as they are (a torch gather, off the hot path), for a model
     with a likelihood on grey levels.  The two paths do not feed the same picture: the binarising one sets a pixel with
-    probability 1 - intensity, the grey one feeds the intensity itself, t = pixel / 255."""
+    probability 1 - intensity, the grey one feeds the intensity itself, t = pixel / 255.  With binarize=False a FLOAT array
+    stays float32 [N, D] (real-valued rows for a model created with real_valued=True) and `next_batch` returns float32 rows."""
 
     def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None, pixel_mask=None,
                  binarize: bool = True):
         dev = L.require_gpu()
         pixels = torch.as_tensor(pixels)
-        self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.uint8).contiguous()
+        keep_float = not binarize and pixels.dtype.is_floating_point
+        self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.float32 if keep_float else torch.uint8).contiguous()
         self.labels = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
         self.y_observed = None if y_observed is None else torch.as_tensor(y_observed).to(dev, torch.int32).contiguous()
         self.N, self.D = self.pixels.shape

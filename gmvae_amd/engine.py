@@ -136,6 +136,20 @@ def check_likelihood(model, y_inference, grad_estimator, semi_supervised, weight
     return sigma
 
 
+LIKELIHOOD_SCALES = ("fixed", "learned")
+
+
+def check_real_valued(likelihood, real_valued=False, likelihood_scale="fixed"):
+    """The argument check of Engine(real_valued=, likelihood_scale=) (no device needed): the library's refusals of GMVAE_X_F32
+    and GMVAE_LIK_SCALE_LEARNED -- both need the Gaussian likelihood (whose own refusals check_likelihood holds)."""
+    if likelihood_scale not in LIKELIHOOD_SCALES:
+        raise ValueError(f"likelihood_scale must be one of {LIKELIHOOD_SCALES}, got {likelihood_scale!r}")
+    if real_valued and likelihood != "gaussian":
+        raise ValueError(f"real_valued=True needs likelihood='gaussian', got likelihood={likelihood!r}")
+    if likelihood_scale == "learned" and likelihood != "gaussian":
+        raise ValueError(f"likelihood_scale='learned' needs likelihood='gaussian', got likelihood={likelihood!r}")
+
+
 def check_clip_norm(clip_norm):
     """The argument check of Engine(clip_norm=) and set_clip_norm (no device needed): None (off) or a threshold > 0; inf reports
     the norm and never clips.  Returns the value as a float, or None."""
@@ -209,7 +223,7 @@ class Engine:
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
                  y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed",
                  pixel_mask: bool = False, clip_norm: Optional[float] = None, likelihood: str = "bernoulli",
-                 likelihood_sigma: float = 1.0):
+                 likelihood_sigma: float = 1.0, real_valued: bool = False, likelihood_scale: str = "fixed"):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -255,8 +269,15 @@ class Engine:
         decoder's output, fixed scale likelihood_sigma; set_likelihood_sigma changes it between steps and replays, a device-side
         write).  x is then taken as uint8 grey levels as given; a float tensor must lie in [0, 1] and is rounded to the nearest
         k / 255.  Every network that reads x reads t; tail[5] / tail[6] is the per-pixel squared reconstruction error.  General
-        schedule; combines with clip_norm alone.  Parameters and checkpoints have the same layout under every likelihood."""
+        schedule; combines with clip_norm alone.  Parameters and checkpoints have the same layout under every likelihood.
+        real_valued (likelihood "gaussian"; include/gmvae_hip.h GMVAE_X_F32): x is a float feature matrix [B, D] -- embeddings,
+        sensor vectors, tabular data -- taken as given (float32, any finite values; no uint8): the networks and the likelihood
+        read x itself.  likelihood_scale (likelihood "gaussian"; GMVAE_LIK_SCALE_LEARNED): "fixed" -- one sigma, the default --
+        or "learned": a scale per dimension, sigma_d = exp(rho_d), rho = the parameter "decoder/log_sigma" [1, D] initialised to
+        ln(likelihood_sigma) and trained like every other parameter (it is the layout's last entry; a checkpoint carries it,
+        and restoring one without it into such an engine, or the reverse, raises).  set_likelihood_sigma then raises."""
         clip_norm = check_clip_norm(clip_norm)
+        check_real_valued(likelihood, real_valued, likelihood_scale)
         likelihood_sigma = check_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective,
                                             temperature_on_device, y_estimator, pixel_mask, likelihood, likelihood_sigma)
         check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
@@ -314,6 +335,8 @@ class Engine:
         self.clip_norm = clip_norm
         self.likelihood = likelihood
         self.likelihood_sigma = likelihood_sigma
+        self.real_valued = bool(real_valued)
+        self.likelihood_scale = likelihood_scale
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
                        gen_bias_init=float(gen_bias_init), hidden_act=hidden_act)
@@ -356,7 +379,7 @@ class Engine:
         # the Gaussian likelihood's sigma on the device: every workspace's "lik_sigma" cell is a copy of it
         self._sigma_dev = None
         self._sigma_cells: Dict[tuple, torch.Tensor] = {}
-        if self.likelihood == "gaussian":
+        if self.likelihood == "gaussian" and self.likelihood_scale == "fixed":
             self._sigma_dev = torch.full((1,), self.likelihood_sigma, dtype=torch.float32, device=self.device)
         self.init_parameters(random_seed)
 
@@ -374,6 +397,7 @@ class Engine:
         yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
         pmask = (L.OBJ_PIXEL_MASK if self.pixel_mask else 0) | (L.OPT_CLIP_NORM if self.clip_norm is not None else 0)
         pmask |= L.LIKELIHOODS[self.likelihood]
+        pmask |= (L.X_F32 if self.real_valued else 0) | (L.LIK_SCALE_LEARNED if self.likelihood_scale == "learned" else 0)
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
                            sched_flags=(L.SCHED_SAFE if self.safe_schedule else 0) | self._obj_flags() | wobj | yh | pmask | extra_flags, **self.hp)
@@ -417,6 +441,9 @@ class Engine:
         for name, (rows, cols), off in self.layout:
             if name.endswith("/b"):
                 continue
+            if name == L.LOG_SIGMA:             # rho = ln sigma for every dimension
+                flat[off:off + rows * cols] = math.log(self.likelihood_sigma)
+                continue
             fan_in, fan_out = (cols, cols) if name == "mixture_logits" else (rows, cols)
             lim = math.sqrt(6.0 / (fan_in + fan_out))
             flat[off:off + rows * cols] = (torch.rand(rows * cols, generator=gen) * 2 - 1) * lim
@@ -433,7 +460,7 @@ class Engine:
         out = {}
         for name, (rows, cols), off in self.layout:
             v = self.params.detach()[off:off + rows * cols]
-            if name.endswith("/b") or name == "mixture_logits":
+            if name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA):
                 out[name] = v
             else:
                 out[name] = v.view(rows, cols)
@@ -443,7 +470,7 @@ class Engine:
         out = {}
         for name, (rows, cols), off in self.layout:
             v = flat[off:off + rows * cols]
-            out[name] = v if (name.endswith("/b") or name == "mixture_logits") else v.view(rows, cols)
+            out[name] = v if (name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA)) else v.view(rows, cols)
         return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -463,6 +490,9 @@ class Engine:
         return sd
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        if (L.LOG_SIGMA in sd) != (self.likelihood_scale == "learned"):
+            raise ValueError(f"this checkpoint {'carries' if L.LOG_SIGMA in sd else 'has no'} {L.LOG_SIGMA!r}: it cannot be restored "
+                             f"into an engine with likelihood_scale={self.likelihood_scale!r}")
         self._param_epoch += 1
         views = self.views()
         with torch.no_grad():
@@ -514,7 +544,7 @@ class Engine:
     # ------------------------------------------------------- the Gaussian likelihood's sigma (likelihood_sigma)
     def _bind_sigma(self, key, d, ws):
         """The workspace's "lik_sigma" cell <- the engine's sigma (a zeroed cell means sigma = 0: a non-finite step)."""
-        if (d.sched_flags & L.LIK_MASK) == L.LIK_GAUSSIAN:
+        if (d.sched_flags & L.LIK_MASK) == L.LIK_GAUSSIAN and not d.sched_flags & L.LIK_SCALE_LEARNED:
             off = L.workspace_offset(d, self.model, "lik_sigma") // 4
             self._sigma_cells[key] = ws[off:off + 1]
             self._sigma_cells[key].copy_(self._sigma_dev, non_blocking=True)
@@ -523,6 +553,9 @@ class Engine:
         """The Gaussian likelihood's scale the next steps read, eager or replayed: device-side writes, no host sync, no recapture."""
         if self.likelihood != "gaussian":
             raise ValueError("set_likelihood_sigma needs an engine created with likelihood='gaussian'")
+        if self.likelihood_scale == "learned":
+            raise ValueError("set_likelihood_sigma: with likelihood_scale='learned' the scale is the parameter "
+                             f"{L.LOG_SIGMA!r}, not a setting")
         self.likelihood_sigma = check_likelihood(self.model_name, "gumbel", "standard", False, False, False, "relaxed", False,
                                                  "gaussian", sigma)
         self._sigma_dev.fill_(self.likelihood_sigma)
@@ -622,6 +655,16 @@ class Engine:
 
     def _prep_x(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(self.device)
+        if self.real_valued:
+            # a float feature matrix, as given: float32, contiguous, [B, D], its base 16-byte aligned (GMVAE_X_F32)
+            if not x.dtype.is_floating_point:
+                raise ValueError(f"real_valued=True takes a float tensor [B, {self.D}], got {x.dtype}")
+            x = x.to(torch.float32).reshape(x.shape[0], -1).contiguous()
+            if x.shape[1] != self.D:
+                raise ValueError(f"expected [B,{self.D}] inputs, got {tuple(x.shape)}")
+            if x.numel() and not bool(torch.isfinite(x).all()):
+                raise ValueError("real_valued=True takes finite values: x holds NaN or inf")
+            return x.clone() if x.data_ptr() % 16 else x
         if self.likelihood != "bernoulli" and x.dtype.is_floating_point:
             # grey levels: a float image in [0, 1] -> the nearest k / 255 (uint8 tensors are taken as grey levels as given)
             if x.numel() and not bool(((x >= 0) & (x <= 1)).all()):
@@ -801,7 +844,9 @@ class Engine:
 
     def mlp(self, net: int, inp: torch.Tensor, in2: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One conditional network's MLP on the device (snt.nets.MLP, scripts/base.py:47-60)."""
-        if self.likelihood != "bernoulli" and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
+        if self.real_valued and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
+            inp = self._prep_x(inp)                                 # (the networks that read x read the floats themselves)
+        elif self.likelihood != "bernoulli" and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
             inp = self._prep_x(inp).to(torch.float32) / 255.0       # (the networks that read x read t = x / 255 as fp32)
         is_u8 = inp.dtype in (torch.uint8, torch.bool)
         inp = self._as_u8(inp.to(self.device)) if is_u8 else inp.to(self.device, torch.float32).contiguous()
@@ -960,10 +1005,11 @@ class Engine:
         if key in self._graphs:
             self.step_dev.fill_(self.global_step)   # eager steps may have run since the capture
             return self._graphs[key][:2]
+        xdt = torch.float32 if self.real_valued else torch.uint8      # (GMVAE_X_F32: step i reads the floats at x + i B D)
         if n_steps == 1:
-            static_x = torch.zeros(B, self.D, dtype=torch.uint8, device=self.device)
+            static_x = torch.zeros(B, self.D, dtype=xdt, device=self.device)
         else:
-            static_x = torch.zeros(n_steps, B, self.D, dtype=torch.uint8, device=self.device)
+            static_x = torch.zeros(n_steps, B, self.D, dtype=xdt, device=self.device)
         d, ws = self._workspace(B)
         rows = {inp: self._slots(inp, d, ws)[:n_steps] for inp in active}      # step i reads row i; the caller fills them
         for inp, view in rows.items():

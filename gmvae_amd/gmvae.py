@@ -118,8 +118,12 @@ class TrainableGMVAE(GMVAE):
         samples of z per component, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_y)."""
         return self._need_engine().posterior_y(images, n_samples, chunk)["log_post"]
 
-    def predict_clusters(self, images, n_samples):
-        """The component the model's posterior p(y | x) assigns each example to: an int64 [B] device tensor."""
+    def predict_clusters(self, images, n_samples=None):
+        """The component the model's posterior p(y | x) assigns each example to: an int64 [B] device tensor.  A model on
+        real-valued rows (real_valued=True), whose likelihood the enumerating evaluators refuse, assigns by the inference
+        network's q(y | x) instead and takes no n_samples."""
+        if self._need_engine().real_valued:
+            return self.encoder_y(images).distribution.logits.argmax(dim=1)
         return self.posterior_y(images, n_samples).argmax(dim=1)
 
     @property
@@ -143,6 +147,8 @@ class TrainableGMVAE(GMVAE):
             out["observed_share"] = t[7] / (t[6] + t[7])
         if e.likelihood != "bernoulli":            # (the per-pixel squared error of the mean image A'(lambda) against t = x / 255)
             out["recon_mse"] = t[5] / t[6]
+        if e.likelihood_scale == "learned":        # (the mean of the learned per-dimension scales sigma_d = exp(rho_d))
+            out["sigma_mean"] = torch.exp(e.views()["decoder/log_sigma"]).mean()
         if e.clip_norm is not None:                # (of the last eager optimizer step: the norm before clipping, clipped 0 / 1)
             out["grad_norm"], out["clipped"] = e.grad_clip[0], e.grad_clip[2]
         if self._last_labels is not None:
@@ -172,9 +178,9 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
                  semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0,
                  temperature_on_device=False, y_estimator="relaxed", pixel_mask=False, clip_norm=None, likelihood="bernoulli",
-                 likelihood_sigma=1.0):
+                 likelihood_sigma=1.0, real_valued=False, likelihood_scale="fixed"):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
-    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask, clip_norm, likelihood, likelihood_sigma: Engine).  y_inference="marginal" trains and
+    sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask, clip_norm, likelihood, likelihood_sigma, real_valued, likelihood_scale: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z
     importance-weighted over n_samples samples per component.  The parameters and their names are the same in every mode, so
     a checkpoint of any loads in the others."""
@@ -186,7 +192,8 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                     y_inference=y_inference, grad_estimator=grad_estimator, semi_supervised=semi_supervised,
                     sup_weight=sup_weight, weighted_objective=weighted_objective, kl_weight=kl_weight, y_weight=y_weight,
                     y_free_nats=y_free_nats, temperature_on_device=temperature_on_device, y_estimator=y_estimator,
-                    pixel_mask=pixel_mask, clip_norm=clip_norm, likelihood=likelihood, likelihood_sigma=likelihood_sigma)
+                    pixel_mask=pixel_mask, clip_norm=clip_norm, likelihood=likelihood, likelihood_sigma=likelihood_sigma,
+                    real_valued=real_valued, likelihood_scale=likelihood_scale)
     prior_gmm = base.ConditionalNormal(size=latent_size, hidden_layer_sizes=None,
                                        hidden_activation_fn=hidden_activation_fn, sigma_min=sigma_min,
                                        raw_sigma_bias=raw_sigma_bias, name="prior_gmm").bind(engine, L.NET_PRIOR_GMM)

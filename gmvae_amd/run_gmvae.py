@@ -85,7 +85,17 @@ def build_parser():
       help="the decoder's likelihood: bernoulli on binarised pixels (the reference), or on the GREY levels t = pixel / 255 the "
       "Bernoulli cross-entropy on soft targets (grey_bernoulli), the continuous Bernoulli or a Gaussian with the fixed scale "
       "--likelihood_sigma; train and eval then report recon_mse, the per-pixel squared error of the mean image")
-    a("--likelihood_sigma", type=float, default=1.0, help="--likelihood=gaussian: the fixed scale sigma")
+    a("--likelihood_sigma", type=float, default=1.0, help="--likelihood=gaussian: the fixed scale sigma (with "
+      "--likelihood_scale=learned: where every dimension's scale starts)")
+    a("--real_valued", action="store_true", help="--likelihood=gaussian: the rows are float feature vectors (embeddings, sensor "
+      "vectors, tabular data) fed as they are -- from --data_npy, or a synthetic mixture of Gaussian blobs with labels")
+    a("--likelihood_scale", default="fixed", choices=["fixed", "learned"], help="--likelihood=gaussian: one fixed scale, or a "
+      "scale per dimension learned with the model (the parameter decoder/log_sigma)")
+    a("--data_npy", default=None, help="--real_valued: a .npy file holding the float32 [N, D] rows (train and eval read the same "
+      "file); --data_dim follows it")
+    a("--labels_npy", default=None, help="--data_npy: a .npy file holding the N integer labels (clustering accuracy only)")
+    a("--standardize", action="store_true", help="--real_valued: subtract the per-feature mean and divide by the per-feature "
+      "standard deviation of the train rows; both are saved in the checkpoint and applied in eval")
     return p
 
 
@@ -177,6 +187,22 @@ def check_args(p, cfg):
         if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
             p.error(f"{what} is not available with --iw_enum_samples, --posterior_samples or --component_posterior_samples "
                     "(they would score Bernoulli): use --iw_samples")
+    if cfg.real_valued and cfg.likelihood != "gaussian":
+        p.error("--real_valued needs --likelihood=gaussian")
+    if cfg.likelihood_scale == "learned" and cfg.likelihood != "gaussian":
+        p.error("--likelihood_scale=learned needs --likelihood=gaussian")
+    if (cfg.data_npy or cfg.standardize) and not cfg.real_valued:
+        p.error("--data_npy and --standardize need --real_valued")
+    if cfg.labels_npy and not cfg.data_npy:
+        p.error("--labels_npy needs --data_npy")
+    if cfg.data_npy:
+        try:
+            shape = runners.npy_shape(cfg.data_npy)
+        except (OSError, ValueError) as e:
+            p.error(f"--data_npy: {e}")
+        if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+            p.error(f"--data_npy must hold a float32 [N, D] array, got shape {shape}")
+        cfg.data_dim = int(shape[1])
     return cfg
 
 

@@ -39,14 +39,17 @@ def _load_mnist(root: str, split: str):
     return None
 
 
-def create_dataset(config, split="train", shuffle=True, repeat=True, device="cuda", with_index=False):
+def create_dataset(config, split="train", shuffle=True, repeat=True, device="cuda", with_index=False, standardize=None):
     """Yields (images bool/uint8 [B,784] on device, labels int64 [B]) -- the output contract of
     scripts/runners.py:21-62.  Dynamic binarisation keeps the reference's INVERTED rule
     `image < U(0,1)` (runners.py:44-47: P(pixel=1) = 1 - intensity) and is redrawn every epoch;
     examples are shuffled per epoch (the reference's batch-level shuffle order is not copied).
     The last partial batch is kept (no drop_remainder, runners.py:51).  Without local MNIST files
     (--data_dir) a synthetic Bernoulli(0.87) set with random labels stands in.  with_index: yields a third item, the index in
-    the split of the batch's first example (its rows follow in order when shuffle=False)."""
+    the split of the batch's first example (its rows follow in order when shuffle=False).  --real_valued: float32 rows as
+    they are (real_rows; standardize = the checkpoint's (mean, std))."""
+    if real_valued(config):
+        return _real_batches(config, shuffle, repeat, device, with_index, standardize)
     data = _load_mnist(getattr(config, "data_dir", "") or "", split) if getattr(config, "data_dir", None) else None
     rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
     gen = torch.Generator(device=device)
@@ -77,6 +80,77 @@ def create_dataset(config, split="train", shuffle=True, repeat=True, device="cud
             for s in range(0, n, B):
                 idx = order[s:s + B]
                 yield (binar[idx], labels[idx], a + s) if with_index else (binar[idx], labels[idx])
+            if not repeat:
+                return
+    return it()
+
+
+def real_valued(config) -> bool:
+    """--real_valued: the rows are float feature vectors fed as they are (Engine(real_valued=True))."""
+    return bool(getattr(config, "real_valued", False))
+
+
+def npy_shape(path: str):
+    """The shape of the array in a .npy file, from its header."""
+    return tuple(np.load(path, mmap_mode="r").shape)
+
+
+def synthetic_real(n: int, D: int):
+    """The synthetic stand-in of a real-valued run: (float32 [n, D], int64 labels [n]) -- a fixed-seed mixture of 10
+    well-separated Gaussian blobs (centres drawn at scale 3, noise of 0.2 .. 0.6 per feature), so that clustering accuracy
+    means something; train and eval see the same rows."""
+    rng = np.random.default_rng(6)
+    k = 10
+    centres = rng.normal(0.0, 3.0, (k, D))
+    noise = rng.uniform(0.2, 0.6, D)
+    lab = rng.integers(0, k, n)
+    x = centres[lab] + rng.normal(0.0, 1.0, (n, D)) * noise[None, :]
+    return x.astype(np.float32), lab.astype(np.int64)
+
+
+def real_rows(config):
+    """--real_valued: (float32 [N, D] rows, int64 [N] labels) from --data_npy / --labels_npy (labels 0 without the second
+    file), or synthetic_real(--synthetic_size, --data_dim)."""
+    path = getattr(config, "data_npy", None)
+    if not path:
+        return synthetic_real(int(getattr(config, "synthetic_size", 8192)), int(getattr(config, "data_dim", 784)))
+    x = np.ascontiguousarray(np.load(path), dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError(f"--data_npy must hold a float32 [N, D] array, got shape {x.shape}")
+    lp = getattr(config, "labels_npy", None)
+    lab = np.asarray(np.load(lp)).astype(np.int64).reshape(-1) if lp else np.zeros(x.shape[0], np.int64)
+    if lab.shape[0] != x.shape[0]:
+        raise ValueError(f"--labels_npy holds {lab.shape[0]} labels for {x.shape[0]} rows")
+    return x, lab
+
+
+def standardize_stats(x: np.ndarray):
+    """--standardize: the per-feature (mean, std) of the rows as float32 tensors [D]; a constant feature keeps std 1."""
+    mean, std = x.mean(axis=0, dtype=np.float64), x.std(axis=0, dtype=np.float64)
+    std[std == 0] = 1.0
+    return torch.from_numpy(mean.astype(np.float32)), torch.from_numpy(std.astype(np.float32))
+
+
+def _standardized(x: np.ndarray, stats) -> np.ndarray:
+    return x if stats is None else ((x - stats[0].numpy()[None, :]) / stats[1].numpy()[None, :]).astype(np.float32)
+
+
+def _real_batches(config, shuffle, repeat, device, with_index, stats):
+    x, lab = real_rows(config)
+    rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
+    a, b = parallel.shard_rows(x.shape[0], rank, world)
+    xt = torch.from_numpy(_standardized(x, stats)[a:b]).to(device)
+    labels = torch.from_numpy(lab[a:b]).to(device)
+    gen = torch.Generator(device=device)
+    gen.manual_seed((config.random_seed or 0) * 7919 + 17 + rank)
+    n, B = xt.shape[0], int(config.batch_size)
+
+    def it():
+        while True:
+            order = torch.randperm(n, device=device, generator=gen) if shuffle else torch.arange(n, device=device)
+            for s in range(0, n, B):
+                idx = order[s:s + B]
+                yield (xt[idx], labels[idx], a + s) if with_index else (xt[idx], labels[idx])
             if not repeat:
                 return
     return it()
@@ -172,6 +246,7 @@ def create_model(config, data_dim, weighted=None, temperature_on_device=None, cl
                  y_estimator=getattr(config, "y_estimator", "relaxed"))
     pmask = dict(pixel_mask=float(getattr(config, "missing_rate", 0.0) or 0.0) > 0.0)      # (--missing_rate: train AND eval)
     pmask.update(likelihood=likelihood_of(config)[0], likelihood_sigma=likelihood_of(config)[1])      # (--likelihood: likewise)
+    pmask.update(real_valued=real_valued(config), likelihood_scale=getattr(config, "likelihood_scale", "fixed") or "fixed")
     hidden = [config.hidden_size] * config.num_layers
     ns = int(getattr(config, "n_samples", 1))
     ge = getattr(config, "grad_estimator", "standard")
@@ -230,6 +305,9 @@ def _save_checkpoint(model, path: str):
     sd = model.state_dict()
     sd["likelihood"] = model._engine.likelihood
     sd["likelihood_sigma"] = torch.tensor(model._engine.likelihood_sigma, dtype=torch.float64)
+    sd["real_valued"], sd["likelihood_scale"] = model._engine.real_valued, model._engine.likelihood_scale
+    if getattr(model, "standardize", None) is not None:      # (--standardize: the train rows' per-feature mean and std)
+        sd["standardize_mean"], sd["standardize_std"] = model.standardize
     torch.save(sd, tmp)
     os.replace(tmp, path)
 
@@ -244,6 +322,12 @@ def _restore_checkpoint(model, path: str):
         raise ValueError(f"{path} was trained with --likelihood={lik}" + (f" --likelihood_sigma={sigma:g}" if lik == "gaussian" else "")
                          + f": it cannot be restored under --likelihood={eng.likelihood}"
                          + (f" --likelihood_sigma={eng.likelihood_sigma:g}" if eng.likelihood == "gaussian" else ""))
+    real, scale = bool(sd.pop("real_valued", False)), sd.pop("likelihood_scale", "fixed")
+    if real != eng.real_valued or scale != eng.likelihood_scale:
+        raise ValueError(f"{path} was trained with{'' if real else 'out'} --real_valued and --likelihood_scale={scale}: it cannot "
+                         f"be restored with{'' if eng.real_valued else 'out'} --real_valued and --likelihood_scale={eng.likelihood_scale}")
+    mean, std = sd.pop("standardize_mean", None), sd.pop("standardize_std", None)
+    model.standardize = None if mean is None else (mean, std)
     model.load_state_dict(sd)
 
 
@@ -276,12 +360,19 @@ def select_labelled(labels, per_class: int, seed: int) -> np.ndarray:
     return out
 
 
-def create_device_dataset(config, split="train", shuffle=True):
+def create_device_dataset(config, split="train", shuffle=True, standardize=None):
     """The input pipeline of scripts/runners.py:21-62 with the raw uint8 pixels resident in HBM (data.DeviceDataset):
     this rank's contiguous shard of the split's rows (+ labels), shuffled per epoch on the device; binarisation happens
     per step on the device (gmvae_binarize: inside the train graph, or as a launch in the eager loop).  Without local
-    MNIST files a synthetic set of intensity 33/255 (P[x = 1] = 0.87 after the reference's inverted rule) stands in."""
+    MNIST files a synthetic set of intensity 33/255 (P[x = 1] = 0.87 after the reference's inverted rule) stands in.
+    --real_valued: the float32 rows of real_rows (standardize = the (mean, std) to apply), resident as they are."""
     from .data import DeviceDataset
+    if real_valued(config):
+        x, lab = real_rows(config)
+        rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
+        a, b = parallel.shard_rows(x.shape[0], rank, world)
+        return DeviceDataset(_standardized(x, standardize)[a:b], lab[a:b], shuffle=shuffle,
+                             seed=(config.random_seed or 0) * 7919 + 17 + rank, binarize=False)
     data = _load_mnist(getattr(config, "data_dir", "") or "", split) if getattr(config, "data_dir", None) else None
     rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
     if data is None:
@@ -366,7 +457,9 @@ def run_train(config):
         if rank == 0:
             print(f"restored {_ckpt(config)} at step {eng.global_step}")
     eng.sync_replicas()            # default --random_seed=None: every process drew its own init; rank 0's wins
-    ds = create_device_dataset(config, "train", shuffle=True)
+    if real_valued(config) and getattr(config, "standardize", False) and getattr(model, "standardize", None) is None:
+        model.standardize = standardize_stats(real_rows(config)[0])      # (a restored checkpoint keeps its own)
+    ds = create_device_dataset(config, "train", shuffle=True, standardize=getattr(model, "standardize", None))
     B, lr, every = int(config.batch_size), float(config.learning_rate), int(config.summarise_every)
     eager = bool(getattr(config, "eager", False)) or os.environ.get("GMVAE_EAGER_TRAIN") == "1"
     bseed = eng.noise_seed ^ Engine.BINARIZE_SEED_XOR
@@ -388,7 +481,7 @@ def run_train(config):
     tags = [inp.tag for inp in STEP_INPUTS if inp.option in inputs]
     grey = eng.likelihood != "bernoulli"                    # grey batches are gathered, never binarised: capture_train_step's branch
     if grey:
-        tags = tags + ["grey"]
+        tags = tags + ["real" if eng.real_valued else "grey"]
     run_train.last_path = ("eager" if eager else "dp-graph" if world > 1 else f"graph+{tags[0]}" if tags else "pipeline-graph")
     run_train.temperature_log = []                          # temperature on the device: (0-based step index, temperature) of the
                                                             # LAST launch's steps, as placed in replay.y_temperature
@@ -606,7 +699,9 @@ def run_eval(config):
     py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
     # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
     pc_n, pc_rows, pc_stats = int(getattr(config, "component_posterior_samples", 0) or 0), [], []
-    for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True):
+    q_logits = []                                           # --real_valued, gmvae: q(y|x)'s logits over the split, for cluster_acc_q
+    for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
+                                                standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
             po = eng.posterior_component(images, pc_n, chunk=iw_chunk, row0=first)
             pc_rows.append(po["log_post"])
@@ -640,6 +735,8 @@ def run_eval(config):
             class_hits[1] += labels.numel()
         if py_n > 0:
             py_logits.append(o["logits"])
+        if eng.real_valued and config.model == "gmvae":
+            q_logits.append(o["logits"])
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
@@ -671,6 +768,12 @@ def run_eval(config):
     if eng.likelihood != "bernoulli":
         # the per-pixel squared error of the mean image A'(lambda) against t = pixel / 255 (tail[5] / tail[6] over the split)
         res[f"{config.split}/recon_mse"] = pm_tot[0].item() / max(pm_tot[1].item(), 1.0)
+    if eng.likelihood_scale == "learned":
+        res[f"{config.split}/sigma_mean"] = torch.exp(eng.views()["decoder/log_sigma"]).mean().item()
+    if q_logits:
+        # clustering accuracy of q(y|x) over the WHOLE split, components matched to labels by majority (utils.cluster_acc)
+        res[f"{config.split}/cluster_acc_q"] = utils.cluster_acc(torch.cat(q_logits), torch.cat(labs), int(config.mixture_components),
+                                                                 all_reduce=True).item()
     if iw_n > 0:
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:

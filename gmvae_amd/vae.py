@@ -111,6 +111,8 @@ class TrainableVAE(VAE):
             out["observed_share"] = t[7] / (t[6] + t[7])
         if e.likelihood != "bernoulli":            # (the per-pixel squared error of the mean image A'(lambda) against t = x / 255)
             out["recon_mse"] = t[5] / t[6]
+        if e.likelihood_scale == "learned":        # (the mean of the learned per-dimension scales sigma_d = exp(rho_d))
+            out["sigma_mean"] = torch.exp(e.views()["decoder/log_sigma"]).mean()
         if e.clip_norm is not None:                # (of the last eager optimizer step: the norm before clipping, clipped 0 / 1)
             out["grad_norm"], out["clipped"] = e.grad_clip[0], e.grad_clip[2]
         return out
@@ -129,7 +131,8 @@ class TrainableVAE(VAE):
 def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=None,
                hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                random_seed=None, n_samples=1, grad_estimator="standard", weighted_objective=False, kl_weight=1.0,
-               y_weight=1.0, y_free_nats=0.0, pixel_mask=False, clip_norm=None, likelihood="bernoulli", likelihood_sigma=1.0):
+               y_weight=1.0, y_free_nats=0.0, pixel_mask=False, clip_norm=None, likelihood="bernoulli", likelihood_sigma=1.0,
+               real_valued=False, likelihood_scale="fixed"):
     """Factory with the signature of scripts/vae.py:191-200 (+ pixel_mask: run_model / compute_loss / iw_bound take mask=,
     Engine; + n_samples, the
     IWAE extension of SURVEY.md A15; 1 == the reference; + grad_estimator: "dreg" = the doubly
@@ -137,7 +140,8 @@ def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=
     Engine's weighted objective -- the VAE family has no y term, so y_weight and y_free_nats are ignored; + clip_norm: the
     gradient clipped by its global norm in front of Adam, Engine; summaries then carry grad_norm and clipped; + likelihood,
     likelihood_sigma: "grey_bernoulli", "continuous_bernoulli" or "gaussian" on grey levels t = x / 255, Engine; the decoder
-    then returns that distribution, reconstruct_images its mean, and summaries carry recon_mse)."""
+    then returns that distribution, reconstruct_images its mean, and summaries carry recon_mse; + real_valued,
+    likelihood_scale: float feature rows under the Gaussian, with a fixed or a learned per-dimension scale, Engine)."""
     if fcnet_hidden_sizes is None:
         fcnet_hidden_sizes = [latent_size]                     # scripts/vae.py:228-229
     name = "vae_gmp" if mixture_components > 1 else "vae"
@@ -145,7 +149,8 @@ def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=
                     sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, gen_bias_init=gen_bias_init,
                     random_seed=random_seed, hidden_act=base.activation_name(hidden_activation_fn),
                     grad_estimator=grad_estimator, weighted_objective=weighted_objective, kl_weight=kl_weight,
-                    y_weight=y_weight, y_free_nats=y_free_nats, pixel_mask=pixel_mask, clip_norm=clip_norm, likelihood=likelihood, likelihood_sigma=likelihood_sigma)
+                    y_weight=y_weight, y_free_nats=y_free_nats, pixel_mask=pixel_mask, clip_norm=clip_norm, likelihood=likelihood, likelihood_sigma=likelihood_sigma,
+                    real_valued=real_valued, likelihood_scale=likelihood_scale)
     if mixture_components > 1:
         def prior():
             v = engine.views()

@@ -24,7 +24,7 @@
  *     which waits no longer block; re-zero the workspace to clear it);
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*), is
  *     asynchronous and graph-capturable; no global state;
- *   - all float tensors are fp32 row-major; x is uint8/bool {0,1} [B,D] (uint8 grey levels 0..255 under GMVAE_LIK_*);
+ *   - all float tensors are fp32 row-major; x is uint8/bool {0,1} [B,D] (uint8 grey levels 0..255 under GMVAE_LIK_*; float [B,D] under GMVAE_X_F32);
  *   - sample-dependent tensors have R = B*S rows, row r = b*S + s.
  */
 #ifndef GMVAE_HIP_H_
@@ -380,7 +380,28 @@ enum { GMVAE_SCHED_SAFE = 1,
        GMVAE_LIK_GREY_BERNOULLI = 1 << 11,
        GMVAE_LIK_CONT_BERNOULLI = 2 << 11,
        GMVAE_LIK_GAUSSIAN = 3 << 11,
-       GMVAE_LIK_MASK = 3 << 11 };
+       GMVAE_LIK_MASK = 3 << 11,
+       /* real-valued data: x points to float [B][D], any finite values, NOT bytes.  The parameter keeps its type
+        * (const uint8_t* x) and the library reinterprets it as const float*; the pointer must be 16-byte aligned
+        * (GMVAE_E_ALIGN), and step s of a train graph reads the floats at x + s B D.  Requires GMVAE_LIK_GAUSSIAN (GMVAE_E_DIMS
+        * with any other value of the field): t_bd = x_bd itself.  The networks' first layers and their weight gradients take x
+        * as the fp32 operand -- no t pass, no t region in the workspace --, and the likelihood epilogue reads its target as a
+        * float on every tile path (interior, last column tile, element by element where D % 4 != 0 or a row is unaligned).
+        * tail[5] and tail[6] stay the squared error and B D.  "general+gauss+f32". */
+       GMVAE_X_F32 = 1 << 13,
+       /* the Gaussian's scale per dimension and learned: sigma_d = exp(rho_d), rho = "decoder/log_sigma" [1, D], the LAST entry
+        * of the parameter layout (gmvae_param_count / gmvae_param_layout report it under this bit alone; P_padded grows by D
+        * rounded up to 4; without the bit the layout is unchanged).  Requires GMVAE_LIK_GAUSSIAN (GMVAE_E_DIMS otherwise); byte
+        * or fp32 input.  The "lik_sigma" cell is absent (GMVAE_E_NET).
+        *   log p(t_bd | lambda_rd) = -(lambda_rd - t_bd)^2 / (2 sigma_d^2) - rho_d - ln(2 pi) / 2
+        *   g_rd = (lambda_rd - t_bd) / sigma_d^2                  (the epilogue loads rho per column quad, as the bias)
+        *   d loss / d rho_d = sum_r rw_r (1 - sigma_d^2 g_rd^2)   (rw: the backward's row weights, 1 where the step has none)
+        * The last line is a launch pair of its own behind the backward's row weights (liksig.hpp): a row-weighted column
+        * reduction over the stored g [R][D], fixed order, no atomics, then the slab partials summed in index order into the
+        * gradient buffer's slabs -- a SUM like every other entry, so TF-Adam, GMVAE_OPT_CLIP_NORM, the data-parallel all-reduce
+        * and checkpoints treat rho as any other parameter.  "general+gauss+lsig", "general+gauss+f32+lsig+clip".
+        * Both bits: honoured and refused exactly where GMVAE_LIK_GAUSSIAN is (above). */
+       GMVAE_LIK_SCALE_LEARNED = 1 << 14 };
 #define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) / masks (GMVAE_OBJ_PIXEL_MASK) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
@@ -706,7 +727,7 @@ int gmvae_dp_graph_create(const GmvaeDims* dims, int model, const uint8_t* x, in
                           float beta2, float epsilon, void* comm, float* tail_log, void** graph_out);
 
 /* Debugging aid: byte offset inside the workspace of a named intermediate ("hy1","hg1","hd1","y",
- * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "clip_norm" and "grad_clip" under GMVAE_OPT_CLIP_NORM; "lik_sigma" under GMVAE_LIK_GAUSSIAN; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
+ * "logits","qp","pp","z","g","dqp","dpp","dlogits","dbuf0".."dbuf2","s1","s4", ...; "labels" and "sup_weight" under GMVAE_OBJ_LABELS; "obj_weights", "rwk" and "y_floor" under GMVAE_OBJ_WEIGHTS; "y_temperature" under GMVAE_Y_TEMP_DEV; "y_soft" under GMVAE_Y_STRAIGHT_THROUGH; "pixel_mask" under GMVAE_OBJ_PIXEL_MASK; "clip_norm" and "grad_clip" under GMVAE_OPT_CLIP_NORM; "lik_sigma" under GMVAE_LIK_GAUSSIAN without GMVAE_LIK_SCALE_LEARNED; "he<i>" / "hg<i>" / "hd<i>", i >= 1:
  * the kept input activation of layer i of the encoder (encoder_y for GMVAE) / encoder_gmm / decoder -- the parity
  * tests read the ReLU masks of a step from them). */
 int gmvae_workspace_offset(const GmvaeDims* dims, int model, const char* name, uint64_t* byte_offset);
@@ -721,7 +742,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+grey" / "+cb" / "+gauss" under GMVAE_LIK_*, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+grey" / "+cb" / "+gauss" under GMVAE_LIK_*, "+f32" under GMVAE_X_F32, "+lsig" under GMVAE_LIK_SCALE_LEARNED, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
