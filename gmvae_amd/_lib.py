@@ -47,7 +47,7 @@ def _load():
             f"{LIB_PATH} is missing: the HIP extension has not been built. "
             "Run `python build_hip.py` (or __graft_entry__.build()). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    vp, u64, i32, f32 = C.c_void_p, C.c_uint64, C.c_int, C.c_float
+    vp, u64, i64, i32, f32 = C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_float
     dp = C.POINTER(GmvaeDims)
     sigs = {
         "gmvae_abi_version": ([], i32),
@@ -64,6 +64,9 @@ def _load():
         "gmvae_posterior_y": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "gmvae_posterior_component_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
         "gmvae_posterior_component": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
+        "gmvae_mixture_logpdf_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
+        "gmvae_mixture_logpdf_accumulate": ([vp, i64, i32, vp, vp, vp, i64, i64, i64, vp, i32, vp, vp], i32),
+        "gmvae_mixture_logpdf_finish": ([i64, i32, i32, C.c_double, vp, vp, vp, vp, vp], i32),
         "adam_tf_step": ([vp, vp, vp, vp, u64, f32, f32, f32, f32, u64, vp, f32, vp, vp, vp], i32),
         "gmvae_grad_clip_scratch_bytes": ([u64, C.POINTER(u64)], i32),
         "gmvae_grad_clip": ([vp, u64, vp, vp, vp, vp], i32),

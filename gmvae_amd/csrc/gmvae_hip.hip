@@ -42,6 +42,7 @@
 #include "lik.hpp"
 #include "liksig.hpp"
 #include "gclip.hpp"
+#include "aggpost.hpp"
 
 using namespace gmvae;
 
@@ -3300,6 +3301,71 @@ int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x
                               uint64_t seed, uint64_t step, void* stream) {
   return iw_run(IW_POSTERIOR_COMPONENT, dims, model, x, params, n_samples, {log_joint_out, log_post_out, stats_out}, tail,
                 workspace, seed, step, stream);
+}
+
+// gmvae_mixture_logpdf_*: csrc/aggpost.hpp.  Workspace: the running states [E], E = ap_states(M, L, per_dim), then the slices'
+// partial states (ap_part_states), 16 bytes each; checks in the order dims, NULL, alignment, all before any launch.
+static int ap_check_sizes(int64_t M, int L) {
+  return (M < 1 || L < 1 || M > (1ll << 30) || L > (1 << 16)) ? GMVAE_E_DIMS : 0;
+}
+static int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int gmvae_mixture_logpdf_workspace_bytes(int64_t M, int L, int per_dim, uint64_t* bytes) {
+  if (int e = ap_check_sizes(M, L)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  const uint64_t E = ap_states(M, L, per_dim);
+  *bytes = ((E + ap_part_states(M, L, per_dim)) * sizeof(ApState) + 255) / 256 * 256;
+  return 0;
+}
+
+int gmvae_mixture_logpdf_accumulate(const float* z, int64_t M, int L, const float* mu, const float* sigma, const float* logw,
+                                    int64_t C, int64_t c_first, int64_t comps_per_owner, const int64_t* query_owner, int per_dim,
+                                    void* workspace, void* stream) {
+  if (int e = ap_check_sizes(M, L)) return e;
+  if (C < 1 || C > (1ll << 30) || c_first < 0 || (query_owner && comps_per_owner < 1)) return GMVAE_E_DIMS;
+  if (!z || !mu || !sigma || !logw || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(z, 4) || !aligned_to(mu, 4) || !aligned_to(sigma, 4) || !aligned_to(logw, 4) ||
+      (query_owner && !aligned_to(query_owner, 8)) || !aligned16(workspace))
+    return GMVAE_E_ALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the joint kernel and the per-dimension kernel split the chunk into slices of their own (ap_slices at per_dim 0 and 1)
+  const ApSplit sj = ap_split(C, ap_slices(M, L, 0)), sd = ap_split(C, ap_slices(M, L, 1));
+  const uint64_t E = ap_states(M, L, per_dim);
+  ApState* const run = static_cast<ApState*>(workspace);
+  ApState* const part = run + E;
+  const unsigned qt = (unsigned)((M + kApBlock - 1) / kApBlock);
+  (void)hipGetLastError();
+  // the partial states of the slices in use: joint [sj.used][M], own [sj.used][M], per dimension [sd.used][M L]
+  ApState* const pj = part;
+  ApState* const po = part + (uint64_t)sj.used * M;
+  ApState* const pd = part + (uint64_t)sj.used * 2 * M;
+  hipLaunchKernelGGL(aggpost_joint, dim3(qt, (unsigned)sj.used), dim3(kApBlock), 0, st, z, (int)M, L, mu, sigma, logw, (int)C,
+                     (long long)c_first, (long long)comps_per_owner, reinterpret_cast<const long long*>(query_owner), sj.per_slice,
+                     pj, po);
+  hipLaunchKernelGGL(aggpost_fold, dim3(qt), dim3(kApBlock), 0, st, run, pj, (unsigned long long)M, sj.used);
+  if (query_owner) hipLaunchKernelGGL(aggpost_fold, dim3(qt), dim3(kApBlock), 0, st, run + M, po, (unsigned long long)M, sj.used);
+  if (per_dim) {
+    const uint64_t ML = (uint64_t)M * (uint64_t)L;
+    hipLaunchKernelGGL(aggpost_dim, dim3(qt, (unsigned)sd.used, (unsigned)((L + kApDimDims - 1) / kApDimDims)), dim3(kApBlock), 0, st,
+                       z, (int)M, L, mu, sigma, logw, (int)C, sd.per_slice, pd);
+    hipLaunchKernelGGL(aggpost_fold, dim3((unsigned)((ML + kApBlock - 1) / kApBlock)), dim3(kApBlock), 0, st, run + 2 * (uint64_t)M,
+                       pd, (unsigned long long)ML, sd.used);
+  }
+  return (int)hipGetLastError();
+}
+
+int gmvae_mixture_logpdf_finish(int64_t M, int L, int per_dim, double log_norm, float* log_joint_out, float* log_dim_out,
+                                float* log_own_out, const void* workspace, void* stream) {
+  if (int e = ap_check_sizes(M, L)) return e;
+  if (!workspace) return GMVAE_E_NULL;
+  if (!aligned_to(log_joint_out, 4) || !aligned_to(log_dim_out, 4) || !aligned_to(log_own_out, 4) || !aligned16(workspace))
+    return GMVAE_E_ALIGN;
+  const uint64_t E = ap_states(M, L, per_dim);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(aggpost_finish, dim3((unsigned)((E + kApBlock - 1) / kApBlock)), dim3(kApBlock), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const ApState*>(workspace), (unsigned long long)M,
+                     (unsigned long long)E, log_norm, log_joint_out, log_own_out, per_dim ? log_dim_out : nullptr);
+  return (int)hipGetLastError();
 }
 
 int adam_tf_step(float* params, float* m, float* v, const float* grads, uint64_t P, float lr, float beta1,

@@ -842,6 +842,148 @@ class Engine:
         return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_post_prior=stats[:, 2],
                     ess=stats[:, 3], tail=tail)
 
+    AGG_CHUNK = 2048               # default examples per pass of aggregate_posterior (K rows each for the GMVAE)
+
+    def _normal_head(self, out: torch.Tensor):
+        """(mu, sigma) of a conditional normal's MLP output [rows, 2 L]: sigma = max(softplus(raw + raw_sigma_bias), sigma_min)
+        (scripts/base.py:66-72)."""
+        mu, raw = out[:, :self.Lz], out[:, self.Lz:]
+        sigma = torch.nn.functional.softplus(raw + self.hp["raw_sigma_bias"]).clamp_min(self.hp["sigma_min"])
+        return mu.contiguous(), sigma.contiguous()
+
+    def _latent_components(self, xb: torch.Tensor):
+        """q(z | x) of a batch as mixture components, example-major: (log pi [n, Kc], mu [n Kc, L], sigma [n Kc, L]) with Kc = K
+        for the GMVAE -- pi = softmax(encoder_y(x)), (mu, sigma) = encoder_gmm(x, one-hot k), the convention of iw_bound_enum_y
+        and posterior_y whatever the engine's y_inference -- and Kc = 1, log pi = 0 for the VAE family."""
+        n = xb.shape[0]
+        if self.model != L.MODEL_GMVAE:
+            mu, sigma = self._normal_head(self.mlp(L.NET_ENCODER, xb))
+            return torch.zeros(n, 1, dtype=torch.float32, device=self.device), mu, sigma
+        logpi = torch.log_softmax(self.mlp(L.NET_ENCODER_Y, xb), dim=1)
+        onehot = torch.eye(self.K, dtype=torch.float32, device=self.device).repeat(n, 1)
+        mu, sigma = self._normal_head(self.mlp(L.NET_ENCODER_GMM, xb.repeat_interleave(self.K, dim=0), onehot))
+        return logpi.contiguous(), mu, sigma
+
+    def _mixture_logpdf(self, ws, z, mu, sigma, logw, c_first=0, comps_per_owner=1, owner=None, per_dim=True):
+        """One chunk of components folded into the workspace's running state (include/gmvae_hip.h
+        gmvae_mixture_logpdf_accumulate)."""
+        rc = L.lib.gmvae_mixture_logpdf_accumulate(L.ptr(z), z.shape[0], self.Lz, L.ptr(mu), L.ptr(sigma), L.ptr(logw),
+                                                   mu.shape[0], int(c_first), int(comps_per_owner), L.ptr(owner), int(per_dim),
+                                                   L.ptr(ws), L.current_stream())
+        L.check(rc, "gmvae_mixture_logpdf_accumulate")
+
+    def _mixture_finish(self, ws, M, per_dim, log_norm, own):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        joint = torch.empty(M, **f32)
+        dim = torch.empty(M, self.Lz, **f32) if per_dim else None
+        lown = torch.empty(M, **f32) if own else None
+        rc = L.lib.gmvae_mixture_logpdf_finish(M, self.Lz, int(per_dim), float(log_norm), L.ptr(joint), L.ptr(dim), L.ptr(lown),
+                                               L.ptr(ws), L.current_stream())
+        L.check(rc, "gmvae_mixture_logpdf_finish")
+        return joint, dim, lown
+
+    @torch.no_grad()
+    def aggregate_posterior(self, x, queries: Optional[torch.Tensor] = None, per_dim: bool = True, chunk: Optional[int] = None,
+                            row0: Optional[int] = None):
+        """Diagnostics of the aggregate posterior q(z) = 1/N sum_n q(z | x_n) over the examples x [N, D] (Hoffman & Johnson 2016;
+        Chen et al. 2018): E_x KL(q(z|x) || p(z)) = I_q(x; z) + KL(q(z) || p(z)), and KL(q(z) || p(z)) = TC(q(z)) + sum_d
+        KL(q(z_d) || p(z_d)) (+ a rest for a mixture prior).  All three models; for the GMVAE q(z | x) = sum_k pi_k(x) N(mu_k(x),
+        sigma_k(x)) with the one-hot y of iw_bound_enum_y and posterior_y, whatever the engine's y_inference.
+        queries: None -- every example -- or an int tensor [M] of indices into x; one sample z_m ~ q(z | x_queries[m]) each (GMVAE:
+        k by Gumbel-max on log pi + g, then z = mu_k + sigma_k eps), the noise being gmvae_noise_fill's rows row0 + m keyed by
+        (noise_seed, global_step), row0 defaulting to rank * M.  Every log-density is a logsumexp over all N (N K) components in
+        the HIP evaluator gmvae_mixture_logpdf_* (include/gmvae_hip.h), streamed `chunk` examples at a time (default AGG_CHUNK):
+        the memory depends on chunk and M, not on N, and the result does not depend on chunk beyond fp64 fold order.
+        Returns a dict.  Per query: z [M, L], log_q_zx [M] = log q(z | x_own), log_q_z [M] = log q(z) (log N subtracted), log_q_zd
+        [M, L] = log q(z_d), log_p_z [M], log_p_zd [M, L] (the prior and its marginals: closed form for the VAE, the same kernel
+        over the K components of the VAE_GMP's mixture and of the GMVAE's 1/K sum_k prior_gmm(e_k)).  Means over the queries, 0-d
+        fp64 device tensors: kl_avg = mean(log_q_zx - log_p_z), mi = mean(log_q_zx - log_q_z) (<= ln N), kl_marginal =
+        mean(log_q_z - log_p_z), tc = mean(log_q_z - sum_d log_q_zd), dim_kl [L] = mean(log_q_zd - log_p_zd).  From the encoder
+        alone: au_variance [L] = the variance over the N examples of E[z_d | x] = sum_k pi_k mu_kd and active_units = the count
+        above 0.01 (Burda et al. 2016); GMVAE: q_y [K] = mean_n pi_n, q_y_entropy = H(q_y), mi_xy = H(q_y) - mean_n H(pi_n) (None
+        for the VAE family).  per_dim=False skips the per-dimension terms (L times the exponentials): log_q_zd, log_p_zd, tc and
+        dim_kl are None.  Not with pixel_mask=True (the encoders here take no mask).  One device: across ranks each rank
+        reports its own shard's aggregate posterior."""
+        if self.pixel_mask:
+            raise ValueError("aggregate_posterior is not available with pixel_mask=True (Engine.mlp encodes x without a mask)")
+        x = self._prep_x(x)
+        N, Lz, gm = x.shape[0], self.Lz, self.model == L.MODEL_GMVAE
+        Kc = self.K if gm else 1
+        if N < 1:
+            raise ValueError("aggregate_posterior needs at least one example")
+        chunk = self.AGG_CHUNK if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if queries is None:
+            qidx = torch.arange(N, dtype=torch.int64, device=self.device)
+        else:
+            qidx = torch.as_tensor(queries).to(self.device, torch.int64).reshape(-1).contiguous()
+            if qidx.numel() < 1 or int(qidx.min()) < 0 or int(qidx.max()) >= N:
+                raise ValueError(f"queries must be a non-empty tensor of indices into the {N} examples")
+        M = qidx.numel()
+        row0 = self.rank * M if row0 is None else int(row0)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        # one sample per query
+        eps = torch.empty(M, Lz, **f32)
+        u = torch.empty(M, self.K, **f32) if gm else None
+        L.check(L.lib.gmvae_noise_fill(L.ptr(eps), L.ptr(u), M, Lz, self.K, row0, self.noise_seed, self.global_step, None,
+                                       L.current_stream()), "gmvae_noise_fill")
+        z = torch.empty(M, Lz, **f32)
+        for m0 in range(0, M, chunk):
+            sl = slice(m0, min(M, m0 + chunk))
+            logpi, mu, sigma = self._latent_components(x[qidx[sl]])
+            rows = torch.arange(logpi.shape[0], device=self.device) * Kc
+            if gm:
+                rows = rows + (logpi.double() - torch.log(-torch.log(u[sl].double()))).argmax(dim=1)
+            z[sl] = mu[rows] + sigma[rows] * eps[sl]
+        # the aggregate posterior: every example's components through the evaluator, and the encoder-only statistics
+        nb = C.c_uint64()
+        L.check(L.lib.gmvae_mixture_logpdf_workspace_bytes(M, Lz, int(per_dim), C.byref(nb)), "gmvae_mixture_logpdf_workspace_bytes")
+        ws = torch.zeros(nb.value // 8, **f64)
+        ez_sum, ez_sq = torch.zeros(Lz, **f64), torch.zeros(Lz, **f64)
+        pi_sum, hy_sum = torch.zeros(Kc, **f64), torch.zeros((), **f64)
+        for n0 in range(0, N, chunk):
+            logpi, mu, sigma = self._latent_components(x[n0:n0 + chunk])
+            self._mixture_logpdf(ws, z, mu, sigma, logpi.reshape(-1), n0 * Kc, Kc, qidx, per_dim)
+            pi = logpi.double().exp()
+            ez = (pi.unsqueeze(2) * mu.double().view(-1, Kc, Lz)).sum(dim=1)
+            ez_sum += ez.sum(dim=0)
+            ez_sq += (ez * ez).sum(dim=0)
+            pi_sum += pi.sum(dim=0)
+            hy_sum -= (pi * logpi.double().clamp_min(-745.0)).sum()
+        log_q_z, log_q_zd, log_q_zx = self._mixture_finish(ws, M, per_dim, math.log(N), True)
+        # the prior
+        if self.model == L.MODEL_VAE:
+            t = -0.5 * z * z - 0.5 * math.log(2.0 * math.pi)
+            log_p_z, log_p_zd = t.double().sum(dim=1).float(), (t if per_dim else None)
+        else:
+            if gm:
+                eye = torch.eye(self.K, **f32)
+                pmu, psig = self._normal_head(self.mlp(L.NET_PRIOR_GMM, eye))
+                plogw = torch.full((self.K,), -math.log(self.K), **f32)
+            else:
+                v = self.views()
+                pmu = v["loc"].contiguous()
+                psig = torch.nn.functional.softplus(v["raw_scale_diag"]).contiguous()
+                plogw = torch.log_softmax(v["mixture_logits"], dim=0).contiguous()
+            ws.zero_()
+            self._mixture_logpdf(ws, z, pmu, psig, plogw, per_dim=per_dim)
+            log_p_z, log_p_zd, _ = self._mixture_finish(ws, M, per_dim, 0.0, False)
+        own, agg, pri = log_q_zx.double(), log_q_z.double(), log_p_z.double()
+        ez_mean = ez_sum / N
+        au_var = (ez_sq / N - ez_mean * ez_mean).clamp_min(0.0)
+        out = dict(z=z, log_q_zx=log_q_zx, log_q_z=log_q_z, log_q_zd=log_q_zd, log_p_z=log_p_z, log_p_zd=log_p_zd,
+                   kl_avg=(own - pri).mean(), mi=(own - agg).mean(), kl_marginal=(agg - pri).mean(),
+                   tc=(agg - log_q_zd.double().sum(dim=1)).mean() if per_dim else None,
+                   dim_kl=(log_q_zd.double() - log_p_zd.double()).mean(dim=0) if per_dim else None,
+                   au_variance=au_var, active_units=(au_var > 0.01).sum(), q_y=None, q_y_entropy=None, mi_xy=None)
+        if gm:
+            q_y = pi_sum / N
+            h_qy = -(q_y * q_y.clamp_min(1e-300).log()).sum()
+            out.update(q_y=q_y, q_y_entropy=h_qy, mi_xy=h_qy - hy_sum / N)
+        return out
+
     def mlp(self, net: int, inp: torch.Tensor, in2: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One conditional network's MLP on the device (snt.nets.MLP, scripts/base.py:47-60)."""
         if self.real_valued and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):

@@ -118,6 +118,11 @@ class TrainableGMVAE(GMVAE):
         samples of z per component, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_y)."""
         return self._need_engine().posterior_y(images, n_samples, chunk)["log_post"]
 
+    def latent_diagnostics(self, images, queries=None, per_dim=True):
+        """The aggregate posterior's diagnostics over `images` (Engine.aggregate_posterior): the dict of per-query log-densities
+        and of kl_avg = mi + kl_marginal, tc, dim_kl, active_units, q_y, q_y_entropy and mi_xy."""
+        return self._need_engine().aggregate_posterior(images, queries=queries, per_dim=per_dim)
+
     def predict_clusters(self, images, n_samples=None):
         """The component the model's posterior p(y | x) assigns each example to: an int64 [B] device tensor.  A model on
         real-valued rows (real_valued=True), whose likelihood the enumerating evaluators refuse, assigns by the inference

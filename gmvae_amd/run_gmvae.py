@@ -48,6 +48,9 @@ def build_parser():
       "p(k|x) over the components of its mixture prior by importance sampling at this many samples per example "
       "(Engine.posterior_component) -- its clustering accuracy, its entropy, KL(p(k|x) || pi) and the effective sample size; "
       "0 = off")
+    a("--latent_diagnostics", type=int, default=0, help="eval: also report the aggregate posterior's diagnostics over the first "
+      "N examples of the split (Engine.aggregate_posterior) -- the mutual information I(x; z), KL(q(z) || p(z)), the total "
+      "correlation of q(z), their sum kl_avg, the active units, and for gmvae I(x; y) and the entropy of q(y); 0 = off")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -110,6 +113,13 @@ def check_args(p, cfg):
             p.error("--component_posterior_samples is the posterior over the VAE's mixture prior: it needs --model=vae_gmp")
         if cfg.mode != "eval":
             p.error("--component_posterior_samples needs --mode=eval")
+    if cfg.latent_diagnostics < 0:
+        p.error("--latent_diagnostics must be >= 0 (0 = off)")
+    if cfg.latent_diagnostics:
+        if cfg.mode != "eval":
+            p.error("--latent_diagnostics needs --mode=eval")
+        if cfg.missing_rate > 0:
+            p.error("--latent_diagnostics is not available with --missing_rate (the encoders it runs take no mask)")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

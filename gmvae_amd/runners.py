@@ -700,6 +700,8 @@ def run_eval(config):
     # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
     pc_n, pc_rows, pc_stats = int(getattr(config, "component_posterior_samples", 0) or 0), [], []
     q_logits = []                                           # --real_valued, gmvae: q(y|x)'s logits over the split, for cluster_acc_q
+    # --latent_diagnostics N: the first N examples of the split, as the aggregate posterior's components and as its queries
+    ld_n, ld_imgs = int(getattr(config, "latent_diagnostics", 0) or 0), []
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -710,6 +712,8 @@ def run_eval(config):
             po = eng.posterior_y(images, py_n, chunk=iw_chunk, row0=first)
             py_rows.append(po["log_post"])
             py_stats.append(torch.stack([po["bound"], po["entropy"], po["kl_q_post"], po["ess"]], dim=1))
+        if first < ld_n:
+            ld_imgs.append(images[:ld_n - first])
         mk = None if pmask_all is None else pmask_all[first:first + images.shape[0]]
         if iw_n > 0:
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
@@ -794,6 +798,14 @@ def run_eval(config):
         res[f"{config.split}/posterior_entropy_{pc_n}_per_example"] = pc_tot[1].item() / n
         res[f"{config.split}/kl_posterior_prior_{pc_n}_per_example"] = pc_tot[2].item() / n
         res[f"{config.split}/ess_{pc_n}_per_example"] = pc_tot[3].item() / n
+    if ld_imgs:
+        # the decomposition of kl_div_z over this rank's first N examples (Engine.aggregate_posterior): E_x KL(q(z|x) || p(z)) =
+        # kl_avg = mi_xz + kl_marginal, the total correlation of q(z), the dimensions in use; GMVAE: what q(y|x) says about x
+        ld = eng.aggregate_posterior(torch.cat(ld_imgs))
+        for key, name in (("mi", "mi_xz"), ("kl_marginal", "kl_marginal"), ("tc", "total_correlation"), ("kl_avg", "kl_avg"),
+                          ("active_units", "active_units"), ("mi_xy", "mi_xy"), ("q_y_entropy", "q_y_entropy")):
+            if ld[key] is not None:
+                res[f"{config.split}/{name}"] = ld[key].item()
     if rank == 0:
         for k, v in res.items():
             print(f"{k}: {v}")

@@ -93,6 +93,11 @@ class TrainableVAE(VAE):
         n_samples samples of z, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_component)."""
         return self._need_engine().posterior_component(images, n_samples, chunk)["log_post"]
 
+    def latent_diagnostics(self, images, queries=None, per_dim=True):
+        """The aggregate posterior's diagnostics over `images` (Engine.aggregate_posterior): the dict of per-query log-densities
+        and of kl_avg = mi + kl_marginal, tc, dim_kl, active_units."""
+        return self._need_engine().aggregate_posterior(images, queries=queries, per_dim=per_dim)
+
     def predict_clusters(self, images, n_samples):
         """The component the model's posterior p(k | x) assigns each example to: an int64 [B] device tensor."""
         return self.posterior_component(images, n_samples).argmax(dim=1)

@@ -569,6 +569,38 @@ int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x
                               float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace,
                               uint64_t seed, uint64_t step, void* stream);
 
+/* The log-density of a weighted diagonal-Gaussian mixture at M query points, streamed over chunks of components (model
+ * independent; Engine.aggregate_posterior runs the aggregate posterior q(z) = 1/N sum_n q(z|x_n) and the mixture priors through
+ * it).  Components c < C of a chunk: logw [C] (finite or -inf: a -inf component contributes nothing and yields no NaN), mu [C][L],
+ * sigma [C][L]; queries z [M][L]; all fp32 in device memory.  PRECONDITION: sigma > 0 (as the step's own -log q terms assume;
+ * nothing clamps it here).  Per query m, over the components of every chunk accumulated since the workspace was zeroed:
+ *   log_joint [m]  = logsumexp_c (logw_c + sum_d log N(z_md; mu_cd, sigma_cd)) - log_norm
+ *   log_dim [m][d] = logsumexp_c (logw_c + log N(z_md; mu_cd, sigma_cd)) - log_norm     (per_dim != 0 only: it is L times the
+ *                    exponentials, and a call with per_dim == 0 launches none of it)
+ *   log_own [m]    = the logsumexp of log_joint restricted to the components of the query's own example, no log_norm subtracted
+ *                    (query_owner != NULL only).  Components are laid out example-major: global component c_first + c belongs to
+ *                    example (c_first + c) / comps_per_owner, and query_owner [M] (int64) names each query's example.  It comes
+ *                    from the same fp32 terms as log_joint, so log q(z|x) - log q(z) carries no rounding of its own.
+ * gmvae_mixture_logpdf_accumulate folds one chunk into the running state of the M queries (c_first: the global index of the
+ * chunk's first component); gmvae_mixture_logpdf_finish writes the outputs (each may be NULL; log_dim_out is ignored at
+ * per_dim == 0; a state no component has reached gives -inf).  M, L and per_dim must be the same in the size query, in every
+ * accumulate and in finish: they fix the workspace's layout.
+ * The workspace (gmvae_mixture_logpdf_workspace_bytes; a ZEROED workspace is the empty state, so zero it before the first chunk
+ * of every evaluation) holds an fp64 (max, sum of exp(. - max)) per query, per own and per (query, dimension), and as many again
+ * per slice of a chunk: memory grows with M (and M L under per_dim), never with the number of components.  A sum of 0 marks an
+ * empty state, so log-densities of -1e4 to -1e7 (far components) come out finite.  Arithmetic: r = (z - mu) (1 / sigma) in fp32
+ * on the vector units; per tile of components a max and an fp32 sum of exponentials; fp64 across tiles, slices and calls.  One
+ * owner per state, fixed-order folds, no float atomics: two calls give the same bits; chunking changes only the fp64 fold order.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (M, L or C < 1, M or C > 2^30, L > 2^16, c_first < 0, comps_per_owner < 1
+ * with a query_owner); GMVAE_E_NULL (z, mu, sigma, logw, workspace, bytes); GMVAE_E_ALIGN (float arrays 4 bytes, query_owner 8,
+ * the workspace 16). */
+int gmvae_mixture_logpdf_workspace_bytes(int64_t M, int L, int per_dim, uint64_t* bytes);
+int gmvae_mixture_logpdf_accumulate(const float* z, int64_t M, int L, const float* mu, const float* sigma, const float* logw,
+                                    int64_t C, int64_t c_first, int64_t comps_per_owner, const int64_t* query_owner, int per_dim,
+                                    void* workspace, void* stream);
+int gmvae_mixture_logpdf_finish(int64_t M, int L, int per_dim, double log_norm, float* log_joint_out, float* log_dim_out,
+                                float* log_own_out, const void* workspace, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
