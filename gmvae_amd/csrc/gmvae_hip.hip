@@ -3254,6 +3254,8 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (int e = check_x_align(dims, x)) return e;
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
+  const char* fc = getenv("GMVAE_FORCE_CFG");
+  if (fc) cx.force_cfg = atoi(fc);
   StepArgs a = {dims, model, x, eps, u, params, nullptr, tail, row_terms, z_out, y_out, logits_out, workspace, seed,
                 step, nullptr, false};
   return run_step(cx, a);

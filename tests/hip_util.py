@@ -50,6 +50,13 @@ def put(alloc, name, a, dtype, pitch):
     return v
 
 
+def put_x(alloc, x, D):
+    """The batch placed in `alloc` at exactly its bytes, read-only: uint8 [B, D] as B D bytes, float32 [B, D] (GMVAE_X_F32) as
+    4 B D bytes."""
+    f32 = np.asarray(x).dtype == np.float32
+    return put(alloc, "x", x, torch.float32 if f32 else torch.uint8, 4 * D if f32 else D)
+
+
 def out(alloc, name, shape, pitch):
     """A writable fp32 output placed in `alloc`: every byte 0xFF (a NaN) until the call writes it."""
     return alloc.place(name, 4 * int(np.prod(shape)), pitch, True, dtype=torch.float32).view(*shape)
@@ -95,7 +102,8 @@ FORWARD_OUTPUTS = ("rows", "z", "y", "logits")
 
 
 def forward_in(alloc, model, d, flat, x, eps, u, row0=0, flags=0, seed=0, step=0, outputs=FORWARD_OUTPUTS, prepare=None):
-    """gmvae_forward at d.S samples with every buffer in `alloc`: dict of tail [8] and the optional outputs named in `outputs`
+    """gmvae_forward at d.S samples with every buffer in `alloc` (x uint8, or float32 under GMVAE_X_F32): dict of tail [8] and the
+    optional outputs named in `outputs`
     (rows [R, 4], z [R, L], y [R, K], logits [B, K]; the others are passed as NULL) as numpy.  prepare(cd, ws): fills the
     caller-written workspace regions and narrows the writable set before the call."""
     alloc.reset()
@@ -105,7 +113,7 @@ def forward_in(alloc, model, d, flat, x, eps, u, row0=0, flags=0, seed=0, step=0
     R = B * d.S * (d.K if flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW) else 1)
     pitch = pitch_of(d)
     params = put(alloc, "params", flat, torch.float32, pitch)
-    xd = put(alloc, "x", x, torch.uint8, d.D)
+    xd = put_x(alloc, x, d.D)
     ed = None if eps is None else put(alloc, "eps", eps, torch.float32, 4 * d.L)
     ud = None if u is None else put(alloc, "u", u, torch.float32, 4 * d.K)
     shapes = {"rows": (R, 4), "z": (R, d.L), "y": (R, d.K), "logits": (B, d.K)}

@@ -98,7 +98,9 @@ CASES = {
     "gmvae-s3": Case("gmvae", O.Dims(D=96, L=4, K=6, hidden=(16,), S=3), 4),
     "vae-s3": Case("vae", O.Dims(D=96, L=4, K=1, hidden=(16,), S=3), 4),
     "gumbel-d99": Case("gmvae", O.Dims(D=99, L=5, K=7, hidden=(24,)), 5),                  # unaligned rows: the element path
-    "gumbel-784": Case("gmvae", O.Dims(D=784, L=64, K=10, hidden=(64,)), 16),              # interior tiles + the 16-column last tile
+    # B = 16: no 32-row tile is whole, so every tile of the logits launch goes element by element (24 full column tiles + the
+    # 16-column last one); the masked interior block and its predicated last column tile run in tests/test_epilogue_forms.py
+    "gumbel-784": Case("gmvae", O.Dims(D=784, L=64, K=10, hidden=(64,)), 16),
     "vae_gmp-tanh": Case("vae_gmp", O.Dims(D=100, L=5, K=3, hidden=(24,), act="tanh"), 9),
     "gumbel-bias-vec": Case("gmvae", O.Dims(D=100, L=5, K=7, hidden=(24,)), 8, bias_vec=True),
     "vae-saturated": Case("vae", O.Dims(D=100, L=5, K=1, hidden=(24,)), 9, lam_scale=60.0, single_pixel_row=3),

@@ -115,9 +115,9 @@ def terms_in(dtype, model, d: O.Dims, p, x, eps, u=None, sigma=1.0, rho=None):
             "sqerr": f(df * df).sum(dim=1).view(B, S).mean(dim=1).sum().item()}
 
 
-def real_batch(B, D, seed=5):
+def real_batch(B, D, seed=5, big=30.0, sigma_lo=0.05):
     """(x float32 [B, D], rho float32 [D]): standard normal values, about 10 % exact zeros, a quarter of the columns scaled by
-    1e-3 and a quarter by 30; rho uniform per column in [ln 0.05, ln 5]."""
+    1e-3 and a quarter by `big` = 30; rho uniform per column in [ln sigma_lo, ln 5], sigma_lo = 0.05."""
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((B, D))
     x[rng.random((B, D)) < 0.1] = 0.0
@@ -125,8 +125,8 @@ def real_batch(B, D, seed=5):
     cols = rng.permutation(D)
     q = D // 4
     scale[cols[:q]] = 1e-3
-    scale[cols[q:2 * q]] = 30.0
-    rho = rng.uniform(math.log(0.05), math.log(5.0), size=D)
+    scale[cols[q:2 * q]] = big
+    rho = rng.uniform(math.log(sigma_lo), math.log(5.0), size=D)
     return (x * scale).astype(np.float32), rho.astype(np.float32)
 
 
@@ -138,6 +138,8 @@ class Case:
     B: int
     sigma: float = 0.25          # the fixed-scale variant's sigma
     bytes_in: bool = False       # x as grey-level bytes (t = x / 255): the learned scale alone
+    big: float = 30.0            # real_batch's scale of its large columns
+    sigma_lo: float = 0.05       # ... and the lower end of its sigma range
 
 
 CASES = {
@@ -149,7 +151,21 @@ CASES = {
     "gmvae-784": Case("gmvae", O.Dims(D=784, L=64, K=10, hidden=(64,)), 32),             # interior tiles + the 16-column last tile
     "vae-b1-d3": Case("vae", O.Dims(D=3, L=2, K=1, hidden=(8,)), 1),                         # one row, the reduction's scalar path
     "gmvae-bytes": Case("gmvae", O.Dims(D=100, L=5, K=7, hidden=(24,)), 8, bytes_in=True),
+    # rho's reduction (csrc/liksig.hpp) beyond one row slab -- R = B S rows in slabs of rs = 64 rows, doubled until at most 256
+    # slabs; strips of 64 columns -- and the weight gradients under NS = num_splits(R) > 1 split-K slabs:
+    # 3 slabs, the last with 2 rows; two column strips, the second with 36 columns; no row weights
+    "vae-r130": Case("vae", O.Dims(D=100, L=5, K=1, hidden=(24,)), 130),
+    # 11 slabs on the scalar path (D % 4 != 0), the row weights live; NS = 2 with NSB = num_splits(B) = 1: liksig_finish zeroes
+    # slab 1, and the float x's weight gradients lie on fewer slabs than the rest
+    "gmvae-r650": Case("gmvae", O.Dims(D=99, L=5, K=7, hidden=(24,), S=5), 130),
+    # rs doubles to 128: 129 slabs, the last with 66 rows, eight rows per thread; NS = 16; a 4-column last strip on the vector path
+    # Its batch is milder (large columns x 3, sigma >= 0.5): under S = 50 the row weights are softmax_s(log w), an ABSOLUTE error
+    # of log w is a relative error of every gradient, and with the x 30 columns under sigma = 0.05 |log p(x|z)| is 4e5 per row,
+    # where one fp32 rounding is 0.03 -- the fp64 statement with log p(x|z) merely rounded to fp32 then sits 4e-5 of max |g| off,
+    # the whole statement in torch fp32 on the CPU 7e-3 (the device: 2.8e-4).  With this batch: 1e-6 and 6e-6.
+    "vae-r16450": Case("vae", O.Dims(D=68, L=4, K=1, hidden=(16,), S=50), 329, sigma=0.5, big=3.0, sigma_lo=0.5),
 }
+BEYOND_ONE_SLAB = ("vae-r130", "gmvae-r650", "vae-r16450")
 SCALES = ("fixed", "learned")
 VARIANTS = [(n, s) for n, c in CASES.items() for s in SCALES if not (c.bytes_in and s == "fixed")]
 
@@ -176,7 +192,7 @@ def setup(name, scale, seed=0):
     p = O.init_params(model, d, rng)
     _, eps, u = O.make_inputs(d, c.B, model)
     u = u if model == O.MODEL_GMVAE else None
-    xf, rho32 = real_batch(c.B, d.D)
+    xf, rho32 = real_batch(c.B, d.D, big=c.big, sigma_lo=c.sigma_lo)
     if c.bytes_in:
         x = LR.grey_batch(c.B, d.D)
         t = LR.targets(x)
@@ -191,3 +207,53 @@ def setup(name, scale, seed=0):
         flat = np.concatenate([flat, tailp])
         rho = rho32.astype(np.float64)
     return model, d, p32, flat, x, t, eps, u, rho
+
+
+# ---- rho's reduction as csrc/liksig.hpp orders it, in fp32
+LSIG_ROW_LANES, LSIG_MAX_SLABS = 16, 256      # liksig.hpp kLsigRowLanes, kLsigMaxSlabs
+
+
+def liksig_slab_rows(R):
+    """liksig.hpp liksig_slab_rows: 64 rows per slab, doubled until at most 256 slabs."""
+    rs = 64
+    while (R + rs - 1) // rs > LSIG_MAX_SLABS:
+        rs *= 2
+    return rs
+
+
+def rho_terms(C, t, rho, S):
+    """What the reduction reads, from the statement: g = (lambda - t) / sigma^2 [R, D] and the row weights [R] -- softmax_s of
+    log w within an example (all 1 at S = 1) -- as float64."""
+    R = C["lam"].shape[0]
+    g = (C["lam"] - np.repeat(np.asarray(t, np.float64), S, axis=0)) * np.exp(-2.0 * rho)[None, :]
+    lw = C["rows"][:, 3].reshape(R // S, S)
+    w = np.exp(lw - lw.max(axis=1, keepdims=True))
+    return g, (w / w.sum(axis=1, keepdims=True)).reshape(R)
+
+
+def rho_reduction(g, rw, rho, dtype=np.float32):
+    """sum_r rw_r (1 - sigma_d^2 g_rd^2) [D] in `dtype`, in liksig_partial / liksig_finish's order: each of the 16 row lanes of a
+    slab sums its rows (every 16th) in index order with the kernel's two fused multiply-adds per element, the 16 lanes are summed
+    in lane order, then the slabs in index order.  (A fused multiply-add of float32 operands is formed in float64 -- the product
+    is exact there -- and rounded once more to float32.)"""
+    f = dtype
+    R, D = g.shape
+    rs = liksig_slab_rows(R)
+    ns = (R + rs - 1) // rs
+    G, W = np.zeros((ns * rs, D), f), np.zeros(ns * rs, f)      # (rows beyond R: weight 0, fma(0, ., acc) == acc)
+    G[:R], W[:R] = g, rw
+    G, W = G.reshape(ns, rs // LSIG_ROW_LANES, LSIG_ROW_LANES, D), W.reshape(ns, rs // LSIG_ROW_LANES, LSIG_ROW_LANES)
+    s2 = np.exp(f(2.0) * np.asarray(rho, f)).astype(f)
+    fma = lambda a, b, c: (a.astype(np.float64) * b.astype(np.float64) + c).astype(f)
+    acc = np.zeros((ns, LSIG_ROW_LANES, D), f)
+    for i in range(rs // LSIG_ROW_LANES):
+        c = G[:, i]
+        inner = fma((-s2[None, None, :] * c).astype(f), c, 1.0)
+        acc = fma(np.broadcast_to(W[:, i][:, :, None], inner.shape), inner, acc.astype(np.float64))
+    part = np.zeros((ns, D), f)
+    for k in range(LSIG_ROW_LANES):
+        part = (part + acc[:, k]).astype(f)
+    tot = np.zeros(D, f)
+    for s in range(ns):
+        tot = (tot + part[s]).astype(f)
+    return tot.astype(np.float64)

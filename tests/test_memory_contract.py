@@ -11,7 +11,8 @@ the caller-written workspace regions, which the library only reads -- must be bi
   C  3-step train graphs through the C ABI at every `train` corner, bit for bit the same graph in plain allocations; batches at
      4-byte-aligned and odd addresses against 1-step graphs on aligned batches
   D  one gmvae_step and one gmvae_forward per legal set of objective / optimizer bits at a shape where nothing is a multiple of
-     4 or 16, all 32 slots of every caller-written region filled and read-only, bit for bit the plain call
+     4 or 16, all 32 slots of every caller-written region filled and read-only, bit for bit the plain call; the same under every
+     set of likelihood bits, x as bytes or as floats at exactly its size, D = 100 and 99
   E  the chunked evaluators (bit for bit the plain call) and the small entry points (their existing CPU restatements)
 
 A NaN or a 255 that leaks in from a guard band cannot pass the oracle gates of A and B; C, D and E compare paths the header
@@ -305,6 +306,7 @@ def test_train_graph_batches_at_unaligned_addresses(D, H, L, arena):
 SHAPE_D = dict(D=100, L=5, hidden=(24,))            # K = 7 (1 for the VAE), B = 9: nothing a multiple of 4 or 16, B D = 900
 B_D = 9
 EXTRAS = ("GRAD_DREG", "Y_STRAIGHT_THROUGH", "OPT_CLIP_NORM")
+SIGMA_D = 0.5                                       # the caller-written "lik_sigma" cell of the fixed-scale Gaussian sets
 
 
 def r256(n):
@@ -385,6 +387,8 @@ def _fill_step_inputs(alloc, L, cd, model, ws, K, B, D, flags):
         region("pixel_mask", S32 * slot, masks)
     if flags & L.OPT_CLIP_NORM:
         region("clip_norm", 4, np.array([2.5], np.float32))
+    if flags & L.LIK_MASK == L.LIK_GAUSSIAN and not flags & L.LIK_SCALE_LEARNED:
+        region("lik_sigma", 4, np.array([SIGMA_D], np.float32))
     keep.sort()
     free, at = [], 0
     for lo, hi in keep:
@@ -408,7 +412,7 @@ def _flagged_call(alloc, L, H, entry, name, d, B, flags, flat, x, eps, u):
     P, _ = L.param_count(cd, model)
     pitch = H.pitch_of(d)
     params = H.put(alloc, "params", flat, torch.float32, pitch)
-    xd = H.put(alloc, "x", x, torch.uint8, d.D)
+    xd = H.put_x(alloc, x, d.D)
     ed = H.put(alloc, "eps", eps, torch.float32, 4 * d.L)
     ud = None if u is None else H.put(alloc, "u", u, torch.float32, 4 * d.K)
     grads = H.out(alloc, "grads", (P + L.TAIL,), pitch)
@@ -455,6 +459,67 @@ def test_objective_and_optimizer_bits_stay_inside_their_buffers(args, want, H, L
                 assert np.isfinite(tail).all() and tail[4] == B_D, (entry, hex(flags), S, tail)
                 for k in got:
                     _same_bits(got[k], ref[k], f"{name} flags {flags:#x} S={S} {entry} {k}")
+
+
+# the likelihood bits (GMVAE_LIK_*, GMVAE_X_F32, GMVAE_LIK_SCALE_LEARNED): under GMVAE_X_F32 the caller's x is 4 B D bytes of
+# floats, read 16 bytes at a time as a GEMM operand (the first layers and their weight gradients, ragged tiles included) and as
+# the likelihood epilogue's target; "lik_sigma" is a caller-written workspace cell
+LIK_SETS = {"grey": ("LIK_GREY_BERNOULLI",), "cb": ("LIK_CONT_BERNOULLI",), "gauss": ("LIK_GAUSSIAN",),
+            "gauss+f32": ("LIK_GAUSSIAN", "X_F32"), "gauss+lsig": ("LIK_GAUSSIAN", "LIK_SCALE_LEARNED"),
+            "gauss+f32+lsig": ("LIK_GAUSSIAN", "X_F32", "LIK_SCALE_LEARNED")}
+
+
+@pytest.mark.parametrize("name", G.MODELS)
+@pytest.mark.parametrize("lset", list(LIK_SETS))
+def test_likelihood_bits_stay_inside_their_buffers(lset, name, monkeypatch, H, L, arena):
+    """Group D under every likelihood flag set, with and without GMVAE_OPT_CLIP_NORM: B = 9, S in {1, 3}, D = 100 and D = 99
+    (float rows that are not 16-byte aligned), gmvae_step -- once more under GMVAE_FORCE_CFG=2: 128-row tiles over 9 rows read x
+    as an operand -- and gmvae_forward; x at exactly its bytes and read-only, "lik_sigma" read-only; the guards untouched, the
+    tail finite, every output the bits of the same call in plain allocations."""
+    import lik_ref
+    import realx_ref
+    base = 0
+    for f in LIK_SETS[lset]:
+        base |= getattr(L, f)
+    f32, learned = bool(base & L.X_F32), bool(base & L.LIK_SCALE_LEARNED)
+    K = 1 if name == "vae" else 7
+    model = O.MODEL_NAMES[name]
+    for illegal in ("GRAD_DREG", "Y_STRAIGHT_THROUGH"):                 # the library agrees that these do not combine
+        cd = L.make_dims(B_D, 100, 5, K, (24,), sched_flags=base | getattr(L, illegal))
+        with pytest.raises(L.GmvaeError):
+            L.workspace_bytes(cd, L.MODEL_IDS[name])
+    rng = np.random.default_rng(len(lset) + K)
+    for flags in (base, base | L.OPT_CLIP_NORM):
+        for D in (100, 99):
+            xf, rho = realx_ref.real_batch(B_D, D)
+            x = xf if f32 else lik_ref.grey_batch(B_D, D)
+            for S in (1, 3):
+                d = O.Dims(D=D, L=5, hidden=(24,), K=K, S=S)
+                flat = O.pack(model, d, O.init_params(model, d, rng), np.float32)
+                if learned:
+                    flat = np.concatenate([flat, rho, np.zeros(-D % 4, np.float32)])
+                eps = rng.standard_normal((B_D * S, d.L)).astype(np.float32)
+                u = rng.uniform(0.05, 0.95, (B_D * S, K)).astype(np.float32) if name == "gmvae" else None
+                for entry, cfg in (("step", None), ("step", "2"), ("forward", None)):
+                    for k in G.SWITCHES + ("GMVAE_FORCE_CFG", "GMVAE_NO_BIG"):
+                        monkeypatch.delenv(k, raising=False)
+                    if cfg:
+                        monkeypatch.setenv("GMVAE_FORCE_CFG", cfg)
+                    what = f"{name} {lset} flags {flags:#x} D={D} S={S} {entry} cfg {cfg}"
+                    with _Timed("D", arena):
+                        got = _flagged_call(arena, L, H, entry, name, d, B_D, flags, flat, x, eps, u)
+                    cd = H.dims_of(d, B_D)
+                    cd.sched_flags = flags
+                    assert arena.buf("workspace").nbytes == L.workspace_bytes(cd, model)
+                    assert arena.buf("x").nbytes == (4 if f32 else 1) * B_D * D and arena.buf("x").writable == []
+                    assert arena.buf("params").nbytes == 4 * L.param_count(cd, model)[0]
+                    ref = _flagged_call(A.Plain("cuda"), L, H, entry, name, d, B_D, flags, flat, x, eps, u)
+                    tail = got["grads"][-L.TAIL:] if entry == "step" else got["tail"]
+                    assert np.isfinite(tail).all() and tail[4] == B_D and tail[6] == B_D * D, (what, tail)
+                    if entry == "step":
+                        assert np.isfinite(got["grads"]).all(), what
+                    for k in got:
+                        _same_bits(got[k], ref[k], f"{what} {k}")
 
 
 # ------------------------------------------------------------- E: the chunked evaluators and the small entry points

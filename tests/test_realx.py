@@ -54,8 +54,9 @@ def _ws(cd, model, sigma):
     return ws
 
 
-def rstep(model, d, flat, x, eps, u, fl, sigma, seed=5, step=3):
-    """One gmvae_step under the flags (x uint8 or float32 as given): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
+def rstep(model, d, flat, x, eps, u, fl, sigma, seed=5, step=3, stale_rho_slabs=False):
+    """One gmvae_step under the flags (x uint8 or float32 as given): (grad sums [P] float64, tail [8], the step's ReLU masks).
+    stale_rho_slabs: rho's range of every split-K slab of the gradient behind the first holds NaN when the step starts."""
     import torch
     L = _L()
     B = x.shape[0]
@@ -67,6 +68,14 @@ def rstep(model, d, flat, x, eps, u, fl, sigma, seed=5, step=3):
     ud = None if u is None else dev(u, torch.float32)
     grads = torch.full((P + L.TAIL,), float("nan"), dtype=torch.float32, device="cuda")
     ws = _ws(cd, model, sigma)
+    if stale_rho_slabs:
+        D4, NS = RR.pad4(d.D), min(max(B * d.S // 256, 1), 16)          # (gmvae_hip.hip num_splits(R): the slabs a step sums)
+        assert fl & RR.LIK_SCALE_LEARNED and NS > 1
+        off = C.c_uint64()
+        L.check(L.lib.gmvae_workspace_offset(C.byref(cd), model, b"slabs", C.byref(off)), "offset slabs")
+        for k in range(1, NS):
+            at = off.value // 4 + k * P + (P - D4)
+            ws[at:at + D4] = float("nan")
     L.check(L.lib.gmvae_step(C.byref(cd), model, L.ptr(xd), L.ptr(ed), L.ptr(ud), L.ptr(params), L.ptr(grads), L.ptr(ws), seed, step,
                              None, L.current_stream()), "gmvae_step")
     torch.cuda.synchronize()
@@ -98,6 +107,20 @@ def test_step_matches_fp64_statement(name, scale):
         print(f"{what} {RR.LOG_SIGMA}: rel-to-max err {err:.3e}")
         assert err <= 1e-4, (what, err)
         assert not gs[P0 + D:].any()                                # (the pad behind rho's D values)
+
+
+@pytest.mark.parametrize("name", ["gmvae-r650", "vae-r16450"])
+def test_rho_range_of_every_slab_is_rewritten(name):
+    """NS = 2 and 16 split-K slabs: liksig_finish owns rho's range in ALL of them (its sum to slab 0, zeros to the others).  A step
+    that starts with NaN there -- what an earlier step of other sizes may have left -- ends on the bits of the step in a zeroed
+    workspace."""
+    import torch
+    model, d, p32, flat, x, t, eps, u, rho = RR.setup(name, "learned")
+    c = RR.CASES[name]
+    fl = RR.flags(c, "learned")
+    _, _, _, clean = rstep(model, d, flat, x, eps, u, fl, c.sigma)
+    _, _, _, stale = rstep(model, d, flat, x, eps, u, fl, c.sigma, stale_rho_slabs=True)
+    assert bool(torch.isfinite(clean).all()) and torch.equal(clean, stale)
 
 
 # 2 --------------------------------------------------------------------------------------------------------------

@@ -341,3 +341,49 @@ def test_case_statements_are_finite(name, scale):
     print(f"{name}-{scale}: torch fp32 vs fp64, max over rows: logpx {np.abs(t32['rows'] - t64['rows']).max(axis=0).tolist()}; "
           f"rel loss {abs(t32['loss'] - t64['loss']) / abs(t64['loss']):.2e} kl {abs(t32['kl'] - t64['kl']) / max(abs(t64['kl']), 1):.2e}")
     print(f"{name}-{scale}: loss {Cc['loss']:.6g} nll {Cc['nll']:.6g} nll_abs {Cc['nll_abs']:.6g} kl {Cc['kl']:.6g} sqerr {Cc['sqerr']:.6g}")
+
+
+# ------------------------------------------------------------------------- rho's reduction beyond one row slab
+def test_beyond_one_slab_cases_are_what_their_comments_say():
+    """(slabs, rows of the last slab, rows per thread, column strips, columns of the last strip, vector path, NS, NSB) of each case,
+    from liksig.hpp's slab rule and gmvae_hip.hip's num_splits (R / 256, at most 16; NSB = min(NS, num_splits(B)) under S > 1)."""
+    ns = lambda n: min(max(n // 256, 1), 16)
+    want = {"vae-r130": (3, 2, 4, 2, 36, True, 1, 1), "gmvae-r650": (11, 10, 4, 2, 35, False, 2, 1),
+            "vae-r16450": (129, 66, 8, 2, 4, True, 16, 1)}
+    assert set(want) == set(RR.BEYOND_ONE_SLAB)
+    for name in RR.BEYOND_ONE_SLAB:
+        c = RR.CASES[name]
+        R, D, S = c.B * c.d.S, c.d.D, c.d.S
+        rs = RR.liksig_slab_rows(R)
+        slabs = (R + rs - 1) // rs
+        NS = ns(R)
+        got = (slabs, R - (slabs - 1) * rs, rs // RR.LSIG_ROW_LANES, (D + 63) // 64, D - (D - 1) // 64 * 64, D % 4 == 0, NS,
+               min(NS, ns(c.B)) if S > 1 else NS)
+        assert got == want[name], (name, got)
+        assert (RR.liksig_slab_rows(16384), RR.liksig_slab_rows(16385)) == (64, 128)
+
+
+@pytest.mark.parametrize("name", RR.BEYOND_ONE_SLAB)
+def test_rho_reduction_in_the_kernels_order_in_fp32(name):
+    """The reference alone: rho's reduction over the statement's g and row weights, evaluated in numpy float32 in the kernel's
+    order (rows per lane, then the 16 lanes, then the slabs), sits within a quarter of the device gate -- 2.5e-5 of max |ref| --
+    of the fp64 gradient; in float64 the same code IS the statement's gradient.  The fp64 statement itself takes well under a
+    second at these sizes."""
+    import time
+    model, d, p32, flat, x, t, eps, u, rho = RR.setup(name, "learned")
+    B = x.shape[0]
+    t0 = time.perf_counter()
+    Cc, g = RR.loss_and_grads(model, d, p32, t, eps, u, rho=rho)
+    secs = time.perf_counter() - t0
+    ref = g[RR.LOG_SIGMA]
+    gm, rw = RR.rho_terms(Cc, t, rho, d.S)
+    if d.S == 1:
+        assert (rw == 1.0).all()
+    else:
+        assert rw.min() < 0.5 / d.S and rw.max() > 2.0 / d.S                # (the row weights are live)
+    e64 = np.abs(RR.rho_reduction(gm, rw, rho, np.float64) / B - ref).max() / np.abs(ref).max()
+    e32 = np.abs(RR.rho_reduction(gm, rw, rho, np.float32) / B - ref).max() / np.abs(ref).max()
+    print(f"{name}: fp64 statement {secs:.3f} s; rho reduction in the kernel's order: fp64 err {e64:.2e}, fp32 err {e32:.2e} of max |ref| "
+          f"{np.abs(ref).max():.4g}")
+    assert secs < 1.0
+    assert e64 <= 1e-10 and e32 <= 2.5e-5, (name, e64, e32)
