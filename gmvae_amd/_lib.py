@@ -67,6 +67,10 @@ def _load():
         "gmvae_mixture_logpdf_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
         "gmvae_mixture_logpdf_accumulate": ([vp, i64, i32, vp, vp, vp, i64, i64, i64, vp, i32, vp, vp], i32),
         "gmvae_mixture_logpdf_finish": ([i64, i32, i32, C.c_double, vp, vp, vp, vp, vp], i32),
+        "gmvae_tsne_workspace_bytes": ([i64, i32, i64, C.POINTER(u64)], i32),
+        "gmvae_tsne_affinities": ([vp, i64, i32, f32, i64, i64, vp, vp, vp, vp, vp], i32),
+        "gmvae_tsne_gradient": ([vp, i64, i32, vp, vp, vp, f32, vp, vp, vp, vp], i32),
+        "gmvae_tsne_run": ([vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp], i32),
         "adam_tf_step": ([vp, vp, vp, vp, u64, f32, f32, f32, f32, u64, vp, f32, vp, vp, vp], i32),
         "gmvae_grad_clip_scratch_bytes": ([u64, C.POINTER(u64)], i32),
         "gmvae_grad_clip": ([vp, u64, vp, vp, vp, vp], i32),

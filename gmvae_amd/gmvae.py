@@ -56,6 +56,12 @@ class GMVAE:
         y = self.encoder_y(inputs).sample(seed=self.random_seed)
         return self.encoder_gmm(inputs, y).sample(seed=self.random_seed, name="code")
 
+    def embed_latent(self, images, **kw):
+        """The 2-D t-SNE embedding of the latent codes of `images`: transform, then gmvae_amd.tsne.embed(**kw) -- its dict
+        (embedding [N, 2], kl, kl_history, beta, entropy)."""
+        from . import tsne
+        return tsne.embed(self.transform(images), **kw)
+
     def generate_samples(self, num_samples, clusters=None):
         """[num_samples * K, L] draws from every p(z|y=k), or from the given clusters
         (scripts/gmvae.py:152-188)."""

@@ -1,5 +1,6 @@
 """`python -m gmvae_amd.run_gmvae` -- the flag table of scripts/run_gmvae.py:11-58 (same names, defaults)."""
 import argparse
+import os
 
 from . import runners
 
@@ -51,6 +52,12 @@ def build_parser():
     a("--latent_diagnostics", type=int, default=0, help="eval: also report the aggregate posterior's diagnostics over the first "
       "N examples of the split (Engine.aggregate_posterior) -- the mutual information I(x; z), KL(q(z) || p(z)), the total "
       "correlation of q(z), their sum kl_avg, the active units, and for gmvae I(x; y) and the entropy of q(y); 0 = off")
+    a("--embed_latent", type=int, default=0, help="eval: also embed the latent code of the first N examples of the split in two "
+      "dimensions by exact t-SNE on the device (gmvae_amd.tsne.embed; the reference's utils.reduce_dimensionality) -- "
+      "latent_embedding, samples_embedding (the prior draws, where --num_samples allows the perplexity) and embedding_kl; 0 = off")
+    a("--tsne_perplexity", type=float, default=40.0, help="--embed_latent: the perplexity (the reference's 40)")
+    a("--tsne_iters", type=int, default=300, help="--embed_latent: the iterations (the reference's 300)")
+    a("--embedding_out", default=None, help="--embed_latent: write latent_embedding to this .npy file")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -120,6 +127,19 @@ def check_args(p, cfg):
             p.error("--latent_diagnostics needs --mode=eval")
         if cfg.missing_rate > 0:
             p.error("--latent_diagnostics is not available with --missing_rate (the encoders it runs take no mask)")
+    if cfg.embed_latent < 0:
+        p.error("--embed_latent must be >= 0 (0 = off)")
+    if cfg.embed_latent:
+        if cfg.mode != "eval":
+            p.error("--embed_latent needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--embed_latent embeds one rank's codes: it is not available with more than one rank")
+        if cfg.embed_latent < 4 or not 1.0 < cfg.tsne_perplexity < cfg.embed_latent - 1:
+            p.error("--embed_latent N needs N >= 4 and --tsne_perplexity in (1, N - 1)")
+        if cfg.tsne_iters < 0:
+            p.error("--tsne_iters must be >= 0")
+    elif cfg.embedding_out:
+        p.error("--embedding_out needs --embed_latent")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

@@ -2,7 +2,8 @@
 
 `create_dataset`, `create_model`, `run_train`, `run_eval` keep the reference's names
 (scripts/runners.py:21,65,106,235).  What is NOT reproduced: TensorBoard summaries,
-image tiles, t-SNE and matplotlib plots (visualisation, out of scope -- DESIGN.md 6).
+image tiles and matplotlib plots (visualisation, out of scope -- DESIGN.md 6); the t-SNE embedding those plots show is
+computed (run_eval --embed_latent, tsne.py).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import Iterator, Tuple
 import numpy as np
 import torch
 
-from . import gmvae, parallel, utils, vae
+from . import gmvae, parallel, tsne, utils, vae
 
 
 # ------------------------------------------------------------------ data
@@ -664,6 +665,13 @@ def run_train(config):
     return model
 
 
+def _check_embed_size(config, em_n, n, perp):
+    """--embed_latent N on a split of fewer than N examples: the perplexity must still fit the codes there are."""
+    if n < 4 or not perp < n - 1:
+        raise ValueError(f"--embed_latent {em_n}: the {config.split} split holds {n} examples, too few for --tsne_perplexity "
+                         f"{perp:g}, which must lie in (1, examples - 1): lower --tsne_perplexity or evaluate a larger split")
+
+
 @torch.no_grad()
 def run_eval(config):
     """scripts/runners.py:235-459 without the plots.  Reports the true per-example loss and, under a
@@ -702,6 +710,13 @@ def run_eval(config):
     q_logits = []                                           # --real_valued, gmvae: q(y|x)'s logits over the split, for cluster_acc_q
     # --latent_diagnostics N: the first N examples of the split, as the aggregate posterior's components and as its queries
     ld_n, ld_imgs = int(getattr(config, "latent_diagnostics", 0) or 0), []
+    # --embed_latent N: the code of the first N examples of the split, embedded in two dimensions by exact t-SNE (tsne.embed)
+    em_n = int(getattr(config, "embed_latent", 0) or 0)
+    if em_n and world > 1:
+        raise ValueError("--embed_latent embeds one rank's codes: it is not available with more than one rank")
+    if em_n and not getattr(config, "data_dir", None) and not getattr(config, "data_npy", None):
+        # a synthetic split's size is known before the pass (a file's is checked when its codes are in hand)
+        _check_embed_size(config, em_n, min(em_n, int(getattr(config, "synthetic_size", 8192))), float(getattr(config, "tsne_perplexity", 40.0)))
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -833,4 +848,20 @@ def run_eval(config):
         sample_images = torch.stack((sample_images, sample_images_k), dim=0)
         res["sampled_cluster"] = k
     res["sample_images"] = sample_images
+    if em_n:
+        # utils.reduce_dimensionality on the code and on the prior draws (scripts/runners.py:446-450), without the plots
+        perp, iters = float(getattr(config, "tsne_perplexity", 40.0)), int(getattr(config, "tsne_iters", 300))
+        seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
+        em_codes = res["latent_state"][:em_n]
+        _check_embed_size(config, em_n, em_codes.shape[0], perp)
+        emb = tsne.embed(em_codes, perplexity=perp, n_iter=iters, seed=seed)
+        res["latent_embedding"] = emb["embedding"]
+        res[f"{config.split}/embedding_kl"] = emb["kl"].item()
+        smp = res["samples"]
+        res["samples_embedding"] = (tsne.embed(smp, perplexity=perp, n_iter=iters, seed=seed)["embedding"]
+                                    if smp.shape[0] >= 4 and perp < smp.shape[0] - 1 else None)
+        if rank == 0:
+            print(f"{config.split}/embedding_kl: {res[f'{config.split}/embedding_kl']}")
+        if getattr(config, "embedding_out", None):
+            np.save(config.embedding_out, res["latent_embedding"].cpu().numpy())
     return res

@@ -21,6 +21,17 @@ def entropy(logits, targets):
     return -(targets * torch.log_softmax(logits, -1)).sum(1)
 
 
+def reduce_dimensionality(data, dim=2, perplexity=40):
+    """scripts/utils.py:148-153: data with more than 2 columns goes through exact t-SNE on the device (gmvae_amd.tsne.embed, the
+    reference's perplexity 40 and 300 iterations) and comes back as a [N, 2] device tensor; anything else is returned as it is."""
+    if dim != 2:
+        raise ValueError("reduce_dimensionality embeds into 2 dimensions only (dim=2)")
+    if data.shape[-1] <= 2:
+        return data
+    from . import tsne
+    return tsne.embed(data, perplexity=float(perplexity), n_iter=300)["embedding"]
+
+
 def cluster_acc_from_hist(hist: torch.Tensor) -> torch.Tensor:
     """Clustering accuracy from the [K, n_labels] cluster x label histogram: matches = sum_k max_l hist[k, l]
     (every sample of a cluster that carries the cluster's majority label).  Histograms add across data-parallel

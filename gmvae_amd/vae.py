@@ -52,6 +52,12 @@ class VAE:
         """MEAN latent code (scripts/vae.py:108-114)."""
         return self.encoder(inputs).mean(name="code")
 
+    def embed_latent(self, images, **kw):
+        """The 2-D t-SNE embedding of the latent codes of `images`: transform, then gmvae_amd.tsne.embed(**kw) -- its dict
+        (embedding [N, 2], kl, kl_history, beta, entropy)."""
+        from . import tsne
+        return tsne.embed(self.transform(images), **kw)
+
     def generate_samples(self, num_samples):
         z = self.prior().sample(num_samples, seed=self.random_seed, name="samples")
         return z.reshape(num_samples, -1)

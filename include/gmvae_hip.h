@@ -601,6 +601,45 @@ int gmvae_mixture_logpdf_accumulate(const float* z, int64_t M, int L, const floa
 int gmvae_mixture_logpdf_finish(int64_t M, int L, int per_dim, double log_norm, float* log_joint_out, float* log_dim_out,
                                 float* log_own_out, const void* workspace, void* stream);
 
+/* Exact t-SNE of N codes into two dimensions on the device (model independent; gmvae_amd.tsne.embed, utils.reduce_dimensionality
+ * and run_eval's --embed_latent go through it; the reference's evaluation does the same with scikit-learn, scripts/utils.py:148-153).
+ * O(N^2) per iteration, no tree, no FFT; memory grows with N (and rows N for the affinity stage), never with N^2.
+ * codes [N][L], beta / logz / entropy [N], y / vel / gains / grad_out [N][2], kl_history [n_iter], stats_out [4]: fp32 in device
+ * memory.  d2_ij = sum_d (c_id - c_jd)^2 in the difference form, fp64 differences and sum.
+ *   gmvae_tsne_affinities, for the rows i in [r0, r0 + rows): the beta_i > 0 at which the entropy of p_{j|i} = exp(-beta_i d2_ij -
+ *     logz_i), logz_i = logsumexp_{j != i}(-beta_i d2_ij), is ln(perplexity): beta = 1, doubled or halved until the root is
+ *     bracketed, then bisected until fp32 cannot split the bracket (at most 100 halvings; H's sums in fp64), which leaves
+ *     |H_i - ln perplexity| far inside 1e-5 and beta, logz and p_{j|i} at the root where H is flat in beta.  The customary stop
+ *     at |H_i - ln perplexity| <= 1e-5 is deliberately NOT applied: where a row's nearest neighbours nearly tie it leaves logz
+ *     2.6e-4 off the root (csrc/tsne.hpp).  It writes beta, logz and
+ *     entropy (the H_i reached) at [r0, r0 + rows) and nothing else outside the workspace; a row's result does not depend on
+ *     (r0, rows), so a caller may chunk the rows to bound the workspace.  A row with no root -- a point with at least `perplexity`
+ *     exact duplicates -- keeps the last beta tried and reports the entropy reached there.
+ *   gmvae_tsne_gradient, at the embedding y with p_ij = (p_{j|i} + p_{i|j}) / 2N, p_ii = 0, w_ij = 1 / (1 + |y_i - y_j|^2),
+ *     Z = sum_{i != j} w_ij:  grad_out_i = 4 sum_j (exaggeration p_ij - w_ij / Z) w_ij (y_i - y_j);  stats_out (may be NULL) =
+ *     {Z, sum p ln w, KL, sum p ln p} with KL = sum p ln p - sum p ln w + ln Z over i != j (the un-exaggerated P; p = 0
+ *     contributes 0).
+ *   gmvae_tsne_run: n_iter iterations of (gradient; scikit-learn's _gradient_descent update without recentring: gains += 0.2
+ *     where vel grad < 0, else gains *= 0.8, floored at 0.01; vel = momentum vel - lr gains grad; y += vel) enqueued on `stream`
+ *     with no host synchronisation: exaggeration and momentum 0.5 for the iterations it < exaggeration_iters, then 1 and 0.8.
+ *     y holds the initial embedding on entry and the result on return; vel and gains are the caller's state (0 and 1 to begin
+ *     with).  kl_history (may be NULL) [it] = the KL at the embedding iteration `it` started from.
+ * The workspace (gmvae_tsne_workspace_bytes(N, L, rows): rows = the most rows an affinity call will take, 1 if none) holds the
+ * pairwise pass's fp64 partial sums per point and slice and the chunk's d2 [rows][N]; it needs no initialisation, and every call
+ * leaves it free for the next.  The caller owns every other byte: no call writes outside its outputs and the workspace.
+ * One owner per sum, fixed-order fp64 folds, no float atomics: two calls give the same bits.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (N < 4, N > 2^20, L < 1, L > 2^16, perplexity outside (1, N - 1),
+ * rows < 1, r0 < 0 or r0 + rows > N, n_iter < 0); GMVAE_E_NULL (any pointer not marked "may be NULL"); GMVAE_E_ALIGN (float
+ * arrays 4 bytes, the workspace 16). */
+int gmvae_tsne_workspace_bytes(int64_t N, int L, int64_t rows, uint64_t* bytes);
+int gmvae_tsne_affinities(const float* codes, int64_t N, int L, float perplexity, int64_t r0, int64_t rows, float* beta,
+                          float* logz, float* entropy, void* workspace, void* stream);
+int gmvae_tsne_gradient(const float* codes, int64_t N, int L, const float* beta, const float* logz, const float* y,
+                        float exaggeration, float* grad_out, float* stats_out, void* workspace, void* stream);
+int gmvae_tsne_run(const float* codes, int64_t N, int L, const float* beta, const float* logz, float* y, float* vel,
+                   float* gains, int n_iter, int exaggeration_iters, float exaggeration, float lr, float* kl_history,
+                   void* workspace, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
