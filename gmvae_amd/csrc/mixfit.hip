@@ -1,0 +1,86 @@
+// gmvae_mixfit_*: the host side of csrc/mixfit.hpp (include/gmvae_hip.h).  A translation unit of its own, for the reason at the top
+// of csrc/tsne.hip: the model-independent evaluator's kernels, descriptors and symbols stay out of the training step's code object.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/gmvae_hip.h"
+#include "mixfit.hpp"
+
+using namespace gmvae;
+
+namespace {
+
+int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int mf_check_sizes(int64_t N, int L, int K) {
+  if (N < 1 || N > (1ll << 24) || L < 1 || L > 4096 || K < 1 || K > 256 || (int64_t)K * L > kMfMaxKL) return GMVAE_E_DIMS;
+  return 0;
+}
+
+// Workspace, a function of (N, L, K): the workgroups' partial sums [groups][stride] (fp64).  Nothing is kept per row.
+uint64_t mf_workspace_bytes(const MfPlan& p) { return ((uint64_t)p.groups * (uint64_t)p.stride * sizeof(double) + 15) / 16 * 16; }
+
+// one-shot per DEVICE: the pass may ask for more than 64 KiB of dynamic LDS
+void mf_allow_lds() {
+  static bool seen[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+    if (seen[dev]) return;
+    seen[dev] = true;
+  }
+  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_pass<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_pass<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmvae_mixfit_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes) {
+  if (int e = mf_check_sizes(N, L, K)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  *bytes = mf_workspace_bytes(mf_plan(N, L, K));
+  return 0;
+}
+
+int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* sigma,
+                        float* log_resp_out, float* lse_out, void* workspace, void* stream) {
+  if (int e = mf_check_sizes(N, L, K)) return e;
+  if (!codes || !logw || !mu || !sigma || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(sigma, 4) || !aligned_to(log_resp_out, 4) ||
+      !aligned_to(lse_out, 4) || !aligned_to(workspace, 16))
+    return GMVAE_E_ALIGN;
+  const MfPlan p = mf_plan(N, L, K);
+  (void)hipGetLastError();
+  mf_allow_lds();
+  hipLaunchKernelGGL(mixfit_pass<false>, dim3((unsigned)p.groups), dim3(kMfBlock), p.lds, static_cast<hipStream_t>(stream), codes, (int)N,
+                     L, K, logw, mu, sigma, p.tile, p.per_group, log_resp_out, lse_out, (double*)nullptr, p.stride);
+  return (int)hipGetLastError();
+}
+
+int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* sigma, float reg_covar, int n_iter,
+                     float* loglik_history, float* counts_out, void* workspace, void* stream) {
+  if (int e = mf_check_sizes(N, L, K)) return e;
+  if (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) return GMVAE_E_DIMS;
+  if (!codes || !logw || !mu || !sigma || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(sigma, 4) ||
+      !aligned_to(loglik_history, 4) || !aligned_to(counts_out, 4) || !aligned_to(workspace, 16))
+    return GMVAE_E_ALIGN;
+  if (n_iter == 0) return 0;
+  const MfPlan p = mf_plan(N, L, K);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* const part = static_cast<double*>(workspace);
+  const unsigned update_blocks = (unsigned)((K * L + kMfFoldSlots - 1) / kMfFoldSlots) + 1;
+  (void)hipGetLastError();
+  mf_allow_lds();
+  for (int it = 0; it < n_iter; ++it) {
+    hipLaunchKernelGGL(mixfit_pass<true>, dim3((unsigned)p.groups), dim3(kMfBlock), p.lds, st, codes, (int)N, L, K, logw, mu, sigma,
+                       p.tile, p.per_group, (float*)nullptr, (float*)nullptr, part, p.stride);
+    hipLaunchKernelGGL(mixfit_update, dim3(update_blocks), dim3(kMfBlock), 0, st, part, p.groups, p.stride, (int)N, L, K, reg_covar, logw,
+                       mu, sigma, loglik_history ? loglik_history + it : nullptr, it == n_iter - 1 ? counts_out : nullptr);
+  }
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -129,6 +129,29 @@ class TrainableGMVAE(GMVAE):
         and of kl_avg = mi + kl_marginal, tc, dim_kl, active_units, q_y, q_y_entropy and mi_xy."""
         return self._need_engine().aggregate_posterior(images, queries=queries, per_dim=per_dim)
 
+    def fit_latent_mixture(self, images, n_components=None, **kw):
+        """A diagonal Gaussian mixture fitted by EM on the device to the codes self.transform(images) -- the sampled code run_eval
+        stores in latent_state -- (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init).  n_components defaults to
+        the model's mixture size.  Returns fit's dict plus `log_resp` [N, K], the responsibilities of those images."""
+        from . import mixfit
+        return mixfit.fit_latent(self, images, self.mix_components if n_components is None else n_components, **kw)
+
+    def init_prior_from_mixture(self, fit):
+        """Starts p(z | y = k) from a fitted mixture (fit_latent_mixture's or gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)).
+        prior_gmm is a Linear on the one-hot y with no hidden layer, so a table: its bias becomes 0 and row k of its weight (mu_k,
+        softplus^-1(max(sigma_k, sigma_min)) - raw_sigma_bias), so that prior_gmm(e_k) = N(mu_k, max(sigma_k, sigma_min)).  p(y)
+        STAYS UNIFORM: the fitted weights logw are not used.  Written through state_dict() / load_state_dict(), so whatever the
+        engine derives from its parameters is rebuilt.  Adam's slots are left as they are: the call is meant before training or
+        between phases.  ValueError for a fit whose K or L is not the model's."""
+        from . import mixfit
+        e = self._need_engine()
+        _, mu, sigma = mixfit.checked_fit(fit, e.K, e.Lz, e.device)
+        raw = mixfit.softplus_inverse(sigma.clamp_min(float(e.hp["sigma_min"]))) - float(e.hp["raw_sigma_bias"])
+        sd = self.state_dict()
+        sd["prior_gmm_fcnet/linear_0/w"] = torch.cat([mu, raw], dim=1)
+        sd["prior_gmm_fcnet/linear_0/b"] = torch.zeros(2 * e.Lz, dtype=torch.float32, device=e.device)
+        self.load_state_dict(sd)
+
     def predict_clusters(self, images, n_samples=None):
         """The component the model's posterior p(y | x) assigns each example to: an int64 [B] device tensor.  A model on
         real-valued rows (real_valued=True), whose likelihood the enumerating evaluators refuse, assigns by the inference

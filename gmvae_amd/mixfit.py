@@ -1,0 +1,176 @@
+"""A diagonal Gaussian mixture fitted to latent codes by EM on the device (include/gmvae_hip.h gmvae_mixfit_*; csrc/mixfit.hpp):
+the "VAE + GMM" baseline of the deep-clustering tables, and the initialiser of a mixture prior from a pretrained encoder's codes
+(VaDE).  Model independent: codes are any fp32 [N, L] device tensor.  The statement is tests/mixfit_ref.py."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib as L
+
+MAX_N, MAX_L, MAX_K, MAX_KL = 1 << 24, 4096, 256, 16384      # the library's gate (include/gmvae_hip.h)
+
+
+def _check_sizes(N, Lz, K):
+    if not (1 <= N <= MAX_N and 1 <= Lz <= MAX_L):
+        raise ValueError(f"codes must be [N, L] with 1 <= N <= 2^24 and 1 <= L <= {MAX_L}: got [{N}, {Lz}]")
+    if not (1 <= K <= MAX_K and K * Lz <= MAX_KL):
+        raise ValueError(f"K must lie in [1, {MAX_K}] with K * L <= {MAX_KL}: K = {K}, L = {Lz}")
+
+
+def workspace_bytes(N, Lz, K):
+    b = C.c_uint64()
+    L.check(L.lib.gmvae_mixfit_workspace_bytes(int(N), int(Lz), int(K), C.byref(b)), "gmvae_mixfit_workspace_bytes")
+    return b.value
+
+
+def _codes(codes):
+    codes = torch.as_tensor(codes).to(L.require_gpu(), torch.float32).contiguous()
+    if codes.dim() != 2:
+        raise ValueError("codes must be [N, L]")
+    return codes
+
+
+def _params(params, Lz, dev, K=None):
+    """(logw [K], mu [K, L], sigma [K, L]) as fresh contiguous fp32 device tensors, from a tuple or a dict with those keys."""
+    if isinstance(params, dict):
+        params = (params["logw"], params["mu"], params["sigma"])
+    if len(params) != 3:
+        raise ValueError("a mixture is (logw, mu, sigma)")
+    logw, mu, sigma = (torch.as_tensor(t).to(dev, torch.float32).contiguous().clone() for t in params)
+    if logw.dim() != 1 or mu.shape != (logw.shape[0], Lz) or sigma.shape != mu.shape or (K is not None and logw.shape[0] != K):
+        raise ValueError(f"a mixture is logw [K], mu [K, {Lz}], sigma [K, {Lz}]"
+                         + (f" with K = {K}" if K is not None else "")
+                         + f": got {tuple(logw.shape)}, {tuple(mu.shape)}, {tuple(sigma.shape)}")
+    return logw, mu, sigma
+
+
+def assign(codes, params, workspace=None):
+    """The E-step of codes [N, L] under the mixture `params` = (logw, mu, sigma) or a dict with those keys (fit's): a dict of
+    `log_resp` [N, K] = ln r_nk and `lse` [N] = ln p(z_n)."""
+    codes = _codes(codes)
+    N, Lz = codes.shape
+    logw, mu, sigma = _params(params, Lz, codes.device)
+    K = logw.shape[0]
+    _check_sizes(N, Lz, K)
+    if workspace is None:
+        workspace = torch.empty(workspace_bytes(N, Lz, K), dtype=torch.uint8, device=codes.device)
+    log_resp = torch.empty(N, K, dtype=torch.float32, device=codes.device)
+    lse = torch.empty(N, dtype=torch.float32, device=codes.device)
+    L.check(L.lib.gmvae_mixfit_assign(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(sigma), L.ptr(log_resp), L.ptr(lse),
+                                      L.ptr(workspace), L.current_stream()), "gmvae_mixfit_assign")
+    return {"log_resp": log_resp, "lse": lse}
+
+
+def uniforms(K, seed=0, device=None):
+    """The K uniforms of a seeding: row 0 of gmvae_noise_fill's `u` output, key `seed`, step 0."""
+    u = torch.empty(1, int(K), dtype=torch.float32, device=device or L.require_gpu())
+    L.check(L.lib.gmvae_noise_fill(None, L.ptr(u), 1, 1, int(K), 0, int(seed), 0, None, L.current_stream()), "gmvae_noise_fill")
+    return u[0]
+
+
+def kmeanspp(codes, K, seed=0):
+    """k-means++ seeding: the int64 [K] indices of the chosen rows.  i_0 = min(floor(u_0 N), N - 1); for k >= 1, d2min_n = the
+    smallest squared distance (fp64 differences) to the centres so far, c = its fp64 cumulative sum in index order, i_k = the first
+    index with c > u_k c[N-1] (c[N-1] = 0: i_k = min(floor(u_k N), N - 1)); u = uniforms(K, seed).  K rounds of a few torch ops on
+    the device; nothing synchronises with the host."""
+    codes = _codes(codes)
+    N, Lz = codes.shape
+    K = int(K)
+    _check_sizes(N, Lz, K)
+    z = codes.double()
+    u = uniforms(K, seed, codes.device).double()
+    last = torch.tensor(N - 1, dtype=torch.int64, device=codes.device)
+    fallback = torch.minimum(torch.floor(u * N).to(torch.int64), last)      # [K]
+    idx = [fallback[0]]
+    d2 = ((z - z.index_select(0, idx[0].view(1))) ** 2).sum(dim=1)
+    for k in range(1, K):
+        c = torch.cumsum(d2, dim=0)
+        i = torch.minimum(torch.searchsorted(c, (u[k] * c[-1]).view(1), right=True)[0], last)
+        i = torch.where(c[-1] == 0, fallback[k], i)
+        idx.append(i)
+        d2 = torch.minimum(d2, ((z - z.index_select(0, i.view(1))) ** 2).sum(dim=1))
+    return torch.stack(idx)
+
+
+def _run(codes, logw, mu, sigma, reg_covar, n_iter, ws):
+    """n_iter iterations in place; (loglik_history [n_iter], counts [K]).  n_iter = 0: counts = the E-step's R_k at the start."""
+    N, Lz = codes.shape
+    K = logw.shape[0]
+    hist = torch.empty(n_iter, dtype=torch.float32, device=codes.device)
+    counts = torch.empty(K, dtype=torch.float32, device=codes.device)
+    L.check(L.lib.gmvae_mixfit_run(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(sigma), float(reg_covar), n_iter,
+                                   L.ptr(hist) if n_iter else None, L.ptr(counts), L.ptr(ws), L.current_stream()), "gmvae_mixfit_run")
+    if n_iter == 0:
+        counts = assign(codes, (logw, mu, sigma), ws)["log_resp"].double().exp().sum(dim=0).float()
+    return hist, counts
+
+
+def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
+    """EM for a K-component diagonal Gaussian mixture on codes [N, L]: a dict of `logw` [K], `mu` and `sigma` [K, L], `counts` [K]
+    (R_k of the last iteration), `loglik` (1/N sum_n ln p(z_n) at the returned parameters, from one assign pass after the run; a
+    0-d fp64 tensor), `loglik_history` [n_iter] (the value each iteration started from) and `centres` (the int64 [K] rows the
+    seeding chose).  The start: mu = the rows kmeanspp(codes, K, seed) chose, sigma = every component at the per-dimension standard
+    deviation of all codes (fp64, floored at sqrt(reg_covar)), logw = -ln K.  init = (logw, mu, sigma) replaces the seeding;
+    `centres` is then None.  n_init > 1 runs the seeds seed, seed + 1, ... and returns the run with the largest final `loglik`
+    (init and n_init > 1 exclude each other).  A fixed number of iterations, no stopping rule: the history is returned.
+    Everything stays on the device; nothing synchronises with the host."""
+    codes = _codes(codes)
+    N, Lz = codes.shape
+    K, n_iter, n_init = int(K), int(n_iter), int(n_init)
+    _check_sizes(N, Lz, K)
+    if n_iter < 0:
+        raise ValueError("n_iter must be >= 0")
+    if n_init < 1:
+        raise ValueError("n_init must be >= 1")
+    if not (math.isfinite(float(reg_covar)) and float(reg_covar) > 0):
+        raise ValueError("reg_covar must be a finite number > 0")
+    if init is not None and n_init != 1:
+        raise ValueError("init replaces the seeding: n_init must be 1")
+    dev = codes.device
+    ws = torch.empty(workspace_bytes(N, Lz, K), dtype=torch.uint8, device=dev)
+    runs = []
+    for j in range(n_init):
+        if init is not None:
+            logw, mu, sigma = _params(init, Lz, dev, K)
+            centres = None
+        else:
+            centres = kmeanspp(codes, K, int(seed) + j)
+            mu = codes.index_select(0, centres).contiguous()
+            sd = codes.double().std(dim=0, unbiased=False).clamp_min(math.sqrt(float(reg_covar)))
+            sigma = sd.float().expand(K, Lz).contiguous()
+            logw = torch.full((K,), -math.log(K), dtype=torch.float32, device=dev)
+        hist, counts = _run(codes, logw, mu, sigma, reg_covar, n_iter, ws)
+        loglik = assign(codes, (logw, mu, sigma), ws)["lse"].double().mean()
+        runs.append({"logw": logw, "mu": mu, "sigma": sigma, "counts": counts, "loglik": loglik, "loglik_history": hist,
+                     "centres": centres})
+    if n_init == 1:
+        return runs[0]
+    best = torch.stack([r["loglik"] for r in runs]).argmax().view(1)      # (a NaN loglik would win the argmax: it is then reported)
+    return {k: torch.stack([r[k] for r in runs]).index_select(0, best)[0] for k in runs[0]}
+
+
+def softplus_inverse(sigma):
+    """raw with softplus(raw) = sigma: sigma + ln(-expm1(-sigma)), evaluated in fp64, returned in fp32."""
+    s = sigma.double()
+    return (s + torch.log(-torch.expm1(-s))).float()
+
+
+def fit_latent(model, images, n_components, **kw):
+    """model.fit_latent_mixture: fit(model.transform(images), n_components, **kw) plus `log_resp` [N, K] of those codes."""
+    if n_components is None:
+        raise ValueError("n_components is required: this model has no mixture to take the number of components from")
+    codes = _codes(model.transform(images))
+    out = fit(codes, int(n_components), **kw)
+    out["log_resp"] = assign(codes, out)["log_resp"]
+    return out
+
+
+def checked_fit(fit_dict, K, Lz, dev):
+    """(logw, mu, sigma) of a fit for a prior of K components in L dimensions, or ValueError."""
+    try:
+        return _params(fit_dict, Lz, dev, K)
+    except ValueError as e:
+        raise ValueError(f"the fitted mixture does not match this model's prior (K = {K}, L = {Lz}): {e}") from None

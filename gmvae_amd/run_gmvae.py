@@ -58,6 +58,13 @@ def build_parser():
     a("--tsne_perplexity", type=float, default=40.0, help="--embed_latent: the perplexity (the reference's 40)")
     a("--tsne_iters", type=int, default=300, help="--embed_latent: the iterations (the reference's 300)")
     a("--embedding_out", default=None, help="--embed_latent: write latent_embedding to this .npy file")
+    a("--fit_latent_mixture", type=int, default=0, help="eval: also fit a diagonal Gaussian mixture of --mixture_components "
+      "components by EM on the device to the latent code of the first N examples of the split (gmvae_amd.mixfit.fit; seed "
+      "--random_seed, or 0) and assign the whole split -- latent_mixture_loglik, cluster_acc_latent_mixture (the VAE + GMM "
+      "baseline) and latent_mixture; 0 = off")
+    a("--mixture_fit_iters", type=int, default=100, help="--fit_latent_mixture: the EM iterations")
+    a("--mixture_fit_inits", type=int, default=1, help="--fit_latent_mixture: the seedings tried; the fit with the largest "
+      "log-likelihood is kept")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -140,6 +147,19 @@ def check_args(p, cfg):
             p.error("--tsne_iters must be >= 0")
     elif cfg.embedding_out:
         p.error("--embedding_out needs --embed_latent")
+    if cfg.fit_latent_mixture < 0:
+        p.error("--fit_latent_mixture must be >= 0 (0 = off)")
+    if cfg.fit_latent_mixture:
+        if cfg.mode != "eval":
+            p.error("--fit_latent_mixture needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--fit_latent_mixture fits one rank's codes: it is not available with more than one rank")
+        if cfg.fit_latent_mixture < cfg.mixture_components:
+            p.error("--fit_latent_mixture N needs N >= --mixture_components")
+        if cfg.mixture_fit_iters < 0:
+            p.error("--mixture_fit_iters must be >= 0")
+        if cfg.mixture_fit_inits < 1:
+            p.error("--mixture_fit_inits must be >= 1")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

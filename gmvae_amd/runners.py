@@ -17,7 +17,7 @@ from typing import Iterator, Tuple
 import numpy as np
 import torch
 
-from . import gmvae, parallel, tsne, utils, vae
+from . import gmvae, mixfit, parallel, tsne, utils, vae
 
 
 # ------------------------------------------------------------------ data
@@ -717,6 +717,10 @@ def run_eval(config):
     if em_n and not getattr(config, "data_dir", None) and not getattr(config, "data_npy", None):
         # a synthetic split's size is known before the pass (a file's is checked when its codes are in hand)
         _check_embed_size(config, em_n, min(em_n, int(getattr(config, "synthetic_size", 8192))), float(getattr(config, "tsne_perplexity", 40.0)))
+    # --fit_latent_mixture N: a mixture fitted to the code of the first N examples of the split, the whole split assigned (mixfit.fit)
+    mf_n = int(getattr(config, "fit_latent_mixture", 0) or 0)
+    if mf_n and world > 1:
+        raise ValueError("--fit_latent_mixture fits one rank's codes: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -864,4 +868,21 @@ def run_eval(config):
             print(f"{config.split}/embedding_kl: {res[f'{config.split}/embedding_kl']}")
         if getattr(config, "embedding_out", None):
             np.save(config.embedding_out, res["latent_embedding"].cpu().numpy())
+    if mf_n:
+        # the "VAE + GMM" baseline: EM on the first N codes, then every code of the split assigned to its component
+        K = int(config.mixture_components)
+        seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
+        mf_codes = res["latent_state"]
+        if mf_codes[:mf_n].shape[0] < K:
+            raise ValueError(f"--fit_latent_mixture {mf_n}: the {config.split} split holds {mf_codes.shape[0]} examples, fewer than "
+                             f"--mixture_components {K}")
+        fitted = mixfit.fit(mf_codes[:mf_n], K, n_iter=int(getattr(config, "mixture_fit_iters", 100)),
+                            n_init=int(getattr(config, "mixture_fit_inits", 1)), seed=seed)
+        whole = mixfit.assign(mf_codes, fitted)
+        res[f"{config.split}/latent_mixture_loglik"] = whole["lse"].double().mean().item()
+        res[f"{config.split}/cluster_acc_latent_mixture"] = utils.cluster_acc(whole["log_resp"], res["labels"], K).item()
+        res["latent_mixture"] = fitted
+        if rank == 0:
+            for k in ("latent_mixture_loglik", "cluster_acc_latent_mixture"):
+                print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
     return res

@@ -104,6 +104,30 @@ class TrainableVAE(VAE):
         and of kl_avg = mi + kl_marginal, tc, dim_kl, active_units."""
         return self._need_engine().aggregate_posterior(images, queries=queries, per_dim=per_dim)
 
+    def fit_latent_mixture(self, images, n_components=None, **kw):
+        """A diagonal Gaussian mixture fitted by EM on the device to the codes self.transform(images) -- the "VAE + GMM" baseline
+        (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init).  n_components defaults to the mixture prior's size
+        and is required for the plain VAE.  Returns fit's dict plus `log_resp` [N, K], the responsibilities of those images."""
+        from . import mixfit
+        if n_components is None and self.mix_components > 1:
+            n_components = self.mix_components
+        return mixfit.fit_latent(self, images, n_components, **kw)
+
+    def init_prior_from_mixture(self, fit):
+        """Starts the learned mixture prior (mixture_components > 1) from a fitted mixture (fit_latent_mixture's or
+        gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)): mixture_logits = logw, loc = mu, raw_scale_diag = softplus^-1(sigma) =
+        sigma + ln(-expm1(-sigma)).  Written through state_dict() / load_state_dict(), so whatever the engine derives from its
+        parameters is rebuilt.  Adam's slots are left as they are: the call is meant before training or between phases.
+        ValueError for the plain VAE (it has no mixture prior) and for a fit whose K or L is not the prior's."""
+        from . import mixfit
+        e = self._need_engine()
+        if self.mix_components <= 1:
+            raise ValueError("the plain VAE has no mixture prior to initialise (create_vae(mixture_components > 1))")
+        logw, mu, sigma = mixfit.checked_fit(fit, e.K, e.Lz, e.device)
+        sd = self.state_dict()
+        sd["mixture_logits"], sd["loc"], sd["raw_scale_diag"] = logw, mu, mixfit.softplus_inverse(sigma)
+        self.load_state_dict(sd)
+
     def predict_clusters(self, images, n_samples):
         """The component the model's posterior p(k | x) assigns each example to: an int64 [B] device tensor."""
         return self.posterior_component(images, n_samples).argmax(dim=1)

@@ -640,6 +640,40 @@ int gmvae_tsne_run(const float* codes, int64_t N, int L, const float* beta, cons
                    float* gains, int n_iter, int exaggeration_iters, float exaggeration, float lr, float* kl_history,
                    void* workspace, void* stream);
 
+/* A K-component diagonal Gaussian mixture fitted to N codes by EM on the device, and the responsibilities of a given mixture
+ * (model independent; gmvae_amd.mixfit.fit / assign, model.fit_latent_mixture, model.init_prior_from_mixture and run_eval's
+ * --fit_latent_mixture go through it; the reference has no counterpart).  The statement is tests/mixfit_ref.py.
+ * codes z [N][L], logw [K], mu / sigma [K][L], log_resp_out [N][K], lse_out [N], loglik_history [n_iter], counts_out [K]: fp32 in
+ * device memory.  A logw entry may be -inf: such a component contributes nothing and yields no NaN.  PRECONDITION: sigma > 0 (as
+ * for gmvae_mixture_logpdf_*; nothing clamps it here).
+ *   E-step:  l_nk = logw_k - 1/2 sum_d ((z_nd - mu_kd) / sigma_kd)^2 - sum_d ln sigma_kd - (L/2) ln 2 pi (the difference form, fp64
+ *     on the vector units: log r is a difference of numbers of the size of l, csrc/mixfit.hpp);  lse_n = logsumexp_k l_nk,
+ *     max-subtracted;  log r_nk = l_nk - lse_n;  r_nk = exp(log r_nk), an fp32 exponential.
+ *   M-step, centred at the current mean (the differences z_nd - mu_kd come first; no sum r z^2 - mean^2 form anywhere):
+ *     R_k = sum_n r_nk, S1_kd = sum_n r_nk (z_nd - mu_kd), S2_kd = sum_n r_nk (z_nd - mu_kd)^2, all three in fp64;
+ *     R'_k = R_k + 10 * 2^-52 (scikit-learn's constant), m_kd = S1_kd / R'_k, mu'_kd = mu_kd + m_kd,
+ *     sigma'_kd = sqrt(max(S2_kd / R'_k - m_kd^2, 0) + reg_covar), logw'_k = ln(R'_k / sum_j R'_j).  No component is special-cased:
+ *     an empty one keeps its mean, gets sigma = sqrt(reg_covar) and a weight of about 10 * 2^-52 / N.
+ *   gmvae_mixfit_assign: the E-step at the given parameters: log_resp_out and lse_out (each may be NULL).
+ *   gmvae_mixfit_run: n_iter iterations enqueued on `stream` with no host synchronisation, two launches each: iteration `it` runs
+ *     the E-step at the current parameters, records loglik_history [it] = 1/N sum_n lse_n (may be NULL; the value the iteration
+ *     started from, as kl_history does), then applies the M-step to logw, mu and sigma in place.  counts_out (may be NULL) = R_k of
+ *     the last iteration.  n_iter = 0 is a valid call that changes nothing.
+ * Sizes: 1 <= N <= 2^24, 1 <= L <= 4096, 1 <= K <= 256 and K L <= 16,384 -- the parameter image (mu and 1 / sigma) stays resident
+ * in the LDS of every workgroup, and at K L = 16,384 it takes 128 KiB of the 160 KiB; nothing needs to be a multiple of anything.
+ * The workspace (gmvae_mixfit_workspace_bytes(N, L, K)) holds the workgroups' fp64 partial sums, K (2 L + 1) + 1 values for each of
+ * at most 256 workgroups, and nothing per row; it needs no initialisation, and every call leaves it free for the next.  The caller
+ * owns every other byte: no call writes outside its outputs, the parameters (run) and the workspace.
+ * One owner per sum, fixed-order fp64 folds, no float atomics: two calls give the same bits.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (N < 1, N > 2^24, L < 1, L > 4096, K < 1, K > 256, K L > 16,384, n_iter < 0,
+ * reg_covar not finite and > 0); GMVAE_E_NULL (any pointer not marked "may be NULL"); GMVAE_E_ALIGN (float arrays 4 bytes, the
+ * workspace 16). */
+int gmvae_mixfit_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes);
+int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* sigma,
+                        float* log_resp_out, float* lse_out, void* workspace, void* stream);
+int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* sigma, float reg_covar,
+                     int n_iter, float* loglik_history, float* counts_out, void* workspace, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
