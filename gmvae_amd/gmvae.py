@@ -136,6 +136,15 @@ class TrainableGMVAE(GMVAE):
         from . import mixfit
         return mixfit.fit_latent(self, images, self.mix_components if n_components is None else n_components, **kw)
 
+    def neighbour_scores(self, images, labels=None, clusters=None, k=10, n_labels=10, **kw):
+        """The neighbourhood scores of the codes self.transform(images) (gmvae_amd.neighbours.scores): with `labels` knn_acc_loo (the
+        leave-one-out k-NN accuracy), silhouette_labels and their per-example tensors knn_pred and silhouette_labels_samples; with
+        `clusters` (an int tensor [N]) silhouette_clusters and silhouette_clusters_samples; with both nmi and ari.  clusters None: the
+        model's own clustering -- argmax q(y | x) over the mixture components.  The scores are 0-d device tensors; nothing
+        synchronises."""
+        from . import neighbours
+        return neighbours.model_scores(self, images, labels, clusters, k=k, n_labels=n_labels, **kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts p(z | y = k) from a fitted mixture (fit_latent_mixture's or gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)).
         prior_gmm is a Linear on the one-hot y with no hidden layer, so a table: its bias becomes 0 and row k of its weight (mu_k,

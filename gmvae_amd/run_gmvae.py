@@ -65,6 +65,12 @@ def build_parser():
     a("--mixture_fit_iters", type=int, default=100, help="--fit_latent_mixture: the EM iterations")
     a("--mixture_fit_inits", type=int, default=1, help="--fit_latent_mixture: the seedings tried; the fit with the largest "
       "log-likelihood is kept")
+    a("--neighbour_scores", type=int, default=0, help="eval: also score the latent code of the first N examples of the split by "
+      "its neighbourhoods on the device (gmvae_amd.neighbours) -- knn_acc_loo_{k}, silhouette_labels, and for a clustering the run "
+      "has in hand -- gmvae: argmax q(y|x); vae_gmp: the posterior over the prior's components, ONLY together with "
+      "--component_posterior_samples; vae: none -- silhouette_clusters, nmi_clusters and ari_clusters; with --fit_latent_mixture the same three for the fitted "
+      "mixture's assignment, with --embed_latent embedding_trustworthiness_{k} and embedding_continuity_{k}; 0 = off")
+    a("--knn_k", type=int, default=10, help="--neighbour_scores: the number of neighbours k")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -160,6 +166,15 @@ def check_args(p, cfg):
             p.error("--mixture_fit_iters must be >= 0")
         if cfg.mixture_fit_inits < 1:
             p.error("--mixture_fit_inits must be >= 1")
+    if cfg.neighbour_scores < 0:
+        p.error("--neighbour_scores must be >= 0 (0 = off)")
+    if cfg.neighbour_scores:
+        if cfg.mode != "eval":
+            p.error("--neighbour_scores needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--neighbour_scores scores one rank's codes: it is not available with more than one rank")
+        if not 1 <= cfg.knn_k <= 256 or not cfg.neighbour_scores > 2 * cfg.knn_k:
+            p.error("--neighbour_scores N needs --knn_k in [1, 256] and N > 2 * --knn_k")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

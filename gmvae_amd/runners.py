@@ -17,7 +17,7 @@ from typing import Iterator, Tuple
 import numpy as np
 import torch
 
-from . import gmvae, mixfit, parallel, tsne, utils, vae
+from . import gmvae, mixfit, neighbours, parallel, tsne, utils, vae
 
 
 # ------------------------------------------------------------------ data
@@ -721,6 +721,10 @@ def run_eval(config):
     mf_n = int(getattr(config, "fit_latent_mixture", 0) or 0)
     if mf_n and world > 1:
         raise ValueError("--fit_latent_mixture fits one rank's codes: it is not available with more than one rank")
+    # --neighbour_scores N: the code of the first N examples of the split scored by its neighbourhoods (neighbours.scores)
+    ns_n, ns_k, ns_logits = int(getattr(config, "neighbour_scores", 0) or 0), int(getattr(config, "knn_k", 10)), []
+    if ns_n and world > 1:
+        raise ValueError("--neighbour_scores scores one rank's codes: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -760,6 +764,8 @@ def run_eval(config):
             py_logits.append(o["logits"])
         if eng.real_valued and config.model == "gmvae":
             q_logits.append(o["logits"])
+        if ns_n and config.model == "gmvae" and first < ns_n:
+            ns_logits.append(o["logits"][:ns_n - first])
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
@@ -884,5 +890,38 @@ def run_eval(config):
         res["latent_mixture"] = fitted
         if rank == 0:
             for k in ("latent_mixture_loglik", "cluster_acc_latent_mixture"):
+                print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if ns_n:
+        # the model's own clustering, where it has one: the GMVAE's argmax q(y|x), the VAE_GMP's posterior over its prior's
+        # components (--component_posterior_samples); then the fitted mixture's assignment, then the embedding's neighbourhoods
+        K = int(config.mixture_components)
+        ns_codes, ns_labs = res["latent_state"][:ns_n], res["labels"][:ns_n].to(eng.device)
+        n = ns_codes.shape[0]
+        if not n > 2 * ns_k:
+            raise ValueError(f"--neighbour_scores {ns_n}: the {config.split} split holds {n} examples, too few for --knn_k {ns_k}, "
+                             f"which must be below examples / 2: lower --knn_k or evaluate a larger split")
+        n_labels = max(10, int(ns_labs.max().item()) + 1)                  # (as utils.cluster_acc widens its histogram)
+        if n_labels > neighbours.MAX_C:
+            raise ValueError(f"--neighbour_scores: the labels reach {n_labels - 1}, past the {neighbours.MAX_C} classes it takes")
+        clusters = (torch.cat(ns_logits).argmax(dim=1) if ns_logits else torch.cat(pc_rows)[:ns_n].argmax(dim=1) if pc_rows else None)
+        sc = neighbours.scores(ns_codes, ns_labs, clusters, k=ns_k, n_labels=n_labels, n_clusters=K if clusters is not None else None)
+        new = {f"knn_acc_loo_{ns_k}": sc["knn_acc_loo"], "silhouette_labels": sc["silhouette_labels"]}
+        if clusters is not None:
+            new.update(silhouette_clusters=sc["silhouette_clusters"], nmi_clusters=sc["nmi"], ari_clusters=sc["ari"])
+            res["neighbour_clusters"] = clusters                               # the clustering that was scored, [examples scored]
+        if mf_n:
+            assigned = whole["log_resp"][:ns_n].argmax(dim=1)
+            new.update(silhouette_latent_mixture=neighbours.silhouette(ns_codes, assigned, K)["score"],
+                       nmi_latent_mixture=neighbours.nmi(ns_labs, assigned, n_labels, K),
+                       ari_latent_mixture=neighbours.ari(ns_labs, assigned, n_labels, K))
+        if em_n:
+            m = min(n, res["latent_embedding"].shape[0])
+            if not m > 2 * ns_k:
+                raise ValueError(f"--neighbour_scores with --embed_latent {em_n}: {m} embedded examples are too few for --knn_k {ns_k}")
+            new[f"embedding_trustworthiness_{ns_k}"] = neighbours.trustworthiness(ns_codes[:m], res["latent_embedding"][:m], ns_k)
+            new[f"embedding_continuity_{ns_k}"] = neighbours.continuity(ns_codes[:m], res["latent_embedding"][:m], ns_k)
+        for k, v in new.items():
+            res[f"{config.split}/{k}"] = v.item()
+            if rank == 0:
                 print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
     return res

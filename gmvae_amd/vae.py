@@ -113,6 +113,15 @@ class TrainableVAE(VAE):
             n_components = self.mix_components
         return mixfit.fit_latent(self, images, n_components, **kw)
 
+    def neighbour_scores(self, images, labels=None, clusters=None, k=10, n_labels=10, **kw):
+        """The neighbourhood scores of the codes self.transform(images) (gmvae_amd.neighbours.scores): with `labels` knn_acc_loo (the
+        leave-one-out k-NN accuracy), silhouette_labels and their per-example tensors knn_pred and silhouette_labels_samples; with
+        `clusters` (an int tensor [N]) silhouette_clusters and silhouette_clusters_samples; with both nmi and ari.  clusters None: the
+        model's own clustering -- the mixture-prior VAE's predict_clusters(images, cluster_samples), 16 samples unless given, over
+        its mixture components; the plain VAE has none.  The scores are 0-d device tensors; nothing synchronises."""
+        from . import neighbours
+        return neighbours.model_scores(self, images, labels, clusters, k=k, n_labels=n_labels, **kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts the learned mixture prior (mixture_components > 1) from a fitted mixture (fit_latent_mixture's or
         gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)): mixture_logits = logw, loc = mu, raw_scale_diag = softplus^-1(sigma) =

@@ -674,6 +674,42 @@ int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float
 int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* sigma, float reg_covar,
                      int n_iter, float* loglik_history, float* counts_out, void* workspace, void* stream);
 
+/* Exact brute-force nearest neighbours of queries q [Nq][L] among references r [Nr][L] (fp32, device memory), the rank of given
+ * candidates in the same order, and distance sums per class (model independent; gmvae_amd.neighbours -- knn, the k-NN classifier,
+ * the silhouette, trustworthiness and continuity --, model.neighbour_scores and run_eval's --neighbour_scores go through it; the
+ * reference has no counterpart).  The statement is tests/neigh_ref.py; the kernels are csrc/neigh.hpp.
+ *   Distance: D_ij = sum_d (q_id - r_jd)^2 in the difference form, fp64 differences and sum (never |q|^2 + |r|^2 - 2 q.r, so never
+ *     the matrix cores);  d_ij = D_ij rounded once to fp32;  a non-finite d_ij counts as +inf.
+ *   Order: reference j precedes j' for query i when (d_ij, j) < (d_ij', j') lexicographically: ties in distance go to the smaller
+ *     index.  A total order, so every result below is independent of tiling, slicing and of how the caller chunks the queries.
+ *   Self: with self_offset >= 0 query i is reference row self_offset + i, which is left out of the order for that query; with
+ *     self_offset = -1 nothing is left out.
+ *   gmvae_knn_search: idx_out [Nq][k] (int32) and d2_out [Nq][k] (fp32) = the first k references in that order and their d,
+ *     ascending; either may be NULL, not both.
+ *   gmvae_knn_ranks: for candidates cand [Nq][m] (int32), rank_out [Nq][m] (int32) = the number of references (self left out) that
+ *     strictly precede cand[i][t] in query i's order; a candidate equal to self or outside [0, Nr) gets -1.  search and ranks build
+ *     d by the same device code: ranks(idx of search)[i][t] == t exactly.
+ *   gmvae_knn_class_sums: for labels [Nr] (int32), sums_out [Nq][C] (fp64) = sum over {j: labels_j = c} of sqrt(D_ij): the fp64
+ *     square root of the fp64 D, added in ascending j within slices of 1024 references, the slices in slice order.  A label outside
+ *     [0, C) contributes nowhere (an unlabelled reference).  Self is not excluded: it contributes sqrt(0).
+ * Sizes: 1 <= Nq <= 2^30, 1 <= Nr <= 2^24, 1 <= L <= 4096, 1 <= k, m <= 256, k <= Nr - (self_offset >= 0 ? 1 : 0), 1 <= C <= 256,
+ * self_offset in {-1} or [0, Nr - Nq]; nothing needs to be a multiple of anything.
+ * The workspace (gmvae_knn_workspace_bytes(Nq, Nr, L, k, C), which reads no device memory) holds d [Nq][Nr] or the class sums'
+ * parts per slice, whichever is larger: it follows Nq Nr -- the caller chooses Nq per call and chunks a larger set of queries --,
+ * needs no initialisation, and every call leaves it free for the next.  The caller owns every other byte: no call writes outside
+ * its outputs and the workspace, and every index written is in [0, Nr) whatever the inputs hold, NaN included.
+ * Everything is enqueued on `stream` with no host synchronisation.  One owner per output, integer counters, fixed-order fp64 folds,
+ * no float atomics: two calls give the same bits.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (the sizes above); GMVAE_E_NULL (any pointer not marked "may be NULL", or
+ * both of search's outputs); GMVAE_E_ALIGN (float and int arrays 4 bytes, sums_out 8, the workspace 16). */
+int gmvae_knn_workspace_bytes(int64_t Nq, int64_t Nr, int L, int k, int C, uint64_t* bytes);
+int gmvae_knn_search(const float* q, int64_t Nq, const float* r, int64_t Nr, int L, int k, int64_t self_offset, int32_t* idx_out,
+                     float* d2_out, void* workspace, void* stream);
+int gmvae_knn_ranks(const float* q, int64_t Nq, const float* r, int64_t Nr, int L, int64_t self_offset, const int32_t* cand, int m,
+                    int32_t* rank_out, void* workspace, void* stream);
+int gmvae_knn_class_sums(const float* q, int64_t Nq, const float* r, int64_t Nr, int L, const int32_t* labels, int C,
+                         double* sums_out, void* workspace, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
