@@ -74,6 +74,9 @@ def _load():
         "gmvae_mixfit_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
         "gmvae_mixfit_assign": ([vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
         "gmvae_mixfit_run": ([vp, i64, i32, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp], i32),
+        "gmvae_mixfit_full_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
+        "gmvae_mixfit_full_assign": ([vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "gmvae_mixfit_full_run": ([vp, i64, i32, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp], i32),
         "gmvae_knn_workspace_bytes": ([i64, i64, i32, i32, i32, C.POINTER(u64)], i32),
         "gmvae_knn_search": ([vp, i64, vp, i64, i32, i32, i64, vp, vp, vp, vp], i32),
         "gmvae_knn_ranks": ([vp, i64, vp, i64, i32, i64, vp, i32, vp, vp, vp], i32),

@@ -1,4 +1,4 @@
-// gmvae_mixfit_*: the host side of csrc/mixfit.hpp (include/gmvae_hip.h).  A translation unit of its own, for the reason at the top
+// gmvae_mixfit_* and gmvae_mixfit_full_*: the host side of csrc/mixfit.hpp and csrc/mixfit_full.hpp (include/gmvae_hip.h).  A translation unit of its own, for the reason at the top
 // of csrc/tsne.hip: the model-independent evaluator's kernels, descriptors and symbols stay out of the training step's code object.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -6,6 +6,7 @@
 
 #include "../../include/gmvae_hip.h"
 #include "mixfit.hpp"
+#include "mixfit_full.hpp"
 
 using namespace gmvae;
 
@@ -79,6 +80,95 @@ int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, f
                        p.tile, p.per_group, (float*)nullptr, (float*)nullptr, part, p.stride);
     hipLaunchKernelGGL(mixfit_update, dim3(update_blocks), dim3(kMfBlock), 0, st, part, p.groups, p.stride, (int)N, L, K, reg_covar, logw,
                        mu, sigma, loglik_history ? loglik_history + it : nullptr, it == n_iter - 1 ? counts_out : nullptr);
+  }
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ full covariances
+namespace {
+
+int mff_check_sizes(int64_t N, int L, int K) {
+  if (N < 1 || N > (1ll << 24) || L < 1 || L > kMffMaxL || K < 1 || K > 256 || (int64_t)K * L * L > kMffMaxKLL) return GMVAE_E_DIMS;
+  return 0;
+}
+
+// Workspace, in doubles: W [K][L (L + 1) / 2], sum ln C_dd [K], then the workgroups' partial sums [groups][stride].  Nothing per row.
+uint64_t mff_part_offset(int L, int K) { return (uint64_t)K * (uint64_t)mff_tri(L) + (uint64_t)K; }
+uint64_t mff_workspace_bytes(const MffPlan& p, int L, int K) {
+  return ((mff_part_offset(L, K) + (uint64_t)p.groups * (uint64_t)p.stride) * sizeof(double) + 15) / 16 * 16;
+}
+
+// one-shot per DEVICE: the kernels may ask for more than 64 KiB of dynamic LDS
+void mff_allow_lds() {
+  static bool seen[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+    if (seen[dev]) return;
+    seen[dev] = true;
+  }
+  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_factor), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_pass<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_pass<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmvae_mixfit_full_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes) {
+  if (int e = mff_check_sizes(N, L, K)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  *bytes = mff_workspace_bytes(mff_plan(N, L, K), L, K);
+  return 0;
+}
+
+int gmvae_mixfit_full_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* cov,
+                             float* log_resp_out, float* lse_out, int32_t* info_out, void* workspace, void* stream) {
+  if (int e = mff_check_sizes(N, L, K)) return e;
+  if (!codes || !logw || !mu || !cov || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(cov, 4) || !aligned_to(log_resp_out, 4) ||
+      !aligned_to(lse_out, 4) || !aligned_to(info_out, 4) || !aligned_to(workspace, 16))
+    return GMVAE_E_ALIGN;
+  const MffPlan p = mff_plan(N, L, K);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* const W = static_cast<double*>(workspace);
+  double* const sumlog = W + (size_t)K * mff_tri(L);
+  (void)hipGetLastError();
+  mff_allow_lds();
+  hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMffBlock), p.lds_factor, st, cov, L, W, sumlog, info_out, 1);
+  hipLaunchKernelGGL(mixfit_full_pass<false>, dim3((unsigned)p.groups), dim3(kMffBlock), p.lds, st, codes, (int)N, L, K, logw, mu,
+                     (const double*)W, (const double*)sumlog, p.tile, p.per_group, log_resp_out, lse_out, (double*)nullptr, p.stride);
+  return (int)hipGetLastError();
+}
+
+int gmvae_mixfit_full_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* cov, float reg_covar, int n_iter,
+                          float* loglik_history, float* counts_out, int32_t* info_out, void* workspace, void* stream) {
+  if (int e = mff_check_sizes(N, L, K)) return e;
+  if (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) return GMVAE_E_DIMS;
+  if (!codes || !logw || !mu || !cov || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(cov, 4) || !aligned_to(loglik_history, 4) ||
+      !aligned_to(counts_out, 4) || !aligned_to(info_out, 4) || !aligned_to(workspace, 16))
+    return GMVAE_E_ALIGN;
+  if (n_iter == 0) return 0;
+  const MffPlan p = mff_plan(N, L, K);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* const W = static_cast<double*>(workspace);
+  double* const sumlog = W + (size_t)K * mff_tri(L);
+  double* const part = W + mff_part_offset(L, K);
+  const unsigned update_blocks = (unsigned)((K * mff_tri(L) + kMfFoldSlots - 1) / kMfFoldSlots) + 1;
+  (void)hipGetLastError();
+  mff_allow_lds();
+  for (int it = 0; it < n_iter; ++it) {
+    hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMffBlock), p.lds_factor, st, (const float*)cov, L, W, sumlog, info_out,
+                       it == 0 ? 1 : 0);
+    hipLaunchKernelGGL(mixfit_full_pass<true>, dim3((unsigned)p.groups), dim3(kMffBlock), p.lds, st, codes, (int)N, L, K,
+                       (const float*)logw, (const float*)mu, (const double*)W, (const double*)sumlog, p.tile, p.per_group,
+                       (float*)nullptr, (float*)nullptr, part, p.stride);
+    hipLaunchKernelGGL(mixfit_full_update, dim3(update_blocks), dim3(kMfBlock), 0, st, (const double*)part, p.groups, p.stride, (int)N, L,
+                       K, reg_covar, logw, mu, cov, loglik_history ? loglik_history + it : nullptr,
+                       it == n_iter - 1 ? counts_out : nullptr);
   }
   return (int)hipGetLastError();
 }

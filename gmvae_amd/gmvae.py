@@ -131,7 +131,7 @@ class TrainableGMVAE(GMVAE):
 
     def fit_latent_mixture(self, images, n_components=None, **kw):
         """A diagonal Gaussian mixture fitted by EM on the device to the codes self.transform(images) -- the sampled code run_eval
-        stores in latent_state -- (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init).  n_components defaults to
+        stores in latent_state -- (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init, covariance).  n_components defaults to
         the model's mixture size.  Returns fit's dict plus `log_resp` [N, K], the responsibilities of those images."""
         from . import mixfit
         return mixfit.fit_latent(self, images, self.mix_components if n_components is None else n_components, **kw)

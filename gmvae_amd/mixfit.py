@@ -1,6 +1,8 @@
 """A diagonal Gaussian mixture fitted to latent codes by EM on the device (include/gmvae_hip.h gmvae_mixfit_*; csrc/mixfit.hpp):
 the "VAE + GMM" baseline of the deep-clustering tables, and the initialiser of a mixture prior from a pretrained encoder's codes
-(VaDE).  Model independent: codes are any fp32 [N, L] device tensor.  The statement is tests/mixfit_ref.py."""
+(VaDE).  Model independent: codes are any fp32 [N, L] device tensor.  The statement is tests/mixfit_ref.py.
+covariance="full" fits one L x L covariance per component instead (gmvae_mixfit_full_*; csrc/mixfit_full.hpp; the statement is
+tests/mixfit_full_ref.py): scikit-learn's GaussianMixture default, for codes whose clusters are not axis-aligned."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +13,8 @@ import torch
 from . import _lib as L
 
 MAX_N, MAX_L, MAX_K, MAX_KL = 1 << 24, 4096, 256, 16384      # the library's gate (include/gmvae_hip.h)
+MAX_L_FULL, MAX_KLL_FULL = 128, 1 << 20                      # ... and the full-covariance fit's
+COVARIANCES = ("diag", "full")
 
 
 def _check_sizes(N, Lz, K):
@@ -18,6 +22,19 @@ def _check_sizes(N, Lz, K):
         raise ValueError(f"codes must be [N, L] with 1 <= N <= 2^24 and 1 <= L <= {MAX_L}: got [{N}, {Lz}]")
     if not (1 <= K <= MAX_K and K * Lz <= MAX_KL):
         raise ValueError(f"K must lie in [1, {MAX_K}] with K * L <= {MAX_KL}: K = {K}, L = {Lz}")
+
+
+def _check_sizes_full(N, Lz, K):
+    if not (1 <= N <= MAX_N and 1 <= Lz <= MAX_L_FULL):
+        raise ValueError(f"covariance='full': codes must be [N, L] with 1 <= N <= 2^24 and 1 <= L <= {MAX_L_FULL}: got [{N}, {Lz}]")
+    if not (1 <= K <= MAX_K and K * Lz * Lz <= MAX_KLL_FULL):
+        raise ValueError(f"covariance='full': K must lie in [1, {MAX_K}] with K * L^2 <= 2^20: K = {K}, L = {Lz}")
+
+
+def full_workspace_bytes(N, Lz, K):
+    b = C.c_uint64()
+    L.check(L.lib.gmvae_mixfit_full_workspace_bytes(int(N), int(Lz), int(K), C.byref(b)), "gmvae_mixfit_full_workspace_bytes")
+    return b.value
 
 
 def workspace_bytes(N, Lz, K):
@@ -47,10 +64,50 @@ def _params(params, Lz, dev, K=None):
     return logw, mu, sigma
 
 
+def is_full(params):
+    """Whether `params` is a full-covariance mixture: a dict with `cov`, or a tuple whose third member is 3-D."""
+    if isinstance(params, dict):
+        return "cov" in params
+    return len(params) == 3 and torch.as_tensor(params[2]).dim() == 3
+
+
+def _params_full(params, Lz, dev, K=None):
+    """(logw [K], mu [K, L], cov [K, L, L]) as fresh contiguous fp32 device tensors, from a tuple or a dict with those keys."""
+    if isinstance(params, dict):
+        params = (params["logw"], params["mu"], params["cov"])
+    if len(params) != 3:
+        raise ValueError("a full-covariance mixture is (logw, mu, cov)")
+    logw, mu, cov = (torch.as_tensor(t).to(dev, torch.float32).contiguous().clone() for t in params)
+    if logw.dim() != 1 or mu.shape != (logw.shape[0], Lz) or cov.shape != (logw.shape[0], Lz, Lz) or (K is not None and logw.shape[0] != K):
+        raise ValueError(f"a full-covariance mixture is logw [K], mu [K, {Lz}], cov [K, {Lz}, {Lz}]"
+                         + (f" with K = {K}" if K is not None else "")
+                         + f": got {tuple(logw.shape)}, {tuple(mu.shape)}, {tuple(cov.shape)}")
+    return logw, mu, cov
+
+
+def _assign_full(codes, params, workspace=None):
+    N, Lz = codes.shape
+    logw, mu, cov = _params_full(params, Lz, codes.device)
+    K = logw.shape[0]
+    _check_sizes_full(N, Lz, K)
+    if workspace is None:
+        workspace = torch.empty(full_workspace_bytes(N, Lz, K), dtype=torch.uint8, device=codes.device)
+    log_resp = torch.empty(N, K, dtype=torch.float32, device=codes.device)
+    lse = torch.empty(N, dtype=torch.float32, device=codes.device)
+    info = torch.empty(K, dtype=torch.int32, device=codes.device)
+    L.check(L.lib.gmvae_mixfit_full_assign(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(cov), L.ptr(log_resp), L.ptr(lse),
+                                           L.ptr(info), L.ptr(workspace), L.current_stream()), "gmvae_mixfit_full_assign")
+    return {"log_resp": log_resp, "lse": lse, "info": info}
+
+
 def assign(codes, params, workspace=None):
     """The E-step of codes [N, L] under the mixture `params` = (logw, mu, sigma) or a dict with those keys (fit's): a dict of
-    `log_resp` [N, K] = ln r_nk and `lse` [N] = ln p(z_n)."""
+    `log_resp` [N, K] = ln r_nk and `lse` [N] = ln p(z_n).  A dict with `cov`, or a tuple whose third member is 3-D, is a
+    full-covariance mixture (logw, mu, cov [K, L, L]): the dict then also holds `info` [K] (int32), the factorisation's verdict on
+    each covariance -- 0, or j + 1 for the first pivot j that is not > 0, and that component's column of `log_resp` is -inf."""
     codes = _codes(codes)
+    if is_full(params):
+        return _assign_full(codes, params, workspace)
     N, Lz = codes.shape
     logw, mu, sigma = _params(params, Lz, codes.device)
     K = logw.shape[0]
@@ -108,7 +165,23 @@ def _run(codes, logw, mu, sigma, reg_covar, n_iter, ws):
     return hist, counts
 
 
-def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
+def _run_full(codes, logw, mu, cov, reg_covar, n_iter, ws):
+    """n_iter iterations in place; (loglik_history [n_iter], counts [K], info [K]).  n_iter = 0: counts and info of the start."""
+    N, Lz = codes.shape
+    K = logw.shape[0]
+    hist = torch.empty(n_iter, dtype=torch.float32, device=codes.device)
+    counts = torch.empty(K, dtype=torch.float32, device=codes.device)
+    info = torch.empty(K, dtype=torch.int32, device=codes.device)
+    L.check(L.lib.gmvae_mixfit_full_run(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(cov), float(reg_covar), n_iter,
+                                        L.ptr(hist) if n_iter else None, L.ptr(counts), L.ptr(info), L.ptr(ws), L.current_stream()),
+            "gmvae_mixfit_full_run")
+    if n_iter == 0:
+        a = _assign_full(codes, (logw, mu, cov), ws)
+        counts, info = a["log_resp"].double().exp().sum(dim=0).float(), a["info"]
+    return hist, counts, info
+
+
+def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None, covariance="diag"):
     """EM for a K-component diagonal Gaussian mixture on codes [N, L]: a dict of `logw` [K], `mu` and `sigma` [K, L], `counts` [K]
     (R_k of the last iteration), `loglik` (1/N sum_n ln p(z_n) at the returned parameters, from one assign pass after the run; a
     0-d fp64 tensor), `loglik_history` [n_iter] (the value each iteration started from) and `centres` (the int64 [K] rows the
@@ -116,11 +189,20 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
     deviation of all codes (fp64, floored at sqrt(reg_covar)), logw = -ln K.  init = (logw, mu, sigma) replaces the seeding;
     `centres` is then None.  n_init > 1 runs the seeds seed, seed + 1, ... and returns the run with the largest final `loglik`
     (init and n_init > 1 exclude each other).  A fixed number of iterations, no stopping rule: the history is returned.
+    covariance="full": one covariance per component -- `cov` [K, L, L] (symmetric) in place of `sigma`, and `info` [K] (int32: 0, or
+    j + 1 where a factorisation first met a pivot j that was not > 0; such a component sits that E-step out and restarts from
+    reg_covar I).  The same seeding and logw; cov_k = diag(sd^2) of all codes floored at reg_covar, so the first E-step is the
+    diagonal fit's.  init = (logw, mu, cov [K, L, L]).  L <= 128 and K L^2 <= 2^20.
     Everything stays on the device; nothing synchronises with the host."""
     codes = _codes(codes)
     N, Lz = codes.shape
     K, n_iter, n_init = int(K), int(n_iter), int(n_init)
+    if covariance not in COVARIANCES:
+        raise ValueError(f"covariance must be one of {COVARIANCES}: got {covariance!r}")
+    full = covariance == "full"
     _check_sizes(N, Lz, K)
+    if full:
+        _check_sizes_full(N, Lz, K)
     if n_iter < 0:
         raise ValueError("n_iter must be >= 0")
     if n_init < 1:
@@ -130,10 +212,15 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
     if init is not None and n_init != 1:
         raise ValueError("init replaces the seeding: n_init must be 1")
     dev = codes.device
-    ws = torch.empty(workspace_bytes(N, Lz, K), dtype=torch.uint8, device=dev)
+    ws = torch.empty(full_workspace_bytes(N, Lz, K) if full else workspace_bytes(N, Lz, K), dtype=torch.uint8, device=dev)
     runs = []
     for j in range(n_init):
-        if init is not None:
+        if init is not None and full:
+            if not is_full(init):
+                raise ValueError("covariance='full' takes init = (logw, mu, cov [K, L, L])")
+            logw, mu, cov = _params_full(init, Lz, dev, K)
+            centres = None
+        elif init is not None:
             logw, mu, sigma = _params(init, Lz, dev, K)
             centres = None
         else:
@@ -142,6 +229,15 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
             sd = codes.double().std(dim=0, unbiased=False).clamp_min(math.sqrt(float(reg_covar)))
             sigma = sd.float().expand(K, Lz).contiguous()
             logw = torch.full((K,), -math.log(K), dtype=torch.float32, device=dev)
+            if full:
+                var = codes.double().var(dim=0, unbiased=False).clamp_min(float(reg_covar))
+                cov = torch.diag(var).float().expand(K, Lz, Lz).contiguous()
+        if full:
+            hist, counts, info = _run_full(codes, logw, mu, cov, reg_covar, n_iter, ws)
+            loglik = _assign_full(codes, (logw, mu, cov), ws)["lse"].double().mean()
+            runs.append({"logw": logw, "mu": mu, "cov": cov, "counts": counts, "loglik": loglik, "loglik_history": hist,
+                         "centres": centres, "info": info})
+            continue
         hist, counts = _run(codes, logw, mu, sigma, reg_covar, n_iter, ws)
         loglik = assign(codes, (logw, mu, sigma), ws)["lse"].double().mean()
         runs.append({"logw": logw, "mu": mu, "sigma": sigma, "counts": counts, "loglik": loglik, "loglik_history": hist,
@@ -150,6 +246,31 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None):
         return runs[0]
     best = torch.stack([r["loglik"] for r in runs]).argmax().view(1)      # (a NaN loglik would win the argmax: it is then reported)
     return {k: torch.stack([r[k] for r in runs]).index_select(0, best)[0] for k in runs[0]}
+
+
+def n_parameters(K, Lz, covariance="diag"):
+    """The free parameters of a K-component mixture in L dimensions (scikit-learn's GaussianMixture._n_parameters): K - 1 weights,
+    K L means, and K L variances (diag) or K L (L + 1) / 2 covariance entries (full)."""
+    if covariance not in COVARIANCES:
+        raise ValueError(f"covariance must be one of {COVARIANCES}: got {covariance!r}")
+    K, Lz = int(K), int(Lz)
+    return K - 1 + K * Lz + (K * Lz * (Lz + 1) // 2 if covariance == "full" else K * Lz)
+
+
+def _fit_parameters(fit_dict):
+    K, Lz = fit_dict["mu"].shape
+    return n_parameters(K, Lz, "full" if "cov" in fit_dict else "diag")
+
+
+def bic(fit_dict, N):
+    """The Bayesian information criterion of a fit (either covariance) on the N codes it was fitted to: -2 N loglik + p ln N
+    (scikit-learn's definition; smaller is better).  A 0-d fp64 tensor; nothing synchronises with the host."""
+    return -2.0 * int(N) * fit_dict["loglik"].double() + _fit_parameters(fit_dict) * math.log(int(N))
+
+
+def aic(fit_dict, N):
+    """The Akaike information criterion: -2 N loglik + 2 p."""
+    return -2.0 * int(N) * fit_dict["loglik"].double() + 2.0 * _fit_parameters(fit_dict)
 
 
 def softplus_inverse(sigma):
@@ -170,6 +291,8 @@ def fit_latent(model, images, n_components, **kw):
 
 def checked_fit(fit_dict, K, Lz, dev):
     """(logw, mu, sigma) of a fit for a prior of K components in L dimensions, or ValueError."""
+    if is_full(fit_dict):
+        raise ValueError("the fitted mixture has full covariances and this model's priors are diagonal: fit with covariance='diag'")
     try:
         return _params(fit_dict, Lz, dev, K)
     except ValueError as e:

@@ -65,6 +65,11 @@ def build_parser():
     a("--mixture_fit_iters", type=int, default=100, help="--fit_latent_mixture: the EM iterations")
     a("--mixture_fit_inits", type=int, default=1, help="--fit_latent_mixture: the seedings tried; the fit with the largest "
       "log-likelihood is kept")
+    a("--mixture_covariance", default="diag", choices=["diag", "full"], help="--fit_latent_mixture: axis-aligned components, or "
+      "one full covariance per component (scikit-learn's GaussianMixture default; needs --latent_size <= 128); full: "
+      "latent_mixture carries cov and info in place of sigma")
+    a("--mixture_bic", action="store_true", help="--fit_latent_mixture: also report latent_mixture_bic, the Bayesian information "
+      "criterion of the fit on the examples it was fitted to (scikit-learn's definition; smaller is better)")
     a("--neighbour_scores", type=int, default=0, help="eval: also score the latent code of the first N examples of the split by "
       "its neighbourhoods on the device (gmvae_amd.neighbours) -- knn_acc_loo_{k}, silhouette_labels, and for a clustering the run "
       "has in hand -- gmvae: argmax q(y|x); vae_gmp: the posterior over the prior's components, ONLY together with "
@@ -166,6 +171,15 @@ def check_args(p, cfg):
             p.error("--mixture_fit_iters must be >= 0")
         if cfg.mixture_fit_inits < 1:
             p.error("--mixture_fit_inits must be >= 1")
+    if cfg.mixture_covariance != "diag":
+        if not cfg.fit_latent_mixture:
+            p.error("--mixture_covariance needs --fit_latent_mixture")
+        if cfg.latent_size > 128:
+            p.error("--mixture_covariance=full needs --latent_size <= 128")
+        if cfg.mixture_components * cfg.latent_size ** 2 > 1 << 20:
+            p.error("--mixture_covariance=full needs --mixture_components * --latent_size^2 <= 2^20")
+    if cfg.mixture_bic and not cfg.fit_latent_mixture:
+        p.error("--mixture_bic needs --fit_latent_mixture")
     if cfg.neighbour_scores < 0:
         p.error("--neighbour_scores must be >= 0 (0 = off)")
     if cfg.neighbour_scores:

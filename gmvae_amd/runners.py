@@ -883,13 +883,16 @@ def run_eval(config):
             raise ValueError(f"--fit_latent_mixture {mf_n}: the {config.split} split holds {mf_codes.shape[0]} examples, fewer than "
                              f"--mixture_components {K}")
         fitted = mixfit.fit(mf_codes[:mf_n], K, n_iter=int(getattr(config, "mixture_fit_iters", 100)),
-                            n_init=int(getattr(config, "mixture_fit_inits", 1)), seed=seed)
+                            n_init=int(getattr(config, "mixture_fit_inits", 1)), seed=seed,
+                            covariance=getattr(config, "mixture_covariance", "diag"))
         whole = mixfit.assign(mf_codes, fitted)
         res[f"{config.split}/latent_mixture_loglik"] = whole["lse"].double().mean().item()
         res[f"{config.split}/cluster_acc_latent_mixture"] = utils.cluster_acc(whole["log_resp"], res["labels"], K).item()
         res["latent_mixture"] = fitted
+        if getattr(config, "mixture_bic", False):
+            res[f"{config.split}/latent_mixture_bic"] = mixfit.bic(fitted, mf_codes[:mf_n].shape[0]).item()
         if rank == 0:
-            for k in ("latent_mixture_loglik", "cluster_acc_latent_mixture"):
+            for k in ("latent_mixture_loglik", "cluster_acc_latent_mixture") + (("latent_mixture_bic",) if getattr(config, "mixture_bic", False) else ()):
                 print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
     if ns_n:
         # the model's own clustering, where it has one: the GMVAE's argmax q(y|x), the VAE_GMP's posterior over its prior's

@@ -106,7 +106,7 @@ class TrainableVAE(VAE):
 
     def fit_latent_mixture(self, images, n_components=None, **kw):
         """A diagonal Gaussian mixture fitted by EM on the device to the codes self.transform(images) -- the "VAE + GMM" baseline
-        (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init).  n_components defaults to the mixture prior's size
+        (gmvae_amd.mixfit.fit(**kw): n_iter, n_init, reg_covar, seed, init, covariance).  n_components defaults to the mixture prior's size
         and is required for the plain VAE.  Returns fit's dict plus `log_resp` [N, K], the responsibilities of those images."""
         from . import mixfit
         if n_components is None and self.mix_components > 1:

@@ -674,6 +674,51 @@ int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float
 int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* sigma, float reg_covar,
                      int n_iter, float* loglik_history, float* counts_out, void* workspace, void* stream);
 
+/* The same with FULL covariances: a K-component Gaussian mixture with one L x L covariance per component, fitted by EM on the
+ * device (scikit-learn's GaussianMixture default, covariance_type = 'full'; gmvae_amd.mixfit.fit(covariance="full") / assign,
+ * model.fit_latent_mixture(covariance="full") and run_eval's --mixture_covariance=full go through it).  The statement is
+ * tests/mixfit_full_ref.py; the kernels are csrc/mixfit_full.hpp.
+ * codes z [N][L], logw [K], mu [K][L], cov [K][L][L], log_resp_out [N][K], lse_out [N], loglik_history [n_iter], counts_out [K]:
+ * fp32 in device memory; info_out [K]: int32.  Only the lower triangle of cov (diagonal included) is read.  A logw entry may be -inf.
+ *   Factor, on the device in fp64, a workgroup per component: C_k = the lower Cholesky factor of that triangle, pivots
+ *     p_j = a_jj - sum_{i<j} C_ji^2.  A pivot that is not > 0 (NaN included) gives info_k = j + 1 for the first such j (LAPACK's
+ *     convention), else info_k = 0.  A component with info_k != 0 is absent from that E-step: l_nk = -inf for every n, exactly as a
+ *     logw_k of -inf behaves, and no NaN anywhere else.  W_k = C_k^-1 and sum_d ln C_k,dd go to the workspace.
+ *   E-step:  l_nk = logw_k - 1/2 |W_k (z_n - mu_k)|^2 - sum_d ln C_k,dd - (L/2) ln 2 pi, a triangular product in fp64;  lse, log r
+ *     and r as in gmvae_mixfit_*.
+ *   M-step, centred at the current mean (no sum r z z^T - mean mean^T form anywhere):  R_k = sum_n r_nk, S1_kd = sum_n r_nk
+ *     (z_nd - mu_kd), S2_kde = sum_n r_nk (z_nd - mu_kd) (z_ne - mu_ke), all in fp64 (S2 on v_mfma_f64_16x16x4_f64, the blocks on or
+ *     below the diagonal only);  R'_k = R_k + 10 * 2^-52, m = S1 / R', mu' = mu + m, cov'_kde = S2_kde / R' - m_d m_e, its diagonal
+ *     max(., 0) + reg_covar, written to both triangles (bit-symmetric);  logw'_k = ln(R'_k / sum_j R'_j).  No component is
+ *     special-cased: an empty or absent one keeps its mean and gets cov' = reg_covar I, so it is positive definite again in the
+ *     next iteration.
+ *   gmvae_mixfit_full_assign: factor and the E-step at the given parameters: log_resp_out, lse_out and info_out (each may be NULL);
+ *     info_out = this call's info_k.  Two launches.
+ *   gmvae_mixfit_full_run: n_iter iterations enqueued on `stream` with no host synchronisation, three launches each (factor, pass,
+ *     update): iteration `it` factors, runs the E-step, records loglik_history [it] = 1/N sum_n lse_n (may be NULL), then applies
+ *     the M-step to logw, mu and cov in place (rounded to fp32: the arrays are fp32).  counts_out (may be NULL) = R_k of the last
+ *     iteration.  info_out (may be NULL): iteration 0 stores its info_k, a later iteration stores only over a 0 -- the caller sees a
+ *     component's first failure and initialises nothing.  n_iter = 0 is a valid call that changes nothing.
+ * Sizes: 1 <= N <= 2^24, 1 <= L <= 128 (one component's packed fp64 triangle is 66,048 bytes, and the factor kernel holds two in
+ * the 160 KiB LDS), 1 <= K <= 256 and K L^2 <= 2^20; nothing needs to be a multiple of anything.
+ * The workspace (gmvae_mixfit_full_workspace_bytes(N, L, K)), with P = L (L + 1) / 2, is
+ *     8 (K P + K + G (K (P + L + 1) + 1)) bytes rounded up to 16:  W [K][P], sum ln C_dd [K], and for each of G row slices the partial
+ *     sums S2 [K][P], S1 [K][L], R [K] and sum lse (all fp64), nothing per row;
+ *     G = ceil(N / per), per = ceil(tiles / g) T, tiles = ceil(N / T), g = min(tiles, 256, floor(2^23 / (K (P + L + 1) + 1))),
+ *     T = min(64, floor((163,840 - 8 (P + L)) / (8 ((L | 1) + (K | 1) + 3) + 4 (L | 1)))) rounded down to a multiple of 4 -- so at most
+ *     256 slices and 64 MiB of partial sums.
+ * It needs no initialisation, and every call leaves it free for the next.  The caller owns every other byte: no call writes
+ * outside its non-NULL outputs, the parameters (run) and the workspace.
+ * One owner per sum, fixed-order fp64 folds, no float atomics: two calls give the same bits, on any workspace contents.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (N < 1, N > 2^24, L < 1, L > 128, K < 1, K > 256, K L^2 > 2^20, n_iter < 0,
+ * reg_covar not finite and > 0); GMVAE_E_NULL (any pointer not marked "may be NULL"); GMVAE_E_ALIGN (float and int32 arrays 4
+ * bytes, the workspace 16). */
+int gmvae_mixfit_full_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes);
+int gmvae_mixfit_full_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* cov,
+                             float* log_resp_out, float* lse_out, int32_t* info_out, void* workspace, void* stream);
+int gmvae_mixfit_full_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* cov, float reg_covar,
+                          int n_iter, float* loglik_history, float* counts_out, int32_t* info_out, void* workspace, void* stream);
+
 /* Exact brute-force nearest neighbours of queries q [Nq][L] among references r [Nr][L] (fp32, device memory), the rank of given
  * candidates in the same order, and distance sums per class (model independent; gmvae_amd.neighbours -- knn, the k-NN classifier,
  * the silhouette, trustworthiness and continuity --, model.neighbour_scores and run_eval's --neighbour_scores go through it; the
