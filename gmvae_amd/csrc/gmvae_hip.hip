@@ -2777,7 +2777,10 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
         hipLaunchKernelGGL(ymarg_dw, dim3((unsigned)(ya.p[0].blocks + ya.p[1].blocks)), dim3(256), 0, st, ya);
         rowk(cx, "ymarg_dw");
       } else {
-      const int nsy = small_ns((long long)K * G.dim[1]);
+      int nsy = small_ns((long long)K * G.dim[1]);
+      // (D * H0 % 4 != 0: finalize_grads adds whole float4s, and the one the x and y rows share lies in the x rows' range -- with
+      //  a count of their own the y rows' first elements lost every slab beyond the x rows' whenever the two counts differed)
+      if (((uint64_t)D * G.dim[1]) % 4) nsy = nsx;
       if (nsy != NS) brange(G.w[0] + (uint64_t)D * G.dim[1], (uint64_t)K * G.dim[1], nsy);
       g.add(p_tn(w.y, false, K, 1, dcur, G.dim[1], K, G.dim[1], R, sl + G.w[0] + (uint64_t)D * G.dim[1], nullptr, nsy,
                  PP, nullptr));
