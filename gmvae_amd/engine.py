@@ -164,6 +164,31 @@ def check_clip_norm(clip_norm):
     return c
 
 
+AIS_SCHEDULES = ("sigmoid", "linear")
+
+
+def ais_schedule(schedule, n_temps: int) -> torch.Tensor:
+    """The annealing path of Engine.ais_bound as a float64 CPU tensor beta_0 = 0 < ... < beta_T = 1: "linear" -- t / T --,
+    "sigmoid" -- (s(4 (2 t / T - 1)) - s(-4)) / (s(4) - s(-4)), s the logistic function (Wu et al. 2017: more temperatures near
+    both ends) -- or a tensor of n_temps + 1 values, which is checked."""
+    T = int(n_temps)
+    if isinstance(schedule, str):
+        if schedule not in AIS_SCHEDULES:
+            raise ValueError(f"schedule must be one of {AIS_SCHEDULES} or a tensor, got {schedule!r}")
+        t = torch.arange(T + 1, dtype=torch.float64)
+        if schedule == "linear":
+            b = t / T
+        else:
+            s = lambda v: torch.sigmoid(torch.as_tensor(v, dtype=torch.float64))
+            b = (s(4.0 * (2.0 * t / T - 1.0)) - s(-4.0)) / (s(4.0) - s(-4.0))
+        b[0], b[-1] = 0.0, 1.0
+        return b
+    b = torch.as_tensor(schedule).detach().to("cpu", torch.float64).reshape(-1)
+    if b.numel() != T + 1 or float(b[0]) != 0.0 or float(b[-1]) != 1.0 or not bool((b[1:] > b[:-1]).all()):
+        raise ValueError(f"a schedule tensor holds n_temps + 1 = {T + 1} increasing values from 0 to 1")
+    return b
+
+
 def _check_labels(engine, y_observed, B):
     if y_observed.dtype.is_floating_point or y_observed.dtype == torch.bool or y_observed.numel() != B:
         raise ValueError(f"y_observed must be an int tensor of {B} observed components (-1: unlabelled)")
@@ -841,6 +866,70 @@ class Engine:
         (lj, lp, stats), tail = self._chunked_eval("posterior_component", x, n_samples, chunk, row0)
         return dict(log_joint=lj, log_post=lp, bound=stats[:, 0], entropy=stats[:, 1], kl_post_prior=stats[:, 2],
                     ess=stats[:, 3], tail=tail)
+
+    def ais_bound(self, x, n_chains: int = 16, n_temps: int = 1000, schedule="sigmoid", n_leapfrog: int = 10,
+                  step_size: float = 0.05, init: str = "prior", adapt: bool = True, row0: Optional[int] = None,
+                  eps: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, step_up: float = 1.02,
+                  step_down: float = 0.96):
+        """log p(x) by annealed importance sampling with HMC transitions (include/gmvae_hip.h gmvae_ais; Neal 2001; Wu et al.
+        2017): n_chains chains per example anneal from the base to p(z) p(x|z) over n_temps temperatures, n_leapfrog leapfrog
+        steps of step_size per transition.  It uses the generative model alone, so -- unlike iw_bound, iw_bound_enum_y and the
+        posteriors, which are importance sampling from the inference network -- its gap says nothing about q, and it tightens
+        towards log p(x) as n_temps grows: iw_bound far below ais_bound is a weak encoder, both low a weak decoder.
+        init: "prior" -- the chains start from p(z) -- or "encoder": from the example's inference mixture (_latent_components:
+        q(z|x), for the GMVAE sum_k q(k|x) q(z|x, e_k)), a shorter path for the same target.
+        schedule: "sigmoid" -- beta_t = (s(4 (2 t / T - 1)) - s(-4)) / (s(4) - s(-4)) --, "linear", or a tensor of n_temps + 1
+        increasing values from 0 to 1.
+        adapt: every chain multiplies its step size by step_up after an accepted transition and step_down after a rejected one
+        (1.02 and 0.96: their fixed point is an acceptance rate of ln(1 / 0.96) / (ln 1.02 + ln(1 / 0.96)) = 0.67), clipped to
+        [1e-4, 1].  adapt=False keeps step_size: that is the strictly valid AIS -- an adapted step depends on the chain's past,
+        so the adapted estimate is not exactly unbiased in the weights; in practice the difference is far below the chains'
+        standard error.
+        Returns dict(bound [B] = logsumexp_c log w - ln n_chains, logw [B, n_chains], stats [B, 4] = (bound, effective sample
+        size of the chains' weights, mean acceptance rate, mean final step size), z [B n_chains, L] = the chains' final states
+        (approximate posterior samples), tail [8] = the batch sums of (-bound, ESS, acceptance rate, step size), B).  For the
+        GMVAE the bound estimates log p(x) itself, the uniform p(y) inside: it is comparable to iw_bound_enum_y's bound MINUS ln K
+        (that one leaves the + ln K out).
+        Chain c of row b draws Philox row (row0 + b) * n_chains + c keyed by (noise_seed, global_step * (n_temps + 1) + t), row0
+        defaulting to rank * B: the result does not depend on the batch size or the sharding.  eps [n_temps + 1, B n_chains, L] and
+        u [n_temps + 1, B n_chains] replace the draw (tests).  Bernoulli likelihood only; not with pixel_mask."""
+        if self.pixel_mask or self.likelihood != "bernoulli":
+            raise ValueError("ais_bound scores the Bernoulli likelihood on every pixel: not available with pixel_mask=True or "
+                             f"likelihood={self.likelihood!r}")
+        if init not in ("prior", "encoder"):
+            raise ValueError(f"init must be 'prior' or 'encoder', got {init!r}")
+        C_, T, nl = int(n_chains), int(n_temps), int(n_leapfrog)
+        if C_ < 1 or T < 1 or nl < 1:
+            raise ValueError(f"n_chains, n_temps and n_leapfrog must be >= 1, got {C_}, {T}, {nl}")
+        if not (0.0 < float(step_size) < float("inf")):
+            raise ValueError(f"step_size must be positive and finite, got {step_size}")
+        betas = ais_schedule(schedule, T).to(self.device, torch.float32).contiguous()
+        x = self._prep_x(x)
+        B = x.shape[0]
+        d = self.dims(B, 1, row0)
+        base, base_K = None, 0
+        if init == "encoder":
+            logpi, mu, sigma = self._latent_components(x)
+            base_K = logpi.shape[1]
+            base = torch.cat([logpi.reshape(B, base_K), mu.reshape(B, -1), sigma.reshape(B, -1)], dim=1).contiguous()
+        n = B * C_
+        eps = self._prep_noise(eps, (T + 1) * n, self.Lz)
+        u = self._prep_noise(u, (T + 1) * n, 1)
+        up, down = (float(step_up), float(step_down)) if adapt else (1.0, 1.0)
+        nw = L.ais_workspace_bytes(d, self.model, base_K, C_) // 4 + 64
+        ws = self._chunked_ws.get(("ais", B, C_, base_K))
+        if ws is None or ws.numel() < nw:
+            ws = self._chunked_ws[("ais", B, C_, base_K)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        o = dict(logw=torch.empty(B, C_, **f32), bound=torch.empty(B, **f32), stats=torch.empty(B, 4, **f32),
+                 z=torch.empty(n, self.Lz, **f32), tail=torch.empty(L.TAIL, **f32))
+        rc = L.lib.gmvae_ais(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(base), base_K, L.ptr(betas), T, C_, nl,
+                             float(step_size), up, down, L.ptr(eps), L.ptr(u), L.ptr(o["logw"]), L.ptr(o["bound"]),
+                             L.ptr(o["stats"]), L.ptr(o["z"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
+                             L.current_stream())
+        L.check(rc, "gmvae_ais")
+        self._keep_ais = (x, base, betas, eps, u)
+        return o
 
     AGG_CHUNK = 2048               # default examples per pass of aggregate_posterior (K rows each for the GMVAE)
 

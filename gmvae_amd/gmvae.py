@@ -119,6 +119,13 @@ class TrainableGMVAE(GMVAE):
         a [B] device tensor (Engine.iw_bound_enum_y)."""
         return self._need_engine().iw_bound_enum_y(images, n_samples, chunk)["bound"]
 
+    def ais_bound(self, images, n_chains=16, n_temps=1000, **kw):
+        """log p(x) per example by annealed importance sampling with HMC transitions, from the generative model alone -- its gap
+        does not depend on the inference network, unlike iw_bound's --: Engine.ais_bound's dict (bound [B], logw [B, n_chains],
+        stats [B, 4] = bound, ESS, acceptance rate, step size; z; tail).  **kw: schedule, n_leapfrog, step_size, init, adapt.
+        The bound is of log p(x) itself, the uniform p(y) inside: iw_bound_enum_y's bound minus ln K; the same for every y_inference."""
+        return self._need_engine().ais_bound(images, n_chains, n_temps, **kw)
+
     def posterior_y(self, images, n_samples, chunk=None):
         """ln p(y = k | x) of the model itself (not the inference network's q(y|x)), by importance sampling with n_samples
         samples of z per component, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_y)."""

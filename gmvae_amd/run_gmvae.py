@@ -42,6 +42,15 @@ def build_parser():
     a("--iw_enum_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the importance-weighted "
       "bound with y summed out over the mixture components at this many samples per example and component "
       "(Engine.iw_bound_enum_y); 0 = off")
+    a("--ais_chains", type=int, default=0, help="eval: also estimate log p(x) by annealed importance sampling with HMC transitions "
+      "from the generative model alone (Engine.ais_bound), this many chains per example; reports ais_log_px, the chains' "
+      "effective sample size and acceptance rate, and the gap to the importance-weighted bound when --iw_samples (gmvae: "
+      "--iw_enum_samples) is given too; needs --ais_temps; 0 = off")
+    a("--ais_temps", type=int, default=0, help="--ais_chains: the number of temperatures of the annealing path")
+    a("--ais_leapfrog", type=int, default=10, help="--ais_chains: leapfrog steps per HMC transition")
+    a("--ais_step_size", type=float, default=0.05, help="--ais_chains: the initial leapfrog step size (adapted per chain)")
+    a("--ais_init", default="prior", choices=["prior", "encoder"], help="--ais_chains: the chains' base distribution")
+    a("--ais_schedule", default="sigmoid", choices=["sigmoid", "linear"], help="--ais_chains: the annealing path")
     a("--posterior_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the model's own "
       "posterior p(y|x) by importance sampling at this many samples per example and component (Engine.posterior_y) -- its "
       "clustering accuracy next to q(y|x)'s, its entropy, KL(q(y|x) || p(y|x)) and the effective sample size; 0 = off")
@@ -189,6 +198,17 @@ def check_args(p, cfg):
             p.error("--neighbour_scores scores one rank's codes: it is not available with more than one rank")
         if not 1 <= cfg.knn_k <= 256 or not cfg.neighbour_scores > 2 * cfg.knn_k:
             p.error("--neighbour_scores N needs --knn_k in [1, 256] and N > 2 * --knn_k")
+    if cfg.ais_chains < 0 or cfg.ais_temps < 0:
+        p.error("--ais_chains and --ais_temps must be >= 0 (0 = off)")
+    if bool(cfg.ais_chains) != bool(cfg.ais_temps):
+        p.error("--ais_chains and --ais_temps go together")
+    if cfg.ais_chains:
+        if cfg.mode != "eval":
+            p.error("--ais_chains needs --mode=eval")
+        if cfg.ais_leapfrog < 1 or not (cfg.ais_step_size > 0 and cfg.ais_step_size < float("inf")):
+            p.error("--ais_leapfrog must be >= 1 and --ais_step_size a finite number > 0")
+        if cfg.missing_rate > 0 or cfg.likelihood != "bernoulli":
+            p.error("--ais_chains scores the Bernoulli likelihood on every pixel: not available with --missing_rate or --likelihood")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

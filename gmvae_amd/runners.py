@@ -703,6 +703,8 @@ def run_eval(config):
     iw_n, iw_chunk, iw_rows = int(getattr(config, "iw_samples", 0) or 0), getattr(config, "iw_chunk", None), []
     # --iw_enum_samples N: the same with y summed out over the mixture components (GMVAE, either --y_inference), keyed alike
     ie_n, ie_rows = int(getattr(config, "iw_enum_samples", 0) or 0), []
+    # --ais_chains C --ais_temps T: log p(x) by annealed importance sampling from the generative model alone, keyed alike
+    ais_c, ais_t, ais_rows = int(getattr(config, "ais_chains", 0) or 0), int(getattr(config, "ais_temps", 0) or 0), []
     # --posterior_samples N: the model's own posterior p(y|x) by importance sampling per component (GMVAE), keyed alike
     py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
     # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
@@ -742,6 +744,11 @@ def run_eval(config):
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
         if ie_n > 0:
             ie_rows.append(eng.iw_bound_enum_y(images, ie_n, chunk=iw_chunk, row0=first)["bound"])
+        if ais_c > 0:
+            ais_rows.append(eng.ais_bound(images, ais_c, ais_t, schedule=getattr(config, "ais_schedule", "sigmoid"),
+                                          n_leapfrog=int(getattr(config, "ais_leapfrog", 10)),
+                                          step_size=float(getattr(config, "ais_step_size", 0.05)),
+                                          init=getattr(config, "ais_init", "prior"), row0=first)["stats"])
         o = eng.forward(images, mask=mk)
         tot += o["tail"][:5]
         pm_tot += o["tail"][5:8].double()
@@ -770,8 +777,11 @@ def run_eval(config):
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
     pc_tot = torch.cat(pc_stats).double().sum(0) if pc_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
+    ais_tot = torch.cat(ais_rows).double().sum(0) if ais_rows else torch.zeros(4, dtype=torch.float64, device=eng.device)
     if world > 1:
         parallel.all_reduce_flat(tot)
+        if ais_c > 0:
+            parallel.all_reduce_flat(ais_tot)
         parallel.all_reduce_flat(iw_sum)
         parallel.all_reduce_flat(class_hits)
         parallel.all_reduce_flat(pm_tot)
@@ -807,6 +817,18 @@ def run_eval(config):
         res[f"{config.split}/iw_bound_{iw_n}_per_example"] = iw_sum.item() / n
     if ie_n > 0:
         res[f"{config.split}/iw_bound_enum_y_{ie_n}_per_example"] = ie_sum.item() / n
+    if ais_c > 0:
+        # log p(x) itself (the GMVAE's uniform p(y) inside): the gap to an importance-weighted bound is what the inference
+        # network loses; iw_bound_enum_y leaves a + ln K out, which the gap puts back
+        res[f"{config.split}/ais_log_px"] = ais_tot[0].item() / n
+        res[f"{config.split}/ais_ess"] = ais_tot[1].item() / n
+        res[f"{config.split}/ais_accept_rate"] = ais_tot[2].item() / n
+        res[f"{config.split}/ais_step_size"] = ais_tot[3].item() / n
+        if ie_n > 0:
+            res[f"{config.split}/ais_gap_to_iw_bound_enum_y"] = ((ais_tot[0].item() - ie_sum.item()) / n
+                                                                 + math.log(int(config.mixture_components)))
+        elif iw_n > 0 and config.model != "gmvae":
+            res[f"{config.split}/ais_gap_to_iw_bound"] = (ais_tot[0].item() - iw_sum.item()) / n
     if py_n > 0:
         # clustering accuracy over the WHOLE split (the ranks' histograms add), by the model's posterior and by q(y|x)
         K, all_labs = int(config.mixture_components), torch.cat(labs)
@@ -843,6 +865,7 @@ def run_eval(config):
     res["labels"] = torch.cat(labs) if labs else None
     res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
     res["iw_bounds_enum_y"] = torch.cat(ie_rows) if ie_rows else None
+    res["ais_stats"] = torch.cat(ais_rows) if ais_rows else None     # [..., 4]: log p(x) estimate, ESS, acceptance rate, step size
     if py_n > 0:
         res["log_posterior_y"] = torch.cat(py_rows)                  # [this rank's examples, K], in split order
         res["posterior_y_stats"] = torch.cat(py_stats)               # [..., 4]: bound, entropy, KL(q || p(y|x)), ESS

@@ -94,6 +94,12 @@ class TrainableVAE(VAE):
         a [B] device tensor (Engine.iw_bound).  mask: the bound on log p(x_observed)."""
         return self._need_engine().iw_bound(images, n_samples, chunk, mask=mask)["bound"]
 
+    def ais_bound(self, images, n_chains=16, n_temps=1000, **kw):
+        """log p(x) per example by annealed importance sampling with HMC transitions, from the generative model alone -- its gap
+        does not depend on the inference network, unlike iw_bound's --: Engine.ais_bound's dict (bound [B], logw [B, n_chains],
+        stats [B, 4] = bound, ESS, acceptance rate, step size; z; tail).  **kw: schedule, n_leapfrog, step_size, init, adapt."""
+        return self._need_engine().ais_bound(images, n_chains, n_temps, **kw)
+
     def posterior_component(self, images, n_samples, chunk=None):
         """ln p(k | x) over the components of the learned mixture prior (mixture_components > 1), by importance sampling with
         n_samples samples of z, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_component)."""

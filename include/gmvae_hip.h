@@ -755,6 +755,56 @@ int gmvae_knn_ranks(const float* q, int64_t Nq, const float* r, int64_t Nr, int 
 int gmvae_knn_class_sums(const float* q, int64_t Nq, const float* r, int64_t Nr, int L, const int32_t* labels, int C,
                          double* sums_out, void* workspace, void* stream);
 
+/* log p(x) by annealed importance sampling (AIS) with Hamiltonian Monte Carlo transitions (Neal 2001; Wu, Burda, Salakhutdinov &
+ * Grosse 2017): the generative model alone, so -- unlike gmvae_iw_bound* -- its gap does not depend on the inference network, and
+ * it tightens towards log p(x) as n_temps grows (Engine.ais_bound, model.ais_bound and run_gmvae --mode=eval --ais_chains go
+ * through it; the reference has no counterpart).  The statement is tests/ais_ref.py; the kernels are csrc/ais.hpp.
+ *   Prior: p(z) = sum_k pi_k N(z; mu_k, diag sigma_k^2), built from `params` by a prep launch -- VAE: one standard normal;
+ *     VAE_GMP: loc, softplus(raw_scale_diag), log_softmax(mixture_logits); GMVAE: pi_k = 1 / K, (mu_k, sigma_k) = prior_gmm's
+ *     normal head at e_k (sigma_min, raw_sigma_bias as gmvae_forward).  So for the GMVAE the estimate is of log p(x) ITSELF, the
+ *     uniform p(y) inside: gmvae_iw_bound_enum_y's bound minus ln K.
+ *   Base r_b: base == NULL, base_K == 0: the prior.  Else the caller's table, one record of base_K (1 + 2 L) floats per example:
+ *     ln w [base_K], mu [base_K][L], sigma [base_K][L] (sigma > 0; the inference mixture sum_k q(k|x_b) q(z|x_b,e_k), one
+ *     Gaussian for the VAE family).
+ *   Likelihood: gmvae_forward's Bernoulli term on x in {0, 1} -- the decoder MLP at dims' sizes, gen_bias_init / gen_bias_vec, any
+ *     hidden_act, the activation's derivative taken from the activation (ReLU' = 0 at a pre-activation <= 0).
+ *   Path: betas_dev, n_temps + 1 floats on the device, 0 = beta_0 < ... < beta_T = 1 (not checked; beta_0 is taken as 0),
+ *     f_t = r^(1 - beta_t) (p p(x|.))^beta_t; with the prior as the base it is p(z) p(x|z)^beta_t, the prior evaluated once.
+ *   Chain (b, c), c < n_chains: at t = 0 a component of the base by inverse CDF of its weights with one uniform, z_0 = mu_k +
+ *     sigma_k eps.  At t = 1 .. T: log w += (beta_t - beta_{t-1}) (log p(z) + log p(x|z) - log r(z)) at z_{t-1}; then one HMC
+ *     transition on f_t -- a fresh momentum ~ N(0, I), n_leapfrog leapfrog steps of size e (half step, full steps, half step on
+ *     the momentum), H = -log f_t(z) + |p|^2 / 2, accepted iff ln u < H_old - H_new, a non-finite H_new rejects --; then
+ *     e <- clip(e * (accepted ? step_up : step_down), 1e-4, 1), e = step0 at the start, per chain.  step_up = step_down = 1 turns
+ *     the adaptation off: that is the strictly valid AIS (an adapted step size depends on the chain's past).  The transition at
+ *     beta_T is run; z_T is an approximate posterior sample.
+ *   Noise: chain (b, c) is Philox row (dims->row0 + b) n_chains + c, and its draw at transition t (t = 0: the start) is what
+ *     gmvae_noise_fill(eps, u, rows, L, 1, row_base, seed, step (n_temps + 1) + t) returns: eps = z_0's noise or the momentum,
+ *     u[0] = the component's or the accept's uniform.  eps [n_temps + 1][B n_chains][L] and u [n_temps + 1][B n_chains] (each
+ *     may be NULL: Philox) replace the draw.  Results do not depend on the batch, the sharding or the launches.
+ *   Outputs (each may be NULL but tail): logw_out [B][n_chains]; bound_out [B] = logsumexp_c log w_bc - ln n_chains;
+ *     stats_out [B][4] = the bound, the effective sample size (sum w)^2 / sum w^2 of the chains' weights, the mean acceptance rate,
+ *     the mean final step size; z_out [B n_chains][L] = z_T; tail [GMVAE_TAIL] = the sums over b of -bound, ESS, acceptance rate
+ *     and step size, [4] = B, [5..7] = 0.
+ * One workgroup owns 16 chains for every temperature of a launch (a panel may span examples and be ragged at the end); the layer
+ * products run on the fp32 matrix cores, element-wise work in fp32, the sums over D and L and H itself in fp64.  The call
+ * enqueues the prep launch, launches of at most 32 transitions each (GMVAE_AIS_LAUNCH_TEMPS in the environment sets another cap;
+ * the chain state is carried in the workspace, and the result does not depend on the cap), and two finishing launches, with no
+ * host synchronisation.  The workspace (gmvae_ais_workspace_bytes at the same dims, base_K and n_chains; 256-byte aligned; needs
+ * no initialisation) is O(B n_chains L), independent of n_temps; after the call its first B n_chains 64-bit words hold the chains'
+ * accept records, bit t - 1 of word b n_chains + c set iff transition t <= 64 of chain (b, c) was accepted.  No workgroup waits for another, no atomics, fixed-order sums:
+ * two calls give the same bits.
+ * Sizes: n_hidden <= 3, hidden widths <= 512, L <= 128, K <= 64 (VAE: K is ignored), base_K <= 64, any D >= 1, B n_chains <= 2^30.
+ * Checks, before any launch, in this order: GMVAE_E_NULL (dims); GMVAE_E_MODEL; GMVAE_E_DIMS (the sizes above; any GMVAE_LIK_*
+ * field other than the Bernoulli, GMVAE_X_F32, GMVAE_LIK_SCALE_LEARNED or GMVAE_OBJ_PIXEL_MASK in dims->sched_flags -- the other
+ * bits are ignored --; n_temps, n_chains or n_leapfrog < 1; (row0 + B) n_chains >= 2^38; a step size or factor that is not
+ * positive and finite; base without base_K); GMVAE_E_NULL (x, params, betas_dev, tail, workspace, base with base_K > 0);
+ * GMVAE_E_ALIGN (params 16 bytes, the workspace 256, every other array 4). */
+int gmvae_ais_workspace_bytes(const GmvaeDims* dims, int model, int base_K, int n_chains, uint64_t* bytes);
+int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
+              const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0, float step_up, float step_down,
+              const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out, float* tail,
+              void* workspace, uint64_t seed, uint64_t step, void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
