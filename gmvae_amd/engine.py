@@ -931,6 +931,96 @@ class Engine:
         self._keep_ais = (x, base, betas, eps, u)
         return o
 
+    REFINE_STATS = ("elbo_start", "elbo_refined", "iw_start", "iw_refined", "ess_refined", "updates", "mean_shift",
+                    "log_sigma_ratio")
+
+    def refine_posterior(self, x, n_steps: int = 500, n_samples: int = 4, n_eval: int = 256, lr: float = 0.05,
+                         betas=(0.9, 0.999), adam_eps: float = 1e-8, row0: Optional[int] = None,
+                         eps: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None):
+        """Per-example refinement of q(z|x) (include/gmvae_hip.h gmvae_refine; Cremer, Li & Duvenaud 2018): for every example a
+        local Gaussian q_phi(z) = N(m, diag sigma^2) starts at the encoder's output and climbs the example's own ELBO, log p(x, z)
+        with y summed out, by n_steps steps of TF-Adam ascent (lr, betas, adam_eps) on n_samples reparameterised draws each; the
+        ELBO and the importance-weighted bound of the start and of the refined phi* are then evaluated on the same n_eval draws
+        (rounded up to a multiple of n_samples).  elbo_refined - elbo_start is what the encoder loses against the best member of
+        its own family on that example (the amortisation gap); what remains up to log p(x) only a richer family closes.
+        The start comes from _latent_components: q(z|x) for the VAE family; for the GMVAE the component at argmax_k q(k|x),
+        lowest index on ties.  start [B, 2 L] = (mu_0, sigma_0) replaces it.
+        Returns dict(phi [B, 2 L] = (m*, sigma*), trace [n_steps, B] = the ELBO estimate before each step, stats [B, 8] and its
+        columns by name -- elbo_start, elbo_refined, iw_start, iw_refined, ess_refined (of the n_eval weights at phi*), updates
+        (steps applied: a step whose gradient is not finite is skipped), mean_shift = mean_l |m* - mu_0| / sigma_0,
+        log_sigma_ratio = mean_l ln(sigma* / sigma_0) --, tail [8] = the batch sums of the first four, B).
+        Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step * (n_steps + rounds + 1)
+        + t), row0 defaulting to rank * B: the result does not depend on the batch size or the sharding.  eps [n_steps + rounds,
+        B n_samples, L] replaces the draw (tests).  Bernoulli likelihood only; not with pixel_mask."""
+        if self.pixel_mask or self.likelihood != "bernoulli":
+            raise ValueError("refine_posterior scores the Bernoulli likelihood on every pixel: not available with pixel_mask=True "
+                             f"or likelihood={self.likelihood!r}")
+        T, S, N = int(n_steps), int(n_samples), int(n_eval)
+        if S not in (1, 2, 4, 8, 16):
+            raise ValueError(f"n_samples must be one of 1, 2, 4, 8, 16, got {n_samples}")
+        if T < 0 or N < 1:
+            raise ValueError(f"n_steps must be >= 0 and n_eval >= 1, got {T}, {N}")
+        if not (0.0 < float(lr) < float("inf")):
+            raise ValueError(f"lr must be positive and finite, got {lr}")
+        R = (N + S - 1) // S
+        x = self._prep_x(x)
+        B = x.shape[0]
+        d = self.dims(B, 1, row0)
+        if start is None:
+            logpi, mu, sigma = self._latent_components(x)
+            Kc = logpi.shape[1]
+            k = torch.argmax(logpi, dim=1) + Kc * torch.arange(B, device=self.device)      # (argmax: the first of equal values)
+            start = torch.cat([mu[k], sigma[k]], dim=1)
+        start = start.to(self.device, torch.float32).contiguous()
+        if tuple(start.shape) != (B, 2 * self.Lz):
+            raise ValueError(f"start must be [B, 2 L] = [{B}, {2 * self.Lz}] (mu_0, sigma_0), got {tuple(start.shape)}")
+        eps = self._prep_noise(eps, (T + R) * B * S, self.Lz)
+        nw = L.refine_workspace_bytes(d, self.model, S) // 4 + 64
+        ws = self._chunked_ws.get(("refine", B, S))
+        if ws is None or ws.numel() < nw:
+            ws = self._chunked_ws[("refine", B, S)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        o = dict(phi=torch.empty(B, 2 * self.Lz, **f32), trace=torch.empty(T, B, **f32), stats=torch.empty(B, 8, **f32),
+                 tail=torch.empty(L.TAIL, **f32))
+        rc = L.lib.gmvae_refine(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(start), T, S, R, float(lr),
+                                float(betas[0]), float(betas[1]), float(adam_eps), L.ptr(eps), L.ptr(o["phi"]),
+                                L.ptr(o["trace"]) if T else None, L.ptr(o["stats"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed,
+                                self.global_step, L.current_stream())
+        L.check(rc, "gmvae_refine")
+        self._keep_refine = (x, start, eps)
+        for i, name in enumerate(self.REFINE_STATS):
+            o[name] = o["stats"][:, i]
+        o["start"] = start
+        return o
+
+    def inference_gaps(self, x, n_steps: int = 500, n_samples: int = 4, n_eval: int = 256, lr: float = 0.05, betas=(0.9, 0.999),
+                       adam_eps: float = 1e-8, ais: Optional[dict] = None, row0: Optional[int] = None):
+        """The inference gap log p(x) - L[q(z|x)] of a batch split in two (Cremer, Li & Duvenaud 2018), batch means as floats:
+          amortisation_gap = elbo_refined - elbo_amortised: what the encoder loses against q*, the best single Gaussian for each
+            example (refine_posterior) -- more encoder capacity or training closes it;
+          approximation_gap = log_px - elbo_refined: what the family loses -- only a richer family or another model closes it.
+        elbo_amortised is refine_posterior's elbo_start for the VAE family.  For the GMVAE it is the z-marginal ELBO of the
+        inference MIXTURE sum_k q(k|x) q(z|x, e_k), E_q[log p(x, z) - log q(z|x)] on n_eval draws (ais_bound at n_temps=1,
+        init="encoder": the mean of its log w), and elbo_start, the ELBO of the one component refine_posterior starts from, is
+        reported beside it.  The GMVAE's amortised family is thus a K-mixture and the local one a single Gaussian: where q(y|x) is
+        genuinely spread the mixture can beat every single Gaussian and the amortisation gap is NEGATIVE; it is reported as it is.
+        log_px is the larger of the batch means of iw_refined and, with ais = a dict of ais_bound's arguments (n_chains, n_temps,
+        ...), of the AIS bound (ais_log_px, else None): both are lower bounds in expectation, so the larger is the better
+        estimate -- Cremer et al.'s convention.  Also returned: iw_bound_refined, the per-example tensors elbo_amortised_rows,
+        ais_rows (or None) and refine = refine_posterior's dict.  row0 as refine_posterior's."""
+        r = self.refine_posterior(x, n_steps, n_samples, n_eval, lr, betas, adam_eps, row0=row0)
+        am = r["elbo_start"].double()
+        if self.model == L.MODEL_GMVAE:
+            am = self.ais_bound(x, n_chains=int(n_eval), n_temps=1, init="encoder", n_leapfrog=1, row0=row0)["logw"].double().mean(dim=1)
+        ab = None if ais is None else self.ais_bound(x, row0=row0, **ais)["bound"].double()
+        o = dict(refine=r, elbo_amortised_rows=am, ais_rows=ab, elbo_amortised=am.mean().item(),
+                 elbo_start=r["elbo_start"].double().mean().item(), elbo_refined=r["elbo_refined"].double().mean().item(),
+                 iw_bound_refined=r["iw_refined"].double().mean().item(), ais_log_px=None if ab is None else ab.mean().item())
+        o["log_px"] = o["iw_bound_refined"] if ab is None else max(o["iw_bound_refined"], o["ais_log_px"])
+        o["amortisation_gap"] = o["elbo_refined"] - o["elbo_amortised"]
+        o["approximation_gap"] = o["log_px"] - o["elbo_refined"]
+        return o
+
     AGG_CHUNK = 2048               # default examples per pass of aggregate_posterior (K rows each for the GMVAE)
 
     def _normal_head(self, out: torch.Tensor):

@@ -126,6 +126,13 @@ class TrainableGMVAE(GMVAE):
         The bound is of log p(x) itself, the uniform p(y) inside: iw_bound_enum_y's bound minus ln K; the same for every y_inference."""
         return self._need_engine().ais_bound(images, n_chains, n_temps, **kw)
 
+    def inference_gaps(self, images, n_steps=500, n_samples=4, n_eval=256, ais=None, **kw):
+        """The inference gap log p(x) - L[q(z|x)] split into its amortisation and approximation parts by refining q(z|x) per
+        example (Cremer, Li & Duvenaud 2018): Engine.inference_gaps's dict (elbo_amortised, elbo_refined, iw_bound_refined,
+        log_px, amortisation_gap, approximation_gap as batch means; ais = a dict of ais_bound's arguments adds ais_log_px).
+        **kw: lr, betas, adam_eps, row0."""
+        return self._need_engine().inference_gaps(images, n_steps, n_samples, n_eval, ais=ais, **kw)
+
     def posterior_y(self, images, n_samples, chunk=None):
         """ln p(y = k | x) of the model itself (not the inference network's q(y|x)), by importance sampling with n_samples
         samples of z per component, streamed in chunks of `chunk`: a [B, K] device tensor (Engine.posterior_y)."""

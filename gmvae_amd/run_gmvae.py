@@ -51,6 +51,12 @@ def build_parser():
     a("--ais_step_size", type=float, default=0.05, help="--ais_chains: the initial leapfrog step size (adapted per chain)")
     a("--ais_init", default="prior", choices=["prior", "encoder"], help="--ais_chains: the chains' base distribution")
     a("--ais_schedule", default="sigmoid", choices=["sigmoid", "linear"], help="--ais_chains: the annealing path")
+    a("--refine_steps", type=int, default=0, help="eval: also split the inference gap by refining q(z|x) per example with this many "
+      "steps of Adam ascent on the example's own ELBO (Engine.inference_gaps); reports elbo_amortised, elbo_refined, "
+      "iw_bound_refined, amortisation_gap and approximation_gap over the split (--ais_chains: ais_log_px joins log_px); 0 = off")
+    a("--refine_samples", type=int, default=4, help="--refine_steps: Monte-Carlo samples per step (1, 2, 4, 8 or 16)")
+    a("--refine_lr", type=float, default=0.05, help="--refine_steps: Adam's learning rate")
+    a("--refine_eval_samples", type=int, default=256, help="--refine_steps: samples per example of the closing evaluation")
     a("--posterior_samples", type=int, default=0, help="eval, gmvae (either --y_inference): also report the model's own "
       "posterior p(y|x) by importance sampling at this many samples per example and component (Engine.posterior_y) -- its "
       "clustering accuracy next to q(y|x)'s, its entropy, KL(q(y|x) || p(y|x)) and the effective sample size; 0 = off")
@@ -209,6 +215,19 @@ def check_args(p, cfg):
             p.error("--ais_leapfrog must be >= 1 and --ais_step_size a finite number > 0")
         if cfg.missing_rate > 0 or cfg.likelihood != "bernoulli":
             p.error("--ais_chains scores the Bernoulli likelihood on every pixel: not available with --missing_rate or --likelihood")
+    if cfg.refine_steps < 0:
+        p.error("--refine_steps must be >= 0 (0 = off)")
+    if not cfg.refine_steps and (cfg.refine_samples, cfg.refine_lr, cfg.refine_eval_samples) != (4, 0.05, 256):
+        p.error("--refine_samples, --refine_lr and --refine_eval_samples need --refine_steps")
+    if cfg.refine_steps:
+        if cfg.mode != "eval":
+            p.error("--refine_steps needs --mode=eval")
+        if cfg.refine_samples not in (1, 2, 4, 8, 16) or cfg.refine_eval_samples < 1:
+            p.error("--refine_samples must be 1, 2, 4, 8 or 16 and --refine_eval_samples >= 1")
+        if not (cfg.refine_lr > 0 and cfg.refine_lr < float("inf")):
+            p.error("--refine_lr must be a finite number > 0")
+        if cfg.missing_rate > 0 or cfg.likelihood != "bernoulli":
+            p.error("--refine_steps scores the Bernoulli likelihood on every pixel: not available with --missing_rate or --likelihood")
     if cfg.y_inference == "marginal":
         if cfg.model != "gmvae":
             p.error("--y_inference=marginal needs --model=gmvae")

@@ -705,6 +705,8 @@ def run_eval(config):
     ie_n, ie_rows = int(getattr(config, "iw_enum_samples", 0) or 0), []
     # --ais_chains C --ais_temps T: log p(x) by annealed importance sampling from the generative model alone, keyed alike
     ais_c, ais_t, ais_rows = int(getattr(config, "ais_chains", 0) or 0), int(getattr(config, "ais_temps", 0) or 0), []
+    # --refine_steps N: the inference gap split by per-example refinement of q(z|x) (Engine.inference_gaps), keyed alike
+    rf_t, rf_rows, rf_stats = int(getattr(config, "refine_steps", 0) or 0), [], []
     # --posterior_samples N: the model's own posterior p(y|x) by importance sampling per component (GMVAE), keyed alike
     py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
     # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
@@ -749,6 +751,11 @@ def run_eval(config):
                                           n_leapfrog=int(getattr(config, "ais_leapfrog", 10)),
                                           step_size=float(getattr(config, "ais_step_size", 0.05)),
                                           init=getattr(config, "ais_init", "prior"), row0=first)["stats"])
+        if rf_t > 0:
+            g = eng.inference_gaps(images, rf_t, int(getattr(config, "refine_samples", 4)), int(getattr(config, "refine_eval_samples", 256)),
+                                   float(getattr(config, "refine_lr", 0.05)), row0=first)
+            rf_rows.append(g["elbo_amortised_rows"])
+            rf_stats.append(g["refine"]["stats"])
         o = eng.forward(images, mask=mk)
         tot += o["tail"][:5]
         pm_tot += o["tail"][5:8].double()
@@ -778,8 +785,14 @@ def run_eval(config):
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
     pc_tot = torch.cat(pc_stats).double().sum(0) if pc_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
     ais_tot = torch.cat(ais_rows).double().sum(0) if ais_rows else torch.zeros(4, dtype=torch.float64, device=eng.device)
+    # the sums over this rank's examples of (elbo_amortised, elbo_refined, iw_refined)
+    rf_tot = torch.zeros(3, dtype=torch.float64, device=eng.device)
+    if rf_rows:
+        rf_tot = torch.stack([torch.cat(rf_rows).sum(), *torch.cat(rf_stats)[:, [1, 3]].double().sum(0)])
     if world > 1:
         parallel.all_reduce_flat(tot)
+        if rf_t > 0:
+            parallel.all_reduce_flat(rf_tot)
         if ais_c > 0:
             parallel.all_reduce_flat(ais_tot)
         parallel.all_reduce_flat(iw_sum)
@@ -829,6 +842,14 @@ def run_eval(config):
                                                                  + math.log(int(config.mixture_components)))
         elif iw_n > 0 and config.model != "gmvae":
             res[f"{config.split}/ais_gap_to_iw_bound"] = (ais_tot[0].item() - iw_sum.item()) / n
+    if rf_t > 0:
+        # the inference gap in its two parts (Cremer et al. 2018); log p(x) is the larger of the two lower bounds in hand
+        am, er, ir = (rf_tot / n).tolist()
+        log_px = max(ir, ais_tot[0].item() / n) if ais_c > 0 else ir
+        res[f"{config.split}/elbo_amortised"], res[f"{config.split}/elbo_refined"] = am, er
+        res[f"{config.split}/iw_bound_refined"] = ir
+        res[f"{config.split}/amortisation_gap"] = er - am
+        res[f"{config.split}/approximation_gap"] = log_px - er
     if py_n > 0:
         # clustering accuracy over the WHOLE split (the ranks' histograms add), by the model's posterior and by q(y|x)
         K, all_labs = int(config.mixture_components), torch.cat(labs)
@@ -865,6 +886,7 @@ def run_eval(config):
     res["labels"] = torch.cat(labs) if labs else None
     res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
     res["iw_bounds_enum_y"] = torch.cat(ie_rows) if ie_rows else None
+    res["refine_stats"] = torch.cat(rf_stats) if rf_stats else None   # [..., 8]: Engine.REFINE_STATS
     res["ais_stats"] = torch.cat(ais_rows) if ais_rows else None     # [..., 4]: log p(x) estimate, ESS, acceptance rate, step size
     if py_n > 0:
         res["log_posterior_y"] = torch.cat(py_rows)                  # [this rank's examples, K], in split order

@@ -805,6 +805,46 @@ int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* p
               const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out, float* tail,
               void* workspace, uint64_t seed, uint64_t step, void* stream);
 
+/* Per-example refinement of q(z|x): the two parts of the inference gap log p(x) - L[q(z|x)] (Cremer, Li & Duvenaud 2018).  For each
+ * example a local Gaussian q_phi(z) = N(m, diag e^{2 s}) starts at the caller's (mu_0, sigma_0) and climbs the example's own ELBO by
+ * stochastic gradient ascent; the ELBO and the importance-weighted bound of the start and of the refined phi* are then evaluated on
+ * common noise.  L[phi*] - L[q(z|x)] is the amortisation gap, log p(x) - L[phi*] the approximation gap (Engine.refine_posterior,
+ * model.inference_gaps and run_gmvae --mode=eval --refine_steps go through it; the reference has no counterpart).  The statement
+ * is tests/refine_ref.py; the kernels are csrc/refine.hpp, the evaluation csrc/ais.hpp's.
+ *   Target: log p(x, z) = log p(z) + log p(x|z), prior and likelihood exactly as gmvae_ais takes them (y summed out for the GMVAE).
+ *   Start: start [B][2 L] = mu_0 [L], sigma_0 [L] per example (sigma_0 > 0), s_0 = ln sigma_0.
+ *   Step t = 1 .. n_steps, n_samples = S draws eps_s: z_s = m + e^s eps_s, g_s = grad_z log p(x, z_s);
+ *     L-hat_t = 1/S sum_s log p(x, z_s) + sum_l s_l + L/2 (1 + ln 2 pi);  dm = 1/S sum_s g_s;  ds = 1/S sum_s g_s e^s eps_s + 1;
+ *     then one ASCENT step of adam_tf_step's update on the 2 L parameters (lr, beta1, beta2, adam_eps, the example's own count;
+ *     alpha_t from fp64 pow), and s clamped to [-20, 5].  An example whose gradient is not finite skips that update: moments and
+ *     count untouched.
+ *   Evaluation: n_eval_rounds rounds of S fresh draws, N = n_eval_rounds S; log w = log p(x, z) - log q_phi(z) at phi* and at phi_0
+ *     on the SAME eps; the ELBO = mean log w, the importance-weighted bound = logsumexp log w - ln N, sums in fp64.
+ *   Noise: row (b, s) is Philox row (dims->row0 + b) S + s, and its draw at t (steps 0 .. n_steps - 1, then the rounds) is what
+ *     gmvae_noise_fill(eps, NULL-able u, rows, L, 1, row_base, seed, step (n_steps + n_eval_rounds + 1) + t) returns.
+ *     eps [n_steps + n_eval_rounds][B S][L] (may be NULL: Philox) replaces the draw.  Results do not depend on the batch, the
+ *     sharding or the launches.
+ *   Outputs (each may be NULL but tail): phi_out [B][2 L] = m*, sigma* = e^{s*}; trace_out [n_steps][B] = L-hat_t before the
+ *     update of step t; stats_out [B][8] = elbo_start, elbo_refined, iw_start, iw_refined, the effective sample size of the N
+ *     weights at phi*, updates applied, mean_l |m* - mu_0| / sigma_0, mean_l ln(sigma* / sigma_0); tail [GMVAE_TAIL] = the sums
+ *     over b of the first four, [4] = B, [5..7] = 0.  n_steps = 0 is legal: phi* = phi_0.
+ * One workgroup owns 16 rows (samples) for every step of a launch; an example's S samples lie in one panel and its first row owns
+ * the optimizer state.  The call enqueues the prior's prep launch, launches of at most 256 steps or rounds each
+ * (GMVAE_REFINE_LAUNCH_STEPS in the environment sets another cap; the state is carried in the workspace, and the result does not
+ * depend on the cap), and two finishing launches, with no host synchronisation.  The workspace (gmvae_refine_workspace_bytes at
+ * the same dims and n_samples; 256-byte aligned; needs no initialisation) is O(B (L + S)), independent of n_steps.  No workgroup
+ * waits for another, no atomics, fixed-order sums: two calls give the same bits.
+ * Sizes: those of gmvae_ais (n_hidden <= 3, widths <= 512, L <= 128, K <= 64, any D >= 1), B S <= 2^30.
+ * Checks, before any launch, in this order: GMVAE_E_NULL (dims); GMVAE_E_MODEL; GMVAE_E_DIMS (the sizes above; the likelihood and
+ * mask bits gmvae_ais refuses; n_samples not in {1, 2, 4, 8, 16}; n_steps < 0; n_eval_rounds < 1; n_steps + n_eval_rounds > 2^24;
+ * (row0 + B) S >= 2^38; lr not positive and finite; beta1 or beta2 outside [0, 1); adam_eps negative or not finite);
+ * GMVAE_E_NULL (x, params, start, tail, workspace); GMVAE_E_ALIGN (params 16 bytes, the workspace 256, every other array 4). */
+int gmvae_refine_workspace_bytes(const GmvaeDims* dims, int model, int n_samples, uint64_t* bytes);
+int gmvae_refine(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* start, int n_steps,
+                 int n_samples, int n_eval_rounds, float lr, float beta1, float beta2, float adam_eps, const float* eps,
+                 float* phi_out, float* trace_out, float* stats_out, float* tail, void* workspace, uint64_t seed, uint64_t step,
+                 void* stream);
+
 /* tf.compat.v1.train.AdamOptimizer.apply_gradients (scripts/runners.py:181-183):
  * epsilon is added to the UN-corrected sqrt(v).  t = 1-based step count.
  * t_dev (may be NULL): device pointer overriding t (graph replay).
