@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "adam.hpp"
 #include "gemm.hpp"
 
 namespace gmvae {
@@ -885,19 +886,7 @@ __device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, const l
 }
 
 // ---------------------------------------------------------------- Adam
-// TF1 AdamOptimizer / ApplyAdam (scripts/runners.py:181-183):
-//   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; theta -= lr_t*m/(sqrt(v)+eps)
-// One launch over the whole flat buffer (multi-tensor by construction).
-// ONE statement of the update for every kernel that applies it (adam_tf, finalize_adam's two thread maps, adam_tf_img):
-// the roundings are pinned with explicit intrinsics, so the same inputs give the same bits whichever kernel ran
-// (the compiler contracts a*b+c differently from one kernel to the next otherwise).
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, const float g, const float gscale, const float lr_t,
-                                            const float omb1, const float omb2, const float eps) {
-  const float gj = __fmul_rn(g, gscale);
-  m = __fmaf_rn(__fsub_rn(gj, m), omb1, m);
-  v = __fmaf_rn(__fmaf_rn(gj, gj, -v), omb2, v);
-  p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, lr_t), __fadd_rn(__fsqrt_rn(v), eps)));
-}
+// The update statement is adam.hpp's adam_update.  One launch over the whole flat buffer (multi-tensor by construction).
 
 // Parameter ranges whose weight gradients were split over fewer slabs than the rest (the uint8-activation
 // problems of the fused dW launch run on the bf16 matrix cores and take half the splits of the fp32 ones).

@@ -5,14 +5,13 @@
 #include <stdint.h>
 
 #include "../../include/gmvae_hip.h"
+#include "hostutil.hpp"
 #include "mixfit.hpp"
 #include "mixfit_full.hpp"
 
 using namespace gmvae;
 
 namespace {
-
-int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 int mf_check_sizes(int64_t N, int L, int K) {
   if (N < 1 || N > (1ll << 24) || L < 1 || L > 4096 || K < 1 || K > 256 || (int64_t)K * L > kMfMaxKL) return GMVAE_E_DIMS;

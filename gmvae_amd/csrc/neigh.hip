@@ -6,13 +6,12 @@
 #include <stdint.h>
 
 #include "../../include/gmvae_hip.h"
+#include "hostutil.hpp"
 #include "neigh.hpp"
 
 using namespace gmvae;
 
 namespace {
-
-int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Workspace, a function of (Nq, Nr, C): search and ranks hold d [Nq][Nr] (fp32) in it, class_sums the slices' parts
 // [nn_class_slices(Nr)][C][Nq] (fp64); both begin at its start -- every call leaves it free for the next.

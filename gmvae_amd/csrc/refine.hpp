@@ -1,11 +1,11 @@
-// gmvae_refine (include/gmvae_hip.h; host side: csrc/refine.hip): per-example refinement of q(z|x) -- stochastic-gradient ascent on
+// gmvae_refine (include/gmvae_hip.h; host side: csrc/ais.hip): per-example refinement of q(z|x) -- stochastic-gradient ascent on
 // one example's own ELBO over the parameters phi = (m, s) of a local Gaussian q_phi(z) = N(m, diag e^{2 s}) (Cremer, Li & Duvenaud
 // 2018), then the ELBO and the importance-weighted bound of the start phi_0 and of the refined phi* on common noise.  The statement
 // is tests/refine_ref.py.
 //   Target: log p(x, z) = log p(z) + log p(x|z) -- csrc/ais.hpp's ais_eval with enc = 0: A = log p(z), B = log p(x|z), the gradient
 //   gA + gB.  Nothing of ais.hpp is restated: the panel geometry, the LDS layout (ais_lds) and the evaluation are its own.
 //   Step t < n_steps, S samples eps_s:  z_s = m + e^s eps_s;  L-hat = 1/S sum_s log p(x, z_s) + sum_l s_l + L/2 (1 + ln 2 pi);
-//     dm = 1/S sum_s g_s;  ds = 1/S sum_s g_s e^s eps_s + 1;  one ASCENT step of TF-Adam (kernels.hpp adam_update on -d) on the 2 L
+//     dm = 1/S sum_s g_s;  ds = 1/S sum_s g_s e^s eps_s + 1;  one ASCENT step of TF-Adam (adam.hpp adam_update on -d) on the 2 L
 //     parameters with the example's own count t_b; a gradient that is not finite skips the update (moments and t_b untouched, as
 //     gclip.hpp does for the training step); s clamped to [-20, 5] after the update.
 //   Round t >= n_steps: S fresh eps, log w = log p(x, z) - log q_phi(z) at phi* and at phi_0 on the SAME eps: two evaluations.
@@ -23,15 +23,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "aux.hpp"
-
-// ais.hpp defines its kernels as plain functions, so a second translation unit of one library cannot include it as it stands: the
-// host stubs would be defined twice.  Its text is included INSIDE this namespace instead (the headers above are already in, so
-// its own includes are empty): this unit's copies are refine_tu::gmvae::ais_*, and ais.hpp is not edited.
-namespace refine_tu {
-using namespace ::gmvae;      // (aux.hpp's noise_vals)
+// ais.hpp defines its kernels as plain functions, so one library can include it from one translation unit only: csrc/ais.hip
+// includes this header and hosts both entry points.
+#include "adam.hpp"
 #include "ais.hpp"
-using namespace gmvae;        // (refine_tu::gmvae: the copies above)
+
+namespace gmvae {
 
 constexpr float kRefineSMin = -20.f, kRefineSMax = 5.f;
 
@@ -45,15 +42,6 @@ struct RefineArgs {
   double* acc;                   // [B S][8]: (max, sum e, sum e^2, sum) of log w at phi*, then at phi_0
   float* trace;                  // [n_steps][B] or null
 };
-
-// kernels.hpp adam_update, restated (that header carries the training step's kernels, which this code object does not want): the
-// roundings pinned the same way.
-__device__ __forceinline__ void refine_adam(float& p, float& m, float& v, const float g, const float lr_t, const float omb1,
-                                            const float omb2, const float eps) {
-  m = __fmaf_rn(__fsub_rn(g, m), omb1, m);
-  v = __fmaf_rn(__fmaf_rn(g, g, -v), omb2, v);
-  p = __fsub_rn(p, __fdiv_rn(__fmul_rn(m, lr_t), __fadd_rn(__fsqrt_rn(v), eps)));
-}
 
 // one more log w into a running (max, sum e^(lw - max), sum e^(2 (lw - max)), sum lw)
 __device__ __forceinline__ void refine_fold(double* r, const double lw) {
@@ -171,10 +159,10 @@ __global__ __launch_bounds__(kAisThreads, 2) void refine_run(const RefineArgs ra
           if (live)
             for (int l = j; l < L; l += 16) {
               float m_l = ph[l], s_l = ph[L + l], m1 = ph[2 * L + l], v1 = ph[3 * L + l];
-              refine_adam(m_l, m1, v1, -gAb[l], lr_t, omb1, omb2, ra.aeps);
+              adam_update(m_l, m1, v1, -gAb[l], 1.f, lr_t, omb1, omb2, ra.aeps);      // (g * 1 is g; a non-finite g never gets here)
               ph[l] = m_l; ph[2 * L + l] = m1; ph[3 * L + l] = v1;
               float m2 = ph[4 * L + l], v2 = ph[5 * L + l];
-              refine_adam(s_l, m2, v2, -gBb[l], lr_t, omb1, omb2, ra.aeps);
+              adam_update(s_l, m2, v2, -gBb[l], 1.f, lr_t, omb1, omb2, ra.aeps);
               ph[L + l] = fminf(fmaxf(s_l, kRefineSMin), kRefineSMax); ph[4 * L + l] = m2; ph[5 * L + l] = v2;
             }
         }
@@ -226,4 +214,4 @@ __global__ __launch_bounds__(kAisThreads) void refine_finish(const float* __rest
   fin[b * 4] = elbo[1]; fin[b * 4 + 1] = elbo[0]; fin[b * 4 + 2] = iw[1]; fin[b * 4 + 3] = iw[0];
 }
 
-}  // namespace refine_tu
+}  // namespace gmvae

@@ -7,13 +7,13 @@
 #include <stdint.h>
 
 #include "../../include/gmvae_hip.h"
+#include "hostutil.hpp"
 #include "tsne.hpp"
 
 using namespace gmvae;
 
 namespace {
 
-int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 int aligned16(const void* p) { return aligned_to(p, 16); }
 
 // gmvae_tsne_*: csrc/tsne.hpp.  Workspace, a function of (N, rows): the slices' partial sums [ts_slices(N)][N][kTsAcc] and the

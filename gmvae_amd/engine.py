@@ -772,6 +772,19 @@ class Engine:
 
     IW_CHUNK_ROWS = 51200          # default B * chunk of iw_bound: the rows of bench.py's eval_iwae pass (B = 1024, S = 50)
 
+    def _cached_ws(self, key, n_words: int):
+        """(an evaluator's workspace of at least n_words zeroed floats, kept under `key`; whether this call allocated it)."""
+        ws = self._chunked_ws.get(key)
+        if ws is not None and ws.numel() >= n_words:
+            return ws, False
+        self._chunked_ws[key] = torch.zeros(n_words, dtype=torch.float32, device=self.device)
+        return self._chunked_ws[key], True
+
+    def _require_plain_bernoulli(self, what: str):
+        if self.pixel_mask or self.likelihood != "bernoulli":
+            raise ValueError(f"{what} scores the Bernoulli likelihood on every pixel: not available with pixel_mask=True or "
+                             f"likelihood={self.likelihood!r}")
+
     # the chunked importance-sampling evaluators, gmvae_<kind> and gmvae_<kind>_workspace_bytes of include/gmvae_hip.h:
     # kind -> (y enumerated: K rows per sample in the default chunk; outputs per component: log_joint [B, K], log_post [B, K]
     # and stats [B, 4] in place of bound [B] and mean_logw [B])
@@ -796,10 +809,8 @@ class Engine:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
         d = self.dims(B, chunk, row0)
         d.sched_flags &= ~_EVAL_MASKED      # (as the library's iw_dims does: the same size query, the same run)
-        nw = getattr(L, f"{kind}_workspace_bytes")(d, self.model) // 4 + 64
-        ws = self._chunked_ws.get((kind, B, chunk))
-        if ws is None or ws.numel() < nw:
-            ws = self._chunked_ws[(kind, B, chunk)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        ws, fresh = self._cached_ws((kind, B, chunk), getattr(L, f"{kind}_workspace_bytes")(d, self.model) // 4 + 64)
+        if fresh:
             self._bind_sigma((kind, B, chunk), d, ws)      # (the forward's workspace opens the evaluator's: the same offsets)
         self._bind_step_inputs(d, ws, mask=mask)      # (the forward's workspace opens the evaluator's: the same offsets)
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -893,9 +904,7 @@ class Engine:
         Chain c of row b draws Philox row (row0 + b) * n_chains + c keyed by (noise_seed, global_step * (n_temps + 1) + t), row0
         defaulting to rank * B: the result does not depend on the batch size or the sharding.  eps [n_temps + 1, B n_chains, L] and
         u [n_temps + 1, B n_chains] replace the draw (tests).  Bernoulli likelihood only; not with pixel_mask."""
-        if self.pixel_mask or self.likelihood != "bernoulli":
-            raise ValueError("ais_bound scores the Bernoulli likelihood on every pixel: not available with pixel_mask=True or "
-                             f"likelihood={self.likelihood!r}")
+        self._require_plain_bernoulli("ais_bound")
         if init not in ("prior", "encoder"):
             raise ValueError(f"init must be 'prior' or 'encoder', got {init!r}")
         C_, T, nl = int(n_chains), int(n_temps), int(n_leapfrog)
@@ -916,10 +925,7 @@ class Engine:
         eps = self._prep_noise(eps, (T + 1) * n, self.Lz)
         u = self._prep_noise(u, (T + 1) * n, 1)
         up, down = (float(step_up), float(step_down)) if adapt else (1.0, 1.0)
-        nw = L.ais_workspace_bytes(d, self.model, base_K, C_) // 4 + 64
-        ws = self._chunked_ws.get(("ais", B, C_, base_K))
-        if ws is None or ws.numel() < nw:
-            ws = self._chunked_ws[("ais", B, C_, base_K)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        ws, _ = self._cached_ws(("ais", B, C_, base_K), L.ais_workspace_bytes(d, self.model, base_K, C_) // 4 + 64)
         f32 = dict(dtype=torch.float32, device=self.device)
         o = dict(logw=torch.empty(B, C_, **f32), bound=torch.empty(B, **f32), stats=torch.empty(B, 4, **f32),
                  z=torch.empty(n, self.Lz, **f32), tail=torch.empty(L.TAIL, **f32))
@@ -952,9 +958,7 @@ class Engine:
         Sample s of row b draws Philox row (row0 + b) * n_samples + s keyed by (noise_seed, global_step * (n_steps + rounds + 1)
         + t), row0 defaulting to rank * B: the result does not depend on the batch size or the sharding.  eps [n_steps + rounds,
         B n_samples, L] replaces the draw (tests).  Bernoulli likelihood only; not with pixel_mask."""
-        if self.pixel_mask or self.likelihood != "bernoulli":
-            raise ValueError("refine_posterior scores the Bernoulli likelihood on every pixel: not available with pixel_mask=True "
-                             f"or likelihood={self.likelihood!r}")
+        self._require_plain_bernoulli("refine_posterior")
         T, S, N = int(n_steps), int(n_samples), int(n_eval)
         if S not in (1, 2, 4, 8, 16):
             raise ValueError(f"n_samples must be one of 1, 2, 4, 8, 16, got {n_samples}")
@@ -975,10 +979,7 @@ class Engine:
         if tuple(start.shape) != (B, 2 * self.Lz):
             raise ValueError(f"start must be [B, 2 L] = [{B}, {2 * self.Lz}] (mu_0, sigma_0), got {tuple(start.shape)}")
         eps = self._prep_noise(eps, (T + R) * B * S, self.Lz)
-        nw = L.refine_workspace_bytes(d, self.model, S) // 4 + 64
-        ws = self._chunked_ws.get(("refine", B, S))
-        if ws is None or ws.numel() < nw:
-            ws = self._chunked_ws[("refine", B, S)] = torch.zeros(nw, dtype=torch.float32, device=self.device)
+        ws, _ = self._cached_ws(("refine", B, S), L.refine_workspace_bytes(d, self.model, S) // 4 + 64)
         f32 = dict(dtype=torch.float32, device=self.device)
         o = dict(phi=torch.empty(B, 2 * self.Lz, **f32), trace=torch.empty(T, B, **f32), stats=torch.empty(B, 8, **f32),
                  tail=torch.empty(L.TAIL, **f32))

@@ -810,7 +810,7 @@ int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* p
  * stochastic gradient ascent; the ELBO and the importance-weighted bound of the start and of the refined phi* are then evaluated on
  * common noise.  L[phi*] - L[q(z|x)] is the amortisation gap, log p(x) - L[phi*] the approximation gap (Engine.refine_posterior,
  * model.inference_gaps and run_gmvae --mode=eval --refine_steps go through it; the reference has no counterpart).  The statement
- * is tests/refine_ref.py; the kernels are csrc/refine.hpp, the evaluation csrc/ais.hpp's.
+ * is tests/refine_ref.py; the kernels are csrc/refine.hpp, the evaluation csrc/ais.hpp's, the host side csrc/ais.hip.
  *   Target: log p(x, z) = log p(z) + log p(x|z), prior and likelihood exactly as gmvae_ais takes them (y summed out for the GMVAE).
  *   Start: start [B][2 L] = mu_0 [L], sigma_0 [L] per example (sigma_0 > 0), s_0 = ln sigma_0.
  *   Step t = 1 .. n_steps, n_samples = S draws eps_s: z_s = m + e^s eps_s, g_s = grad_z log p(x, z_s);

@@ -1,4 +1,4 @@
-"""fp64 statement of one TF-Adam update (TF1 ApplyAdam; csrc/kernels.hpp adam_update) and the per-element bounds an fp32
+"""fp64 statement of one TF-Adam update (TF1 ApplyAdam; csrc/adam.hpp adam_update) and the per-element bounds an fp32
 evaluation of it has to stay inside -- test infrastructure, a plain module: the checker of tests/test_optimizer_sites*.py.
 
 The update is elementwise.  Given the fp32 values a device held BEFORE a step -- p, m, v -- the gradient SUM it left in the

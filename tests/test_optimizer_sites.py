@@ -1,6 +1,6 @@
 """-m gpu: every fused TF-Adam site of the library held to the update statement, element by element.
 
-adam_update (csrc/kernels.hpp) is one statement applied from about thirty call sites, each with its own plumbing of alpha_t,
+adam_update (csrc/adam.hpp) is one statement applied from about thirty call sites, each with its own plumbing of alpha_t,
 1 - b1, 1 - b2, eps and 1 / count and its own map from threads to the elements of the flat buffer.  The update is elementwise,
 and every schedule leaves the gradient SUMS it applied in the gradient buffer and the count in tail[4]: from the device's own
 (p, m, v) before a step and its own g after it, tests/adam_ref.py predicts (p', m', v') in fp64 to a few fp32 roundings -- the
