@@ -43,6 +43,7 @@
 #include "liksig.hpp"
 #include "gclip.hpp"
 #include "aggpost.hpp"
+#include "hostutil.hpp"      // aligned_to, first_on_device
 
 using namespace gmvae;
 
@@ -127,14 +128,6 @@ static bool device_is_gfx950() {
     is_of[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && !strncmp(pr.gcnArchName, "gfx950", 6)) ? 1 : -1;
   }
   return is_of[dev] > 0;
-}
-// one-shot per DEVICE (hipFuncSetAttribute belongs to the device's code object; a process may drive several devices)
-static bool first_on_device(bool (&seen)[64]) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
-  if (seen[dev]) return false;
-  seen[dev] = true;
-  return true;
 }
 // ------------------------------------------------------------------ layout
 struct NetL {
@@ -2891,7 +2884,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   return cx.err;
 }
 
-static int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static int aligned16(const void* p) { return aligned_to(p, 16); }
 // GMVAE_X_F32: x is read as float [B][D] -- its base 16-byte aligned (behind the NULL checks of every entry point that takes x)
 static int check_x_align(const GmvaeDims* d, const void* x) { return (x_f32(*d) && !aligned16(x)) ? GMVAE_E_ALIGN : 0; }
 
@@ -3313,7 +3306,6 @@ int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x
 static int ap_check_sizes(int64_t M, int L) {
   return (M < 1 || L < 1 || M > (1ll << 30) || L > (1 << 16)) ? GMVAE_E_DIMS : 0;
 }
-static int aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 int gmvae_mixture_logpdf_workspace_bytes(int64_t M, int L, int per_dim, uint64_t* bytes) {
   if (int e = ap_check_sizes(M, L)) return e;

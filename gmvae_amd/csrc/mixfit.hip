@@ -1,8 +1,13 @@
 // gmvae_mixfit_* and gmvae_mixfit_full_*: the host side of csrc/mixfit.hpp and csrc/mixfit_full.hpp (include/gmvae_hip.h).  A translation unit of its own, for the reason at the top
 // of csrc/tsne.hip: the model-independent evaluator's kernels, descriptors and symbols stay out of the training step's code object.
+// What the two fits' entry points share stands once, at the top: the N and K gate, the n_iter / reg_covar check, the pointer and
+// alignment ladder, the once-per-device LDS attribute and the iteration loop's optional outputs.  Each fit's own L and product
+// gate, workspace layout and launches stay beside its plan.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "../../include/gmvae_hip.h"
 #include "hostutil.hpp"
@@ -13,24 +18,70 @@ using namespace gmvae;
 
 namespace {
 
+typedef std::initializer_list<const void*> Pointers;
+
+// the checks, in the header's order: sizes -- the gate on N and K here, each fit's L and product next to it --, then n_iter and
+// reg_covar (run), then NULL, then alignment
+bool nk_in_gate(int64_t N, int K) { return N >= 1 && N <= (1ll << 24) && K >= 1 && K <= 256; }
+
+int check_iterations(int n_iter, float reg_covar) {
+  return (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) ? GMVAE_E_DIMS : 0;
+}
+
+// `required` may not be NULL; they and the `optional` outputs are 4-byte aligned, the workspace (required too) 16
+int check_pointers(Pointers required, Pointers optional, const void* workspace) {
+  for (const void* p : required)
+    if (!p) return GMVAE_E_NULL;
+  if (!workspace) return GMVAE_E_NULL;
+  for (const void* p : required)
+    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
+  for (const void* p : optional)
+    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
+  return aligned_to(workspace, 16) ? 0 : GMVAE_E_ALIGN;
+}
+
+// one-shot per DEVICE (`seen` is the caller's table): these kernels may ask for more than 64 KiB of dynamic LDS
+void allow_lds(bool (&seen)[64], Pointers kernels) {
+  if (!first_on_device(seen)) return;
+  for (const void* k : kernels) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+}
+
+// n_iter times iteration(it, history slot `it` or NULL, counts_out on the last iteration or NULL)
+template <class Iteration>
+int run_iterations(int n_iter, float* loglik_history, float* counts_out, Iteration iteration) {
+  for (int it = 0; it < n_iter; ++it)
+    iteration(it, loglik_history ? loglik_history + it : nullptr, it == n_iter - 1 ? counts_out : nullptr);
+  return (int)hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------- diagonal covariances
 int mf_check_sizes(int64_t N, int L, int K) {
-  if (N < 1 || N > (1ll << 24) || L < 1 || L > 4096 || K < 1 || K > 256 || (int64_t)K * L > kMfMaxKL) return GMVAE_E_DIMS;
-  return 0;
+  return (!nk_in_gate(N, K) || L < 1 || L > 4096 || (int64_t)K * L > kMfMaxKL) ? GMVAE_E_DIMS : 0;
 }
 
 // Workspace, a function of (N, L, K): the workgroups' partial sums [groups][stride] (fp64).  Nothing is kept per row.
 uint64_t mf_workspace_bytes(const MfPlan& p) { return ((uint64_t)p.groups * (uint64_t)p.stride * sizeof(double) + 15) / 16 * 16; }
 
-// one-shot per DEVICE: the pass may ask for more than 64 KiB of dynamic LDS
 void mf_allow_lds() {
   static bool seen[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-    if (seen[dev]) return;
-    seen[dev] = true;
-  }
-  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_pass<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
-  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_pass<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
+  allow_lds(seen, {reinterpret_cast<const void*>(mixfit_pass<true>), reinterpret_cast<const void*>(mixfit_pass<false>)});
+}
+
+// ------------------------------------------------------------------------------------------------ full covariances
+int mff_check_sizes(int64_t N, int L, int K) {
+  return (!nk_in_gate(N, K) || L < 1 || L > kMffMaxL || (int64_t)K * L * L > kMffMaxKLL) ? GMVAE_E_DIMS : 0;
+}
+
+// Workspace, in doubles: W [K][L (L + 1) / 2], sum ln C_dd [K], then the workgroups' partial sums [groups][stride].  Nothing per row.
+uint64_t mff_part_offset(int L, int K) { return (uint64_t)K * (uint64_t)mff_tri(L) + (uint64_t)K; }
+uint64_t mff_workspace_bytes(const MffPlan& p, int L, int K) {
+  return ((mff_part_offset(L, K) + (uint64_t)p.groups * (uint64_t)p.stride) * sizeof(double) + 15) / 16 * 16;
+}
+
+void mff_allow_lds() {
+  static bool seen[64];
+  allow_lds(seen, {reinterpret_cast<const void*>(mixfit_full_factor), reinterpret_cast<const void*>(mixfit_full_pass<true>),
+                   reinterpret_cast<const void*>(mixfit_full_pass<false>)});
 }
 
 }  // namespace
@@ -47,10 +98,7 @@ int gmvae_mixfit_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes) {
 int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* sigma,
                         float* log_resp_out, float* lse_out, void* workspace, void* stream) {
   if (int e = mf_check_sizes(N, L, K)) return e;
-  if (!codes || !logw || !mu || !sigma || !workspace) return GMVAE_E_NULL;
-  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(sigma, 4) || !aligned_to(log_resp_out, 4) ||
-      !aligned_to(lse_out, 4) || !aligned_to(workspace, 16))
-    return GMVAE_E_ALIGN;
+  if (int e = check_pointers({codes, logw, mu, sigma}, {log_resp_out, lse_out}, workspace)) return e;
   const MfPlan p = mf_plan(N, L, K);
   (void)hipGetLastError();
   mf_allow_lds();
@@ -62,11 +110,8 @@ int gmvae_mixfit_assign(const float* codes, int64_t N, int L, int K, const float
 int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* sigma, float reg_covar, int n_iter,
                      float* loglik_history, float* counts_out, void* workspace, void* stream) {
   if (int e = mf_check_sizes(N, L, K)) return e;
-  if (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) return GMVAE_E_DIMS;
-  if (!codes || !logw || !mu || !sigma || !workspace) return GMVAE_E_NULL;
-  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(sigma, 4) ||
-      !aligned_to(loglik_history, 4) || !aligned_to(counts_out, 4) || !aligned_to(workspace, 16))
-    return GMVAE_E_ALIGN;
+  if (int e = check_iterations(n_iter, reg_covar)) return e;
+  if (int e = check_pointers({codes, logw, mu, sigma}, {loglik_history, counts_out}, workspace)) return e;
   if (n_iter == 0) return 0;
   const MfPlan p = mf_plan(N, L, K);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -74,47 +119,13 @@ int gmvae_mixfit_run(const float* codes, int64_t N, int L, int K, float* logw, f
   const unsigned update_blocks = (unsigned)((K * L + kMfFoldSlots - 1) / kMfFoldSlots) + 1;
   (void)hipGetLastError();
   mf_allow_lds();
-  for (int it = 0; it < n_iter; ++it) {
+  return run_iterations(n_iter, loglik_history, counts_out, [&](int, float* hist, float* counts) {
     hipLaunchKernelGGL(mixfit_pass<true>, dim3((unsigned)p.groups), dim3(kMfBlock), p.lds, st, codes, (int)N, L, K, logw, mu, sigma,
                        p.tile, p.per_group, (float*)nullptr, (float*)nullptr, part, p.stride);
     hipLaunchKernelGGL(mixfit_update, dim3(update_blocks), dim3(kMfBlock), 0, st, part, p.groups, p.stride, (int)N, L, K, reg_covar, logw,
-                       mu, sigma, loglik_history ? loglik_history + it : nullptr, it == n_iter - 1 ? counts_out : nullptr);
-  }
-  return (int)hipGetLastError();
+                       mu, sigma, hist, counts);
+  });
 }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ full covariances
-namespace {
-
-int mff_check_sizes(int64_t N, int L, int K) {
-  if (N < 1 || N > (1ll << 24) || L < 1 || L > kMffMaxL || K < 1 || K > 256 || (int64_t)K * L * L > kMffMaxKLL) return GMVAE_E_DIMS;
-  return 0;
-}
-
-// Workspace, in doubles: W [K][L (L + 1) / 2], sum ln C_dd [K], then the workgroups' partial sums [groups][stride].  Nothing per row.
-uint64_t mff_part_offset(int L, int K) { return (uint64_t)K * (uint64_t)mff_tri(L) + (uint64_t)K; }
-uint64_t mff_workspace_bytes(const MffPlan& p, int L, int K) {
-  return ((mff_part_offset(L, K) + (uint64_t)p.groups * (uint64_t)p.stride) * sizeof(double) + 15) / 16 * 16;
-}
-
-// one-shot per DEVICE: the kernels may ask for more than 64 KiB of dynamic LDS
-void mff_allow_lds() {
-  static bool seen[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-    if (seen[dev]) return;
-    seen[dev] = true;
-  }
-  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_factor), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
-  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_pass<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
-  hipFuncSetAttribute(reinterpret_cast<const void*>(mixfit_full_pass<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
-}
-
-}  // namespace
-
-extern "C" {
 
 int gmvae_mixfit_full_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes) {
   if (int e = mff_check_sizes(N, L, K)) return e;
@@ -126,18 +137,15 @@ int gmvae_mixfit_full_workspace_bytes(int64_t N, int L, int K, uint64_t* bytes) 
 int gmvae_mixfit_full_assign(const float* codes, int64_t N, int L, int K, const float* logw, const float* mu, const float* cov,
                              float* log_resp_out, float* lse_out, int32_t* info_out, void* workspace, void* stream) {
   if (int e = mff_check_sizes(N, L, K)) return e;
-  if (!codes || !logw || !mu || !cov || !workspace) return GMVAE_E_NULL;
-  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(cov, 4) || !aligned_to(log_resp_out, 4) ||
-      !aligned_to(lse_out, 4) || !aligned_to(info_out, 4) || !aligned_to(workspace, 16))
-    return GMVAE_E_ALIGN;
+  if (int e = check_pointers({codes, logw, mu, cov}, {log_resp_out, lse_out, info_out}, workspace)) return e;
   const MffPlan p = mff_plan(N, L, K);
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* const W = static_cast<double*>(workspace);
   double* const sumlog = W + (size_t)K * mff_tri(L);
   (void)hipGetLastError();
   mff_allow_lds();
-  hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMffBlock), p.lds_factor, st, cov, L, W, sumlog, info_out, 1);
-  hipLaunchKernelGGL(mixfit_full_pass<false>, dim3((unsigned)p.groups), dim3(kMffBlock), p.lds, st, codes, (int)N, L, K, logw, mu,
+  hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMfBlock), p.lds_factor, st, cov, L, W, sumlog, info_out, 1);
+  hipLaunchKernelGGL(mixfit_full_pass<false>, dim3((unsigned)p.groups), dim3(kMfBlock), p.lds, st, codes, (int)N, L, K, logw, mu,
                      (const double*)W, (const double*)sumlog, p.tile, p.per_group, log_resp_out, lse_out, (double*)nullptr, p.stride);
   return (int)hipGetLastError();
 }
@@ -145,11 +153,8 @@ int gmvae_mixfit_full_assign(const float* codes, int64_t N, int L, int K, const 
 int gmvae_mixfit_full_run(const float* codes, int64_t N, int L, int K, float* logw, float* mu, float* cov, float reg_covar, int n_iter,
                           float* loglik_history, float* counts_out, int32_t* info_out, void* workspace, void* stream) {
   if (int e = mff_check_sizes(N, L, K)) return e;
-  if (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) return GMVAE_E_DIMS;
-  if (!codes || !logw || !mu || !cov || !workspace) return GMVAE_E_NULL;
-  if (!aligned_to(codes, 4) || !aligned_to(logw, 4) || !aligned_to(mu, 4) || !aligned_to(cov, 4) || !aligned_to(loglik_history, 4) ||
-      !aligned_to(counts_out, 4) || !aligned_to(info_out, 4) || !aligned_to(workspace, 16))
-    return GMVAE_E_ALIGN;
+  if (int e = check_iterations(n_iter, reg_covar)) return e;
+  if (int e = check_pointers({codes, logw, mu, cov}, {loglik_history, counts_out, info_out}, workspace)) return e;
   if (n_iter == 0) return 0;
   const MffPlan p = mff_plan(N, L, K);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -159,17 +164,15 @@ int gmvae_mixfit_full_run(const float* codes, int64_t N, int L, int K, float* lo
   const unsigned update_blocks = (unsigned)((K * mff_tri(L) + kMfFoldSlots - 1) / kMfFoldSlots) + 1;
   (void)hipGetLastError();
   mff_allow_lds();
-  for (int it = 0; it < n_iter; ++it) {
-    hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMffBlock), p.lds_factor, st, (const float*)cov, L, W, sumlog, info_out,
+  return run_iterations(n_iter, loglik_history, counts_out, [&](int it, float* hist, float* counts) {
+    hipLaunchKernelGGL(mixfit_full_factor, dim3((unsigned)K), dim3(kMfBlock), p.lds_factor, st, (const float*)cov, L, W, sumlog, info_out,
                        it == 0 ? 1 : 0);
-    hipLaunchKernelGGL(mixfit_full_pass<true>, dim3((unsigned)p.groups), dim3(kMffBlock), p.lds, st, codes, (int)N, L, K,
+    hipLaunchKernelGGL(mixfit_full_pass<true>, dim3((unsigned)p.groups), dim3(kMfBlock), p.lds, st, codes, (int)N, L, K,
                        (const float*)logw, (const float*)mu, (const double*)W, (const double*)sumlog, p.tile, p.per_group,
                        (float*)nullptr, (float*)nullptr, part, p.stride);
     hipLaunchKernelGGL(mixfit_full_update, dim3(update_blocks), dim3(kMfBlock), 0, st, (const double*)part, p.groups, p.stride, (int)N, L,
-                       K, reg_covar, logw, mu, cov, loglik_history ? loglik_history + it : nullptr,
-                       it == n_iter - 1 ? counts_out : nullptr);
-  }
-  return (int)hipGetLastError();
+                       K, reg_covar, logw, mu, cov, hist, counts);
+  });
 }
 
 }  // extern "C"

@@ -32,6 +32,12 @@
 // contiguous run of workgroups in order, the 16 runs added in order by the slot's first thread -- applies the M-step to its slot
 // and writes mu and sigma in place; one more block folds R_k for every k and sum lse, and writes logw, counts_out and the history
 // entry.  One owner per sum, fixed-order folds, no float atomics: two runs give the same bits.
+// Shared with the full-covariance fit (csrc/mixfit_full.hpp): the plan's tail (mf_plan_groups), MF_ADVANCE, mf_wave_sum, the fold
+// (mf_fold_run) and the update's last block (mf_update_weights, which takes the offset of R_k in a workgroup's partials as an
+// int), with kMfBlock, kMfMaxGroups, kMfLdsBytes and the fold's shape.  The E-step's tail -- stage, rows, the tile's sum of lse,
+// sweep -- is NOT shared: as forceinline helpers it compiled to the same instructions in another schedule, and one pass or the
+// other then ran 1 to 5 % slower on the MI355X (profiles/mixfit_notes.md), so mixfit_pass and mixfit_full_pass each keep their
+// own text of those four steps, and a change to one of them is to be made in both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -57,17 +63,21 @@ static inline size_t mf_lds_bytes(int L, int K, int T) {
   const size_t Lp = (size_t)(L | 1), Kp = (size_t)(K | 1);
   return 8 * (3 * (size_t)T + (size_t)T * Kp + (size_t)K) + 4 * (2 * (size_t)K * Lp + (size_t)T * Lp);
 }
+// the tail of a plan: N rows in tiles of T -> whole tiles per workgroup -> workgroups, gmax of them at most
+static inline void mf_plan_groups(MfPlan& p, int64_t N, int64_t T, int64_t gmax) {
+  const int64_t tiles = (N + T - 1) / T, g = tiles < gmax ? tiles : gmax;
+  const int64_t per = (tiles + g - 1) / g * T;
+  p.tile = (int)T;
+  p.per_group = (int)per;
+  p.groups = (int)((N + per - 1) / per);
+}
 static inline MfPlan mf_plan(int64_t N, int L, int K) {
   MfPlan p;
   const size_t image = mf_lds_bytes(L, K, 0), row = mf_lds_bytes(L, K, 1) - image;
   int64_t T = (int64_t)(((size_t)kMfLdsBytes - image) / row);      // >= 1 inside the gate: image <= 135,168 and row <= 16,452 bytes
   T = T > kMfMaxTile ? kMfMaxTile : T;
   T = T > N ? N : T;
-  const int64_t tiles = (N + T - 1) / T, g = tiles < kMfMaxGroups ? tiles : kMfMaxGroups;
-  const int64_t per = (tiles + g - 1) / g * T;
-  p.tile = (int)T;
-  p.per_group = (int)per;
-  p.groups = (int)((N + per - 1) / per);
+  mf_plan_groups(p, N, T, kMfMaxGroups);
   p.stride = (2 * L + 1) * K + 1;      // S1 [K][L], S2 [K][L], R [K], sum lse
   p.lds = mf_lds_bytes(L, K, (int)T);
   return p;
@@ -238,14 +248,47 @@ __device__ __forceinline__ double mf_fold_run(const double* __restrict__ part, c
   return a;
 }
 
+// the update's last block: folds R_k for every k (offset offR + k of a workgroup's partials) and sum lse (offR + K), and writes
+// logw, counts_out and the history entry.  s_p: the kernel's fold planes, of which [0] and [1][0] serve here
+__device__ __forceinline__ void mf_update_weights(const double* __restrict__ part, const int G, const int stride, const int offR,
+                                                  const int N, const int K, float* __restrict__ logw, float* __restrict__ hist_out,
+                                                  float* __restrict__ counts_out, double (*s_p)[kMfFoldSlots][kMfFoldParts + 1]) {
+  __shared__ double s_R[256];
+  __shared__ double s_tot;
+  const int tid = threadIdx.x, q = tid / kMfFoldParts, p = tid % kMfFoldParts;
+  for (int k0 = 0; k0 < K; k0 += kMfFoldSlots) {
+    const int k = k0 + q;
+    if (k < K) s_p[0][q][p] = mf_fold_run(part, G, stride, (size_t)(offR + k), p);
+    __syncthreads();
+    if (k < K && p == 0) {
+      double R = 0.0;
+      for (int j = 0; j < kMfFoldParts; ++j) R += s_p[0][q][j];
+      s_R[k] = R;
+    }
+    __syncthreads();
+  }
+  if (q == 0) s_p[1][0][p] = mf_fold_run(part, G, stride, (size_t)(offR + K), p);
+  __syncthreads();
+  if (tid == 0) {
+    double tot = 0.0, lse = 0.0;
+    for (int k = 0; k < K; ++k) tot += s_R[k] + kMfEps0;
+    for (int j = 0; j < kMfFoldParts; ++j) lse += s_p[1][0][j];
+    s_tot = tot;
+    if (hist_out) *hist_out = (float)(lse / (double)N);
+  }
+  __syncthreads();
+  if (tid < K) {
+    logw[tid] = (float)log((s_R[tid] + kMfEps0) / s_tot);
+    if (counts_out) counts_out[tid] = (float)s_R[tid];
+  }
+}
+
 // blocks [0, slot_blocks): the M-step of kMfFoldSlots slots (k, d) each; the last block: logw, counts_out, the history entry
 __global__ __launch_bounds__(kMfBlock) void mixfit_update(const double* __restrict__ part, const int G, const int stride, const int N,
                                                           const int L, const int K, const float reg_covar, float* __restrict__ logw,
                                                           float* __restrict__ mu, float* __restrict__ sigma,
                                                           float* __restrict__ hist_out, float* __restrict__ counts_out) {
   __shared__ double s_p[3][kMfFoldSlots][kMfFoldParts + 1];
-  __shared__ double s_R[256];
-  __shared__ double s_tot;
   const int tid = threadIdx.x, q = tid / kMfFoldParts, p = tid % kMfFoldParts, KL = K * L;
   const int slot_blocks = (KL + kMfFoldSlots - 1) / kMfFoldSlots;
   if ((int)blockIdx.x < slot_blocks) {
@@ -273,31 +316,7 @@ __global__ __launch_bounds__(kMfBlock) void mixfit_update(const double* __restri
     }
     return;
   }
-  for (int k0 = 0; k0 < K; k0 += kMfFoldSlots) {
-    const int k = k0 + q;
-    if (k < K) s_p[0][q][p] = mf_fold_run(part, G, stride, (size_t)2 * KL + k, p);
-    __syncthreads();
-    if (k < K && p == 0) {
-      double R = 0.0;
-      for (int j = 0; j < kMfFoldParts; ++j) R += s_p[0][q][j];
-      s_R[k] = R;
-    }
-    __syncthreads();
-  }
-  if (q == 0) s_p[1][0][p] = mf_fold_run(part, G, stride, (size_t)2 * KL + K, p);
-  __syncthreads();
-  if (tid == 0) {
-    double tot = 0.0, lse = 0.0;
-    for (int k = 0; k < K; ++k) tot += s_R[k] + kMfEps0;
-    for (int j = 0; j < kMfFoldParts; ++j) lse += s_p[1][0][j];
-    s_tot = tot;
-    if (hist_out) *hist_out = (float)(lse / (double)N);
-  }
-  __syncthreads();
-  if (tid < K) {
-    logw[tid] = (float)log((s_R[tid] + kMfEps0) / s_tot);
-    if (counts_out) counts_out[tid] = (float)s_R[tid];
-  }
+  mf_update_weights(part, G, stride, 2 * KL, N, K, logw, hist_out, counts_out, s_p);
 }
 
 }  // namespace gmvae

@@ -16,7 +16,7 @@
 // it: a uniform decision); column t of a and row t of x divided by c = sqrt(p); then the two rank-1 updates a_ij -= C_it C_jt
 // (t < j <= i) and x_ij -= C_it X_tj (j <= t < i) over a 16 x 16 thread grid.  Two barriers a step; a ends as C_k and x as
 // W_k = C_k^-1.  W_k (packed) and sum_d ln C_dd go to the workspace; a failed component stores W_k = 0 and +inf.
-// mixfit_full_pass: a workgroup of kMffBlock threads owns a contiguous slice of `per_group` rows and walks it in tiles of T rows
+// mixfit_full_pass: a workgroup of kMfBlock threads owns a contiguous slice of `per_group` rows and walks it in tiles of T rows
 // (T a multiple of 4, <= kMffMaxTile, chosen on the host so that everything below fits the LDS, mff_plan).  K L^2 fp64 does not fit
 // the LDS (320 KiB at K = 10, L = 64), so the tile of rows is resident and the components pass by it, one W_k staged at a time.
 // LDS, all dynamic: W_k packed [L (L + 1) / 2] and mu_k [L] (fp64); z - mu_k [T][L | 1] (fp64; the odd row stride of 8-byte words keeps
@@ -29,7 +29,9 @@
 //           of a row are added by xor shuffles in a fixed order; l = c_k - q / 2.  (The same product on the vector units, 16
 //           threads sharing four rows, took 1.1 ms of a 1.38 ms iteration at N = 60,000, L = 64, K = 10:
 //           profiles/mixfit_full_notes.md);
-//   rows, sweep:  as mixfit_pass: max, fp32 exponentials summed in fp64, lse, log r written coalesced, r left in LDS;
+//   rows, sweep:  as mixfit_pass (the same text, kept in step by hand: csrc/mixfit.hpp says why): max, fp32 exponentials summed in
+//           fp64, lse, log r written coalesced, r left in LDS; here l = -inf -- an absent component -- gives log r = -inf even in a
+//           row whose every l is -inf;
 //   M, for each k (kAccum):  z - mu_k staged again; R_k and S1_kd by four threads each, added by shuffles; S2_k by v_mfma_f64_16x16x4_f64: a wave
 //           owns 16 x 16 blocks (bi >= bj only) of the L x L sum, A = (r_n (z_n - mu_k)_i) [16 x 4 rows], B = (z_n - mu_k)_j
 //           [4 rows x 16], four rows of the tile an instruction; lane l holds A[i = l & 15][n = l >> 4] and B[n = l >> 4][j = l & 15],
@@ -41,7 +43,9 @@
 // mixfit_full_update: folds the G workgroups' partials as mixfit_update does (16 slots a block, 16 threads a slot, fixed order):
 // a slot is one (k, i, j <= i); it folds S2_kij, S1_ki, S1_kj and R_k (the same folds in the same order wherever they are
 // repeated, so the same bits), applies the M-step and writes cov'_kij and cov'_kji -- bit-symmetric -- and, where i = j, mu'_ki.
-// One more block folds R_k for every k and sum lse, and writes logw, counts_out and the history entry.
+// One more block folds R_k for every k and sum lse, and writes logw, counts_out and the history entry: mixfit_update's last block
+// (csrc/mixfit.hpp mf_update_weights) at this layout's offset of R.  The plan ends in mf_plan_groups; the block size and the
+// workgroup limit are kMfBlock and kMfMaxGroups.
 // One owner per sum, fixed-order fp64 folds, no float atomics: two runs give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,9 +56,7 @@
 
 namespace gmvae {
 
-constexpr int kMffBlock = 256;                     // threads of a workgroup
 constexpr int kMffMaxTile = 64;                    // rows per tile at most: 16 rows for each of the four waves
-constexpr int kMffMaxGroups = 256;                 // workgroups of a pass at most: one per CU
 constexpr int kMffMaxL = 128;                      // the factor kernel holds 2 L (L + 1) / 2 fp64 in LDS: 129 KiB
 constexpr int kMffMaxKLL = 1 << 20;                // the K L^2 gate
 constexpr int64_t kMffMaxPart = 1ll << 23;         // doubles of partial sums at most (64 MiB): bounds the number of row slices
@@ -65,9 +67,8 @@ __host__ __device__ static inline int mff_tri(int i) { return i * (i + 1) / 2; }
 
 // the pass's shape for (N, L, K): rows per tile, rows per workgroup (whole tiles), workgroups, doubles per workgroup's partials,
 // LDS bytes of the pass and of the factor kernel
-struct MffPlan {
-  int tile, per_group, groups, stride;
-  size_t lds, lds_factor;
+struct MffPlan : MfPlan {
+  size_t lds_factor;
 };
 static inline size_t mff_lds_bytes(int L, int K, int T) {
   const size_t Lp = (size_t)(L | 1), Kp = (size_t)(K | 1), P = (size_t)mff_tri(L);
@@ -81,18 +82,14 @@ static inline MffPlan mff_plan(int64_t N, int L, int K) {
   T &= ~(int64_t)3;
   p.stride = K * (mff_tri(L) + L + 1) + 1;      // S2 [K][L (L + 1) / 2], S1 [K][L], R [K], sum lse
   int64_t gmax = kMffMaxPart / p.stride;        // >= 7 inside the gate
-  gmax = gmax > kMffMaxGroups ? kMffMaxGroups : gmax;
-  const int64_t tiles = (N + T - 1) / T, g = tiles < gmax ? tiles : gmax;
-  const int64_t per = (tiles + g - 1) / g * T;
-  p.tile = (int)T;
-  p.per_group = (int)per;
-  p.groups = (int)((N + per - 1) / per);
+  gmax = gmax > kMfMaxGroups ? kMfMaxGroups : gmax;
+  mf_plan_groups(p, N, T, gmax);
   p.lds = mff_lds_bytes(L, K, (int)T);
   p.lds_factor = 16 * (size_t)mff_tri(L);
   return p;
 }
 
-__global__ __launch_bounds__(kMffBlock) void mixfit_full_factor(const float* __restrict__ cov, const int L, double* __restrict__ Wg,
+__global__ __launch_bounds__(kMfBlock) void mixfit_full_factor(const float* __restrict__ cov, const int L, double* __restrict__ Wg,
                                                                 double* __restrict__ sumlog, int32_t* __restrict__ info_out,
                                                                 const int first) {
   extern __shared__ __attribute__((aligned(16))) char mff_smem[];
@@ -101,13 +98,13 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_factor(const float* __r
   double* const x = a + P;                                    // [P]: the identity, then W_k
   const float* __restrict__ src = cov + (size_t)k * L * L;
   {
-    const int i0 = tid / L, step_i = kMffBlock / L;
-    for (int s = tid, i = i0, j = tid - i0 * L; s < L * L; s += kMffBlock) {
+    const int i0 = tid / L, step_i = kMfBlock / L;
+    for (int s = tid, i = i0, j = tid - i0 * L; s < L * L; s += kMfBlock) {
       if (j <= i) {
         a[mff_tri(i) + j] = (double)src[s];
         x[mff_tri(i) + j] = i == j ? 1.0 : 0.0;
       }
-      MF_ADVANCE(i, j, step_i, kMffBlock - step_i * L, L);
+      MF_ADVANCE(i, j, step_i, kMfBlock - step_i * L, L);
     }
   }
   __syncthreads();
@@ -138,7 +135,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_factor(const float* __r
     __syncthreads();
   }
   double* __restrict__ dst = Wg + (size_t)k * P;
-  for (int s = tid; s < P; s += kMffBlock) dst[s] = info ? 0.0 : x[s];
+  for (int s = tid; s < P; s += kMfBlock) dst[s] = info ? 0.0 : x[s];
   if (tid == 0) {
     sumlog[k] = info ? (double)INFINITY : sl;
     if (info_out && (first || info_out[k] == 0)) info_out[k] = info;
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_factor(const float* __r
 }
 
 template <bool kAccum>
-__global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __restrict__ codes, const int N, const int L, const int K,
+__global__ __launch_bounds__(kMfBlock) void mixfit_full_pass(const float* __restrict__ codes, const int N, const int L, const int K,
                                                               const float* __restrict__ logw, const float* __restrict__ mu,
                                                               const double* __restrict__ Wg, const double* __restrict__ sumlog,
                                                               const int T, const int per_group, float* __restrict__ log_resp_out,
@@ -162,8 +159,8 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
   double* const s_ls = s_m + T;                                 // [T]
   float* const s_z = reinterpret_cast<float*>(s_ls + T);        // [T][Lp]
 
-  const int nL0 = tid / L, dL0 = tid - nL0 * L, stepL_n = kMffBlock / L, stepL_d = kMffBlock - stepL_n * L;
-  const int nK0 = tid / K, kK0 = tid - nK0 * K, stepK_n = kMffBlock / K, stepK_d = kMffBlock - stepK_n * K;
+  const int nL0 = tid / L, dL0 = tid - nL0 * L, stepL_n = kMfBlock / L, stepL_d = kMfBlock - stepL_n * L;
+  const int nK0 = tid / K, kK0 = tid - nK0 * K, stepK_n = kMfBlock / K, stepK_d = kMfBlock - stepK_n * K;
   const int wave = tid >> 6, lane = tid & 63, nb = (L + 15) >> 4;
 
   const int64_t g_lo = (int64_t)blockIdx.x * per_group, g_hi = g_lo + per_group < N ? g_lo + per_group : N;
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
     {
       const float* __restrict__ src = codes + (size_t)r0 * L;
       int n = nL0, d = dL0;
-      for (int i = tid; i < rows * L; i += kMffBlock) {
+      for (int i = tid; i < rows * L; i += kMfBlock) {
         s_z[n * Lp + d] = src[i];
         MF_ADVANCE(n, d, stepL_n, stepL_d, L);
       }
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
     // z - mu_k for all T rows (0 past the end of the tile), mu_k in s_mu: called between two barriers
     auto stage_dz = [&]() {
       int n = nL0, d = dL0;
-      for (int i = tid; i < T * L; i += kMffBlock) {
+      for (int i = tid; i < T * L; i += kMfBlock) {
         s_dz[n * Lp + d] = n < rows ? (double)s_z[n * Lp + d] - s_mu[d] : 0.0;
         MF_ADVANCE(n, d, stepL_n, stepL_d, L);
       }
@@ -192,7 +189,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
       __syncthreads();      // s_z is staged; the previous component's products have read s_W and s_dz
       {
         const double* __restrict__ wk = Wg + (size_t)k * P;
-        for (int s = tid; s < P; s += kMffBlock) s_W[s] = wk[s];
+        for (int s = tid; s < P; s += kMfBlock) s_W[s] = wk[s];
         if (tid < L) s_mu[tid] = (double)mu[(size_t)k * L + tid];
       }
       __syncthreads();
@@ -200,7 +197,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
       __syncthreads();
       const double sk = sumlog[k];
       const double c = sk == (double)INFINITY ? -(double)INFINITY : ((double)logw[k] - sk) - 0.91893853320467274178 * (double)L;
-      for (int rb = wave; 16 * rb < rows; rb += kMffBlock >> 6) {      // (uniform in the wave: the MFMA runs with every lane on)
+      for (int rb = wave; 16 * rb < rows; rb += kMfBlock >> 6) {      // (uniform in the wave: the MFMA runs with every lane on)
         const int n = 16 * rb + (lane & 15), jj = lane >> 4;
         const bool n_in = n < rows;
         const double* __restrict__ zr = s_dz + (n_in ? n : 0) * Lp;
@@ -263,7 +260,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
       for (int n = tid; n < rows; n += 64) a += s_lse[n];
       lse_acc += mf_wave_sum(a);
     }
-    for (int i = tid, n = nK0, k = kK0; i < rows * K; i += kMffBlock) {
+    for (int i = tid, n = nK0, k = kK0; i < rows * K; i += kMfBlock) {
       const double l = s_l[n * Kp + k];
       const float lr = l == -(double)INFINITY ? -INFINITY : (float)((l - s_m[n]) - s_ls[n]);
       if (log_resp_out) log_resp_out[(size_t)r0 * K + i] = lr;
@@ -279,7 +276,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
         __syncthreads();
         stage_dz();
         __syncthreads();
-        for (int s = tid; s < 4 * (L + 1); s += kMffBlock) {      // item (d, part): the rows part, part + 4, ...; d = L is R_k
+        for (int s = tid; s < 4 * (L + 1); s += kMfBlock) {      // item (d, part): the rows part, part + 4, ...; d = L is R_k
           const int d = s >> 2, part = s & 3;
           double a = 0.0;
           if (d < L) {
@@ -295,7 +292,7 @@ __global__ __launch_bounds__(kMffBlock) void mixfit_full_pass(const float* __res
             gpart[off] = a;
           }
         }
-        for (int b = wave; b < nblk; b += kMffBlock >> 6) {      // (uniform in the wave: the MFMA runs with every lane on)
+        for (int b = wave; b < nblk; b += kMfBlock >> 6) {      // (uniform in the wave: the MFMA runs with every lane on)
           int bi = 0, bj = b;
           while (bj > bi) {
             bj -= bi + 1;
@@ -342,8 +339,6 @@ __global__ __launch_bounds__(kMfBlock) void mixfit_full_update(const double* __r
                                                                float* __restrict__ mu, float* __restrict__ cov,
                                                                float* __restrict__ hist_out, float* __restrict__ counts_out) {
   __shared__ double s_p[4][kMfFoldSlots][kMfFoldParts + 1];
-  __shared__ double s_R[256];
-  __shared__ double s_tot;
   const int tid = threadIdx.x, q = tid / kMfFoldParts, p = tid % kMfFoldParts, P = mff_tri(L), KP = K * P;
   const int slot_blocks = (KP + kMfFoldSlots - 1) / kMfFoldSlots;
   if ((int)blockIdx.x < slot_blocks) {
@@ -388,31 +383,7 @@ __global__ __launch_bounds__(kMfBlock) void mixfit_full_update(const double* __r
     }
     return;
   }
-  for (int k0 = 0; k0 < K; k0 += kMfFoldSlots) {
-    const int k = k0 + q;
-    if (k < K) s_p[0][q][p] = mf_fold_run(part, G, stride, (size_t)KP + K * L + k, p);
-    __syncthreads();
-    if (k < K && p == 0) {
-      double R = 0.0;
-      for (int u = 0; u < kMfFoldParts; ++u) R += s_p[0][q][u];
-      s_R[k] = R;
-    }
-    __syncthreads();
-  }
-  if (q == 0) s_p[1][0][p] = mf_fold_run(part, G, stride, (size_t)KP + K * L + K, p);
-  __syncthreads();
-  if (tid == 0) {
-    double tot = 0.0, lse = 0.0;
-    for (int k = 0; k < K; ++k) tot += s_R[k] + kMfEps0;
-    for (int u = 0; u < kMfFoldParts; ++u) lse += s_p[1][0][u];
-    s_tot = tot;
-    if (hist_out) *hist_out = (float)(lse / (double)N);
-  }
-  __syncthreads();
-  if (tid < K) {
-    logw[tid] = (float)log((s_R[tid] + kMfEps0) / s_tot);
-    if (counts_out) counts_out[tid] = (float)s_R[tid];
-  }
+  mf_update_weights(part, G, stride, KP + K * L, N, K, logw, hist_out, counts_out, s_p);
 }
 
 }  // namespace gmvae

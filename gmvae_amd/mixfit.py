@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -31,16 +32,33 @@ def _check_sizes_full(N, Lz, K):
         raise ValueError(f"covariance='full': K must lie in [1, {MAX_K}] with K * L^2 <= 2^20: K = {K}, L = {Lz}")
 
 
-def full_workspace_bytes(N, Lz, K):
-    b = C.c_uint64()
-    L.check(L.lib.gmvae_mixfit_full_workspace_bytes(int(N), int(Lz), int(K), C.byref(b)), "gmvae_mixfit_full_workspace_bytes")
+class _Kind(NamedTuple):
+    """A covariance kind: what `_params`, `assign`, `_run`, the workspace's size and `fit` need to know about it."""
+    what: str                    # the mixture's name in a message
+    third: str                   # the third parameter's name, next to logw [K] and mu [K, L] ...
+    third_shape: Callable        # ... and its shape, of (K, L)
+    check_sizes: Callable        # the library's gate for this kind, as a ValueError
+    entry: str                   # the library's entry points: entry + "_workspace_bytes", "_assign", "_run"
+    info: bool                   # whether assign and run take info_out [K] (int32), ahead of the workspace
+
+
+_DIAG = _Kind("a mixture", "sigma", lambda K, Lz: (K, Lz), _check_sizes, "gmvae_mixfit", False)
+_FULL = _Kind("a full-covariance mixture", "cov", lambda K, Lz: (K, Lz, Lz), _check_sizes_full, "gmvae_mixfit_full", True)
+_KINDS = {"diag": _DIAG, "full": _FULL}
+
+
+def _workspace_bytes(kind, N, Lz, K):
+    b, name = C.c_uint64(), kind.entry + "_workspace_bytes"
+    L.check(getattr(L.lib, name)(int(N), int(Lz), int(K), C.byref(b)), name)
     return b.value
 
 
 def workspace_bytes(N, Lz, K):
-    b = C.c_uint64()
-    L.check(L.lib.gmvae_mixfit_workspace_bytes(int(N), int(Lz), int(K), C.byref(b)), "gmvae_mixfit_workspace_bytes")
-    return b.value
+    return _workspace_bytes(_DIAG, N, Lz, K)
+
+
+def full_workspace_bytes(N, Lz, K):
+    return _workspace_bytes(_FULL, N, Lz, K)
 
 
 def _codes(codes):
@@ -50,20 +68,6 @@ def _codes(codes):
     return codes
 
 
-def _params(params, Lz, dev, K=None):
-    """(logw [K], mu [K, L], sigma [K, L]) as fresh contiguous fp32 device tensors, from a tuple or a dict with those keys."""
-    if isinstance(params, dict):
-        params = (params["logw"], params["mu"], params["sigma"])
-    if len(params) != 3:
-        raise ValueError("a mixture is (logw, mu, sigma)")
-    logw, mu, sigma = (torch.as_tensor(t).to(dev, torch.float32).contiguous().clone() for t in params)
-    if logw.dim() != 1 or mu.shape != (logw.shape[0], Lz) or sigma.shape != mu.shape or (K is not None and logw.shape[0] != K):
-        raise ValueError(f"a mixture is logw [K], mu [K, {Lz}], sigma [K, {Lz}]"
-                         + (f" with K = {K}" if K is not None else "")
-                         + f": got {tuple(logw.shape)}, {tuple(mu.shape)}, {tuple(sigma.shape)}")
-    return logw, mu, sigma
-
-
 def is_full(params):
     """Whether `params` is a full-covariance mixture: a dict with `cov`, or a tuple whose third member is 3-D."""
     if isinstance(params, dict):
@@ -71,33 +75,44 @@ def is_full(params):
     return len(params) == 3 and torch.as_tensor(params[2]).dim() == 3
 
 
-def _params_full(params, Lz, dev, K=None):
-    """(logw [K], mu [K, L], cov [K, L, L]) as fresh contiguous fp32 device tensors, from a tuple or a dict with those keys."""
+def _params(kind, params, Lz, dev, K=None):
+    """(logw [K], mu [K, L], sigma [K, L] or cov [K, L, L]) as fresh contiguous fp32 device tensors, from a tuple or a dict with those keys."""
     if isinstance(params, dict):
-        params = (params["logw"], params["mu"], params["cov"])
+        params = (params["logw"], params["mu"], params[kind.third])
     if len(params) != 3:
-        raise ValueError("a full-covariance mixture is (logw, mu, cov)")
-    logw, mu, cov = (torch.as_tensor(t).to(dev, torch.float32).contiguous().clone() for t in params)
-    if logw.dim() != 1 or mu.shape != (logw.shape[0], Lz) or cov.shape != (logw.shape[0], Lz, Lz) or (K is not None and logw.shape[0] != K):
-        raise ValueError(f"a full-covariance mixture is logw [K], mu [K, {Lz}], cov [K, {Lz}, {Lz}]"
+        raise ValueError(f"{kind.what} is (logw, mu, {kind.third})")
+    logw, mu, third = (torch.as_tensor(t).to(dev, torch.float32).contiguous().clone() for t in params)
+    k = logw.shape[0] if logw.dim() == 1 else None
+    if k is None or mu.shape != (k, Lz) or third.shape != kind.third_shape(k, Lz) or (K is not None and k != K):
+        shape = ", ".join(str(n) for n in kind.third_shape("K", Lz))
+        raise ValueError(f"{kind.what} is logw [K], mu [K, {Lz}], {kind.third} [{shape}]"
                          + (f" with K = {K}" if K is not None else "")
-                         + f": got {tuple(logw.shape)}, {tuple(mu.shape)}, {tuple(cov.shape)}")
-    return logw, mu, cov
+                         + f": got {tuple(logw.shape)}, {tuple(mu.shape)}, {tuple(third.shape)}")
+    return logw, mu, third
 
 
-def _assign_full(codes, params, workspace=None):
+def _info(kind, K, dev):
+    """The info_out argument of a kind's assign and run: (the tensor or None, the arguments it adds to the call)."""
+    if not kind.info:
+        return None, ()
+    info = torch.empty(K, dtype=torch.int32, device=dev)
+    return info, (L.ptr(info),)
+
+
+def _assign(kind, codes, params, workspace=None):
     N, Lz = codes.shape
-    logw, mu, cov = _params_full(params, Lz, codes.device)
+    logw, mu, third = _params(kind, params, Lz, codes.device)
     K = logw.shape[0]
-    _check_sizes_full(N, Lz, K)
+    kind.check_sizes(N, Lz, K)
     if workspace is None:
-        workspace = torch.empty(full_workspace_bytes(N, Lz, K), dtype=torch.uint8, device=codes.device)
+        workspace = torch.empty(_workspace_bytes(kind, N, Lz, K), dtype=torch.uint8, device=codes.device)
     log_resp = torch.empty(N, K, dtype=torch.float32, device=codes.device)
     lse = torch.empty(N, dtype=torch.float32, device=codes.device)
-    info = torch.empty(K, dtype=torch.int32, device=codes.device)
-    L.check(L.lib.gmvae_mixfit_full_assign(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(cov), L.ptr(log_resp), L.ptr(lse),
-                                           L.ptr(info), L.ptr(workspace), L.current_stream()), "gmvae_mixfit_full_assign")
-    return {"log_resp": log_resp, "lse": lse, "info": info}
+    info, info_arg = _info(kind, K, codes.device)
+    name = kind.entry + "_assign"
+    L.check(getattr(L.lib, name)(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(third), L.ptr(log_resp), L.ptr(lse), *info_arg,
+                                 L.ptr(workspace), L.current_stream()), name)
+    return {"log_resp": log_resp, "lse": lse, **({"info": info} if kind.info else {})}
 
 
 def assign(codes, params, workspace=None):
@@ -105,20 +120,7 @@ def assign(codes, params, workspace=None):
     `log_resp` [N, K] = ln r_nk and `lse` [N] = ln p(z_n).  A dict with `cov`, or a tuple whose third member is 3-D, is a
     full-covariance mixture (logw, mu, cov [K, L, L]): the dict then also holds `info` [K] (int32), the factorisation's verdict on
     each covariance -- 0, or j + 1 for the first pivot j that is not > 0, and that component's column of `log_resp` is -inf."""
-    codes = _codes(codes)
-    if is_full(params):
-        return _assign_full(codes, params, workspace)
-    N, Lz = codes.shape
-    logw, mu, sigma = _params(params, Lz, codes.device)
-    K = logw.shape[0]
-    _check_sizes(N, Lz, K)
-    if workspace is None:
-        workspace = torch.empty(workspace_bytes(N, Lz, K), dtype=torch.uint8, device=codes.device)
-    log_resp = torch.empty(N, K, dtype=torch.float32, device=codes.device)
-    lse = torch.empty(N, dtype=torch.float32, device=codes.device)
-    L.check(L.lib.gmvae_mixfit_assign(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(sigma), L.ptr(log_resp), L.ptr(lse),
-                                      L.ptr(workspace), L.current_stream()), "gmvae_mixfit_assign")
-    return {"log_resp": log_resp, "lse": lse}
+    return _assign(_FULL if is_full(params) else _DIAG, _codes(codes), params, workspace)
 
 
 def uniforms(K, seed=0, device=None):
@@ -152,32 +154,20 @@ def kmeanspp(codes, K, seed=0):
     return torch.stack(idx)
 
 
-def _run(codes, logw, mu, sigma, reg_covar, n_iter, ws):
-    """n_iter iterations in place; (loglik_history [n_iter], counts [K]).  n_iter = 0: counts = the E-step's R_k at the start."""
+def _run(kind, codes, logw, mu, third, reg_covar, n_iter, ws):
+    """n_iter iterations in place; (loglik_history [n_iter], counts [K], info [K] or None).  n_iter = 0: counts = the E-step's R_k
+    at the start, and info that E-step's."""
     N, Lz = codes.shape
     K = logw.shape[0]
     hist = torch.empty(n_iter, dtype=torch.float32, device=codes.device)
     counts = torch.empty(K, dtype=torch.float32, device=codes.device)
-    L.check(L.lib.gmvae_mixfit_run(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(sigma), float(reg_covar), n_iter,
-                                   L.ptr(hist) if n_iter else None, L.ptr(counts), L.ptr(ws), L.current_stream()), "gmvae_mixfit_run")
+    info, info_arg = _info(kind, K, codes.device)
+    name = kind.entry + "_run"
+    L.check(getattr(L.lib, name)(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(third), float(reg_covar), n_iter,
+                                 L.ptr(hist) if n_iter else None, L.ptr(counts), *info_arg, L.ptr(ws), L.current_stream()), name)
     if n_iter == 0:
-        counts = assign(codes, (logw, mu, sigma), ws)["log_resp"].double().exp().sum(dim=0).float()
-    return hist, counts
-
-
-def _run_full(codes, logw, mu, cov, reg_covar, n_iter, ws):
-    """n_iter iterations in place; (loglik_history [n_iter], counts [K], info [K]).  n_iter = 0: counts and info of the start."""
-    N, Lz = codes.shape
-    K = logw.shape[0]
-    hist = torch.empty(n_iter, dtype=torch.float32, device=codes.device)
-    counts = torch.empty(K, dtype=torch.float32, device=codes.device)
-    info = torch.empty(K, dtype=torch.int32, device=codes.device)
-    L.check(L.lib.gmvae_mixfit_full_run(L.ptr(codes), N, Lz, K, L.ptr(logw), L.ptr(mu), L.ptr(cov), float(reg_covar), n_iter,
-                                        L.ptr(hist) if n_iter else None, L.ptr(counts), L.ptr(info), L.ptr(ws), L.current_stream()),
-            "gmvae_mixfit_full_run")
-    if n_iter == 0:
-        a = _assign_full(codes, (logw, mu, cov), ws)
-        counts, info = a["log_resp"].double().exp().sum(dim=0).float(), a["info"]
+        a = _assign(kind, codes, (logw, mu, third), ws)
+        counts, info = a["log_resp"].double().exp().sum(dim=0).float(), a.get("info")
     return hist, counts, info
 
 
@@ -199,10 +189,9 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None, covar
     K, n_iter, n_init = int(K), int(n_iter), int(n_init)
     if covariance not in COVARIANCES:
         raise ValueError(f"covariance must be one of {COVARIANCES}: got {covariance!r}")
-    full = covariance == "full"
+    kind = _KINDS[covariance]
     _check_sizes(N, Lz, K)
-    if full:
-        _check_sizes_full(N, Lz, K)
+    kind.check_sizes(N, Lz, K)
     if n_iter < 0:
         raise ValueError("n_iter must be >= 0")
     if n_init < 1:
@@ -212,36 +201,28 @@ def fit(codes, K, n_iter=100, n_init=1, reg_covar=1e-6, seed=0, init=None, covar
     if init is not None and n_init != 1:
         raise ValueError("init replaces the seeding: n_init must be 1")
     dev = codes.device
-    ws = torch.empty(full_workspace_bytes(N, Lz, K) if full else workspace_bytes(N, Lz, K), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_workspace_bytes(kind, N, Lz, K), dtype=torch.uint8, device=dev)
     runs = []
     for j in range(n_init):
-        if init is not None and full:
-            if not is_full(init):
+        if init is not None:
+            if kind is _FULL and not is_full(init):
                 raise ValueError("covariance='full' takes init = (logw, mu, cov [K, L, L])")
-            logw, mu, cov = _params_full(init, Lz, dev, K)
-            centres = None
-        elif init is not None:
-            logw, mu, sigma = _params(init, Lz, dev, K)
+            logw, mu, third = _params(kind, init, Lz, dev, K)
             centres = None
         else:
             centres = kmeanspp(codes, K, int(seed) + j)
             mu = codes.index_select(0, centres).contiguous()
-            sd = codes.double().std(dim=0, unbiased=False).clamp_min(math.sqrt(float(reg_covar)))
-            sigma = sd.float().expand(K, Lz).contiguous()
             logw = torch.full((K,), -math.log(K), dtype=torch.float32, device=dev)
-            if full:
+            if kind is _FULL:
                 var = codes.double().var(dim=0, unbiased=False).clamp_min(float(reg_covar))
-                cov = torch.diag(var).float().expand(K, Lz, Lz).contiguous()
-        if full:
-            hist, counts, info = _run_full(codes, logw, mu, cov, reg_covar, n_iter, ws)
-            loglik = _assign_full(codes, (logw, mu, cov), ws)["lse"].double().mean()
-            runs.append({"logw": logw, "mu": mu, "cov": cov, "counts": counts, "loglik": loglik, "loglik_history": hist,
-                         "centres": centres, "info": info})
-            continue
-        hist, counts = _run(codes, logw, mu, sigma, reg_covar, n_iter, ws)
-        loglik = assign(codes, (logw, mu, sigma), ws)["lse"].double().mean()
-        runs.append({"logw": logw, "mu": mu, "sigma": sigma, "counts": counts, "loglik": loglik, "loglik_history": hist,
-                     "centres": centres})
+                third = torch.diag(var).float().expand(K, Lz, Lz).contiguous()
+            else:
+                sd = codes.double().std(dim=0, unbiased=False).clamp_min(math.sqrt(float(reg_covar)))
+                third = sd.float().expand(K, Lz).contiguous()
+        hist, counts, info = _run(kind, codes, logw, mu, third, reg_covar, n_iter, ws)
+        loglik = _assign(kind, codes, (logw, mu, third), ws)["lse"].double().mean()
+        runs.append({"logw": logw, "mu": mu, kind.third: third, "counts": counts, "loglik": loglik, "loglik_history": hist,
+                     "centres": centres, **({"info": info} if kind.info else {})})
     if n_init == 1:
         return runs[0]
     best = torch.stack([r["loglik"] for r in runs]).argmax().view(1)      # (a NaN loglik would win the argmax: it is then reported)
@@ -294,6 +275,6 @@ def checked_fit(fit_dict, K, Lz, dev):
     if is_full(fit_dict):
         raise ValueError("the fitted mixture has full covariances and this model's priors are diagonal: fit with covariance='diag'")
     try:
-        return _params(fit_dict, Lz, dev, K)
+        return _params(_DIAG, fit_dict, Lz, dev, K)
     except ValueError as e:
         raise ValueError(f"the fitted mixture does not match this model's prior (K = {K}, L = {Lz}): {e}") from None

@@ -14,8 +14,9 @@ import pytest
 import torch
 
 import mixfit_ref as R
+import mixfit_util as U
 import oracle as O
-from arena import Arena
+from mixfit_util import DIAG, REG, _L, dev, gate_err, sid
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +24,6 @@ SHAPES = [(1, 1, 1), (67, 5, 3), (403, 16, 4), (1031, 64, 10), (259, 67, 65), (1
 TWO_TILES = (300, 4096, 4)            # csrc/mixfit.hpp mf_plan: 1 row per tile, 150 workgroups of 2 tiles
 ALL_SHAPES = SHAPES + [TWO_TILES]
 REGIMES = ["blob", "offset50", "offset1000", "far", "tight"]
-REG = 1e-6
-sid = lambda s: "x".join(map(str, s))
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def make_case(shape, regime):
@@ -55,30 +49,8 @@ def make_case(shape, regime):
     return z, logw, mu, sigma
 
 
-_REF = {}
-
-
 def reference(shape, regime):
-    """The statement's E-step and M-step of a case, computed once and left unchanged."""
-    if (shape, regime) not in _REF:
-        z, logw, mu, sigma = make_case(shape, regime)
-        l, lse, lr = R.estep(z, logw, mu, sigma)
-        logw2, mu2, sigma2, counts = R.mstep(z, lr, mu, REG)
-        _REF[(shape, regime)] = dict(lse=lse, log_resp=lr, logw=logw2, mu=mu2, sigma=sigma2, counts=counts, hist=lse.mean())
-    return _REF[(shape, regime)]
-
-
-def gate_err(got, ref):
-    """max |got - ref| / max(1, |ref|); where ref is -inf, got must be -inf too."""
-    got, ref = np.atleast_1d(np.asarray(got, np.float64)), np.atleast_1d(np.asarray(ref, np.float64))
-    inf = np.isneginf(ref)
-    if not np.array_equal(np.isneginf(got), inf) or not np.all(np.isfinite(got[~inf])):
-        return math.inf
-    return float((np.abs(got[~inf] - ref[~inf]) / np.maximum(1.0, np.abs(ref[~inf]))).max()) if (~inf).any() else 0.0
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return U.reference(DIAG, make_case, shape, regime)
 
 
 def device_lse_by_mixture_logpdf(z, logw, mu, sigma):
@@ -95,23 +67,6 @@ def device_lse_by_mixture_logpdf(z, logw, mu, sigma):
                                                   L.ptr(ws), L.current_stream()), "accumulate")
     L.check(L.lib.gmvae_mixture_logpdf_finish(N, Lz, 0, 0.0, L.ptr(out), None, None, L.ptr(ws), L.current_stream()), "finish")
     return out.cpu().numpy()
-
-
-def run_once(z, logw, mu, sigma, n_iter=1, ws=None):
-    """gmvae_mixfit_run on copies: (logw, mu, sigma, hist, counts) as arrays."""
-    from gmvae_amd import mixfit
-    L = _L()
-    N, Lz = z.shape
-    K = logw.shape[0]
-    zd, wd, md, sd = dev(z), dev(logw), dev(mu), dev(sigma)
-    hist = torch.empty(n_iter, dtype=torch.float32, device="cuda")
-    counts = torch.empty(K, dtype=torch.float32, device="cuda")
-    if ws is None:
-        ws = torch.empty(mixfit.workspace_bytes(N, Lz, K), dtype=torch.uint8, device="cuda")
-    L.check(L.lib.gmvae_mixfit_run(L.ptr(zd), N, Lz, K, L.ptr(wd), L.ptr(md), L.ptr(sd), REG, n_iter, L.ptr(hist), L.ptr(counts),
-                                   L.ptr(ws), L.current_stream()), "gmvae_mixfit_run")
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in (wd, md, sd, hist, counts))
 
 
 def offset_mu_err(mu_got, ref):
@@ -141,10 +96,9 @@ def test_assign_and_one_iteration_match_the_statement(shape, regime):
     errs = {"lse": gate_err(lse, ref["lse"]), "log_resp": gate_err(lr, ref["log_resp"]),
             "rows_of_r": float(np.abs(np.exp(lr.astype(np.float64)).sum(axis=1) - 1).max()),
             "lse_vs_mixture_logpdf": gate_err(lse, device_lse_by_mixture_logpdf(z, logw, mu, sigma))}
-    logw2, mu2, sigma2, hist, counts = run_once(z, logw, mu, sigma)
-    errs.update(logw=gate_err(logw2, ref["logw"]), mu=gate_err(mu2, ref["mu"]), counts=gate_err(counts, ref["counts"]),
-                hist=gate_err(hist[0], ref["hist"]),
-                sigma=float((np.abs(sigma2 - ref["sigma"]) / ref["sigma"]).max()) if np.isfinite(sigma2).all() else math.inf)
+    got = U.run_once(DIAG, z, logw, mu, sigma)
+    mu2 = got[1]
+    errs.update(U.one_iteration_errs(DIAG, got, ref))
     mu_in_sigma = offset_mu_err(mu2, ref)
     raw = float((np.abs(mu2 - ref["mu"]) / ref["sigma"]).max())
     print(shape, regime, {k: f"{v:.2e}" for k, v in errs.items()}, f"|mu' - ref| / sigma_ref {raw:.2e}, beyond the fp32 output's rounding {mu_in_sigma:.2e}")
@@ -156,87 +110,12 @@ def test_assign_and_one_iteration_match_the_statement(shape, regime):
 
 
 def test_two_runs_give_the_same_bits_on_any_workspace():
-    from gmvae_amd import mixfit
-    for shape, regime in (((1031, 64, 10), "blob"), ((259, 67, 65), "offset50"), (TWO_TILES, "blob")):
-        z, logw, mu, sigma = make_case(shape, regime)
-        a = run_once(z, logw, mu, sigma, n_iter=3)
-        b = run_once(z, logw, mu, sigma, n_iter=3)
-        nan_ws = torch.full((mixfit.workspace_bytes(*[shape[0], shape[1], shape[2]]),), 0xFF, dtype=torch.uint8, device="cuda")
-        c = run_once(z, logw, mu, sigma, n_iter=3, ws=nan_ws)
-        for x, y, w in zip(a, b, c):
-            assert np.array_equal(x, y, equal_nan=True) and np.array_equal(x, w, equal_nan=True), (shape, regime)
-        assert all(np.isfinite(t).all() for t in a[1:])                                     # (logw may hold its -inf no longer, too)
-        o1, o2 = (mixfit.assign(dev(z), (dev(logw), dev(mu), dev(sigma))) for _ in range(2))
-        assert torch.equal(o1["lse"], o2["lse"]) and torch.equal(o1["log_resp"], o2["log_resp"])
+    U.check_same_bits_on_any_workspace(DIAG, make_case, (((1031, 64, 10), "blob"), ((259, 67, 65), "offset50"), (TWO_TILES, "blob")))
 
 
 def test_memory_contract_on_guarded_buffers():
-    """Every call on arena buffers (N = 259, L = 67, K = 65: no size is a multiple of anything): assign changes its two outputs, run
-    the parameters, the history, the counts and the workspace -- nothing else; each optional output may be NULL; n_iter = 0 changes
-    nothing at all."""
-    from gmvae_amd import mixfit
-    L = _L()
-    shape, regime = (259, 67, 65), "blob"
-    N, Lz, K = shape
-    z, logw, mu, sigma = make_case(shape, regime)
-    ref = reference(shape, regime)
-    ar = Arena("cuda", 24 << 20)
-    f32 = torch.float32
-    bufs = {}
-    for name, a, pitch in (("codes", z, Lz * 4), ("logw", logw, 4), ("mu", mu, Lz * 4), ("sigma", sigma, Lz * 4)):
-        bufs[name] = ar.place(name, a.nbytes, pitch, False, f32)
-        bufs[name].copy_(torch.from_numpy(a.reshape(-1)))
-    log_resp = ar.place("log_resp", N * K * 4, K * 4, False, f32)
-    lse = ar.place("lse", N * 4, 4, False, f32)
-    n_iter = 3
-    hist = ar.place("loglik_history", n_iter * 4, 4, False, f32)
-    counts = ar.place("counts", K * 4, 4, False, f32)
-    ws = ar.place("workspace", mixfit.workspace_bytes(N, Lz, K), 16, False, torch.uint8)
-
-    def call_assign(lr, ls):
-        return L.lib.gmvae_mixfit_assign(L.ptr(bufs["codes"]), N, Lz, K, L.ptr(bufs["logw"]), L.ptr(bufs["mu"]), L.ptr(bufs["sigma"]),
-                                         L.ptr(lr), L.ptr(ls), L.ptr(ws), L.current_stream())
-
-    def call_run(n, h, c):
-        return L.lib.gmvae_mixfit_run(L.ptr(bufs["codes"]), N, Lz, K, L.ptr(bufs["logw"]), L.ptr(bufs["mu"]), L.ptr(bufs["sigma"]), REG,
-                                      n, L.ptr(h), L.ptr(c), L.ptr(ws), L.current_stream())
-
-    for names, lr, ls in ((("log_resp", "lse"), log_resp, lse), (("log_resp",), log_resp, None), (("lse",), None, lse), ((), None, None)):
-        for k in ("log_resp", "lse"):
-            ar.set_writable(k, k in names)
-        ar.snapshot()
-        assert call_assign(lr, ls) == 0
-        ar.check()
-    errs = {"lse": gate_err(lse.cpu().numpy(), ref["lse"]), "log_resp": gate_err(log_resp.view(N, K).cpu().numpy(), ref["log_resp"])}
-    print("arena assign", {k: f"{v:.2e}" for k, v in errs.items()})
-    assert max(errs.values()) <= 1e-4
-    for k in ("log_resp", "lse"):
-        ar.set_writable(k, False)
-    # n_iter = 0: nothing changes, the workspace included
-    ar.snapshot()
-    assert call_run(0, hist, counts) == 0
-    ar.check()
-    for k in ("logw", "mu", "sigma", "workspace"):
-        ar.set_writable(k, True)
-    # one iteration with both optional outputs, against the statement
-    ar.set_writable("loglik_history", [(0, 4)])
-    ar.set_writable("counts", True)
-    ar.snapshot()
-    assert call_run(1, hist, counts) == 0
-    ar.check()
-    errs = {"logw": gate_err(bufs["logw"].cpu().numpy(), ref["logw"]), "mu": gate_err(bufs["mu"].view(K, Lz).cpu().numpy(), ref["mu"]),
-            "counts": gate_err(counts.cpu().numpy(), ref["counts"]), "hist": gate_err(hist[:1].cpu().numpy(), ref["hist"]),
-            "sigma": float((np.abs(bufs["sigma"].view(K, Lz).cpu().numpy() - ref["sigma"]) / ref["sigma"]).max())}
-    print("arena run", {k: f"{v:.2e}" for k, v in errs.items()})
-    assert max(errs.values()) <= 1e-4
-    # each optional output NULL in turn
-    for h, c in ((hist, None), (None, counts), (None, None)):
-        ar.set_writable("loglik_history", [(0, n_iter * 4)] if h is not None else False)
-        ar.set_writable("counts", c is not None)
-        ar.snapshot()
-        assert call_run(n_iter, h, c) == 0
-        ar.check()
-    assert all(torch.isfinite(t).all() for t in (bufs["mu"], bufs["sigma"], hist, counts)) and not torch.isnan(bufs["logw"]).any()
+    """N = 259, L = 67, K = 65: no size is a multiple of anything.  The statement of the contract is mixfit_util's."""
+    U.check_memory_contract(DIAG, make_case, (259, 67, 65), 24 << 20)
 
 
 # ------------------------------------------------------------------------------------------------------------ a trajectory

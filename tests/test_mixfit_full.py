@@ -15,7 +15,8 @@ import torch
 
 import mixfit_full_ref as F
 import mixfit_ref as R
-from arena import Arena
+import mixfit_util as U
+from mixfit_util import FULL, REG, cov_err, dev, gate_err, sid
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +24,6 @@ SHAPES = [(1, 1, 1), (67, 5, 3), (403, 16, 4), (1031, 64, 10), (259, 67, 3), (13
 TWO_TILES = (16453, 19, 2)            # csrc/mixfit_full.hpp mff_plan: 64 rows per tile, 258 tiles, 129 workgroups of 2 tiles
 ALL_SHAPES = SHAPES + [TWO_TILES]
 REGIMES = ["blob", "offset50", "far", "tight", "absent"]
-REG = 1e-6
-sid = lambda s: "x".join(map(str, s))
-
-
-def _L():
-    from gmvae_amd import _lib
-    return _lib
 
 
 def spd(rng, K, Lz, lo, hi):
@@ -73,63 +67,12 @@ def make_case(shape, regime):
     return z, logw, mu, cov
 
 
-_REF = {}
-
-
 def reference(shape, regime):
-    """The statement's E-step and M-step of a case, computed once and left unchanged."""
-    if (shape, regime) not in _REF:
-        z, logw, mu, cov = make_case(shape, regime)
-        l, lse, lr, info = F.estep(z, logw, mu, cov)
-        logw2, mu2, cov2, counts = F.mstep(z, lr, mu, REG)
-        with np.errstate(invalid="ignore"):
-            _REF[(shape, regime)] = dict(lse=lse, log_resp=lr, info=info, logw=logw2, mu=mu2, cov=cov2, counts=counts, hist=lse.mean())
-    return _REF[(shape, regime)]
+    return U.reference(FULL, make_case, shape, regime)
 
 
-def gate_err(got, ref):
-    """max |got - ref| / max(1, |ref|); where ref is -inf, got must be -inf too."""
-    got, ref = np.atleast_1d(np.asarray(got, np.float64)), np.atleast_1d(np.asarray(ref, np.float64))
-    inf = np.isneginf(ref)
-    if not np.array_equal(np.isneginf(got), inf) or not np.all(np.isfinite(got[~inf])):
-        return math.inf
-    return float((np.abs(got[~inf] - ref[~inf]) / np.maximum(1.0, np.abs(ref[~inf]))).max()) if (~inf).any() else 0.0
-
-
-def cov_err(got, ref):
-    """max over components of max_de |got - ref| / max_de |ref_k|: the gate on cov' is 1e-4 of each component's largest entry."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    if not np.isfinite(got).all():
-        return math.inf
-    return float((np.abs(got - ref).max(axis=(1, 2)) / np.abs(ref).max(axis=(1, 2))).max())
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def run_once(z, logw, mu, cov, n_iter=1, ws=None):
-    """gmvae_mixfit_full_run on copies: (logw, mu, cov, hist, counts, info) as arrays."""
-    from gmvae_amd import mixfit
-    L = _L()
-    N, Lz = z.shape
-    K = logw.shape[0]
-    zd, wd, md, cd = dev(z), dev(logw), dev(mu), dev(cov)
-    hist = torch.empty(n_iter, dtype=torch.float32, device="cuda")
-    counts = torch.empty(K, dtype=torch.float32, device="cuda")
-    info = torch.full((K,), -7, dtype=torch.int32, device="cuda")        # (the caller initialises nothing)
-    if ws is None:
-        ws = torch.empty(mixfit.full_workspace_bytes(N, Lz, K), dtype=torch.uint8, device="cuda")
-    L.check(L.lib.gmvae_mixfit_full_run(L.ptr(zd), N, Lz, K, L.ptr(wd), L.ptr(md), L.ptr(cd), REG, n_iter, L.ptr(hist), L.ptr(counts),
-                                        L.ptr(info), L.ptr(ws), L.current_stream()), "gmvae_mixfit_full_run")
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in (wd, md, cd, hist, counts, info))
-
-
-def one_iteration_errs(got, ref):
-    logw2, mu2, cov2, hist, counts, info = got
-    return dict(logw=gate_err(logw2, ref["logw"]), mu=gate_err(mu2, ref["mu"]), counts=gate_err(counts, ref["counts"]),
-                hist=gate_err(hist[0], ref["hist"]), cov=cov_err(cov2, ref["cov"]))
+def run_once(z, logw, mu, cov, n_iter=1):
+    return U.run_once(FULL, z, logw, mu, cov, n_iter)
 
 
 CASES = [(s, r) for s in ALL_SHAPES for r in REGIMES]
@@ -151,7 +94,7 @@ def test_assign_and_one_iteration_match_the_statement(shape, regime):
     errs = {"lse": gate_err(lse, ref["lse"]), "log_resp": gate_err(lr, ref["log_resp"]),
             "rows_of_r": float(np.abs(np.exp(lr[live].astype(np.float64)).sum(axis=1) - 1).max()) if live.any() else 0.0}
     got = run_once(z, logw, mu, cov)
-    errs.update(one_iteration_errs(got, ref))
+    errs.update(U.one_iteration_errs(FULL, got, ref))
     print(shape, regime, {k: f"{v:.2e}" for k, v in errs.items()}, "info", info[:4].tolist())
     rows_of_r = errs.pop("rows_of_r")
     assert info.dtype == np.int32 and np.array_equal(info, want_info) and np.array_equal(got[5], want_info)
@@ -175,91 +118,12 @@ def test_assign_and_one_iteration_match_the_statement(shape, regime):
 
 
 def test_two_runs_give_the_same_bits_on_any_workspace():
-    from gmvae_amd import mixfit
-    for shape, regime in (((1031, 64, 10), "blob"), ((259, 67, 3), "offset50"), (TWO_TILES, "blob")):
-        z, logw, mu, cov = make_case(shape, regime)
-        a = run_once(z, logw, mu, cov, n_iter=3)
-        b = run_once(z, logw, mu, cov, n_iter=3)
-        ff_ws = torch.full((mixfit.full_workspace_bytes(*shape),), 0xFF, dtype=torch.uint8, device="cuda")
-        c = run_once(z, logw, mu, cov, n_iter=3, ws=ff_ws)
-        for x, y, w in zip(a, b, c):
-            assert np.array_equal(x, y, equal_nan=True) and np.array_equal(x, w, equal_nan=True), (shape, regime)
-        assert all(np.isfinite(t).all() for t in a[1:5]) and not a[5].any()
-        o1, o2 = (mixfit.assign(dev(z), (dev(logw), dev(mu), dev(cov))) for _ in range(2))
-        assert all(torch.equal(o1[k], o2[k]) for k in ("lse", "log_resp", "info"))
+    U.check_same_bits_on_any_workspace(FULL, make_case, (((1031, 64, 10), "blob"), ((259, 67, 3), "offset50"), (TWO_TILES, "blob")))
 
 
 def test_memory_contract_on_guarded_buffers():
-    """Every call on arena buffers (N = 259, L = 67, K = 3): assign changes its non-NULL outputs and the workspace, run the
-    parameters, its non-NULL outputs and the workspace -- nothing else; each optional output may be NULL; n_iter = 0 changes nothing
-    at all."""
-    from gmvae_amd import mixfit
-    L = _L()
-    shape, regime = (259, 67, 3), "blob"
-    N, Lz, K = shape
-    z, logw, mu, cov = make_case(shape, regime)
-    ref = reference(shape, regime)
-    ar = Arena("cuda", 8 << 20)
-    f32 = torch.float32
-    bufs = {}
-    for name, a, pitch in (("codes", z, Lz * 4), ("logw", logw, 4), ("mu", mu, Lz * 4), ("cov", cov, Lz * 4)):
-        bufs[name] = ar.place(name, a.nbytes, pitch, False, f32)
-        bufs[name].copy_(torch.from_numpy(a.reshape(-1)))
-    log_resp = ar.place("log_resp", N * K * 4, K * 4, False, f32)
-    lse = ar.place("lse", N * 4, 4, False, f32)
-    info = ar.place("info", K * 4, 4, False, torch.int32)
-    n_iter = 3
-    hist = ar.place("loglik_history", n_iter * 4, 4, False, f32)
-    counts = ar.place("counts", K * 4, 4, False, f32)
-    ws = ar.place("workspace", mixfit.full_workspace_bytes(N, Lz, K), 16, True, torch.uint8)
-
-    def call_assign(lr, ls, inf):
-        return L.lib.gmvae_mixfit_full_assign(L.ptr(bufs["codes"]), N, Lz, K, L.ptr(bufs["logw"]), L.ptr(bufs["mu"]), L.ptr(bufs["cov"]),
-                                              L.ptr(lr), L.ptr(ls), L.ptr(inf), L.ptr(ws), L.current_stream())
-
-    def call_run(n, h, c, inf):
-        return L.lib.gmvae_mixfit_full_run(L.ptr(bufs["codes"]), N, Lz, K, L.ptr(bufs["logw"]), L.ptr(bufs["mu"]), L.ptr(bufs["cov"]), REG,
-                                           n, L.ptr(h), L.ptr(c), L.ptr(inf), L.ptr(ws), L.current_stream())
-
-    outs = {"log_resp": log_resp, "lse": lse, "info": info}
-    for names in (("log_resp", "lse", "info"), ("lse", "info"), ("log_resp", "info"), ("log_resp", "lse"), ()):
-        for k in outs:
-            ar.set_writable(k, k in names)
-        ar.snapshot()
-        assert call_assign(*(outs[k] if k in names else None for k in ("log_resp", "lse", "info"))) == 0
-        ar.check()
-    errs = {"lse": gate_err(lse.cpu().numpy(), ref["lse"]), "log_resp": gate_err(log_resp.view(N, K).cpu().numpy(), ref["log_resp"])}
-    print("arena assign", {k: f"{v:.2e}" for k, v in errs.items()}, info.tolist())
-    assert max(errs.values()) <= 1e-4 and info.tolist() == [0] * K
-    for k in outs:
-        ar.set_writable(k, False)
-    # n_iter = 0: nothing changes, the workspace included
-    ar.set_writable("workspace", False)
-    ar.snapshot()
-    assert call_run(0, hist, counts, info) == 0
-    ar.check()
-    for k in ("logw", "mu", "cov", "workspace"):
-        ar.set_writable(k, True)
-    # one iteration with every optional output, against the statement
-    ar.set_writable("loglik_history", [(0, 4)])
-    ar.set_writable("counts", True)
-    ar.set_writable("info", True)
-    ar.snapshot()
-    assert call_run(1, hist, counts, info) == 0
-    ar.check()
-    got = tuple(t.cpu().numpy() for t in (bufs["logw"], bufs["mu"].view(K, Lz), bufs["cov"].view(K, Lz, Lz), hist[:1], counts, info))
-    errs = one_iteration_errs(got, ref)
-    print("arena run", {k: f"{v:.2e}" for k, v in errs.items()})
-    assert max(errs.values()) <= 1e-4 and info.tolist() == [0] * K
-    # each optional output NULL in turn
-    for h, c, inf in ((None, counts, info), (hist, None, info), (hist, counts, None), (None, None, None)):
-        ar.set_writable("loglik_history", [(0, n_iter * 4)] if h is not None else False)
-        ar.set_writable("counts", c is not None)
-        ar.set_writable("info", inf is not None)
-        ar.snapshot()
-        assert call_run(n_iter, h, c, inf) == 0
-        ar.check()
-    assert all(torch.isfinite(t).all() for t in (bufs["logw"], bufs["mu"], bufs["cov"], hist, counts))
+    """N = 259, L = 67, K = 3.  The statement of the contract is mixfit_util's."""
+    U.check_memory_contract(FULL, make_case, (259, 67, 3), 8 << 20)
 
 
 # ------------------------------------------------------------------------------------------------------------ a trajectory
