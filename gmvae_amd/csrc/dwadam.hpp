@@ -19,6 +19,7 @@
 #pragma once
 #include <type_traits>
 
+#include "bf16x3.hpp"
 #include "chain.hpp"
 
 namespace gmvae {
@@ -181,9 +182,7 @@ __device__ __forceinline__ void dw_contract(const void* __restrict__ Ap, const f
 // register-direct loads of the fp32 form already hold (k-step s = 8 blk + j of lane group h).  Per block of 8 k-steps a
 // lane repacks: A tile t = bf16(byte t of its 8 packed words) (v_cvt_f32_ubyte + v_perm), B = the three pieces of its 8
 // dY values (and / sub / perm): ~100 VALU instructions beside 12 MFMAs.
-__device__ __forceinline__ unsigned pack_hi16(const float f1, const float f0) {     // (bf16 bits of f0) | (bf16 bits of f1) << 16, truncating
-  return __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
-}
+// (pack_hi16 and the split into pieces, split3_bf16: bf16x3.hpp)
 __device__ __forceinline__ void dw_contract_u8x3(const unsigned char* __restrict__ A8, const float* __restrict__ dY, const int lda,
                                                  const int ldy, const int M, const int N, const int m0, const int n0, const int b_lo,
                                                  const int ln, const int lk, f32x4 (&acc)[4], float& cs) {
@@ -209,11 +208,9 @@ __device__ __forceinline__ void dw_contract_u8x3(const unsigned char* __restrict
     for (int jp = 0; jp < 4; ++jp) {
       const float v0 = n_ok ? bvv[8 * blk + 2 * jp] : 0.f, v1 = n_ok ? bvv[8 * blk + 2 * jp + 1] : 0.f;
       cs += v0; cs += v1;
-      bh[jp] = pack_hi16(v1, v0);
-      const float r0 = v0 - __uint_as_float(__float_as_uint(v0) & 0xffff0000u), r1 = v1 - __uint_as_float(__float_as_uint(v1) & 0xffff0000u);
-      bm[jp] = pack_hi16(r1, r0);
-      const float s0 = r0 - __uint_as_float(__float_as_uint(r0) & 0xffff0000u), s1 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-      bl[jp] = pack_hi16(s1, s0);
+      unsigned ph, pm, pl;
+      split3_bf16(v0, v1, ph, pm, pl);
+      bh[jp] = ph; bm[jp] = pm; bl[jp] = pl;
     }
     const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh), Bm = __builtin_bit_cast(bf16x8, bm), Bl = __builtin_bit_cast(bf16x8, bl);
 #pragma unroll
@@ -261,11 +258,9 @@ __device__ __forceinline__ void dw_u8x3_rest(const unsigned (&av)[32], const flo
     for (int jp = 0; jp < 4; ++jp) {
       const float v0 = n_ok ? bvv[8 * blk + 2 * jp] : 0.f, v1 = n_ok ? bvv[8 * blk + 2 * jp + 1] : 0.f;
       cs += v0; cs += v1;
-      bh[jp] = pack_hi16(v1, v0);
-      const float r0 = v0 - __uint_as_float(__float_as_uint(v0) & 0xffff0000u), r1 = v1 - __uint_as_float(__float_as_uint(v1) & 0xffff0000u);
-      bm[jp] = pack_hi16(r1, r0);
-      const float s0 = r0 - __uint_as_float(__float_as_uint(r0) & 0xffff0000u), s1 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-      bl[jp] = pack_hi16(s1, s0);
+      unsigned ph, pm, pl;
+      split3_bf16(v0, v1, ph, pm, pl);
+      bh[jp] = ph; bm[jp] = pm; bl[jp] = pl;
     }
     const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh), Bm = __builtin_bit_cast(bf16x8, bm), Bl = __builtin_bit_cast(bf16x8, bl);
 #pragma unroll

@@ -21,8 +21,14 @@
 // split over the EIGHT workgroups of two neighbouring panels: workgroup (panel 2s + h, quarter q) multiplies the 32 rows of
 // both panels by rows [196 q, 196 q + 196) of ONE of the two first-layer weight tensors (h = 0: encoder_y's, 1: encoder_gmm's
 // x rows) -- 50 KB of weights per workgroup instead of 100 (its wait for them was 6.3 k of the stage's 17 k cycles) for the
-// same 392 matrix instructions and the same exchange (2048 granules out, 16 per lane in).
+// same exchange (2048 granules out, 16 per lane in).  That product runs on the bf16 matrix cores, EXACTLY (bf16x3.hpp): the batch
+// bytes are exact in bf16 and each fp32 weight is split into hi + mid + lo bf16 pieces, so every product is exact and the fp32
+// accumulation is the only rounding -- 7 blocks of 32 contraction steps x 3 v_mfma_f32_16x16x32_bf16 (16 cycles) per row tile
+// instead of 49 v_mfma_f32_16x16x4_f32 (32 cycles): 672 instead of 3136 matrix cycles per SIMD.  A wave owns one 16-column tile
+// for both row tiles and one part of the contraction, so each weight is split once per workgroup (fl_block below).  (For |w|
+// below about 2^-102 the lo piece is a subnormal bf16 and may be flushed: at most 2^-126 x 255 per product.)
 #pragma once
+#include "bf16x3.hpp"
 #include "mega.hpp"
 
 namespace gmvae {
@@ -81,12 +87,19 @@ struct M2 {
   static constexpr int P_dl = P_dhg + 16 * ld64;  // [16][20]
   static_assert(P_dl + 16 * ldk <= P_dhd, "backward panels must fit the dred region");
   static_assert(total * 4 <= 160 * 1024, "LDS budget");
-  // the in-launch first layer's staging ([196][64] weights + [32][226] x image) lies BEHIND the forward operand image (over
-  // the panels, which nothing uses yet): the image's DMA is then issued at the kernel's start, beside the weight bursts,
-  // instead of after the exchange's publish -- where its 66 KB sat in front of every wave's polls (vmcnt retires in order:
-  // the exchange took 2.4 us, the time of that DMA, for a hand-off whose latency is ~1 us)
+  // the in-launch first layer's staging ([196][64] fp32 weights + the pair's 32 batch rows as bf16 + the contraction halves'
+  // partial tiles) lies BEHIND the forward operand image (over the panels, which nothing uses yet): the image's DMA is then issued
+  // at the kernel's start, beside the weight bursts, instead of after the exchange's publish -- where its 66 KB sat in front of
+  // every wave's polls (vmcnt retires in order: the exchange took 2.4 us, the time of that DMA, for a hand-off whose latency is ~1 us)
   static constexpr int fl_kq = 196, fl_W = imgF, fl_A = fl_W + fl_kq * 64;
-  static_assert(fl_A + 32 * kFlLda <= total, "first-layer staging must fit");
+  // x image: [32][fl_lda] dwords = 232 bf16 per row, 7 blocks of 32 contraction steps (columns >= 196 are never written: their
+  // operands are zeroed in registers).  464 bytes = 29 sixteen-byte slots: odd, so the 16 rows of a ds_read_b128 lane group
+  // fall on 16 slots with at most one pair sharing one
+  static constexpr int fl_lda = 116;
+  static constexpr int fl_X = fl_A + 32 * fl_lda;               // [8 waves][64 lanes][4]: a wave's partial tile for its partner
+  static constexpr int fl_end = fl_X + 8 * 64 * 4;
+  static_assert(fl_kq <= 7 * 32 && 7 * 32 / 2 + 4 <= fl_lda && (fl_lda * 4) % 16 == 0 && (fl_A * 4) % 16 == 0, "x image rows: 16-byte operand reads");
+  static_assert(fl_end <= total, "first-layer staging must fit");
   static constexpr int imgF_pieces = (imgF + 2047) / 2048;      // 1 KB LDS-DMA pieces per wave (the last ones clamped: uniform counts)
 };
 
@@ -161,6 +174,45 @@ __device__ __forceinline__ void st1o(float* p, const float v) {
   __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One block of 32 contraction steps of the in-launch first layer on exact bf16 piece products (bf16x3.hpp): rows = the pair's 32
+// batch rows (two row tiles), columns = this wave's 16 of the weight tensor.  Contraction step (lane group lk, element j) of the
+// block is weight row k = 32 BLK + 8 lk + j of the quarter: the A operand is ONE 16-byte read of the bf16 x image (Ar: row ln of
+// row tile 0 at this lane group's 8 steps of block 0), the B operand 8 values of the fp32 weight staging (We / Wo: this lane's
+// column in the even / odd rows -- the LDS-DMA's swizzle --, lkoff = 8 lk rows) split into hi + mid + lo ONCE for both row tiles.
+// Block 6 holds steps 192..223 of which 192..195 exist: the others get zero operands on BOTH sides and a clamped weight address
+// (lane group 0's rows; the x image's columns >= 196 were never written).  Smallest pieces first, as in the weight-gradient tiles.
+// (Measured, tools/flstamps.py: a block is bound by the SIMD's vector issue -- ~55 vector instructions at ~4 cycles plus the 8
+// cycles each MFMA holds it, two waves per SIMD.  The blocks as a run-time loop, or with every LDS read of a wave hoisted in
+// front of its first split, were both slower than this straight-line form.)
+template <int BLK>
+__device__ __forceinline__ void fl_block(const float* __restrict__ We, const float* __restrict__ Wo, const int lkoff,
+                                         const unsigned* __restrict__ Ar, const int lk, f32x4 (&acc)[2]) {
+  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+  static_assert(BLK >= 0 && BLK < 7 && M2::fl_kq == 6 * 32 + 4, "7 blocks, the last one of 4 steps");
+  constexpr bool last = BLK == 6;
+  const bool live = !last || lk == 0;
+  const float* const pe = We + (last ? 0 : lkoff) + 32 * BLK * 64;
+  const float* const po = Wo + (last ? 0 : lkoff) + 32 * BLK * 64;
+  u32x4_t bh = {0u, 0u, 0u, 0u}, bm = {0u, 0u, 0u, 0u}, bl = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int jp = 0; jp < (last ? 2 : 4); ++jp) {
+    const float w0 = pe[2 * jp * 64], w1 = po[(2 * jp + 1) * 64];
+    unsigned ph, pm, pl;
+    split3_bf16(live ? w0 : 0.f, live ? w1 : 0.f, ph, pm, pl);
+    bh[jp] = ph; bm[jp] = pm; bl[jp] = pl;
+  }
+  const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh), Bm = __builtin_bit_cast(bf16x8, bm), Bl = __builtin_bit_cast(bf16x8, bl);
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) {
+    u32x4_t aw = *reinterpret_cast<const u32x4_t*>(Ar + rt * kPanel * M2::fl_lda + 16 * BLK);
+    if (last) { aw[0] = live ? aw[0] : 0u; aw[1] = live ? aw[1] : 0u; aw[2] = 0u; aw[3] = 0u; }
+    const bf16x8 At = __builtin_bit_cast(bf16x8, aw);
+    acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(At, Bl, acc[rt], 0, 0, 0);
+    acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(At, Bm, acc[rt], 0, 0, 0);
+    acc[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(At, Bh, acc[rt], 0, 0, 0);
+  }
+}
+
 // The launch's body.  FUSE = 0: the whole of mega2_fwd_bwd (below).  FUSE = 1: the per-row part of mega3_step (mega3.hpp), whose
 // workgroups go on to the weight-gradient tiles: the body then leaves alpha_t and the closing span stamp to the caller.  Returns
 // what the workgroup was: 0 a phantom panel's (its share of the pair's first layer is out), 1 a producer (partials published),
@@ -231,7 +283,8 @@ __device__ __forceinline__ int mega2_body(M2_BODY_PARAMS, const MegaArgs& a, flo
   {
     constexpr int KQ = M2::fl_kq, kq4 = KQ / 4;
     float* const Wst = sm + M2::fl_W;
-    float* const A_x = sm + M2::fl_A;
+    unsigned* const A_x = reinterpret_cast<unsigned*>(sm + M2::fl_A);
+    float* const X_h = sm + M2::fl_X;
     const int k0 = q * KQ;
     const int sp = pnl >> 1, hh = pnl & 1;         // the pair of panels; this workgroup's weight tensor (and its own row tile)
     const int rs0 = sp * 2 * kPanel;               // first of the pair's 32 rows
@@ -240,7 +293,7 @@ __device__ __forceinline__ int mega2_body(M2_BODY_PARAMS, const MegaArgs& a, flo
     const unsigned long long step = step_;
     constexpr int qer = L / 4, qur = (K + 3) / 4, qe = kPanel * qer, qu = kPanel * qur;
     float nz[4] = {0.f, 0.f, 0.f, 0.f};
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     unsigned xw[4];
     const int row_ = lane >> 4, piece = lane & 15;
     const int src = row_ * 64 + ((piece ^ ((row_ & 1) << 2)) << 2);
@@ -276,32 +329,60 @@ __device__ __forceinline__ int mega2_body(M2_BODY_PARAMS, const MegaArgs& a, flo
       const int row = li / qpr, quad = li - row * qpr;
       noise_vals(a.row0 + (unsigned long long)(r0 + row), (unsigned)quad, is_u, a.seed, step, nz);
     }
+    // Counted waits: a wave has issued, in this order, 3 weight bursts (first half), 4 x loads, 4 weight bursts (second half) and
+    // M2::imgF_pieces = 9 image pieces: 20 vector-memory operations, which retire in order.
     static_assert(M2::imgF_pieces == 9, "the counted waits below assume 9 image pieces per wave");
-    asm volatile("s_waitcnt vmcnt(13)" ::: "memory");                     // the first half and the x bytes are in
+    asm volatile("s_waitcnt vmcnt(13)" ::: "memory");                     // 20 - 13: the oldest 7 -- the first half's bursts and the x bytes -- are in
     M2_FC(1);
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
+    for (int it = 0; it < 4; ++it) {               // the bytes as bf16 (exact): 4 per dword, one 8-byte LDS store
       const int i = tid + it * kMT;
       if (i < 2 * kPanel * kq4) {
-        const int row = i / kq4, k4 = (i - row * kq4) * 4;
+        const int row = i / kq4, c = i - row * kq4;
         const unsigned w = xw[it];
-        float2* const dst = reinterpret_cast<float2*>(A_x + row * kFlLda + k4);
-        dst[0] = make_float2((float)(w & 0xff), (float)((w >> 8) & 0xff));
-        dst[1] = make_float2((float)((w >> 16) & 0xff), (float)(w >> 24));
+        *reinterpret_cast<uint2*>(A_x + row * M2::fl_lda + 2 * c) =
+            make_uint2(pack_hi16((float)((w >> 8) & 0xff), (float)(w & 0xff)), pack_hi16((float)(w >> 24), (float)((w >> 16) & 0xff)));
       }
     }
     __syncthreads();
     M2_FC(2);
-    const int tl = wave & 3, rt = wave >> 2;        // this wave's 16 columns of the tensor, its row tile (= panel of the pair)
-    const int swz = ((tl * 16 + ln) ^ ((lk & 1) << 4)) - (tl * 16 + ln);
-    const float* const Wt = Wst + swz;
-    const float* const At = A_x + rt * kPanel * kFlLda;
-    acc = tile_ksteps<1, kFlLda>(At, Wt, H, 1, tl, 0, 24, 24, lane, acc);
+    // Wave map: a wave owns ONE column tile (tl) for BOTH row tiles and one part of the contraction (kh), so every weight value is
+    // split into pieces once per workgroup.  The seven blocks of 32 steps: kh = 0 takes blocks 0, 1 | 3, 4, kh = 1 blocks 2 | 5, 6
+    // (before | behind the second half's wait: blocks 0..2 are the first half's 96 weight rows; block 6 is the 4-step one).
+    // Waves w and w + 4 share a SIMD: both parts run side by side on each.
+    const int tl = wave & 3, kh = wave >> 2;
+    const int col = tl * 16 + ln, lkoff = 8 * lk * H;
+    const float* const We = Wst + col;              // even weight rows; odd rows: the LDS-DMA's swizzle puts the column at col ^ 16
+    const float* const Wo = Wst + (col ^ 16);
+    const unsigned* const Ar = A_x + ln * M2::fl_lda + 4 * lk;
+    if (kh == 0) {
+      fl_block<0>(We, Wo, lkoff, Ar, lk, acc2);
+      fl_block<1>(We, Wo, lkoff, Ar, lk, acc2);
+    } else {
+      fl_block<2>(We, Wo, lkoff, Ar, lk, acc2);
+    }
     M2_FC(3);
-    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");                      // the second half (the image may still be landing)
+    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");                      // 20 - 9: the oldest 11 -- the second half's bursts too (the image may still be landing)
     __syncthreads();
     M2_FC(4);
-    acc = tile_ksteps<1, kFlLda>(At, Wt, H, 1, tl, 24, 49, 49, lane, acc);
+    if (kh == 0) {
+      fl_block<3>(We, Wo, lkoff, Ar, lk, acc2);
+      fl_block<4>(We, Wo, lkoff, Ar, lk, acc2);
+    } else {
+      fl_block<5>(We, Wo, lkoff, Ar, lk, acc2);
+      fl_block<6>(We, Wo, lkoff, Ar, lk, acc2);
+    }
+    // the two parts meet: wave (tl, kh) publishes the tile (column tile tl, row tile kh) -- the granules' place is that of the
+    // one-tile-per-wave map -- and hands the other row tile's partial to its partner (tl, 1 - kh).  The sum's order is fixed:
+    // (blocks 0, 1, 3, 4) + (blocks 2, 5, 6).
+    st4(X_h + (wave * 64 + lane) * 4, f4(kh ? acc2[0] : acc2[1]));
+    __syncthreads();
+    f32x4 acc;
+    {
+      const float4 o = ld4(X_h + ((wave ^ 4) * 64 + lane) * 4);
+      const f32x4 other = {o.x, o.y, o.z, o.w}, mine = kh ? acc2[1] : acc2[0];
+      acc = (kh ? other : mine) + (kh ? mine : other);
+    }
     constexpr int ngr = 2 * kPanel * H;            // granules one workgroup publishes: [32 rows][64 columns]
     {
       unsigned long long* xo = a.xfl + (((long long)sp * 4 + q) * 2 + hh) * ngr;

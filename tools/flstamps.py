@@ -17,7 +17,8 @@ torch.cuda.synchronize()
 d, ws = e._workspace(B)
 off = C.c_uint64(); L.check(L.lib.gmvae_workspace_offset(C.byref(d), e.model, b"stamps", C.byref(off)), "off")
 raw = ws.view(torch.int64)[off.value // 8: off.value // 8 + nP * 4 * 16].cpu().numpy().reshape(nP * 4, 16).astype(np.float64)
-names = ["loads issued", "first half + x landed", "x image + sync", "MFMA 1", "second half landed + sync", "MFMA 2 + publish",
+names = ["loads issued", "first half + x landed", "x image (bf16) + sync", "blocks before the second half (split + MFMA)",
+         "second half landed + sync", "blocks behind it + halves' exchange + publish",
          "exchange polls done", "decoder operands issued, image waited, sync", "bias + ReLU + sync (stage end)"]
 cols = [8, 9, 10, 11, 12, 13, 14, 15, 1]
 prev = raw[:, 0]
