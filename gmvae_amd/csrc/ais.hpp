@@ -29,6 +29,9 @@
 // transitions t_lo .. t_hi; t = 0 is the start (component by inverse CDF, z_0 = mu_k + sigma_k eps) and shares the one evaluation
 // call site.
 // LDS at the largest admitted sizes (3 x 512 hidden, L = 128, K = 64): 150,016 bytes of the 160 KiB (ais_lds).
+// The chain's state is fp32: a base whose sigma_kl lies below an ulp of mu_kl (6e-8 |mu|) is not resolved -- z_0 = fl(mu + sigma eps)
+// is then mu itself and log r(z_0) is off by eps^2 / 2 per such dimension.  Trained encoders stay four orders above that; a
+// diverged one (sigma = 2e-9) does not, and tests/test_inference_saturated.py holds such a case to the statement of an fp32 start.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

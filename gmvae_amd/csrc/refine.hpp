@@ -7,7 +7,10 @@
 //   Step t < n_steps, S samples eps_s:  z_s = m + e^s eps_s;  L-hat = 1/S sum_s log p(x, z_s) + sum_l s_l + L/2 (1 + ln 2 pi);
 //     dm = 1/S sum_s g_s;  ds = 1/S sum_s g_s e^s eps_s + 1;  one ASCENT step of TF-Adam (adam.hpp adam_update on -d) on the 2 L
 //     parameters with the example's own count t_b; a gradient that is not finite skips the update (moments and t_b untouched, as
-//     gclip.hpp does for the training step); s clamped to [-20, 5] after the update.
+//     gclip.hpp does for the training step), and so does one with an element of kRefineGMax = 2^63.5 = 1.3e19 or more in
+//     magnitude: adam_update squares the element in fp32, 2^64 squared is past fp32's largest number, and a second moment of inf
+//     would freeze that element for every later step while the rest of the example moved on (a prior sigma of 2e-9 gives
+//     2.5e17 per unit distance: such gradients are finite and reachable); s clamped to [-20, 5] after the update.
 //   Round t >= n_steps: S fresh eps, log w = log p(x, z) - log q_phi(z) at phi* and at phi_0 on the SAME eps: two evaluations.
 // One workgroup of 256 threads owns a panel of kAisRows = 16 rows for every step of the launch; a row is one Monte-Carlo sample, an
 // example's S samples (S in {1, 2, 4, 8, 16}) lie in one panel, which holds 16 / S examples; rows past the end repeat the last
@@ -31,6 +34,7 @@
 namespace gmvae {
 
 constexpr float kRefineSMin = -20.f, kRefineSMax = 5.f;
+constexpr float kRefineGMax = 0x1.6a09e6p+63f;      // 2^63.5 rounded to fp32: its square, 2^127, is the last binade fp32 has
 
 struct RefineArgs {
   AisArgs a;                     // the evaluation's: enc = 0, C = S, n = B S, T = n_steps + n_rounds (ais_noise's key)
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(kAisThreads, 2) void refine_run(const RefineArgs ra
             ds += g * sg * (double)pb[i * s.ldz + l];
           }
           const float fm = (float)(dm / (double)S), fs = (float)(ds / (double)S + 1.0);
-          if (!(fabsf(fm) < INFINITY) || !(fabsf(fs) < INFINITY)) bad = 1.0;
+          if (!(fabsf(fm) < kRefineGMax) || !(fabsf(fs) < kRefineGMax)) bad = 1.0;      // (a NaN compares false: skipped)
           gAb[l] = fm;
           gBb[l] = fs;
         }

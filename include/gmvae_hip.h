@@ -816,8 +816,9 @@ int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* p
  *   Step t = 1 .. n_steps, n_samples = S draws eps_s: z_s = m + e^s eps_s, g_s = grad_z log p(x, z_s);
  *     L-hat_t = 1/S sum_s log p(x, z_s) + sum_l s_l + L/2 (1 + ln 2 pi);  dm = 1/S sum_s g_s;  ds = 1/S sum_s g_s e^s eps_s + 1;
  *     then one ASCENT step of adam_tf_step's update on the 2 L parameters (lr, beta1, beta2, adam_eps, the example's own count;
- *     alpha_t from fp64 pow), and s clamped to [-20, 5].  An example whose gradient is not finite skips that update: moments and
- *     count untouched.
+ *     alpha_t from fp64 pow), and s clamped to [-20, 5].  An example whose gradient is not finite, or has an element of 2^63.5
+ *     (1.3e19) or more in magnitude -- its square is at the edge of fp32, and the update's second moment would become inf --,
+ *     skips that update: moments and count untouched.
  *   Evaluation: n_eval_rounds rounds of S fresh draws, N = n_eval_rounds S; log w = log p(x, z) - log q_phi(z) at phi* and at phi_0
  *     on the SAME eps; the ELBO = mean log w, the importance-weighted bound = logsumexp log w - ln N, sums in fp64.
  *   Noise: row (b, s) is Philox row (dims->row0 + b) S + s, and its draw at t (steps 0 .. n_steps - 1, then the rounds) is what

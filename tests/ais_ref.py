@@ -12,7 +12,9 @@ by inverse CDF, z_0 = mu_k + sigma_k eps), t >= 1 the transition at beta_t (eps 
 
 ais() also reports, per chain, whether an fp32 evaluation can be held to its accept sequence: a chain is DECIDED if every
 |ln u - dH| exceeds 1e-4 (|H_old| + |H_new|) + 1e-6, every ReLU pre-activation along its path exceeds 1e-5 in magnitude, and the
-component pick is not within 1e-6 of a CDF edge."""
+component pick is not within 1e-6 of a CDF edge.  Two keyword paths serve the cases outside the Xavier regime
+(tests/inference_saturated_cases.py): nonfinite_is_decided, and jitter_seed with well_conditioned() -- a conditioning measure from
+the statement alone, for where the fixed margins above say nothing."""
 import math
 
 import numpy as np
@@ -144,9 +146,30 @@ class Target:
         return mu[rows, k] + sg[rows, k] * eps, edge
 
 
-def ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init="prior", step_up=1.02, step_down=0.96, base=None):
+def ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init="prior", step_up=1.02, step_down=0.96, base=None,
+        nonfinite_is_decided=False, jitter_seed=None, z0_fp32=False):
     """The chains of every example of x.  Returns dict(logw [B, C], bound [B], stats [B, 4], z [B C, L], tail [8],
-    accepts [T, B C] bool, decided [B C] bool, steps [B C])."""
+    accepts [T, B C] bool, decided [B C] bool, steps [B C], h_new [T, B C], z0 [B C, L], clips [B C, 2] = the number of
+    transitions whose step size the clip to STEP_MIN, to STEP_MAX changed).
+    nonfinite_is_decided: a transition whose fp64 h_new is not finite counts as a decided reject -- fp32 overflows no later than
+    fp64, and a NaN of inf - inf is a NaN in both --; the ReLU margin is then not asked of that transition's path.
+    jitter_seed: every gradient a transition consumes is multiplied elementwise by 1 + 2^-20 r, r = +-1 from
+    default_rng(jitter_seed) -- a few fp32 ulps --, and the start z_0 is rounded to fp32, the format a device holds the chain's
+    state in (a base sigma below an ulp of mu, 6e-8 |mu|, is not resolved by such a state: log r(z_0) then depends on the
+    rounding by up to eps^2 / 2 per dimension): the second run of well_conditioned().
+    z0_fp32: the first run starts from z_0 rounded to fp32 as well -- the statement of a chain whose state is fp32 from the start,
+    for a case whose base is that narrow."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):      # (a proposal that is not finite is a case here)
+        return _ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init, step_up, step_down, base, nonfinite_is_decided,
+                    jitter_seed, z0_fp32)
+
+
+def _ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init, step_up, step_down, base, nonfinite_is_decided, jitter_seed,
+         z0_fp32):
+    jit = lambda g: g
+    if jitter_seed is not None:
+        jrng = np.random.default_rng(jitter_seed)
+        jit = lambda g: g * (1.0 + 2.0 ** -20 * jrng.choice([-1.0, 1.0], size=g.shape))
     betas = np.asarray(betas, F64)
     T = len(betas) - 1
     B = np.asarray(x).shape[0]
@@ -155,12 +178,17 @@ def ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init="prior", step_
     u = np.asarray(u, F64).reshape(T + 1, R)
     tg = Target(model, d, p, x, C, init, base)
     z, edge = tg.start(eps[0], u[0])
+    if jitter_seed is not None or z0_fp32:
+        z = z.astype(np.float32).astype(F64)
+    z0 = z.copy()
     decided = edge > 1e-6
     vA, vB, gA, gB, margin = tg.parts(z)
+    gA, gB = jit(gA), jit(gB)
     decided &= margin > 1e-5
     logw = np.zeros(R)
     step = np.full(R, min(max(float(step0), STEP_MIN), STEP_MAX))
     accepts = np.zeros((T, R), bool)
+    h_news, clips = np.zeros((T, R)), np.zeros((R, 2), np.int64)
     for t in range(1, T + 1):
         logw = logw + (betas[t] - betas[t - 1]) * tg.dlogw(vA, vB)
         cA, cB = tg.coef(betas[t])
@@ -173,18 +201,24 @@ def ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init="prior", step_
         for i in range(1, n_leapfrog + 1):
             zn = zn + e * mom
             nA, nB, ngA, ngB, margin = tg.parts(zn)
+            ngA, ngB = jit(ngA), jit(ngB)
             path_ok &= margin > 1e-5
             mom = mom + (e if i < n_leapfrog else 0.5 * e) * (cA * ngA + cB * ngB)
         h_new = -(cA * nA + cB * nB) + 0.5 * (mom * mom).sum(axis=1)
         with np.errstate(invalid="ignore"):
             dh = h_old - h_new
             acc = np.isfinite(h_new) & (np.log(u[t]) < dh)
-            decided &= path_ok & np.isfinite(h_new) & (np.abs(np.log(u[t]) - dh) > 1e-4 * (np.abs(h_old) + np.abs(h_new)) + 1e-6)
+            clear = path_ok & np.isfinite(h_new) & (np.abs(np.log(u[t]) - dh) > 1e-4 * (np.abs(h_old) + np.abs(h_new)) + 1e-6)
+            decided &= (clear | ~np.isfinite(h_new)) if nonfinite_is_decided else clear
         accepts[t - 1] = acc
+        h_news[t - 1] = h_new
         a = acc[:, None]
         z, gA, gB = np.where(a, zn, z), np.where(a, ngA, gA), np.where(a, ngB, gB)
         vA, vB = np.where(acc, nA, vA), np.where(acc, nB, vB)
-        step = np.clip(step * np.where(acc, step_up, step_down), STEP_MIN, STEP_MAX)
+        raw = step * np.where(acc, step_up, step_down)
+        clips[:, 0] += raw < STEP_MIN
+        clips[:, 1] += raw > STEP_MAX
+        step = np.clip(raw, STEP_MIN, STEP_MAX)
     lw = logw.reshape(B, C)
     m = lw.max(axis=1, keepdims=True)
     w = np.exp(lw - m)
@@ -193,7 +227,30 @@ def ais(model, d, p, x, betas, C, n_leapfrog, step0, eps, u, init="prior", step_
     rate = accepts.reshape(T, B, C).mean(axis=(0, 2))
     stats = np.stack([bound, ess, rate, step.reshape(B, C).mean(axis=1)], axis=1)
     tail = np.array([-bound.sum(), ess.sum(), rate.sum(), stats[:, 3].sum(), B, 0, 0, 0], F64)
-    return dict(logw=lw, bound=bound, stats=stats, z=z, tail=tail, accepts=accepts, decided=decided, steps=step)
+    return dict(logw=lw, bound=bound, stats=stats, z=z, tail=tail, accepts=accepts, decided=decided, steps=step,
+                h_new=h_news, z0=z0, clips=clips)
+
+
+def well_conditioned(ref, jittered, keys=("logw", "z"), rel=1e-5):
+    """[rows] bool from two runs of a statement, the second with jitter_seed set: the accept sequence (ais) or the applied count
+    (refine_ref.refine) is unchanged and every output named moves by at most rel max(1, |.|) -- a tenth of the project's 1e-4
+    gate, which so keeps a tenfold margin over what rounding of a few fp32 ulps in the gradients does to the reference itself.
+    An output that is not finite in both runs alike counts as unmoved."""
+    n = ref["decided"].shape[0]
+    if "accepts" in ref:
+        ok = (ref["accepts"] == jittered["accepts"]).all(axis=0)
+    else:
+        ok = ref["stats"][:, 5] == jittered["stats"][:, 5]
+    for k in keys:
+        a, b = np.asarray(ref[k], F64), np.asarray(jittered[k], F64)
+        if k == "trace":                                   # [n_steps, B]
+            a, b = a.T, b.T
+        a, b = a.reshape(n, -1), b.reshape(n, -1)
+        with np.errstate(invalid="ignore"):
+            same = np.abs(a - b) <= rel * np.maximum(1.0, np.abs(a))
+            same |= ~np.isfinite(a) & ~np.isfinite(b) & ((a == b) | (np.isnan(a) & np.isnan(b)))
+        ok &= same.all(axis=1)
+    return ok
 
 
 def bound_stderr(logw):

@@ -7,7 +7,11 @@ then the ELBO and the importance-weighted bound of the start and of the refined 
   step t: z_s = m + e^s eps_s, g_s = grad_z log p(x, z_s); L-hat_t = 1/S sum_s log p(x, z_s) + sum_l s_l + L/2 (1 + ln 2 pi);
     dm = 1/S sum_s g_s, ds = 1/S sum_s g_s e^s eps_s + 1; one ASCENT step of adam_ref.predict on the 2 L parameters (the gradient
     handed over negated; parameters and moments held in fp32, alpha_t in the fp64-pow form, the example's own count); an example
-    whose gradient is not finite skips the update (moments and count untouched); s clamped to [-20, 5] after the update;
+    whose gradient has an element that is not finite, or, rounded to fp32, is 2^63.5 = 1.3e19 or more in magnitude, skips the
+    update (moments and count untouched) -- the device squares the element in fp32 and 2^64 squared is past fp32's largest
+    number: its second moment would become inf and freeze the element for good where an fp64 update would move it, so both
+    skip, with half a binade to spare; s clamped to
+    [-20, 5] after the update;
   evaluation: R rounds of S fresh eps, N = R S; log w = log p(x, z) - log q_phi(z) at phi* and phi_0 on the SAME eps; the ELBO =
     mean log w, the importance-weighted bound = logsumexp log w - ln N, the effective sample size of the N weights at phi*.
 
@@ -16,7 +20,8 @@ Noise is an explicit input: eps [n_steps + R, B S, L], row (b, s) -> b S + s.
 refine() also reports, per example, whether an fp32 evaluation can be held to it (the idea of ais_ref's DECIDED chains): an example
 is DECIDED if every ReLU pre-activation on its path exceeds 1e-5 in magnitude; at every applied step and element sqrt(v') >= 1e-3
 times the example's largest sqrt(v') of that step (below that Adam's ratio m' / sqrt(v') amplifies the gradient's rounding); and no
-s lands within 1e-6 of a clamp edge."""
+s lands within 1e-6 of a clamp edge.  Keyword paths for the cases outside the Xavier regime (tests/inference_saturated_cases.py):
+rule="clearance" with jitter_seed and ais_ref.well_conditioned, and count="global"."""
 import math
 
 import numpy as np
@@ -28,6 +33,7 @@ import oracle as O
 F64 = np.float64
 LOG_2PI = math.log(2.0 * math.pi)
 S_MIN, S_MAX = -20.0, 5.0
+G_MAX = np.float32(2.0 ** 63.5)      # kRefineGMax: a gradient element at or above it, as the device holds it in fp32, skips the update
 STATS = ("elbo_start", "elbo_refined", "iw_start", "iw_refined", "ess_refined", "updates", "mean_shift", "log_sigma_ratio")
 
 
@@ -77,9 +83,18 @@ def log_weights(joint, m, sg, ls, e):
         return val.reshape(B, S) - lq, margin.reshape(B, S).min(axis=1)
 
 
-def refine(model, d, p, x, start, n_steps, S, R, lr, b1, b2, adam_eps, eps):
-    """Returns dict(phi [B, 2 L] = (m*, sigma*), trace [n_steps, B], stats [B, 8] (STATS), tail [8], decided [B] bool,
-    logw_start, logw_refined [B, R S])."""
+def refine(model, d, p, x, start, n_steps, S, R, lr, b1, b2, adam_eps, eps, rule="sqrt_v", jitter_seed=None, count="own"):
+    """Returns dict(phi [B, 2 L] = (m*, sigma*), trace [n_steps, B], stats [B, 8] (STATS), bounds = stats[:, :4], tail [8],
+    decided [B] bool, logw_start, logw_refined [B, R S], grads [n_steps, B, 2 L], clamped [B, 2] = the updates of the example
+    that were clipped at S_MIN, at S_MAX).
+    rule: "sqrt_v" -- DECIDED as the module states it; "clearance" -- the ReLU margin and the clamp clearance alone, for the
+    regimes whose gradients span too many orders for the sqrt(v') rule to hold on any example: the caller then asks
+    ais_ref.well_conditioned of a second run as well.
+    jitter_seed: the gradient each step consumes is multiplied elementwise by 1 + 2^-20 r, r = +-1 from
+    default_rng(jitter_seed): that second run.
+    count: "own" -- alpha_t from the example's own count of applied updates, as the device does; "global" -- from the step index
+    t + 1, the mistake tests/test_inference_saturated_cpu.py shows the own-count case can see."""
+    jrng = None if jitter_seed is None else np.random.default_rng(jitter_seed)
     B, L = np.asarray(x).shape[0], d.L
     eps = np.asarray(eps, F64).reshape(n_steps + R, B, S, L)
     start = np.asarray(start, np.float32)
@@ -93,21 +108,30 @@ def refine(model, d, p, x, start, n_steps, S, R, lr, b1, b2, adam_eps, eps):
     cnt = np.zeros(B, np.int64)
     decided = np.ones(B, bool)
     trace = np.zeros((n_steps, B))
+    grads, clamped = np.zeros((n_steps, B, 2 * L)), np.zeros((B, 2), np.int64)
     for t in range(n_steps):
         p64 = par.astype(F64)
         lh, dm, ds, margin = elbo_and_grad(joint, p64[:, :L], p64[:, L:], eps[t])
         trace[t] = lh
         grad = np.concatenate([dm, ds], axis=1)
-        ok = np.isfinite(grad).all(axis=1)
+        if jrng is not None:
+            grad = grad * (1.0 + 2.0 ** -20 * jrng.choice([-1.0, 1.0], size=grad.shape))
+        grads[t] = grad
         with np.errstate(all="ignore"):
-            p2, m2, v2, _ = adam_ref.predict(par, am, av, -grad, 1, (cnt + 1)[:, None], lr, b1, b2, adam_eps)
+            ok = (np.abs(grad.astype(np.float32)) < G_MAX).all(axis=1)           # (a NaN compares false)
+            step_t = (cnt + 1)[:, None] if count == "own" else t + 1
+            p2, m2, v2, _ = adam_ref.predict(par, am, av, -grad, 1, step_t, lr, b1, b2, adam_eps)
             sv = np.sqrt(v2)
-            decided &= ~ok | ((margin > 1e-5) & (sv >= 1e-3 * sv.max(axis=1, keepdims=True)).all(axis=1) &
+            ratio = (sv >= 1e-3 * sv.max(axis=1, keepdims=True)).all(axis=1) if rule == "sqrt_v" else True
+            decided &= ~ok | ((margin > 1e-5) & ratio &
                               (np.abs(p2[:, L:] - S_MIN) > 1e-6).all(axis=1) & (np.abs(p2[:, L:] - S_MAX) > 1e-6).all(axis=1))
+            clamped[:, 0] += ok & (p2[:, L:] < S_MIN).any(axis=1)
+            clamped[:, 1] += ok & (p2[:, L:] > S_MAX).any(axis=1)
             p2[:, L:] = np.clip(p2[:, L:], S_MIN, S_MAX)
         o = ok[:, None]
-        par = np.where(o, p2.astype(np.float32), par)
-        am, av = np.where(o, m2.astype(np.float32), am), np.where(o, v2.astype(np.float32), av)
+        with np.errstate(all="ignore"):                                          # (a skipped example's p2, m2, v2 are not used)
+            par = np.where(o, p2.astype(np.float32), par)
+            am, av = np.where(o, m2.astype(np.float32), am), np.where(o, v2.astype(np.float32), av)
         cnt = cnt + ok
     m1, ls1 = par[:, :L].astype(F64), par[:, L:].astype(F64)
     with np.errstate(all="ignore"):
@@ -133,8 +157,8 @@ def refine(model, d, p, x, start, n_steps, S, R, lr, b1, b2, adam_eps, eps):
     with np.errstate(all="ignore"):
         stats = np.stack([e0, e1, i0, i1, ess, cnt.astype(F64), (np.abs(m1 - mu0) / sg0).mean(axis=1), (ls1 - ls0).mean(axis=1)], axis=1)
     tail = np.array([e0.sum(), e1.sum(), i0.sum(), i1.sum(), B, 0, 0, 0], F64)
-    return dict(phi=np.concatenate([m1, sg1], axis=1), trace=trace, stats=stats, tail=tail, decided=decided, logw_start=lw0,
-                logw_refined=lw1)
+    return dict(phi=np.concatenate([m1, sg1], axis=1), trace=trace, stats=stats, bounds=stats[:, :4], tail=tail, decided=decided,
+                logw_start=lw0, logw_refined=lw1, grads=grads, clamped=clamped)
 
 
 # ------------------------------------------------------------------------------------------------------- the parity cases
