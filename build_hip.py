@@ -14,7 +14,7 @@ SRC = os.path.join(HERE, "csrc", "gmvae_hip.hip")
 SRC_EVAL = os.path.join(HERE, "csrc", "tsne.hip")
 SRC_MIXFIT = os.path.join(HERE, "csrc", "mixfit.hip")      # a third one, for the same reason
 SRC_NEIGH = os.path.join(HERE, "csrc", "neigh.hip")        # and a fourth
-SRC_AIS = os.path.join(HERE, "csrc", "ais.hip")            # and a fifth: gmvae_ais and gmvae_refine (ais.hpp's kernels, defined once)
+SRC_AIS = os.path.join(HERE, "csrc", "ais.hip")            # and a fifth: gmvae_ais, gmvae_refine, gmvae_simulate, gmvae_ais_reverse (ais.hpp's kernels, defined once)
 import glob
 DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*"))) + [os.path.join(ROOT, "include", "gmvae_hip.h")]
 OUT = os.path.join(HERE, "lib", "libgmvae_hip.so")

@@ -83,6 +83,11 @@ def _load():
         "gmvae_knn_class_sums": ([vp, i64, vp, i64, i32, vp, i32, vp, vp, vp], i32),
         "gmvae_ais_workspace_bytes": ([dp, i32, i32, i32, C.POINTER(u64)], i32),
         "gmvae_ais": ([dp, i32, vp, vp, vp, i32, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64, vp], i32),
+        "gmvae_simulate_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
+        "gmvae_simulate": ([dp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64, vp], i32),
+        "gmvae_ais_reverse_workspace_bytes": ([dp, i32, i32, i32, C.POINTER(u64)], i32),
+        "gmvae_ais_reverse": ([dp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, u64,
+                               u64, vp], i32),
         "gmvae_refine_workspace_bytes": ([dp, i32, i32, C.POINTER(u64)], i32),
         "gmvae_refine": ([dp, i32, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "adam_tf_step": ([vp, vp, vp, vp, u64, f32, f32, f32, f32, u64, vp, f32, vp, vp, vp], i32),
@@ -247,6 +252,21 @@ def ais_workspace_bytes(dims, model, base_K, n_chains):
     """Bytes of gmvae_ais's workspace (include/gmvae_hip.h gmvae_ais_workspace_bytes)."""
     b = C.c_uint64()
     check(lib.gmvae_ais_workspace_bytes(C.byref(dims), int(model), int(base_K), int(n_chains), C.byref(b)), "gmvae_ais_workspace_bytes")
+    return b.value
+
+
+def simulate_workspace_bytes(dims, model):
+    """Bytes of gmvae_simulate's workspace (include/gmvae_hip.h gmvae_simulate_workspace_bytes)."""
+    b = C.c_uint64()
+    check(lib.gmvae_simulate_workspace_bytes(C.byref(dims), int(model), C.byref(b)), "gmvae_simulate_workspace_bytes")
+    return b.value
+
+
+def ais_reverse_workspace_bytes(dims, model, base_K, n_chains):
+    """Bytes of gmvae_ais_reverse's workspace (include/gmvae_hip.h gmvae_ais_reverse_workspace_bytes)."""
+    b = C.c_uint64()
+    check(lib.gmvae_ais_reverse_workspace_bytes(C.byref(dims), int(model), int(base_K), int(n_chains), C.byref(b)),
+          "gmvae_ais_reverse_workspace_bytes")
     return b.value
 
 

@@ -1,5 +1,5 @@
-// gmvae_ais and gmvae_refine: the host side of csrc/ais.hpp and csrc/refine.hpp (include/gmvae_hip.h).  ONE translation unit for
-// the two entry points, because the kernels of ais.hpp are plain definitions: a library defines them once, so whatever evaluates
+// gmvae_ais, gmvae_refine, gmvae_simulate and gmvae_ais_reverse: the host side of csrc/ais.hpp, csrc/refine.hpp and csrc/bdmc.hpp
+// (include/gmvae_hip.h).  ONE translation unit for these entry points, because the kernels of ais.hpp are plain definitions: a library defines them once, so whatever evaluates
 // with ais_eval is hosted here.  A unit -- and so a device code object -- apart from the training step's, for the reason
 // csrc/tsne.hip gives: the training step's code object, and with it the placement of the one-launch step's code, is what it was
 // without these kernels.
@@ -12,6 +12,7 @@
 
 #include "../../include/gmvae_hip.h"
 #include "ais.hpp"
+#include "bdmc.hpp"
 #include "hostutil.hpp"
 #include "refine.hpp"
 
@@ -200,37 +201,29 @@ int finish_and_tail(hipStream_t st, int B, double* fin, float* tail, Kernel fini
   return (int)hipGetLastError();
 }
 
-}  // namespace
-
-extern "C" {
-
-int gmvae_ais_workspace_bytes(const GmvaeDims* dims, int model, int base_K, int n_chains, uint64_t* bytes) {
-  if (int e = ais_check(dims, model, base_K, 1, n_chains, 1)) return e;
-  if (!bytes) return GMVAE_E_NULL;
-  *bytes = ais_ws(*dims, model, base_K, n_chains).total;
-  return 0;
-}
-
-int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
-              const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0, float step_up, float step_down,
-              const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out, float* tail,
-              void* workspace, uint64_t seed, uint64_t step, void* stream) {
+// ---- gmvae_ais and gmvae_ais_reverse: one host path.  reverse: the chains start at z_start [B][L] and run T .. 1 (csrc/bdmc.hpp).
+int run_chains(bool reverse, const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
+               const float* z_start, const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0, float step_up,
+               float step_down, const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out,
+               float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream) {
   if (int e = ais_check(dims, model, base_K, n_temps, n_chains, n_leapfrog)) return e;
   if (!(step0 > 0.f) || !(step_up > 0.f) || !(step_down > 0.f) || !(step0 < INFINITY) || !(step_up < INFINITY) ||
       !(step_down < INFINITY))
     return GMVAE_E_DIMS;
   if ((base != nullptr) != (base_K > 0)) return base ? GMVAE_E_DIMS : GMVAE_E_NULL;
-  if (!x || !params || !betas_dev || !tail || !workspace) return GMVAE_E_NULL;
+  if (!x || !params || !betas_dev || !tail || !workspace || (reverse && !z_start)) return GMVAE_E_NULL;
   if (!aligned_to(params, 16) || !aligned_to(base, 4) || !aligned_to(betas_dev, 4) || !aligned_to(eps, 4) || !aligned_to(u, 4) ||
       !aligned_to(logw_out, 4) || !aligned_to(bound_out, 4) || !aligned_to(stats_out, 4) || !aligned_to(z_out, 4) ||
-      !aligned_to(tail, 4) || !aligned_to(workspace, 256) || !aligned_to(dims->gen_bias_vec, 4))
+      !aligned_to(tail, 4) || !aligned_to(workspace, 256) || !aligned_to(dims->gen_bias_vec, 4) || !aligned_to(z_start, 4))
     return GMVAE_E_ALIGN;
   const GmvaeDims& d = *dims;
   const AisWs w = ais_ws(d, model, base_K, n_chains);
   char* const ws = static_cast<char*>(workspace);
-  AisArgs a;
+  RevArgs ra;
+  AisArgs& a = ra.a;
   AisPrep p;
   if (int e = bind_model(d, model, params, x, ws, w.prior, a, p)) return e;
+  ra.z_start = z_start;
   p.Kb = base_K; p.base = base; p.base_c = at<double>(ws, w.base_c);
   a.C = n_chains;
   a.n = (long long)d.B * n_chains;
@@ -249,18 +242,100 @@ int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* p
   const int cap = launch_cap("GMVAE_AIS_LAUNCH_TEMPS", kAisLaunchTemps);
   const unsigned lds = ais_lds(d.L, d.n_hidden, a.hidden).total;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int e = raise_lds(ais_run, lds)) return e;
+  if (int e = reverse ? raise_lds(bdmc_rev_run, lds) : raise_lds(ais_run, lds)) return e;
   hipLaunchKernelGGL(ais_prep, dim3(1u + (a.enc ? (unsigned)d.B : 0u)), dim3(kAisThreads), 0, st, p);
   const unsigned panels = (unsigned)((a.n + kAisRows - 1) / kAisRows);
-  // the start (t = 0) rides on the first launch: transitions 0 .. cap, then cap more per launch
-  for (int t_lo = 0; t_lo <= n_temps;) {
-    const int t_hi = (int)(((long long)t_lo + cap < n_temps) ? t_lo + cap : n_temps);
-    a.t_lo = t_lo; a.t_hi = t_hi;
-    hipLaunchKernelGGL(ais_run, dim3(panels), dim3(kAisThreads), lds, st, a);
-    t_lo = t_hi + 1;
+  if (!reverse) {
+    // the start (t = 0) rides on the first launch: transitions 0 .. cap, then cap more per launch
+    for (int t_lo = 0; t_lo <= n_temps;) {
+      const int t_hi = (int)(((long long)t_lo + cap < n_temps) ? t_lo + cap : n_temps);
+      a.t_lo = t_lo; a.t_hi = t_hi;
+      hipLaunchKernelGGL(ais_run, dim3(panels), dim3(kAisThreads), lds, st, a);
+      t_lo = t_hi + 1;
+    }
+  } else {
+    // descending, the mirror image: the start (t = T + 1) and transitions T .. T + 1 - cap, then cap more per launch down to 1
+    for (int t_hi = n_temps + 1; t_hi >= 1;) {
+      const int t_lo = t_hi - cap > 1 ? t_hi - cap : 1;
+      a.t_lo = t_lo; a.t_hi = t_hi;
+      hipLaunchKernelGGL(bdmc_rev_run, dim3(panels), dim3(kAisThreads), lds, st, ra);
+      t_hi = t_lo - 1;
+    }
   }
   return finish_and_tail(st, d.B, at<double>(ws, w.fin), tail, ais_finish, a.st_d, a.st_eps, a.st_acc, d.B, n_chains, n_temps,
-                         logw_out, bound_out, stats_out);
+                         reverse ? -1.0 : 1.0, logw_out, bound_out, stats_out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmvae_ais_workspace_bytes(const GmvaeDims* dims, int model, int base_K, int n_chains, uint64_t* bytes) {
+  if (int e = ais_check(dims, model, base_K, 1, n_chains, 1)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  *bytes = ais_ws(*dims, model, base_K, n_chains).total;
+  return 0;
+}
+
+int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
+              const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0, float step_up, float step_down,
+              const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out, float* tail,
+              void* workspace, uint64_t seed, uint64_t step, void* stream) {
+  return run_chains(false, dims, model, x, params, base, base_K, nullptr, betas_dev, n_temps, n_chains, n_leapfrog, step0, step_up,
+                    step_down, eps, u, logw_out, bound_out, stats_out, z_out, tail, workspace, seed, step, stream);
+}
+
+int gmvae_ais_reverse_workspace_bytes(const GmvaeDims* dims, int model, int base_K, int n_chains, uint64_t* bytes) {
+  return gmvae_ais_workspace_bytes(dims, model, base_K, n_chains, bytes);      // (the chains' state is the forward chains')
+}
+
+int gmvae_ais_reverse(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
+                      const float* z_start, const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0,
+                      float step_up, float step_down, const float* eps, const float* u, float* logw_out, float* bound_out,
+                      float* stats_out, float* z_out, float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream) {
+  return run_chains(true, dims, model, x, params, base, base_K, z_start, betas_dev, n_temps, n_chains, n_leapfrog, step0, step_up,
+                    step_down, eps, u, logw_out, bound_out, stats_out, z_out, tail, workspace, seed, step, stream);
+}
+
+int gmvae_simulate_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes) {
+  if (int e = ais_check(dims, model, 0, 1, 1, 1)) return e;
+  if (!bytes) return GMVAE_E_NULL;
+  uint64_t o = 0;
+  (void)carve_prior(o, (uint64_t)prior_K(*dims, model), (uint64_t)dims->L);
+  *bytes = o;
+  return 0;
+}
+
+int gmvae_simulate(const GmvaeDims* dims, int model, const float* params, const float* eps, const float* u, const float* ux,
+                   float* z_out, int32_t* k_out, uint8_t* x_out, float* prob_out, void* workspace, uint64_t seed, uint64_t step,
+                   void* stream) {
+  if (int e = ais_check(dims, model, 0, 1, 1, 1)) return e;
+  if (!params || !z_out || !k_out || !x_out || !workspace) return GMVAE_E_NULL;
+  if (!aligned_to(params, 16) || !aligned_to(eps, 4) || !aligned_to(u, 4) || !aligned_to(ux, 4) || !aligned_to(z_out, 4) ||
+      !aligned_to(k_out, 4) || !aligned_to(x_out, 4) || !aligned_to(prob_out, 4) || !aligned_to(workspace, 256) ||
+      !aligned_to(dims->gen_bias_vec, 4))
+    return GMVAE_E_ALIGN;
+  const GmvaeDims& d = *dims;
+  uint64_t o = 0;
+  const PriorWs w = carve_prior(o, (uint64_t)prior_K(d, model), (uint64_t)d.L);
+  SimArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  AisArgs& a = sa.a;
+  AisPrep p;
+  if (int e = bind_model(d, model, params, nullptr, static_cast<char*>(workspace), w, a, p)) return e;
+  a.C = 1;
+  a.n = d.B;
+  a.T = 1;                                        // (ais_noise keys the draw of t by step (T + 1) + t: 2 step, and 2 step + 1 the pixels)
+  a.eps = eps; a.u = u;
+  a.row_base = d.row0; a.seed = seed; a.step = step;
+  sa.ux = ux;
+  sa.z_out = z_out; sa.k_out = k_out; sa.x_out = x_out; sa.prob_out = prob_out;
+  const unsigned lds = ais_lds(d.L, d.n_hidden, a.hidden).total;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int e = raise_lds(sim_rows, lds)) return e;
+  hipLaunchKernelGGL(ais_prep, dim3(1), dim3(kAisThreads), 0, st, p);
+  hipLaunchKernelGGL(sim_rows, dim3((unsigned)((d.B + kAisRows - 1) / kAisRows)), dim3(kAisThreads), lds, st, sa);
+  return (int)hipGetLastError();
 }
 
 int gmvae_refine_workspace_bytes(const GmvaeDims* dims, int model, int n_samples, uint64_t* bytes) {

@@ -523,10 +523,12 @@ __global__ __launch_bounds__(kAisThreads) void ais_prep(const AisPrep a) {
   }
 }
 
-// ---- per example: log w as floats, the bound, the chains' statistics; fin [B][4] keeps them in fp64 for the tail
+// ---- per example: log w as floats, the bound, the chains' statistics; fin [B][4] keeps them in fp64 for the tail.  sign = 1: the
+// lower bound of the forward chains (a product with 1.0 is exact: their bits are what they were); sign = -1: the upper bound
+// -(logsumexp_c log w_rev - ln C) of the reverse chains (csrc/bdmc.hpp).
 __global__ __launch_bounds__(kAisThreads) void ais_finish(const double* __restrict__ st_d, const float* __restrict__ st_eps,
                                                           const int* __restrict__ st_acc, const int B, const int C, const int T,
-                                                          float* __restrict__ logw_out, float* __restrict__ bound_out,
+                                                          const double sign, float* __restrict__ logw_out, float* __restrict__ bound_out,
                                                           float* __restrict__ stats_out, double* __restrict__ fin) {
   const int b = blockIdx.x * kAisThreads + threadIdx.x;
   if (b >= B) return;
@@ -543,7 +545,7 @@ __global__ __launch_bounds__(kAisThreads) void ais_finish(const double* __restri
     na += st_acc[c0 + c];
     if (logw_out) logw_out[c0 + c] = (float)lw;
   }
-  const double bound = m + log(s1) - log((double)C), ess = s1 * s1 / s2, acc = (double)na / ((double)C * (double)T), me = se / (double)C;
+  const double bound = sign * (m + log(s1) - log((double)C)), ess = s1 * s1 / s2, acc = (double)na / ((double)C * (double)T), me = se / (double)C;
   if (bound_out) bound_out[b] = (float)bound;
   if (stats_out) {
     stats_out[b * 4] = (float)bound; stats_out[b * 4 + 1] = (float)ess; stats_out[b * 4 + 2] = (float)acc; stats_out[b * 4 + 3] = (float)me;

@@ -904,7 +904,13 @@ class Engine:
         Chain c of row b draws Philox row (row0 + b) * n_chains + c keyed by (noise_seed, global_step * (n_temps + 1) + t), row0
         defaulting to rank * B: the result does not depend on the batch size or the sharding.  eps [n_temps + 1, B n_chains, L] and
         u [n_temps + 1, B n_chains] replace the draw (tests).  Bernoulli likelihood only; not with pixel_mask."""
-        self._require_plain_bernoulli("ais_bound")
+        return self._ais_chains("ais_bound", x, None, n_chains, n_temps, schedule, n_leapfrog, step_size, init, adapt, row0, eps, u,
+                                step_up, step_down, self.noise_seed)
+
+    def _ais_chains(self, what, x, z_start, n_chains, n_temps, schedule, n_leapfrog, step_size, init, adapt, row0, eps, u, step_up,
+                    step_down, seed):
+        """One gmvae_ais call (z_start None) or one gmvae_ais_reverse call from z_start [B, L]: the common host side."""
+        self._require_plain_bernoulli(what)
         if init not in ("prior", "encoder"):
             raise ValueError(f"init must be 'prior' or 'encoder', got {init!r}")
         C_, T, nl = int(n_chains), int(n_temps), int(n_leapfrog)
@@ -929,13 +935,93 @@ class Engine:
         f32 = dict(dtype=torch.float32, device=self.device)
         o = dict(logw=torch.empty(B, C_, **f32), bound=torch.empty(B, **f32), stats=torch.empty(B, 4, **f32),
                  z=torch.empty(n, self.Lz, **f32), tail=torch.empty(L.TAIL, **f32))
-        rc = L.lib.gmvae_ais(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(base), base_K, L.ptr(betas), T, C_, nl,
-                             float(step_size), up, down, L.ptr(eps), L.ptr(u), L.ptr(o["logw"]), L.ptr(o["bound"]),
-                             L.ptr(o["stats"]), L.ptr(o["z"]), L.ptr(o["tail"]), L.ptr(ws), self.noise_seed, self.global_step,
-                             L.current_stream())
-        L.check(rc, "gmvae_ais")
-        self._keep_ais = (x, base, betas, eps, u)
+        out = (L.ptr(eps), L.ptr(u), L.ptr(o["logw"]), L.ptr(o["bound"]), L.ptr(o["stats"]), L.ptr(o["z"]), L.ptr(o["tail"]), L.ptr(ws),
+               int(seed), self.global_step, L.current_stream())
+        if z_start is None:
+            rc = L.lib.gmvae_ais(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(base), base_K, L.ptr(betas), T, C_, nl,
+                                 float(step_size), up, down, *out)
+        else:
+            z_start = z_start.to(self.device, torch.float32).contiguous()
+            if tuple(z_start.shape) != (B, self.Lz):
+                raise ValueError(f"z_start must be [B, L] = [{B}, {self.Lz}], got {tuple(z_start.shape)}")
+            rc = L.lib.gmvae_ais_reverse(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), L.ptr(base), base_K, L.ptr(z_start),
+                                         L.ptr(betas), T, C_, nl, float(step_size), up, down, *out)
+        L.check(rc, "gmvae_ais" if z_start is None else "gmvae_ais_reverse")
+        self._keep_ais = (x, base, betas, eps, u, z_start)
         return o
+
+    # Philox keys of the bidirectional pair: the forward chains keep ais_bound's key (noise_seed), the simulation and the reverse
+    # chains each take the seed with a fixed pattern folded in -- another Philox key is another stream, so the three are disjoint
+    _SIM_SALT, _REV_SALT = 0x53494D5F42444D43, 0x5245565F42444D43
+
+    def simulate(self, n: int, row0: Optional[int] = None, eps: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
+                 ux: Optional[torch.Tensor] = None):
+        """n ancestral samples (z*, x) ~ p(z) p(x|z) from the generative model (include/gmvae_hip.h gmvae_simulate): a component k
+        of the prior by inverse CDF (for the GMVAE k is y, uniform), z* = mu_k + sigma_k eps, x_d = [u_d < sigmoid(lambda_d(z*))].
+        z* is an EXACT posterior sample for x -- what ais_bound_reverse starts from.  Returns dict(z [n, L], k [n] int32,
+        x [n, D] uint8, prob [n, D] = sigmoid(lambda)).  Example b draws Philox row row0 + b (default rank * n) keyed by
+        (noise_seed with a fixed pattern folded in, 2 global_step and 2 global_step + 1): disjoint from every other draw of this
+        engine, independent of the batch and the sharding.  eps [n, L], u [n] and ux [n, D] replace the draws (tests).
+        Bernoulli likelihood only; not with pixel_mask."""
+        self._require_plain_bernoulli("simulate")
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"n must be >= 1, got {n}")
+        d = self.dims(n, 1, row0)
+        eps, u, ux = self._prep_noise(eps, n, self.Lz), self._prep_noise(u, n, 1), self._prep_noise(ux, n, self.D)
+        ws, _ = self._cached_ws(("simulate",), L.simulate_workspace_bytes(d, self.model) // 4 + 64)
+        o = dict(z=torch.empty(n, self.Lz, dtype=torch.float32, device=self.device),
+                 k=torch.empty(n, dtype=torch.int32, device=self.device),
+                 x=torch.empty(n, self.D, dtype=torch.uint8, device=self.device),
+                 prob=torch.empty(n, self.D, dtype=torch.float32, device=self.device))
+        rc = L.lib.gmvae_simulate(C.byref(d), self.model, L.ptr(self.params), L.ptr(eps), L.ptr(u), L.ptr(ux), L.ptr(o["z"]),
+                                  L.ptr(o["k"]), L.ptr(o["x"]), L.ptr(o["prob"]), L.ptr(ws), self.noise_seed ^ self._SIM_SALT,
+                                  self.global_step, L.current_stream())
+        L.check(rc, "gmvae_simulate")
+        self._keep_sim = (eps, u, ux)
+        return o
+
+    def ais_bound_reverse(self, x, z_start, n_chains: int = 16, n_temps: int = 1000, schedule="sigmoid", n_leapfrog: int = 10,
+                          step_size: float = 0.05, init: str = "prior", adapt: bool = True, row0: Optional[int] = None,
+                          eps: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, step_up: float = 1.02,
+                          step_down: float = 0.96):
+        """An UPPER bound on log p(x) from ais_bound's chains run backwards (include/gmvae_hip.h gmvae_ais_reverse; Grosse,
+        Ghahramani & Adams 2015): every chain of example b starts at z_start[b], which must be an exact posterior sample for x[b],
+        and anneals from beta = 1 down to 0 -- at each temperature first the HMC transition, then the weight update at the new
+        point.  Such a sample exists ONLY for simulated data (simulate's z for simulate's x): there is no exact posterior sample
+        for a real x, and so no upper bound for it.
+        Keywords and the returned dict are ais_bound's, with bound [B] = -(logsumexp_c log w_rev - ln n_chains) the upper bound,
+        logw = log w_rev, stats = (that bound, the ESS of the reverse weights, acceptance rate, final step size), z = the chains'
+        ends z_0, tail[0] the batch sum of -bound.  adapt=False is the strictly valid form, as for ais_bound: an adapted step size
+        depends on the chain's past, so the adapted weights are not exactly unbiased; in practice the difference is far below the
+        chains' standard error.  The chains draw ais_bound's Philox rows and steps under another key (noise_seed with a fixed
+        pattern folded in), so the two directions never share a draw.  eps and u have ais_bound's layout, slot 0 unused."""
+        return self._ais_chains("ais_bound_reverse", x, z_start, n_chains, n_temps, schedule, n_leapfrog, step_size, init, adapt,
+                                row0, eps, u, step_up, step_down, self.noise_seed ^ self._REV_SALT)
+
+    def bdmc_gap(self, n_examples: int, n_chains: int = 16, n_temps: int = 1000, row0: Optional[int] = None, **kw):
+        """Bidirectional Monte Carlo (Grosse, Ghahramani & Adams 2015; the validation of Wu et al. 2017): how far below log p(x)
+        ais_bound sits at these settings.  n_examples are simulated from the model (simulate); ais_bound on the simulated x gives
+        the lower bound -- the very call ais_bound(x_sim, n_chains, n_temps, row0=row0, **kw), bit for bit --, ais_bound_reverse
+        from the simulation's own z the upper one, on Philox keys disjoint from both.  In expectation lower <= log p(x) <= upper,
+        so gap = upper - lower bounds the bias of ais_log_px at n_chains, n_temps and kw (ais_bound's keywords: schedule,
+        n_leapfrog, step_size, init, adapt, step_up, step_down).  The upper bound exists only for simulated data, because there is
+        no exact posterior sample for a real x: the gap is a statement about data distributed as the model's own samples, and
+        carries over to real data as far as the model fits them.  adapt=False is the strictly valid form in both directions
+        (ais_bound's caveat).
+        Returns dict(lower [n], upper [n], gap [n], lower_ess, upper_ess, lower_accept, upper_accept [n], x [n, D], z [n, L],
+        k [n], forward, reverse = the two calls' dicts, and the means lower_mean, upper_mean, gap_mean, upper_ess_mean,
+        upper_accept_mean)."""
+        sim = self.simulate(n_examples, row0=row0)
+        fwd = self.ais_bound(sim["x"], n_chains, n_temps, row0=row0, **kw)
+        rev = self.ais_bound_reverse(sim["x"], sim["z"], n_chains, n_temps, row0=row0, **kw)
+        lower, upper = fwd["bound"], rev["bound"]
+        gap = upper.double() - lower.double()
+        return dict(lower=lower, upper=upper, gap=gap, lower_ess=fwd["stats"][:, 1], upper_ess=rev["stats"][:, 1],
+                    lower_accept=fwd["stats"][:, 2], upper_accept=rev["stats"][:, 2], x=sim["x"], z=sim["z"], k=sim["k"],
+                    forward=fwd, reverse=rev, lower_mean=lower.double().mean().item(), upper_mean=upper.double().mean().item(),
+                    gap_mean=gap.mean().item(), upper_ess_mean=rev["stats"][:, 1].double().mean().item(),
+                    upper_accept_mean=rev["stats"][:, 2].double().mean().item())
 
     REFINE_STATS = ("elbo_start", "elbo_refined", "iw_start", "iw_refined", "ess_refined", "updates", "mean_shift",
                     "log_sigma_ratio")

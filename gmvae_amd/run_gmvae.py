@@ -51,6 +51,11 @@ def build_parser():
     a("--ais_step_size", type=float, default=0.05, help="--ais_chains: the initial leapfrog step size (adapted per chain)")
     a("--ais_init", default="prior", choices=["prior", "encoder"], help="--ais_chains: the chains' base distribution")
     a("--ais_schedule", default="sigmoid", choices=["sigmoid", "linear"], help="--ais_chains: the annealing path")
+    a("--bdmc_examples", type=int, default=0, help="eval, with --ais_chains / --ais_temps: bidirectional Monte Carlo (Engine.bdmc_gap) on "
+      "this many examples SIMULATED from the model, at the --ais_* settings: reverse AIS chains from each example's exact "
+      "posterior sample give an upper bound on log p(x) beside ais_bound's lower one; reports bdmc_lower, bdmc_upper, bdmc_gap and "
+      "the reverse chains' effective sample size and acceptance rate.  The upper bound exists only for simulated data; the gap "
+      "bounds the bias of ais_log_px at these settings on data distributed as the model's own samples; 0 = off")
     a("--refine_steps", type=int, default=0, help="eval: also split the inference gap by refining q(z|x) per example with this many "
       "steps of Adam ascent on the example's own ELBO (Engine.inference_gaps); reports elbo_amortised, elbo_refined, "
       "iw_bound_refined, amortisation_gap and approximation_gap over the split (--ais_chains: ais_log_px joins log_px); 0 = off")
@@ -215,6 +220,10 @@ def check_args(p, cfg):
             p.error("--ais_leapfrog must be >= 1 and --ais_step_size a finite number > 0")
         if cfg.missing_rate > 0 or cfg.likelihood != "bernoulli":
             p.error("--ais_chains scores the Bernoulli likelihood on every pixel: not available with --missing_rate or --likelihood")
+    if cfg.bdmc_examples < 0:
+        p.error("--bdmc_examples must be >= 0 (0 = off)")
+    if cfg.bdmc_examples and not cfg.ais_chains:
+        p.error("--bdmc_examples runs at the --ais_* settings: it needs --ais_chains and --ais_temps")
     if cfg.refine_steps < 0:
         p.error("--refine_steps must be >= 0 (0 = off)")
     if not cfg.refine_steps and (cfg.refine_samples, cfg.refine_lr, cfg.refine_eval_samples) != (4, 0.05, 256):

@@ -780,6 +780,22 @@ def run_eval(config):
             q_logits.append(o["logits"])
         if ns_n and config.model == "gmvae" and first < ns_n:
             ns_logits.append(o["logits"][:ns_n - first])
+    # --bdmc_examples N: bidirectional Monte Carlo on N examples SIMULATED from the model (Engine.bdmc_gap) at the --ais_* settings:
+    # example i is Philox row i whatever --batch_size or the number of ranks; each rank takes a contiguous share
+    bd_n, bd_rows = int(getattr(config, "bdmc_examples", 0) or 0), []
+    if bd_n > 0:
+        share = (bd_n + world - 1) // world
+        lo, hi = min(rank * share, bd_n), min((rank + 1) * share, bd_n)
+        for first in range(lo, hi, int(config.batch_size)):
+            g = eng.bdmc_gap(min(int(config.batch_size), hi - first), ais_c, ais_t, row0=first,
+                             schedule=getattr(config, "ais_schedule", "sigmoid"), n_leapfrog=int(getattr(config, "ais_leapfrog", 10)),
+                             step_size=float(getattr(config, "ais_step_size", 0.05)), init=getattr(config, "ais_init", "prior"))
+            bd_rows.append(torch.stack([g["lower"], g["upper"], g["upper_ess"], g["upper_accept"]], dim=1))
+    # the sums over this rank's simulated examples of (lower, upper, reverse ESS, reverse acceptance rate), and their number
+    bd_tot = torch.zeros(5, dtype=torch.float64, device=eng.device)
+    if bd_rows:
+        bd_tot[:4] = torch.cat(bd_rows).double().sum(0)
+        bd_tot[4] = sum(r.shape[0] for r in bd_rows)
     iw_sum = torch.cat(iw_rows).double().sum().reshape(1) if iw_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     ie_sum = torch.cat(ie_rows).double().sum().reshape(1) if ie_rows else torch.zeros(1, dtype=torch.float64, device=eng.device)
     py_tot = torch.cat(py_stats).double().sum(0) if py_stats else torch.zeros(4, dtype=torch.float64, device=eng.device)
@@ -795,6 +811,8 @@ def run_eval(config):
             parallel.all_reduce_flat(rf_tot)
         if ais_c > 0:
             parallel.all_reduce_flat(ais_tot)
+        if bd_n > 0:
+            parallel.all_reduce_flat(bd_tot)
         parallel.all_reduce_flat(iw_sum)
         parallel.all_reduce_flat(class_hits)
         parallel.all_reduce_flat(pm_tot)
@@ -842,6 +860,15 @@ def run_eval(config):
                                                                  + math.log(int(config.mixture_components)))
         elif iw_n > 0 and config.model != "gmvae":
             res[f"{config.split}/ais_gap_to_iw_bound"] = (ais_tot[0].item() - iw_sum.item()) / n
+    if bd_n > 0:
+        # lower <= log p(x) <= upper in expectation ON SIMULATED DATA (a real x has no exact posterior sample, so no upper bound):
+        # the gap bounds the bias of ais_log_px at these settings on data distributed as the model's own samples
+        m = bd_tot[4].item()
+        res[f"{config.split}/bdmc_lower"] = bd_tot[0].item() / m
+        res[f"{config.split}/bdmc_upper"] = bd_tot[1].item() / m
+        res[f"{config.split}/bdmc_gap"] = (bd_tot[1].item() - bd_tot[0].item()) / m
+        res[f"{config.split}/bdmc_reverse_ess"] = bd_tot[2].item() / m
+        res[f"{config.split}/bdmc_reverse_accept_rate"] = bd_tot[3].item() / m
     if rf_t > 0:
         # the inference gap in its two parts (Cremer et al. 2018); log p(x) is the larger of the two lower bounds in hand
         am, er, ir = (rf_tot / n).tolist()
@@ -887,6 +914,7 @@ def run_eval(config):
     res["iw_bounds"] = torch.cat(iw_rows) if iw_rows else None      # this rank's examples, in split order
     res["iw_bounds_enum_y"] = torch.cat(ie_rows) if ie_rows else None
     res["refine_stats"] = torch.cat(rf_stats) if rf_stats else None   # [..., 8]: Engine.REFINE_STATS
+    res["bdmc_stats"] = torch.cat(bd_rows) if bd_rows else None     # [..., 4]: lower, upper, reverse ESS, reverse acceptance rate
     res["ais_stats"] = torch.cat(ais_rows) if ais_rows else None     # [..., 4]: log p(x) estimate, ESS, acceptance rate, step size
     if py_n > 0:
         res["log_posterior_y"] = torch.cat(py_rows)                  # [this rank's examples, K], in split order

@@ -100,6 +100,17 @@ class TrainableVAE(VAE):
         stats [B, 4] = bound, ESS, acceptance rate, step size; z; tail).  **kw: schedule, n_leapfrog, step_size, init, adapt."""
         return self._need_engine().ais_bound(images, n_chains, n_temps, **kw)
 
+    def simulate(self, num_samples, **kw):
+        """num_samples ancestral samples (z*, x) from the generative model on the device: Engine.simulate's dict (z, k, x, prob);
+        z* is an exact posterior sample for x.  generate_samples stays the reference's sampler; this one is what bdmc_gap needs."""
+        return self._need_engine().simulate(num_samples, **kw)
+
+    def bdmc_gap(self, n_examples, n_chains=16, n_temps=1000, **kw):
+        """Bidirectional Monte Carlo: lower (ais_bound) and upper (reverse chains from the exact posterior sample) bounds on
+        log p(x) of n_examples SIMULATED examples -- Engine.bdmc_gap's dict (lower, upper, gap, ...).  The upper bound exists only
+        for simulated data; the gap bounds the bias of ais_bound at these settings on data distributed as the model's samples."""
+        return self._need_engine().bdmc_gap(n_examples, n_chains, n_temps, **kw)
+
     def inference_gaps(self, images, n_steps=500, n_samples=4, n_eval=256, ais=None, **kw):
         """The inference gap log p(x) - L[q(z|x)] split into its amortisation and approximation parts by refining q(z|x) per
         example (Cremer, Li & Duvenaud 2018): Engine.inference_gaps's dict (elbo_amortised, elbo_refined, iw_bound_refined,

@@ -805,6 +805,54 @@ int gmvae_ais(const GmvaeDims* dims, int model, const uint8_t* x, const float* p
               const float* eps, const float* u, float* logw_out, float* bound_out, float* stats_out, float* z_out, float* tail,
               void* workspace, uint64_t seed, uint64_t step, void* stream);
 
+/* Bidirectional Monte Carlo (Grosse, Ghahramani & Adams 2015; the validation of Wu, Burda, Salakhutdinov & Grosse 2017): an UPPER
+ * bound on log p(x) beside gmvae_ais's lower one, on data the model itself generates.  gmvae_simulate draws (z*, x) ~ p(z) p(x|z),
+ * so z* is an exact posterior sample for x; gmvae_ais_reverse runs gmvae_ais's chain backwards from z*, beta = 1 down to 0.  The
+ * reversal of a Metropolis-corrected HMC kernel is the kernel itself, and the ratio of the reverse to the forward path density is
+ * w Z_0 / Z_T, so the reverse weights have E[w_rev] = 1 / p(x): -(logsumexp_c log w_rev - ln n_chains) bounds log p(x) from above in
+ * expectation.  The two bounds bracket log p(x), and their difference bounds the bias of gmvae_ais at these settings ON DATA
+ * DISTRIBUTED AS THE MODEL'S OWN SAMPLES; for a real x there is no exact posterior sample and so no upper bound.
+ * (Engine.simulate, Engine.ais_bound_reverse, Engine.bdmc_gap, model.bdmc_gap and run_gmvae --mode=eval --bdmc_examples go through
+ * them; the reference has no counterpart.)  The statement is tests/bdmc_ref.py; the kernels are csrc/bdmc.hpp.
+ *
+ * gmvae_simulate, example b < dims->B: a component k of the prior table (gmvae_ais's) by inverse CDF of its weights with one
+ *   uniform; z* = mu_k + sigma_k eps; lambda = decoder(z*) + gen_bias_init / gen_bias_vec (any hidden_act); x_d = [u_d <
+ *   sigmoid(lambda_d)].  Outputs: z_out [B][L]; k_out [B] (for the GMVAE this is y); x_out [B][D] bytes 0 / 1; prob_out [B][D] =
+ *   sigmoid(lambda) (may be NULL).
+ *   Noise: example b is Philox row dims->row0 + b; eps and the component's uniform are what gmvae_noise_fill(eps, u, B, L, 1, row0,
+ *   seed, 2 step) returns, the pixel uniforms the u of gmvae_noise_fill(NULL, u, B, 1, D, row0, seed, 2 step + 1).  eps [B][L],
+ *   u [B] and ux [B][D] (each may be NULL: Philox) replace the draws.
+ *   The workspace (gmvae_simulate_workspace_bytes; 256-byte aligned; needs no initialisation) holds the prior table.  Two
+ *   launches, no host synchronisation; one workgroup owns 16 examples.
+ *   Checks, before any launch, in this order: gmvae_ais's GMVAE_E_NULL (dims), GMVAE_E_MODEL and GMVAE_E_DIMS on the sizes, the
+ *   likelihood and mask bits and row0 + B < 2^38; GMVAE_E_NULL (params, z_out, k_out, x_out, workspace); GMVAE_E_ALIGN (params 16
+ *   bytes, the workspace 256, every other array 4 -- x_out included).
+ *
+ * gmvae_ais_reverse: gmvae_ais's arguments, sizes, gates, workspace layout and guarantees, with z_start [B][L] after base_K.
+ *   Chain (b, c) starts at z_T = z_start[b] -- all n_chains chains of an example from the one exact sample.  For t = T .. 1: first
+ *   one HMC transition on f_t from the current point, exactly gmvae_ais's (fresh momentum, n_leapfrog leapfrog steps, H in fp64,
+ *   accepted iff ln u < H_old - H_new, a non-finite H_new rejects, the same step-size update and clip); then
+ *   log w_rev -= (beta_t - beta_{t-1}) (log p(z) + log p(x|z) - log r(z)) at the NEW point z_{t-1}.
+ *   Noise: chain (b, c) is Philox row (dims->row0 + b) n_chains + c at step (n_temps + 1) + t for transition t, exactly as
+ *   gmvae_ais keys it (index 0 is unused): a caller that runs both directions separates them by `step` or `seed`.  eps
+ *   [n_temps + 1][B n_chains][L] and u [n_temps + 1][B n_chains] have gmvae_ais's layout, slot 0 ignored.
+ *   Outputs (each may be NULL but tail): logw_out = log w_rev; bound_out [B] = -(logsumexp_c log w_rev - ln n_chains), the upper
+ *   bound; stats_out [B][4] = that bound, the effective sample size of the reverse weights, the mean acceptance rate, the mean
+ *   final step size; z_out = z_0; tail = the sums over b laid out as gmvae_ais's, with ITS sign convention in slot 0: [0] = the
+ *   sum of -bound (here sum_b logsumexp_c log w_rev - ln n_chains), [1..3] the sums of ESS, acceptance rate and step size,
+ *   [4] = B, [5..7] = 0.  The accept record is gmvae_ais's: bit t - 1 of the chain's word for transition t <= 64.
+ *   Launches hold at most 32 transitions, descending in t (GMVAE_AIS_LAUNCH_TEMPS sets another cap; the result does not depend on
+ *   it).  Checks: gmvae_ais's, in its order, with z_start added to the GMVAE_E_NULL and the 4-byte GMVAE_E_ALIGN checks. */
+int gmvae_simulate_workspace_bytes(const GmvaeDims* dims, int model, uint64_t* bytes);
+int gmvae_simulate(const GmvaeDims* dims, int model, const float* params, const float* eps, const float* u, const float* ux,
+                   float* z_out, int32_t* k_out, uint8_t* x_out, float* prob_out, void* workspace, uint64_t seed, uint64_t step,
+                   void* stream);
+int gmvae_ais_reverse_workspace_bytes(const GmvaeDims* dims, int model, int base_K, int n_chains, uint64_t* bytes);
+int gmvae_ais_reverse(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, const float* base, int base_K,
+                      const float* z_start, const float* betas_dev, int n_temps, int n_chains, int n_leapfrog, float step0,
+                      float step_up, float step_down, const float* eps, const float* u, float* logw_out, float* bound_out,
+                      float* stats_out, float* z_out, float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream);
+
 /* Per-example refinement of q(z|x): the two parts of the inference gap log p(x) - L[q(z|x)] (Cremer, Li & Duvenaud 2018).  For each
  * example a local Gaussian q_phi(z) = N(m, diag e^{2 s}) starts at the caller's (mu_0, sigma_0) and climbs the example's own ELBO by
  * stochastic gradient ascent; the ELBO and the importance-weighted bound of the start and of the refined phi* are then evaluated on
