@@ -64,6 +64,8 @@ def _load():
         "gmvae_posterior_y": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "gmvae_posterior_component_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),
         "gmvae_posterior_component": ([dp, i32, vp, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp], i32),
+        "gmvae_impute_workspace_bytes": ([dp, i32, i32, C.POINTER(u64)], i32),
+        "gmvae_impute": ([dp, i32, vp, vp, u64, i32, vp, vp, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "gmvae_mixture_logpdf_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
         "gmvae_mixture_logpdf_accumulate": ([vp, i64, i32, vp, vp, vp, i64, i64, i64, vp, i32, vp, vp], i32),
         "gmvae_mixture_logpdf_finish": ([i64, i32, i32, C.c_double, vp, vp, vp, vp, vp], i32),
@@ -246,6 +248,13 @@ iw_bound_workspace_bytes = _chunked_workspace_bytes("iw_bound")
 iw_bound_enum_y_workspace_bytes = _chunked_workspace_bytes("iw_bound_enum_y")
 posterior_y_workspace_bytes = _chunked_workspace_bytes("posterior_y")
 posterior_component_workspace_bytes = _chunked_workspace_bytes("posterior_component")
+
+
+def impute_workspace_bytes(dims, model, n_draws=0):
+    """Bytes of gmvae_impute's workspace (include/gmvae_hip.h gmvae_impute_workspace_bytes)."""
+    b = C.c_uint64()
+    check(lib.gmvae_impute_workspace_bytes(C.byref(dims), int(model), int(n_draws), C.byref(b)), "gmvae_impute_workspace_bytes")
+    return b.value
 
 
 def ais_workspace_bytes(dims, model, base_K, n_chains):

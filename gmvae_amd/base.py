@@ -360,3 +360,52 @@ def impute(model, images, mask):
     xm = torch.where(m, images, torch.zeros_like(images))
     rec = model.reconstruct_images(xm).reshape(images.shape)
     return torch.where(m, images.to(rec.dtype), rec)
+
+
+def _bound_engine(model, what):
+    if model._engine is None:
+        raise ValueError(f"{what} runs on the model's Engine: create the model through the runners / bind an Engine first")
+    return model._engine
+
+
+def impute_posterior(model, images, mask, n_samples, n_draws=0, seed=None):
+    """VAE.impute / GMVAE.impute with n_samples given: Engine.impute_posterior's posterior-mean imputation (a float tensor of
+    the images' shape), or with n_draws = M > 0 the M completed images [B, M, ...] as uint8: the decoder (Engine.mlp) on the
+    sampling-importance-resampling draws of z, Bernoulli draws from a torch generator seeded with `seed` (None: the engine's
+    noise seed) at the missing pixels, the observed pixels copied."""
+    from . import _lib as L
+    eng = _bound_engine(model, "impute(n_samples=)")
+    B = images.shape[0]
+    x = images.reshape(B, -1)
+    m = torch.as_tensor(mask).reshape(B, -1)
+    o = eng.impute_posterior(x, n_samples, mask=m, n_draws=n_draws)
+    if not n_draws:
+        return o["imputed"].reshape(images.shape)
+    M = int(n_draws)
+    lam = eng.mlp(L.NET_DECODER, o["draw_z"].reshape(B * M, -1))
+    gen = torch.Generator(device=lam.device)
+    gen.manual_seed(int(eng.noise_seed if seed is None else seed) & (2 ** 63 - 1))
+    draws = (torch.rand(lam.shape, generator=gen, device=lam.device) < torch.sigmoid(lam)).to(torch.uint8).view(B, M, -1)
+    obs = (m.to(lam.device) != 0)[:, None, :]
+    xs = (x.to(lam.device) != 0).to(torch.uint8)[:, None, :]
+    return torch.where(obs, xs, draws).reshape(B, M, *images.shape[1:])
+
+
+def imputation_scores(model, images, mask, n_samples):
+    """VAE.imputation_scores / GMVAE.imputation_scores: the importance-sampling imputation p^ (Engine.impute_posterior, the
+    encoders fed mask * images) scored against the truth in `images` at the missing pixels: dict(nll = the cross-entropy per
+    missing pixel, error_rate = the share of missing pixels where round(p^) != x, cond_loglik = the mean over the examples of
+    log p^(x_missing | x_observed), ess = the mean effective sample size, n_missing), Python floats."""
+    eng = _bound_engine(model, "imputation_scores")
+    B = images.shape[0]
+    x = images.reshape(B, -1).to(eng.device)
+    m = torch.as_tensor(mask).reshape(B, -1).to(eng.device) != 0
+    o = eng.impute_posterior(x, n_samples, mask=m)
+    t = (x != 0).double()
+    p = o["mean"].double().clamp(1e-12, 1.0 - 1e-12)
+    miss = (~m).double()
+    n_missing = miss.sum().item()
+    ce = -(miss * (t * p.log() + (1.0 - t) * (-p).log1p())).sum().item()
+    wrong = (miss * ((p >= 0.5).double() != t).double()).sum().item()
+    return dict(nll=ce / max(n_missing, 1.0), error_rate=wrong / max(n_missing, 1.0), cond_loglik=o["cond_loglik"].double().mean().item(),
+                ess=o["ess"].double().mean().item(), n_missing=n_missing)

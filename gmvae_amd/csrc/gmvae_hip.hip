@@ -43,6 +43,7 @@
 #include "liksig.hpp"
 #include "gclip.hpp"
 #include "aggpost.hpp"
+#include "impute.hpp"      // gmvae_impute: the argument record and the host launch functions (kernels: impute.hip)
 #include "hostutil.hpp"      // aligned_to, first_on_device
 
 using namespace gmvae;
@@ -670,6 +671,7 @@ struct Ctx {
   Prof* prof = nullptr;
   int err = 0;
   int force_cfg = -1;
+  int nparts = 0;          // column tiles of the last general forward's logits launch: WS::part / hpart [R][nparts] (gmvae_impute)
   Ctx() { (void)hipGetLastError(); }   // drop any stale error another library left on this thread
   void mark(const char* name, double flops) {
     if (!prof || !prof->active || prof->n >= MAX_LEVELS) return;
@@ -954,6 +956,7 @@ struct StepArgs {
   int slot = 0;                // which slot of the per-step inputs' regions the step reads (step_inputs; step i of a train graph: i)
   bool iw_chunk = false;       // a chunk pass of gmvae_iw_bound: iw_tail writes the tail, [5..7] = 0 -- no pmask_tail
   const StepPlan* plan = nullptr;      // the caller has taken the step's plan already (dp_step_impl)
+  bool general = false;        // forward only: never the evalf launch -- the caller reads the general forward's activations (gmvae_impute)
 };
 
 static void rowk(Ctx& cx, const char* name) {
@@ -1093,6 +1096,7 @@ struct StepCtx {
   bool dp_graph = false;     // StepArgs::dp_graph
   bool imgs_ready = false;   // StepArgs::imgs_ready
   bool gen_noise = false;    // eps comes from the in-kernel Philox
+  bool general = false;      // StepArgs::general
   const float* params = nullptr;      // (null: no image plan -- gmvae_step_schedule and the profiles' admission)
 };
 struct StepPlan {
@@ -1133,7 +1137,7 @@ static StepPlan plan_step(const GmvaeDims& d, int model, const Layout& L, const 
   // evalf: a workgroup stages 8 batch rows per table pass: with ONE sample per row and more than 8 batch rows per workgroup a pass
   // is half a panel on one wave (measured, tools/eval_time.py: B = 8192, S = 1: 110 / 139 us against 115 / 81 on the chain /
   // general schedules; every other shape tried is 1.0 - 2.4x faster here)
-  const bool evalf_ok = bits_ok && !c.backward && !env_on("GMVAE_NO_EVALF") && evalf_shape(d, model) &&
+  const bool evalf_ok = bits_ok && !c.backward && !env_on("GMVAE_NO_EVALF") && !c.general && evalf_shape(d, model) &&
                         !(d.S == 1 && (B + eval_fused_grid(d) - 1) / eval_fused_grid(d) > EV::NB);
   const bool fused_ok = bits_ok && !c.outputs && !env_on("GMVAE_NO_FUSED") && fused_shape(d, model);
   p.kind = mega_ok ? STEP_MEGA : skinny_ok ? STEP_SKINNY : evalf_ok ? STEP_EVALF : fused_ok ? STEP_FUSED : STEP_GENERAL;
@@ -1204,6 +1208,7 @@ static StepCtx step_ctx(const StepArgs& a) {
   c.backward = a.backward; c.outputs = a.z_out || a.y_out || a.logits_out;
   c.adam_own = a.adam_p && a.adam_p == a.params; c.step_dev = a.step_dev != nullptr;
   c.dp_graph = a.dp_graph; c.imgs_ready = a.imgs_ready; c.gen_noise = !a.eps; c.params = a.params;
+  c.general = a.general;
   return c;
 }
 // the plan of a training step as gmvae_step runs it, from the dims alone (gmvae_step_schedule, the profiles' admission)
@@ -2516,6 +2521,7 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       g.add(p);
       const int bn = cfg_bn(launch_group(cx, g, "fwd_dec_bernoulli"));
       nparts = (D + bn - 1) / bn;
+      cx.nparts = nparts;
     }
   }
   float* tail = a.backward ? a.grads + L.P_pad : a.tail;
@@ -2891,12 +2897,19 @@ static int check_x_align(const GmvaeDims* d, const void* x) { return (x_f32(*d) 
 // ---- the chunked importance-sampling evaluators (gmvae_iw_bound, gmvae_iw_bound_enum_y, gmvae_posterior_y,
 // gmvae_posterior_component): ONE host path.  A kind is a row of kIwKinds, its own workspace regions in iw_lay and its merge
 // (and finishing) launch in iw_run; the dims, the layout, the argument checks and the two chunk loops are shared.
-enum IwKind { IW_BOUND, IW_BOUND_ENUM_Y, IW_POSTERIOR_Y, IW_POSTERIOR_COMPONENT };
+enum IwKind { IW_BOUND, IW_BOUND_ENUM_Y, IW_POSTERIOR_Y, IW_POSTERIOR_COMPONENT, IW_IMPUTE };
 struct IwKindRow {
   int model;        // the one model the kind takes, or -1: all three
   bool enum_y;      // y summed out over K: S K rows per batch row (Philox row ((row0 + b) n + s) K + k), no u
 };
-constexpr IwKindRow kIwKinds[] = {{-1, false}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_VAE_GMP, false}};
+constexpr IwKindRow kIwKinds[] = {{-1, false}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_GMVAE, true}, {GMVAE_MODEL_VAE_GMP, false},
+                                  {-1, false}};
+// gmvae_impute's arguments beyond the evaluators' common ones (out[] = mean, stats, logw)
+struct ImputeOuts {
+  int n_draws;
+  int64_t* draw_index;
+  float* draw_z;
+};
 // bits that mean nothing to an evaluator: no gradient, no labels, no weights, and the operand images are prepared here, once
 // per call.  Masked HERE alone, so the size query and the run carve the workspace from the same dims.
 constexpr unsigned kIwMasked = GMVAE_SCHED_EVAL_IMAGES_VALID | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
@@ -2912,7 +2925,7 @@ static int iw_dims(IwKind kind, const GmvaeDims* dims, int model, GmvaeDims& d) 
   // other kinds refuse it -- masking it off would silently score the unobserved pixels.  Its refusals hold before the other
   // bits are masked off.
   if (int e = check_pmask_dims(dims)) return e;
-  if (pixel_mask(d) && kind != IW_BOUND) return GMVAE_E_DIMS;
+  if (pixel_mask(d) && kind != IW_BOUND && kind != IW_IMPUTE) return GMVAE_E_DIMS;      // (gmvae_impute: the same weights)
   // GMVAE_LIK_* likewise: gmvae_iw_bound honours it (the bound on log p(t) under the likelihood), the other kinds refuse it --
   // masking it off would silently score Bernoulli
   if (int e = check_lik_dims(dims)) return e;
@@ -2936,9 +2949,12 @@ struct IwLay {
   uint64_t pc_state, pc_ess, pc_side, pc_inv, pc_cst; // gmvae_posterior_component: state [B][K][2] fp64, ess [B][3] fp64, side = the
                                                       // chunk's [R][K] component terms (evalf sizes) or its z [R][L] (every other
                                                       // shape), inv [K][L] and cst [K] (gmp_consts, general schedule)
+  uint64_t im_z, im_wgt, im_state, im_factor, im_keys, im_acc, im_bound;      // gmvae_impute (impute.hpp): the chunk's z [R][L] and
+                                                      // weights [R], state [B][8] fp64, factor [B] fp64, the draws' keys [B][M] fp64,
+                                                      // acc [B][pad4(D)] fp64, iw_merge's bound [B]
   uint64_t bytes;
 };
-static void iw_lay(IwKind kind, const GmvaeDims& d, int model, const Layout& L, IwLay& o) {
+static void iw_lay(IwKind kind, const GmvaeDims& d, int model, const Layout& L, IwLay& o, int n_draws = 0) {
   WS w;
   carve(d, model, L, nullptr, w);
   uint64_t off = (w.bytes + 255) / 256 * 256;
@@ -2959,17 +2975,29 @@ static void iw_lay(IwKind kind, const GmvaeDims& d, int model, const Layout& L, 
     o.pc_inv = take(K * Lz * 4);
     o.pc_cst = take(K * 4);
   }
+  if (kind == IW_IMPUTE) {
+    o.im_z = take(R * Lz * 4);
+    o.im_wgt = take(R * 4);
+    o.im_state = take(B * 8 * 8);
+    o.im_factor = take(B * 8);
+    o.im_keys = take(B * (uint64_t)(n_draws > 0 ? n_draws : 1) * 8);
+    o.im_acc = take(B * pad4((uint64_t)d.D) * 8);
+    o.im_bound = take(B * 4);
+  }
   o.bytes = off;
 }
 
-static int iw_workspace_bytes(IwKind kind, const GmvaeDims* dims, int model, uint64_t* bytes) {
+static bool impute_draws_ok(int n_draws) { return n_draws >= 0 && n_draws <= kImputeMaxDraws; }
+
+static int iw_workspace_bytes(IwKind kind, const GmvaeDims* dims, int model, uint64_t* bytes, int n_draws = 0) {
   GmvaeDims d;
   if (int e = iw_dims(kind, dims, model, d)) return e;
+  if (!impute_draws_ok(n_draws)) return GMVAE_E_DIMS;
   if (!bytes) return GMVAE_E_NULL;
   Layout L;
   build_layout(d, model, L);
   IwLay il;
-  iw_lay(kind, d, model, L, il);
+  iw_lay(kind, d, model, L, il, n_draws);
   *bytes = il.bytes;
   return 0;
 }
@@ -2999,6 +3027,7 @@ struct IwCall {
   float* tail;
   void* workspace;
   uint64_t n, nch, seed, step;
+  bool general = false;      // the chunk passes never take the evalf launch (gmvae_impute reads WS::hd[top])
   template <class T> T* at(uint64_t off) const { return reinterpret_cast<T*>(static_cast<char*>(workspace) + off); }
 };
 static StepArgs iw_step_args(const IwCall& c, const float* eps, const float* u, float* tail, float* rows, float* z_out) {
@@ -3016,7 +3045,8 @@ static int iw_general_chunks(Ctx& cx, const IwCall& c, float* z_out, Merge merge
   float* const u = c.model == GMVAE_MODEL_GMVAE && !marginal_y(d) ? c.at<float>(c.il.u) : nullptr;
   StepArgs a = iw_step_args(c, eps, u, c.at<float>(c.il.ftail), c.at<float>(c.il.rows), z_out);
   a.iw_chunk = true;
-  const uint64_t S = d.S, q = noise_items(true, u != nullptr, (uint64_t)d.B * S * per, d.L, d.K);
+  a.general = c.general;
+  const uint64_t S = d.S, q =noise_items(true, u != nullptr, (uint64_t)d.B * S * per, d.L, d.K);
   for (uint64_t i = 0; i < c.nch; ++i) {
     hipLaunchKernelGGL(iw_noise_fill, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, cx.st, eps, u, d.B, d.S * per, d.L, d.K,
                        (unsigned long long)d.row0, (unsigned long long)(c.n * per), (unsigned long long)(i * S * per),
@@ -3057,10 +3087,15 @@ static void iw_evalf_chunks(Ctx& cx, IwCall& c, Extra extra, Launch launch) {
 //   gmp_consts once and iw_merge_comp on the forward's z --, then iw_post_comp_finish
 // and iw_tail on the slots.  out[]: (bound, mean_logw) or (log_joint, log_post, stats).
 static int iw_run(IwKind kind, const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n,
-                  float* const (&out)[3], float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream) {
+                  float* const (&out)[3], float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream,
+                  const ImputeOuts* im = nullptr) {
   IwCall c;
   if (int e = iw_dims(kind, dims, model, c.d)) return e;
+  if (im && !impute_draws_ok(im->n_draws)) return GMVAE_E_DIMS;
   if (int e = iw_check_args(kind, c.d, x, params, n, out, tail, workspace)) return e;
+  if (im && (!aligned16(im->draw_index) || !aligned16(im->draw_z))) return GMVAE_E_ALIGN;
+  // (gmvae_impute: impute_fold's grid is a workgroup per batch row and 64-column tile)
+  if (im && (long long)c.d.B * ((c.d.D + kImputeTile - 1) / kImputeTile) > 0x7fffffffLL) return GMVAE_E_DIMS;
   Ctx cx;
   cx.st = static_cast<hipStream_t>(stream);
   hipStream_t st = cx.st;
@@ -3069,7 +3104,7 @@ static int iw_run(IwKind kind, const GmvaeDims* dims, int model, const uint8_t* 
   c.nch = (n + d.S - 1) / d.S;
   build_layout(d, model, c.L);
   carve(d, model, c.L, workspace, c.w);
-  iw_lay(kind, d, model, c.L, c.il);
+  iw_lay(kind, d, model, c.L, c.il, im ? im->n_draws : 0);
   const IwLay& il = c.il;
   const int B = d.B, S = d.S, K = d.K;
   const bool gm = model == GMVAE_MODEL_GMVAE;
@@ -3153,6 +3188,44 @@ static int iw_run(IwKind kind, const GmvaeDims* dims, int model, const uint8_t* 
       hipLaunchKernelGGL(iw_post_comp_finish, grid4, dim3(256), 0, st, (const double*)state, (const double*)ess,
                          params + c.L.mixlog, B, K, (unsigned long long)n, out[0], out[1], out[2], rsum);
       rowk(cx, "iw_post_comp_finish");
+      break;
+    }
+    case IW_IMPUTE: {
+      // gmvae_iw_bound's general loop (the same rows, so iw_merge gives the same bound) with the chunk's z kept; behind every
+      // forward impute_merge and impute_fold read what it left in the workspace: rows, z, hpart and the decoder's top activation
+      // WS::hd[top] [R][H] -- written post-activation for all R rows by whichever launch ran that layer (rows_ws, rows_nn_bf6 or
+      // the grouped GEMM: each stores to w.hd[i + 1] with the ReLU / activation epilogue).  Without a hidden layer the output
+      // layer reads z itself.
+      const NetL& Dn = c.L.dec;
+      const int top = Dn.nl - 1;
+      float* const zs = c.at<float>(il.im_z);
+      c.general = true;
+      ma.iw_bound = c.at<float>(il.im_bound); ma.iw_mlw = nullptr;
+      ImputeArgs ia;
+      memset(&ia, 0, sizeof(ia));
+      ia.B = B; ia.S = S; ia.D = d.D; ia.H = Dn.dim[top]; ia.L = d.L; ia.K = K; ia.M = im->n_draws;
+      ia.n = n; ia.row0 = d.row0; ia.seed = seed; ia.step = step;
+      ia.rows_ws = rows; ia.hpart = pixel_mask(d) ? c.w.hpart : nullptr; ia.mcnt = pixel_mask(d) ? c.w.mcnt : nullptr;
+      ia.z = zs; ia.h = top == 0 ? zs : c.w.hd[top];
+      ia.W = params + Dn.w[top]; ia.bias = params + Dn.b[top]; ia.bias2 = d.gen_bias_vec; ia.bias_const = d.gen_bias_init;
+      ia.state = c.at<double>(il.im_state); ia.keys = c.at<double>(il.im_keys); ia.wgt = c.at<float>(il.im_wgt);
+      ia.factor = c.at<double>(il.im_factor); ia.acc = c.at<double>(il.im_acc); ia.bound = ma.iw_bound;
+      ia.mean_out = out[0]; ia.stats_out = out[1]; ia.logw_out = out[2]; ia.draw_z_out = im->draw_z; ia.slots = rsum;
+      ia.draw_index_out = reinterpret_cast<long long*>(im->draw_index);
+      auto ran = [&](int e, const char* name) {
+        if (!cx.err) cx.err = e;
+        cx.mark(name, 0);
+      };
+      if (int e = iw_general_chunks(cx, c, zs, [&](uint64_t s0, bool last) {
+            ma.iw_s0 = s0; ma.iw_final = last;
+            hipLaunchKernelGGL(iw_merge, grid4, dim3(256), 0, st, ma);
+            rowk(cx, "iw_merge");
+            ia.s0 = s0; ia.nparts = cx.nparts;
+            ran(impute_launch_merge(st, ia), "impute_merge");
+            ran(impute_launch_fold(st, ia), "impute_fold");
+          }))
+        return e;
+      ran(impute_launch_finish(st, ia), "impute_finish");      // (its slots: (-bound, ESS, cond_loglik, missing) for iw_tail)
       break;
     }
   }
@@ -3299,6 +3372,18 @@ int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x
                               uint64_t seed, uint64_t step, void* stream) {
   return iw_run(IW_POSTERIOR_COMPONENT, dims, model, x, params, n_samples, {log_joint_out, log_post_out, stats_out}, tail,
                 workspace, seed, step, stream);
+}
+
+int gmvae_impute_workspace_bytes(const GmvaeDims* dims, int model, int n_draws, uint64_t* bytes) {
+  return iw_workspace_bytes(IW_IMPUTE, dims, model, bytes, n_draws);
+}
+
+int gmvae_impute(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples, int n_draws,
+                 float* mean_out, float* stats_out, float* logw_out, int64_t* draw_index_out, float* draw_z_out, float* tail,
+                 void* workspace, uint64_t seed, uint64_t step, void* stream) {
+  const ImputeOuts im = {n_draws, draw_index_out, draw_z_out};
+  return iw_run(IW_IMPUTE, dims, model, x, params, n_samples, {mean_out, stats_out, logw_out}, tail, workspace, seed, step, stream,
+                &im);
 }
 
 // gmvae_mixture_logpdf_*: csrc/aggpost.hpp.  Workspace: the running states [E], E = ap_states(M, L, per_dim), then the slices'

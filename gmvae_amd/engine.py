@@ -136,6 +136,30 @@ def check_likelihood(model, y_inference, grad_estimator, semi_supervised, weight
     return sigma
 
 
+IMPUTE_MAX_DRAWS = 16
+
+
+def check_impute_args(model, y_inference, likelihood, pixel_mask, n_samples, n_draws=0, has_mask=False):
+    """The argument check of Engine.impute_posterior (no device needed): the library's refusals of gmvae_impute.  Returns
+    (n_samples, n_draws) as ints."""
+    if L.MODEL_IDS.get(model) == L.MODEL_GMVAE and y_inference != "gumbel":
+        raise ValueError(f"impute_posterior is not available with y_inference={y_inference!r} (its weights are the Gumbel "
+                         "objective's, as iw_bound's)")
+    if likelihood != "bernoulli":
+        raise ValueError(f"impute_posterior is not available with likelihood={likelihood!r} (it imputes Bernoulli pixels)")
+    try:
+        n, m = int(n_samples), int(n_draws)
+    except (TypeError, ValueError):
+        raise ValueError(f"n_samples and n_draws must be integers, got {n_samples!r}, {n_draws!r}") from None
+    if n < 1:
+        raise ValueError(f"n_samples must be >= 1, got {n}")
+    if not 0 <= m <= IMPUTE_MAX_DRAWS:
+        raise ValueError(f"n_draws must be in 0 .. {IMPUTE_MAX_DRAWS}, got {m}")
+    if has_mask and not pixel_mask:
+        raise ValueError("impute_posterior(mask=) needs an engine created with pixel_mask=True")
+    return n, m
+
+
 LIKELIHOOD_SCALES = ("fixed", "learned")
 
 
@@ -789,12 +813,14 @@ class Engine:
     # kind -> (y enumerated: K rows per sample in the default chunk; outputs per component: log_joint [B, K], log_post [B, K]
     # and stats [B, 4] in place of bound [B] and mean_logw [B])
     _CHUNKED = {"iw_bound": (False, False), "iw_bound_enum_y": (True, False), "posterior_y": (True, True),
-                "posterior_component": (False, True)}
+                "posterior_component": (False, True), "impute": (False, False)}
 
-    def _chunked_eval(self, kind: str, x, n_samples: int, chunk: Optional[int], row0: Optional[int], mask=None):
-        """One call of a chunked evaluator: (its output tensors in the order of the C signature, tail [8])."""
+    def _chunked_eval(self, kind: str, x, n_samples: int, chunk: Optional[int], row0: Optional[int], mask=None,
+                      n_draws: int = 0, return_logw: bool = False):
+        """One call of a chunked evaluator: (its output tensors in the order of the C signature, tail [8]).  kind "impute"
+        (gmvae_impute) takes n_draws and return_logw too; an output it was not asked for is None."""
         enum_y, per_component = self._CHUNKED[kind]
-        if self.pixel_mask and kind != "iw_bound":
+        if self.pixel_mask and kind not in ("iw_bound", "impute"):
             raise ValueError(f"{kind} is not available with pixel_mask=True (it would score the unobserved pixels): use iw_bound")
         if self.likelihood != "bernoulli" and kind != "iw_bound":
             raise ValueError(f"{kind} is not available with likelihood={self.likelihood!r} (it would score Bernoulli): use iw_bound")
@@ -809,14 +835,27 @@ class Engine:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
         d = self.dims(B, chunk, row0)
         d.sched_flags &= ~_EVAL_MASKED      # (as the library's iw_dims does: the same size query, the same run)
-        ws, fresh = self._cached_ws((kind, B, chunk), getattr(L, f"{kind}_workspace_bytes")(d, self.model) // 4 + 64)
+        if kind == "impute":
+            key, nbytes = (kind, B, chunk, n_draws), L.impute_workspace_bytes(d, self.model, n_draws)
+        else:
+            key, nbytes = (kind, B, chunk), getattr(L, f"{kind}_workspace_bytes")(d, self.model)
+        ws, fresh = self._cached_ws(key, nbytes // 4 + 64)
         if fresh:
-            self._bind_sigma((kind, B, chunk), d, ws)      # (the forward's workspace opens the evaluator's: the same offsets)
+            self._bind_sigma(key, d, ws)      # (the forward's workspace opens the evaluator's: the same offsets)
         self._bind_step_inputs(d, ws, mask=mask)      # (the forward's workspace opens the evaluator's: the same offsets)
         f32 = dict(dtype=torch.float32, device=self.device)
         shapes = ((B, self.K), (B, self.K), (B, 4)) if per_component else ((B,), (B,))
         outs = [torch.empty(*shape, **f32) for shape in shapes]
         tail = torch.empty(L.TAIL, **f32)
+        if kind == "impute":
+            outs = [torch.empty(B, self.D, **f32), torch.empty(B, 4, **f32), torch.empty(B, n, **f32) if return_logw else None,
+                    torch.empty(B, n_draws, dtype=torch.int64, device=self.device) if n_draws else None,
+                    torch.empty(B, n_draws, self.Lz, **f32) if n_draws else None]
+            rc = L.lib.gmvae_impute(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, n_draws, *map(L.ptr, outs),
+                                    L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step, L.current_stream())
+            L.check(rc, "gmvae_impute")
+            self._keep_iw = x
+            return outs, tail
         rc = getattr(L.lib, f"gmvae_{kind}")(C.byref(d), self.model, L.ptr(x), L.ptr(self.params), n, *map(L.ptr, outs),
                                              L.ptr(tail), L.ptr(ws), self.noise_seed, self.global_step, L.current_stream())
         L.check(rc, f"gmvae_{kind}")
@@ -836,6 +875,26 @@ class Engine:
                              "(it is the Gumbel objective's bound)")
         (bound, mean_logw), tail = self._chunked_eval("iw_bound", x, n_samples, chunk, row0, mask)
         return dict(bound=bound, mean_logw=mean_logw, tail=tail)
+
+    def impute_posterior(self, x, n_samples: int, mask: Optional[torch.Tensor] = None, n_draws: int = 0,
+                         chunk: Optional[int] = None, row0: Optional[int] = None, return_logw: bool = False):
+        """The missing pixels imputed by self-normalised importance sampling on iw_bound's weights (Mattei & Frellsen, MIWAE,
+        2019; include/gmvae_hip.h gmvae_impute): dict(mean [B, D] = sum_s w~_s sigmoid(lambda_s) ~ E[x | x_observed] at every
+        pixel, imputed = where(mask, x, mean), bound [B] -- iw_bound's --, ess [B], cond_loglik [B] ~ log p(x_missing |
+        x_observed) at the x given (0 for a row with nothing missing), max_weight [B], draw_index [B, n_draws] (int64) and
+        draw_z [B, n_draws, L] -- sampling-importance-resampling draws of z, None at n_draws = 0 --, logw [B, n_samples] with
+        return_logw (else None), tail [8] = the batch sums of (-bound, ess, cond_loglik, missing pixels), B).  mask
+        (pixel_mask=True): non-zero = observed; None: every pixel observed, the posterior-mean reconstruction.  chunk, row0 and
+        the noise keying as iw_bound: the result does not depend on the chunk, the batch size or the sharding."""
+        n, m = check_impute_args(self.model_name, self.y_inference, self.likelihood, self.pixel_mask, n_samples, n_draws,
+                                 mask is not None)
+        (mean, stats, logw, di, dz), tail = self._chunked_eval("impute", x, n, chunk, row0, mask, n_draws=m,
+                                                               return_logw=return_logw)
+        xs = self._keep_iw.reshape(mean.shape)
+        imputed = mean if mask is None else torch.where(_check_mask(self, mask, mean.shape[0]).reshape(mean.shape),
+                                                        xs.to(mean.dtype), mean)
+        return dict(mean=mean, imputed=imputed, bound=stats[:, 0], ess=stats[:, 1], cond_loglik=stats[:, 2],
+                    max_weight=stats[:, 3], draw_index=di, draw_z=dz, logw=logw, tail=tail)
 
     def iw_bound_enum_y(self, x, n_samples: int, chunk: Optional[int] = None, row0: Optional[int] = None):
         """The GMVAE's importance-weighted bound with y summed out exactly over its K components, streamed in chunks

@@ -126,6 +126,11 @@ def build_parser():
       "missing independently with this probability -- ONE fixed mask per row, the same in train and eval; the loss, the "
       "gradients and --iw_samples count the observed pixels alone, the missing ones are scored as imputation_nll (0 = off)")
     a("--missing_seed", type=int, default=0, help="seed of --missing_rate's masks")
+    a("--impute_samples", type=int, default=0, help="eval with --missing_rate: impute the missing pixels by importance sampling "
+      "at this many samples per example (Mattei & Frellsen 2019) and report imputation_nll_is, imputation_error_rate_is, "
+      "imputation_cond_loglik and imputation_ess next to the one-draw imputation_nll (0 = off)")
+    a("--impute_draws", type=int, default=0, help="with --impute_samples: also draw this many multiple imputations per example "
+      "by sampling-importance-resampling (0 .. 16) and report the share of distinct draws")
     a("--clip_norm", type=float, default=0.0, help="train: clip the batch-mean gradient by its global norm to this threshold "
       "in front of Adam and skip the steps whose gradient or loss is not finite; the log reports the norm's mean and maximum "
       "and the clipped and skipped shares per summary window (inf: report only; 0 = off)")
@@ -295,6 +300,12 @@ def check_args(p, cfg):
         if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
             p.error("--missing_rate is not available with --iw_enum_samples, --posterior_samples or "
                     "--component_posterior_samples (they would score the unobserved pixels): use --iw_samples")
+    if cfg.impute_samples < 0 or not 0 <= cfg.impute_draws <= 16:
+        p.error("--impute_samples must be >= 0 and --impute_draws in 0 .. 16")
+    if cfg.impute_draws and not cfg.impute_samples:
+        p.error("--impute_draws needs --impute_samples")
+    if cfg.impute_samples and not (cfg.mode == "eval" and cfg.missing_rate > 0):
+        p.error("--impute_samples needs --mode=eval and --missing_rate > 0")
     if not (cfg.likelihood_sigma > 0 and cfg.likelihood_sigma < float("inf")):
         p.error("--likelihood_sigma must be a finite number > 0")
     if cfg.likelihood != "bernoulli":

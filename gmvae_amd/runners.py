@@ -711,6 +711,11 @@ def run_eval(config):
     py_n, py_rows, py_stats, py_logits = int(getattr(config, "posterior_samples", 0) or 0), [], [], []
     # --component_posterior_samples N: the VAE_GMP's posterior p(k|x) over the components of its mixture prior, keyed alike
     pc_n, pc_rows, pc_stats = int(getattr(config, "component_posterior_samples", 0) or 0), [], []
+    # --impute_samples N [--impute_draws M] (with --missing_rate): the missing pixels imputed by importance sampling
+    # (Engine.impute_posterior), keyed alike; the sums over this rank's examples of (cross-entropy and wrong roundings at the
+    # missing pixels, missing pixels, cond_loglik, ESS, distinct draws per example, examples)
+    im_n, im_m = int(getattr(config, "impute_samples", 0) or 0), int(getattr(config, "impute_draws", 0) or 0)
+    im_tot = torch.zeros(7, dtype=torch.float64, device=eng.device)
     q_logits = []                                           # --real_valued, gmvae: q(y|x)'s logits over the split, for cluster_acc_q
     # --latent_diagnostics N: the first N examples of the split, as the aggregate posterior's components and as its queries
     ld_n, ld_imgs = int(getattr(config, "latent_diagnostics", 0) or 0), []
@@ -746,6 +751,19 @@ def run_eval(config):
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
         if ie_n > 0:
             ie_rows.append(eng.iw_bound_enum_y(images, ie_n, chunk=iw_chunk, row0=first)["bound"])
+        if im_n > 0 and mk is not None:
+            io = eng.impute_posterior(images, im_n, mask=mk, n_draws=im_m, chunk=iw_chunk, row0=first)
+            t = (images.reshape(io["mean"].shape).to(eng.device) != 0).double()
+            ph = io["mean"].double().clamp(1e-12, 1.0 - 1e-12)
+            miss = (mk.to(eng.device) == 0).double()
+            distinct = torch.zeros((), dtype=torch.float64, device=eng.device)
+            if im_m > 0:
+                srt = io["draw_index"].sort(dim=1).values
+                distinct = (1 + (srt[:, 1:] != srt[:, :-1]).sum(dim=1)).double().sum()
+            im_tot += torch.stack([-(miss * (t * ph.log() + (1.0 - t) * (-ph).log1p())).sum(),
+                                   (miss * ((ph >= 0.5).double() != t).double()).sum(), miss.sum(),
+                                   io["cond_loglik"].double().sum(), io["ess"].double().sum(), distinct,
+                                   torch.tensor(float(t.shape[0]), dtype=torch.float64, device=eng.device)])
         if ais_c > 0:
             ais_rows.append(eng.ais_bound(images, ais_c, ais_t, schedule=getattr(config, "ais_schedule", "sigmoid"),
                                           n_leapfrog=int(getattr(config, "ais_leapfrog", 10)),
@@ -816,6 +834,8 @@ def run_eval(config):
         parallel.all_reduce_flat(iw_sum)
         parallel.all_reduce_flat(class_hits)
         parallel.all_reduce_flat(pm_tot)
+        if im_n > 0:
+            parallel.all_reduce_flat(im_tot)
         if ie_n > 0:
             parallel.all_reduce_flat(ie_sum)
         if py_n > 0:
@@ -835,6 +855,16 @@ def run_eval(config):
         if pm_tot[1].item() > 0:
             res[f"{config.split}/imputation_nll"] = pm_tot[0].item() / pm_tot[1].item()
         res[f"{config.split}/observed_share"] = pm_tot[2].item() / (pm_tot[1].item() + pm_tot[2].item())
+        if im_n > 0:
+            # the same held-out pixels scored under the importance-sampling imputation p^ at im_n samples; cond_loglik per
+            # example is the proper score log p^(x_missing | x_observed), ESS the effective number of the im_n samples
+            it = im_tot.tolist()
+            res[f"{config.split}/imputation_nll_is"] = it[0] / max(it[2], 1.0)
+            res[f"{config.split}/imputation_error_rate_is"] = it[1] / max(it[2], 1.0)
+            res[f"{config.split}/imputation_cond_loglik"] = it[3] / max(it[6], 1.0)
+            res[f"{config.split}/imputation_ess"] = it[4] / max(it[6], 1.0)
+            if im_m > 0:
+                res[f"{config.split}/imputation_distinct_draws"] = it[5] / max(it[6], 1.0) / im_m
     if eng.likelihood != "bernoulli":
         # the per-pixel squared error of the mean image A'(lambda) against t = pixel / 255 (tail[5] / tail[6] over the split)
         res[f"{config.split}/recon_mse"] = pm_tot[0].item() / max(pm_tot[1].item(), 1.0)

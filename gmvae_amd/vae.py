@@ -42,11 +42,21 @@ class VAE:
             z = self.generate_samples(num_samples)
         return self.decoder(z).mean(name="sample_images")
 
-    def impute(self, images, mask):
+    def impute(self, images, mask, n_samples=None, n_draws=0, seed=None):
         """Fills in the missing pixels: mask * images + (1 - mask) * reconstruct_images(mask * images) -- the observed pixels
         exactly as given, the others the decoder's mean from the zero-imputed input the networks were trained on (a model
-        created with pixel_mask=True).  A float tensor of the images' shape."""
-        return base.impute(self, images, mask)
+        created with pixel_mask=True).  A float tensor of the images' shape.
+        n_samples = N: the missing pixels are the importance-sampling estimate of E[x_missing | x_observed] at N samples
+        (Engine.impute_posterior) in place of one draw's decoder mean; with n_draws = M > 0, M completed images [B, M, ...]
+        (uint8) by sampling-importance-resampling, the Bernoulli draws seeded by `seed` (base.impute_posterior)."""
+        if n_samples is None:
+            return base.impute(self, images, mask)
+        return base.impute_posterior(self, images, mask, n_samples, n_draws, seed)
+
+    def imputation_scores(self, images, mask, n_samples):
+        """The importance-sampling imputation scored against the truth in `images` at the missing pixels: dict(nll,
+        error_rate, cond_loglik, ess, n_missing) (base.imputation_scores)."""
+        return base.imputation_scores(self, images, mask, n_samples)
 
     def transform(self, inputs):
         """MEAN latent code (scripts/vae.py:108-114)."""

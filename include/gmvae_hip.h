@@ -569,6 +569,40 @@ int gmvae_posterior_component(const GmvaeDims* dims, int model, const uint8_t* x
                               float* log_joint_out, float* log_post_out, float* stats_out, float* tail, void* workspace,
                               uint64_t seed, uint64_t step, void* stream);
 
+/* Imputation of the missing pixels by self-normalised importance sampling (Mattei & Frellsen, MIWAE, 2019) on gmvae_iw_bound's
+ * own weights: the same samples (Philox rows (row0 + b) n + s, chunks of dims->S samples, limits and error codes), the same
+ * log w_bs -- under GMVAE_OBJ_PIXEL_MASK from the observed pixels alone, the mask read from slot 0; without the bit every pixel
+ * is observed and the result is the posterior-mean reconstruction.  With w~_bs = softmax_s log w_bs, lambda_bs the decoder's
+ * logits at z_bs (gen_bias_init included, scalar or vector) and hid_bs the held-out Bernoulli term (GMVAE_OBJ_PIXEL_MASK above):
+ *   mean_out [B][D] (may be NULL): p^_bd = sum_s w~_bs sigmoid(lambda_bsd) ~ E[x_d | x_observed], at EVERY pixel, observed or not;
+ *   stats_out [B][4] (may be NULL): [0] bound_b = logsumexp_s log w_bs - log n, gmvae_iw_bound's bound bit for bit;
+ *     [1] ESS_b = (sum_s w_bs)^2 / sum_s w_bs^2, in [1, n]; [2] cond_loglik_b = logsumexp_s (log w_bs + hid_bs) -
+ *     logsumexp_s log w_bs ~ log p(x_missing | x_observed) at the x given (the proper score of an imputation; exactly 0 for a
+ *     row with nothing missing; x at a missing pixel is read by this output alone); [3] max_s w~_bs;
+ *   logw_out [B][n] (may be NULL): log w_bs -- the one output whose size follows n;
+ *   draw_index_out [B][M] int64 and draw_z_out [B][M][L] (each may be NULL; M = n_draws in 0 .. 16): sampling-importance-
+ *     resampling by the Gumbel-max rule, draw m keeps s* = argmax_s (log w_bs + g_bsm), g = -ln(-ln u), u = column
+ *     4 ceil(K / 4) + m of the u stream of sample s's Philox row (behind the columns the forward itself may read); ties go to
+ *     the lower s; draw_z is that sample's z: decoding it and drawing the missing pixels gives one multiple imputation;
+ *   tail [GMVAE_TAIL]: [0] sum_b -bound_b, [1] sum_b ESS_b, [2] sum_b cond_loglik_b, [3] sum_b of the missing pixels, [4] B, [5..7] 0.
+ * A weight of exactly 0 (log w = -inf) contributes nothing and makes no NaN; a row whose weights are all 0, or that holds a NaN,
+ * gives NaN in mean_out and stats_out[1..3].  Every size takes the general chunk passes (never the one-launch evaluation: the
+ * decoder's top activation is read back from the workspace); per chunk the strided noise fill, the forward, iw_merge, then
+ * impute_merge (a wave per row: the fp64 fold of the weights, the draws' reservoirs) and impute_fold (csrc/impute.hip: the output
+ * layer recomputed as fp32 MFMA products against a 64-column tile of its weights held in LDS, sigmoid and the weighted sum over the
+ * chunk's samples in the epilogue, fp64 accumulators [B][pad4(D)] in the workspace -- the [B n D] mean images are never stored);
+ * then impute_finish and the tail.  One owner per output, fixed-order reductions, no float atomics: two calls give the same bits;
+ * the result does not depend on the chunk, the batch or the sharding beyond the forward's own summation order and the fp64
+ * rounding of the folds.  The workspace (its size from gmvae_impute_workspace_bytes at the same dims and n_draws; zeroed once) is
+ * gmvae_iw_bound's plus the chunk's z and weights, the per-row state and the accumulators.
+ * GMVAE_E_DIMS for a GMVAE_LIK_* other than Bernoulli, GMVAE_OBJ_MARGINAL_Y*, n_draws outside 0 .. 16, n_samples == 0 or
+ * (row0 + B) * n_samples >= 2^38; GMVAE_E_ALIGN for unaligned x, params, outputs or workspace; GMVAE_E_NULL for a missing x,
+ * params, tail or workspace.  Every check happens before any launch. */
+int gmvae_impute_workspace_bytes(const GmvaeDims* dims, int model, int n_draws, uint64_t* bytes);
+int gmvae_impute(const GmvaeDims* dims, int model, const uint8_t* x, const float* params, uint64_t n_samples, int n_draws,
+                 float* mean_out, float* stats_out, float* logw_out, int64_t* draw_index_out, float* draw_z_out,
+                 float* tail, void* workspace, uint64_t seed, uint64_t step, void* stream);
+
 /* The log-density of a weighted diagonal-Gaussian mixture at M query points, streamed over chunks of components (model
  * independent; Engine.aggregate_posterior runs the aggregate posterior q(z) = 1/N sum_n q(z|x_n) and the mixture priors through
  * it).  Components c < C of a chunk: logw [C] (finite or -inf: a -inf component contributes nothing and yields no NaN), mu [C][L],
