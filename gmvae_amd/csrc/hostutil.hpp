@@ -1,8 +1,13 @@
-// What the host sides of the translation units (gmvae_hip.hip, tsne.hip, mixfit.hip, neigh.hip, ais.hip) share: pointer alignment
-// (a null pointer is aligned), the workspaces' 256-byte rounding, and the once-per-device guard.
+// What the host sides of the translation units (gmvae_hip.hip, tsne.hip, mixfit.hip, neigh.hip, ais.hip, linprobe.hip) share: pointer
+// alignment (a null pointer is aligned), the workspaces' 256-byte rounding, the once-per-device guard, and the evaluators' pointer
+// ladder and LDS attribute.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <initializer_list>
+
+#include "../../include/gmvae_hip.h"
 
 namespace gmvae {
 
@@ -17,6 +22,26 @@ inline bool first_on_device(bool (&seen)[64]) {
   if (seen[dev]) return false;
   seen[dev] = true;
   return true;
+}
+
+// The pointer ladder of the model-independent evaluators (mixfit.hip, linprobe.hip), in the header's order -- NULL, then alignment:
+// `required` may not be NULL; they and the `optional` outputs are 4-byte aligned, the workspace (required too) 16
+typedef std::initializer_list<const void*> Pointers;
+inline int check_pointers(Pointers required, Pointers optional, const void* workspace) {
+  for (const void* p : required)
+    if (!p) return GMVAE_E_NULL;
+  if (!workspace) return GMVAE_E_NULL;
+  for (const void* p : required)
+    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
+  for (const void* p : optional)
+    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
+  return aligned_to(workspace, 16) ? 0 : GMVAE_E_ALIGN;
+}
+
+// one-shot per DEVICE (`seen` is the caller's table): these kernels may ask for up to `bytes` of dynamic LDS, past the 64 KiB default
+inline void allow_lds(bool (&seen)[64], Pointers kernels, int bytes) {
+  if (!first_on_device(seen)) return;
+  for (const void* k : kernels) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 }  // namespace gmvae

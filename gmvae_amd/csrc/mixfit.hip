@@ -1,13 +1,11 @@
 // gmvae_mixfit_* and gmvae_mixfit_full_*: the host side of csrc/mixfit.hpp and csrc/mixfit_full.hpp (include/gmvae_hip.h).  A translation unit of its own, for the reason at the top
 // of csrc/tsne.hip: the model-independent evaluator's kernels, descriptors and symbols stay out of the training step's code object.
-// What the two fits' entry points share stands once, at the top: the N and K gate, the n_iter / reg_covar check, the pointer and
-// alignment ladder, the once-per-device LDS attribute and the iteration loop's optional outputs.  Each fit's own L and product
-// gate, workspace layout and launches stay beside its plan.
+// What the two fits' entry points share stands once, at the top: the N and K gate, the n_iter / reg_covar check and the iteration
+// loop's optional outputs; the pointer and alignment ladder and the once-per-device LDS attribute are csrc/hostutil.hpp's.  Each
+// fit's own L and product gate, workspace layout and launches stay beside its plan.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-
-#include <initializer_list>
 
 #include "../../include/gmvae_hip.h"
 #include "hostutil.hpp"
@@ -18,32 +16,12 @@ using namespace gmvae;
 
 namespace {
 
-typedef std::initializer_list<const void*> Pointers;
-
 // the checks, in the header's order: sizes -- the gate on N and K here, each fit's L and product next to it --, then n_iter and
 // reg_covar (run), then NULL, then alignment
 bool nk_in_gate(int64_t N, int K) { return N >= 1 && N <= (1ll << 24) && K >= 1 && K <= 256; }
 
 int check_iterations(int n_iter, float reg_covar) {
   return (n_iter < 0 || !(reg_covar > 0.f) || !isfinite(reg_covar)) ? GMVAE_E_DIMS : 0;
-}
-
-// `required` may not be NULL; they and the `optional` outputs are 4-byte aligned, the workspace (required too) 16
-int check_pointers(Pointers required, Pointers optional, const void* workspace) {
-  for (const void* p : required)
-    if (!p) return GMVAE_E_NULL;
-  if (!workspace) return GMVAE_E_NULL;
-  for (const void* p : required)
-    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
-  for (const void* p : optional)
-    if (!aligned_to(p, 4)) return GMVAE_E_ALIGN;
-  return aligned_to(workspace, 16) ? 0 : GMVAE_E_ALIGN;
-}
-
-// one-shot per DEVICE (`seen` is the caller's table): these kernels may ask for more than 64 KiB of dynamic LDS
-void allow_lds(bool (&seen)[64], Pointers kernels) {
-  if (!first_on_device(seen)) return;
-  for (const void* k : kernels) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMfLdsBytes);
 }
 
 // n_iter times iteration(it, history slot `it` or NULL, counts_out on the last iteration or NULL)
@@ -64,7 +42,7 @@ uint64_t mf_workspace_bytes(const MfPlan& p) { return ((uint64_t)p.groups * (uin
 
 void mf_allow_lds() {
   static bool seen[64];
-  allow_lds(seen, {reinterpret_cast<const void*>(mixfit_pass<true>), reinterpret_cast<const void*>(mixfit_pass<false>)});
+  allow_lds(seen, {reinterpret_cast<const void*>(mixfit_pass<true>), reinterpret_cast<const void*>(mixfit_pass<false>)}, kMfLdsBytes);
 }
 
 // ------------------------------------------------------------------------------------------------ full covariances
@@ -81,7 +59,7 @@ uint64_t mff_workspace_bytes(const MffPlan& p, int L, int K) {
 void mff_allow_lds() {
   static bool seen[64];
   allow_lds(seen, {reinterpret_cast<const void*>(mixfit_full_factor), reinterpret_cast<const void*>(mixfit_full_pass<true>),
-                   reinterpret_cast<const void*>(mixfit_full_pass<false>)});
+                   reinterpret_cast<const void*>(mixfit_full_pass<false>)}, kMfLdsBytes);
 }
 
 }  // namespace

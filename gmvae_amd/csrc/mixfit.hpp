@@ -33,7 +33,8 @@
 // and writes mu and sigma in place; one more block folds R_k for every k and sum lse, and writes logw, counts_out and the history
 // entry.  One owner per sum, fixed-order folds, no float atomics: two runs give the same bits.
 // Shared with the full-covariance fit (csrc/mixfit_full.hpp): the plan's tail (mf_plan_groups), MF_ADVANCE, mf_wave_sum, the fold
-// (mf_fold_run) and the update's last block (mf_update_weights, which takes the offset of R_k in a workgroup's partials as an
+// (mf_fold_run) -- these in csrc/mixfit_common.hpp, where csrc/linprobe.hpp, another translation unit that may not see this file's
+// kernels defined a second time, shares them too -- and the update's last block (mf_update_weights, which takes the offset of R_k in a workgroup's partials as an
 // int), with kMfBlock, kMfMaxGroups, kMfLdsBytes and the fold's shape.  The E-step's tail -- stage, rows, the tile's sum of lse,
 // sweep -- is NOT shared: as forceinline helpers it compiled to the same instructions in another schedule, and one pass or the
 // other then ran 1 to 5 % slower on the MI355X (profiles/mixfit_notes.md), so mixfit_pass and mixfit_full_pass each keep their
@@ -43,33 +44,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mixfit_common.hpp"
+
 namespace gmvae {
 
-constexpr int kMfBlock = 256;             // threads of a workgroup
-constexpr int kMfMaxTile = 128;           // rows per tile at most (one thread per row in the row step)
-constexpr int kMfMaxGroups = 256;         // workgroups of a pass at most: one per CU
-constexpr int kMfLdsBytes = 160 * 1024;   // the LDS of a CU
-constexpr int kMfMaxKL = 16384;           // the K L gate: the parameter image is then 128 KiB
-constexpr int kMfFoldSlots = 16;          // mixfit_update: slots per block
-constexpr int kMfFoldParts = 16;          // ... and threads per slot
-constexpr double kMfEps0 = 10.0 * 2.220446049250313e-16;      // scikit-learn's 10 * finfo(float64).eps
-
-// the pass's shape for (N, L, K): rows per tile, rows per workgroup (whole tiles), workgroups, LDS bytes, doubles per workgroup's partials
-struct MfPlan {
-  int tile, per_group, groups, stride;
-  size_t lds;
-};
 static inline size_t mf_lds_bytes(int L, int K, int T) {
   const size_t Lp = (size_t)(L | 1), Kp = (size_t)(K | 1);
   return 8 * (3 * (size_t)T + (size_t)T * Kp + (size_t)K) + 4 * (2 * (size_t)K * Lp + (size_t)T * Lp);
-}
-// the tail of a plan: N rows in tiles of T -> whole tiles per workgroup -> workgroups, gmax of them at most
-static inline void mf_plan_groups(MfPlan& p, int64_t N, int64_t T, int64_t gmax) {
-  const int64_t tiles = (N + T - 1) / T, g = tiles < gmax ? tiles : gmax;
-  const int64_t per = (tiles + g - 1) / g * T;
-  p.tile = (int)T;
-  p.per_group = (int)per;
-  p.groups = (int)((N + per - 1) / per);
 }
 static inline MfPlan mf_plan(int64_t N, int L, int K) {
   MfPlan p;
@@ -82,23 +63,6 @@ static inline MfPlan mf_plan(int64_t N, int L, int K) {
   p.lds = mf_lds_bytes(L, K, (int)T);
   return p;
 }
-
-__device__ __forceinline__ double mf_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);      // (a + b == b + a: every lane ends with the same bits)
-  return v;
-}
-
-// (q, r) of item i by `den` -> those of item i + kMfBlock
-#define MF_ADVANCE(q, r, step_q, step_r, den) \
-  do {                                        \
-    q += step_q;                              \
-    r += step_r;                              \
-    if (r >= den) {                           \
-      r -= den;                               \
-      q += 1;                                 \
-    }                                         \
-  } while (0)
 
 template <bool kAccum>
 __global__ __launch_bounds__(kMfBlock) void mixfit_pass(const float* __restrict__ codes, const int N, const int L, const int K,
@@ -237,15 +201,6 @@ __global__ __launch_bounds__(kMfBlock) void mixfit_pass(const float* __restrict_
     }
   }
   if (kAccum && tid == 0) gpart[2 * KL + K] = lse_acc;
-}
-
-// this thread's run of the G workgroups' values at offset `off`, added in order
-__device__ __forceinline__ double mf_fold_run(const double* __restrict__ part, const int G, const int stride, const size_t off,
-                                              const int p) {
-  const int run = (G + kMfFoldParts - 1) / kMfFoldParts, g0 = p * run, g1 = g0 + run < G ? g0 + run : G;
-  double a = 0.0;
-  for (int g = g0; g < g1; ++g) a += part[(size_t)g * stride + off];
-  return a;
 }
 
 // the update's last block: folds R_k for every k (offset offR + k of a workgroup's partials) and sum lse (offR + K), and writes

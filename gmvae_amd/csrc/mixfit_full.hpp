@@ -61,10 +61,6 @@ constexpr int kMffMaxL = 128;                      // the factor kernel holds 2 
 constexpr int kMffMaxKLL = 1 << 20;                // the K L^2 gate
 constexpr int64_t kMffMaxPart = 1ll << 23;         // doubles of partial sums at most (64 MiB): bounds the number of row slices
 
-typedef double mff_d4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ static inline int mff_tri(int i) { return i * (i + 1) / 2; }
-
 // the pass's shape for (N, L, K): rows per tile, rows per workgroup (whole tiles), workgroups, doubles per workgroup's partials,
 // LDS bytes of the pass and of the factor kernel
 struct MffPlan : MfPlan {
@@ -108,32 +104,8 @@ __global__ __launch_bounds__(kMfBlock) void mixfit_full_factor(const float* __re
     }
   }
   __syncthreads();
-  const int ti = tid >> 4, tj = tid & 15;
-  int info = 0;
-  double sl = 0.0;
-  for (int t = 0; t < L; ++t) {
-    const double p = a[mff_tri(t) + t];      // (nobody writes a_tt in step t: every thread takes the same branch)
-    if (!(p > 0.0)) {
-      info = t + 1;
-      break;
-    }
-    const double c = sqrt(p);
-    sl += log(c);
-    if (tid < L - t - 1) {
-      a[mff_tri(t + 1 + tid) + t] /= c;
-    } else if (tid < L) {
-      x[mff_tri(t) + tid - (L - t - 1)] /= c;
-    }
-    __syncthreads();
-    for (int i = t + 1 + ti; i < L; i += 16) {
-      double* const ai = a + mff_tri(i);
-      double* const xi = x + mff_tri(i);
-      const double cit = ai[t];
-      for (int j = t + 1 + tj; j <= i; j += 16) ai[j] = fma(-cit, a[mff_tri(j) + t], ai[j]);
-      for (int j = tj; j <= t; j += 16) xi[j] = fma(-cit, x[mff_tri(t) + j], xi[j]);
-    }
-    __syncthreads();
-  }
+  double sl;
+  const int info = mff_factor_lds(a, x, L, tid, sl);
   double* __restrict__ dst = Wg + (size_t)k * P;
   for (int s = tid; s < P; s += kMfBlock) dst[s] = info ? 0.0 : x[s];
   if (tid == 0) {

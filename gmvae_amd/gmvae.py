@@ -180,6 +180,16 @@ class TrainableGMVAE(GMVAE):
         from . import neighbours
         return neighbours.model_scores(self, images, labels, clusters, k=k, n_labels=n_labels, **kw)
 
+    def linear_probe(self, train_images, train_labels, test_images=None, test_labels=None, n_classes=10, labelled_per_class=0,
+                     seed=0, **fit_kw):
+        """A linear classifier fitted on the device to the frozen codes self.transform(train_images) (gmvae_amd.linprobe.fit(**fit_kw):
+        l2, n_iter, standardize) and scored there and on the test images: `train_accuracy`, `train_nll`, `test_accuracy`, `test_nll`
+        (0-d device tensors), `n_labelled` and `fit`.  labelled_per_class > 0 fits on the labels runners.select_labelled picks with
+        `seed` -- the "M1" baseline of a semi-supervised run with the same flag."""
+        from . import linprobe
+        return linprobe.model_probe(self, train_images, train_labels, test_images, test_labels, n_classes=n_classes,
+                                    labelled_per_class=labelled_per_class, seed=seed, **fit_kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts p(z | y = k) from a fitted mixture (fit_latent_mixture's or gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)).
         prior_gmm is a Linear on the one-hot y with no hidden layer, so a table: its bias becomes 0 and row k of its weight (mu_k,

@@ -96,6 +96,16 @@ def build_parser():
       "--component_posterior_samples; vae: none -- silhouette_clusters, nmi_clusters and ari_clusters; with --fit_latent_mixture the same three for the fitted "
       "mixture's assignment, with --embed_latent embedding_trustworthiness_{k} and embedding_continuity_{k}; 0 = off")
     a("--knn_k", type=int, default=10, help="--neighbour_scores: the number of neighbours k")
+    a("--linear_probe", type=int, default=0, help="eval: also fit a linear classifier (softmax regression) on the device to the latent "
+      "code of the first N examples of the split and score it on the next --probe_test (gmvae_amd.linprobe) -- linear_probe_acc, "
+      "linear_probe_nll, linear_probe_train_acc and linear_probe_grad_max (the convergence readout); 0 = off")
+    a("--probe_test", type=int, default=0, help="--linear_probe: the examples scored, those behind the N fitted (0: what is left of "
+      "the split, N at most)")
+    a("--probe_l2", type=float, default=1e-3, help="--linear_probe: the l2 penalty on the weights")
+    a("--probe_iters", type=int, default=300, help="--linear_probe: the iterations")
+    a("--probe_labelled_per_class", type=int, default=0, help="--linear_probe: fit on this many labels per class of the N examples, "
+      "chosen as --labelled_per_class chooses with --random_seed (the M1 baseline of Kingma et al. 2014); 0 = every label")
+    a("--probe_standardize", action="store_true", help="--linear_probe: centre and scale the code per dimension by the fitted rows")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -214,6 +224,21 @@ def check_args(p, cfg):
             p.error("--neighbour_scores scores one rank's codes: it is not available with more than one rank")
         if not 1 <= cfg.knn_k <= 256 or not cfg.neighbour_scores > 2 * cfg.knn_k:
             p.error("--neighbour_scores N needs --knn_k in [1, 256] and N > 2 * --knn_k")
+    if cfg.linear_probe < 0:
+        p.error("--linear_probe must be >= 0 (0 = off)")
+    if cfg.linear_probe:
+        if cfg.mode != "eval":
+            p.error("--linear_probe needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--linear_probe fits one rank's codes: it is not available with more than one rank")
+        if cfg.latent_size > 128:
+            p.error("--linear_probe needs --latent_size <= 128")
+        if cfg.probe_test < 0 or cfg.probe_iters < 0 or cfg.probe_labelled_per_class < 0:
+            p.error("--probe_test, --probe_iters and --probe_labelled_per_class must be >= 0")
+        if not (cfg.probe_l2 > 0 and cfg.probe_l2 < float("inf")):
+            p.error("--probe_l2 must be a finite number > 0")
+    elif (cfg.probe_test, cfg.probe_l2, cfg.probe_iters, cfg.probe_labelled_per_class, cfg.probe_standardize) != (0, 1e-3, 300, 0, False):
+        p.error("--probe_test, --probe_l2, --probe_iters, --probe_labelled_per_class and --probe_standardize need --linear_probe")
     if cfg.ais_chains < 0 or cfg.ais_temps < 0:
         p.error("--ais_chains and --ais_temps must be >= 0 (0 = off)")
     if bool(cfg.ais_chains) != bool(cfg.ais_temps):

@@ -17,7 +17,7 @@ from typing import Iterator, Tuple
 import numpy as np
 import torch
 
-from . import gmvae, mixfit, neighbours, parallel, tsne, utils, vae
+from . import gmvae, linprobe, mixfit, neighbours, parallel, tsne, utils, vae
 
 
 # ------------------------------------------------------------------ data
@@ -734,6 +734,10 @@ def run_eval(config):
     ns_n, ns_k, ns_logits = int(getattr(config, "neighbour_scores", 0) or 0), int(getattr(config, "knn_k", 10)), []
     if ns_n and world > 1:
         raise ValueError("--neighbour_scores scores one rank's codes: it is not available with more than one rank")
+    # --linear_probe N: a linear classifier fitted to the code of the first N examples of the split, scored on the next M (linprobe.fit)
+    lp_n = int(getattr(config, "linear_probe", 0) or 0)
+    if lp_n and world > 1:
+        raise ValueError("--linear_probe fits one rank's codes: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -1027,6 +1031,31 @@ def run_eval(config):
             new[f"embedding_trustworthiness_{ns_k}"] = neighbours.trustworthiness(ns_codes[:m], res["latent_embedding"][:m], ns_k)
             new[f"embedding_continuity_{ns_k}"] = neighbours.continuity(ns_codes[:m], res["latent_embedding"][:m], ns_k)
         for k, v in new.items():
+            res[f"{config.split}/{k}"] = v.item()
+            if rank == 0:
+                print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if lp_n:
+        # the linear probe: fitted on the first N codes (with --probe_labelled_per_class on the labels select_labelled shows: the M1
+        # baseline of a semi-supervised run with the same seed), scored on the next M
+        lp_codes, lp_labs = res["latent_state"], res["labels"]
+        total = lp_codes.shape[0]
+        lp_m = int(getattr(config, "probe_test", 0) or 0) or min(lp_n, total - lp_n)
+        if lp_n >= total or lp_m < 1 or lp_n + lp_m > total:
+            raise ValueError(f"--linear_probe {lp_n} with --probe_test {lp_m}: the {config.split} split holds {total} examples; it "
+                             f"must hold the N fitted and at least one more to score")
+        n_labels = max(10, int(lp_labs.max().item()) + 1)                  # (as utils.cluster_acc widens its histogram)
+        linprobe.check_sizes(lp_n, lp_codes.shape[1], n_labels)
+        seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
+        lpc = int(getattr(config, "probe_labelled_per_class", 0) or 0)
+        train_labs = lp_labs[:lp_n]
+        shown = torch.from_numpy(select_labelled(train_labs.cpu().numpy(), lpc, seed)) if lpc > 0 else train_labs
+        fitted = linprobe.fit(lp_codes[:lp_n], shown, n_labels, l2=float(getattr(config, "probe_l2", 1e-3)),
+                              n_iter=int(getattr(config, "probe_iters", 300)), standardize=bool(getattr(config, "probe_standardize", False)))
+        tr = linprobe.score(lp_codes[:lp_n], train_labs, fitted)
+        te = linprobe.score(lp_codes[lp_n:lp_n + lp_m], lp_labs[lp_n:lp_n + lp_m], fitted)
+        res["linear_probe"] = fitted
+        for k, v in (("linear_probe_acc", te["accuracy"]), ("linear_probe_nll", te["nll"]), ("linear_probe_train_acc", tr["accuracy"]),
+                     ("linear_probe_grad_max", fitted["grad_max"])):
             res[f"{config.split}/{k}"] = v.item()
             if rank == 0:
                 print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")

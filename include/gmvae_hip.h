@@ -789,6 +789,39 @@ int gmvae_knn_ranks(const float* q, int64_t Nq, const float* r, int64_t Nr, int 
 int gmvae_knn_class_sums(const float* q, int64_t Nq, const float* r, int64_t Nr, int L, const int32_t* labels, int C,
                          double* sums_out, void* workspace, void* stream);
 
+/* A linear probe: multinomial logistic regression with an l2 penalty fitted to codes x [N][L] (fp32, device memory) with labels
+ * y [N] (int32), and its predictions (model independent; gmvae_amd.linprobe, model.linear_probe and run_eval's --linear_probe go
+ * through it; the reference has no counterpart).  The statement is tests/linprobe_ref.py; the kernels are csrc/linprobe.hpp.
+ *   Labels: a label outside [0, C) marks the row unlabelled -- weight 0 in the fit, left out of predict's sums.  n = the labelled
+ *     rows, xbar = their mean (fp64).
+ *   Model: p_n = softmax((x_n - xbar) W + b);  f(W, b) = -(1/n) sum_labelled ln p_n[y_n] + (l2 / 2) |W|_F^2  (the bias is free).
+ *   Metric, built once: A = 1/2 (1/n) sum_labelled (x_n - xbar)(x_n - xbar)^T + l2 I in fp64 (Boehning's bound: the Hessian of f in
+ *     W is <= I_C (x) A, in b <= 1/2 I; the centring decouples the two), its Cholesky factor, A^-1.
+ *   gmvae_linprobe_fit: FISTA in that metric with unit steps, Theta_0 = V_0 = 0: at the extrapolated point V, G_W = (1/n) sum
+ *     (x_n - xbar)^T (p_n - e_y) + l2 V_W and G_b = (1/n) sum (p_n - e_y); Theta' = (V_W - A^-1 G_W, V_b - 2 G_b); V' = Theta' +
+ *     beta (Theta' - Theta), beta = (t - 1) / t', t' = (1 + sqrt(1 + 4 t^2)) / 2, t_0 = 1 (computed on the host in fp64, one per
+ *     launch).  No line search, no stopping rule: 3 + 2 n_iter launches enqueued on `stream` with no host synchronisation.
+ *     Outputs: W_out [L][C] and b_out [C] = b - xbar W, so that the UN-centred logits x W_out + b_out are the model's;
+ *     loss_history [n_iter] (may be NULL), entry it = f at the point iteration it evaluated; grad_max_out [1] (may be NULL) = max
+ *     |G| at the last evaluated point (NaN if n_iter = 0); info_out [1] (int32, may be NULL) = 0, j + 1 for the first pivot j of
+ *     the factorisation that is not > 0, or -1 if no row is labelled -- W_out and b_out are then 0 and the history NaN.
+ *   gmvae_linprobe_predict: log_prob_out [N][C] = ln softmax(x W + b) and pred_out [N] (int32) = its FIRST maximal index (either
+ *     may be NULL); with labels (may be NULL) sums_out [3] (fp64, may be NULL) = the labelled rows, those with pred = y, and sum
+ *     -ln p[y] over them (all 0 without labels).
+ * Arithmetic: the logits are fp64 sums of exact products of fp32 numbers (V_W rounded to fp32 for the pass), the exponentials fp32,
+ * every sum over rows and the whole update fp64.  One owner per sum, fixed-order folds, no float atomics: two calls give the same bits.
+ * Sizes: 1 <= N <= 2^24, 1 <= L <= 128, 2 <= C <= 256, C L <= 16,384, n_iter >= 0, l2 finite and > 0.
+ * The workspace (gmvae_linprobe_workspace_bytes(N, L, C), which reads no device memory) holds xbar, A^-1, Theta, V and the
+ * workgroups' partial sums (at most 256 row slices', nothing per row); it needs no initialisation, and fit and predict may share it
+ * one after the other.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (the sizes above); GMVAE_E_NULL (any pointer not marked "may be NULL");
+ * GMVAE_E_ALIGN (float and int32 arrays 4 bytes, sums_out 8, the workspace 16). */
+int gmvae_linprobe_workspace_bytes(int64_t N, int L, int C, uint64_t* bytes);
+int gmvae_linprobe_fit(const float* codes, const int32_t* labels, int64_t N, int L, int C, double l2, int n_iter, float* W_out,
+                       float* b_out, float* loss_history, float* grad_max_out, int32_t* info_out, void* workspace, void* stream);
+int gmvae_linprobe_predict(const float* codes, const int32_t* labels, int64_t N, int L, int C, const float* W, const float* b,
+                           float* log_prob_out, int32_t* pred_out, double* sums_out, void* workspace, void* stream);
+
 /* log p(x) by annealed importance sampling (AIS) with Hamiltonian Monte Carlo transitions (Neal 2001; Wu, Burda, Salakhutdinov &
  * Grosse 2017): the generative model alone, so -- unlike gmvae_iw_bound* -- its gap does not depend on the inference network, and
  * it tightens towards log p(x) as n_temps grows (Engine.ais_bound, model.ais_bound and run_gmvae --mode=eval --ais_chains go
