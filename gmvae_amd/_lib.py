@@ -169,6 +169,12 @@ LIKELIHOODS = {"bernoulli": 0, "grey_bernoulli": LIK_GREY_BERNOULLI, "continuous
 # ... x as float [B][D] / the Gaussian's scale per dimension and learned (include/gmvae_hip.h GMVAE_X_F32, GMVAE_LIK_SCALE_LEARNED)
 X_F32, LIK_SCALE_LEARNED = 1 << 13, 1 << 14
 LOG_SIGMA = "decoder/log_sigma"      # ... its parameter rho [1, D], the layout's last entry
+# ... count data under a Poisson / negative-binomial decoder, lambda the log-mean (include/gmvae_hip.h GMVAE_LIK_POISSON,
+# GMVAE_LIK_NEG_BINOMIAL): each with X_F32, the LIK_* field 0
+LIK_POISSON, LIK_NEG_BINOMIAL = 1 << 15, 1 << 16
+# Engine(likelihood=...) beside LIKELIHOODS: the count likelihoods' bits
+COUNT_LIKELIHOODS = {"poisson": LIK_POISSON, "negative_binomial": LIK_NEG_BINOMIAL}
+LOG_DISPERSION = "decoder/log_dispersion"      # ... the negative binomial's rho [1, D] (r = exp(rho)), the layout's last entry
 # Engine(y_estimator=...): the relaxed Gumbel-softmax sample, or its straight-through form (Jang et al. 2017)
 Y_ESTIMATORS = ("relaxed", "straight_through")
 LABEL_SLOTS = 32      # GMVAE_LABEL_SLOTS: label sets in a workspace under OBJ_LABELS = the most steps of one train graph

@@ -186,6 +186,50 @@ class NormalDiagScale:
         return (-0.5 * e * e - torch.log(self.sigma) - 0.5 * math.log(2 * math.pi)).sum(-1)
 
 
+class Poisson:
+    """Independent Poisson with the LOG-mean as its parameter: the decoder's distribution under likelihood="poisson".
+    log p(x) = x l - exp(l) - lgamma(x + 1) summed over the last dimension; x >= 0, real values allowed."""
+
+    def __init__(self, log_rate, name="Poisson"):
+        self.log_rate, self.name = log_rate, name
+
+    def mean(self, name=None):
+        return torch.exp(self.log_rate)
+
+    def sample(self, seed=None):
+        return torch.poisson(self.mean(), generator=_gen(seed, self.log_rate.device))
+
+    def log_prob(self, x):
+        x = x.to(self.log_rate.dtype)
+        return (x * self.log_rate - torch.exp(self.log_rate) - torch.lgamma(x + 1.0)).sum(-1)
+
+
+class NegativeBinomial:
+    """Independent negative binomial with mean exp(l) and inverse dispersion r_d = exp(rho_d) (variance mean + mean^2 / r): the
+    decoder's distribution under likelihood="negative_binomial".  With u = l - rho and sp = softplus,
+    log p(x) = lgamma(x + r) - lgamma(r) - lgamma(x + 1) - x sp(-u) - r sp(u): l is never exponentiated alone."""
+
+    def __init__(self, log_mean, log_dispersion, name="NegativeBinomial"):
+        self.log_mean, self.name = log_mean, name
+        self.log_dispersion = log_dispersion.to(log_mean.device, log_mean.dtype)
+
+    def mean(self, name=None):
+        return torch.exp(self.log_mean)
+
+    def sample(self, seed=None):
+        """The gamma-Poisson mixture: rate ~ Gamma(r, r / mean), x ~ Poisson(rate)."""
+        g = _gen(seed, self.log_mean.device)
+        r = torch.exp(self.log_dispersion).expand_as(self.log_mean)
+        rate = torch._standard_gamma(r, generator=g) * torch.exp(self.log_mean - self.log_dispersion)
+        return torch.poisson(rate, generator=g)
+
+    def log_prob(self, x):
+        x = x.to(self.log_mean.dtype)
+        r, u = torch.exp(self.log_dispersion), self.log_mean - self.log_dispersion
+        sp = torch.nn.functional.softplus
+        return (torch.lgamma(x + r) - torch.lgamma(r) - torch.lgamma(x + 1.0) - x * sp(-u) - r * sp(u)).sum(-1)
+
+
 class _Categorical:
     def __init__(self, logits):
         self.logits = logits
@@ -321,6 +365,10 @@ class ConditionalBernoulli(_Conditional):
             return NormalDiagScale(lam, torch.exp(self._engine.views()["decoder/log_sigma"]), name=self._name)
         if lik == "gaussian":
             return NormalFixedScale(lam, self._engine.likelihood_sigma, name=self._name)
+        if lik == "poisson":
+            return Poisson(lam, name=self._name)
+        if lik == "negative_binomial":
+            return NegativeBinomial(lam, self._engine.views()["decoder/log_dispersion"], name=self._name)
         return IndependentBernoulli(lam, name=self._name)
 
 

@@ -35,7 +35,7 @@ int check_model(const GmvaeDims* d, int model) {
     if (d->hidden[i] < 1 || d->hidden[i] > kAisMaxWidth) return GMVAE_E_DIMS;
   if (d->hidden_act < GMVAE_ACT_RELU || d->hidden_act > GMVAE_ACT_ELU) return GMVAE_E_DIMS;
   if (d->gen_bias_vec ? d->gen_bias_len != d->D : d->gen_bias_len != 0) return GMVAE_E_DIMS;
-  if (d->sched_flags & (GMVAE_LIK_MASK | GMVAE_OBJ_PIXEL_MASK | GMVAE_X_F32 | GMVAE_LIK_SCALE_LEARNED)) return GMVAE_E_DIMS;
+  if (d->sched_flags & (GMVAE_LIK_MASK | GMVAE_OBJ_PIXEL_MASK | GMVAE_X_F32 | GMVAE_LIK_SCALE_LEARNED | GMVAE_LIK_POISSON | GMVAE_LIK_NEG_BINOMIAL)) return GMVAE_E_DIMS;
   return 0;
 }
 int check_rows(const GmvaeDims* d, int per_example) {

@@ -25,6 +25,7 @@
 
 #include "aux.hpp"
 #include "lik.hpp"
+#include "count.hpp"
 
 namespace gmvae {
 
@@ -101,6 +102,10 @@ struct Problem {
   const float* lik_sigma;       // on the grey-level bytes x; fp32 C = (A' - t) / phi, no planes; part sums the log-probability terms, part2
                                 // the squared errors (A' - t)^2; lik_sigma: the Gaussian's device cell (read once per workgroup)
                                 // lik | LIK_XF32: x is float [.][ldx], the target itself; lik | LIK_RHO: lik_sigma is rho [N], sigma_n = exp(rho_n)
+                                // lik | LIK_POIS / LIK_NB (count.hpp; with LIK_XF32, the kind field 0; gemm_grouped's COUNT instances):
+                                // x holds counts, lik_sigma is the negative binomial's rho [N]; addsrc [M / add_div] is added once to
+                                // each row's log-probability (column tile 0's partial); c3_stride != 0: sp(u) leaves as a second
+                                // fp32 plane C + c3_stride (rho's gradient reads it)
   Segment seg[2];
 };
 
@@ -1265,7 +1270,9 @@ __device__ __forceinline__ void big_rounds(float* __restrict__ lds, const float*
 // BIG = 1: the 128x128 instance for launches in which EVERY tile is interior, fp32 and made of whole rounds (the host
 // checks: big_eligible); its only main loop is big_rounds -- a kernel of its own so that the general loop's loaders do
 // not share its register budget.  BIG = 2: every problem of the launch reads pre-split planes (plane_rounds3).
-template <class C, int BIG = 0>
+// COUNT: the instances whose EPI_LIK epilogue is the count likelihoods' branch (count.hpp) -- kernels of their own, launched for
+// the logits GEMM of a count step alone, so that every other instance keeps its code byte for byte.
+template <class C, int BIG = 0, bool COUNT = false>
 __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const Launch L) {
   __shared__ __attribute__((aligned(16))) float lds[C::LDS_FLOATS];
   constexpr int kBK = C::BK;
@@ -1831,6 +1838,105 @@ __global__ __launch_bounds__(C::THREADS, C::WAVES_EU) void gemm_grouped(const La
             C3s[o] = (unsigned short)hi; C3s[o + c3ss] = (unsigned short)mi; C3s[o + 2 * c3ss] = (unsigned short)lo;
           }
         }
+      }
+    }
+  } else if (COUNT && epi == EPI_LIK) {  // counts (Problem::lik & LIK_COUNT): lambda the log-mean -> (g, sum_d log p, sum_d (softplus(lambda) - log1p(x))^2)
+    // The count likelihoods (count.hpp) as a branch of their own beside the likelihood epilogue below, which keeps its code: the
+    // same tile paths -- interior, the last column tile of an N that is no multiple of the tile, element by element at the edges
+    // --, fp32 targets from x, the negative binomial's rho per column quad, two chains per row finished in fp64.  The terms of
+    // log p that do not depend on lambda arrive summed per example in lik_c and join the row's sum in column tile 0.  (`COUNT &&`: a constant, so the other instances do not carry the branch.)
+    const float* const xf = reinterpret_cast<const float*>(L.p[pi].x);
+    float* part = L.p[pi].part;
+    float* const part2 = L.p[pi].part2;
+    const int ldx = L.p[pi].ldx, x_div = L.p[pi].x_div, nparts = L.p[pi].nparts;
+    const bool nbin = (L.p[pi].lik & LIK_NB) != 0;
+    const float* const rh = L.p[pi].lik_sigma;
+    const float* const cb = L.p[pi].addsrc;
+    const int c_div = L.p[pi].add_div;
+    float* const spo = (nbin && Cout && L.p[pi].c3_stride) ? Cout + L.p[pi].c3_stride : nullptr;
+    if (m0 + C::BM <= M && (n0 + C::BN <= N || (N & 3) == 0) && (ldc & 3) == 0 && (!Cout || al16(Cout)) && al16(bias) &&
+        (!bias2 || al16(bias2)) && (ldx & 3) == 0 && al16(xf) && (!nbin || al16(rh)) && (!spo || al16(spo))) {
+      constexpr int RPP = C::THREADS / GPR;
+      const int c4 = tid % GPR, r0 = tid / GPR, nb = n0 + 4 * c4;
+      const bool nv = nb < N;                      // (this thread's column quad exists)
+      float4 b4 = nv ? *reinterpret_cast<const float4*>(bias + nb) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bias2 && nv) { const float4 c4v = *reinterpret_cast<const float4*>(bias2 + nb); b4.x += c4v.x; b4.y += c4v.y; b4.z += c4v.z; b4.w += c4v.w; }
+      const float bc[4] = {b4.x + addconst, b4.y + addconst, b4.z + addconst, b4.w + addconst};
+      float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (nbin && nv) r4 = *reinterpret_cast<const float4*>(rh + nb);
+      const float rv[4] = {r4.x, r4.y, r4.z, r4.w};
+      const float re[4] = {expf(r4.x), expf(r4.y), expf(r4.z), expf(r4.w)};      // (r_d = exp(rho_d))
+      auto passes = [&](auto nb_c) {
+        constexpr bool NB = decltype(nb_c)::value;
+#pragma unroll
+        for (int q = 0; q < PASSES; ++q) {
+          const int row = r0 + RPP * q;
+          f32x4 tv = {0.f, 0.f, 0.f, 0.f};
+          if (nv) tv = *reinterpret_cast<const f32x4*>(xf + (long long)((m0 + row) / x_div) * ldx + nb);
+          f32x4 acc = *reinterpret_cast<const f32x4*>(lds + row * C::LDC + 4 * c4);
+#pragma unroll
+          for (int w = 1; w < C::WK; ++w) acc += *reinterpret_cast<const f32x4*>(lds + (w * C::BM + row) * C::LDC + 4 * c4);
+          float v[4], sv[4], lps = 0.f, sqs = 0.f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float lp, df;
+            count_term<NB>(acc[j] + bc[j], tv[j], rv[j], re[j], lp, v[j], sv[j], df);
+            lps += lp; sqs = fmaf(df, df, sqs);
+          }
+          if (Cout && nv) *reinterpret_cast<float4*>(Cout + (long long)(m0 + row) * ldc + nb) = make_float4(v[0], v[1], v[2], v[3]);
+          if constexpr (NB) { if (spo && nv) *reinterpret_cast<float4*>(spo + (long long)(m0 + row) * ldc + nb) = make_float4(sv[0], sv[1], sv[2], sv[3]); }
+          *reinterpret_cast<float2*>(lds + row * C::LDC + 4 * c4) = nv ? make_float2(lps, sqs) : make_float2(0.f, 0.f);
+        }
+      };
+      if (nbin) passes(std::true_type{}); else passes(std::false_type{});
+      __syncthreads();
+      if (tid < C::BM) {
+        double t = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < GPR; ++c) { t += (double)lds[tid * C::LDC + 4 * c]; t2 += (double)lds[tid * C::LDC + 4 * c + 1]; }
+        if (tn == 0) t += (double)cb[(m0 + tid) / c_div];
+        part[(long long)(m0 + tid) * nparts + tn] = (float)t;
+        part2[(long long)(m0 + tid) * nparts + tn] = (float)t2;
+      }
+    } else
+#pragma unroll 1
+    for (int ps = 0; ps < PASSES; ++ps) {
+      const int gidx = tid + ps * C::THREADS;
+      const int row = gidx / GPR, c4 = gidx % GPR;
+      float4 v4 = *reinterpret_cast<const float4*>(lds + row * C::LDC + 4 * c4);
+#pragma unroll
+      for (int w = 1; w < C::WK; ++w) {
+        const float4 o = *reinterpret_cast<const float4*>(lds + (w * C::BM + row) * C::LDC + 4 * c4);
+        v4.x += o.x; v4.y += o.y; v4.z += o.z; v4.w += o.w;
+      }
+      const int m = m0 + row, nb = n0 + 4 * c4;
+      double rsum = 0.0, rsum2 = 0.0;
+      if (m < M && nb < N) {
+        float v[4] = {v4.x, v4.y, v4.z, v4.w}, sv[4];
+        const float* const xr = xf + (long long)(m / x_div) * ldx;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = min(nb + j, N - 1);
+          const float lam = v[j] + bias[n] + (bias2 ? bias2[n] : 0.f) + addconst;
+          const float rho_n = nbin ? rh[n] : 0.f;
+          float lp, df;
+          if (nbin) count_term<true>(lam, xr[n], rho_n, expf(rho_n), lp, v[j], sv[j], df);
+          else count_term<false>(lam, xr[n], 0.f, 0.f, lp, v[j], sv[j], df);
+          rsum += (nb + j < N) ? (double)lp : 0.0;
+          rsum2 += (nb + j < N) ? (double)df * (double)df : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (nb + j >= N) break;
+          if (Cout) Cout[(long long)m * ldc + nb + j] = v[j];
+          if (spo) spo[(long long)m * ldc + nb + j] = sv[j];
+        }
+      }
+#pragma unroll
+      for (int o = GPR / 2; o > 0; o >>= 1) { rsum += __shfl_xor(rsum, o, 64); rsum2 += __shfl_xor(rsum2, o, 64); }
+      if (m < M && c4 == 0) {
+        if (tn == 0) rsum += (double)cb[m / c_div];
+        part[(long long)m * nparts + tn] = (float)rsum; part2[(long long)m * nparts + tn] = (float)rsum2;
       }
     }
   } else if (epi == EPI_LIK) {  // lambda -> ((A'(lambda) - t) / phi, sum_d (t lambda - A(lambda)) / phi + c(t), sum_d (A' - t)^2), t = x / 255

@@ -41,6 +41,7 @@
 #include "pmask.hpp"
 #include "lik.hpp"
 #include "liksig.hpp"
+#include "count.hpp"
 #include "gclip.hpp"
 #include "aggpost.hpp"
 #include "impute.hpp"      // gmvae_impute: the argument record and the host launch functions (kernels: impute.hip)
@@ -89,7 +90,17 @@ static bool pixel_mask(const GmvaeDims& d) { return (d.sched_flags & GMVAE_OBJ_P
 // GMVAE_LIK_*: the decoder's likelihood on grey-level bytes (lik.hpp: t = x / 255 as fp32 for every network that reads x, the
 // likelihood epilogue of gemm.hpp, lik_tail behind loss_tail) -- the general schedule only, fp32 logits GEMM, no planes.
 // 0: the Bernoulli on {0, 1}; else LIK_GREY / LIK_CB / LIK_GAUSS
-static int lik_kind(const GmvaeDims& d) { return (int)((d.sched_flags & GMVAE_LIK_MASK) >> 11); }
+// ... or the count likelihoods' bits (count.hpp): LIK_POISSON / LIK_NEGBIN where the field is 0 (check_lik_dims refuses both at
+// once and either beside the field), so that every site that asks "a likelihood of lik.hpp's family?" -- the general schedule,
+// no planes, the evaluators' refusals -- answers for them too
+enum { LIK_POISSON = 4, LIK_NEGBIN = 5 };
+static int lik_kind(const GmvaeDims& d) {
+  const int f = (int)((d.sched_flags & GMVAE_LIK_MASK) >> 11);
+  if (f) return f;
+  return (d.sched_flags & GMVAE_LIK_POISSON) ? LIK_POISSON : (d.sched_flags & GMVAE_LIK_NEG_BINOMIAL) ? LIK_NEGBIN : 0;
+}
+static bool lik_count(const GmvaeDims& d) { return (d.sched_flags & (GMVAE_LIK_POISSON | GMVAE_LIK_NEG_BINOMIAL)) != 0; }
+static bool lik_negbin(const GmvaeDims& d) { return (d.sched_flags & GMVAE_LIK_NEG_BINOMIAL) != 0; }
 // GMVAE_X_F32: x is float [B][D] behind the ABI's const uint8_t* -- the first layers' fp32 operand and the epilogue's target
 // itself, no lik_rows pass.  GMVAE_LIK_SCALE_LEARNED: sigma_d = exp(rho_d), rho the layout's last entry (liksig.hpp has its
 // gradient).  Both under LIK_GAUSS alone (check_lik_dims).
@@ -226,7 +237,10 @@ static int check_pmask_dims(const GmvaeDims* d) {
 // ... and GMVAE_LIK_* together with any other objective or estimator bit (GMVAE_OPT_CLIP_NORM combines): the three models'
 // standard objectives (the GMVAE's Gumbel draw) at any S only; the combinations are follow-ups  (gmvae_forward's check too)
 static int check_lik_dims(const GmvaeDims* d) {
-  if ((x_f32(*d) || lik_learned(*d)) && lik_kind(*d) != LIK_GAUSS) return GMVAE_E_DIMS;      // (either bit without the Gaussian)
+  if (lik_count(*d)) {      // (counts: fp32 x, the field 0, no learned Gaussian scale, one likelihood)
+    if (!x_f32(*d) || (d->sched_flags & GMVAE_LIK_MASK) || lik_learned(*d)) return GMVAE_E_DIMS;
+    if ((d->sched_flags & GMVAE_LIK_POISSON) && (d->sched_flags & GMVAE_LIK_NEG_BINOMIAL)) return GMVAE_E_DIMS;
+  } else if ((x_f32(*d) || lik_learned(*d)) && lik_kind(*d) != LIK_GAUSS) return GMVAE_E_DIMS;      // (either bit without the Gaussian)
   if (!lik_kind(*d)) return 0;
   return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
                             GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH | GMVAE_OBJ_PIXEL_MASK)) ? GMVAE_E_DIMS : 0;
@@ -261,6 +275,7 @@ static void build_layout(const GmvaeDims& d, int model, Layout& L) {
     add_net(L, L.dec, "decoder", d.L, d.hidden, d.n_hidden, d.D);
   }
   if (lik_learned(d)) add_entry(L, "decoder/log_sigma", 1, d.D, L.logsig);      // (the last entry: without the bit the layout is unchanged)
+  if (lik_negbin(d)) add_entry(L, "decoder/log_dispersion", 1, d.D, L.logsig);      // (GMVAE_LIK_NEG_BINOMIAL's rho in the same slot: never both)
 }
 
 // --------------------------------------------------------------- workspace
@@ -290,6 +305,10 @@ struct WS {
   float *lik_sigma, *lik_t, *lik_part;
   // GMVAE_LIK_SCALE_LEARNED: liksig_partial's slab partials [liksig_slabs(R)][pad4(D)] (no lik_sigma); GMVAE_X_F32: no lik_t
   float* lsig_part;
+  // GMVAE_LIK_POISSON / GMVAE_LIK_NEG_BINOMIAL (count.hpp): lik_t holds log1p(x); c [B] the per-example constants; under the
+  // negative binomial sp(u) [R D] beside g and count_disp_partial's fp64 slab partials [liksig_slabs(R)][pad4(D)]
+  float *count_c, *count_sp;
+  double* count_part;
   // GMVAE_OPT_CLIP_NORM: the caller's threshold (one float, read only), the records [GMVAE_LABEL_SLOTS][4] the library writes
   // and the fp64 partials of the sum of squares, one per 1024 elements of the gradient buffer
   float *clip_norm, *grad_clip;
@@ -588,8 +607,13 @@ static void carve(const GmvaeDims& d, int model, const Layout& L, void* base, WS
   }
   if (lik_kind(d)) {                              // (behind everything, as above; in front of the clip regions: a field of its own)
     if (lik_kind(d) == LIK_GAUSS && !lik_learned(d)) w.lik_sigma = take(4);
-    if (!x_f32(d)) w.lik_t = take(B * D);
+    if (!x_f32(d) || lik_count(d)) w.lik_t = take(B * D);
     w.lik_part = take(R * ((D + 31) / 32));
+    if (lik_count(d)) w.count_c = take(B);
+    if (lik_negbin(d)) {
+      w.count_sp = take(R * D);
+      w.count_part = reinterpret_cast<double*>(take(2 * (uint64_t)liksig_slabs((long long)R) * pad4(D)));
+    }
     if (lik_learned(d)) w.lsig_part = take((uint64_t)liksig_slabs((long long)R) * pad4(D));
   }
   if (clip_norm(d)) {                             // (behind everything, as above: dims without the bit keep their size and every offset)
@@ -865,7 +889,22 @@ static int launch_group(Ctx& cx, Group& g, const char* name, int cfg = -1, unsig
     }
   }
   int tiles;
-  if (cfg == 2) {
+  bool count = false;      // (the logits GEMM of a count step: the COUNT instances, general loop)
+  for (int i = 0; i < g.L.nprob; ++i) count = count || (g.L.p[i].epi == EPI_LIK && (g.L.p[i].lik & LIK_COUNT));
+  if (count) {
+    if (planes) { cx.err = cx.err ? cx.err : GMVAE_E_DIMS; return 2; }
+    if (cfg == 2) {
+      tiles = g.L.total_tiles = tile_up<CfgL>(g.L);
+      hipLaunchKernelGGL((gemm_grouped<CfgL, 0, true>), dim3(tiles + g.L.aux.nblocks), dim3(kThreads), 0, cx.st, g.L);
+    } else if (cfg == 1 || cfg == 3) {
+      cfg = 1;
+      tiles = g.L.total_tiles = tile_up<CfgM>(g.L);
+      hipLaunchKernelGGL((gemm_grouped<CfgM, 0, true>), dim3(tiles + g.L.aux.nblocks), dim3(kThreads), 0, cx.st, g.L);
+    } else {
+      tiles = g.L.total_tiles = tile_up<CfgS>(g.L);
+      hipLaunchKernelGGL((gemm_grouped<CfgS, 0, true>), dim3(tiles + g.L.aux.nblocks), dim3(kThreads), 0, cx.st, g.L);
+    }
+  } else if (cfg == 2) {
     tiles = g.L.total_tiles = tile_up<CfgL>(g.L);
     const bool no_big = getenv("GMVAE_NO_BIG") != nullptr;      // diagnostic / A-B: the general loop
     // f16 pairs: 256-row tiles (one 8-wave workgroup per CU, 0.75 of the LDS-DMA bytes per product) where every problem's rows
@@ -1119,6 +1158,7 @@ constexpr unsigned kGeneralOnlyFwd =
     GMVAE_Y_TEMP_DEV |                // ytemp.hpp's kernels in y_head_fwd's / y_head_bwd's / y_head_bwd_w's place
     GMVAE_Y_STRAIGHT_THROUGH |        // (the same)
     GMVAE_OBJ_PIXEL_MASK |            // pmask.hpp: x~ = m x, the masked Bernoulli epilogue of gemm.hpp, pmask_tail behind loss_tail
+    GMVAE_LIK_POISSON | GMVAE_LIK_NEG_BINOMIAL |      // count.hpp: t = log1p(x), the count branch of that epilogue, c_b, rho's gradient
     GMVAE_LIK_MASK;                   // lik.hpp: t = x / 255 as fp32, the likelihood epilogue of gemm.hpp, lik_tail behind loss_tail
 constexpr unsigned kGeneralOnlyTrain = kGeneralOnlyFwd |
     GMVAE_GRAD_DREG |                 // kernels.hpp z_head_bwd_dreg: the backward of the general schedule alone
@@ -2208,15 +2248,22 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
   // the likelihood epilogue's target
   const int lik = lik_kind(d);
   const bool xf = x_f32(d), lsig = lik_learned(d);       // (check_lik_dims: under LIK_GAUSS alone)
-  if ((xf || lsig) && lik != LIK_GAUSS) return GMVAE_E_DIMS;
+  const bool cnt = lik_count(d), nbin = lik_negbin(d);      // (check_lik_dims: fp32 x, the field 0)
+  if ((xf || lsig) && lik != LIK_GAUSS && !cnt) return GMVAE_E_DIMS;
+  if (cnt && (!xf || lsig || !w.lik_t || !w.count_c || (nbin && (!w.count_sp || !w.count_part)))) return GMVAE_E_DIMS;
   if (lik && (marg || pmask || (!xf && !w.lik_t) || !w.lik_part || (lik == LIK_GAUSS && !lsig && !w.lik_sigma) || (lsig && !w.lsig_part)))
     return GMVAE_E_DIMS;
-  // (the first layers' operand: bytes, t, or under GMVAE_X_F32 the caller's floats themselves)
-  const void* const xop = lik ? (xf ? (const void*)a.x : (const void*)w.lik_t) : (const void*)xin;
+  // (the first layers' operand: bytes, t, or under GMVAE_X_F32 the caller's floats themselves -- counts: t = log1p(x))
+  const void* const xop = lik ? ((xf && !cnt) ? (const void*)a.x : (const void*)w.lik_t) : (const void*)xin;
   const bool xu8 = !lik;
   if (lik && !xf) {
     hipLaunchKernelGGL(lik_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, w.lik_t, B, D);
     rowk(cx, "lik_rows");
+  }
+  if (cnt) {      // one read of x: t = log1p(x) and c_b, the terms of log p that do not depend on lambda (rho's under the NB)
+    hipLaunchKernelGGL(count_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, reinterpret_cast<const float*>(a.x),
+                       nbin ? P + L.logsig : (const float*)nullptr, w.lik_t, w.count_c, B, D);
+    rowk(cx, "count_rows");
   }
   if (pmask) {
     hipLaunchKernelGGL(pmask_rows, dim3(grid_for(B, 1, 8 * device_cus())), dim3(256), 0, st, a.x, pm, w.xm, w.mcnt, B, D);
@@ -2472,6 +2519,12 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
       if (lik) {      // (the likelihood form: the log-probability terms to part, the squared errors to part2, (A' - t) / phi to C)
         p.epi = EPI_LIK; p.lik = lik | (xf ? LIK_XF32 : 0) | (lsig ? LIK_RHO : 0); p.part2 = w.lik_part;
         p.lik_sigma = lsig ? P + L.logsig : w.lik_sigma;      // (the cell, or rho [D])
+        if (cnt) {      // (the count branch: g to C, sp(u) beside it for rho's gradient, c_b into column tile 0's partial)
+          p.lik = LIK_XF32 | (nbin ? LIK_NB : LIK_POIS);
+          p.lik_sigma = nbin ? P + L.logsig : nullptr;
+          p.addsrc = w.count_c; p.add_div = S;
+          p.c3_stride = (nbin && a.backward) ? (long long)(w.count_sp - w.g) : 0;      // (the sp(u) plane, in floats from C)
+        }
       }
       if (fwdp) {
         // forward only: both operands as f16 pairs, the weight's planes zero-padded to whole 128-column tiles
@@ -2628,6 +2681,13 @@ static int run_step_impl(Ctx& cx, const StepArgs& a) {
                        w.lsig_part, R, D, Dp, liksig_slab_rows(R));
     hipLaunchKernelGGL(liksig_finish, dim3((Dp + 255) / 256), dim3(256), 0, st, w.lsig_part, nsl, sl, PP, NS, (long long)L.logsig, Dp);
     rowk(cx, "liksig");
+  }
+  if (nbin) {      // GMVAE_LIK_NEG_BINOMIAL: rho's gradient from the stored g and sp(u), x and the row weights, into rho's range of the slabs
+    const int Dp = (int)pad4((uint64_t)D), nsl = liksig_slabs(R);
+    hipLaunchKernelGGL(count_disp_partial, dim3((D + kCdCols - 1) / kCdCols, nsl), dim3(256), 0, st, w.g, w.count_sp,
+                       reinterpret_cast<const float*>(a.x), rwS, P + L.logsig, w.count_part, R, D, Dp, liksig_slab_rows(R), S);
+    hipLaunchKernelGGL(count_disp_finish, dim3((Dp + 255) / 256), dim3(256), 0, st, w.count_part, nsl, sl, PP, NS, (long long)L.logsig, Dp);
+    rowk(cx, "count_disp");
   }
   int pb = 0;
   const float* dcur = w.g;
@@ -4127,7 +4187,7 @@ int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48) {
   snprintf(out48, 48, "%s%s%s%s%s%s%s%s%s%s%s%s%s", nm, marginal_iw_obj(d) ? "+marginal_iw" : marginal_y(d) ? "+marginal" : "",
            sup_labels(d) ? "+labels" : "", obj_weights(d) ? "+weights" : "", y_temp_dev(d) ? "+temp" : "",
            y_straight(d) ? "+st" : "", pixel_mask(d) ? "+mask" : "",
-           lik_kind(d) == LIK_GREY ? "+grey" : lik_kind(d) == LIK_CB ? "+cb" : lik_kind(d) == LIK_GAUSS ? "+gauss" : "",
+           lik_kind(d) == LIK_GREY ? "+grey" : lik_kind(d) == LIK_CB ? "+cb" : lik_kind(d) == LIK_GAUSS ? "+gauss" : lik_kind(d) == LIK_POISSON ? "+pois" : lik_kind(d) == LIK_NEGBIN ? "+nb" : "",
            x_f32(d) ? "+f32" : "", lik_learned(d) ? "+lsig" : "", dreg_grad(d) ? "+dreg" : "", clip_norm(d) ? "+clip" : "",
            pn.planes ? "+planes" : "");
   return 0;

@@ -48,13 +48,20 @@ class DeviceDataset:
     binarize=False: `next_batch` returns the gathered GREY rows as they are (a torch gather, off the hot path), for a model
     with a likelihood on grey levels.  The two paths do not feed the same picture: the binarising one sets a pixel with
     probability 1 - intensity, the grey one feeds the intensity itself, t = pixel / 255.  With binarize=False a FLOAT array
-    stays float32 [N, D] (real-valued rows for a model created with real_valued=True) and `next_batch` returns float32 rows."""
+    stays float32 [N, D] (real-valued rows for a model created with real_valued=True) and `next_batch` returns float32 rows.
+    counts=True (with binarize=False and a float array): the rows are counts for a Poisson / negative-binomial model, used as
+    they are; a negative or non-finite entry is refused here, once, on the host, before the upload."""
 
     def __init__(self, pixels, labels=None, shuffle: bool = True, seed: int = 0, y_observed=None, pixel_mask=None,
-                 binarize: bool = True):
+                 binarize: bool = True, counts: bool = False):
         dev = L.require_gpu()
         pixels = torch.as_tensor(pixels)
         keep_float = not binarize and pixels.dtype.is_floating_point
+        if counts:
+            if not keep_float:
+                raise ValueError("counts=True takes a float array with binarize=False")
+            if pixels.numel() and not (bool(torch.isfinite(pixels).all()) and bool((pixels >= 0).all())):
+                raise ValueError("count rows must be finite and >= 0")
         self.pixels = pixels.reshape(pixels.shape[0], -1).to(dev, torch.float32 if keep_float else torch.uint8).contiguous()
         self.labels = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
         self.y_observed = None if y_observed is None else torch.as_tensor(y_observed).to(dev, torch.int32).contiguous()

@@ -118,6 +118,23 @@ def check_likelihood(model, y_inference, grad_estimator, semi_supervised, weight
         raise ValueError(f"likelihood_sigma must be a finite number > 0, got {likelihood_sigma!r}")
     if likelihood == "bernoulli":
         return sigma
+    _check_likelihood_alone(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                            y_estimator, pixel_mask, likelihood)
+    return sigma
+
+
+def check_count_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                           y_estimator, pixel_mask, likelihood):
+    """The argument check of Engine(likelihood="poisson" | "negative_binomial") (no device needed): the library's refusals of
+    GMVAE_LIK_POISSON / GMVAE_LIK_NEG_BINOMIAL -- those of GMVAE_LIK_*."""
+    if likelihood not in L.COUNT_LIKELIHOODS:
+        raise ValueError(f"likelihood must be one of {tuple(L.COUNT_LIKELIHOODS)}, got {likelihood!r}")
+    _check_likelihood_alone(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                            y_estimator, pixel_mask, likelihood)
+
+
+def _check_likelihood_alone(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                            y_estimator, pixel_mask, likelihood):
     what = f"likelihood={likelihood!r}"
     if L.MODEL_IDS.get(model) == L.MODEL_GMVAE and y_inference != "gumbel":
         raise ValueError(f"{what} is not available with y_inference={y_inference!r}: use 'gumbel'")
@@ -133,7 +150,6 @@ def check_likelihood(model, y_inference, grad_estimator, semi_supervised, weight
         raise ValueError(f"{what} is not available with y_estimator={y_estimator!r}")
     if pixel_mask:
         raise ValueError(f"{what} is not available with pixel_mask=True")
-    return sigma
 
 
 IMPUTE_MAX_DRAWS = 16
@@ -163,11 +179,18 @@ def check_impute_args(model, y_inference, likelihood, pixel_mask, n_samples, n_d
 LIKELIHOOD_SCALES = ("fixed", "learned")
 
 
-def check_real_valued(likelihood, real_valued=False, likelihood_scale="fixed"):
+def check_real_valued(likelihood, real_valued=None, likelihood_scale="fixed"):
     """The argument check of Engine(real_valued=, likelihood_scale=) (no device needed): the library's refusals of GMVAE_X_F32
     and GMVAE_LIK_SCALE_LEARNED -- both need the Gaussian likelihood (whose own refusals check_likelihood holds)."""
     if likelihood_scale not in LIKELIHOOD_SCALES:
         raise ValueError(f"likelihood_scale must be one of {LIKELIHOOD_SCALES}, got {likelihood_scale!r}")
+    if likelihood in L.COUNT_LIKELIHOODS:
+        # counts (GMVAE_LIK_POISSON / GMVAE_LIK_NEG_BINOMIAL): float rows are implied -- an explicit False contradicts it
+        if real_valued is not None and not real_valued:
+            raise ValueError(f"likelihood={likelihood!r} takes float count rows: real_valued=False contradicts it")
+        if likelihood_scale == "learned":
+            raise ValueError(f"likelihood_scale='learned' needs likelihood='gaussian', got likelihood={likelihood!r}")
+        return
     if real_valued and likelihood != "gaussian":
         raise ValueError(f"real_valued=True needs likelihood='gaussian', got likelihood={likelihood!r}")
     if likelihood_scale == "learned" and likelihood != "gaussian":
@@ -272,7 +295,7 @@ class Engine:
                  sup_weight: float = 1.0, weighted_objective: bool = False, kl_weight: float = 1.0, y_weight: float = 1.0,
                  y_free_nats: float = 0.0, temperature_on_device: bool = False, y_estimator: str = "relaxed",
                  pixel_mask: bool = False, clip_norm: Optional[float] = None, likelihood: str = "bernoulli",
-                 likelihood_sigma: float = 1.0, real_valued: bool = False, likelihood_scale: str = "fixed"):
+                 likelihood_sigma: float = 1.0, real_valued: Optional[bool] = None, likelihood_scale: str = "fixed"):
         """gen_bias_init: a scalar or a vector of data_size values (scripts/base.py:102-103: "a scalar or vector Tensor
         that is added to the output of the fully connected network", e.g. the logit of the training-set mean).
         y_inference (GMVAE): "gumbel" -- one Gumbel-softmax draw of y per sample (scripts/gmvae.py:238-240, the default) -- or
@@ -324,11 +347,21 @@ class Engine:
         read x itself.  likelihood_scale (likelihood "gaussian"; GMVAE_LIK_SCALE_LEARNED): "fixed" -- one sigma, the default --
         or "learned": a scale per dimension, sigma_d = exp(rho_d), rho = the parameter "decoder/log_sigma" [1, D] initialised to
         ln(likelihood_sigma) and trained like every other parameter (it is the layout's last entry; a checkpoint carries it,
-        and restoring one without it into such an engine, or the reverse, raises).  set_likelihood_sigma then raises."""
+        and restoring one without it into such an engine, or the reverse, raises).  set_likelihood_sigma then raises.
+        likelihood "poisson" / "negative_binomial" (GMVAE_LIK_POISSON / GMVAE_LIK_NEG_BINOMIAL): x is a float matrix [B, D] of
+        counts (finite, >= 0; real_valued is implied, an explicit False raises), the decoder's output is the LOG-mean, every
+        network that reads x reads log1p(x), and tail[5] / tail[6] is the squared error of log1p(mean) against log1p(x).  The
+        negative binomial's inverse dispersion r_d = exp(rho_d) is the parameter "decoder/log_dispersion" [1, D], initialised to
+        0 (r = 1) and trained like every other parameter (the layout's last entry, carried by checkpoints)."""
         clip_norm = check_clip_norm(clip_norm)
         check_real_valued(likelihood, real_valued, likelihood_scale)
-        likelihood_sigma = check_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective,
-                                            temperature_on_device, y_estimator, pixel_mask, likelihood, likelihood_sigma)
+        if likelihood in L.COUNT_LIKELIHOODS:
+            check_count_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
+                                   y_estimator, pixel_mask, likelihood)
+            likelihood_sigma = 1.0
+        else:
+            likelihood_sigma = check_likelihood(model, y_inference, grad_estimator, semi_supervised, weighted_objective,
+                                                temperature_on_device, y_estimator, pixel_mask, likelihood, likelihood_sigma)
         check_pixel_mask(model, y_inference, grad_estimator, semi_supervised, weighted_objective, temperature_on_device,
                          y_estimator, pixel_mask)
         check_y_head(model, y_inference, temperature, temperature_on_device, y_estimator)
@@ -384,7 +417,8 @@ class Engine:
         self.clip_norm = clip_norm
         self.likelihood = likelihood
         self.likelihood_sigma = likelihood_sigma
-        self.real_valued = bool(real_valued)
+        self.count_likelihood = likelihood in L.COUNT_LIKELIHOODS
+        self.real_valued = bool(real_valued) or self.count_likelihood
         self.likelihood_scale = likelihood_scale
         self.rows_per_x = self._rows_per_x(self.S)      # sample-dependent rows per batch row
         self.hp = dict(sigma_min=sigma_min, raw_sigma_bias=raw_sigma_bias, temperature=float(temperature),
@@ -445,7 +479,7 @@ class Engine:
         wobj = L.OBJ_WEIGHTS if self.weighted_objective and int(S) == 1 else 0
         yh = (L.Y_TEMP_DEV if self.temperature_on_device else 0) | (L.Y_STRAIGHT_THROUGH if self.y_estimator == "straight_through" else 0)
         pmask = (L.OBJ_PIXEL_MASK if self.pixel_mask else 0) | (L.OPT_CLIP_NORM if self.clip_norm is not None else 0)
-        pmask |= L.LIKELIHOODS[self.likelihood]
+        pmask |= L.COUNT_LIKELIHOODS[self.likelihood] if self.count_likelihood else L.LIKELIHOODS[self.likelihood]
         pmask |= (L.X_F32 if self.real_valued else 0) | (L.LIK_SCALE_LEARNED if self.likelihood_scale == "learned" else 0)
         return L.make_dims(B, self.D, self.Lz, self.K, self.hidden, S=S,
                            row0=self.rank * B if row0 is None else int(row0), gen_bias_vec=self.gen_bias_vec,
@@ -493,6 +527,9 @@ class Engine:
             if name == L.LOG_SIGMA:             # rho = ln sigma for every dimension
                 flat[off:off + rows * cols] = math.log(self.likelihood_sigma)
                 continue
+            if name == L.LOG_DISPERSION:        # rho = 0: inverse dispersion r = 1 for every dimension
+                flat[off:off + rows * cols] = 0.0
+                continue
             fan_in, fan_out = (cols, cols) if name == "mixture_logits" else (rows, cols)
             lim = math.sqrt(6.0 / (fan_in + fan_out))
             flat[off:off + rows * cols] = (torch.rand(rows * cols, generator=gen) * 2 - 1) * lim
@@ -509,7 +546,7 @@ class Engine:
         out = {}
         for name, (rows, cols), off in self.layout:
             v = self.params.detach()[off:off + rows * cols]
-            if name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA):
+            if name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA, L.LOG_DISPERSION):
                 out[name] = v
             else:
                 out[name] = v.view(rows, cols)
@@ -519,7 +556,7 @@ class Engine:
         out = {}
         for name, (rows, cols), off in self.layout:
             v = flat[off:off + rows * cols]
-            out[name] = v if (name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA)) else v.view(rows, cols)
+            out[name] = v if (name.endswith("/b") or name in ("mixture_logits", L.LOG_SIGMA, L.LOG_DISPERSION)) else v.view(rows, cols)
         return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -539,6 +576,9 @@ class Engine:
         return sd
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
+        if (L.LOG_DISPERSION in sd) != (self.likelihood == "negative_binomial"):
+            raise ValueError(f"this checkpoint {'carries' if L.LOG_DISPERSION in sd else 'has no'} {L.LOG_DISPERSION!r}: it cannot "
+                             f"be restored into an engine with likelihood={self.likelihood!r}")
         if (L.LOG_SIGMA in sd) != (self.likelihood_scale == "learned"):
             raise ValueError(f"this checkpoint {'carries' if L.LOG_SIGMA in sd else 'has no'} {L.LOG_SIGMA!r}: it cannot be restored "
                              f"into an engine with likelihood_scale={self.likelihood_scale!r}")
@@ -713,6 +753,8 @@ class Engine:
                 raise ValueError(f"expected [B,{self.D}] inputs, got {tuple(x.shape)}")
             if x.numel() and not bool(torch.isfinite(x).all()):
                 raise ValueError("real_valued=True takes finite values: x holds NaN or inf")
+            if self.count_likelihood and x.numel() and bool((x < 0).any()):
+                raise ValueError(f"likelihood={self.likelihood!r} takes counts: x holds negative values")
             return x.clone() if x.data_ptr() % 16 else x
         if self.likelihood != "bernoulli" and x.dtype.is_floating_point:
             # grey levels: a float image in [0, 1] -> the nearest k / 255 (uint8 tensors are taken as grey levels as given)
@@ -1313,6 +1355,8 @@ class Engine:
         """One conditional network's MLP on the device (snt.nets.MLP, scripts/base.py:47-60)."""
         if self.real_valued and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
             inp = self._prep_x(inp)                                 # (the networks that read x read the floats themselves)
+            if self.count_likelihood:
+                inp = torch.log1p(inp)                              # (... counts: t = log1p(x))
         elif self.likelihood != "bernoulli" and net in (L.NET_ENCODER_Y, L.NET_ENCODER_GMM, L.NET_ENCODER):
             inp = self._prep_x(inp).to(torch.float32) / 255.0       # (the networks that read x read t = x / 255 as fp32)
         is_u8 = inp.dtype in (torch.uint8, torch.bool)

@@ -237,6 +237,8 @@ class TrainableGMVAE(GMVAE):
             out["recon_mse"] = t[5] / t[6]
         if e.likelihood_scale == "learned":        # (the mean of the learned per-dimension scales sigma_d = exp(rho_d))
             out["sigma_mean"] = torch.exp(e.views()["decoder/log_sigma"]).mean()
+        if e.likelihood == "negative_binomial":    # (the mean of the learned inverse dispersions r_d = exp(rho_d))
+            out["dispersion_mean"] = torch.exp(e.views()["decoder/log_dispersion"]).mean()
         if e.clip_norm is not None:                # (of the last eager optimizer step: the norm before clipping, clipped 0 / 1)
             out["grad_norm"], out["clipped"] = e.grad_clip[0], e.grad_clip[2]
         if self._last_labels is not None:
@@ -266,7 +268,7 @@ def create_gmvae(data_size, latent_size, mixture_components=1, fcnet_hidden_size
                  temperature=1.0, random_seed=None, n_samples=1, y_inference="gumbel", grad_estimator="standard",
                  semi_supervised=False, sup_weight=1.0, weighted_objective=False, kl_weight=1.0, y_weight=1.0, y_free_nats=0.0,
                  temperature_on_device=False, y_estimator="relaxed", pixel_mask=False, clip_norm=None, likelihood="bernoulli",
-                 likelihood_sigma=1.0, real_valued=False, likelihood_scale="fixed"):
+                 likelihood_sigma=1.0, real_valued=None, likelihood_scale="fixed"):
     """Factory with the signature of scripts/gmvae.py:277-287 (+ n_samples, y_inference, grad_estimator, semi_supervised,
     sup_weight, weighted_objective, kl_weight, y_weight, y_free_nats, temperature_on_device, y_estimator, pixel_mask, clip_norm, likelihood, likelihood_sigma, real_valued, likelihood_scale: Engine).  y_inference="marginal" trains and
     evaluates the objective with y summed out exactly over the K components (Engine); "marginal_iw" the same with z

@@ -144,10 +144,14 @@ def build_parser():
     a("--clip_norm", type=float, default=0.0, help="train: clip the batch-mean gradient by its global norm to this threshold "
       "in front of Adam and skip the steps whose gradient or loss is not finite; the log reports the norm's mean and maximum "
       "and the clipped and skipped shares per summary window (inf: report only; 0 = off)")
-    a("--likelihood", default="bernoulli", choices=["bernoulli", "grey_bernoulli", "continuous_bernoulli", "gaussian"],
+    a("--likelihood", default="bernoulli", choices=["bernoulli", "grey_bernoulli", "continuous_bernoulli", "gaussian", "poisson", "negative_binomial"],
       help="the decoder's likelihood: bernoulli on binarised pixels (the reference), or on the GREY levels t = pixel / 255 the "
       "Bernoulli cross-entropy on soft targets (grey_bernoulli), the continuous Bernoulli or a Gaussian with the fixed scale "
-      "--likelihood_sigma; train and eval then report recon_mse, the per-pixel squared error of the mean image")
+      "--likelihood_sigma; train and eval then report recon_mse, the per-pixel squared error of the mean image.  poisson / "
+      "negative_binomial: the rows are COUNTS (float32 >= 0 from --data_npy, which is then required), "
+      "the decoder's output is the log-mean, the networks read log1p(count); --real_valued is implied, --standardize refused; "
+      "recon_mse is then the squared error of log1p(mean) against log1p(count), and the negative binomial learns an inverse "
+      "dispersion per dimension (the parameter decoder/log_dispersion, reported as dispersion_mean)")
     a("--likelihood_sigma", type=float, default=1.0, help="--likelihood=gaussian: the fixed scale sigma (with "
       "--likelihood_scale=learned: where every dimension's scale starts)")
     a("--real_valued", action="store_true", help="--likelihood=gaussian: the rows are float feature vectors (embeddings, sensor "
@@ -350,7 +354,14 @@ def check_args(p, cfg):
         if cfg.iw_enum_samples or cfg.posterior_samples or cfg.component_posterior_samples:
             p.error(f"{what} is not available with --iw_enum_samples, --posterior_samples or --component_posterior_samples "
                     "(they would score Bernoulli): use --iw_samples")
-    if cfg.real_valued and cfg.likelihood != "gaussian":
+    if cfg.likelihood in ("poisson", "negative_binomial"):
+        if cfg.standardize:
+            p.error(f"--standardize is not available with --likelihood={cfg.likelihood}: counts are fed as they are")
+        if not cfg.data_npy:
+            p.error(f"--likelihood={cfg.likelihood} needs --data_npy: a float32 [N, D] file of counts (runners.synthetic_counts "
+                    "makes a stand-in)")
+        cfg.real_valued = True      # (implied: float rows)
+    if cfg.real_valued and cfg.likelihood not in ("gaussian", "poisson", "negative_binomial"):
         p.error("--real_valued needs --likelihood=gaussian")
     if cfg.likelihood_scale == "learned" and cfg.likelihood != "gaussian":
         p.error("--likelihood_scale=learned needs --likelihood=gaussian")

@@ -88,7 +88,7 @@ def create_dataset(config, split="train", shuffle=True, repeat=True, device="cud
 
 def real_valued(config) -> bool:
     """--real_valued: the rows are float feature vectors fed as they are (Engine(real_valued=True))."""
-    return bool(getattr(config, "real_valued", False))
+    return bool(getattr(config, "real_valued", False)) or count_data(config)
 
 
 def npy_shape(path: str):
@@ -109,10 +109,43 @@ def synthetic_real(n: int, D: int):
     return x.astype(np.float32), lab.astype(np.int64)
 
 
+def count_data(config) -> bool:
+    """--likelihood=poisson | negative_binomial: the rows are counts (Engine(likelihood=...); float rows are implied)."""
+    return getattr(config, "likelihood", "bernoulli") in ("poisson", "negative_binomial")
+
+
+def synthetic_counts(n: int, D: int, k: int = 3, seed: int = 7):
+    """The synthetic stand-in of a count run: (float32 [n, D] counts, int64 labels [n]) -- a fixed-seed K-cluster gamma-Poisson
+    mixture.  Each cluster has its own log-normal mean profile over the features (a tenth of them raised tenfold, so that the
+    clusters differ where it matters), each feature its own inverse dispersion r in [0.5, 4]; a row draws its rates from
+    Gamma(r, r / mean) and its counts from Poisson(rate): over-dispersed and zero-heavy, like an expression matrix."""
+    rng = np.random.default_rng(seed)
+    base = np.exp(rng.normal(0.0, 1.0, (1, D)))
+    prof = base * np.exp(rng.normal(0.0, 0.5, (k, D)))
+    prof = prof * np.where(rng.random((k, D)) < 0.1, 10.0, 1.0)
+    r = rng.uniform(0.5, 4.0, D)
+    lab = rng.integers(0, k, n)
+    mean = prof[lab]
+    rate = rng.gamma(np.broadcast_to(r, mean.shape), mean / r)
+    return rng.poisson(rate).astype(np.float32), lab.astype(np.int64)
+
+
+def check_counts(x: np.ndarray) -> np.ndarray:
+    """Count rows are finite and >= 0: checked once, on the host, where the rows are loaded."""
+    if not np.isfinite(x).all():
+        raise ValueError("count data must be finite: the rows hold NaN or inf")
+    if (x < 0).any():
+        raise ValueError("count data must be >= 0: the rows hold negative values")
+    return x
+
+
 def real_rows(config):
     """--real_valued: (float32 [N, D] rows, int64 [N] labels) from --data_npy / --labels_npy (labels 0 without the second
     file), or synthetic_real(--synthetic_size, --data_dim)."""
     path = getattr(config, "data_npy", None)
+    if not path and count_data(config):
+        return synthetic_counts(int(getattr(config, "synthetic_size", 8192)), int(getattr(config, "data_dim", 784)),
+                                max(int(getattr(config, "mixture_components", 3) or 3), 1))
     if not path:
         return synthetic_real(int(getattr(config, "synthetic_size", 8192)), int(getattr(config, "data_dim", 784)))
     x = np.ascontiguousarray(np.load(path), dtype=np.float32)
@@ -122,6 +155,8 @@ def real_rows(config):
     lab = np.asarray(np.load(lp)).astype(np.int64).reshape(-1) if lp else np.zeros(x.shape[0], np.int64)
     if lab.shape[0] != x.shape[0]:
         raise ValueError(f"--labels_npy holds {lab.shape[0]} labels for {x.shape[0]} rows")
+    if count_data(config):
+        check_counts(x)
     return x, lab
 
 
@@ -373,7 +408,7 @@ def create_device_dataset(config, split="train", shuffle=True, standardize=None)
         rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
         a, b = parallel.shard_rows(x.shape[0], rank, world)
         return DeviceDataset(_standardized(x, standardize)[a:b], lab[a:b], shuffle=shuffle,
-                             seed=(config.random_seed or 0) * 7919 + 17 + rank, binarize=False)
+                             seed=(config.random_seed or 0) * 7919 + 17 + rank, binarize=False, counts=count_data(config))
     data = _load_mnist(getattr(config, "data_dir", "") or "", split) if getattr(config, "data_dir", None) else None
     rank, world = (parallel.dist.get_rank(), parallel.dist.get_world_size()) if parallel.dist.is_initialized() else (0, 1)
     if data is None:
@@ -874,6 +909,8 @@ def run_eval(config):
         res[f"{config.split}/recon_mse"] = pm_tot[0].item() / max(pm_tot[1].item(), 1.0)
     if eng.likelihood_scale == "learned":
         res[f"{config.split}/sigma_mean"] = torch.exp(eng.views()["decoder/log_sigma"]).mean().item()
+    if eng.likelihood == "negative_binomial":
+        res[f"{config.split}/dispersion_mean"] = torch.exp(eng.views()["decoder/log_dispersion"]).mean().item()
     if q_logits:
         # clustering accuracy of q(y|x) over the WHOLE split, components matched to labels by majority (utils.cluster_acc)
         res[f"{config.split}/cluster_acc_q"] = utils.cluster_acc(torch.cat(q_logits), torch.cat(labs), int(config.mixture_components),

@@ -201,6 +201,8 @@ class TrainableVAE(VAE):
             out["recon_mse"] = t[5] / t[6]
         if e.likelihood_scale == "learned":        # (the mean of the learned per-dimension scales sigma_d = exp(rho_d))
             out["sigma_mean"] = torch.exp(e.views()["decoder/log_sigma"]).mean()
+        if e.likelihood == "negative_binomial":    # (the mean of the learned inverse dispersions r_d = exp(rho_d))
+            out["dispersion_mean"] = torch.exp(e.views()["decoder/log_dispersion"]).mean()
         if e.clip_norm is not None:                # (of the last eager optimizer step: the norm before clipping, clipped 0 / 1)
             out["grad_norm"], out["clipped"] = e.grad_clip[0], e.grad_clip[2]
         return out
@@ -220,7 +222,7 @@ def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=
                hidden_activation_fn=torch.relu, sigma_min=0.001, raw_sigma_bias=0.25, gen_bias_init=0.0,
                random_seed=None, n_samples=1, grad_estimator="standard", weighted_objective=False, kl_weight=1.0,
                y_weight=1.0, y_free_nats=0.0, pixel_mask=False, clip_norm=None, likelihood="bernoulli", likelihood_sigma=1.0,
-               real_valued=False, likelihood_scale="fixed"):
+               real_valued=None, likelihood_scale="fixed"):
     """Factory with the signature of scripts/vae.py:191-200 (+ pixel_mask: run_model / compute_loss / iw_bound take mask=,
     Engine; + n_samples, the
     IWAE extension of SURVEY.md A15; 1 == the reference; + grad_estimator: "dreg" = the doubly
@@ -229,7 +231,9 @@ def create_vae(data_size, latent_size, mixture_components=1, fcnet_hidden_sizes=
     gradient clipped by its global norm in front of Adam, Engine; summaries then carry grad_norm and clipped; + likelihood,
     likelihood_sigma: "grey_bernoulli", "continuous_bernoulli" or "gaussian" on grey levels t = x / 255, Engine; the decoder
     then returns that distribution, reconstruct_images its mean, and summaries carry recon_mse; + real_valued,
-    likelihood_scale: float feature rows under the Gaussian, with a fixed or a learned per-dimension scale, Engine)."""
+    likelihood_scale: float feature rows under the Gaussian, with a fixed or a learned per-dimension scale, Engine; likelihood
+    "poisson" / "negative_binomial": float count rows, the decoder returns base.Poisson / base.NegativeBinomial with mean
+    exp(lambda), summaries carry dispersion_mean under the latter, Engine)."""
     if fcnet_hidden_sizes is None:
         fcnet_hidden_sizes = [latent_size]                     # scripts/vae.py:228-229
     name = "vae_gmp" if mixture_components > 1 else "vae"

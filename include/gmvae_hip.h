@@ -401,7 +401,35 @@ enum { GMVAE_SCHED_SAFE = 1,
         * gradient buffer's slabs -- a SUM like every other entry, so TF-Adam, GMVAE_OPT_CLIP_NORM, the data-parallel all-reduce
         * and checkpoints treat rho as any other parameter.  "general+gauss+lsig", "general+gauss+f32+lsig+clip".
         * Both bits: honoured and refused exactly where GMVAE_LIK_GAUSSIAN is (above). */
-       GMVAE_LIK_SCALE_LEARNED = 1 << 14 };
+       GMVAE_LIK_SCALE_LEARNED = 1 << 14,
+       /* count data: x is float [B][D] holding finite values >= 0 (integer-valued in practice; nothing assumes it, lgamma takes
+        * reals), lambda_rd -- the decoder's output exactly as above -- is the LOG-MEAN.  Two bits, mutually exclusive; each
+        * requires GMVAE_X_F32 (so x 16-byte aligned, GMVAE_E_ALIGN), the GMVAE_LIK_* field 0 and GMVAE_LIK_SCALE_LEARNED clear
+        * (GMVAE_E_DIMS otherwise).  Networks that read x read t_bd = log1p(x_bd) as fp32; the likelihood's target is x_bd.
+        *   GMVAE_LIK_POISSON        log p = x l - exp(l) - lgamma(x + 1)                     g = exp(l) - x
+        *                            (no clamp: l > 88 gives a non-finite step, which GMVAE_OPT_CLIP_NORM skips)
+        *   GMVAE_LIK_NEG_BINOMIAL   mean exp(l), inverse dispersion r_d = exp(rho_d), u = l - rho_d, sp = softplus:
+        *                            log p = lgamma(x + r) - lgamma(r) - lgamma(x + 1) - x sp(-u) - r sp(u)
+        *                            g = (r + x) sigmoid(u) - x
+        *                            d log p / d rho_d = r [psi(x + r) - psi(r) - sp(u)] + g         (psi = digamma)
+        *                            (lambda is never exponentiated alone: finite for every finite lambda and rho)
+        * rho = "decoder/log_dispersion" [1, D] is the LAST entry of the parameter layout under GMVAE_LIK_NEG_BINOMIAL, in the
+        * slot and with the padding rules of "decoder/log_sigma": TF-Adam, GMVAE_OPT_CLIP_NORM, the all-reduce and checkpoints see
+        * an ordinary parameter.  Its gradient is a launch pair behind the backward's row weights (count.hpp: fp64 digamma by
+        * recurrence to an argument >= 6 and the asymptotic series; a row-weighted fixed-order fp64 column reduction over the stored
+        * g and sp(u) planes, no atomics, slab 0 of rho's range written and the other slabs zeroed).
+        * The terms of log p that do not depend on lambda are summed once per example in fp64 by the rows pass that also writes
+        * t (c_b = sum_d [lgamma(x + r_d) - lgamma(r_d)] - lgamma(x + 1), an fp64 difference) and added to each of its S rows.
+        * Tail: [0..4] keep their meanings ([1] includes every constant); [5] = sum_b mean_s sum_d (log1p(exp lambda_rd) -
+        * log1p(x_bd))^2, the squared error of the mean on the scale the networks see; [6] = B D; [7] = 0.
+        * The workspace grows where GMVAE_LIK_*'s regions stand: float [B D] t, float [R][nparts] the squared-error partials, float
+        * [B] c; under the negative binomial float [R D] sp(u) and the dispersion pass's fp64 slab partials.
+        * Honoured and refused exactly where GMVAE_LIK_GAUSSIAN | GMVAE_X_F32 is: the general schedule only; GMVAE_OPT_CLIP_NORM
+        * combines, every other objective bit returns GMVAE_E_DIMS; gmvae_iw_bound gives the bound on log p(x) under the count
+        * likelihood; the pipeline graph and every other evaluator (*_enum_y, posterior_*, impute, ais*, simulate, refine) refuse
+        * before any launch.  gmvae_step_schedule appends "+pois" or "+nb" where "+gauss" stands: "general+nb+f32+clip". */
+       GMVAE_LIK_POISSON = 1 << 15,
+       GMVAE_LIK_NEG_BINOMIAL = 1 << 16 };
 #define GMVAE_LABEL_SLOTS 32  /* label sets (GMVAE_OBJ_LABELS) / weight rows (GMVAE_OBJ_WEIGHTS) / temperatures (GMVAE_Y_TEMP_DEV) / masks (GMVAE_OBJ_PIXEL_MASK) a workspace holds: the most steps of one train graph */
 enum { GMVAE_ACT_RELU = 0, GMVAE_ACT_TANH = 1, GMVAE_ACT_SIGMOID = 2, GMVAE_ACT_ELU = 3 };
 
@@ -1134,7 +1162,7 @@ int gmvae_debug_sk_stamps_free(void);
 
 /* Which schedule a TRAINING step of these sizes takes, as text (<= 47 chars + NUL into out48): "mega2", "mega", "skinny",
  * "fused" or "general", with "+marginal" appended under GMVAE_OBJ_MARGINAL_Y ("+marginal_iw" under
- * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+grey" / "+cb" / "+gauss" under GMVAE_LIK_*, "+f32" under GMVAE_X_F32, "+lsig" under GMVAE_LIK_SCALE_LEARNED, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
+ * GMVAE_OBJ_MARGINAL_Y_IW), then "+labels" under GMVAE_OBJ_LABELS, "+weights" under GMVAE_OBJ_WEIGHTS, "+temp" under GMVAE_Y_TEMP_DEV, "+st" under GMVAE_Y_STRAIGHT_THROUGH, "+mask" under GMVAE_OBJ_PIXEL_MASK, "+grey" / "+cb" / "+gauss" under GMVAE_LIK_*, "+pois" / "+nb" under GMVAE_LIK_POISSON / GMVAE_LIK_NEG_BINOMIAL, "+f32" under GMVAE_X_F32, "+lsig" under GMVAE_LIK_SCALE_LEARNED, "+dreg" under GMVAE_GRAD_DREG, "+clip" under GMVAE_OPT_CLIP_NORM, and "+planes" appended where the top decoder layer's GEMMs run as bf16 piece products on pre-split
  * operands (gemm.hpp plane_rounds3).  Host-side, reads the same environment switches as the step.  bench.py prices its
  * roofline line with it. */
 int gmvae_step_schedule(const GmvaeDims* dims, int model, char* out48);
