@@ -190,6 +190,15 @@ class TrainableGMVAE(GMVAE):
         return linprobe.model_probe(self, train_images, train_labels, test_images, test_labels, n_classes=n_classes,
                                     labelled_per_class=labelled_per_class, seed=seed, **fit_kw)
 
+    def sample_test(self, images, n_generations=None, space="data", **kw):
+        """The kernel two-sample test of the model's samples against `images` on the device (gmvae_amd.twosample.mmd_test(**kw):
+        n_perms, kernel, bandwidth, scales, seed): space "data" -- simulate(n_generations)["x"] against the binarised images
+        (Bernoulli likelihood only) --, "code" -- the sampled code transform(images) against the prior draws z* of simulate: does
+        the aggregate posterior match the prior, with a p-value, next to latent_diagnostics' KL -- or "both".  A dict per space
+        asked for, each mmd_test's (mmd2, p_value, null, witness_x, witness_y, sigma, n_perms, kscale)."""
+        from . import twosample
+        return twosample.model_test(self, images, n_generations, space, **kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts p(z | y = k) from a fitted mixture (fit_latent_mixture's or gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)).
         prior_gmm is a Linear on the one-hot y with no hidden layer, so a table: its bias becomes 0 and row k of its weight (mu_k,

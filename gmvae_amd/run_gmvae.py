@@ -106,6 +106,15 @@ def build_parser():
     a("--probe_labelled_per_class", type=int, default=0, help="--linear_probe: fit on this many labels per class of the N examples, "
       "chosen as --labelled_per_class chooses with --random_seed (the M1 baseline of Kingma et al. 2014); 0 = every label")
     a("--probe_standardize", action="store_true", help="--linear_probe: centre and scale the code per dimension by the fitted rows")
+    a("--sample_test", type=int, default=0, help="eval: also run the kernel two-sample test (MMD with a permutation null, on the "
+      "device; gmvae_amd.twosample) of N samples of the model against the first N examples of the split -- mmd2_data and mmd_p_data "
+      "(the simulated images against the data), mmd2_code and mmd_p_code (the prior's draws against one draw of q(z|x) per example: "
+      "does the aggregate posterior match the prior); 0 = off")
+    a("--sample_test_perms", type=int, default=1000, help="--sample_test: the splits, the observed one included (the smallest p-value "
+      "is 1 / this)")
+    a("--sample_test_kernel", default="rbf", choices=["rbf", "energy"], help="--sample_test: the rbf kernel at the median distance "
+      "and half and twice it, or the energy distance's kernel -|x - y|")
+    a("--sample_test_space", default="data", choices=["data", "code", "both"], help="--sample_test: what is compared")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -243,6 +252,24 @@ def check_args(p, cfg):
             p.error("--probe_l2 must be a finite number > 0")
     elif (cfg.probe_test, cfg.probe_l2, cfg.probe_iters, cfg.probe_labelled_per_class, cfg.probe_standardize) != (0, 1e-3, 300, 0, False):
         p.error("--probe_test, --probe_l2, --probe_iters, --probe_labelled_per_class and --probe_standardize need --linear_probe")
+    if cfg.sample_test < 0 or cfg.sample_test == 1:
+        p.error("--sample_test must be 0 (off) or >= 2")
+    if cfg.sample_test:
+        if cfg.mode != "eval":
+            p.error("--sample_test needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--sample_test tests one rank's examples: it is not available with more than one rank")
+        if not 1 <= cfg.sample_test_perms <= 4096:
+            p.error("--sample_test_perms must lie in [1, 4096]")
+        if 2 * cfg.sample_test > 1 << 20:
+            p.error("--sample_test N needs 2 N <= 2^20")
+        if cfg.missing_rate > 0:
+            p.error("--sample_test is not available with --missing_rate (the samples have every pixel, and the encoders that draw "
+                    "the code take no mask)")
+        if cfg.sample_test_space != "code" and cfg.likelihood != "bernoulli":
+            p.error("--sample_test compares simulated binary images: --sample_test_space=data and both need the Bernoulli likelihood")
+    elif (cfg.sample_test_perms, cfg.sample_test_kernel, cfg.sample_test_space) != (1000, "rbf", "data"):
+        p.error("--sample_test_perms, --sample_test_kernel and --sample_test_space need --sample_test")
     if cfg.ais_chains < 0 or cfg.ais_temps < 0:
         p.error("--ais_chains and --ais_temps must be >= 0 (0 = off)")
     if bool(cfg.ais_chains) != bool(cfg.ais_temps):

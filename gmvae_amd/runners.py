@@ -773,6 +773,10 @@ def run_eval(config):
     lp_n = int(getattr(config, "linear_probe", 0) or 0)
     if lp_n and world > 1:
         raise ValueError("--linear_probe fits one rank's codes: it is not available with more than one rank")
+    # --sample_test N: the kernel two-sample test of N samples of the model against the first N examples of the split (twosample)
+    st_n, st_imgs = int(getattr(config, "sample_test", 0) or 0), []
+    if st_n and world > 1:
+        raise ValueError("--sample_test tests one rank's examples: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -785,6 +789,8 @@ def run_eval(config):
             py_stats.append(torch.stack([po["bound"], po["entropy"], po["kl_q_post"], po["ess"]], dim=1))
         if first < ld_n:
             ld_imgs.append(images[:ld_n - first])
+        if first < st_n:
+            st_imgs.append(images[:st_n - first])
         mk = None if pmask_all is None else pmask_all[first:first + images.shape[0]]
         if iw_n > 0:
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
@@ -1096,4 +1102,19 @@ def run_eval(config):
             res[f"{config.split}/{k}"] = v.item()
             if rank == 0:
                 print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if st_n:
+        # the two-sample test: as many samples of the model as examples, per space the statistic and its permutation p-value
+        st_x = torch.cat(st_imgs)
+        if st_x.shape[0] < 2:
+            raise ValueError(f"--sample_test {st_n}: the {config.split} split holds {st_x.shape[0]} examples; the test needs two")
+        seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
+        tested = model.sample_test(st_x, space=getattr(config, "sample_test_space", "data"),
+                                   n_perms=int(getattr(config, "sample_test_perms", 1000)),
+                                   kernel=getattr(config, "sample_test_kernel", "rbf"), seed=seed)
+        res["sample_test"] = tested
+        for space, t in tested.items():
+            for k, v in ((f"mmd2_{space}", t["mmd2"]), (f"mmd_p_{space}", t["p_value"])):
+                res[f"{config.split}/{k}"] = v.item()
+                if rank == 0:
+                    print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
     return res

@@ -166,6 +166,15 @@ class TrainableVAE(VAE):
         return linprobe.model_probe(self, train_images, train_labels, test_images, test_labels, n_classes=n_classes,
                                     labelled_per_class=labelled_per_class, seed=seed, **fit_kw)
 
+    def sample_test(self, images, n_generations=None, space="data", **kw):
+        """The kernel two-sample test of the model's samples against `images` on the device (gmvae_amd.twosample.mmd_test(**kw):
+        n_perms, kernel, bandwidth, scales, seed): space "data" -- simulate(n_generations)["x"] against the binarised images
+        (Bernoulli likelihood only) --, "code" -- one draw of encoder(x).sample() per image against the prior draws z* of simulate:
+        does the aggregate posterior match the prior, with a p-value, next to latent_diagnostics' KL -- or "both".  A dict per
+        space asked for, each mmd_test's (mmd2, p_value, null, witness_x, witness_y, sigma, n_perms, kscale)."""
+        from . import twosample
+        return twosample.model_test(self, images, n_generations, space, **kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts the learned mixture prior (mixture_components > 1) from a fitted mixture (fit_latent_mixture's or
         gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)): mixture_logits = logw, loc = mu, raw_scale_diag = softplus^-1(sigma) =

@@ -850,6 +850,39 @@ int gmvae_linprobe_fit(const float* codes, const int32_t* labels, int64_t N, int
 int gmvae_linprobe_predict(const float* codes, const int32_t* labels, int64_t N, int L, int C, const float* W, const float* b,
                            float* log_prob_out, int32_t* pred_out, double* sums_out, void* workspace, void* stream);
 
+/* The kernel two-sample test (Gretton et al. 2012): the unbiased MMD^2 between two samples for P splits of one pooled sample
+ * z [N][D] (fp32, device memory) -- split 0 the observed one, the others the permutation null (model independent;
+ * gmvae_amd.twosample, model.sample_test and run_eval's --sample_test go through it; the reference has no counterpart).  The
+ * statement is tests/twosample_ref.py; the kernels are csrc/twosample.hpp.
+ *   Splits: assign [P][N] (uint8, device memory), non-zero where the point belongs to the first sample; n_p = the non-zero entries
+ *     of row p and m_p = N - n_p are counted on the device, so the rows may differ in size.
+ *   Distance: d2_ij = sum_d (z_id - z_jd)^2 in fp64.  GMVAE_MMD_ENERGY: from differences, each taken and squared in fp64 and added
+ *     in ascending d.  GMVAE_MMD_RBF: the kernel is translation invariant, so from the expanded square |zc_i|^2 + |zc_j|^2 -
+ *     2 zc_i . zc_j on the rows centred by the pooled mean, all fp64, clamped at 0 (tests/test_twosample_cpu.py: the two forms
+ *     differ by 3e-6 of the test's gate on its cases).
+ *   Kernel: GMVAE_MMD_RBF: k = (1/Q) sum_q exp(-gamma[q] d2), 1 <= Q <= 8, gamma [Q] (fp64, HOST memory, read before the
+ *     launches; finite and >= 0), the exponential fp64.  GMVAE_MMD_ENERGY: k = -sqrt(d2) -- MMD^2 is then the energy distance --,
+ *     gamma and Q ignored (gamma may be NULL); two equal rows give exactly k = 0.
+ *   Statistic: K0 = K with a zero diagonal, e = row p of assign as 0 / 1; a = e^T K0 e, b = e^T K0 1, c = 1^T K0 1 (fp64);
+ *     mmd2 [P] (fp64): mmd2[p] = a / (n (n - 1)) + (c - 2 b + a) / (m (m - 1)) - 2 (b - a) / (n m), NaN where n < 2 or m < 2.
+ *   Rows of split 0: row_all [N] = K0 1 and row_first [N] = K0 e_0 (fp64; either may be NULL): the witness function's sums.
+ * Nothing of size N^2 is stored: the workspace (gmvae_mmd_workspace_bytes(N, D, P), which reads no device memory) holds the
+ * workgroups' partial sums of a and b -- ceil(N / 32) row tiles times at most 16 column slabs, P doubles each --, 2 N doubles
+ * per slab for the two row outputs and, for the rbf kernel's centring, at most 65 D + N doubles; it needs no initialisation.  Two
+ * launches (energy) or five (rbf: the mean in two, the norms, the tiles, the finish) enqueued on `stream` with no host
+ * synchronisation.
+ * One owner per output, fixed-order fp64 sums (the order follows from N alone), no float atomics: two calls give the same bits, and
+ * mmd2[p] does not depend on which other splits the call holds.
+ * Sizes: 2 <= N <= 2^20, 1 <= D <= 4096, 1 <= P <= 4096.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (the sizes above); GMVAE_E_MODEL (the kernel kind); GMVAE_E_DIMS (Q, a
+ * gamma that is negative or not finite) and GMVAE_E_NULL (gamma) under GMVAE_MMD_RBF; GMVAE_E_NULL (z, assign, mmd2, workspace);
+ * GMVAE_E_ALIGN (z 4 bytes, the fp64 outputs 8, the workspace 16). */
+#define GMVAE_MMD_RBF 0
+#define GMVAE_MMD_ENERGY 1
+int gmvae_mmd_workspace_bytes(int N, int D, int P, uint64_t* bytes);
+int gmvae_mmd(const float* z, int N, int D, const uint8_t* assign, int P, int kernel, const double* gamma, int Q, double* mmd2,
+              double* row_all, double* row_first, void* workspace, void* stream);
+
 /* log p(x) by annealed importance sampling (AIS) with Hamiltonian Monte Carlo transitions (Neal 2001; Wu, Burda, Salakhutdinov &
  * Grosse 2017): the generative model alone, so -- unlike gmvae_iw_bound* -- its gap does not depend on the inference network, and
  * it tightens towards log p(x) as n_temps grows (Engine.ais_bound, model.ais_bound and run_gmvae --mode=eval --ais_chains go
