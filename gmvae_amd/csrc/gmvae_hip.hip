@@ -245,8 +245,15 @@ static int check_lik_dims(const GmvaeDims* d) {
   return (d->sched_flags & (GMVAE_OBJ_MARGINAL_Y | GMVAE_OBJ_MARGINAL_Y_IW | GMVAE_GRAD_DREG | GMVAE_OBJ_LABELS | GMVAE_OBJ_WEIGHTS |
                             GMVAE_Y_TEMP_DEV | GMVAE_Y_STRAIGHT_THROUGH | GMVAE_OBJ_PIXEL_MASK)) ? GMVAE_E_DIMS : 0;
 }
+// gmvae_step, gmvae_forward and the graphs: (row0 + B) S [K with y summed out] < 2^38, Philox's row field, whatever the objective
+// (check_dims holds it under GMVAE_OBJ_MARGINAL_Y_IW; the evaluators bound their own rows, (row0 + B) n, in iw_check_args)
+static int check_row_field(const GmvaeDims* d) {
+  const uint64_t per = (uint64_t)d->S * (marginal_y(*d) ? (uint64_t)d->K : 1), end = d->row0 + (uint64_t)d->B;
+  return (end < d->row0 || end > ((1ull << 38) - 1) / per) ? GMVAE_E_DIMS : 0;
+}
 static int check_step_dims(const GmvaeDims* d, int model) {
   if (int e = check_dims(d, model)) return e;
+  if (int e = check_row_field(d)) return e;
   if (int e = check_lik_dims(d)) return e;
   if (int e = check_pmask_dims(d)) return e;
   if (int e = check_label_dims(d, model)) return e;
@@ -3377,6 +3384,7 @@ int gmvae_forward(const GmvaeDims* dims, int model, const uint8_t* x, const floa
   if (int e = check_ytemp_dims(dims, model)) return e;
   if (int e = check_lik_dims(dims)) return e;
   if (int e = check_pmask_dims(dims)) return e;
+  if (int e = check_row_field(dims)) return e;
   if (!x || !params || !tail || !workspace) return GMVAE_E_NULL;
   if (!aligned16(params) || !aligned16(workspace) || (eps && !aligned16(eps)) || (u && !aligned16(u)))
     return GMVAE_E_ALIGN;

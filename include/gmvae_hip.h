@@ -72,7 +72,9 @@ typedef struct GmvaeDims {
    * device's first batch row, rank * B for equal shards, 0 on a single device.  It enters ONLY the Philox counters
    * of the in-kernel noise (eps, u) and of gmvae_binarize: row b of this device draws what row row0 + b of the
    * single-device step on the whole global batch draws, so G shards reproduce the 1-device step on G*B rows.
-   * Sizes, layouts and the workspace do not depend on it. */
+   * Sizes, layouts and the workspace do not depend on it.  The Philox counter holds 38 bits of the row: gmvae_step,
+   * gmvae_forward, the graphs and gmvae_workspace_bytes return GMVAE_E_DIMS if (row0 + B)*S >= 2^38 ((row0 + B)*S*K with y
+   * summed out); the evaluators bound their own rows (below). */
   uint64_t row0;
   /* ABI v3 -- vector bias_init of ConditionalBernoulli (scripts/base.py:102-103 "a scalar or vector Tensor that is added
    * to the output of the fully connected network", e.g. the logit of the training-set mean; added at base.py:135):

@@ -14,3 +14,5 @@ closed-form known-answer values of SURVEY.md section 4 and by an independent
 torch.distributions + autograd (fp64) statement in tests/test_oracle.py.
 """
 from .gmvae_oracle import *  # noqa: F401,F403
+# Test references call the noise as `oracle.noise(...)`, looked up at call time: tests/shard_cases.py rows_truncated swaps this
+# attribute to draw the rows a 32-bit Philox row would give.  Do not bind it with `from oracle import noise` in a *_ref.py.

@@ -43,12 +43,14 @@ def _cdims(d, B, fl):
     return cd
 
 
-def cstep(model, d, flat, x, eps, u, fl, seed=5, step=3):
-    """One gmvae_step under the flags (x float32): (grad sums [P] float64, tail [8], the step's ReLU masks, the buffer's bits)."""
+def cstep(model, d, flat, x, eps, u, fl, seed=5, step=3, row0=0):
+    """One gmvae_step at row0 under the flags (x float32): (grad sums [P] float64, tail [8], the step's ReLU masks, the buffer's
+    bits)."""
     import torch
     L = _L()
     B = x.shape[0]
     cd = _cdims(d, B, fl)
+    cd.row0 = row0
     P, _ = L.param_count(cd, model)
     assert P == flat.shape[0]
     params, xd = dev(flat, torch.float32), dev(x, torch.float32)

@@ -48,16 +48,16 @@ def _setup(model, d, B, S, seed=0):
     return flat, x, eps
 
 
-def dstep(model, d, S, flat, x, eps, flags, seed=5, step=3):
-    """One gmvae_step with sched_flags = flags: dict(g [P] float64 gradient sums, tail [8], masks, dlogits [B, K] | None,
+def dstep(model, d, S, flat, x, eps, flags, seed=5, step=3, row0=0):
+    """One gmvae_step at row0 with sched_flags = flags (eps None: in-kernel noise): dict(g [P] float64 gradient sums, tail [8], masks, dlogits [B, K] | None,
     schedule)."""
     L = _L()
     B = x.shape[0]
     u = None
-    if model == O.MODEL_GMVAE and not flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW):
+    if eps is not None and model == O.MODEL_GMVAE and not flags & (L.OBJ_MARGINAL_Y | L.OBJ_MARGINAL_Y_IW):
         u = np.random.default_rng(9).uniform(0.05, 0.95, (B * S, d.K))
     g, tail, masks, ws, cd = hip_step(model, dataclasses.replace(d, S=S), flat, x, eps, u, seed, step, want_masks=True, flags=flags,
-                                      mask_rows=_rows_per_x(model, d, S), want_ws=True)
+                                      row0=row0, mask_rows=_rows_per_x(model, d, S), want_ws=True)
     dlogits = None
     if model == O.MODEL_GMVAE:
         off = L.workspace_offset(cd, model, "dlogits") // 4

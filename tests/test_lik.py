@@ -39,9 +39,11 @@ def _inputs(lik, sigma):
     return {"lik_sigma": np.array([sigma], np.float32)} if lik == "gauss" else None
 
 
-def lstep(model, d, flat, x, eps, u, lik, sigma=1.0):
-    """One gmvae_step under the likelihood (sigma in its workspace cell): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=LR.FLAG[lik] if lik else 0, inputs=_inputs(lik, sigma))
+def lstep(model, d, flat, x, eps, u, lik, sigma=1.0, row0=0):
+    """One gmvae_step at row0 under the likelihood (sigma in its workspace cell): (grad sums [P] float64, tail [8], the step's
+    ReLU masks)."""
+    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=LR.FLAG[lik] if lik else 0, row0=row0,
+                    inputs=_inputs(lik, sigma))
 
 
 def lik_gates(what, tail, B, Cc):

@@ -174,7 +174,8 @@ def test_shard_rows_cover_and_balance():
 @pytest.mark.gpu
 def test_hip_step_sharded_sum_equals_full_batch():
     """1-GPU stand-in for the N-GPU equality: gradient SUMS of two row shards add up to the full-batch
-    buffer (what the all-reduce computes), to fp32 reduction-order tolerance."""
+    buffer (what the all-reduce computes), to fp32 reduction-order tolerance.
+    Every other objective family and uneven shards at row0 != 0: tests/test_shards.py."""
     import hip_util as H
     d = O.Dims(D=784, L=16, K=10, hidden=(64,))
     model = O.MODEL_GMVAE
@@ -199,7 +200,8 @@ def test_hip_step_sharded_sum_equals_full_batch():
 def test_virtual_ranks_with_row_offsets_sum_to_the_full_batch_philox_step(model, Lz, K, Bg, G, Hd):
     """In-kernel Philox noise (eps = u = NULL) under data parallelism: G 'virtual ranks' on one GPU, each stepping
     its row shard with GmvaeDims.row0 = its first global row, leave gradient sums that add up to the single-device
-    step on the whole batch with row0 = 0 -- same seed, same step, same eps/u rows."""
+    step on the whole batch with row0 = 0 -- same seed, same step, same eps/u rows.
+    Every other objective family and uneven shards at row0 != 0: tests/test_shards.py."""
     import ctypes as C
     import hip_util as H
     from gmvae_amd import _lib as L
@@ -249,7 +251,8 @@ def test_config5_full_shard_is_the_sum_of_its_row_shards():
     GLOBAL row, the step on 512 rows leaves the sum of the steps on its four 128-row shards (row0 = 0, 128, 256, 384) -- gradient
     sums, loss sum and row count -- although the two runs take different slab counts, tile grids and per-tensor pair scales; and
     the full-size step is bit-identical when repeated.  (The 128-row shard itself is compared with the oracle in
-    tests/test_hip_parity.py::test_plane_gemms_at_config5_dims_under_natural_gating.)"""
+    tests/test_hip_parity.py::test_plane_gemms_at_config5_dims_under_natural_gating.)
+    Every other objective family and uneven shards at row0 != 0: tests/test_shards.py."""
     import ctypes as C
     import hip_util as H
     from gmvae_amd import _lib as L

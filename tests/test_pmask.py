@@ -38,9 +38,9 @@ def _fill_mask(ws, cd, model, mask):
     write_inputs(ws, cd, model, {"pixel_mask": mask})
 
 
-def pstep(model, d, flat, x, eps, u, mask, bit=True):
-    """One gmvae_step (slot 0 of the masks = mask): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
-    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=_L().OBJ_PIXEL_MASK if bit else 0,
+def pstep(model, d, flat, x, eps, u, mask, bit=True, row0=0):
+    """One gmvae_step at row0 (slot 0 of the masks = mask): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
+    return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=_L().OBJ_PIXEL_MASK if bit else 0, row0=row0,
                     inputs={"pixel_mask": mask} if bit else None)
 
 

@@ -54,13 +54,14 @@ def _ws(cd, model, sigma):
     return ws
 
 
-def rstep(model, d, flat, x, eps, u, fl, sigma, seed=5, step=3, stale_rho_slabs=False):
-    """One gmvae_step under the flags (x uint8 or float32 as given): (grad sums [P] float64, tail [8], the step's ReLU masks).
+def rstep(model, d, flat, x, eps, u, fl, sigma, seed=5, step=3, stale_rho_slabs=False, row0=0):
+    """One gmvae_step at row0 under the flags (x uint8 or float32 as given): (grad sums [P] float64, tail [8], the step's ReLU masks).
     stale_rho_slabs: rho's range of every split-K slab of the gradient behind the first holds NaN when the step starts."""
     import torch
     L = _L()
     B = x.shape[0]
     cd = _cdims(d, B, fl)
+    cd.row0 = row0
     P, _ = L.param_count(cd, model)
     assert P == flat.shape[0]
     params, xd = dev(flat, torch.float32), _xdev(x)

@@ -29,10 +29,10 @@ def _cdims(model, marginal, d, B, bit=True):
     return cd
 
 
-def wstep(model, marginal, d, flat, x, eps, u, weights, bit=True):
-    """One gmvae_step (slot 0 of the weight rows = weights): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
+def wstep(model, marginal, d, flat, x, eps, u, weights, bit=True, row0=0):
+    """One gmvae_step at row0 (slot 0 of the weight rows = weights): (grad sums [P] float64, tail [8], the step's ReLU masks)."""
     return hip_step(model, d, flat, x, eps, u, 5, 3, want_masks=True, flags=_cdims(model, marginal, d, x.shape[0], bit).sched_flags,
-                    mask_rows=d.K if marginal else 1, inputs={"obj_weights": list(weights) + [0.0]} if bit else None)
+                    row0=row0, mask_rows=d.K if marginal else 1, inputs={"obj_weights": list(weights) + [0.0]} if bit else None)
 
 
 def compare_step(name, weights, what, case=None, ref=None):

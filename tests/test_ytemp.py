@@ -33,9 +33,9 @@ def _ref(name, tau, st):
     return _REF[key]
 
 
-def _cdims(name, B, temp_dev, st, temperature):
+def _cdims(name, B, temp_dev, st, temperature, d=None):
     L = _L()
-    d = TR.CASES[name][0]
+    d = d or TR.CASES[name][0]
     cd = dims_of(dataclasses.replace(d, temperature=temperature), B)
     cd.sched_flags = ((L.Y_TEMP_DEV if temp_dev else 0) | (L.Y_STRAIGHT_THROUGH if st else 0) |
                       (L.OBJ_WEIGHTS if TR.case_weights(name) else 0))
@@ -54,14 +54,16 @@ def _inputs(cd, name, tau):
     return inputs
 
 
-def ystep(name, tau, st, temp_dev=True, temperature=1.0):
-    """One gmvae_step of a case.  temp_dev: slot 0 holds tau and dims->temperature the decoy `temperature`; else
-    dims->temperature = tau.  Returns (grad sums [P] float64, tail [8], the step's ReLU masks, the workspace, its dims)."""
-    d, p32, flat, x, eps, u = TR.setup(name)
+def ystep(name, tau, st, temp_dev=True, temperature=1.0, case=None, row0=0):
+    """One gmvae_step of a case at row0.  temp_dev: slot 0 holds tau and dims->temperature the decoy `temperature`; else
+    dims->temperature = tau.  case: (Dims, p32, flat, x, eps, u) in TR.setup's form where they are not the named case's own
+    (tests/test_shards.py; `name` then only says whether the weights go with it).
+    Returns (grad sums [P] float64, tail [8], the step's ReLU masks, the workspace, its dims)."""
+    d, p32, flat, x, eps, u = case or TR.setup(name)
     temperature = temperature if temp_dev else tau
-    cd = _cdims(name, x.shape[0], temp_dev, st, temperature)
+    cd = _cdims(name, x.shape[0], temp_dev, st, temperature, d)
     return hip_step(GM, dataclasses.replace(d, temperature=temperature), flat, x, eps, u, 5, 3, want_masks=True, flags=cd.sched_flags,
-                    inputs=_inputs(cd, name, tau), want_ws=True)
+                    row0=row0, inputs=_inputs(cd, name, tau), want_ws=True)
 
 
 def compare_step(name, tau, st, rtol=1e-4):
