@@ -199,6 +199,15 @@ class TrainableGMVAE(GMVAE):
         from . import twosample
         return twosample.model_test(self, images, n_generations, space, **kw)
 
+    def sample_distance(self, images, n_generations=None, space="data", n_perms=0, **kw):
+        """The debiased Sinkhorn divergence between the model's samples and `images` on the device (gmvae_amd.sinkhorn.divergence(**kw):
+        blur, blur_rel, n_iter, n_final; with n_perms > 0 divergence_test, which adds a permutation null and p_value and takes seed)
+        on the pairs of samples sample_test compares, with its seeds and refusals: a transport distance in the space's own units
+        next to sample_test's verdict.  A dict per space asked for; read marginal_err -- convergence depends on the data -- and
+        compare values only at equal sample sizes and blur (gmvae_amd.sinkhorn)."""
+        from . import sinkhorn
+        return sinkhorn.model_distance(self, images, n_generations, space, n_perms, **kw)
+
     def init_prior_from_mixture(self, fit):
         """Starts p(z | y = k) from a fitted mixture (fit_latent_mixture's or gmvae_amd.mixfit.fit's dict, or (logw, mu, sigma)).
         prior_gmm is a Linear on the one-hot y with no hidden layer, so a table: its bias becomes 0 and row k of its weight (mu_k,

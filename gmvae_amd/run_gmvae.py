@@ -115,6 +115,16 @@ def build_parser():
     a("--sample_test_kernel", default="rbf", choices=["rbf", "energy"], help="--sample_test: the rbf kernel at the median distance "
       "and half and twice it, or the energy distance's kernel -|x - y|")
     a("--sample_test_space", default="data", choices=["data", "code", "both"], help="--sample_test: what is compared")
+    a("--sample_distance", type=int, default=0, help="eval: also measure the debiased Sinkhorn divergence (a transport distance under "
+      "the cost |u - v|^2 / 2, on the device; gmvae_amd.sinkhorn) between N samples of the model and the first N examples of the "
+      "split, on the pairs of samples --sample_test compares -- sinkhorn_data and sinkhorn_code, with sinkhorn_marginal_err_data and "
+      "sinkhorn_marginal_err_code (the convergence readout: the divergence is low until it is small); 0 = off")
+    a("--sample_distance_space", default="data", choices=["data", "code", "both"], help="--sample_distance: what is compared")
+    a("--sinkhorn_blur_rel", type=float, default=0.1, help="--sample_distance: the blur as a fraction of the root-mean-square "
+      "distance of the pooled sample (the final temperature is its square); values compare only at equal N and blur")
+    a("--sinkhorn_iters", type=int, default=200, help="--sample_distance: the iterations")
+    a("--sample_distance_perms", type=int, default=0, help="--sample_distance: with P > 0 also a permutation null of P splits, the "
+      "observed one included -- sinkhorn_p_data and sinkhorn_p_code (one library call a split)")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -270,6 +280,29 @@ def check_args(p, cfg):
             p.error("--sample_test compares simulated binary images: --sample_test_space=data and both need the Bernoulli likelihood")
     elif (cfg.sample_test_perms, cfg.sample_test_kernel, cfg.sample_test_space) != (1000, "rbf", "data"):
         p.error("--sample_test_perms, --sample_test_kernel and --sample_test_space need --sample_test")
+    if cfg.sample_distance < 0 or cfg.sample_distance == 1:
+        p.error("--sample_distance must be 0 (off) or >= 2")
+    if cfg.sample_distance:
+        if cfg.mode != "eval":
+            p.error("--sample_distance needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--sample_distance compares one rank's examples: it is not available with more than one rank")
+        if not 0 <= cfg.sample_distance_perms <= 4096:
+            p.error("--sample_distance_perms must lie in [0, 4096]")
+        if cfg.sample_distance > 1 << 20:
+            p.error("--sample_distance N needs N <= 2^20")
+        if not 1 <= cfg.sinkhorn_iters <= 100000:
+            p.error("--sinkhorn_iters must lie in [1, 100000]")
+        if not (cfg.sinkhorn_blur_rel > 0 and cfg.sinkhorn_blur_rel < float("inf")):
+            p.error("--sinkhorn_blur_rel must be a finite number > 0")
+        if cfg.missing_rate > 0:
+            p.error("--sample_distance is not available with --missing_rate (the samples have every pixel, and the encoders that "
+                    "draw the code take no mask)")
+        if cfg.sample_distance_space != "code" and cfg.likelihood != "bernoulli":
+            p.error("--sample_distance compares simulated binary images: --sample_distance_space=data and both need the Bernoulli "
+                    "likelihood")
+    elif (cfg.sample_distance_space, cfg.sinkhorn_blur_rel, cfg.sinkhorn_iters, cfg.sample_distance_perms) != ("data", 0.1, 200, 0):
+        p.error("--sample_distance_space, --sinkhorn_blur_rel, --sinkhorn_iters and --sample_distance_perms need --sample_distance")
     if cfg.ais_chains < 0 or cfg.ais_temps < 0:
         p.error("--ais_chains and --ais_temps must be >= 0 (0 = off)")
     if bool(cfg.ais_chains) != bool(cfg.ais_temps):

@@ -777,6 +777,10 @@ def run_eval(config):
     st_n, st_imgs = int(getattr(config, "sample_test", 0) or 0), []
     if st_n and world > 1:
         raise ValueError("--sample_test tests one rank's examples: it is not available with more than one rank")
+    # --sample_distance N: the Sinkhorn divergence between N samples of the model and the first N examples of the split (sinkhorn)
+    sd_n, sd_imgs = int(getattr(config, "sample_distance", 0) or 0), []
+    if sd_n and world > 1:
+        raise ValueError("--sample_distance compares one rank's examples: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
         if pc_n > 0:
@@ -791,6 +795,8 @@ def run_eval(config):
             ld_imgs.append(images[:ld_n - first])
         if first < st_n:
             st_imgs.append(images[:st_n - first])
+        if first < sd_n:
+            sd_imgs.append(images[:sd_n - first])
         mk = None if pmask_all is None else pmask_all[first:first + images.shape[0]]
         if iw_n > 0:
             iw_rows.append(eng.iw_bound(images, iw_n, chunk=iw_chunk, row0=first, mask=mk)["bound"])
@@ -1114,6 +1120,23 @@ def run_eval(config):
         res["sample_test"] = tested
         for space, t in tested.items():
             for k, v in ((f"mmd2_{space}", t["mmd2"]), (f"mmd_p_{space}", t["p_value"])):
+                res[f"{config.split}/{k}"] = v.item()
+                if rank == 0:
+                    print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if sd_n:
+        # the transport distance: as many samples of the model as examples, per space the divergence and its convergence readout
+        sd_x = torch.cat(sd_imgs)
+        if sd_x.shape[0] < 2:
+            raise ValueError(f"--sample_distance {sd_n}: the {config.split} split holds {sd_x.shape[0]} examples; it needs two")
+        seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
+        sd_p = int(getattr(config, "sample_distance_perms", 0) or 0)
+        measured = model.sample_distance(sd_x, space=getattr(config, "sample_distance_space", "data"), n_perms=sd_p,
+                                         blur_rel=float(getattr(config, "sinkhorn_blur_rel", 0.1)),
+                                         n_iter=int(getattr(config, "sinkhorn_iters", 200)), **({"seed": seed} if sd_p else {}))
+        res["sample_distance"] = measured
+        for space, t in measured.items():
+            for k, v in ((f"sinkhorn_{space}", t["sinkhorn"]), (f"sinkhorn_marginal_err_{space}", t["marginal_err"])) + \
+                    (((f"sinkhorn_p_{space}", t["p_value"]),) if sd_p else ()):
                 res[f"{config.split}/{k}"] = v.item()
                 if rank == 0:
                     print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")

@@ -202,13 +202,20 @@ def model_test(model, images, n_generations=None, space="data", **kw):
         refuses, the prior draws come from the prior's own distribution on a stream independent of the posterior draw
         (_prior_draws).
     Not with pixel_mask=True.  n_generations defaults to the number of images.  {"data": ..., "code": ...} with the spaces asked for ("both": both)."""
+    return {s: mmd_test(first, second, **kw) for s, (first, second) in model_samples(model, images, n_generations, space).items()}
+
+
+def model_samples(model, images, n_generations=None, space="data", what="sample_test"):
+    """The pairs of samples model.sample_test and model.sample_distance compare, {"data": (simulated x, binarised images), "code":
+    (prior draws, posterior draws)} with the spaces asked for, as model_test describes them; `what` names the caller in the
+    refusals."""
     if space not in SPACES:
         raise ValueError(f"space must be one of {SPACES}: got {space!r}")
     B = images.shape[0]
     n = B if n_generations is None else int(n_generations)
     eng = model._need_engine()
     if eng.pixel_mask:
-        raise ValueError("sample_test is not available with pixel_mask=True (simulate draws every pixel, and the encoders here "
+        raise ValueError(f"{what} is not available with pixel_mask=True (simulate draws every pixel, and the encoders here "
                          "take no mask)")
     out = {}
     sim = None
@@ -216,12 +223,12 @@ def model_test(model, images, n_generations=None, space="data", **kw):
         sim = model.simulate(n)
     if space in ("data", "both"):
         x = torch.as_tensor(images).to(eng.device).reshape(B, -1)
-        out["data"] = mmd_test(sim["x"].float(), (x != 0).float(), **kw)
+        out["data"] = (sim["x"].float(), (x != 0).float())
     if space in ("code", "both"):
         if hasattr(model, "encoder_y"):
             code = model.transform(images)
         else:
             code = model.encoder(images).sample(seed=model.random_seed)
         prior = sim["z"] if sim is not None else _prior_draws(model, n)
-        out["code"] = mmd_test(prior, code.reshape(B, -1), **kw)
+        out["code"] = (prior, code.reshape(B, -1))
     return out

@@ -885,6 +885,40 @@ int gmvae_mmd_workspace_bytes(int N, int D, int P, uint64_t* bytes);
 int gmvae_mmd(const float* z, int N, int D, const uint8_t* assign, int P, int kernel, const double* gamma, int Q, double* mmd2,
               double* row_all, double* row_first, void* workspace, void* stream);
 
+/* The debiased Sinkhorn divergence (Genevay et al. 2018; Feydy et al. 2019) between two weighted samples x [n][D] and y [m][D]
+ * (fp32, device memory) under the cost C(u, v) = 1/2 |u - v|^2: a transport distance in the data's own units, next to gmvae_mmd's
+ * verdict (model independent; gmvae_amd.sinkhorn, model.sample_distance and run_eval's --sample_distance go through it; the
+ * reference has no counterpart).  The statement is tests/sinkhorn_ref.py; the kernels are csrc/sinkhorn.hpp.
+ *   Weights: a [n], b [m] (fp64, device memory), positive; either may be NULL: uniform.  log a - log sum a is taken in fp64 on the
+ *     device, and the outputs' weighted sums divide by sum a, so the weights need not be normalised to the last bit.
+ *   Schedule: eps_dev [n_iter + 1] (fp64, DEVICE memory, read by the kernels; positive, not checked): the temperature of iteration
+ *     t < n_iter and, last, of the final pass.
+ *   Cost: from the expanded square (|zc_i|^2 + |zc_j|^2) / 2 - zc_i . zc_j on the rows centred by the mean of the pooled sample, all
+ *     fp64, clamped at 0 (tests/test_sinkhorn_cpu.py measures the form against differences in longdouble); C_ii = 0 exactly where a
+ *     sample is compared with itself.
+ *   Softmin: softmin_e(pts, h, w)(u) = -e log sum_j w_j exp((h_j - C(u, pts_j)) / e), the exponential fp64, a running (max, sum) per
+ *     row.
+ *   Iteration: f, g, p, q start at 0.  For t < n_iter, e = eps_dev[t]: f <- softmin(y, g, b) at x, p <- (p + softmin(x, p, a) at x) /
+ *     2, q <- (q + softmin(y, q, b) at y) / 2; then g <- softmin(x, f, a) at y with the new f, and p and q averaged once more.  Last
+ *     pass at e = eps_dev[n_iter]: f' = softmin(y, g, b) at x, p' = softmin(x, p, a) at x, q' = softmin(y, q, b) at y, not averaged.
+ *   Outputs (fp64, device memory): f [n] = f', g [m], p [n] = p', q [m] = q'; out [4] = (S, part_x, part_y, marginal_err) with
+ *     part_x = <a, f' - p'>, part_y = <b, g - q'>, S = part_x + part_y and marginal_err = max_i |expm1((f_i - f'_i) / eps_dev[n_iter])|,
+ *     the relative error of the transport plan's row marginals (the column marginals are exact after the second half-step): the
+ *     convergence readout.  S is not converged unless marginal_err is small, and it has no zero point at finite n.
+ * Nothing of size n m is stored: the workspace (gmvae_sinkhorn_workspace_bytes(n, m, D), which reads no device memory) holds a
+ * (max, sum) pair per row, problem and column slab -- at most 2 * 3 * 16 max(n, m) doubles --, 3 (n + m) doubles per row and at most
+ * 65 D for the mean; it needs no initialisation.  Four set-up launches, two per half-step (the half-step's three softmins are the
+ * problems of one launch) and one at the end, enqueued on `stream` with no host synchronisation.
+ * One owner per output, fixed-order fp64 sums (the order follows from n and m alone), no float atomics: two calls give the same bits.
+ * Sizes: 1 <= n, m <= 2^20, 1 <= D <= 4096, 1 <= n_iter <= 100000.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (the sizes above); GMVAE_E_NULL (x, y, eps_dev, f, g, p, q, out,
+ * workspace); GMVAE_E_ALIGN (x and y 4 bytes, every fp64 array 8, the workspace 16). */
+int gmvae_sinkhorn_workspace_bytes(int64_t n, int64_t m, int D, uint64_t* bytes);
+int gmvae_sinkhorn(const float* x, int64_t n, const float* y, int64_t m, int D, const double* a /* [n], nullable = uniform */,
+                   const double* b /* [m], nullable = uniform */, const double* eps_dev /* [n_iter + 1], device */, int n_iter,
+                   double* f, double* g, double* p, double* q, double* out /* [4]: S, part_x, part_y, marginal_err */,
+                   void* workspace, void* stream);
+
 /* log p(x) by annealed importance sampling (AIS) with Hamiltonian Monte Carlo transitions (Neal 2001; Wu, Burda, Salakhutdinov &
  * Grosse 2017): the generative model alone, so -- unlike gmvae_iw_bound* -- its gap does not depend on the inference network, and
  * it tightens towards log p(x) as n_temps grows (Engine.ais_bound, model.ais_bound and run_gmvae --mode=eval --ais_chains go
