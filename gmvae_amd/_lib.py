@@ -90,6 +90,10 @@ def _load():
         "gmvae_mmd": ([vp, i32, i32, vp, i32, i32, C.POINTER(C.c_double), i32, vp, vp, vp, vp, vp], i32),
         "gmvae_sinkhorn_workspace_bytes": ([i64, i64, i32, C.POINTER(u64)], i32),
         "gmvae_sinkhorn": ([vp, i64, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp], i32),
+        "gmvae_pca_workspace_bytes": ([i64, i32, i32, C.POINTER(u64)], i32),
+        "gmvae_pca_fit": ([vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "gmvae_pca_transform": ([vp, i64, i32, i32, vp, vp, vp, vp, vp], i32),
+        "gmvae_sym_eigh": ([vp, i32, i32, vp, vp, vp, vp, vp], i32),
         "gmvae_ais_workspace_bytes": ([dp, i32, i32, i32, C.POINTER(u64)], i32),
         "gmvae_ais": ([dp, i32, vp, vp, vp, i32, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64, vp], i32),
         "gmvae_simulate_workspace_bytes": ([dp, i32, C.POINTER(u64)], i32),

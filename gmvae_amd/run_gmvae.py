@@ -125,6 +125,18 @@ def build_parser():
     a("--sinkhorn_iters", type=int, default=200, help="--sample_distance: the iterations")
     a("--sample_distance_perms", type=int, default=0, help="--sample_distance: with P > 0 also a permutation null of P splits, the "
       "observed one included -- sinkhorn_p_data and sinkhorn_p_code (one library call a split)")
+    a("--latent_pca", type=int, default=0, help="eval: also report the principal component spectrum of the latent code of the first N "
+      "examples of the split (gmvae_amd.pca.fit on the device) -- latent_pca_dim90 (the components that reach 90 %% of the variance), "
+      "latent_pca_participation ((sum lambda)^2 / sum lambda^2), latent_pca_top_ratio, latent_pca_offdiag (the solver's convergence "
+      "readout) and latent_pca; 0 = off")
+    a("--tsne_init", default="random", choices=["random", "pca"], help="--embed_latent: start from 1e-4 x normals (the default), or "
+      "from the code's first two principal components (scikit-learn's default since 1.2)")
+    a("--pca_baseline", type=int, default=0, help="--fit_latent_mixture: also the PCA + GMM baseline -- the first N examples as the "
+      "encoder reads them, projected on their first k principal components (gmvae_amd.pca), fitted with the same mixture settings -- "
+      "pca_mixture_loglik, cluster_acc_pca_mixture and pca_residual_max (the subspace iteration's convergence readout); 0 = off")
+    a("--sample_frechet", type=int, default=0, help="eval: also report frechet_code, the Frechet distance (gmvae_amd.pca) between the "
+      "Gaussians fitted to the two code samples --sample_test --sample_test_space=code compares, N examples each; needs "
+      "--latent_size <= 128; 0 = off")
     a("--y_inference", default="gumbel", choices=["gumbel", "marginal", "marginal_iw"], help="gmvae: one Gumbel-softmax draw "
       "of y (the reference), y summed out exactly over the mixture components, or y summed out with --n_samples importance "
       "samples of z per component (marginal_iw)")
@@ -303,6 +315,39 @@ def check_args(p, cfg):
                     "likelihood")
     elif (cfg.sample_distance_space, cfg.sinkhorn_blur_rel, cfg.sinkhorn_iters, cfg.sample_distance_perms) != ("data", 0.1, 200, 0):
         p.error("--sample_distance_space, --sinkhorn_blur_rel, --sinkhorn_iters and --sample_distance_perms need --sample_distance")
+    if cfg.latent_pca < 0 or cfg.latent_pca == 1:
+        p.error("--latent_pca must be 0 (off) or >= 2")
+    if cfg.latent_pca:
+        if cfg.mode != "eval":
+            p.error("--latent_pca needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--latent_pca fits one rank's codes: it is not available with more than one rank")
+        if cfg.latent_size > 4096:
+            p.error("--latent_pca needs --latent_size <= 4096")
+    if cfg.tsne_init != "random" and not cfg.embed_latent:
+        p.error("--tsne_init needs --embed_latent")
+    if cfg.pca_baseline < 0:
+        p.error("--pca_baseline must be >= 0 (0 = off)")
+    if cfg.pca_baseline:
+        if not cfg.fit_latent_mixture:
+            p.error("--pca_baseline needs --fit_latent_mixture")
+        if cfg.pca_baseline > 128:
+            p.error("--pca_baseline k needs k <= 128")
+        if cfg.fit_latent_mixture < 2:
+            p.error("--pca_baseline needs --fit_latent_mixture N with N >= 2")
+        if cfg.missing_rate > 0:
+            p.error("--pca_baseline is not available with --missing_rate (it projects every pixel)")
+    if cfg.sample_frechet < 0 or cfg.sample_frechet == 1:
+        p.error("--sample_frechet must be 0 (off) or >= 2")
+    if cfg.sample_frechet:
+        if cfg.mode != "eval":
+            p.error("--sample_frechet needs --mode=eval")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--sample_frechet compares one rank's examples: it is not available with more than one rank")
+        if cfg.latent_size > 128:
+            p.error("--sample_frechet needs --latent_size <= 128")
+        if cfg.missing_rate > 0:
+            p.error("--sample_frechet is not available with --missing_rate (the encoders that draw the code take no mask)")
     if cfg.ais_chains < 0 or cfg.ais_temps < 0:
         p.error("--ais_chains and --ais_temps must be >= 0 (0 = off)")
     if bool(cfg.ais_chains) != bool(cfg.ais_temps):

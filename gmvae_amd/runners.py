@@ -17,7 +17,7 @@ from typing import Iterator, Tuple
 import numpy as np
 import torch
 
-from . import gmvae, linprobe, mixfit, neighbours, parallel, tsne, utils, vae
+from . import gmvae, linprobe, mixfit, neighbours, parallel, pca, tsne, twosample, utils, vae
 
 
 # ------------------------------------------------------------------ data
@@ -781,8 +781,24 @@ def run_eval(config):
     sd_n, sd_imgs = int(getattr(config, "sample_distance", 0) or 0), []
     if sd_n and world > 1:
         raise ValueError("--sample_distance compares one rank's examples: it is not available with more than one rank")
+    # --latent_pca N: the spectrum of the code of the first N examples of the split (pca.fit)
+    lpca_n = int(getattr(config, "latent_pca", 0) or 0)
+    if lpca_n and world > 1:
+        raise ValueError("--latent_pca fits one rank's codes: it is not available with more than one rank")
+    # --pca_baseline k: PCA + GMM on the examples --fit_latent_mixture fits, as the encoder reads them
+    pb_k, pb_imgs = int(getattr(config, "pca_baseline", 0) or 0), []
+    if pb_k and not mf_n:
+        raise ValueError("--pca_baseline needs --fit_latent_mixture")
+    # --sample_frechet N: the Frechet distance between the two code samples --sample_test compares (pca.frechet_distance)
+    sf_n, sf_imgs = int(getattr(config, "sample_frechet", 0) or 0), []
+    if sf_n and world > 1:
+        raise ValueError("--sample_frechet compares one rank's examples: it is not available with more than one rank")
     for images, labels, first in create_dataset(config, config.split, shuffle=False, repeat=False, with_index=True,
                                                 standardize=getattr(model, "standardize", None)):
+        if pb_k and first < mf_n:
+            pb_imgs.append(images[:mf_n - first])
+        if first < sf_n:
+            sf_imgs.append(images[:sf_n - first])
         if pc_n > 0:
             po = eng.posterior_component(images, pc_n, chunk=iw_chunk, row0=first)
             pc_rows.append(po["log_post"])
@@ -1020,7 +1036,8 @@ def run_eval(config):
         seed = int(config.random_seed) if getattr(config, "random_seed", None) is not None else 0
         em_codes = res["latent_state"][:em_n]
         _check_embed_size(config, em_n, em_codes.shape[0], perp)
-        emb = tsne.embed(em_codes, perplexity=perp, n_iter=iters, seed=seed)
+        emb = tsne.embed(em_codes, perplexity=perp, n_iter=iters, seed=seed,
+                         init="pca" if getattr(config, "tsne_init", "random") == "pca" else None)
         res["latent_embedding"] = emb["embedding"]
         res[f"{config.split}/embedding_kl"] = emb["kl"].item()
         smp = res["samples"]
@@ -1050,6 +1067,49 @@ def run_eval(config):
         if rank == 0:
             for k in ("latent_mixture_loglik", "cluster_acc_latent_mixture") + (("latent_mixture_bic",) if getattr(config, "mixture_bic", False) else ()):
                 print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if pb_k:
+        # the "PCA + GMM" baseline: the same examples as the encoder reads them (binary under the Bernoulli likelihood, else the
+        # values themselves), projected on their first k principal components, fitted with the latent fit's settings
+        pb_x = torch.cat(pb_imgs).to(eng.device)
+        pb_x = pb_x.reshape(pb_x.shape[0], -1)
+        pb_x = (pb_x != 0).float() if eng.likelihood == "bernoulli" else pb_x.float()
+        n, D = pb_x.shape
+        if n < max(2, K) or D > pca.MAX_D or pb_k > min(D, pca.MAX_M):
+            raise ValueError(f"--pca_baseline {pb_k}: needs at least max(2, --mixture_components) examples (the split gave {n}), a data "
+                             f"dimension of at most {pca.MAX_D} (it is {D}) and k <= min(data dimension, {pca.MAX_M})")
+        pb_fit = pca.fit(pb_x, n_components=pb_k, seed=seed)
+        if int(pb_fit["info"].item()) != 0:
+            raise ValueError(f"--pca_baseline {pb_k}: the {n} examples span fewer dimensions than the subspace iteration's "
+                             f"{min(pb_k + pca.OVERSAMPLE, pca.MAX_M, D)} vectors: lower k or fit more examples")
+        pb_z = pca.transform(pb_x, pb_fit)
+        pb_mix = mixfit.fit(pb_z, K, n_iter=int(getattr(config, "mixture_fit_iters", 100)),
+                            n_init=int(getattr(config, "mixture_fit_inits", 1)), seed=seed,
+                            covariance=getattr(config, "mixture_covariance", "diag"))
+        pb_as = mixfit.assign(pb_z, pb_mix)
+        res[f"{config.split}/pca_mixture_loglik"] = pb_as["lse"].double().mean().item()
+        res[f"{config.split}/cluster_acc_pca_mixture"] = utils.cluster_acc(pb_as["log_resp"], res["labels"][:n], K).item()
+        res[f"{config.split}/pca_residual_max"] = pb_fit["residual"].max().item()
+        res["pca_baseline"] = {"pca": pb_fit, "mixture": pb_mix}
+        if rank == 0:
+            for k in ("pca_mixture_loglik", "cluster_acc_pca_mixture", "pca_residual_max"):
+                print(f"{config.split}/{k}: {res[f'{config.split}/{k}']}")
+    if lpca_n:
+        # the rotation-invariant counterpart of the active units: the spectrum of the code's covariance
+        lp_fit = pca.fit(res["latent_state"][:lpca_n])
+        res["latent_pca"] = lp_fit
+        for k, v in {**pca.spectrum_summary(lp_fit), "offdiag": lp_fit["offdiag"]}.items():
+            res[f"{config.split}/latent_pca_{k}"] = v.item()
+            if rank == 0:
+                print(f"{config.split}/latent_pca_{k}: {res[f'{config.split}/latent_pca_{k}']}")
+    if sf_n:
+        sf_x = torch.cat(sf_imgs)
+        if sf_x.shape[0] < 2:
+            raise ValueError(f"--sample_frechet {sf_n}: the {config.split} split holds {sf_x.shape[0]} examples; it needs two")
+        prior, code = twosample.model_samples(model, sf_x, None, "code", what="--sample_frechet")["code"]
+        res["sample_frechet"] = pca.frechet_distance(prior, code)
+        res[f"{config.split}/frechet_code"] = res["sample_frechet"]["distance"].item()
+        if rank == 0:
+            print(f"{config.split}/frechet_code: {res[f'{config.split}/frechet_code']}")
     if ns_n:
         # the model's own clustering, where it has one: the GMVAE's argmax q(y|x), the VAE_GMP's posterior over its prior's
         # components (--component_posterior_samples); then the fitted mixture's assignment, then the embedding's neighbourhoods

@@ -61,7 +61,9 @@ def embed(codes, perplexity=40.0, n_iter=300, early_exaggeration=12.0, exaggerat
     """The 2-D embedding of codes [N, L]: a dict of `embedding` [N, 2], `kl` (at the embedding, a 0-d tensor), `kl_history`
     [n_iter] (the KL each iteration started from), `beta` and `entropy` [N].  The defaults are the reference's call under
     scikit-learn's defaults: early exaggeration 12 with momentum 0.5 for the first min(250, n_iter) iterations, then 1 and
-    0.8; learning_rate "auto" = max(N / 48, 50); init: 1e-4 * Philox normals keyed by `seed` unless an [N, 2] tensor is given.
+    0.8; learning_rate "auto" = max(N / 48, 50); init: 1e-4 * Philox normals keyed by `seed` unless an [N, 2] tensor is given, or
+    "pca" (scikit-learn's default since 1.2): the codes' first two principal components, the first scaled to standard deviation
+    1e-4 (gmvae_amd.pca.tsne_init).
     Everything stays on the device; nothing synchronises with the host."""
     dev = L.require_gpu()
     codes = torch.as_tensor(codes).to(dev, torch.float32).contiguous()
@@ -79,6 +81,11 @@ def embed(codes, perplexity=40.0, n_iter=300, early_exaggeration=12.0, exaggerat
     beta, logz, entropy = affinities(codes, perplexity, rows, ws)
     if init is None:
         y = initial_embedding(N, seed, dev)
+    elif isinstance(init, str):
+        if init != "pca":
+            raise ValueError(f'init must be None, "pca" or an [N, 2] tensor: got {init!r}')
+        from . import pca
+        y = pca.tsne_init(codes)
     else:
         y = torch.as_tensor(init).to(dev, torch.float32).contiguous().clone()
         if y.shape != (N, 2):

@@ -166,6 +166,12 @@ class TrainableVAE(VAE):
         return linprobe.model_probe(self, train_images, train_labels, test_images, test_labels, n_classes=n_classes,
                                     labelled_per_class=labelled_per_class, seed=seed, **fit_kw)
 
+    def latent_pca(self, images, **kw):
+        """The principal components and the spectrum of the codes self.transform(images) on the device (gmvae_amd.pca.fit(**kw)), with
+        spectrum_summary's rotation-invariant readouts `dim90`, `participation` and `top_ratio` in the same dict."""
+        from . import pca
+        return pca.model_latent_pca(self, images, **kw)
+
     def sample_test(self, images, n_generations=None, space="data", **kw):
         """The kernel two-sample test of the model's samples against `images` on the device (gmvae_amd.twosample.mmd_test(**kw):
         n_perms, kernel, bandwidth, scales, seed): space "data" -- simulate(n_generations)["x"] against the binarised images

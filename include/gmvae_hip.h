@@ -919,6 +919,42 @@ int gmvae_sinkhorn(const float* x, int64_t n, const float* y, int64_t m, int D, 
                    double* f, double* g, double* p, double* q, double* out /* [4]: S, part_x, part_y, marginal_err */,
                    void* workspace, void* stream);
 
+/* Principal component analysis of N rows x [N][D] (fp32, device memory), and the small dense symmetric eigensolver under it (model
+ * independent; gmvae_amd.pca, model.latent_pca, tsne.embed(init="pca") and run_eval's --latent_pca, --pca_baseline, --sample_frechet
+ * and --tsne_init go through it; the reference has no counterpart).  The statement is tests/pca_ref.py; the kernels are
+ * csrc/pca.hpp.
+ *   mu = (1/N) sum_n x_n and C = (1/(N - 1)) sum_n (x_n - mu)(x_n - mu)^T in fp64, every row centred BEFORE the product (never the
+ *     expanded square), on the fp64 MFMA; C stays in the workspace.
+ *   gmvae_sym_eigh: A [n][n] (fp64, symmetric; the lower triangle is read), n <= 128 -> w_out [n] descending (ties by original index)
+ *     and V_out [n][n] with the eigenvectors in its COLUMNS, each signed so that its entry of largest magnitude (the first such
+ *     index) is positive; offdiag_out [1] (may be NULL) = max |off-diagonal| / max |diagonal| of the rotated matrix, the convergence
+ *     readout (0 where the diagonal is 0).  Cyclic Jacobi in one workgroup, round-robin ordering, EXACTLY n_sweeps sweeps; its
+ *     workspace is n n doubles.
+ *   gmvae_pca_fit: D <= 128 (then m = D): the solver on C; components_out [k][D] = the first k eigenvectors as rows, variance_out
+ *     [k] their eigenvalues, residual_out [k] = 0.  D > 128: subspace iteration on the stored C (no further pass over x) from V0
+ *     [D][m] (fp64, orthonormal columns, device memory): n_iter times W = C V, G = W^T W = R R^T, V = W R^-T; then W = C V, T = 1/2
+ *     (V^T W + W^T V) = Q diag(theta) Q^T by the solver; components = the first k columns of V Q (signed as above), variance =
+ *     theta, residual_j = |W q_j - theta_j V q_j|_2: the result is converged only as far as residual says.  mean_out [D]; stats_out
+ *     [4] = tr C, the solver's offdiag, N, reserved (0); info_out [1] (int32, may be NULL) = 0, or 1 + the index of the first
+ *     pivot of a factorisation of G that is not > 0 (the data's rank is below m): every output is then NaN except mean_out,
+ *     stats_out[0] and stats_out[2].  At most 6 launches for D <= 128 and 10 + 3 n_iter and one copy for D > 128, none synchronising
+ *     with the host.
+ *   gmvae_pca_transform: z_out [N][k] (fp32) = ((x - mean) . components^T) . scale (scale [k] may be NULL = 1): every product an fp64
+ *     product of an fp64-centred value, the sums fp64 in ascending d, rounded once.  Needs no workspace.
+ * One owner per sum, fixed-order fp64 folds, no float atomics: two calls give the same bits.
+ * Sizes: 2 <= N <= 2^24 (transform: 1 <= N), 1 <= D <= 4096, 1 <= k <= m <= min(D, 128), m = D where D <= 128, n_iter >= 0,
+ * n_sweeps >= 1.  The workspace (gmvae_pca_workspace_bytes(N, D, m), which reads no device memory) needs no initialisation.
+ * Checks, before any launch, in this order: GMVAE_E_DIMS (the sizes above); GMVAE_E_NULL (any pointer not marked "may be NULL"; V0
+ * may be NULL where D <= 128); GMVAE_E_ALIGN (x and z_out 4 bytes, every fp64 array 8, the workspace 16). */
+int gmvae_pca_workspace_bytes(int64_t N, int D, int m, uint64_t* bytes);
+int gmvae_pca_fit(const float* x, int64_t N, int D, int k, int m, int n_iter, int n_sweeps, const double* V0, double* mean_out,
+                  double* components_out, double* variance_out, double* residual_out, double* stats_out, int32_t* info_out,
+                  void* workspace, void* stream);
+int gmvae_pca_transform(const float* x, int64_t N, int D, int k, const double* mean, const double* components, const double* scale,
+                        float* z_out, void* stream);
+int gmvae_sym_eigh(const double* A, int n, int n_sweeps, double* w_out, double* V_out, double* offdiag_out, void* workspace,
+                   void* stream);
+
 /* log p(x) by annealed importance sampling (AIS) with Hamiltonian Monte Carlo transitions (Neal 2001; Wu, Burda, Salakhutdinov &
  * Grosse 2017): the generative model alone, so -- unlike gmvae_iw_bound* -- its gap does not depend on the inference network, and
  * it tightens towards log p(x) as n_temps grows (Engine.ais_bound, model.ais_bound and run_gmvae --mode=eval --ais_chains go
