@@ -17,9 +17,8 @@ SRC_NEIGH = os.path.join(HERE, "csrc", "neigh.hip")        # and a fourth
 SRC_AIS = os.path.join(HERE, "csrc", "ais.hip")            # and a fifth: gmvae_ais, gmvae_refine, gmvae_simulate, gmvae_ais_reverse (ais.hpp's kernels, defined once)
 SRC_IMPUTE = os.path.join(HERE, "csrc", "impute.hip")      # and a sixth: gmvae_impute's kernels (its host path is iw_run in gmvae_hip.hip)
 SRC_LINPROBE = os.path.join(HERE, "csrc", "linprobe.hip")  # and a seventh: gmvae_linprobe_*
-SRC_TWOSAMPLE = os.path.join(HERE, "csrc", "twosample.hip")  # and an eighth: gmvae_mmd
-SRC_SINKHORN = os.path.join(HERE, "csrc", "sinkhorn.hip")    # and a ninth: gmvae_sinkhorn
-SRC_PCA = os.path.join(HERE, "csrc", "pca.hip")              # and a tenth: gmvae_pca_*, gmvae_sym_eigh
+SRC_TWOSAMPLE = os.path.join(HERE, "csrc", "twosample.hip")  # and an eighth: gmvae_mmd, gmvae_sinkhorn (cgram.hpp's kernels, defined once)
+SRC_PCA = os.path.join(HERE, "csrc", "pca.hip")              # and a ninth: gmvae_pca_*, gmvae_sym_eigh
 import glob
 DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*"))) + [os.path.join(ROOT, "include", "gmvae_hip.h")]
 OUT = os.path.join(HERE, "lib", "libgmvae_hip.so")
@@ -41,7 +40,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     # first layer's addresses need no round trip into the cold argument block); translation-unit wide, and a kernel keeps a
     # prologue of ordinary loads for firmware that does not preload
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
-           "-mllvm", "-amdgpu-kernarg-preload-count=14", "-o", OUT, SRC, SRC_EVAL, SRC_MIXFIT, SRC_NEIGH, SRC_AIS, SRC_IMPUTE, SRC_LINPROBE, SRC_TWOSAMPLE, SRC_SINKHORN, SRC_PCA]
+           "-mllvm", "-amdgpu-kernarg-preload-count=14", "-o", OUT, SRC, SRC_EVAL, SRC_MIXFIT, SRC_NEIGH, SRC_AIS, SRC_IMPUTE, SRC_LINPROBE, SRC_TWOSAMPLE, SRC_PCA]
     # PyTorch-ROCm ships its own libamdhip64.so (soname without the .7).  Link against THAT
     # copy so that the process holds one HIP runtime: streams and device pointers handed over
     # by torch are then valid inside this library whatever the import order.

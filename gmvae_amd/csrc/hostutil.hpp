@@ -1,4 +1,4 @@
-// What the host sides of the translation units (gmvae_hip.hip, tsne.hip, mixfit.hip, neigh.hip, ais.hip, linprobe.hip, twosample.hip, sinkhorn.hip) share: pointer
+// What the host sides of the translation units (gmvae_hip.hip, tsne.hip, mixfit.hip, neigh.hip, ais.hip, linprobe.hip, twosample.hip) share: pointer
 // alignment (a null pointer is aligned), the workspaces' 256-byte rounding, the once-per-device guard, and the evaluators' pointer
 // ladder and LDS attribute.
 #pragma once

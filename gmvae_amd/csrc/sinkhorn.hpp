@@ -1,4 +1,4 @@
-// gmvae_sinkhorn (include/gmvae_hip.h; host side: csrc/sinkhorn.hip): the debiased Sinkhorn divergence (Genevay et al. 2018; Feydy
+// gmvae_sinkhorn (include/gmvae_hip.h; host side: csrc/twosample.hip): the debiased Sinkhorn divergence (Genevay et al. 2018; Feydy
 // et al. 2019) between two weighted samples x [n][D] and y [m][D] under the cost C(u, v) = 1/2 |u - v|^2.  Model independent.
 // The statement is tests/sinkhorn_ref.py:
 //   softmin_e(pts, h, w)(u) = -e log sum_j w_j exp((h_j - C(u, pts_j)) / e)
@@ -7,20 +7,16 @@
 //     half B: g <- softmin(x, f, a) at y;  p and q once more
 //   last pass at e = eps[T]: f' = softmin(y, g, b) at x, p' = softmin(x, p, a) at x, q' = softmin(y, q, b) at y, none averaged
 //   part_x = <a, f' - p'>, part_y = <b, g - q'>, S = part_x + part_y, marginal_err = max_i |expm1((f_i - f'_i) / eps[T])|
-// Nothing n m in memory, nothing synchronises with the host, e is read from the device.  The cost comes from the expanded square
-// (n_i + n_j) / 2 - zc_i . zc_j on the rows centred by the pooled mean (fp64; n_i = |zc_i|^2), clamped at 0, the dot products on
-// v_mfma_f64_16x16x4_f64 -- csrc/twosample.hpp's form for rbf, and its three launches in front (sk_mean_part, sk_mean_fold,
-// sk_norms over the pooled rows: x's, then y's); sk_logw leaves log w - log sum w and sum w of both samples.
+// Nothing n m in memory, nothing synchronises with the host, e is read from the device.  The cost (n_i + n_j) / 2 - zc_i . zc_j,
+// clamped at 0, comes from the centred Gram tile of csrc/cgram.hpp over the pooled rows (x's, then y's), with its three launches in
+// front; sk_logw leaves log w - log sum w and sum w of both samples.
 // A softmin is a row-wise log-sum-exp over a cost matrix.  The two or three of a half-step depend on nothing of each other, so
 // they are the PROBLEMS of one launch (blockIdx.z): a problem is (the rows it is evaluated at, the columns it sums over, h, log w),
 // rows and columns each a range of the pooled rows.
-// sk_tiles: a workgroup of eight waves owns kSkRows = 32 rows i of its problem and a slab of column tiles of kSkCols = 64 rows j
+// sk_tiles: a workgroup of eight waves owns kCgRows = 32 rows i of its problem and a slab of column tiles of kCgCols = 64 rows j
 // (blockIdx.y; the slabs follow from n and m alone, sk_plan; a problem with fewer tiles than slabs leaves its last slabs empty:
 // (-inf, 0)).  A workgroup whose row tile lies past its problem's rows leaves before any barrier.  Per column tile:
-//   gram:   D in chunks of kSkDChunk = 32 staged as fp32 [32][33] and [64][33] (and the mean's chunk), each chunk loaded into
-//           registers while the one before it is summed; wave w owns the 16 x 16 block (w >> 2, w & 3) of the tile, eight MFMA
-//           steps a chunk, the operands centred on the way in (A: lane & 15 the row, lane >> 4 the dimension of the step; D: entry
-//           c of a lane is row (lane >> 4) + 4 c, column lane & 15);
+//   gram:   cgram.hpp's pass over D in chunks (cg_fetch, cg_stage, cg_mfma): the wave's four entries of zc_i . zc_j;
 //   s tile: s_ij = logw_j + (h_j - C_ij) / e into the tile [32][65] (fp64); C_ii = 0 exactly on a symmetric problem, -inf in a
 //           column past the end;
 //   max:    thread i < 32 takes its row's largest s of the tile and with it the row's new running maximum M';
@@ -37,43 +33,27 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "cgram.hpp"
+
 namespace gmvae {
 
-constexpr int kSkBlock = 512;             // sk_tiles: eight waves
-constexpr int kSkSmallBlock = 256;        // every other kernel here
-constexpr int kSkRows = 32;               // rows i of a workgroup: two 16-row MFMA blocks
-constexpr int kSkCols = 64;               // rows j of a column tile: four 16-column MFMA blocks
-constexpr int kSkDChunk = 32;             // dimensions staged at a time
-constexpr int kSkStage = (kSkRows + kSkCols) * kSkDChunk / kSkBlock;      // floats of a chunk a thread of sk_tiles stages
-constexpr int kSkMaxSlabs = 16;
-constexpr int kSkFillGroups = 256;        // the slabs fill about this many workgroups a problem where the row tiles alone do not
-constexpr int kSkMeanSlices = 64;         // row slices of the mean, 1024 rows each at least
-constexpr int kSkKld = kSkCols + 1;       // the s tile's leading dimension (doubles)
-constexpr int kSkZld = kSkDChunk + 1;     // the staged rows' (floats)
+constexpr int kSkSmallBlock = 256;        // every kernel here but sk_tiles
 constexpr int kSkProblems = 3;
-
-typedef double sk_d4 __attribute__((ext_vector_type(4)));
 
 // the launches' shape: the slabs and slices, and so the order of every sum, follow from (n, m) alone
 struct SkPlan {
   int R;               // max(n, m): the rows of the larger problem
   int row_tiles;       // of the larger problem: the grid's x
   int slabs;
-  int mean_slices, rows_per_slice;
+  CgSlices mean;
 };
 __host__ __device__ static inline SkPlan sk_plan(int n, int m) {
   SkPlan p;
   p.R = n > m ? n : m;
-  p.row_tiles = (p.R + kSkRows - 1) / kSkRows;
-  const int col_tiles = (p.R + kSkCols - 1) / kSkCols;
-  int s = p.row_tiles >= kSkFillGroups ? 1 : (kSkFillGroups + p.row_tiles - 1) / p.row_tiles;
-  s = s > kSkMaxSlabs ? kSkMaxSlabs : s;
-  p.slabs = s > col_tiles ? col_tiles : s;
-  const int N = n + m;
-  int ms = (N + 1023) / 1024;
-  ms = ms > kSkMeanSlices ? kSkMeanSlices : ms;
-  p.rows_per_slice = (N + ms - 1) / ms;
-  p.mean_slices = (N + p.rows_per_slice - 1) / p.rows_per_slice;
+  p.row_tiles = (p.R + kCgRows - 1) / kCgRows;
+  const int col_tiles = (p.R + kCgCols - 1) / kCgCols;
+  p.slabs = cg_slabs(p.row_tiles, col_tiles);
+  p.mean = cg_mean_slices(n + m);
   return p;
 }
 
@@ -92,7 +72,7 @@ __host__ __device__ static inline SkLayout sk_layout(const SkPlan& p, int n, int
   o.wsum = o.logw + (size_t)n + m;
   o.nrm = o.wsum + 2;
   o.mean_part = o.nrm + (size_t)n + m;
-  o.mean = o.mean_part + (size_t)p.mean_slices * D;
+  o.mean = o.mean_part + (size_t)p.mean.slices * D;
   o.end = o.mean + (size_t)D;
   return o;
 }
@@ -110,52 +90,6 @@ struct SkProbs {
   SkProb p[kSkProblems];
 };
 __device__ static inline SkProb sk_pick(const SkProbs& P, const int z) { return z == 0 ? P.p[0] : z == 1 ? P.p[1] : P.p[2]; }
-
-// pooled row g < n + m, dimension d
-__device__ static inline float sk_at(const float* __restrict__ x, const int n, const float* __restrict__ y, const int D, const int g,
-                                     const int d) {
-  return g < n ? x[(size_t)g * D + d] : y[(size_t)(g - n) * D + d];
-}
-
-// the pooled mean, first pass: workgroup (x, y) adds the rows of slice y in 64 columns; thread (r, c) the rows r, r + 4, ... in order
-__global__ __launch_bounds__(kSkSmallBlock) void sk_mean_part(const float* __restrict__ x, const int n, const float* __restrict__ y, const int m,
-                                                               const int D, const int rows_per_slice, double* __restrict__ part) {
-  __shared__ double s[4][64];
-  const int tid = threadIdx.x, r = tid >> 6, cl = tid & 63, c = blockIdx.x * 64 + cl, N = n + m;
-  const int lo = blockIdx.y * rows_per_slice, hi = lo + rows_per_slice < N ? lo + rows_per_slice : N;
-  double a = 0.0;
-  if (c < D)
-    for (int i = lo + r; i < hi; i += 4) a += (double)sk_at(x, n, y, D, i, c);
-  s[r][cl] = a;
-  __syncthreads();
-  if (r == 0 && c < D) part[(size_t)blockIdx.y * D + c] = ((s[0][cl] + s[1][cl]) + s[2][cl]) + s[3][cl];
-}
-
-// ... second pass: the slices in order
-__global__ __launch_bounds__(kSkSmallBlock) void sk_mean_fold(const double* __restrict__ part, const int slices, const int N, const int D,
-                                                               double* __restrict__ mean) {
-  const int d = blockIdx.x * kSkSmallBlock + threadIdx.x;
-  if (d >= D) return;
-  double a = 0.0;
-  for (int s = 0; s < slices; ++s) a += part[(size_t)s * D + d];
-  mean[d] = a / (double)N;
-}
-
-// |z_i - mean|^2 of the pooled rows: a wave per row, a lane the dimensions lane, lane + 64, ... in order, then the lanes by six
-// exchanges
-__global__ __launch_bounds__(kSkSmallBlock) void sk_norms(const float* __restrict__ x, const int n, const float* __restrict__ y, const int m,
-                                                           const int D, const double* __restrict__ mean, double* __restrict__ nrm) {
-  const int lane = threadIdx.x & 63, i = blockIdx.x * (kSkSmallBlock / 64) + (threadIdx.x >> 6);
-  if (i >= n + m) return;      // (uniform in the wave)
-  double a = 0.0;
-  for (int d = lane; d < D; d += 64) {
-    const double e = (double)sk_at(x, n, y, D, i, d) - mean[d];
-    a = fma(e, e, a);
-  }
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) a += __shfl_xor(a, k);
-  if (lane == 0) nrm[i] = a;
-}
 
 // workgroup 0: a [n] -> logw[0 .. n), wsum[0]; workgroup 1: b [m] -> logw[n ..), wsum[1].  The sum: 256 runs of consecutive
 // entries, then the runs in order.  No weights: uniform, log w = -log count and the sum 1.
@@ -190,19 +124,18 @@ __global__ __launch_bounds__(kSkSmallBlock) void sk_logw(const double* __restric
   for (int i = tid; i < cnt; i += kSkSmallBlock) out[i] = log(w[i]) - lt;
 }
 
-__global__ __launch_bounds__(kSkBlock) void sk_tiles(const float* __restrict__ x, const int n, const float* __restrict__ y, const int D,
+__global__ __launch_bounds__(kCgBlock) void sk_tiles(const float* __restrict__ x, const int n, const float* __restrict__ y, const int D,
                                                       const SkProbs probs, const int slabs, const int R, const double* __restrict__ eps,
                                                       const double* __restrict__ mean, const double* __restrict__ nrm,
                                                       double* __restrict__ part_max, double* __restrict__ part_sum) {
-  __shared__ double s_k[kSkRows * kSkKld];      // the s tile, then its exponentials
-  __shared__ double s_mean[kSkDChunk];
-  __shared__ double s_h[kSkCols], s_lw[kSkCols], s_nj[kSkCols];      // the tile's columns: h, log w, the squared norm
-  __shared__ double s_ni[kSkRows], s_mx[kSkRows];                    // the rows' squared norms and new running maxima
-  __shared__ float s_zi[(kSkRows + kSkCols) * kSkZld];               // [kSkRows][kSkZld], then s_zj [kSkCols][kSkZld]
-  float* const s_zj = s_zi + kSkRows * kSkZld;
+  __shared__ double s_k[kCgRows * kCgKld];      // the s tile, then its exponentials
+  __shared__ double s_mean[kCgDChunk];
+  __shared__ double s_h[kCgCols], s_lw[kCgCols], s_nj[kCgCols];      // the tile's columns: h, log w, the squared norm
+  __shared__ double s_ni[kCgRows], s_mx[kCgRows];                    // the rows' squared norms and new running maxima
+  __shared__ float s_zi[(kCgRows + kCgCols) * kCgZld];               // the staged rows i, then j (cg_stage)
 
   const SkProb pb = sk_pick(probs, blockIdx.z);
-  const int i0 = blockIdx.x * kSkRows;
+  const int i0 = blockIdx.x * kCgRows;
   if (i0 >= pb.row_cnt) return;      // (uniform in the workgroup, before any barrier: the grid is sized by the larger problem)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
   const int slab = blockIdx.y;
@@ -212,54 +145,32 @@ __global__ __launch_bounds__(kSkBlock) void sk_tiles(const float* __restrict__ x
   const int rb = wave >> 2, cb = wave & 3;      // the wave's block of the tile
 
   double M = -INFINITY, S = 0.0;      // (threads 0 .. 31: the row's running maximum and sum over the slab)
-  if (tid < kSkRows) s_ni[tid] = i0 + tid < pb.row_cnt ? nrm[pb.row_off + i0 + tid] : 0.0;
+  if (tid < kCgRows) s_ni[tid] = i0 + tid < pb.row_cnt ? nrm[pb.row_off + i0 + tid] : 0.0;
 
-  // a chunk of kSkDChunk dimensions of the 32 rows i and the 64 rows j, kSkStage floats a thread: loaded into registers a chunk
-  // ahead, so that the loads' latency runs under the sums (a row past the end and a dimension past D as 0)
-  float pre[kSkStage];
+  float pre[kCgStage];
   auto fetch = [&](const int j0, const int dc) {
-#pragma unroll
-    for (int u = 0; u < kSkStage; ++u) {
-      const int s = tid + u * kSkBlock, r = s / kSkDChunk, d = dc + (s % kSkDChunk);
-      const int local = r < kSkRows ? i0 + r : j0 + (r - kSkRows);
-      const bool ok = (r < kSkRows ? local < pb.row_cnt : local < pb.col_cnt) && d < D;
-      pre[u] = ok ? sk_at(x, n, y, D, (r < kSkRows ? pb.row_off : pb.col_off) + local, d) : 0.f;
-    }
+    cg_fetch(pre, CgPooled{x, n, y}, D, pb.row_off, pb.row_cnt, pb.col_off, pb.col_cnt, i0, j0, dc);
   };
-  if (jt_lo < jt_hi) fetch(jt_lo * kSkCols, 0);
+  if (jt_lo < jt_hi) fetch(jt_lo * kCgCols, 0);
 
   for (int jt = jt_lo; jt < jt_hi; ++jt) {
-    const int j0 = jt * kSkCols;
+    const int j0 = jt * kCgCols;
     __syncthreads();      // the previous tile's sums have read s_k, its s tile s_h, s_lw and s_nj
-    if (tid < kSkCols) {
+    if (tid < kCgCols) {
       const int j = j0 + tid;
       const bool ok = j < pb.col_cnt;
       s_h[tid] = ok ? pb.h[j] : 0.0;
       s_lw[tid] = ok ? pb.logw[j] : -INFINITY;
       s_nj[tid] = ok ? nrm[pb.col_off + j] : 0.0;
     }
-    sk_d4 dot = {0.0, 0.0, 0.0, 0.0};
-    for (int dc = 0; dc < D; dc += kSkDChunk) {
-      __syncthreads();      // the previous chunk's sums have read s_zi and s_zj
-#pragma unroll
-      for (int u = 0; u < kSkStage; ++u) {
-        const int s = tid + u * kSkBlock;
-        s_zi[(s / kSkDChunk) * kSkZld + (s % kSkDChunk)] = pre[u];      // (s_zj follows s_zi)
-      }
-      if (tid < kSkDChunk) s_mean[tid] = dc + tid < D ? mean[dc + tid] : 0.0;
-      __syncthreads();
-      // the next chunk -- of this tile or the first of the next -- is on its way while this one is summed
-      if (dc + kSkDChunk < D)
-        fetch(j0, dc + kSkDChunk);
+    cg_d4 dot = {0.0, 0.0, 0.0, 0.0};
+    for (int dc = 0; dc < D; dc += kCgDChunk) {
+      cg_stage<true>(pre, dc, D, s_zi, s_mean, mean);
+      if (dc + kCgDChunk < D)
+        fetch(j0, dc + kCgDChunk);
       else if (jt + 1 < jt_hi)
-        fetch(j0 + kSkCols, 0);
-      const float* __restrict__ ai = s_zi + (16 * rb + l15) * kSkZld + l4;
-      const float* __restrict__ bj = s_zj + (16 * cb + l15) * kSkZld + l4;
-#pragma unroll
-      for (int kk = 0; kk < kSkDChunk / 4; ++kk) {      // (a dimension past D: 0 - 0; a row past the end: -mean, never used)
-        const double mu = s_mean[4 * kk + l4];
-        dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)ai[4 * kk] - mu, (double)bj[4 * kk] - mu, dot, 0, 0, 0);
-      }
+        fetch(j0 + kCgCols, 0);
+      cg_mfma(s_zi, s_mean, rb, cb, l15, l4, dot);
     }
     // the thread's four entries of the tile: rows 16 rb + l4 + 4 c, column 16 cb + l15
     const int lj = 16 * cb + l15, gj = j0 + lj;
@@ -273,31 +184,31 @@ __global__ __launch_bounds__(kSkBlock) void sk_tiles(const float* __restrict__ x
         s = s_lw[lj] + (s_h[lj] - cost) * inv_eps;
       }
       sv[c] = s;
-      s_k[li * kSkKld + lj] = s;
+      s_k[li * kCgKld + lj] = s;
     }
     __syncthreads();
     double Mn = M;
-    if (tid < kSkRows) {
-      const double* __restrict__ kr = s_k + tid * kSkKld;
-      for (int j = 0; j < kSkCols; ++j) Mn = fmax(Mn, kr[j]);
+    if (tid < kCgRows) {
+      const double* __restrict__ kr = s_k + tid * kCgKld;
+      for (int j = 0; j < kCgCols; ++j) Mn = fmax(Mn, kr[j]);
       s_mx[tid] = Mn;
     }
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int li = 16 * rb + l4 + 4 * c;
-      s_k[li * kSkKld + lj] = sv[c] == -INFINITY ? 0.0 : exp(sv[c] - s_mx[li]);
+      s_k[li * kCgKld + lj] = sv[c] == -INFINITY ? 0.0 : exp(sv[c] - s_mx[li]);
     }
     __syncthreads();
-    if (tid < kSkRows) {
-      const double* __restrict__ kr = s_k + tid * kSkKld;
+    if (tid < kCgRows) {
+      const double* __restrict__ kr = s_k + tid * kCgKld;
       double ts = 0.0;
-      for (int j = 0; j < kSkCols; ++j) ts += kr[j];
+      for (int j = 0; j < kCgCols; ++j) ts += kr[j];
       S = (M == -INFINITY ? 0.0 : S * exp(M - Mn)) + ts;
       M = Mn;
     }
   }
-  if (tid < kSkRows && i0 + tid < pb.row_cnt) {
+  if (tid < kCgRows && i0 + tid < pb.row_cnt) {
     const size_t at = ((size_t)blockIdx.z * slabs + slab) * R + i0 + tid;
     part_max[at] = M;
     part_sum[at] = S;

@@ -11,18 +11,15 @@
 // Nothing N^2 in memory, nothing synchronises with the host.  d2 comes in one of two forms:
 //   energy: from differences, each taken and squared in fp64 and added in ascending d: two equal rows give d2 = 0 and so exactly
 //     k = 0, and sqrt sees no cancellation.  Two launches.
-//   rbf:    the kernel is translation invariant, so from the expanded square n_i + n_j - 2 zc_i . zc_j on the rows centred by the
-//     pooled mean (fp64; n_i = |zc_i|^2), the dot products on v_mfma_f64_16x16x4_f64 -- an eighth of the difference form's time
-//     at D = 784 (profiles/twosample_notes.md).  Three small launches in front: mmd_mean_part and mmd_mean_fold (the mean: row
-//     slices, then the slices in order), mmd_norms (a wave per row).  Five launches.
-// mmd_tiles<NT, kEnergy>: a workgroup of eight waves owns kTsRows = 32 rows i, a slab of column tiles of kTsCols = 64 rows j
-// (blockIdx.y; the slabs follow from N alone, ts_plan) and a chunk of PC = 128 NT splits (blockIdx.z; NT in {1, 2, 4, 8} from P,
+//   rbf:    the kernel is translation invariant, so from the centred Gram tile of csrc/cgram.hpp -- an eighth of the difference
+//     form's time at D = 784 (profiles/twosample_notes.md) --, with its three small launches in front.  Five launches.
+// mmd_tiles<NT, kEnergy>: a workgroup of eight waves owns kCgRows = 32 rows i, a slab of column tiles of kCgCols = 64 rows j
+// (blockIdx.y; the slabs follow from N alone, mmd_plan) and a chunk of PC = 128 NT splits (blockIdx.z; NT in {1, 2, 4, 8} from P,
 // so up to 1024 splits share one pass over the Gram matrix).  Per column tile:
 //   stage E:  the tile's bytes of the chunk's splits, [PC][16] words of four j each (a split past P and a row past N as 0);
-//   gram:     D in chunks of kTsDChunk = 32 staged as fp32 [32][33] and [64][33] (and the mean's chunk), each chunk loaded into
-//             registers while the one before it is summed.  energy: thread (ty, tx) owns the four pairs (ty, tx + 16 c).  rbf:
-//             wave w owns the 16 x 16 block (w >> 2, w & 3) of the tile, eight MFMA steps a chunk, the operands centred on the
-//             way in.  Then the kernel function, 0 on the diagonal and past N, into the K tile [32][65] (fp64);
+//   gram:     cgram.hpp's pass over D in chunks (cg_fetch, cg_stage).  rbf: its MFMA steps (cg_mfma); energy: thread (ty, tx) owns
+//             the four pairs (ty, tx + 16 c).  Then the kernel function, 0 on the diagonal and past N, into the K tile [32][65]
+//             (fp64);
 //   row sums: thread i < 32 adds its row of the tile in ascending j onto its running sum: (K0 1)_i over the slab;
 //   T += K E: wave w owns the chunk's columns [16 NT w, 16 NT (w + 1)).  Per step of four j it reads its two K operands (one per
 //             16-row block) and, per 16 splits, a word of E whose byte becomes 0.0 / 1.0 on the way into the MFMA's B operand
@@ -43,161 +40,99 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "cgram.hpp"
+
 namespace gmvae {
 
-constexpr int kTsBlock = 512;             // mmd_tiles: eight waves
-constexpr int kTsWaves = kTsBlock / 64;
-constexpr int kTsSmallBlock = 256;        // every other kernel here
-constexpr int kTsRows = 32;               // rows i of a workgroup: two 16-row MFMA blocks
-constexpr int kTsCols = 64;               // rows j of a column tile: 16 MFMA steps of four
-constexpr int kTsDChunk = 32;             // dimensions staged at a time
-constexpr int kTsStage = (32 + 64) * kTsDChunk / 512;      // floats of a chunk a thread of mmd_tiles stages
-constexpr int kTsMaxQ = 8;                // bandwidths of the rbf kernel
-constexpr int kTsMaxNT = 8;               // 16-split accumulator tiles per wave and row block: a chunk of 128 NT splits
-constexpr int kTsMaxSlabs = 16;
-constexpr int kTsFillGroups = 256;        // the slabs fill about this many workgroups where the row tiles alone do not
-constexpr int kTsMeanSlices = 64;         // row slices of the mean, 1024 rows each at least
-constexpr int kTsKld = kTsCols + 1;       // the K tile's leading dimension (doubles)
-constexpr int kTsZld = kTsDChunk + 1;     // the staged rows' (floats)
-constexpr int kTsEld = kTsCols / 4 + 1;   // the staged splits' (words of four j)
-constexpr int kTsKindRbf = 0, kTsKindEnergy = 1;
+constexpr int kMmdWaves = kCgBlock / 64;
+constexpr int kMmdSmallBlock = 256;        // mmd_finish
+constexpr int kMmdMaxQ = 8;                // bandwidths of the rbf kernel
+constexpr int kMmdMaxNT = 8;               // 16-split accumulator tiles per wave and row block: a chunk of 128 NT splits
+constexpr int kMmdEld = kCgCols / 4 + 1;   // the staged splits' leading dimension (words of four j)
+constexpr int kMmdKindRbf = 0, kMmdKindEnergy = 1;
 
-typedef double ts_d4 __attribute__((ext_vector_type(4)));
-
-struct TsGamma {
-  double g[kTsMaxQ];
+struct MmdGamma {
+  double g[kMmdMaxQ];
 };
 
 // the launches' shape.  The slabs and slices, and so the order of every sum, follow from N alone; the chunk only from P.
-struct TsPlan {
-  int row_tiles, col_tiles, slabs, tiles_per_slab, nt, p_chunks, mean_slices, rows_per_slice;
+struct MmdPlan {
+  int row_tiles, col_tiles, slabs, tiles_per_slab, nt, p_chunks;
+  CgSlices mean;
   size_t groups;      // row_tiles * slabs: the workgroups that own partials
   size_t lds;
 };
-__host__ __device__ static inline TsPlan ts_plan(int N, int P) {
-  TsPlan p;
-  p.row_tiles = (N + kTsRows - 1) / kTsRows;
-  p.col_tiles = (N + kTsCols - 1) / kTsCols;
-  int s = p.row_tiles >= kTsFillGroups ? 1 : (kTsFillGroups + p.row_tiles - 1) / p.row_tiles;
-  s = s > kTsMaxSlabs ? kTsMaxSlabs : s;
-  s = s > p.col_tiles ? p.col_tiles : s;
+__host__ __device__ static inline MmdPlan mmd_plan(int N, int P) {
+  MmdPlan p;
+  p.row_tiles = (N + kCgRows - 1) / kCgRows;
+  p.col_tiles = (N + kCgCols - 1) / kCgCols;
+  const int s = cg_slabs(p.row_tiles, p.col_tiles);
   p.tiles_per_slab = (p.col_tiles + s - 1) / s;
   p.slabs = (p.col_tiles + p.tiles_per_slab - 1) / p.tiles_per_slab;
   p.nt = P <= 128 ? 1 : P <= 256 ? 2 : P <= 512 ? 4 : 8;
   p.p_chunks = (P + 128 * p.nt - 1) / (128 * p.nt);
   p.groups = (size_t)p.row_tiles * p.slabs;
-  int ms = (N + 1023) / 1024;
-  ms = ms > kTsMeanSlices ? kTsMeanSlices : ms;
-  p.rows_per_slice = (N + ms - 1) / ms;
-  p.mean_slices = (N + p.rows_per_slice - 1) / p.rows_per_slice;
-  p.lds = 8 * ((size_t)kTsRows * kTsKld + kTsRows + kTsDChunk) + 4 * ((size_t)(kTsRows + kTsCols) * kTsZld + (size_t)128 * p.nt * kTsEld);
+  p.mean = cg_mean_slices(N);
+  p.lds = 8 * ((size_t)kCgRows * kCgKld + kCgRows + kCgDChunk) + 4 * ((size_t)(kCgRows + kCgCols) * kCgZld + (size_t)128 * p.nt * kMmdEld);
   return p;
 }
 
 // the workspace, in doubles: a and b [groups][P], c [groups], the slabs' row sums and column 0 of T, [slabs][N] each; for rbf the
 // mean's slices [mean_slices][D], the mean [D] and the centred rows' squared norms [N]
-struct TsLayout {
+struct MmdLayout {
   size_t a, b, c, row_all, row_first, mean_part, mean, nrm, end;
 };
-__host__ __device__ static inline TsLayout ts_layout(const TsPlan& p, int N, int D, int P) {
-  TsLayout o;
+__host__ __device__ static inline MmdLayout mmd_layout(const MmdPlan& p, int N, int D, int P) {
+  MmdLayout o;
   o.a = 0;
   o.b = o.a + p.groups * (size_t)P;
   o.c = o.b + p.groups * (size_t)P;
   o.row_all = o.c + p.groups;
   o.row_first = o.row_all + (size_t)p.slabs * N;
   o.mean_part = o.row_first + (size_t)p.slabs * N;
-  o.mean = o.mean_part + (size_t)p.mean_slices * D;
+  o.mean = o.mean_part + (size_t)p.mean.slices * D;
   o.nrm = o.mean + (size_t)D;
   o.end = o.nrm + (size_t)N;
   return o;
 }
 
-// the pooled mean, first pass: workgroup (x, y) adds the rows of slice y in 64 columns; thread (r, c) the rows r, r + 4, ... in order
-__global__ __launch_bounds__(kTsSmallBlock) void mmd_mean_part(const float* __restrict__ z, const int N, const int D, const int rows_per_slice,
-                                                                double* __restrict__ part) {
-  __shared__ double s[4][64];
-  const int tid = threadIdx.x, r = tid >> 6, cl = tid & 63, c = blockIdx.x * 64 + cl;
-  const int lo = blockIdx.y * rows_per_slice, hi = lo + rows_per_slice < N ? lo + rows_per_slice : N;
-  double a = 0.0;
-  if (c < D)
-    for (int i = lo + r; i < hi; i += 4) a += (double)z[(size_t)i * D + c];
-  s[r][cl] = a;
-  __syncthreads();
-  if (r == 0 && c < D) part[(size_t)blockIdx.y * D + c] = ((s[0][cl] + s[1][cl]) + s[2][cl]) + s[3][cl];
-}
-
-// ... second pass: the slices in order
-__global__ __launch_bounds__(kTsSmallBlock) void mmd_mean_fold(const double* __restrict__ part, const int slices, const int N, const int D,
-                                                                double* __restrict__ mean) {
-  const int d = blockIdx.x * kTsSmallBlock + threadIdx.x;
-  if (d >= D) return;
-  double a = 0.0;
-  for (int s = 0; s < slices; ++s) a += part[(size_t)s * D + d];
-  mean[d] = a / (double)N;
-}
-
-// |z_i - mean|^2: a wave per row, a lane the dimensions lane, lane + 64, ... in order, then the lanes by six exchanges
-__global__ __launch_bounds__(kTsSmallBlock) void mmd_norms(const float* __restrict__ z, const int N, const int D, const double* __restrict__ mean,
-                                                            double* __restrict__ nrm) {
-  const int lane = threadIdx.x & 63, i = blockIdx.x * (kTsSmallBlock / 64) + (threadIdx.x >> 6);
-  if (i >= N) return;      // (uniform in the wave)
-  double a = 0.0;
-  for (int d = lane; d < D; d += 64) {
-    const double e = (double)z[(size_t)i * D + d] - mean[d];
-    a = fma(e, e, a);
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) a += __shfl_xor(a, m);
-  if (lane == 0) nrm[i] = a;
-}
-
 template <int NT, bool kEnergy>
-__global__ __launch_bounds__(kTsBlock) void mmd_tiles(const float* __restrict__ z, const int N, const int D, const uint8_t* __restrict__ E,
-                                                       const int P, const TsGamma gam, const int Q, const int tiles_per_slab,
+__global__ __launch_bounds__(kCgBlock) void mmd_tiles(const float* __restrict__ z, const int N, const int D, const uint8_t* __restrict__ E,
+                                                       const int P, const MmdGamma gam, const int Q, const int tiles_per_slab,
                                                        const int col_tiles, const int words_ok, const double* __restrict__ mean,
                                                        const double* __restrict__ nrm, double* __restrict__ part_a,
                                                        double* __restrict__ part_b, double* __restrict__ part_c,
                                                        double* __restrict__ part_row_all, double* __restrict__ part_row_first) {
-  extern __shared__ __attribute__((aligned(16))) char ts_smem[];
+  extern __shared__ __attribute__((aligned(16))) char mmd_smem[];
   constexpr int PC = 128 * NT;
-  double* const s_k = reinterpret_cast<double*>(ts_smem);             // [kTsRows][kTsKld]
-  double* const s_rs = s_k + kTsRows * kTsKld;                        // [kTsRows]
-  double* const s_mean = s_rs + kTsRows;                              // [kTsDChunk] (rbf)
-  float* const s_zi = reinterpret_cast<float*>(s_mean + kTsDChunk);   // [kTsRows][kTsZld]
-  float* const s_zj = s_zi + kTsRows * kTsZld;                        // [kTsCols][kTsZld]
-  uint32_t* const s_e = reinterpret_cast<uint32_t*>(s_zj + kTsCols * kTsZld);      // [PC][kTsEld]
+  double* const s_k = reinterpret_cast<double*>(mmd_smem);             // [kCgRows][kCgKld]
+  double* const s_rs = s_k + kCgRows * kCgKld;                        // [kCgRows]
+  double* const s_mean = s_rs + kCgRows;                              // [kCgDChunk] (rbf)
+  float* const s_zi = reinterpret_cast<float*>(s_mean + kCgDChunk);   // [kCgRows][kCgZld] (cg_stage: s_zj follows it)
+  float* const s_zj = s_zi + kCgRows * kCgZld;                        // [kCgCols][kCgZld]
+  uint32_t* const s_e = reinterpret_cast<uint32_t*>(s_zj + kCgCols * kCgZld);      // [PC][kMmdEld]
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
-  const int i0 = blockIdx.x * kTsRows, slab = blockIdx.y, p0 = blockIdx.z * PC;
+  const int i0 = blockIdx.x * kCgRows, slab = blockIdx.y, p0 = blockIdx.z * PC;
   const int jt_lo = slab * tiles_per_slab, jt_hi = jt_lo + tiles_per_slab < col_tiles ? jt_lo + tiles_per_slab : col_tiles;
   const int wave_p = p0 + wave * 16 * NT;      // the wave's first split
 
-  ts_d4 acc[2][NT];
+  cg_d4 acc[2][NT];
 #pragma unroll
   for (int ct = 0; ct < NT; ++ct) {
-    acc[0][ct] = ts_d4{0.0, 0.0, 0.0, 0.0};
-    acc[1][ct] = ts_d4{0.0, 0.0, 0.0, 0.0};
+    acc[0][ct] = cg_d4{0.0, 0.0, 0.0, 0.0};
+    acc[1][ct] = cg_d4{0.0, 0.0, 0.0, 0.0};
   }
   double rs = 0.0;      // (threads 0 .. 31: the row's sum over the slab)
 
-  // a chunk of kTsDChunk dimensions of the 32 rows i and the 64 rows j, kTsStage floats a thread: loaded into registers a chunk
-  // ahead, so that the loads' latency runs under the sums (a row past N and a dimension past D as 0)
-  float pre[kTsStage];
-  auto fetch = [&](const int j0, const int dc) {
-#pragma unroll
-    for (int u = 0; u < kTsStage; ++u) {
-      const int s = tid + u * kTsBlock, r = s / kTsDChunk, d = dc + (s % kTsDChunk);
-      const int g = r < kTsRows ? i0 + r : j0 + (r - kTsRows);
-      pre[u] = g < N && d < D ? z[(size_t)g * D + d] : 0.f;
-    }
-  };
-  if (jt_lo < jt_hi) fetch(jt_lo * kTsCols, 0);
+  float pre[kCgStage];
+  auto fetch = [&](const int j0, const int dc) { cg_fetch(pre, CgRows{z}, D, 0, N, 0, N, i0, j0, dc); };
+  if (jt_lo < jt_hi) fetch(jt_lo * kCgCols, 0);
 
   for (int jt = jt_lo; jt < jt_hi; ++jt) {
-    const int j0 = jt * kTsCols;
+    const int j0 = jt * kCgCols;
     __syncthreads();      // the previous tile's products have read s_k and s_e
-    for (int s = tid; s < PC * (kTsCols / 4); s += kTsBlock) {
+    for (int s = tid; s < PC * (kCgCols / 4); s += kCgBlock) {
       const int pl = s >> 4, w = s & 15, gp = p0 + pl, j = j0 + 4 * w;
       uint32_t v = 0;
       if (gp < P && j < N) {
@@ -210,46 +145,32 @@ __global__ __launch_bounds__(kTsBlock) void mmd_tiles(const float* __restrict__ 
             if (j + b < N) v |= (uint32_t)src[b] << (8 * b);
         }
       }
-      s_e[pl * kTsEld + w] = v;
+      s_e[pl * kMmdEld + w] = v;
     }
     // d2 of the thread's four entries of the tile: (e_row, e_col + 16 c) under energy, (e_row + 4 c, e_col) under rbf
     double d2[4] = {0.0, 0.0, 0.0, 0.0};
-    ts_d4 dot = {0.0, 0.0, 0.0, 0.0};
+    cg_d4 dot = {0.0, 0.0, 0.0, 0.0};
     const int rb = wave >> 2, cb = wave & 3;      // rbf: the wave's block of the tile
-    for (int dc = 0; dc < D; dc += kTsDChunk) {
-      __syncthreads();      // the previous chunk's sums have read s_zi and s_zj
-#pragma unroll
-      for (int u = 0; u < kTsStage; ++u) {
-        const int s = tid + u * kTsBlock;
-        s_zi[(s / kTsDChunk) * kTsZld + (s % kTsDChunk)] = pre[u];      // (s_zj follows s_zi)
-      }
-      if (!kEnergy && tid < kTsDChunk) s_mean[tid] = dc + tid < D ? mean[dc + tid] : 0.0;
-      __syncthreads();
-      // the next chunk -- of this tile or the first of the next -- is on its way while this one is summed
-      if (dc + kTsDChunk < D)
-        fetch(j0, dc + kTsDChunk);
+    for (int dc = 0; dc < D; dc += kCgDChunk) {
+      cg_stage<!kEnergy>(pre, dc, D, s_zi, s_mean, mean);
+      if (dc + kCgDChunk < D)
+        fetch(j0, dc + kCgDChunk);
       else if (jt + 1 < jt_hi)
-        fetch(j0 + kTsCols, 0);
+        fetch(j0 + kCgCols, 0);
       if (kEnergy) {
-        const int dn = D - dc < kTsDChunk ? D - dc : kTsDChunk;
-        const float* __restrict__ ai = s_zi + (tid >> 4) * kTsZld;
-        const float* __restrict__ bj = s_zj + (tid & 15) * kTsZld;
+        const int dn = D - dc < kCgDChunk ? D - dc : kCgDChunk;
+        const float* __restrict__ ai = s_zi + (tid >> 4) * kCgZld;
+        const float* __restrict__ bj = s_zj + (tid & 15) * kCgZld;
         for (int d = 0; d < dn; ++d) {
           const double a0 = (double)ai[d];
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            const double e0 = a0 - (double)bj[16 * c * kTsZld + d];
+            const double e0 = a0 - (double)bj[16 * c * kCgZld + d];
             d2[c] = fma(e0, e0, d2[c]);
           }
         }
       } else {
-        const float* __restrict__ ai = s_zi + (16 * rb + l15) * kTsZld + l4;
-        const float* __restrict__ bj = s_zj + (16 * cb + l15) * kTsZld + l4;
-#pragma unroll
-        for (int kk = 0; kk < kTsDChunk / 4; ++kk) {      // (a dimension past D: 0 - 0)
-          const double m = s_mean[4 * kk + l4];
-          dot = __builtin_amdgcn_mfma_f64_16x16x4f64((double)ai[4 * kk] - m, (double)bj[4 * kk] - m, dot, 0, 0, 0);
-        }
+        cg_mfma(s_zi, s_mean, rb, cb, l15, l4, dot);
       }
     }
 #pragma unroll
@@ -267,23 +188,23 @@ __global__ __launch_bounds__(kTsBlock) void mmd_tiles(const float* __restrict__ 
           k = s / (double)Q;
         }
       }
-      s_k[li * kTsKld + lj] = k;
+      s_k[li * kCgKld + lj] = k;
     }
     __syncthreads();
-    if (tid < kTsRows) {
-      const double* __restrict__ kr = s_k + tid * kTsKld;
-      for (int j = 0; j < kTsCols; ++j) rs += kr[j];
+    if (tid < kCgRows) {
+      const double* __restrict__ kr = s_k + tid * kCgKld;
+      for (int j = 0; j < kCgCols; ++j) rs += kr[j];
     }
     if (wave_p < P) {      // (uniform in the wave: the MFMA runs with every lane on; a split past P is staged as 0)
-      const double* __restrict__ k0 = s_k + l15 * kTsKld + l4;
-      const uint32_t* __restrict__ we = s_e + (wave * NT * 16 + l15) * kTsEld;
+      const double* __restrict__ k0 = s_k + l15 * kCgKld + l4;
+      const uint32_t* __restrict__ we = s_e + (wave * NT * 16 + l15) * kMmdEld;
       const int sh = 8 * l4;
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
-        const double a0 = k0[4 * ks], a1 = k0[16 * kTsKld + 4 * ks];
+        const double a0 = k0[4 * ks], a1 = k0[16 * kCgKld + 4 * ks];
 #pragma unroll
         for (int ct = 0; ct < NT; ++ct) {
-          const double b = ((we[ct * 16 * kTsEld + ks] >> sh) & 0xffu) ? 1.0 : 0.0;
+          const double b = ((we[ct * 16 * kMmdEld + ks] >> sh) & 0xffu) ? 1.0 : 0.0;
           acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
           acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
         }
@@ -322,40 +243,40 @@ __global__ __launch_bounds__(kTsBlock) void mmd_tiles(const float* __restrict__ 
       }
     }
   }
-  if (tid < kTsRows) {
+  if (tid < kCgRows) {
     s_rs[tid] = rs;
     if (blockIdx.z == 0 && i0 + tid < N) part_row_all[(size_t)slab * N + i0 + tid] = rs;
   }
   __syncthreads();
-  for (int pl = tid; pl < PC; pl += kTsBlock) {
+  for (int pl = tid; pl < PC; pl += kCgBlock) {
     const int gp = p0 + pl;
     if (gp < P) {
       const uint8_t* __restrict__ e = E + (size_t)gp * N;
       double s = 0.0;
-      for (int r = 0; r < kTsRows; ++r)
+      for (int r = 0; r < kCgRows; ++r)
         if (i0 + r < N && e[i0 + r]) s += s_rs[r];
       part_b[grp * P + gp] = s;
     }
   }
   if (blockIdx.z == 0 && tid == 0) {
     double c = 0.0;
-    for (int r = 0; r < kTsRows; ++r) c += s_rs[r];
+    for (int r = 0; r < kCgRows; ++r) c += s_rs[r];
     part_c[grp] = c;
   }
 }
 
 // workgroup p < P: n_p, the partials in index order, mmd2[p]; the workgroups behind them: row_all and row_first, 256 rows each
-__global__ __launch_bounds__(kTsSmallBlock) void mmd_finish(const uint8_t* __restrict__ E, const int N, const int P, const int groups,
+__global__ __launch_bounds__(kMmdSmallBlock) void mmd_finish(const uint8_t* __restrict__ E, const int N, const int P, const int groups,
                                                              const int slabs, const double* __restrict__ part_a,
                                                              const double* __restrict__ part_b, const double* __restrict__ part_c,
                                                              const double* __restrict__ part_row_all,
                                                              const double* __restrict__ part_row_first, double* __restrict__ mmd2,
                                                              double* __restrict__ row_all, double* __restrict__ row_first) {
-  __shared__ double s_a[kTsSmallBlock], s_b[kTsSmallBlock], s_c[kTsSmallBlock];
-  __shared__ int s_n[kTsSmallBlock];
+  __shared__ double s_a[kMmdSmallBlock], s_b[kMmdSmallBlock], s_c[kMmdSmallBlock];
+  __shared__ int s_n[kMmdSmallBlock];
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= P) {
-    const int i = ((int)blockIdx.x - P) * kTsSmallBlock + tid;
+    const int i = ((int)blockIdx.x - P) * kMmdSmallBlock + tid;
     if (i < N) {
       double ra = 0.0, rf = 0.0;
       for (int s = 0; s < slabs; ++s) {
@@ -370,8 +291,8 @@ __global__ __launch_bounds__(kTsSmallBlock) void mmd_finish(const uint8_t* __res
   const int p = blockIdx.x;
   const uint8_t* __restrict__ e = E + (size_t)p * N;
   int cnt = 0;
-  for (int i = tid; i < N; i += kTsSmallBlock) cnt += e[i] ? 1 : 0;
-  const int run = (groups + kTsSmallBlock - 1) / kTsSmallBlock;
+  for (int i = tid; i < N; i += kMmdSmallBlock) cnt += e[i] ? 1 : 0;
+  const int run = (groups + kMmdSmallBlock - 1) / kMmdSmallBlock;
   const int g_lo = tid * run, g_hi = g_lo + run < groups ? g_lo + run : groups;
   double a = 0.0, b = 0.0, c = 0.0;
   for (int g = g_lo; g < g_hi; ++g) {
@@ -387,7 +308,7 @@ __global__ __launch_bounds__(kTsSmallBlock) void mmd_finish(const uint8_t* __res
   if (tid == 0) {
     double A = 0.0, B = 0.0, Cc = 0.0;
     int n = 0;
-    for (int t = 0; t < kTsSmallBlock; ++t) {
+    for (int t = 0; t < kMmdSmallBlock; ++t) {
       A += s_a[t];
       B += s_b[t];
       Cc += s_c[t];

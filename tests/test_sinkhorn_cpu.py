@@ -164,7 +164,7 @@ def test_names_are_declared_exported_and_bound(L):
         assert re.search(rf"\bint {name}\(", header), name
         assert name in L.EXPORTS and hasattr(L.lib, name)
     assert L.lib.gmvae_abi_version() == L.ABI_VERSION == 7
-    assert "sinkhorn.hip" in open(os.path.join(ROOT, "build_hip.py")).read()
+    assert "twosample.hip" in open(os.path.join(ROOT, "build_hip.py")).read()
 
 
 def wsb(L, n, m, D):
